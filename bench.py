@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X Cool-chic decoder on BASELINE.json's metric: decoded Mpixel/s.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak|throughput] [--legs a,b,..] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak|throughput] [--dump-outputs DIR]
+                    [--full [--legs a,b,..] [--no-cpu-baseline] [--no-live-traffic]]
     (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps of the metric and prints the line (`value`, `ms_per_step`); everything
+else below - `from_bytes`, the verification against the oracle's hashes, per-stage times, rooflines, the CPU baseline, the
+other configurations (`--legs`) and, with N > 1, the sharded legs - runs only with --full.  --dump-outputs DIR writes what
+the last timed step left in rank 0's batch (dump_outputs).
 
 `value` = BASELINE configs[1] (config.workload = "kodak24"): the Kodak-24 set - 24 RGB 8-bit 512x768 frames (18
 landscape, 6 portrait), HOP decoder, one frame per batch slot, all in flight on one MI355X.  A "step" = one full decode
@@ -512,6 +518,27 @@ def verify_gathered(name, gathered, frames_of_rank):
     return verify_frames(name, frames_g, stream_of=lambda i: index_g[i])
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: at most this much in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, batch, n):
+    """What the last timed step left in the batch, for comparing two builds output for output: per frame the three integer
+    planes (`planes.npy`) and the f32 synthesis output (`synthesis.npy`), both float32 of shape (frames, 3, k), at the same k
+    pixel positions of every frame - sorted, drawn without replacement with numpy's default_rng(DUMP_SEED) - with k the whole
+    picture or as many as keep the two files within DUMP_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    planes = [batch.planes(s) for s in range(n)]
+    hw = {p.size for fr in planes for p in fr}
+    assert len(hw) == 1, "dump_outputs: frames with planes of different sizes"
+    hw = hw.pop()
+    k = min(hw, DUMP_BYTES // max(1, 2 * n * 3 * 4))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(hw, k, replace=False)) if k < hw else np.arange(hw)
+    np.save(os.path.join(out_dir, "planes.npy"), np.stack([[p.reshape(-1)[idx] for p in fr] for fr in planes]).astype(np.float32))
+    np.save(os.path.join(out_dir, "synthesis.npy"),
+            np.stack([batch.output(s).reshape(3, -1)[:, idx] for s in range(n)]).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -520,10 +547,13 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak", "throughput"], default="strong",
                     help="strong (default): BASELINE's kodak24, its 24 frames round-robin over the ranks; weak: every rank its own "
                          "kodak24; throughput: every rank its own 256 streams (kodak24 repeated: one per CU)")
-    ap.add_argument("--legs", default="all", help="comma list of clic41,gop1080p33,uhd4k,wide,png,e2e,float,envelope,rate,kodak24_hq,clic41_alt,cliffs (rank 0, N = 1) and sharded (N > 1: "
+    ap.add_argument("--full", action="store_true", help="beside the metric: from_bytes, verification, per-stage times, rooflines, "
+                    "CPU baseline and the legs of --legs (off: the timed steps and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--legs", default="all", help="--full: comma list of clic41,gop1080p33,uhd4k,wide,png,e2e,float,envelope,rate,kodak24_hq,clic41_alt,cliffs (rank 0, N = 1) and sharded (N > 1: "
                     "clic41_sharded + throughput_regime with all ranks), or all / none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (roofline.traffic then "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not run the two rocprofv3 --pmc passes (roofline.traffic then "
                     "comes from the tracked profile)")
     ap.add_argument("--allow-variant", action="store_true", help="time the library CCD_LIB names (a profiling / experiment build of "
                     "_build.build_variant) instead of refusing: the line then says which one")
@@ -531,6 +561,8 @@ def main():
                     help="N > 1: nccl = RCCL over xGMI (one GPU per rank); gloo = host-staged exchange, ranks may share a GPU "
                          "(smoke run of the multi-rank path on a single-GPU box)")
     args = ap.parse_args()
+    if not args.full and (args.legs != "all" or args.no_cpu_baseline or args.no_live_traffic):
+        ap.error("--legs, --no-cpu-baseline and --no-live-traffic select parts of a --full run")
 
     if os.environ.get("CCD_LIB") and not args.allow_variant:
         sys.exit("bench.py: CCD_LIB=%s selects a variant build of the library; the benchmark times cool_chic_amd/libccd.so. "
@@ -604,6 +636,48 @@ def main():
     dt, batch, stream, sh = run["dt"], run["batch"], run["stream"], run["sh"]
     launch_ms = run["launch_ms"]
     gathered = [run["gathered"]]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, n_frames)
+    res = None
+    if rank == 0:
+        res = {
+            "metric": "decoded Mpixel/s", "value": px_per_step * args.steps / dt / 1e6, "unit": "Mpixel/s",
+            "n_gpus": world, "gpus_active": gpus_active, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            **({"library_variant": os.environ["CCD_LIB"]} if os.environ.get("CCD_LIB") else {}),
+            "higher_is_better": True, "scaling": "strong" if args.scaling == "strong" else "weak", "vs_baseline": None,
+            "dtype": "int64+f64 entropy / f32 synthesis", "full": args.full,
+            "data": "synthetic (kodim14.cool real + 23 streams re-encoded from rolled/transposed kodim14 latents)",
+            "config": {"workload": {"strong": "kodak24", "weak": "kodak24 (every rank its own copy)",
+                                    "throughput": f"{THROUGHPUT_STREAMS} streams in flight per GPU (kodak24 repeated: one per CU)"}[args.scaling],
+                       "frames_on_rank0": n_frames, "frame": "512x768 RGB 8-bit, HOP decoder", "symbols_per_step_rank0": n_symbols(batch, n_frames),
+                       "parallelism": (f"frame i -> rank i mod {world} (the set's 24 frames sharded), gather of planes to rank 0" if args.scaling == "strong"
+                                       else f"every rank its own frames x{world}, gather of planes to rank 0")},
+            # BASELINE's sets cannot strong-scale, by the format: a stream is ONE serial range-decoder chain on one CU and the step is the
+            # slowest stream's, so 24 frames on N GPUs take as long as on one (they occupy 9 % of one GPU's CUs); see throughput_regime
+            "expected_scaling": ("flat: one serial chain per stream - the step time is the slowest stream's on any number of GPUs (DESIGN.md 6)"
+                                 if args.scaling == "strong" else "~N x: every rank decodes its own frames"),
+            "parity": "integer stages bit-exact vs reference fixtures; float stages bit-exact vs CPU oracle; integer planes <=1 LSB on "
+                      "<=2e-5 of samples vs the reference decoder's output = within the reference's own thread-count noise floor "
+                      "(tests/test_gpu_parity.py)"}
+
+    def finish():
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            # one line per regime on stderr (N > 1 with --full: strong kodak24, sharded clic41, throughput); the contract's ONE JSON line on stdout
+            for label, leg in (("kodak24 (strong)" if args.scaling == "strong" else args.scaling, res), ("clic41_sharded (strong)", res.get("clic41_sharded")),
+                               ("throughput_regime (weak)", res.get("throughput_regime"))):
+                if leg:
+                    ok = f"  verified {leg['verified'].get('ok')}" if "verified" in leg else ""
+                    print(f"[bench] {label:28s} n_gpus {world}  {leg['value']:9.1f} Mpixel/s  {leg['ms_per_step']:8.2f} ms per step{ok}", file=sys.stderr)
+            print(json.dumps(res))
+        batch.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
     # ---- beside it, same steps / warmup, all ranks: from the .cool BYTES in host memory to integer planes in pinned host memory,
     # two sets in flight (`from_bytes`: what a caller who holds files gets; the gap to `value` is what does not hide behind the decode)
     fb = timed_from_bytes([(streams[i], items[i][3]) for i in ids_of(rank)], world, rank, local_rank, args.backend, red_dev, args.steps, args.warmup)
@@ -638,7 +712,6 @@ def main():
                 "verified": verify_gathered("kodak24", rt["gathered"], lambda r: [(i, items[i][3]) for i in t_ids])}
         rt["batch"].close()
 
-    res = None
     if rank == 0:
         # ---- what was timed, against the CPU oracle (hashes of its integer planes for the same 24 streams): this rank's own
         # frames from its batch, and - N > 1 - every rank's frames as they arrived in the gather of the last timed step
@@ -728,25 +801,7 @@ def main():
                                 "achieved": flop_px * rank_px / ff1 / 1e9, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
                                 "frac": flop_px * rank_px / ff1 / 1e9 / FP32_PEAK_TFLOPS, "ms_per_launch": ff1,
                                 "algorithmic_gbs": ff_bytes / ff1 / 1e6, "frac_of_hbm_peak": ff_bytes / ff1 / 1e6 / HBM_PEAK_GBS})
-        res = {
-            "metric": "decoded Mpixel/s", "value": px_per_step * args.steps / dt / 1e6, "unit": "Mpixel/s",
-            "n_gpus": world, "gpus_active": gpus_active, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            **({"library_variant": os.environ["CCD_LIB"]} if os.environ.get("CCD_LIB") else {}),
-            "higher_is_better": True, "scaling": "strong" if args.scaling == "strong" else "weak", "vs_baseline": None,
-            "dtype": "int64+f64 entropy / f32 synthesis",
-            "data": "synthetic (kodim14.cool real + 23 streams re-encoded from rolled/transposed kodim14 latents)",
-            "config": {"workload": {"strong": "kodak24", "weak": "kodak24 (every rank its own copy)",
-                                    "throughput": f"{THROUGHPUT_STREAMS} streams in flight per GPU (kodak24 repeated: one per CU)"}[args.scaling],
-                       "frames_on_rank0": n_frames, "frame": "512x768 RGB 8-bit, HOP decoder", "symbols_per_step_rank0": nsym,
-                       "parallelism": (f"frame i -> rank i mod {world} (the set's 24 frames sharded), gather of planes to rank 0" if args.scaling == "strong"
-                                       else f"every rank its own frames x{world}, gather of planes to rank 0")},
-            # BASELINE's sets cannot strong-scale, by the format: a stream is ONE serial range-decoder chain on one CU and the step is the
-            # slowest stream's, so 24 frames on N GPUs take as long as on one (they occupy 9 % of one GPU's CUs); see throughput_regime
-            "expected_scaling": ("flat: one serial chain per stream - the step time is the slowest stream's on any number of GPUs (DESIGN.md 6)"
-                                 if args.scaling == "strong" else "~N x: every rank decodes its own frames"),
-            "parity": "integer stages bit-exact vs reference fixtures; float stages bit-exact vs CPU oracle; integer planes <=1 LSB on "
-                      "<=2e-5 of samples vs the reference decoder's output = within the reference's own thread-count noise floor "
-                      "(tests/test_gpu_parity.py)",
+        res.update({
             "verified": verified,
             # the same K steps from the stream BYTES: what a caller who holds .cool files gets (the contract keeps `value` on resident
             # inputs; r04's single-shot figure of this was 5.4 % below it)
@@ -785,7 +840,7 @@ def main():
                               "launched by this run after the timed region; mean over launches, first launch dropped; FETCH_SIZE x 2, "
                               "WRITE_SIZE x 1 (profiles/r03/pmc_calibration.json)") if pmc_from == "measured in this run" else
                              f"tracked profile {pmc_from} (rocprofv3 not usable in this run)") if pmc_from else None,
-        }
+        })
         res.update(sharded)
         # ---- per-orientation entropy time: the 6 portrait streams (more, shorter wavefront steps + a network trained on a
         # landscape picture) set the step time
@@ -1025,18 +1080,7 @@ def main():
             if os.path.exists(ref_path):
                 with open(ref_path) as f:
                     res["reference_pytorch_container"] = json.load(f)
-    if world > 1:
-        dist.barrier()
-    if rank == 0:
-        # one line per regime on stderr (N > 1: strong kodak24, sharded clic41, throughput); the contract's ONE JSON line on stdout
-        for label, leg in (("kodak24 (strong)" if args.scaling == "strong" else args.scaling, res), ("clic41_sharded (strong)", res.get("clic41_sharded")),
-                           ("throughput_regime (weak)", res.get("throughput_regime"))):
-            if leg:
-                print(f"[bench] {label:28s} n_gpus {world}  {leg['value']:9.1f} Mpixel/s  {leg['ms_per_step']:8.2f} ms per step  verified {leg['verified'].get('ok')}", file=sys.stderr)
-        print(json.dumps(res))
-    batch.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

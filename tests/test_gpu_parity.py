@@ -1482,7 +1482,7 @@ def _run_bench_two_ranks(extra):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1516,6 +1516,41 @@ def test_bench_two_ranks_weak_scaling_gloo():
     assert res["n_gpus"] == 2 and res["scaling"] == "weak"
     assert res["verified"]["ok"] is True and res["verified"]["frames_checked"] == 24
     assert res["verified"]["gathered"]["ok"] is True and res["verified"]["gathered"]["frames_checked"] == 48
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path, oracle):
+    """A plain bench.py run (no --full): the timed steps and the line only, `steps` as asked for, and --dump-outputs writes the
+    last timed step's integer planes and f32 synthesis output at bench.DUMP_SEED's pixel positions, float32, within 64 MB in
+    all; frame 0 (kodim14.cool) equals the CPU oracle's planes and synthesis output at those positions, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from conftest import ROOT
+    from cool_chic_amd import synth
+
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["metric"] == "decoded Mpixel/s" and res["unit"] == "Mpixel/s" and res["higher_is_better"] is True
+    assert res["steps"] == 3 and res["full"] is False and res["value"] > 0 and res["ms_per_step"] > 0
+    assert res["dtype"] == "int64+f64 entropy / f32 synthesis"
+    assert not {"from_bytes", "verified", "stage_ms_per_step", "cpu_baseline", "baseline_configs"} & set(res)
+    files = sorted(os.listdir(out))
+    assert files == ["planes.npy", "synthesis.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    planes, syn = np.load(out / "planes.npy"), np.load(out / "synthesis.npy")
+    assert planes.dtype == syn.dtype == np.float32 and planes.shape == syn.shape and planes.shape[:2] == (24, 3)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(512 * 768, planes.shape[2], replace=False))
+    stream = synth.kodak24()[0][0]
+    want = oracle.decode_video(stream)[0]["planes"]
+    assert np.array_equal(planes[0], np.stack([p.reshape(-1)[idx] for p in want]).astype(np.float32))
+    ref = oracle.decode_coolchic(*oracle.split_stream(stream)[1][0][1][0])
+    assert np.array_equal(syn[0].view(np.uint32), np.ascontiguousarray(ref["out"].reshape(3, -1)[:, idx]).view(np.uint32))
 
 
 def test_pooled_blocks_are_recycled_and_results_stay_exact(gpu, oracle):

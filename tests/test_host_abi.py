@@ -480,6 +480,17 @@ def test_float_envelope_of_fixtures_and_crafted_networks(oracle):
     assert n_nonfinite >= 2 and n_sub >= 1
 
 
+def test_bench_options_of_a_full_run_need_full():
+    """--legs, --no-cpu-baseline and --no-live-traffic choose parts of a --full run: a plain run refuses them before it touches a
+    GPU instead of ignoring them."""
+    import subprocess
+    import sys
+
+    for extra in (["--legs", "none"], ["--no-cpu-baseline"], ["--no-live-traffic"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "--full" in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_bench_refuses_a_variant_library_and_build_cleans_variants(tmp_path):
     """Housekeeping that protects the numbers: bench.py does not time a library CCD_LIB names unless told
     to, and _build.clean_variants removes variant libraries / object trees of earlier profiling runs (they ship to the GPU box

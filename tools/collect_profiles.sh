@@ -14,7 +14,7 @@ for TAG in kodak24 kodak256 clic41 uhd4k kodak24_hq rate; do
   OUT=$REPO/gpurun_out/prof/$TAG
   rm -rf "$OUT"; mkdir -p "$OUT"
   EXTRA=""; [ "$TAG" = kodak256 ] && EXTRA="--scaling throughput"
-  CMD="python $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-live-traffic --legs none $EXTRA"
+  CMD="python $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-traffic --legs none $EXTRA"
   case "$TAG" in clic41|uhd4k|kodak24_hq) CMD="python $REPO/tools/prof_workload.py $TAG 3";; rate) CMD="python $REPO/tools/prof_rate.py";; esac
   # r06: the counters of the metric's workload come from the SAME command as bench.py's live pass (measure_traffic_live):
   # the metric's batch alone, f32 output kept - r05's tracked summary profiled the whole bench command, whose from-bytes steps

@@ -2,8 +2,8 @@
 # The N-GPU run of bench.py exactly as the driver launches it (one rank per GPU over RCCL / xGMI), with everything the first real
 # run could trip over pinned down: loopback rendezvous, dmabuf IPC, a bounded wait, asynchronous RCCL errors surfaced.
 #     tools/run_8gpu.sh [N = 8] [extra bench.py arguments ...]        e.g.  tools/run_8gpu.sh 4 --steps 10 --warmup 2
-# Prints ONE JSON line on stdout (the bench contract); rank 0 also writes one line per regime - strong kodak24, sharded clic41,
-# throughput - to stderr.  bench.py itself sets the device from LOCAL_RANK BEFORE init_process_group and asserts that the
+# Prints ONE JSON line on stdout (the bench contract); rank 0 also writes one line per regime to stderr - strong kodak24 and,
+# with --full, sharded clic41 and throughput.  bench.py itself sets the device from LOCAL_RANK BEFORE init_process_group and asserts that the
 # communicator has N ranks on N distinct GPUs (`gpus_active`).
 set -euo pipefail
 N="${1:-8}"; shift || true

@@ -75,7 +75,7 @@ def main():
             e["write_bytes"] = tot_w
         out[short] = e
     cmd = {"kodak24": "python tools/prof_workload.py kodak24 2 keep_float [= bench.py's live pass, measure_traffic_live: the metric's batch alone]",
-           "kodak256": "python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-live-traffic --legs none --scaling throughput",
+           "kodak256": "python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-live-traffic --legs none --scaling throughput",
            "rate": "python tools/prof_rate.py"}.get(tag, f"python tools/prof_workload.py {tag} 3")
     doc = {
         "command": cmd + " (tools/collect_profiles.sh; one rocprofv3 run per counter)",
