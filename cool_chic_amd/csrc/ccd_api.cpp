@@ -1757,6 +1757,8 @@ int ccd_inter_reconstruct(int device, void* stream, int frame_type, int h, int w
         return CCD_ERR_ARG;
     // 2 / 4 taps = grid_sample bilinear / bicubic, 6.. = sinc (warp.py:49-56); odd or < 2 fails the reference's asserts (warp.py:41-47)
     if (warp_filter_size < 2 || warp_filter_size > 16 || (warp_filter_size & 1)) return CCD_ERR_VALUE;
+    // 4:2:0 needs even sizes (as in ccd_decode_video): planes_to_444_kernel reads chroma at (y >> 1, x >> 1), past an h/2 x w/2 plane
+    if (frame_data_type < 0 || frame_data_type > 3 || (frame_data_type == 1 && ((h | w) & 1))) return CCD_ERR_VALUE;
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     Block tmp;

@@ -99,11 +99,17 @@ hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, 
     return hipGetLastError();
 }
 
+// the integer part of a flow as a tap offset, saturated to +-(size + 16) (oracle/cc_oracle.c tap_offset): taps beyond lie past the
+// border on the same side, so in-range flows keep their taps and far ones (|flow| >= 2^31 included) read the border; NaN -> lower bound
+__device__ __forceinline__ int ic_tap_offset(float f, int size) {
+    return static_cast<int>(fminf(fmaxf(f, -static_cast<float>(size + 16)), static_cast<float>(size + 16)));
+}
+
 __device__ __forceinline__ void ic_warp_pixel(const float* __restrict__ ref, int H, int W, int gx, int gy, int n_taps, float fx,
                                               float fy, int y, int x, float out[3]) {
     const float rxf = floorf(fx), ryf = floorf(fy);
     const float sx = fx - rxf, sy = fy - ryf;
-    const int rx = static_cast<int>(rxf), ry = static_cast<int>(ryf);
+    const int rx = ic_tap_offset(rxf, W), ry = ic_tap_offset(ryf, H);
     float cx[kMaxTaps], cy[kMaxTaps];
     ic_coeffs(sx, n_taps, cx);
     ic_coeffs(sy, n_taps, cy);
@@ -175,7 +181,7 @@ __device__ __forceinline__ void ic_warp_pixel_t(const float* __restrict__ ref, i
     float cx[NT], cy[NT];
     ic_coeffs_t<NT>(sx, cx);
     ic_coeffs_t<NT>(sy, cy);
-    ic_taps_t<NT>(ref, H, W, gx, gy, static_cast<int>(rxf), static_cast<int>(ryf), cx, cy, y, x, out);
+    ic_taps_t<NT>(ref, H, W, gx, gy, ic_tap_offset(rxf, W), ic_tap_offset(ryf, H), cx, cy, y, x, out);
 }
 
 // ---- warp_filter_size 2 / 4: the Warper's native path = F.grid_sample(bilinear | bicubic, border, align_corners=True)
@@ -323,7 +329,7 @@ __device__ __forceinline__ void ic_warp_pixel_coef8(const float* __restrict__ re
                                                     int gy, float fx, float fy, int y, int x, float out[3]) {
     const float4 a = coef[i], b = coef[plane + i], c = coef[2 * plane + i], d = coef[3 * plane + i];
     const float cx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, cy[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-    ic_taps_t<8>(ref, H, W, gx, gy, static_cast<int>(floorf(fx)), static_cast<int>(floorf(fy)), cx, cy, y, x, out);
+    ic_taps_t<8>(ref, H, W, gx, gy, ic_tap_offset(floorf(fx), W), ic_tap_offset(floorf(fy), H), cx, cy, y, x, out);
 }
 __global__ __launch_bounds__(256) void inter_apply8_kernel(InterParams p, const float4* __restrict__ coef) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);

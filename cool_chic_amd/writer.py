@@ -87,6 +87,8 @@ def frame_header_bytes(display_index: int, frame_type: str, frame_data_type: int
         f.index_references[i] = int(r)
     for i, g in enumerate(global_flow):
         f.global_flow[i] = int(g)
+    if not 0 <= warp_filter_size < 16:  # a 4-bit field
+        raise ValueError(f"warp_filter_size {warp_filter_size} does not fit the frame header")
     f.warp_filter_size = warp_filter_size
     buf = (C.c_uint8 * 64)()
     n = check(lib().ccd_write_frame_header(C.byref(f), buf, 64), "ccd_write_frame_header")

@@ -1175,10 +1175,16 @@ static void sinc_coeffs(float s, int n_taps, float* coef) {
 }
 
 /* One warped sample: ref is [3][H][W] float (already 4:4:4), (gx, gy) the integer global translation. */
+/* The integer part of a flow as a tap offset: saturated to +-(size + 16) first.  Every tap of an offset beyond that lies past
+ * the border on the same side (|lo + j| <= 8), so in-range flows keep their taps and far ones read the border, as the
+ * reference's float grid does; (int) of a float beyond the int range is undefined (x86: INT_MIN, gfx950: saturated), and a
+ * NaN lands on the lower bound through fmaxf. */
+static int tap_offset(float f, int size) { return (int)fminf(fmaxf(f, -(float)(size + 16)), (float)(size + 16)); }
+
 static void warp_pixel(const float* ref, int H, int W, int gx, int gy, int n_taps, float fx, float fy, int y, int x, float out[3]) {
     const float rxf = floorf(fx), ryf = floorf(fy);
     const float sx = fx - rxf, sy = fy - ryf;
-    const int rx = (int)rxf, ry = (int)ryf;
+    const int rx = tap_offset(rxf, W), ry = tap_offset(ryf, H);
     float cx[16], cy[16];
     sinc_coeffs(sx, n_taps, cx);
     sinc_coeffs(sy, n_taps, cy);
@@ -1321,19 +1327,16 @@ static uint16_t quantise_sample(float x, float maxv) {
     return (uint16_t)rintf(q * maxv);
 }
 
-/* decode.py:191-206 for a [3][H][W] float frame -> integer planes of `fr` */
-static void finish_frame(const float* img, int H, int W, int bitdepth, int frame_data_type, ora_frame* fr) {
+/* decode.py:191-206 for a [3][H][W] float frame -> integer planes (caller's buffers; chroma H/2 x W/2 for yuv420) */
+static void finish_frame(const float* img, int H, int W, int bitdepth, int frame_data_type, uint16_t* const* planes) {
     const float maxv = (float)((1 << bitdepth) - 1);
-    fr->h = H; fr->w = W;
     if (frame_data_type == 1) { /* yuv420: decode.py:191-206, yuv.py:274-300 */
-        fr->ch = H / 2; fr->cw = W / 2;
-        fr->plane[0] = (uint16_t*)malloc((size_t)H * W * 2);
-        for (size_t i = 0; i < (size_t)H * W; ++i) fr->plane[0][i] = quantise_sample(img[i], maxv);
+        const int ch = H / 2, cw = W / 2;
+        for (size_t i = 0; i < (size_t)H * W; ++i) planes[0][i] = quantise_sample(img[i], maxv);
         for (int p = 1; p < 3; ++p) {
-            fr->plane[p] = (uint16_t*)malloc((size_t)fr->ch * fr->cw * 2 + 2);
             const float* src = img + (size_t)p * H * W;
-            for (int y = 0; y < fr->ch; ++y)
-                for (int x = 0; x < fr->cw; ++x) {
+            for (int y = 0; y < ch; ++y)
+                for (int x = 0; x < cw; ++x) {
                     /* round to the bit-depth grid, THEN average (decode.py:191 before :196);
                      * F.avg_pool2d: sequential f32 sum over the 2x2 window, divided by 4 */
                     float s = 0.0f;
@@ -1343,33 +1346,66 @@ static void finish_frame(const float* img, int H, int W, int bitdepth, int frame
                     float a = s / 4.0f;
                     a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
                     a = rintf(a * maxv) / maxv;
-                    fr->plane[p][(size_t)y * fr->cw + x] = (uint16_t)rintf(a * maxv);
+                    planes[p][(size_t)y * cw + x] = (uint16_t)rintf(a * maxv);
                 }
         }
     } else {
-        fr->ch = H; fr->cw = W;
         for (int p = 0; p < 3; ++p) {
-            fr->plane[p] = (uint16_t*)malloc((size_t)H * W * 2);
             const float* src = img + (size_t)p * H * W;
-            for (size_t i = 0; i < (size_t)H * W; ++i) fr->plane[p][i] = quantise_sample(src[i], maxv);
+            for (size_t i = 0; i < (size_t)H * W; ++i) planes[p][i] = quantise_sample(src[i], maxv);
         }
     }
 }
 
-/* FrameData of a decoded frame as the [3][H][W] float tensor decode_frame feeds to the warper
+/* Allocates the integer planes of `fr` (h, w, frame_data_type set) */
+static int alloc_planes(ora_frame* fr) {
+    fr->ch = fr->frame_data_type == 1 ? fr->h / 2 : fr->h;
+    fr->cw = fr->frame_data_type == 1 ? fr->w / 2 : fr->w;
+    for (int p = 0; p < 3; ++p) {
+        const size_t n = p ? (size_t)fr->ch * fr->cw : (size_t)fr->h * fr->w;
+        fr->plane[p] = (uint16_t*)malloc(n * 2 + 2);
+        if (!fr->plane[p]) return ORA_ERR_NOMEM;
+    }
+    return ORA_OK;
+}
+
+/* The integer planes of a decoded frame as the [3][H][W] float tensor decode_frame feeds to the warper
  * (decode.py:159-162: yuv420 references go through convert_420_to_444 = nearest x2 of u and v) */
-static float* frame_as_444(const ora_frame* fr) {
-    const int H = fr->h, W = fr->w;
-    const float maxv = (float)((1 << fr->bitdepth) - 1);
+static float* frame_as_444(const uint16_t* const* planes, int H, int W, int bitdepth, int frame_data_type) {
+    const float maxv = (float)((1 << bitdepth) - 1);
+    const int half = frame_data_type == 1, cw = half ? W / 2 : W;
     float* out = (float*)malloc((size_t)3 * H * W * sizeof(float));
+    if (!out) return NULL;
     for (int p = 0; p < 3; ++p)
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
-                const int sy = (p && fr->frame_data_type == 1) ? y >> 1 : y, sx = (p && fr->frame_data_type == 1) ? x >> 1 : x;
-                const int pw = p ? fr->cw : fr->w;
-                out[((size_t)p * H + y) * W + x] = (float)fr->plane[p][(size_t)sy * pw + sx] / maxv;
+                const int sy = (p && half) ? y >> 1 : y, sx = (p && half) ? x >> 1 : x;
+                const int pw = p ? cw : W;
+                out[((size_t)p * H + y) * W + x] = (float)planes[p][(size_t)sy * pw + sx] / maxv;
             }
     return out;
+}
+
+int ora_inter_reconstruct(int frame_type, int h, int w, int bitdepth, int frame_data_type, const float* residue, const float* motion,
+                          const uint16_t* const* ref0_planes, const uint16_t* const* ref1_planes, const int32_t* global_flow,
+                          int warp_filter_size, uint16_t* const* out_planes) {
+    if ((frame_type != 1 && frame_type != 2) || !residue || !motion || !ref0_planes || !global_flow || !out_planes ||
+        (frame_type == 2 && !ref1_planes) || h <= 0 || w <= 0 || bitdepth < 8 || bitdepth > 16)
+        return ORA_ERR_VALUE;
+    if (warp_filter_size < 2 || warp_filter_size > 16 || (warp_filter_size & 1)) return ORA_ERR_VALUE; /* warp.py:41-47 asserts */
+    if (frame_data_type < 0 || frame_data_type > 3 || (frame_data_type == 1 && ((h | w) & 1))) return ORA_ERR_VALUE;
+    const int gf[4] = {global_flow[0], global_flow[1], frame_type == 2 ? global_flow[2] : 0, frame_type == 2 ? global_flow[3] : 0};
+    float* ref0 = frame_as_444(ref0_planes, h, w, bitdepth, frame_data_type);
+    float* ref1 = frame_type == 2 ? frame_as_444(ref1_planes, h, w, bitdepth, frame_data_type) : NULL;
+    float* img = (float*)malloc((size_t)3 * h * w * sizeof(float));
+    int rc = ORA_ERR_NOMEM;
+    if (ref0 && img && (frame_type == 1 || ref1)) {
+        reconstruct_inter(frame_type, h, w, residue, motion, ref0, ref1, gf, warp_filter_size, img);
+        finish_frame(img, h, w, bitdepth, frame_data_type, out_planes);
+        rc = ORA_OK;
+    }
+    free(ref0); free(ref1); free(img);
+    return rc;
 }
 
 int ora_decode_video(const uint8_t* bs, size_t n, ora_video* v) {
@@ -1411,26 +1447,25 @@ int ora_decode_video(const uint8_t* bs, size_t n, ora_video* v) {
         if (rc == ORA_OK) {
             const int H = r[0].out_h, W = r[0].out_w;
             if (fh.frame_type == 0) {
+                fr->h = H; fr->w = W;
                 if (r[0].out_c < 3) rc = ORA_ERR_VALUE;
-                else finish_frame(r[0].out, H, W, fh.bitdepth, fh.frame_data_type, fr);
+                else if ((rc = alloc_planes(fr)) == ORA_OK) finish_frame(r[0].out, H, W, fh.bitdepth, fh.frame_data_type, fr->plane);
             } else {
                 const int need_res = fh.frame_type == 1 ? 4 : 5, need_mot = fh.frame_type == 1 ? 2 : 4;
-                if (r[0].out_c < need_res || r[1].out_c < need_mot || r[1].out_h != H || r[1].out_w != W ||
-                    fh.warp_filter_size < 2 || fh.warp_filter_size > 16 || (fh.warp_filter_size & 1)) rc = ORA_ERR_VALUE; /* warp.py:41-47 asserts */
-                float* refs[2] = {NULL, NULL};
+                if (r[0].out_c < need_res || r[1].out_c < need_mot || r[1].out_h != H || r[1].out_w != W) rc = ORA_ERR_VALUE;
+                const uint16_t* const* refs[2] = {NULL, NULL};
                 for (int k = 0; k < fh.n_refs && rc == ORA_OK; ++k) {
+                    /* the references' planes are read with this frame's sample layout (as ccd_decode_video) */
                     const int ri = fh.index_references[k];
-                    if (ri >= n_frames || !v->frames[ri].plane[0] || v->frames[ri].h != H || v->frames[ri].w != W) rc = ORA_ERR_VALUE;
-                    else refs[k] = frame_as_444(&v->frames[ri]);
+                    if (ri >= n_frames || !v->frames[ri].plane[0] || v->frames[ri].h != H || v->frames[ri].w != W ||
+                        v->frames[ri].bitdepth != fh.bitdepth || v->frames[ri].frame_data_type != fh.frame_data_type) rc = ORA_ERR_VALUE;
+                    else refs[k] = (const uint16_t* const*)v->frames[ri].plane;
                 }
-                if (rc == ORA_OK) {
-                    float* img = (float*)malloc((size_t)3 * H * W * sizeof(float));
-                    reconstruct_inter(fh.frame_type, H, W, r[0].out, r[1].out, refs[0], refs[1], fh.global_flow,
-                                      fh.warp_filter_size, img);
-                    finish_frame(img, H, W, fh.bitdepth, fh.frame_data_type, fr);
-                    free(img);
-                }
-                free(refs[0]); free(refs[1]);
+                fr->h = H; fr->w = W;
+                if (rc == ORA_OK) rc = alloc_planes(fr);
+                if (rc == ORA_OK)
+                    rc = ora_inter_reconstruct(fh.frame_type, H, W, fh.bitdepth, fh.frame_data_type, r[0].out, r[1].out, refs[0], refs[1], fh.global_flow,
+                                               fh.warp_filter_size, fr->plane);
             }
         }
         ora_cc_result_free(&r[0]); ora_cc_result_free(&r[1]);

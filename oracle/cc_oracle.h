@@ -151,6 +151,12 @@ typedef struct {
 } ora_video;
 
 int ora_decode_video(const uint8_t* bitstream, size_t n, ora_video* v);
+/* One P / B frame (decode.py:156-206) on host buffers, the contract of ccd_inter_reconstruct: residue [4|5][h][w] and
+ * motion [2|4][h][w] f32, reference / output planes u16 (h/2 x w/2 chroma for yuv420; 4:2:0 needs even h and w),
+ * global_flow = (x, y) per reference, warp_filter_size 2 / 4 / 6..16 even.  ORA_ERR_VALUE for an invalid argument. */
+int ora_inter_reconstruct(int frame_type, int h, int w, int bitdepth, int frame_data_type, const float* residue, const float* motion,
+                          const uint16_t* const* ref0_planes, const uint16_t* const* ref1_planes, const int32_t* global_flow,
+                          int warp_filter_size, uint16_t* const* out_planes);
 void ora_video_free(ora_video* v);
 
 /* ---- range encoder (constriction RangeEncoder) for round trips --- */

@@ -111,6 +111,9 @@ def lib():
         L.ora_decode_video.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Video)]
         L.ora_video_free.argtypes = [C.POINTER(Video)]
         L.ora_video_free.restype = None
+        L.ora_inter_reconstruct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int,
+                                            C.POINTER(C.c_void_p)]
         L.ora_rc_encoder_new.restype = C.c_void_p
         L.ora_rc_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.ora_rc_encode.restype = None
@@ -240,6 +243,46 @@ def decode_video(bitstream: bytes) -> list:
         return frames
     finally:
         L.ora_video_free(C.byref(v))
+
+
+FRAME_DATA_TYPES = ["rgb", "yuv420", "yuv444", "flow"]
+
+
+def inter_reconstruct(frame_type, residue: np.ndarray, motion: np.ndarray, ref0, ref1, global_flow, warp_filter_size: int,
+                      bitdepth: int, frame_data_type) -> list:
+    """One P / B frame (ora_inter_reconstruct, the contract of ccd_inter_reconstruct on host buffers).  frame_type "P" / "B"
+    (or 1 / 2), residue [4|5][h][w] and motion [2|4][h][w] float32, ref0 / ref1 = three integer planes each (half-size chroma
+    for yuv420; ref1 None for P), global_flow 2 or 4 ints, frame_data_type a name or 0..3.  Returns the three uint16 planes;
+    OracleError (.code = the oracle's return code) when the arguments are rejected."""
+    L = lib()
+    ft = {"P": 1, "B": 2}.get(frame_type, frame_type)
+    fdt = FRAME_DATA_TYPES.index(frame_data_type) if isinstance(frame_data_type, str) else int(frame_data_type)
+    res = np.ascontiguousarray(residue, dtype=np.float32)
+    mot = np.ascontiguousarray(motion, dtype=np.float32)
+    h, w = res.shape[-2:]
+    ch, cw = (h // 2, w // 2) if fdt == 1 else (h, w)
+    out = [np.zeros((h, w), np.uint16), np.zeros((ch, cw), np.uint16), np.zeros((ch, cw), np.uint16)]
+
+    def ptrs(planes):
+        return (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
+
+    keep = [[np.ascontiguousarray(p, dtype=np.uint16) for p in r] if r is not None else None for r in (ref0, ref1)]
+    # the C side trusts the buffer sizes: check them here
+    n_refs = 2 if ft == 2 else 1
+    if res.ndim != 3 or res.shape[0] < 3 + n_refs or mot.shape != (mot.shape[0], h, w) or mot.shape[0] < 2 * n_refs:
+        raise ValueError(f"residue {res.shape} / motion {mot.shape} do not fit a {frame_type} frame")
+    for r in keep[:n_refs]:
+        if r is None or [p.shape for p in r] != [o.shape for o in out]:
+            raise ValueError("reference planes must have the output's plane shapes")
+    gf = (C.c_int32 * 4)(*(list(global_flow) + [0, 0, 0, 0])[:4])
+    rc = L.ora_inter_reconstruct(int(ft), int(h), int(w), int(bitdepth), fdt, res.ctypes.data, mot.ctypes.data,
+                                 ptrs(keep[0]) if keep[0] is not None else None, ptrs(keep[1]) if keep[1] is not None else None,
+                                 gf, int(warp_filter_size), ptrs(out))
+    if rc < 0:
+        err = OracleError(f"ora_inter_reconstruct failed: {rc}")
+        err.code = rc
+        raise err
+    return out
 
 
 def laplace_bounds(mu_idx: int, scale_idx: int, s: int):
