@@ -87,20 +87,10 @@ __device__ unsigned int g_trace_cfg[2];
 #endif
 constexpr int kPipeThreads = CCD_PIPE_THREADS;  // 8 waves: 1 decoder + 7 producers
 constexpr int kPipeWaves = kPipeThreads / 64;
-#ifdef CCD_IDLE_WAVE  // experiment: wave CCD_IDLE_WAVE builds nothing (the decoder's SIMD neighbour is wave 4)
-constexpr int kProducers = kPipeWaves - 2;
-#else
-constexpr int kProducers = kPipeWaves - 1;
-#endif
-// pixels per decoder batch: 16 (two 8-pixel or four 4-pixel tasks), 8 with 2-pixel tasks (bpx / kBpx below)
-#ifndef CCD_BPX_WIDE
-#define CCD_BPX_WIDE 16
-#endif
-// pixels per decoder batch on grids with 8-pixel tasks: 16; 32 (-DCCD_BPX_WIDE=32: half the hand-overs per symbol, the first 16
-// symbols published half-way) is built and bit-exact but SLOWER (50.3 against 46.2 ms on kodak24, as in r01 without the half-way
-// publication): a batch must be complete to be taken whole, and table rows are handed back to the producers in coarser units
-constexpr int kBpxWide = CCD_BPX_WIDE;
-constexpr int kRows = 128;                  // table rows in LDS = slots x pixels per batch (4 x 32, 8 x 16 or 16 x 8)
+constexpr int kProducers = kPipeWaves - 1;  // (the decoder's SIMD neighbour left idle, six producers: nothing to gain, r04)
+// pixels per decoder batch: 16 (two 8-pixel or four 4-pixel tasks), 8 with 2-pixel tasks (bpx / kBpx below).
+// 32-pixel batches for 8-pixel tasks: bit-exact but measured slower (50.3 against 46.2 ms on kodak24, r01/r03)
+constexpr int kRows = 128;                  // table rows in LDS = slots x pixels per batch (8 x 16 or 16 x 8)
 // Producer task = a part of a batch: 8 pixels x 8 lanes on wide wavefronts, 4 pixels x 16 lanes on short ones
 // (small grids are bound by the producers' latency, not their throughput).
 constexpr int kSlots = 16;                  // most batch slots in flight (power of two)
@@ -229,13 +219,13 @@ struct DecState {
     unsigned long long wait_by_j[6];  // grid 0, steps with n >= 64: decoder wait per batch position
 };
 
-__device__ __forceinline__ void lds_store_release(uint32_t* p, uint32_t v) {
+__device__ __forceinline__ void lds_write_release(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // LDS requests of one wave are performed in order, so a relaxed flag store issued after the payload
 // stores is enough for hand-over inside the workgroup; unlike a release it does not also wait for the
 // wave's outstanding GLOBAL stores (the decoder's writes to the latent grid).
-__device__ __forceinline__ void lds_store_ordered(uint32_t* p, uint32_t v) {
+__device__ __forceinline__ void lds_write_ordered(uint32_t* p, uint32_t v) {
     asm volatile("" ::: "memory");
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     asm volatile("" ::: "memory");
@@ -269,7 +259,7 @@ __device__ __forceinline__ bool wait_ge(const uint32_t* p, uint32_t want_v, uint
         // no s_sleep: the waits of this pipeline are short, and waking up costs more than the polling LDS reads (measured)
         if ((++spins & 1023u) == 0) {
             if (lds_load_acquire(s_abort) != 0) return false;
-            if (spins > kSpinLimit) { lds_store_release(s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return false; }
+            if (spins > kSpinLimit) { lds_write_release(s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return false; }
         }
     }
     return true;
@@ -288,7 +278,7 @@ __device__ __forceinline__ bool wait_ge2(const uint32_t* p, uint32_t want_batche
     while (!progress_reached(p, want_batches, want_pixels)) {
         if ((++spins & 1023u) == 0) {
             if (lds_load_acquire(s_abort) != 0) return false;
-            if (spins > kSpinLimit) { lds_store_release(s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return false; }
+            if (spins > kSpinLimit) { lds_write_release(s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return false; }
         }
     }
     return true;
@@ -366,23 +356,13 @@ struct StreamBody {
     bool on;
     __device__ void init(uint32_t H, uint32_t W, int task_pix) {
         const uint32_t T = kStreamMinStep;
-#if CCD_BPX_WIDE == 16 && !defined(CCD_NO_STREAM_BODY)
-#ifdef CCD_STREAM_T4  // experiment (r06): the body of a grid with 4-pixel tasks streamed too (r04 measured it slower, before the 4-symbol parts chained)
-        on = (task_pix == 8 || task_pix == 4) && W > 10u * (T - 1u) && H >= T;
-#else
-        on = task_pix == 8 && W > 10u * (T - 1u) && H >= T;  // (4-pixel tasks streamed: measured slower, profiles/r04/ab_entropy_stream.txt)
-#endif
-#ifndef CCD_STREAM_EVERY_WIDE_GRID
+        on = task_pix == 8 && W > 10u * (T - 1u) && H >= T;  // (4-pixel tasks streamed: measured slower, r04 and r06)
         {   // where it pays: long steps (the decoder is the limit: its per-step costs go away) or steps whose last task is mostly empty.
             // Elsewhere - 39-pixel steps = 8 + 8 + 8 + 8 + 7 - the tasks of step-aligned batches wait for ONE earlier task each instead
             // of two (profiles/r04/ab_entropy_stream.txt: grid 1 of a landscape Kodak picture 16.8 -> 17.3 M ticks when streamed).
             const uint32_t n_pl = (W - 1u) / 10u + 1u, tail = n_pl & 7u;
             on = on && (n_pl >= 48u || (tail >= 1u && tail <= 4u));
         }
-#endif
-#else
-        on = false;
-#endif
         first = 10u * (T - 1u);
         end = on ? W + 10u * (H - T) : 0u;
         pix_before = 5u * T * (T - 1u);
@@ -430,9 +410,9 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
     int task_pix = uni(C.task_pix);  // (of the grid; the ramps around a streamed body run smaller tasks: per segment below)
     const int grid_w = uni(C.W);
     // pixels per batch: 16 (two 8-pixel or four 4-pixel tasks) or 8 (four 2-pixel tasks).  32-pixel batches were tried twice
-    // (r01; r03 with the first half published half-way, kBpxWide above): fewer hand-overs for the decoder, but slower overall.
-    const int bpx = task_pix == 2 ? 8 : (task_pix == 8 ? kBpxWide : 16);
-    const uint32_t bpx_shift = task_pix == 2 ? 3u : (task_pix == 8 && kBpxWide == 32 ? 5u : 4u);
+    // (r01; r03 with the first half published half-way): fewer hand-overs for the decoder, but slower overall.
+    const uint32_t bpx_shift = task_pix == 2 ? 3u : 4u;
+    const int bpx = task_pix == 2 ? 8 : 16;
     const int slot_mask = kRows / bpx - 1;       // 8 / 16 slots share the 128 table rows
     int task_shift = task_pix == 8 ? 3 : (task_pix == 4 ? 2 : 1);
     // LDS byte addresses (the dynamic LDS starts at 0) and per-lane constants of the step loop below
@@ -546,13 +526,11 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_add_u32 s54, %[i], s70\n\t"
                 "s_add_u32 s54, s54, 1\n\t"
                 "s_min_u32 s54, s54, s66\n\t"
-#if CCD_BPX_WIDE == 16 && !defined(CCD_NO_PART_BLOCKS)
                 "s_sub_u32 s58, s54, %[i]\n\t"     // a full 8-symbol part (8-pixel tasks): its unrolled block (ccd_dec_parts8.inc)
                 "s_cmp_eq_u32 s58, 8\n\t"
                 "s_cbranch_scc1 400f\n\t"
                 "s_cmp_eq_u32 s58, 4\n\t"          // a 4-symbol part (4-pixel tasks): ccd_dec_parts4.inc
                 "s_cbranch_scc1 440f\n\t"
-#endif
                 "s_branch 1f\n\t"
                 "8:\n\t"
                 "ds_read_b64 v[40:41], v50\n\t"
@@ -563,17 +541,8 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 // a full batch of 16 symbols takes the unrolled copy of the loop (80:): no loop control on the chain
                 "19:\n\t"
                 "s_sub_u32 s58, s54, %[i]\n\t"
-#if CCD_BPX_WIDE == 32
-                "s_cmp_eq_u32 s58, s69\n\t"
-                "s_cbranch_scc0 1f\n\t"
-                "s_cmp_eq_u32 s69, 32\n\t"
-                "s_cbranch_scc1 70f\n\t"
-                "s_cmp_eq_u32 s69, 16\n\t"
-                "s_cbranch_scc1 80f\n\t"
-#else
                 "s_cmp_eq_u32 s58, 16\n\t"
                 "s_cbranch_scc1 80f\n\t"
-#endif
                 ".p2align 6\n\t"
                 "1:\n\t"
                 // ---- copy 0: (L, P) of the current symbol in v[40:41], two rows ahead in flight (order: dloop_variants.hip)
@@ -723,7 +692,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_branch 7f\n\t"
                 "27:\n\t"
                 "s_add_u32 %[spins], %[spins], s68\n\t"
-#if CCD_BPX_WIDE == 16 && !defined(CCD_NO_PART_BLOCKS)
                 "s_sub_u32 s58, s54, %[i]\n\t"     // the second 8-symbol part of a 16-pixel batch: its unrolled block
                 "s_cmp_eq_u32 s58, 8\n\t"
                 "s_cbranch_scc1 420f\n\t"
@@ -736,7 +704,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_cbranch_scc1 460f\n\t"
                 "s_cmp_eq_u32 s58, 12\n\t"
                 "s_cbranch_scc1 470f\n\t"
-#endif
                 "s_branch 1b\n\t"
                 // the batch is finished (its last part is published): slot handed back, batch counted
                 "29:\n\t"
@@ -857,13 +824,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 // between s[52:53] (even symbols) and s[48:49] (odd): no copy of the new range; odd trampolines swap them back.
                 ".p2align 6\n\t"
                 "80:\n\t"
-#ifdef CCD_BLOCK_TEST_EVERY_SYMBOL
-#include "ccd_dec_block16.inc"
-#elif defined(CCD_MID_PUBLISH)
-#include "ccd_dec_block16pm.inc"  // + the first 8 symbols published half-way
-#else
 #include "ccd_dec_block16p.inc"   // one renormalisation / sentinel test per two symbols (tools/gen_decoder_block.py: block_paired)
-#endif
                 // ---- end of a full batch: the same hand-over as at 2: with a constant lane mask ...
                 "s_mov_b64 exec, 0xffff\n\t"
                 "v_sub_u32 v52, %[top], %[raw]\n\t"
@@ -877,27 +838,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "v_mov_b32 v56, %[seq]\n\t"
                 "v_mov_b32 v57, s58\n\t"
                 "ds_write_b64 %[rdy], v[56:57] offset:64\n\t"
-#if CCD_BPX_WIDE == 32
-                "s_branch 22f\n\t"
-                // ---- the same for a full 32-symbol batch (8-pixel tasks): half the hand-overs per symbol; its first 16 symbols are
-                // published half-way, so progress reaches the producers as often as with 16-symbol batches
-                ".p2align 6\n\t"
-                "70:\n\t"
-#include "ccd_dec_block32.inc"
-                // ---- end of a full batch: the same hand-over as at 2: with a constant lane mask ...
-                "s_bfm_b64 exec, 32, 0\n\t"
-                "v_sub_u32 v52, %[top], %[raw]\n\t"
-                "v_add_u32 v52, 1, v52\n\t"
-                "ds_write_b8 %[ring], v52\n\t"
-                "global_store_byte %[goff], v52, %[lat]\n\t"
-                "s_mov_b64 exec, -1\n\t"
-                "ds_write_b32 v51, %[zero]\n\t"
-                "s_add_u32 %[seq], %[seq], 1\n\t"
-                "s_add_u32 s58, %[pix0], %[i]\n\t"
-                "v_mov_b32 v56, %[seq]\n\t"
-                "v_mov_b32 v57, s58\n\t"
-                "ds_write_b64 %[rdy], v[56:57] offset:64\n\t"
-#endif
                 // ---- ... then the next batch of this step (if any): its ready counter, top symbols and first two rows are requested
                 // straight into the registers the loop uses (the finished batch's are dead by now); LDS answers a wave in order
                 // and producers store rows before they count a part in, so a counter that reads complete vouches for the rows
@@ -915,7 +855,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "v_lshl_add_u32 v50, s56, 9, %[tabl]\n\t"
                 "ds_read_b64 v[40:41], v50\n\t"
                 "ds_read_b64 v[42:43], v50 offset:512\n\t"
-#if CCD_BPX_WIDE == 16
                 // a FULL batch of this step ahead (the common case on the wide grids): its end index needs no clamp, its ready word
                 // is compared with the constant "all parts", and nothing else is tested (s72 = n on grids with 16-symbol batches,
                 // 0 on the others: never full)
@@ -929,7 +868,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_mov_b32 s57, s73\n\t"
                 "s_branch 23f\n\t"
                 "25:\n\t"
-#endif
                 "s_cmp_lt_u32 %[i], %[n]\n\t"
                 "s_cbranch_scc0 30f\n\t"
                 "s_add_u32 s54, %[i], s69\n\t"
@@ -943,19 +881,9 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "v_readfirstlane_b32 s59, v54\n\t"
                 "s_cmp_eq_u32 s59, s57\n\t"
                 "s_cbranch_scc0 23f\n\t"
-#if CCD_BPX_WIDE == 32
-                "s_cmp_eq_u32 s58, s69\n\t"
-                "s_cbranch_scc0 1b\n\t"
-                "s_cmp_eq_u32 s69, 32\n\t"
-                "s_cbranch_scc1 70b\n\t"
-                "s_cmp_eq_u32 s69, 16\n\t"
-                "s_cbranch_scc1 80b\n\t"
-                "s_branch 1b\n\t"
-#else
                 "s_cmp_eq_u32 s58, 16\n\t"
                 "s_cbranch_scc1 80b\n\t"
                 "s_branch 1b\n\t"
-#endif
                 // not complete when asked: poll it like a batch entered from the top (v51 = its counter, v53 = its top symbols)
                 "23:\n\t"
                 "s_mov_b32 s68, 0\n\t"
@@ -985,24 +913,11 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "10:\n\t"
                 "s_mov_b32 %[st], 0\n\t"
                 "s_branch 4f\n\t"
-#ifdef CCD_BLOCK_TEST_EVERY_SYMBOL
-#include "ccd_dec_tramp16.inc"
-#else
 #include "ccd_dec_tramp16p.inc"
-#endif
-#if CCD_BPX_WIDE == 32
-#include "ccd_dec_tramp32.inc"
-#endif
-#if CCD_BPX_WIDE == 16 && !defined(CCD_NO_PART_BLOCKS)
                 // ---- the two 8-symbol parts of a batch that is decoded part by part (the producers are the limit: every short-step
                 // grid, grid 0 of a portrait picture): the paired block above cut in two, each half ending in the part-end handler 2:
 #include "ccd_dec_parts8.inc"
-#ifdef CCD_NO_CHAIN4
-#include "ccd_dec_parts4_nc.inc"  // r05: every 4-symbol part through the part-end handler and a look at the ready word
-#else
-#include "ccd_dec_parts4.inc"
-#endif
-#endif
+#include "ccd_dec_parts4.inc"     // chained 4-symbol parts (r06; unchained, each through the part-end handler: 0.2 % slower)
                 "15:\n\t"
                 "s_mov_b32 %[st], 3\n\t"
                 "s_branch 4f\n\t"
@@ -1074,7 +989,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 // symbol outside the window (or invalid data): full 128-way search
                 const uint64_t scale = rc_range >> kRcPrecision;
                 if ((rc_dist >> kRcPrecision) >= scale) {
-                    lds_store_release(C.s_abort, static_cast<uint32_t>(-CCD_ERR_INVALID_DATA));
+                    lds_write_release(C.s_abort, static_cast<uint32_t>(-CCD_ERR_INVALID_DATA));
                     ok = false;
                     break;
                 }
@@ -1370,21 +1285,14 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
     }
     const PipeCtx& C = C_fix;
     constexpr int kTaskPix = 64 / kLpp;
-    constexpr int kBpx = kTaskPix == 2 ? 8 : (kTaskPix == 8 ? kBpxWide : 16);   // pixels per decoder batch (see decoder_grid)
+    constexpr int kBpx = kTaskPix == 2 ? 8 : 16;   // pixels per decoder batch (see decoder_grid)
     constexpr int kHalves = kBpx / kTaskPix;
     constexpr int kNSlots = kRows / kBpx;
     constexpr int NOUT = (in_pad + kLpp - 1) / kLpp;  // outputs per lane in a hidden layer
     const int lane = threadIdx.x & 63;
     // Everything that steers the task loop is wave-uniform; stated with readfirstlane, the loop control, the dependency
     // arithmetic and the task filter run on the scalar unit instead of as exec-masked vector code.
-#ifdef CCD_IDLE_WAVE
-    const int wave_id = uni(static_cast<int>(threadIdx.x >> 6));
-    const bool idle_wave = wave_id == CCD_IDLE_WAVE;
-    const int pw = wave_id - 1 - (wave_id > CCD_IDLE_WAVE ? 1 : 0);
-#else
-    constexpr bool idle_wave = false;
     const int pw = uni(static_cast<int>(threadIdx.x >> 6) - 1);
-#endif
     const EntropyParams& P = *C.P;
     const int dim = SH::fixed ? SH::dim : uni(C.dim), n_layers = SH::fixed ? SH::n_layers : uni(C.n_layers), n_sp = SH::fixed ? SH::n_sp : uni(C.n_sp);
     const int W = uni(C.W);
@@ -1478,7 +1386,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
         uint32_t t_first = static_cast<uint32_t>(pw) - phase;
         t_first += static_cast<int32_t>(t_first) < 0 ? kProducers : 0;
         {
-            for (uint32_t task = t_first; task < n_tasks && !idle_wave; task += kProducers) {
+            for (uint32_t task = t_first; task < n_tasks; task += kProducers) {
                 const uint32_t j = task >> kHalvesShift;
                 const int half = static_cast<int>(task & (kHalves - 1));
                 seq = seq0 + j;
@@ -1870,7 +1778,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         do {
                             if ((++spins & 1023u) == 0) {
                                 if (lds_load_acquire(C.s_abort) != 0) return seq;  // (abort / lost hand-over: the kernel stops behind this grid, the count is not used)
-                                if (spins > kSpinLimit) { lds_store_release(C.s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return seq; }
+                                if (spins > kSpinLimit) { lds_write_release(C.s_abort, static_cast<uint32_t>(-CCD_ERR_HIP)); return seq; }
                             }
                             asm volatile("ds_read_b32 %0, %2 offset:4\n\tds_read_i8 %1, %3\n\ts_waitcnt lgkmcnt(0)"
                                          : "=&v"(seen_v), "=&v"(r) : "v"(C.s_consumed.off), "v"(C.s_ring.off + cell) : "memory");

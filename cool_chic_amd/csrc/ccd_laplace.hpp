@@ -11,9 +11,8 @@ namespace ccd {
 
 // exp(x) / 2 for x <= 0 in f64, the way glibc does it: x = (128 k' + j) ln2 / 128 + r with |r| <= ln2 / 256, e^x = 2^k' * T[j] *
 // (1 + r + r^2/2 + .. + r^5/120) with T[j] = 2^(j/128) from a 1 KB table (LDS in the kernel), two-part ln2 / 128.  13 f64
-// operations and a Horner chain of depth 4 instead of 21 and depth 7 for the table-free degree-13 version it replaced
-// (-DCCD_EXP_POLY13 keeps that one for A/B).  Error ~1 ulp; what matters is floor(16777088 * cdf), and THAT is proven on the
-// whole reachable domain: tools/cdf_sweep.py compares all 1.0658e10 boundaries with libm (profiles/r03/cdf_sweep.log).
+// operations and a Horner chain of depth 4 instead of 21 and depth 7 for the table-free degree-13 version it replaced.  Error
+// ~1 ulp; what matters is floor(16777088 * cdf), and THAT is proven on the whole reachable domain: tools/cdf_sweep.py compares all 1.0658e10 boundaries with libm (profiles/r03/cdf_sweep.log).
 #ifndef CCD_EXP_LOG
 #define CCD_EXP_LOG 7
 #endif
@@ -26,35 +25,6 @@ namespace ccd {
 static __device__ const double kExpTab[1 << CCD_EXP_LOG] = {  // (one copy per translation unit: the two kernels do not link device code)
 #include CCD_EXP_INC
 };
-#ifdef CCD_EXP_POLY13
-__device__ __forceinline__ double exp_nonpos(double x, const double*) {
-    // branch-free on purpose: four of these chains are interleaved by the table builder
-    const bool tiny = x < -60.0;  // below 2^-86: contributes nothing to a 24-bit cumulative, and 1 - e/2 == 1
-    x = tiny ? -60.0 : x;
-    const double k = rint(x * 1.44269504088896338700e+00);
-    double r = fma(k, -6.93147180369123816490e-01, x);
-    r = fma(k, -1.90821492927058770002e-10, r);
-    // e^r = E(r^2) + r * O(r^2): two independent Horner chains of 7 instead of one of 14
-    const double r2 = r * r;
-    double pe = 1.1470745597729725e-11;           // 1/14!
-    double po = 1.6059043836821613e-10;           // 1/13!
-    pe = fma(pe, r2, 2.08767569878681e-09);       // 1/12!
-    po = fma(po, r2, 2.505210838544172e-08);      // 1/11!
-    pe = fma(pe, r2, 2.755731922398589e-07);      // 1/10!
-    po = fma(po, r2, 2.7557319223985893e-06);     // 1/9!
-    pe = fma(pe, r2, 2.48015873015873e-05);       // 1/8!
-    po = fma(po, r2, 1.984126984126984e-04);      // 1/7!
-    pe = fma(pe, r2, 1.388888888888889e-03);      // 1/6!
-    po = fma(po, r2, 8.333333333333333e-03);      // 1/5!
-    pe = fma(pe, r2, 4.1666666666666664e-02);     // 1/4!
-    po = fma(po, r2, 1.6666666666666666e-01);     // 1/3!
-    pe = fma(pe, r2, 0.5);                        // 1/2!
-    po = fma(po, r2, 1.0);                        // 1/1!
-    pe = fma(pe, r2, 1.0);                        // 1/0!
-    const double e = ldexp(fma(po, r, pe), static_cast<int>(k) - 1);
-    return tiny ? 0.0 : e;
-}
-#else
 constexpr int kExpLog = CCD_EXP_LOG, kExpN = 1 << kExpLog;
 __device__ __forceinline__ double exp_nonpos(double x, const double* tab /* 2^(j/N): LDS in the kernel */) {
     // No clamp for very negative x: kd stays finite, 2^(ki >> log N) underflows to an exact 0 in v_ldexp_f64 (and 1 - 0 == 1), which
@@ -80,7 +50,6 @@ __device__ __forceinline__ double exp_nonpos(double x, const double* tab /* 2^(j
     p = fma(p, r2, r);                                            // e^r - 1
     return ldexp(fma(t, p, t), (ki >> kExpLog) - 1);              // e^x / 2 (the caller's 0.5 *, folded into the exponent)
 }
-#endif
 
 // Left cumulative of symbol s under (mu, b) with rcp = RN(1 / b) from the host.  The quotient (x - mu) / b is formed as
 // (x - mu) * rcp WITHOUT the Newton step that would make it the correctly rounded quotient: with or without it, with or

@@ -419,16 +419,16 @@ def test_ppm_writer_matches_reference(tmp_path, bitdepth):
     assert out.read_bytes() == want
 
 
-def test_generated_kernel_tables_are_current(tmp_path, monkeypatch):
+def test_generated_kernel_files_are_current_and_none_is_orphaned(tmp_path, monkeypatch):
     """The generated pieces of the entropy kernel (the decoder's unrolled symbol blocks, the table of the device exp) are what
-    their generators write: nobody edited one side only."""
+    their generators write: nobody edited one side only, and no generated decoder block is left in the tree that the generator
+    no longer writes."""
     import importlib.util
     import shutil
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "cool_chic_amd", "csrc")
-    names = ["ccd_dec_block16.inc", "ccd_dec_block16p.inc", "ccd_dec_block16pm.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "ccd_dec_parts4_nc.inc", "ccd_dec_block32.inc", "ccd_dec_tramp16.inc",
-             "ccd_dec_tramp32.inc", "ccd_exp_table.inc"]
+    names = ["ccd_dec_block16p.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "ccd_exp_table.inc"]
     # run the generators on a copy of the tree layout (they write next to the sources)
     fake = tmp_path / "repo"
     (fake / "tools").mkdir(parents=True)
@@ -444,6 +444,31 @@ def test_generated_kernel_tables_are_current(tmp_path, monkeypatch):
             mod.main()
     for n in names:
         assert (fake / "cool_chic_amd" / "csrc" / n).read_text() == open(os.path.join(csrc, n)).read(), n
+    # no orphans: every generated decoder block in the tree is one the generator still writes
+    written = {p.name for p in (fake / "cool_chic_amd" / "csrc").glob("ccd_dec_*.inc")}
+    assert written == {n for n in os.listdir(csrc) if n.startswith("ccd_dec_") and n.endswith(".inc")}
+
+
+def test_build_headers_are_exactly_the_included_files():
+    """_build.HEADERS is what is_stale() and the object rebuild watch: it must name every file the sources include (quoted
+    #include, followed through headers; `#include CCD_EXP_INC` counted as its default, ccd_exp_table.inc) and nothing else."""
+    from cool_chic_amd import _build
+
+    csrc = os.path.join(ROOT, "cool_chic_amd", "csrc")
+    included, todo = set(), [os.path.join(csrc, s) for s in _build.SOURCES]
+    while todo:
+        path = todo.pop()
+        text = open(path).read()
+        names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, flags=re.M)
+        names += ["ccd_exp_table.inc" for _ in re.findall(r"^\s*#\s*include\s+CCD_EXP_INC\b", text, flags=re.M)]
+        for name in names:
+            dep = os.path.normpath(os.path.join(os.path.dirname(path), name))
+            if dep not in included:
+                included.add(dep)
+                todo.append(dep)
+    headers = {os.path.normpath(os.path.join(csrc, h)) for h in _build.HEADERS}
+    assert included - headers == set(), "included but not in _build.HEADERS"
+    assert headers - included == set(), "in _build.HEADERS but included by nothing"
 
 
 def test_float_envelope_of_fixtures_and_crafted_networks(oracle):

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Writes the unrolled symbol blocks of the pipelined entropy kernel's decoder (cool_chic_amd/csrc/ccd_dec_block{16,32}.inc and
-ccd_dec_tramp{16,32}.inc): string-literal lines that ccd_entropy_pipe.hip includes into the asm region of decoder_grid.
+"""Writes the unrolled symbol blocks of the pipelined entropy kernel's decoder (cool_chic_amd/csrc/ccd_dec_block16p.inc,
+ccd_dec_tramp16p.inc, ccd_dec_parts8.inc and ccd_dec_parts4.inc): string-literal lines that ccd_entropy_pipe.hip includes into
+the asm region of decoder_grid.
 
-A block decodes a FULL batch of N symbols: the three copies of the symbol loop in rotation without index arithmetic, bound test
-or branch; rows at immediate offsets from the batch's first row (v50); the range alternates between s[52:53] (even symbols) and
-s[48:49] (odd).  A symbol whose new range has a zero high word leaves through its trampoline, which restores the conventions
-of the 3-copy loop (i, v50, range registers) and continues in that loop's handler.  The 32-symbol block publishes its first
-16 symbols half-way (ring cells + pixel count), so progress is published as often as with 16-symbol batches.
+A block decodes a FULL batch of 16 symbols (or one 8- / 4-symbol part of a batch): the three copies of the symbol loop in
+rotation without index arithmetic, bound test or branch; rows at immediate offsets from the batch's first row (v50); one
+renormalisation / sentinel test per two symbols (block_paired).  A pair whose new range has a zero high word leaves through its
+trampoline, which renormalises in place or restores the conventions of the 3-copy loop (i, v50, range registers) and continues
+in that loop's handler.
     python tools/gen_decoder_block.py"""
 from pathlib import Path
 
@@ -15,56 +16,6 @@ PAIRS = [("v40", "v41", "v[46:47]"), ("v42", "v43", "v[40:41]"), ("v46", "v47", 
 
 def q(s):
     return '                "%s\\n\\t"' % s
-
-
-def block(n, tramp0, mid_publish):
-    out = []
-    for j in range(n):
-        cur_l, cur_p, nxt = PAIRS[j % 3]
-        rcur = "s[52:53]" if j % 2 == 0 else "s[48:49]"
-        rnew = ("s48", "s49") if j % 2 == 0 else ("s52", "s53")
-        wait = "s_waitcnt lgkmcnt(4)" if (mid_publish and j in (n // 2, n // 2 + 1)) else "s_waitcnt lgkmcnt(2)"
-        if mid_publish and j == n // 2:
-            out += ["                // half-way: the first %d symbols go to the ring and the pixel count is published (the producers of the next" % (n // 2),
-                    "                // step's first parts start now, as they would behind a %d-symbol batch)" % (n // 2),
-                    q("s_mov_b64 exec, 0x%x" % ((1 << (n // 2)) - 1)), q("v_sub_u32 v52, %[top], %[raw]"), q("v_add_u32 v52, 1, v52"),
-                    q("ds_write_b8 %[ring], v52"), q("s_mov_b64 exec, -1"), q("s_add_u32 s58, %[pix0], %[i]"), q("s_add_u32 s58, s58, %d" % (n // 2)),
-                    q("v_mov_b32 v52, s58"), q("ds_write_b32 %[rdy], v52 offset:68")]
-        out += [q("s_lshr_b64 s[40:41], %s, 24" % rcur),
-                q("ds_read_b64 %s, v50 offset:%d" % (nxt, 512 * (j + 2))),
-                q(wait),
-                q("v_mad_u64_u32 v[44:45], s[42:43], s40, %s, 0" % cur_l),
-                q("v_mad_u32_u24 v45, %s, s41, v45" % cur_l),
-                q("v_cmpx_ge_u64 vcc, s[50:51], v[44:45]"),
-                q("v_mad_u64_u32 v[48:49], s[42:43], s40, %s, 0" % cur_p),
-                q("v_mad_u32_u24 v49, %s, s41, v49" % cur_p),
-                q("s_ff1_i32_b64 s44, vcc"),
-                q("v_writelane_b32 %%[raw], s44, %d" % j),
-                q("v_readfirstlane_b32 %s, v48" % rnew[0]),
-                q("v_readfirstlane_b32 %s, v49" % rnew[1]),
-                q("v_readfirstlane_b32 s46, v44"),
-                q("v_readfirstlane_b32 s47, v45"),
-                q("s_mov_b64 exec, -1"),
-                q("s_cmp_eq_u32 %s, 0" % rnew[1]),
-                q("s_cbranch_scc1 %df" % (tramp0 + j)),
-                q("s_sub_u32 s50, s50, s46"),
-                q("s_subb_u32 s51, s51, s47")]
-    out.append(q("s_add_u32 %%[i], %%[i], %d" % n))
-    return out
-
-
-def trampolines(n, tramp0):
-    out = []
-    for j in range(n):
-        out.append(q("%d:" % (tramp0 + j)))
-        if j % 2:
-            out += [q("s_mov_b64 s[42:43], s[52:53]"), q("s_mov_b64 s[52:53], s[48:49]"), q("s_mov_b64 s[48:49], s[42:43]")]
-        if j:
-            out.append(q("s_add_u32 %%[i], %%[i], %d" % j))
-        if j // 3:
-            out.append(q("v_add_u32 v50, 0x%x, v50" % (0x600 * (j // 3))))
-        out.append(q("s_branch %db" % (40 + j % 3)))
-    return out
 
 
 # ---- the 16-symbol block with ONE renormalisation / sentinel test per TWO symbols --------------------------------------------
@@ -82,11 +33,8 @@ def pair(p):
     return "s[%s:%s]" % (p[0][1:], p[1][1:])
 
 
-def block_paired(n, tramp0, mid_publish=False, label0=300, lane0=0, part=False, cont=False, chain=None):
-    """mid_publish: behind the test of symbols n/2 - 2 and n/2 - 1 the first n/2 symbols go to the ring and the stream's pixel count
-    is published - the first task of the NEXT step (8 pixels: it waits for its left neighbours, the first 8 or 9 symbols of this
-    step) starts its late part half a batch earlier (measured: no gain on the chain-bound grids, + 2 ticks per symbol on grid 0).
-    part: the block of ONE 8-pixel part of a batch that is decoded part by part (symbols lane0 .. lane0 + 7 of the batch; v50 = the
+def block_paired(n, tramp0, label0=300, lane0=0, part=False, cont=False, chain=None):
+    """part: the block of ONE 8-pixel part of a batch that is decoded part by part (symbols lane0 .. lane0 + 7 of the batch; v50 = the
     part's first row); it ends in the loop's part-end handler (2:) like a part that ran through the 3-copy loop.
     chain (r06, 4-symbol parts): label of the NEXT part's block.  The part asks for the slot's ready word two symbols before its end;
     behind its last symbol it publishes itself and, if the next part's bit is set, goes straight on in that part's block (rows
@@ -104,11 +52,7 @@ def block_paired(n, tramp0, mid_publish=False, label0=300, lane0=0, part=False, 
         if part and (cont or chain) and j == n - 2:
             # first part of a batch: ask for the slot's ready word now - behind the block it says whether the second part is there
             out.append(q("ds_read_b32 v54, v51"))
-        if mid_publish and j == n // 2:
-            out += [q("s_mov_b64 exec, 0x%x" % ((1 << (n // 2)) - 1)), q("v_sub_u32 v52, %[top], %[raw]"), q("v_add_u32 v52, 1, v52"),
-                    q("ds_write_b8 %[ring], v52"), q("s_mov_b64 exec, -1"), q("s_add_u32 s58, %[pix0], %[i]"), q("s_add_u32 s58, s58, %d" % (n // 2)),
-                    q("v_mov_b32 v56, s58"), q("ds_write_b32 %[rdy], v56 offset:68")]
-        wait = "s_waitcnt lgkmcnt(4)" if (mid_publish and j in (n // 2, n // 2 + 1)) else "s_waitcnt lgkmcnt(2)"
+        wait = "s_waitcnt lgkmcnt(2)"
         if part and (cont or chain) and j >= n - 2:
             wait = "s_waitcnt lgkmcnt(3)"
         out += [q("s_lshr_b64 s[40:41], %s, 24" % pair(rcur)),
@@ -256,24 +200,19 @@ def trampolines_paired(n, tramp0, label0=300):
 def main():
     root = Path(__file__).resolve().parents[1] / "cool_chic_amd" / "csrc"
     head = "/* Generated by tools/gen_decoder_block.py - do not edit. */\n"
-    for n, tramp0, mid in ((16, 81, False), (32, 101, True)):
-        (root / ("ccd_dec_block%d.inc" % n)).write_text(head + "\n".join(block(n, tramp0, mid)) + "\n")
-        (root / ("ccd_dec_tramp%d.inc" % n)).write_text(head + "\n".join(trampolines(n, tramp0)) + "\n")
     (root / "ccd_dec_block16p.inc").write_text(head + "\n".join(block_paired(16, 201)) + "\n")
-    (root / "ccd_dec_block16pm.inc").write_text(head + "\n".join(block_paired(16, 201, mid_publish=True)) + "\n")
     # the two 8-symbol parts of a 16-pixel batch that is decoded part by part (each with its trampolines behind it)
     parts = []
     for label0, lane0, tramp0 in ((400, 0, 1001), (420, 8, 1401)):
         parts += [q(".p2align 6")] + block_paired(8, tramp0, label0=label0, lane0=lane0, part=True, cont=lane0 == 0) + trampolines_paired(8, tramp0, label0)
     (root / "ccd_dec_parts8.inc").write_text(head + "\n".join(parts) + "\n")
-    # the four 4-symbol parts of a 16-pixel batch of 4-pixel tasks (grids whose widest step has 9 .. 24 pixels); r06: chained - and
-    # the unchained r05 form beside it for A/B (-DCCD_NO_CHAIN4)
-    for chained, fname in ((True, "ccd_dec_parts4.inc"), (False, "ccd_dec_parts4_nc.inc")):
-        parts = []
-        for k in range(4):
-            label0, tramp0 = 440 + 10 * k, 1801 + 400 * k
-            parts += [q(".p2align 6")] + block_paired(4, tramp0, label0=label0, lane0=4 * k, part=True, chain=(label0 + 10) if (chained and k < 3) else None) + trampolines_paired(4, tramp0, label0)
-        (root / fname).write_text(head + "\n".join(parts) + "\n")
+    # the four 4-symbol parts of a 16-pixel batch of 4-pixel tasks (grids whose widest step has 9 .. 24 pixels), each chained to the
+    # next; the last one ends in the part-end handler
+    parts = []
+    for k in range(4):
+        label0, tramp0 = 440 + 10 * k, 1801 + 400 * k
+        parts += [q(".p2align 6")] + block_paired(4, tramp0, label0=label0, lane0=4 * k, part=True, chain=(label0 + 10) if k < 3 else None) + trampolines_paired(4, tramp0, label0)
+    (root / "ccd_dec_parts4.inc").write_text(head + "\n".join(parts) + "\n")
     (root / "ccd_dec_tramp16p.inc").write_text(head + "\n".join(trampolines_paired(16, 201)) + "\n")
 
 

@@ -1,12 +1,17 @@
-// The decoder's full-batch cycle in isolation: the generated 16-symbol block (cool_chic_amd/csrc/ccd_dec_block16.inc) + the
-// hand-over of ccd_entropy_pipe.hip (symbols -> ring and latent grid, ready word reset, progress published, next batch's ready
-// word / top symbols / rows requested, fast entry), over tables that are always ready.  What does a hand-over cost on top of the
-// 16 symbols, alone and next to seven waves that keep the LDS busy?
+// The decoder's full-batch cycle in isolation: the generated 16-symbol block with one test per two symbols
+// (cool_chic_amd/csrc/ccd_dec_block16p.inc, its trampolines ccd_dec_tramp16p.inc) + the hand-over of ccd_entropy_pipe.hip
+// (symbols -> ring and latent grid, ready word reset, progress published, next batch's ready word / top symbols / rows requested,
+// fast entry), over tables that are always ready.  What does a hand-over cost on top of the 16 symbols, alone and next to seven
+// waves that keep the LDS busy?
 //   V = 0: block + the least a loop needs (two row reads, compare, branch)      V = 1: + publication      V = 2: the production cycle
-//     hipcc --offload-arch=gfx950 -O3 -I../../cool_chic_amd/csrc -o dcycle dcycle.hip && ./dcycle
+//     hipcc --offload-arch=gfx950 -O3 -I../../cool_chic_amd/csrc [-DVARIANT=V, default 2] -o dcycle dcycle.hip && ./dcycle
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+
+#ifndef VARIANT
+#define VARIANT 2
+#endif
 
 template <int V>
 __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int busy, int8_t* lat) {
@@ -52,12 +57,8 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             "ds_read_b64 v[42:43], v50 offset:512\n\t"
             ".p2align 6\n\t"
             "80:\n\t"
-#ifdef PAIRED
 #include "ccd_dec_block16p.inc"
-#else
-#include "ccd_dec_block16.inc"
-#endif
-#if defined(VARIANT) && VARIANT >= 1
+#if VARIANT >= 1
             "s_mov_b64 exec, 0xffff\n\t"
             "v_sub_u32 v52, %[top], %[raw]\n\t"
             "v_add_u32 v52, 1, v52\n\t"
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
 #else
             "s_add_u32 %[seq], %[seq], 1\n\t"
 #endif
-#if defined(VARIANT) && VARIANT >= 2
+#if VARIANT >= 2
             "s_and_b32 s55, %[seq], %[smask]\n\t"
             "v_lshl_add_u32 v51, s55, 2, %[rdy]\n\t"
             "ds_read_b32 v54, v51\n\t"
@@ -110,14 +111,9 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             "40:\n\t" "41:\n\t" "42:\n\t"
             "s_mov_b32 %[st], 1\n\t"
             "s_branch 4f\n\t"
-            "15:\n\t"
-            "s_mov_b32 %[st], 3\n\t"
-            "s_branch 4f\n\t"
-#ifdef PAIRED
 #include "ccd_dec_tramp16p.inc"
-#else
-#include "ccd_dec_tramp16.inc"
-#endif
+            "15:\n\t"                              // (behind the trampolines: they leave for it forward, as in the kernel)
+            "s_mov_b32 %[st], 3\n\t"
             "4:\n\t"
             "s_mov_b64 %[dst], s[50:51]\n\t"
             "s_mov_b64 %[rng], s[52:53]\n\t"
@@ -159,12 +155,7 @@ int main() {
             hipDeviceSynchronize();
         }
         hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-        printf("%svariant %d%s, %s: %.1f ticks per 16-symbol batch = %.1f / symbol   (status %llu, symbols %llu, range %016llx, dist %016llx)\n",
-#ifdef PAIRED
-               "paired test, ",
-#else
-               "",
-#endif
+        printf("variant %d%s, %s: %.1f ticks per 16-symbol batch = %.1f / symbol   (status %llu, symbols %llu, range %016llx, dist %016llx)\n",
                VARIANT,
 #ifdef NO_GLOBAL_STORE
                " (no global store)",
