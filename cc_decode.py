@@ -10,5 +10,8 @@ if __name__ == "__main__":
     parser.add_argument("--output", "-o", type=str, help="Decoded file path.")
     parser.add_argument("--verbosity", type=int, help="Verbosity level.", default=0)
     parser.add_argument("--device", type=int, help="GPU index.", default=0)
+    parser.add_argument("--png-level", type=int, choices=(0, 1), default=0,
+                        help="PNG output: 0 = literal-only deflate (default), 1 = with LZ77 matches (smaller files).")
     args = parser.parse_args()
-    decode_video(args.input, decoded_path=args.output, verbosity=args.verbosity, device=args.device)
+    decode_video(args.input, decoded_path=args.output, verbosity=args.verbosity, device=args.device,
+                 png_level=args.png_level)

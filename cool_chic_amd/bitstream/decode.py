@@ -79,8 +79,9 @@ def decode_frame(bitstream_bytes: bytes, reference_frames: List[FrameData], verb
 
 @torch.no_grad()
 def decode_video(bitstream_path: str, decoded_path: Optional[str] = None, max_decoding_order: int = -1,
-                 verbosity: int = 0, device: int = 0) -> Dict[str, FrameData]:
-    """decode.py:26-91: decode a .cool file; returns {display index as str: FrameData}."""
+                 verbosity: int = 0, device: int = 0, png_level: int = 0) -> Dict[str, FrameData]:
+    """decode.py:26-91: decode a .cool file; returns {display index as str: FrameData}.  png_level: level of the
+    device PNG packer when decoded_path is a .png (0 literal-only, 1 with LZ77 matches)."""
     with open(bitstream_path, "rb") as f:
         bitstream_bytes = f.read()
     vh = VideoHeader()
@@ -128,7 +129,7 @@ def decode_video(bitstream_path: str, decoded_path: Optional[str] = None, max_de
     for display_idx in range(n_frames):
         all_frames[str(display_idx)] = frames.get(display_idx)
         if decoded_path is not None and display_idx in frames:
-            save_frame_data_to_file(frames[display_idx], decoded_path, append=display_idx != 0)
+            save_frame_data_to_file(frames[display_idx], decoded_path, append=display_idx != 0, png_level=png_level)
     return all_frames
 
 

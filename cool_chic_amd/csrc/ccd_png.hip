@@ -20,6 +20,8 @@
 //   png_emit_kernel         one workgroup per deflate block: block start = sum of the previous blocks' bits; scanlines
 //                           staged in LDS, per-thread bit counts, scan, bit packing (whole words stored, the two
 //                           boundary words of a thread merged with atomicOr into the zeroed file)
+//   (level 1: png_lz77_match_kernel + png_lz77_parse_kernel between these two, png_emit_lz77_kernel after the second;
+//    see the level-1 section below)
 //   png_trailer_kernel      container bytes, Adler-32 from the row sums
 //   png_crc_kernel          CRC-32 of the IDAT chunk as XOR of 512-byte chunk CRCs multiplied by x^(8 * bytes behind)
 //   png_crc_final_kernel    stores the CRC, the IEND chunk and the file size
@@ -42,6 +44,7 @@ constexpr int kDataStart = 43;        // signature 8 + IHDR 25 + IDAT length/typ
 constexpr int kMaxDim = 16383;        // 14-bit picture sizes (header.py:244-307); one scanline then fits the LDS stage
 constexpr int kStageBytes = 49152;    // LDS stage of png_emit_kernel: >= max(kBlockTarget, 3 * kMaxDim + 1)
 constexpr uint32_t kPoly = 0xEDB88320u;
+constexpr int kNLL = 286, kNDist = 30;  // level 1: HLIT and HDIST of every LZ77 block
 
 inline int rows_per_block(int w) { const int r = kBlockTarget / (3 * w + 1); return r < 1 ? 1 : r; }
 
@@ -58,6 +61,11 @@ struct PngJob {                // one picture (a table of these lives in device 
     uint32_t* meta;            // [0] deflate bits, [1] deflate bytes, [2] file bytes, [3] crc accumulator, [4] overflow flag
     int32_t h, w, rows, nblk;  // rows = rows per deflate block
     uint32_t zero_words, pad;  // words of `out` cleared before the bit packer merges into them
+    // level 1 only (null at level 0), indexed like `scan` / per block
+    uint16_t* prev;            // [h][3 w + 1] nearest earlier position of the block in the same bucket (kNone: none)
+    uint32_t* lz;              // [h][3 w + 1] best match (length << 16 | distance), then the token starting there
+    uint32_t* lz_codes;        // [nblk][kNLL + kNDist] bit-reversed code | length << 16
+    uint32_t* lz_flag;         // [nblk] 1: the block is written with matches (png_emit_kernel leaves it alone)
 };
 
 struct PngBatch {              // kernel argument
@@ -346,6 +354,7 @@ __global__ __launch_bounds__(kThreadsB) void png_emit_kernel(PngBatch B) {
         if (tid == 0) J.meta[4] = 1;  // never with a buffer of ccd_png_bound() bytes
         return;
     }
+    if (J.lz_flag && J.lz_flag[k]) return;  // level 1: png_emit_lz77_kernel writes this block
     // ---- block header
     if (tid == 0) {
         const uint32_t final_blk = k == J.nblk - 1 ? 1u : 0u;
@@ -387,6 +396,445 @@ __global__ __launch_bounds__(kThreadsB) void png_emit_kernel(PngBatch B) {
             ++wi;
             acc >>= 32;
             nacc -= 32;
+        }
+    }
+    if (nacc > 0 && acc != 0) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
+}
+
+// ---- level 1: LZ77 inside each deflate block --------------------------------------------------------------------
+// The canon (restated on the CPU by tests/png_lz77_ref.py):
+//   match   position i of a block has a key if i + 2 < n; bucket h = ((b0 << 16 | b1 << 8 | b2) * 0x9E3779B1) >> 20.
+//           Candidates: the kCand nearest earlier positions of the same bucket with i - j <= kWindow whose 3 bytes equal
+//           those at i.  Length = common prefix (<= 258, <= end of the block, overlap allowed); best = longest, ties to
+//           the nearest; < 3 is no match, length 3 farther than kFar3 is dropped.
+//   parse   lazy-1: next(i) = i + L(i) if L(i) >= 3 and L(i + 1) <= L(i), else i + 1 (a literal).
+//   code    dynamic Huffman, HLIT = 286, HDIST = 30, level 0's code-length code; both trees limited to 15 bits (the
+//           construction of png_filter_huff_kernel on up to 286 symbols; a single distance symbol gets length 1).
+//   choice  a block whose exact bit count is not below its level-0 count keeps the level-0 coding (png_emit_kernel).
+// Kernels, one workgroup per block, all between png_filter_huff_kernel and png_trailer_kernel:
+//   png_lz77_match_kernel  hash chains (prev[] in HBM scratch) and the best match of every position
+//   png_lz77_parse_kernel  lazy parse by pointer jumping over next(i), histograms, both code constructions, exact bit
+//                          counts, choice of the coding; the token of every position replaces its match
+//   png_emit_lz77_kernel   header, tokens (per-thread bit counts, scan, word packing as png_emit_kernel), end-of-block
+constexpr int kCand = 8;
+constexpr int kWindow = 32768;
+constexpr int kFar3 = 4096;
+constexpr int kMaxMatch = 258;
+constexpr int kBuckets = 4096;
+constexpr uint16_t kNone = 0xFFFF;
+constexpr int kHeaderBitsLz = 3 + 5 + 5 + 4 + 19 * 3 + (kNLL + kNDist) * 4;  // 1338
+
+__device__ __forceinline__ uint32_t bucket3(uint32_t b0, uint32_t b1, uint32_t b2) {
+    return ((b0 << 16 | b1 << 8 | b2) * 0x9E3779B1u) >> 20;
+}
+
+// length 3..258 -> symbol 257..285, extra bits, extra value
+__device__ __forceinline__ void len_code(uint32_t L, uint32_t& sym, uint32_t& ne, uint32_t& ev) {
+    if (L == kMaxMatch) { sym = 285; ne = 0; ev = 0; return; }
+    const uint32_t x = L - 3;
+    if (x < 8) { sym = 257 + x; ne = 0; ev = 0; return; }
+    const uint32_t nb = 31 - __clz(x);
+    sym = 257 + 4 * (nb - 1) + ((x >> (nb - 2)) & 3u);
+    ne = nb - 2;
+    ev = x & ((1u << ne) - 1);
+}
+
+// distance 1..32768 -> symbol 0..29, extra bits, extra value
+__device__ __forceinline__ void dist_code(uint32_t D, uint32_t& sym, uint32_t& ne, uint32_t& ev) {
+    const uint32_t x = D - 1;
+    if (x < 4) { sym = x; ne = 0; ev = 0; return; }
+    const uint32_t nb = 31 - __clz(x);
+    sym = 2 * nb + ((x >> (nb - 1)) & 1u);
+    ne = nb - 1;
+    ev = x & ((1u << ne) - 1);
+}
+
+constexpr int kThreadsM = 256;
+constexpr int kSegs = kThreadsM / 64;   // one segment of the block per wave while the chains are built
+
+__global__ __launch_bounds__(kThreadsM) void png_lz77_match_kernel(PngBatch B) {
+    __shared__ uint8_t s_data[kStageBytes];
+    __shared__ uint16_t s_head[kSegs][kBuckets];  // last position of every bucket in the wave's segment so far
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
+    const PngJob J = B.img[im];
+    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
+    const int N = 3 * J.w + 1;
+    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
+    const int n = (y_hi - y_lo) * N;
+    const size_t off = static_cast<size_t>(y_lo) * N;
+    uint16_t* prev = J.prev + off;
+    uint32_t* mt = J.lz + off;
+    for (int i = tid; i < n; i += kThreadsM) s_data[i] = J.scan[off + i];
+    for (int i = tid; i < kSegs * kBuckets; i += kThreadsM) (&s_head[0][0])[i] = kNone;
+    __syncthreads();
+    // ---- chains inside the wave's segment, 64 positions per step: lanes of one bucket found with 12 ballots, the link
+    // goes to the nearest earlier lane of the bucket, else to the segment's head; the last lane of a bucket moves the head
+    const int seg = (n + 64 * kSegs - 1) / (64 * kSegs) * 64;
+    const int s_lo = min(n, wave * seg), s_hi = min(n, s_lo + seg);
+    for (int base = s_lo; base < s_hi; base += 64) {
+        const int i = base + lane;
+        const bool valid = i < s_hi && i + 2 < n;
+        const uint32_t h = valid ? bucket3(s_data[i], s_data[i + 1], s_data[i + 2]) : 0u;
+        uint64_t same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 12; ++b) {
+            const bool bit = (h >> b) & 1u;
+            const uint64_t bal = __ballot(valid && bit);
+            same &= bit ? bal : ~bal;
+        }
+        if (valid) {
+            const uint64_t below = same & ((1ull << lane) - 1);
+            const uint64_t above = same & ~((2ull << lane) - 1);
+            prev[i] = below ? static_cast<uint16_t>(base + 63 - __clzll(below)) : s_head[wave][h];
+            if (!above) s_head[wave][h] = static_cast<uint16_t>(i);
+        }
+    }
+    __syncthreads();
+    // ---- the first position of a bucket in a segment links to the last one in the segments before (same lanes as above)
+    for (int i = s_lo + lane; i < s_hi; i += 64) {
+        if (i + 2 >= n || prev[i] != kNone) continue;
+        const uint32_t h = bucket3(s_data[i], s_data[i + 1], s_data[i + 2]);
+        uint16_t p = kNone;
+        for (int s = wave - 1; s >= 0 && p == kNone; --s) p = s_head[s][h];
+        prev[i] = p;
+    }
+    __syncthreads();
+    // ---- best match of every position: at most kCand links, lengths compared in LDS
+    for (int i = tid; i < n; i += kThreadsM) {
+        uint32_t res = 0;
+        if (i + 2 < n) {
+            const uint8_t c0 = s_data[i], c1 = s_data[i + 1], c2 = s_data[i + 2];
+            const int lim = min(kMaxMatch, n - i);
+            int best = 0, bd = 0;
+            uint32_t j = prev[i];
+            for (int t = 0; t < kCand && j != kNone && i - static_cast<int>(j) <= kWindow; ++t) {
+                if (s_data[j] == c0 && s_data[j + 1] == c1 && s_data[j + 2] == c2) {
+                    int l = 3;
+                    while (l < lim && s_data[j + l] == s_data[i + l]) ++l;
+                    if (l > best) { best = l; bd = i - static_cast<int>(j); }
+                    if (best == lim) break;  // nothing longer exists; ties stay with the nearer candidate
+                }
+                j = prev[j];
+            }
+            if (best >= 3 && !(best == 3 && bd > kFar3)) res = (static_cast<uint32_t>(best) << 16) | static_cast<uint32_t>(bd);
+        }
+        mt[i] = res;
+    }
+}
+
+// ---- length-limited canonical code over up to 512 symbols (png_filter_huff_kernel's construction, any alphabet)
+struct HuffLds {
+    uint32_t key[512], A[512], par[512], dep[512], cnt[514];
+    uint32_t num[kMaxBits + 1], first[kMaxBits + 1], base[kMaxBits + 1];
+    uint32_t m;
+};
+
+// hist[nsym] -> lens[nsym], codes[nsym] (bit-reversed code | length << 16).  Called by every thread of the workgroup.
+template <int kThreads>
+__device__ void huff_code(const uint32_t* hist, int nsym, uint32_t* lens, uint32_t* codes, HuffLds& S) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 514; i += kThreads) S.cnt[i] = 0;
+    for (int i = tid; i < nsym; i += kThreads) lens[i] = 0;
+    if (tid <= kMaxBits) S.num[tid] = 0;
+    if (tid == 0) S.m = 0;
+    __syncthreads();
+    for (int t = tid; t < 512; t += kThreads) {
+        uint32_t key = 0xFFFFFFFFu;
+        if (t < nsym && hist[t] > 0) { key = (hist[t] << 9) | static_cast<uint32_t>(t); atomicAdd(&S.m, 1u); }
+        S.key[t] = key;
+    }
+    __syncthreads();
+    for (int size = 2; size <= 512; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < 512; t += kThreads) {
+                const int partner = t ^ stride;
+                if (partner > t) {
+                    const uint32_t a = S.key[t], b = S.key[partner];
+                    const bool up = (t & size) == 0;
+                    if ((a > b) == up) { S.key[t] = b; S.key[partner] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int m = static_cast<int>(S.m);
+    if (m >= 2) {
+        if (tid == 0) {  // Moffat-Katajainen phase 1 (one lane), as in png_filter_huff_kernel
+            uint32_t* A = S.A;
+            for (int i = 0; i < m; ++i) A[i] = S.key[i] >> 9;
+            A[0] += A[1];
+            int root = 0, leaf = 2;
+            for (int nxt = 1; nxt < m - 1; ++nxt) {
+                if (leaf >= m || A[root] < A[leaf]) { A[nxt] = A[root]; A[root++] = nxt; }
+                else A[nxt] = A[leaf++];
+                if (leaf >= m || (root < nxt && A[root] < A[leaf])) { A[nxt] += A[root]; A[root++] = nxt; }
+                else A[nxt] += A[leaf++];
+            }
+        }
+        __syncthreads();
+        const int ni = m - 1;
+        uint32_t par = 0, dep = 0;
+        if (tid < ni) {
+            par = tid == ni - 1 ? static_cast<uint32_t>(tid) : S.A[tid];
+            dep = tid == ni - 1 ? 0u : 1u;
+            S.par[tid] = par; S.dep[tid] = dep;
+        }
+        __syncthreads();
+        for (int r = 0; r < 9; ++r) {  // 2^9 > 511 levels
+            uint32_t pd = 0, pp = 0;
+            if (tid < ni) { pd = S.dep[par]; pp = S.par[par]; }
+            __syncthreads();
+            if (tid < ni) { dep += pd; par = pp; S.dep[tid] = dep; S.par[tid] = par; }
+            __syncthreads();
+        }
+        if (tid < ni) atomicAdd(&S.cnt[dep], 1u);
+        __syncthreads();
+        for (int t = tid; t < 512; t += kThreads) {
+            const int d = t + 1;
+            const uint32_t leaves = 2u * S.cnt[d - 1] - S.cnt[d];
+            if (leaves) atomicAdd(&S.num[min(d, kMaxBits)], leaves);
+        }
+        __syncthreads();
+    } else if (tid == 0 && m == 1) {
+        S.num[1] = 1;  // a single symbol: one code of length 1 (RFC 1951 allows an incomplete distance code)
+    }
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int l = 1; l <= kMaxBits; ++l) total += S.num[l] << (kMaxBits - l);
+        while (m >= 2 && total != (1u << kMaxBits)) {
+            S.num[kMaxBits]--;
+            for (int l = kMaxBits - 1; l > 0; --l)
+                if (S.num[l]) { S.num[l]--; S.num[l + 1] += 2; break; }
+            --total;
+        }
+        uint32_t first = 0, code = 0;
+        for (int l = kMaxBits; l > 0; --l) { S.first[l] = first; first += S.num[l]; }
+        for (int bits = 1; bits <= kMaxBits; ++bits) {
+            code = (code + (bits > 1 ? S.num[bits - 1] : 0u)) << 1;
+            S.base[bits] = code;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < m; j += kThreads) {
+        int l = kMaxBits;
+        while (static_cast<uint32_t>(j) >= S.first[l] + S.num[l]) --l;
+        lens[S.key[j] & 511u] = static_cast<uint32_t>(l);
+    }
+    __syncthreads();
+    for (int sy = tid; sy < nsym; sy += kThreads) {
+        const uint32_t l = lens[sy];
+        uint32_t v = 0;
+        if (l) {
+            uint32_t rank = 0;
+            for (int q = 0; q < sy; ++q) rank += lens[q] == l ? 1u : 0u;
+            v = rev_bits(S.base[l] + rank, static_cast<int>(l)) | (l << 16);
+        }
+        codes[sy] = v;
+    }
+    __syncthreads();
+}
+
+constexpr int kThreadsP = 1024;
+constexpr int kPerThreadP = kStageBytes / kThreadsP;  // positions per thread in the pointer jumping (48, in 24 pairs)
+constexpr int kJumpRounds = 16;                       // 2^16 > kStageBytes steps of next()
+
+__global__ __launch_bounds__(kThreadsP) void png_lz77_parse_kernel(PngBatch B) {
+    __shared__ uint32_t s_next2[kStageBytes / 2 + 1];  // next^(2^r)(i) as u16, two per word; n is the end
+    uint16_t* s_next = reinterpret_cast<uint16_t*>(s_next2);
+    __shared__ uint32_t s_mark[kStageBytes / 32];  // token starts found so far
+    __shared__ uint32_t s_take[kStageBytes / 32];  // a token starting here is the match found there
+    __shared__ uint32_t s_hll[kNLL], s_hd[kNDist], s_len[kNLL + kNDist], s_code[kNLL + kNDist];
+    __shared__ HuffLds s_h;
+    __shared__ uint32_t s_bits, s_lit_bits;  // bits of the LZ77 coding; of the level-0 coding (png_filter_huff_kernel)
+    const int tid = threadIdx.x;
+    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
+    const PngJob J = B.img[im];
+    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
+    const int N = 3 * J.w + 1;
+    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
+    const int n = (y_hi - y_lo) * N;
+    const size_t off = static_cast<size_t>(y_lo) * N;
+    uint32_t* mt = J.lz + off;
+    for (int i = tid; i < kStageBytes / 32; i += kThreadsP) { s_mark[i] = i == 0 ? 1u : 0u; s_take[i] = 0; }
+    __syncthreads();
+    for (int i = tid; i < n; i += kThreadsP) {
+        const uint32_t L = mt[i] >> 16, L1 = i + 1 < n ? mt[i + 1] >> 16 : 0u;
+        const bool take = L >= 3 && L1 <= L;
+        s_next[i] = static_cast<uint16_t>(take ? i + static_cast<int>(L) : i + 1);
+        if (take) atomicOr(&s_take[i >> 5], 1u << (i & 31));
+    }
+    if (tid == 0) {
+        s_next[n] = s_next[n + 1] = static_cast<uint16_t>(n);  // n + 1 shares the last pair word (n <= kStageBytes - 2)
+        s_bits = 0;
+        s_lit_bits = J.blk_bits[k];
+    }
+    for (int i = tid; i < kNLL; i += kThreadsP) s_hll[i] = i == 256 ? 1u : 0u;
+    for (int i = tid; i < kNDist; i += kThreadsP) s_hd[i] = 0;
+    __syncthreads();
+    // ---- token starts = the path from 0.  Round r: every marked i marks next^(2^r)(i), then the jump doubles.  After
+    // round r the first 2^(r+1) steps of the path are marked (a mark set early in a round only adds path positions).
+    // Each thread owns the position pairs (2 p, 2 p + 1), p = tid + q * kThreadsP: one LDS word per pair and per round.
+    // Positions >= n keep jumping to n (s_next[n] = n, and the pair word of n - 1 / n is read and written whole).
+    const int pairs = (n + 2) / 2;  // words of s_next that hold positions 0 .. n
+    for (int r = 0; r < kJumpRounds; ++r) {
+        uint32_t nn[kPerThreadP / 2];  // the pair's two new jumps
+#pragma unroll
+        for (int q = 0; q < kPerThreadP / 2; ++q) {
+            const int p = tid + q * kThreadsP;
+            uint32_t v = 0;
+            if (p < pairs) {
+                const uint32_t w = s_next2[p];
+                const uint32_t mk = (s_mark[p >> 4] >> ((2 * p) & 31)) & 3u;
+                const int j0 = static_cast<int>(w & 0xFFFFu), j1 = static_cast<int>(w >> 16);
+                if ((mk & 1u) && j0 < n) atomicOr(&s_mark[j0 >> 5], 1u << (j0 & 31));
+                if ((mk & 2u) && j1 < n) atomicOr(&s_mark[j1 >> 5], 1u << (j1 & 31));
+                v = static_cast<uint32_t>(s_next[j0]) | (static_cast<uint32_t>(s_next[j1]) << 16);
+            }
+            nn[q] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kPerThreadP / 2; ++q) {
+            const int p = tid + q * kThreadsP;
+            if (p < pairs) s_next2[p] = nn[q];
+        }
+        __syncthreads();
+        if (s_next[0] == n) break;  // the path from 0 ends within the 2^(r+1) steps marked so far
+    }
+    // ---- tokens (0: inside a match, 1: a literal, else the match), histograms, extra bits
+    uint32_t extra = 0;
+    for (int i = tid; i < n; i += kThreadsP) {
+        uint32_t tok = 0;
+        if ((s_mark[i >> 5] >> (i & 31)) & 1u) {
+            if ((s_take[i >> 5] >> (i & 31)) & 1u) {
+                tok = mt[i];
+                uint32_t sym, ne, ev;
+                len_code(tok >> 16, sym, ne, ev);
+                atomicAdd(&s_hll[sym], 1u);
+                extra += ne;
+                dist_code(tok & 0xFFFFu, sym, ne, ev);
+                atomicAdd(&s_hd[sym], 1u);
+                extra += ne;
+            } else {
+                atomicAdd(&s_hll[J.scan[off + i]], 1u);
+                tok = 1;
+            }
+        }
+        mt[i] = tok;
+    }
+    atomicAdd(&s_bits, extra);
+    __syncthreads();
+    huff_code<kThreadsP>(s_hll, kNLL, s_len, s_code, s_h);
+    huff_code<kThreadsP>(s_hd, kNDist, s_len + kNLL, s_code + kNLL, s_h);
+    uint32_t part = 0;
+    for (int s = tid; s < kNLL + kNDist; s += kThreadsP) part += (s < kNLL ? s_hll[s] : s_hd[s - kNLL]) * s_len[s];
+    atomicAdd(&s_bits, part);
+    __syncthreads();
+    const uint32_t bits = kHeaderBitsLz + s_bits;
+    // every thread decides from LDS: thread 0 alone reads blk_bits[k] (at the start) and writes it (below)
+    const bool lz = bits < s_lit_bits;  // else the level-0 coding of png_filter_huff_kernel stays
+    if (lz) for (int s = tid; s < kNLL + kNDist; s += kThreadsP) J.lz_codes[static_cast<size_t>(k) * (kNLL + kNDist) + s] = s_code[s];
+    if (tid == 0) {
+        J.lz_flag[k] = lz ? 1u : 0u;
+        if (lz) J.blk_bits[k] = bits;
+    }
+}
+
+__global__ __launch_bounds__(kThreadsB) void png_emit_lz77_kernel(PngBatch B) {
+    __shared__ uint8_t s_data[kStageBytes];
+    __shared__ uint32_t s_code[kNLL + kNDist];
+    __shared__ unsigned long long s_part[kThreadsB / 64];
+    __shared__ uint32_t s_scan[kThreadsB];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
+    const PngJob J = B.img[im];
+    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
+    if (!J.lz_flag[k]) return;  // written by png_emit_kernel
+    const int N = 3 * J.w + 1;
+    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
+    const int nb = (y_hi - y_lo) * N;
+    const size_t off = static_cast<size_t>(y_lo) * N;
+    const uint32_t* tk = J.lz + off;
+    unsigned long long before = 0;
+    for (int i = tid; i < k; i += kThreadsB) before += J.blk_bits[i];
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
+    if (lane == 0) s_part[wave] = before;
+    for (int i = tid; i < kNLL + kNDist; i += kThreadsB) s_code[i] = J.lz_codes[static_cast<size_t>(k) * (kNLL + kNDist) + i];
+    for (int i = tid; i < nb; i += kThreadsB) s_data[i] = J.scan[off + i];
+    __syncthreads();
+    before = 0;
+    for (int q = 0; q < kThreadsB / 64; ++q) before += s_part[q];
+    const uint32_t my_bits = J.blk_bits[k];
+    const uint64_t start = static_cast<uint64_t>(kDataStart) * 8 + before;
+    if (start + my_bits + 256 > J.cap_bits) return;  // png_emit_kernel flags the overflow
+    const uint32_t* dcode = s_code + kNLL;
+    // ---- block header: HLIT = 286, HDIST = 30, 19 code-length codes
+    if (tid == 0) {
+        const uint32_t final_blk = k == J.nblk - 1 ? 1u : 0u;
+        or_bits(J.out, start, final_blk | (2u << 1) | ((kNLL - 257u) << 3) | ((kNDist - 1u) << 8) | (15u << 13), 17);
+        const uint32_t eob = s_code[256];
+        or_bits(J.out, start + my_bits - (eob >> 16), eob & 0xFFFFu, static_cast<int>(eob >> 16));
+    }
+    if (tid < 19) or_bits(J.out, start + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);
+    for (int s = tid; s < kNLL + kNDist; s += kThreadsB) or_bits(J.out, start + 74 + 4 * s, rev_bits(s_code[s] >> 16, 4), 4);
+    // ---- tokens starting in a contiguous chunk of positions per thread
+    const int cb = (nb + kThreadsB - 1) / kThreadsB;
+    const int lo = min(nb, tid * cb), hi = min(nb, lo + cb);
+    uint32_t bits = 0;
+    for (int i = lo; i < hi; ++i) {
+        const uint32_t t = tk[i];
+        if (!t) continue;
+        if (t >> 16) {
+            uint32_t sym, ne, ev;
+            len_code(t >> 16, sym, ne, ev);
+            bits += (s_code[sym] >> 16) + ne;
+            dist_code(t & 0xFFFFu, sym, ne, ev);
+            bits += (dcode[sym] >> 16) + ne;
+        } else {
+            bits += s_code[s_data[i]] >> 16;
+        }
+    }
+    uint32_t incl = bits;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_scan[wave] = incl;
+    __syncthreads();
+    uint32_t offset = incl - bits;
+    for (int q = 0; q < wave; ++q) offset += s_scan[q];
+    const uint64_t pos = start + kHeaderBitsLz + offset;
+    uint32_t wi = static_cast<uint32_t>(pos >> 5);
+    int nacc = static_cast<int>(pos & 31);
+    uint64_t acc = 0;
+    bool first = true;
+    auto put = [&](uint32_t value, int n) {  // n <= 15
+        acc |= static_cast<uint64_t>(value) << nacc;
+        nacc += n;
+        if (nacc >= 32) {
+            if (first) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
+            else J.out[wi] = static_cast<uint32_t>(acc);  // every bit of this word belongs to this thread
+            first = false;
+            ++wi;
+            acc >>= 32;
+            nacc -= 32;
+        }
+    };
+    for (int i = lo; i < hi; ++i) {
+        const uint32_t t = tk[i];
+        if (!t) continue;
+        if (t >> 16) {
+            uint32_t sym, ne, ev;
+            len_code(t >> 16, sym, ne, ev);
+            put(s_code[sym] & 0xFFFFu, static_cast<int>(s_code[sym] >> 16));
+            put(ev, static_cast<int>(ne));
+            dist_code(t & 0xFFFFu, sym, ne, ev);
+            put(dcode[sym] & 0xFFFFu, static_cast<int>(dcode[sym] >> 16));
+            put(ev, static_cast<int>(ne));
+        } else {
+            const uint32_t c = s_code[s_data[i]];
+            put(c & 0xFFFFu, static_cast<int>(c >> 16));
         }
     }
     if (nacc > 0 && acc != 0) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
@@ -566,6 +1014,13 @@ struct ccd_png {
     int flip = 0;
     uint32_t x2n[32];
     int pending = 0;                 // pictures of the pack in flight
+    int level = CCD_PNG_LITERAL;     // read when a pack is enqueued
+    // level 1 workspace
+    size_t prev_cap = 0, lz_cap = 0, lzc_cap = 0, flag_cap = 0;
+    uint16_t* d_prev = nullptr;      // [scan bytes]
+    uint32_t* d_lz = nullptr;        // [scan bytes]
+    uint32_t* d_lz_codes = nullptr;  // [blocks][kNLL + kNDist]
+    uint32_t* d_lz_flag = nullptr;   // [blocks]
 };
 
 extern "C" {
@@ -598,6 +1053,10 @@ void ccd_png_destroy(ccd_png* p) {
     if (p->d_blk_bits) (void)hipFree(p->d_blk_bits);
     if (p->d_row_adler) (void)hipFree(p->d_row_adler);
     if (p->d_meta) (void)hipFree(p->d_meta);
+    if (p->d_prev) (void)hipFree(p->d_prev);
+    if (p->d_lz) (void)hipFree(p->d_lz);
+    if (p->d_lz_codes) (void)hipFree(p->d_lz_codes);
+    if (p->d_lz_flag) (void)hipFree(p->d_lz_flag);
     for (int k = 0; k < 2; ++k) {
         if (p->d_jobs[k]) (void)hipFree(p->d_jobs[k]);
         if (p->h_jobs[k]) (void)hipHostFree(p->h_jobs[k]);
@@ -605,6 +1064,12 @@ void ccd_png_destroy(ccd_png* p) {
     }
     if (p->h_meta) (void)hipHostFree(p->h_meta);
     delete p;
+}
+
+int ccd_png_set_level(ccd_png* p, int level) {
+    if (!p || (level != CCD_PNG_LITERAL && level != CCD_PNG_LZ77)) return CCD_ERR_ARG;
+    p->level = level;
+    return CCD_OK;
 }
 
 int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* stream) {
@@ -621,6 +1086,13 @@ int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* strea
     }
     if (hipSetDevice(p->device) != hipSuccess) return CCD_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool lz = p->level == CCD_PNG_LZ77;
+    if (lz && (scan_need > p->prev_cap || scan_need > p->lz_cap || blocks * (kNLL + kNDist) > p->lzc_cap || blocks > p->flag_cap)) {
+        if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;  // the previous pack may still use the old workspace
+        if (!grow(&p->d_prev, &p->prev_cap, scan_need) || !grow(&p->d_lz, &p->lz_cap, scan_need) ||
+            !grow(&p->d_lz_codes, &p->lzc_cap, blocks * (kNLL + kNDist)) || !grow(&p->d_lz_flag, &p->flag_cap, blocks))
+            return CCD_ERR_NOMEM;
+    }
     if (scan_need > p->scan_cap || blocks * 257 > p->codes_cap || blocks > p->bits_cap || rows * 2 > p->adler_cap ||
         static_cast<size_t>(n) > p->jobs_cap || static_cast<size_t>(n) * 8 > p->meta_cap) {
         if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;  // the previous pack may still use the old workspace
@@ -667,6 +1139,12 @@ int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* strea
         J.blk_bits = p->d_blk_bits + blk_off;
         J.row_adler = p->d_row_adler + row_off * 2;
         J.meta = p->d_meta + static_cast<size_t>(i) * 8;
+        if (lz) {
+            J.prev = p->d_prev + scan_off;
+            J.lz = p->d_lz + scan_off;
+            J.lz_codes = p->d_lz_codes + blk_off * (kNLL + kNDist);
+            J.lz_flag = p->d_lz_flag + blk_off;
+        }
         const size_t bound = ccd_png_bound(it.h, it.w);
         J.zero_words = static_cast<uint32_t>(std::min(it.cap & ~static_cast<size_t>(3), (bound + 3) & ~static_cast<size_t>(3)) / 4);
         scan_off += (static_cast<size_t>(it.h) * (3 * static_cast<size_t>(it.w) + 1) + 15) & ~static_cast<size_t>(15);
@@ -689,7 +1167,12 @@ int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* strea
             B.crc_prefix[i + 1] = B.crc_prefix[i] + static_cast<uint32_t>((chunks + 255) / 256);
         }
         hipLaunchKernelGGL(png_filter_huff_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsA), 0, st, B);
+        if (lz) {
+            hipLaunchKernelGGL(png_lz77_match_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsM), 0, st, B);
+            hipLaunchKernelGGL(png_lz77_parse_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsP), 0, st, B);
+        }
         hipLaunchKernelGGL(png_emit_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsB), 0, st, B);
+        if (lz) hipLaunchKernelGGL(png_emit_lz77_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsB), 0, st, B);
         hipLaunchKernelGGL(png_trailer_kernel, dim3(cnt), dim3(256), 0, st, B);
         hipLaunchKernelGGL(png_crc_kernel, dim3(B.crc_prefix[cnt]), dim3(256), 0, st, B);
         hipLaunchKernelGGL(png_crc_final_kernel, dim3(cnt), dim3(64), 0, st, B);

@@ -35,8 +35,8 @@ class FrameData:
         return [q(self.data)[0, c] for c in range(3)]
 
 
-def save_frame_data_to_file(frame_data: FrameData, file_path: str, append: bool = False) -> None:
-    """io/io.py:53-105."""
+def save_frame_data_to_file(frame_data: FrameData, file_path: str, append: bool = False, png_level: int = 0) -> None:
+    """io/io.py:53-105.  png_level: 0 = literal-only deflate blocks, 1 = with LZ77 matches (smaller, same picture)."""
     ext = os.path.splitext(file_path)[1]
     assert ext in (".yuv", ".png", ".ppm"), f"expected a .yuv, .png or .ppm path, found {file_path}"
     if ext == ".png":
@@ -51,7 +51,7 @@ def save_frame_data_to_file(frame_data: FrameData, file_path: str, append: bool 
             data = data.cuda()
         planes = torch.round(data[0].to(torch.float32) * 255.0).to(torch.uint8)
         with open(file_path, "wb") as f:
-            f.write(device_png_bytes(planes))
+            f.write(device_png_bytes(planes, png_level))
         return
     planes = frame_data.integer_planes()
     if ext == ".ppm":

@@ -322,8 +322,11 @@ void ccd_free(void* p);
  * array to PIL / zlib on the host).  r, g, b: device pointers to [h][w] uint8 planes (ccd_batch_plane); out: device
  * buffer, 4-byte aligned, of at least ccd_png_bound(h, w) bytes.  ccd_png_pack only enqueues work on `stream`;
  * ccd_png_finish synchronises the stream and returns the size of the file in `out` (or a negative code).  One pack
- * (single or batch) may be in flight per handle.  The file holds the filtered scanlines in literal-only dynamic-Huffman deflate blocks:
- * any PNG reader decodes exactly the input planes; the bytes differ from PIL's (PNG bytes are not normative). */
+ * (single or batch) may be in flight per handle.  The file holds the filtered scanlines in dynamic-Huffman deflate
+ * blocks: any PNG reader decodes exactly the input planes; the bytes differ from PIL's (PNG bytes are not normative).
+ * Level CCD_PNG_LITERAL (0, the default of a new handle): literal-only blocks.  Level CCD_PNG_LZ77 (1): every block
+ * also searches matches inside itself (LZ77 on the device) and keeps the level-0 coding where
+ * that is not smaller, so a level-1 file is never larger than the level-0 file and ccd_png_bound still holds. */
 typedef struct ccd_png ccd_png;
 typedef struct {
     const uint8_t *r, *g, *b; /* device planes [h][w] */
@@ -341,6 +344,10 @@ int64_t ccd_png_finish(ccd_png* p, void* stream);
  * ccd_png_finish_batch synchronises the stream and fills sizes[n] (n = the count given to the pack). */
 int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* stream);
 int ccd_png_finish_batch(ccd_png* p, void* stream, int64_t* sizes, int n);
+/* Level of the packs enqueued from now on (a pack already in flight is unaffected).  CCD_ERR_ARG for a NULL handle or
+ * a level other than CCD_PNG_LITERAL / CCD_PNG_LZ77. */
+enum { CCD_PNG_LITERAL = 0, CCD_PNG_LZ77 = 1 };
+int ccd_png_set_level(ccd_png* p, int level);
 
 /* ---- rate model (reference: coolchic/component/core/arm.py:448-485 compute_rate / _laplace_cdf, float32) ------
  * rate[i] = -log2(max(cdf(x+0.5) - cdf(x-0.5), 2^-16)) with the continuous Laplace(mu, scale) of the reference.

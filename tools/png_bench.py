@@ -1,4 +1,7 @@
-"""Times the device PNG packer against PIL (zlib level 6, the reference's writer) on the same pictures."""
+"""Times the device PNG packer against PIL (zlib level 6, the reference's writer) on the same pictures.
+
+--level 0 (default) times the literal-only packer, --level 1 the packer with LZ77 matches."""
+import argparse
 import io
 import sys
 import time
@@ -20,7 +23,11 @@ def photo(h, w, seed=0):
 def main():
     from PIL import Image
 
-    p = PngPacker(0)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--level", type=int, choices=(0, 1), default=0, help="PNG packer level")
+    level = ap.parse_args().level
+    p = PngPacker(0, level)
+    print(f"level {level}")
     for h, w in ((512, 768), (1080, 1920), (2160, 3840)):
         planes = photo(h, w)
         d = torch.from_numpy(planes).cuda()
