@@ -12,9 +12,12 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    bitstream.header.{Video,Frame,CoolChic}Header
     io.io.save_frame_data_to_file, io.framedata.FrameData
                                                    io.save_frame_data_to_file, io.FrameData
+    bitstream.encode.encode_frame (range-coding of the latents, encode.py:83-92)
+                                                   encoder.EncodeBatch, writer.encode_coolchic(device=...)
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
+from .encoder import EncodeBatch  # noqa: F401
 
 
 

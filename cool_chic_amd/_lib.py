@@ -141,6 +141,16 @@ SIGNATURES = {
     "ccd_png_pack_batch": (C.c_int, [C.c_void_p, C.POINTER(PngItem), C.c_int, C.c_void_p]),
     "ccd_png_finish_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "ccd_png_set_level": (C.c_int, [C.c_void_p, C.c_int]),
+    "ccd_enc_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_enc_destroy": (None, [C.c_void_p]),
+    "ccd_enc_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_int]),
+    "ccd_enc_size": (C.c_int, [C.c_void_p]),
+    "ccd_enc_run": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_enc_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_enc_slot_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.POINTER(_u8p)]),
+    "ccd_enc_slot_payload": (C.c_int64, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_enc_slot_status": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ccd_enc_payload_bound": (C.c_size_t, [C.c_int64]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

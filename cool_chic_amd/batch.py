@@ -54,6 +54,7 @@ class DecodeBatch:
         if overlap is not None:
             check(lib().ccd_batch_set_option(self._h, self.OPT_OVERLAP, int(bool(overlap))), "ccd_batch_set_option")
         self._meta: List[Tuple[int, int]] = []
+        self._nn: List[bytes] = []
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -74,7 +75,12 @@ class DecodeBatch:
         slot = check(lib().ccd_batch_add(self._h, cc_header, len(cc_header), bytes_nn, len(bytes_nn), bytes_latent,
                                          len(bytes_latent), int(bitdepth), int(frame_data_type)), "ccd_batch_add")
         self._meta.append((int(bitdepth), int(frame_data_type)))
+        self._nn.append(bytes(bytes_nn))
         return slot
+
+    def network_bytes(self, slot: int) -> bytes:
+        """The NN payload the slot was added with (what EncodeBatch.add_from_decode re-frames)."""
+        return self._nn[slot]
 
     def header(self, slot: int) -> CCHeader:
         h = CCHeader()

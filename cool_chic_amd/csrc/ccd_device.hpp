@@ -46,6 +46,23 @@ struct EntropyParams {
                              // is the number of bits a hidden activation may have before the task is redone in int64 (23)
 };
 
+// Per-slot description of the device WRITER (ccd_encode.hip): the entropy model in the layout the decoder uses (`ep`: geometry,
+// integer networks, Laplace tables; ep.latent are the grids to ENCODE, read-only; ep.words / ifce_feat / ring fields unused) plus
+// where a pixel's interval goes.  Coding order: grids n-1 .. 0; inside a grid raster when W <= 9, else wavefront steps
+// c = x + 10 y with the pixels of a step in increasing y (latent.py:66-140).
+struct alignas(8) EncodePair { uint32_t left, width; };  // one 8-byte access
+struct EncodeParams {
+    EntropyParams ep;
+    uint32_t n_symbols;
+    uint32_t n_blocks;                           // workgroups of the contexts kernel: sum of ceil(H * W / 64) over the grids
+    uint32_t block_first[CCD_MAX_GRIDS];         // first workgroup of grid g (grows with g)
+    uint32_t grid_first[CCD_MAX_GRIDS];          // coding-order index of the first symbol of grid g
+    const uint32_t* step_prefix[CCD_MAX_GRIDS];  // [W + 10 (H - 1)]: symbols of grid g coded before step c (null when W <= 9)
+    EncodePair* pairs;                           // [n_symbols] (left, right - left), coding order
+    uint32_t* out;                               // payload words
+    uint32_t cap_words;                          // ccd_enc_payload_bound(n_symbols) / 4
+};
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

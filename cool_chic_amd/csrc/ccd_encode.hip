@@ -1,0 +1,239 @@
+// ccd_encode.hip - the WRITER on the device: range-encodes the latent grids of a cool-chic into exactly the bytes the
+// host writer (ccd_writer.cpp, ccd_encode_coolchic) produces.  DESIGN.md section 4.10.
+//
+// Reference behaviour restated here (paths relative to /root/reference/coolchic):
+//   bitstream/component/latent.py:142-173    the encoder walks the decoder's integer path, wavefront order x + 10 y
+//   bitstream/component/coolchic.py:94-146   IFCE features on the nearest-upsampled stack of the coarser grids
+//   bitstream/component/armint.py:180-203    fixed-point MLP (int64, wrap-around)
+//   bitstream/component/rangecoder.py:46-76  -> constriction 0.4.2 RangeEncoder + QuantizedLaplace(-64,63)
+//
+// The decoder is serial because a pixel's context is made of symbols it has to decode first.  The encoder knows every
+// latent up front, so only the coder's interval recurrence is serial.  Two kernels:
+//   1. encode_contexts_kernel: one work item per latent pixel of every grid of every slot.  Gathers the causal
+//      neighbours, evaluates the IFCE features of its position, runs the ARM in plain wrapping 64-bit arithmetic and
+//      writes the pixel's interval (left, right - left) at the pixel's position IN CODING ORDER.
+//   2. encode_chain_kernel: one wave per slot walks those intervals and runs the range encoder.  The intervals are
+//      fetched 64 at a time by the whole wave; the recurrence is wave-uniform and runs on the scalar unit; words leave
+//      through ordinary vector stores of lane 0.
+#include <hip/hip_runtime.h>
+
+#include "ccd_device.hpp"
+#include "ccd_laplace.hpp"
+
+namespace ccd {
+
+constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever reads the LDS column it wrote (no barrier)
+
+// ---- stage 1: contexts ------------------------------------------------------------------------------------------
+// blockIdx.y = slot, blockIdx.x = index into the slot's blocks: every grid owns ceil(H * W / 64) consecutive blocks
+// (EncodeParams::block_first), so the grid - and with it every network offset - is uniform in a workgroup.
+__global__ __launch_bounds__(kEncThreads) void encode_contexts_kernel(const EncodeParams* slots) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.y];
+    const EntropyParams& P = Q.ep;
+    if (blockIdx.x >= Q.n_blocks) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    int g = 0;
+    while (g + 1 < n_grids && blockIdx.x >= Q.block_first[g + 1]) ++g;  // block_first grows with g
+    const int H = P.grid_h[g], W = P.grid_w[g];
+    const int p = static_cast<int>(blockIdx.x - Q.block_first[g]) * kEncThreads + lane;
+    if (p >= H * W) return;
+    const int y = p / W, x = p - y * W;
+    const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
+    int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
+    int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
+    const int8_t* __restrict__ lat = P.latent[g];
+
+    // the pixel's own symbol: checked before anything depends on it (the host writer: CCD_ERR_VALUE)
+    const int sym = lat[p];
+    if (sym < kAcLo || sym > kAcLo + kAlphabet - 1) { P.status[0] = CCD_ERR_VALUE; return; }
+
+    // ---- contexts, already << 16 (armint.py:193) ----
+    for (int k = 0; k < n_sp; ++k) {
+        const int yy = y - P.ctx_dy[k], xx = x + P.ctx_dx[k];
+        const int64_t v = (yy >= 0 && xx >= 0 && xx < W) ? lat[yy * W + xx] : 0;
+        xa[k * kEncThreads] = static_cast<int64_t>(static_cast<uint64_t>(v) << 16);
+    }
+    // IFCE features of (y >> 1, x >> 1) at the coarser neighbour's size (coolchic.py:94-146).  Evaluated here, per
+    // pixel, instead of once per feature position: four pixels share a position, so the work is done four times, but
+    // it is ~5 % of the ARM's and no feature plane and no second pass exist.
+    const int fin = P.ifce_in[g];
+    if (fin > 0) {
+        const int64_t* fw_ = P.ifce + P.ifce_off[g];  // w[fin][n_if]
+        const int64_t* fb_ = fw_ + fin * n_if;
+        const int fy = y >> 1, fx = x >> 1;
+        const bool first = g == n_grids - 1;          // the stack is a single all-zero channel (coolchic.py:95-96)
+        const int base_level = first ? 0 : P.level[g + 1];
+        for (int o = 0; o < n_if; ++o) {
+            uint64_t acc = static_cast<uint64_t>(fb_[o]);
+            if (!first) {
+                for (int c = 0; c < fin; ++c) {
+                    const int m = g + 1 + c;
+                    const int sh = P.level[m] - base_level;
+                    const int64_t v = P.latent[m][(fy >> sh) * P.grid_w[m] + (fx >> sh)];
+                    acc += static_cast<uint64_t>(v << 16) * static_cast<uint64_t>(fw_[c * n_if + o]);
+                }
+            }
+            const int64_t q8 = static_cast<int64_t>(acc) >> 24;
+            // .to(torch.float) / back to int64 round trip around F.interpolate (coolchic.py:142-144)
+            const int64_t f = static_cast<int32_t>(static_cast<int64_t>(static_cast<float>(q8)));
+            xa[(n_sp + o) * kEncThreads] = static_cast<int64_t>(static_cast<uint64_t>(f) << 16);
+        }
+    } else {
+        for (int o = 0; o < n_if; ++o) xa[(n_sp + o) * kEncThreads] = 0;
+    }
+
+    // ---- ARM (armint.py:180-203): stabiliser branch, hidden layers, output layer; weights are wave-uniform reads ----
+    const int64_t* ws = P.arm + (P.arm_len - 2 - 2 * dim);
+    const int64_t* bs = ws + 2 * dim;
+    uint64_t st0 = static_cast<uint64_t>(bs[0]), st1 = static_cast<uint64_t>(bs[1]);
+    for (int k = 0; k < dim; ++k) {
+        const uint64_t v = static_cast<uint64_t>(xa[k * kEncThreads]);
+        st0 += v * static_cast<uint64_t>(ws[k * 2]);
+        st1 += v * static_cast<uint64_t>(ws[k * 2 + 1]);
+    }
+    int64_t* xin = xa;
+    int64_t* xout = xb;
+    const int64_t* lw = P.arm;
+    for (int l = 0; l < P.n_layers - 1; ++l) {
+        const int64_t* lb = lw + dim * dim;
+        for (int o = 0; o < dim; o += 2) {  // two outputs per pass: two independent accumulator chains
+            const int o1 = min(o + 1, dim - 1);
+            uint64_t a0 = static_cast<uint64_t>(lb[o]), a1 = static_cast<uint64_t>(lb[o1]);
+#pragma unroll 2
+            for (int k = 0; k < dim; ++k) {
+                const uint64_t v = static_cast<uint64_t>(xin[k * kEncThreads]);
+                a0 += v * static_cast<uint64_t>(lw[k * dim + o]);
+                a1 += v * static_cast<uint64_t>(lw[k * dim + o1]);
+            }
+            const int64_t v0 = static_cast<int64_t>(a0), v1 = static_cast<int64_t>(a1);
+            xout[o * kEncThreads] = (v0 < 0 ? 0 : v0) >> 16;
+            xout[o1 * kEncThreads] = (v1 < 0 ? 0 : v1) >> 16;
+        }
+        int64_t* t = xin; xin = xout; xout = t;
+        lw = lb + dim;
+    }
+    {
+        const int64_t* lb = lw + dim * 2;
+        uint64_t a0 = static_cast<uint64_t>(lb[0]), a1 = static_cast<uint64_t>(lb[1]);
+        for (int k = 0; k < dim; ++k) {
+            const uint64_t v = static_cast<uint64_t>(xin[k * kEncThreads]);
+            a0 += v * static_cast<uint64_t>(lw[k * 2]);
+            a1 += v * static_cast<uint64_t>(lw[k * 2 + 1]);
+        }
+        st0 += a0; st1 += a1;
+    }
+    // table indices (latent.py:156-165, rangecoder.py:90-91)
+    const int64_t mi = (static_cast<int64_t>(st0) >> 24) + kMuOffset, si = (static_cast<int64_t>(st1) >> 24) + kScaleOffset;
+    const int mu_idx = static_cast<int>(mi < 0 ? 0 : (mi > kNumMu - 1 ? kNumMu - 1 : mi));
+    const int sc_idx = static_cast<int>(si < 0 ? 0 : (si > kNumScale - 1 ? kNumScale - 1 : si));
+
+    // ---- the symbol's interval under the leaky quantised Laplace model ----
+    const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
+    const double rcp = P.rcp_table[sc_idx];
+    const uint32_t left = window_left(mu, rcp, sym, kExpTab);           // 0 for -64
+    const uint32_t right = window_left(mu, rcp, sym + 1, kExpTab);      // 2^24 for 63
+
+    // ---- position in coding order (latent.py:66-140): raster if W <= 9, else steps c = x + 10 y, increasing y ----
+    uint32_t idx = Q.grid_first[g];
+    if (W <= 9) idx += static_cast<uint32_t>(p);
+    else {
+        const int c = x + 10 * y;
+        const int y0 = c < W ? 0 : (c - W) / 10 + 1;  // first row of the step
+        idx += Q.step_prefix[g][c] + static_cast<uint32_t>(y - y0);
+    }
+    Q.pairs[idx] = EncodePair{left, right - left};
+}
+
+// ---- stage 2: the interval chain --------------------------------------------------------------------------------
+// constriction's RangeEncoder as ccd_writer.cpp:41-83 restates it, one wave per slot.  Every value of the recurrence
+// is the same in all lanes (it is made of v_readlane results and constants), so the compiler keeps it in scalar
+// registers; the only vector work is the fetch of the next 64 intervals and the stores of lane 0.
+// status: [0] error, [1] words written, [2] times an "inverted" run began, [3] runs resolved WITH a carry,
+//         [4] runs resolved without one (the carry path is exercised, not assumed).
+__global__ __launch_bounds__(kEncThreads) void encode_chain_kernel(const EncodeParams* slots) {
+    const EncodeParams& Q = slots[blockIdx.x];
+    int32_t* status = Q.ep.status;
+    const int lane = threadIdx.x;
+    if (status[0] != 0) return;  // a symbol outside the alphabet: the slot emits nothing
+    const uint32_t n = Q.n_symbols, cap = Q.cap_words;
+    uint32_t* __restrict__ out = Q.out;
+    const EncodePair* __restrict__ pairs = Q.pairs;
+
+    uint64_t lower = 0, range = ~uint64_t{0};
+    bool inverted = false;
+    uint32_t n_inverted = 0, first_inverted = 0, pos = 0;
+    uint32_t n_runs = 0, n_carry = 0, n_plain = 0;
+    auto put_word = [&](uint32_t w) {
+        if (lane == 0 && pos < cap) out[pos] = w;
+        ++pos;
+    };
+    auto flush_inverted = [&](bool carry) {
+        put_word(carry ? first_inverted + 1u : first_inverted);
+        const uint32_t fill = carry ? 0u : 0xFFFFFFFFu, m = n_inverted - 1;
+        for (uint32_t j = lane; j < m; j += kEncThreads) if (pos + j < cap) out[pos + j] = fill;
+        pos += m;
+        if (carry) ++n_carry; else ++n_plain;
+    };
+
+    EncodePair nxt{0u, 0u};
+    if (static_cast<uint32_t>(lane) < n) nxt = pairs[lane];
+    for (uint32_t base = 0; base < n; base += kEncThreads) {
+        const EncodePair cur = nxt;
+        const uint32_t ahead = base + kEncThreads + lane;
+        if (ahead < n) nxt = pairs[ahead];  // in flight while this chunk's 64 symbols are coded
+        const int cnt = static_cast<int>(min(static_cast<uint32_t>(kEncThreads), n - base));
+        for (int i = 0; i < cnt; ++i) {
+            const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cur.left), i));
+            const uint32_t w = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cur.width), i));
+            const uint64_t scale = range >> kRcPrecision;
+            range = scale * static_cast<uint64_t>(w);
+            const uint64_t moved = lower + scale * l;
+            if (inverted && static_cast<uint64_t>(moved + range) > moved) { flush_inverted(moved < lower); inverted = false; }
+            lower = moved;
+            if ((range >> 32) == 0) {
+                const uint32_t word = static_cast<uint32_t>(lower >> 32);
+                lower <<= 32; range <<= 32;
+                if (inverted) ++n_inverted;
+                else if (static_cast<uint64_t>(lower + range) > lower) put_word(word);
+                else { inverted = true; n_inverted = 1; first_inverted = word; ++n_runs; }
+            }
+        }
+    }
+    if (n > 0) {  // seal
+        const uint64_t point = lower + ((uint64_t{1} << 32) - 1);
+        if (inverted) flush_inverted(point < lower);
+        const uint32_t point_word = static_cast<uint32_t>(point >> 32);
+        put_word(point_word);
+        if (static_cast<uint32_t>(static_cast<uint64_t>(lower + range) >> 32) == point_word) put_word(0u);
+    }
+    if (lane == 0) {
+        status[0] = pos <= cap ? 0 : CCD_ERR_NOMEM;  // (cannot happen: cap is ccd_enc_payload_bound)
+        status[1] = static_cast<int32_t>(pos);
+        status[2] = static_cast<int32_t>(n_runs);
+        status[3] = static_cast<int32_t>(n_carry);
+        status[4] = static_cast<int32_t>(n_plain);
+    }
+}
+
+size_t encode_contexts_lds_bytes(int dim) { return static_cast<size_t>(2) * dim * kEncThreads * sizeof(int64_t); }
+int encode_block_threads() { return kEncThreads; }
+
+hipError_t launch_encode(const EncodeParams* d_slots, int n_slots, unsigned max_blocks, size_t lds_bytes, hipStream_t stream) {
+    if (n_slots <= 0) return hipSuccess;
+    if (max_blocks > 0) {
+        if (lds_bytes > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_contexts_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(encode_contexts_kernel, dim3(max_blocks, n_slots), dim3(kEncThreads), lds_bytes, stream, d_slots);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(encode_chain_kernel, dim3(n_slots), dim3(kEncThreads), 0, stream, d_slots);
+    return hipGetLastError();
+}
+
+}  // namespace ccd

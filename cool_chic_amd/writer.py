@@ -24,13 +24,19 @@ def range_encode(symbols: np.ndarray, mu_idx: np.ndarray, scale_idx: np.ndarray)
 
 
 def encode_stream(cc_header: bytes, bytes_nn: bytes, latents: Sequence[np.ndarray], bitdepth: int = 8,
-                  frame_data_type: int = 0, img_size=None) -> bytes:
+                  frame_data_type: int = 0, img_size=None, device=None) -> bytes:
     """One-intra-frame .cool file with the architecture of `cc_header`, NN payload `bytes_nn` and the given
-    quantised latents (index 0 = finest grid). `img_size` overrides the header's (H, W)."""
+    quantised latents (index 0 = finest grid). `img_size` overrides the header's (H, W).
+    device=None: the host writer; an integer: the latents are range-coded on that GPU (same bytes)."""
     h = CCHeader()
     check(lib().ccd_read_cc_header(cc_header, len(cc_header), C.byref(h)), "ccd_read_cc_header")
     if img_size is not None:
         h.img_size[0], h.img_size[1] = int(img_size[0]), int(img_size[1])
+    if device is not None:
+        if not 8 <= int(bitdepth) <= 16:
+            check(-7, "encode_stream")  # CCD_ERR_ARG, like ccd_encode_stream
+        return (video_header_bytes(1, [0], []) + frame_header_bytes(0, "I", int(frame_data_type), int(bitdepth)) +
+                encode_coolchic(h, bytes_nn, latents, device=device))
     arrs = [np.ascontiguousarray(a, dtype=np.int8) for a in latents]
     ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
     out = C.POINTER(C.c_uint8)()
@@ -64,8 +70,20 @@ def encode_network(arch: CCHeader, values: np.ndarray) -> bytes:
     return payload
 
 
-def encode_coolchic(arch: CCHeader, bytes_nn: bytes, latents: Sequence[np.ndarray]) -> bytes:
-    """Cool-chic header + NN payload + range-coded latents of one cool-chic (bitstream/encode.py:83-92)."""
+def encode_coolchic(arch: CCHeader, bytes_nn: bytes, latents: Sequence[np.ndarray], device=None) -> bytes:
+    """Cool-chic header + NN payload + range-coded latents of one cool-chic (bitstream/encode.py:83-92).
+    device=None: the host writer; an integer: the device writer on that GPU (encoder.EncodeBatch, same bytes)."""
+    if device is not None:
+        from .encoder import EncodeBatch
+
+        enc = EncodeBatch(int(device))
+        try:
+            slot = enc.add(arch, bytes_nn, latents)
+            enc.run()
+            enc.wait()
+            return enc.bytes(slot)
+        finally:
+            enc.close()
     arrs = [np.ascontiguousarray(a, dtype=np.int8) for a in latents]
     ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
     out = C.POINTER(C.c_uint8)()

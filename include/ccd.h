@@ -349,6 +349,40 @@ int ccd_png_finish_batch(ccd_png* p, void* stream, int64_t* sizes, int n);
 enum { CCD_PNG_LITERAL = 0, CCD_PNG_LZ77 = 1 };
 int ccd_png_set_level(ccd_png* p, int level);
 
+/* ---- bitstream writer on the device (reference: bitstream/encode.py:83-92, component/latent.py:142-173; DESIGN.md
+ * section 4.10).  Turns (architecture, NN payload, latent grids) into exactly the bytes ccd_encode_coolchic returns: the
+ * contexts of every pixel of every grid are evaluated at once (the encoder knows all latents), then one wave per slot runs
+ * the range encoder's interval chain.  All slots of a handle are encoded by the same two launches.
+ * ccd_enc_add: latents[g] = int8 [grid_h[g]][grid_w[g]], host pointers (copied at add; a value outside [-64, 63] is
+ * CCD_ERR_VALUE) or, with latents_on_device != 0, device pointers such as ccd_batch_latent() returns (read when a run
+ * EXECUTES, so they must stay valid; a value outside [-64, 63] makes ccd_enc_wait return CCD_ERR_VALUE for that slot, the
+ * other slots are unaffected).  Returns the slot index.  NULL arguments are CCD_ERR_ARG, a template that does not re-parse
+ * CCD_ERR_VALUE; both are found before the device is touched.
+ * ccd_enc_run only enqueues on `stream`; ccd_enc_wait synchronises and returns the first per-slot error.  One run may be in
+ * flight per handle; a handle can be run again (same bytes) and can take more slots after a run.  ccd_enc_destroy drains
+ * the streams the handle was given. */
+typedef struct ccd_enc ccd_enc;
+int ccd_enc_create(int device, ccd_enc** out);
+void ccd_enc_destroy(ccd_enc* e);
+int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                int latents_on_device);
+int ccd_enc_size(const ccd_enc* e);
+int ccd_enc_run(ccd_enc* e, void* stream);
+int ccd_enc_wait(ccd_enc* e, void* stream);
+/* After wait: cool-chic header (n_bytes_latent filled in) + NN payload + range-coded latents, == ccd_encode_coolchic;
+ * malloc'ed *out, free with ccd_free.  Returns the byte count, the slot's error, or CCD_ERR_ARG (bad slot, no finished run). */
+int64_t ccd_enc_slot_bytes(ccd_enc* e, int slot, uint8_t** out);
+/* The range-coded payload where it was written: device pointer (4-byte aligned) and size in bytes, valid until the next
+ * run / destroy - what a decoder or verifier on the same GPU reads without a copy through the host. */
+int64_t ccd_enc_slot_payload(const ccd_enc* e, int slot, const uint8_t** device_ptr);
+/* After wait: the slot's status; out8 (optional) receives [0] status, [1] payload words, and how the coder's carry was
+ * exercised: [2] "inverted" runs begun (the interval straddled 2^64 at a word boundary), [3] runs resolved with a carry,
+ * [4] resolved without one. */
+int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8);
+/* Size of a slot's payload buffer: every symbol has a width of at least 1 / 2^24, so n symbols give at most
+ * 4 * (ceil(24 n / 32) + 2) bytes.  0 for n < 0. */
+size_t ccd_enc_payload_bound(int64_t n_symbols);
+
 /* ---- rate model (reference: coolchic/component/core/arm.py:448-485 compute_rate / _laplace_cdf, float32) ------
  * rate[i] = -log2(max(cdf(x+0.5) - cdf(x-0.5), 2^-16)) with the continuous Laplace(mu, scale) of the reference.
  * x, mu, scale, rate (optional), total_bits (optional, one double) are DEVICE pointers; asynchronous on `stream`. */
