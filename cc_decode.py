@@ -12,6 +12,13 @@ if __name__ == "__main__":
     parser.add_argument("--device", type=int, help="GPU index.", default=0)
     parser.add_argument("--png-level", type=int, choices=(0, 1), default=0,
                         help="PNG output: 0 = literal-only deflate (default), 1 = with LZ77 matches (smaller files).")
+    parser.add_argument("--source", type=str, default=None,
+                        help="Source of the stream (.png, .ppm or planar .yuv): every decoded frame is scored against it on the GPU.")
+    parser.add_argument("--results", type=str, default=None,
+                        help="With --source: tab-separated file with the rate, PSNR and MS-SSIM of every frame and of the sequence.")
+    parser.add_argument("--no-ms-ssim", action="store_true", help="With --source: PSNR only.")
     args = parser.parse_args()
+    if args.results is not None and args.source is None:
+        parser.error("--results needs --source")
     decode_video(args.input, decoded_path=args.output, verbosity=args.verbosity, device=args.device,
-                 png_level=args.png_level)
+                 png_level=args.png_level, source_path=args.source, ms_ssim=not args.no_ms_ssim, results_path=args.results)

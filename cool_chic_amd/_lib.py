@@ -68,6 +68,16 @@ class PngItem(C.Structure):
                 ("out", C.c_void_p), ("cap", C.c_size_t)]
 
 
+class QualityItem(C.Structure):
+    _fields_ = [("dec", C.c_void_p * 3), ("src", C.c_void_p * 3), ("h", C.c_int32), ("w", C.c_int32), ("ch", C.c_int32),
+                ("cw", C.c_int32), ("bitdepth", C.c_int32)]
+
+
+class QualityResult(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 3), ("n", C.c_uint64 * 3), ("n_scales", C.c_int32 * 3), ("cs", (C.c_double * 5) * 3),
+                ("ssim", (C.c_double * 5) * 3)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -141,6 +151,13 @@ SIGNATURES = {
     "ccd_png_pack_batch": (C.c_int, [C.c_void_p, C.POINTER(PngItem), C.c_int, C.c_void_p]),
     "ccd_png_finish_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "ccd_png_set_level": (C.c_int, [C.c_void_p, C.c_int]),
+    "ccd_quality_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_quality_destroy": (None, [C.c_void_p]),
+    "ccd_quality_score_batch": (C.c_int, [C.c_void_p, C.POINTER(QualityItem), C.c_int, C.c_int, C.c_void_p]),
+    "ccd_quality_finish_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QualityResult), C.c_int]),
+    "ccd_quality_psnr": (C.c_double, [C.POINTER(QualityResult), C.c_int, C.c_int]),
+    "ccd_quality_ms_ssim": (C.c_double, [C.POINTER(QualityResult), C.c_int]),
+    "ccd_quality_scratch_bytes": (C.c_int64, [C.POINTER(QualityItem), C.c_int, C.c_int]),
     "ccd_enc_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_enc_destroy": (None, [C.c_void_p]),
     "ccd_enc_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_int]),

@@ -79,9 +79,15 @@ def decode_frame(bitstream_bytes: bytes, reference_frames: List[FrameData], verb
 
 @torch.no_grad()
 def decode_video(bitstream_path: str, decoded_path: Optional[str] = None, max_decoding_order: int = -1,
-                 verbosity: int = 0, device: int = 0, png_level: int = 0) -> Dict[str, FrameData]:
+                 verbosity: int = 0, device: int = 0, png_level: int = 0, source_path: Optional[str] = None,
+                 results_path: Optional[str] = None, ms_ssim: bool = True) -> Dict[str, FrameData]:
     """decode.py:26-91: decode a .cool file; returns {display index as str: FrameData}.  png_level: level of the
-    device PNG packer when decoded_path is a .png (0 literal-only, 1 with LZ77 matches)."""
+    device PNG packer when decoded_path is a .png (0 literal-only, 1 with LZ77 matches).
+    source_path: the pictures the stream was encoded from; every decoded frame is then scored against them on the device
+    (decode_video_scored, which also returns the scores) and results_path, if given, receives one row per frame."""
+    if source_path is not None or results_path is not None:
+        return decode_video_scored(bitstream_path, source_path, decoded_path, max_decoding_order, verbosity, device, png_level,
+                                   results_path, ms_ssim)[0]
     with open(bitstream_path, "rb") as f:
         bitstream_bytes = f.read()
     vh = VideoHeader()
@@ -131,6 +137,46 @@ def decode_video(bitstream_path: str, decoded_path: Optional[str] = None, max_de
         if decoded_path is not None and display_idx in frames:
             save_frame_data_to_file(frames[display_idx], decoded_path, append=display_idx != 0, png_level=png_level)
     return all_frames
+
+
+def decode_video_scored(bitstream_path: str, source_path: str, decoded_path: Optional[str] = None, max_decoding_order: int = -1,
+                        verbosity: int = 0, device: int = 0, png_level: int = 0, results_path: Optional[str] = None,
+                        ms_ssim: bool = True):
+    """decode_video, then what the reference does next (cc_encode.py:461-505): PSNR (and MS-SSIM) of every decoded frame
+    against its source and the rate it took, all frames scored on the device in one batch (cool_chic_amd/quality.py).
+    source_path: a .png / .ppm picture or a planar .yuv file whose frame d is the source of display index d.
+    Returns (the dictionary of decode_video, [FrameQuality of every decoded frame in display order]); with results_path
+    the tab-separated table of quality.write_results is written as well."""
+    from ..quality import QualityMeter, read_source, write_results
+
+    if source_path is None:
+        raise ValueError("a results file needs the source the frames are scored against (source_path)")
+    all_frames = decode_video(bitstream_path, decoded_path, max_decoding_order, verbosity, device, png_level)
+    # what every frame took in the stream: the bytes _split_frame consumes for it
+    with open(bitstream_path, "rb") as f:
+        bitstream_bytes = f.read()
+    vh = VideoHeader()
+    rest = vh.read_header(bitstream_bytes)
+    n_bytes_video_header = len(bitstream_bytes) - len(rest)
+    structure = vh.get_coding_structure()
+    n_decode = vh.get_value("n_frames") if max_decoding_order == -1 else max_decoding_order + 1
+    taken = {}
+    for k in range(n_decode):
+        before = len(rest)
+        fh, _, rest = _split_frame(rest)
+        taken[structure[k]["display_order"]] = (fh.get_value("frame_type"), before - len(rest))
+    shown = [d for d in range(vh.get_value("n_frames")) if all_frames[str(d)] is not None]
+    frames = [all_frames[str(d)] for d in shown]
+    sources = [read_source(source_path, fd, frame_index=d) for d, fd in zip(shown, frames)]
+    meter = QualityMeter(device)
+    try:
+        qualities = meter.score(frames, sources, ms_ssim=ms_ssim)
+    finally:
+        meter.close()
+    if results_path is not None:
+        write_results(results_path, [(d, taken[d][0], fd.n_pixels, taken[d][1], q) for d, fd, q in zip(shown, frames, qualities)],
+                      n_bytes_video_header)
+    return all_frames, qualities
 
 
 def _decode_gop(rest: bytes, n_decode: int, device: int, group, verbosity: int = 0, collect: Optional[int] = 0,

@@ -389,6 +389,45 @@ size_t ccd_enc_payload_bound(int64_t n_symbols);
 int ccd_compute_rate(int device, void* stream, const float* x, const float* mu, const float* scale, int64_t n,
                      float* rate, double* total_bits);
 
+/* ---- quality of decoded frames against their source, on the device -------------------------
+ * Compares the integer planes of a batch of frames (ccd_batch_plane) with source planes of the same types and sizes in one
+ * set of launches.  PSNR as the reference defines it (training/metrics/mse.py:14-21, loss.py:88-118): the squared error of
+ * every plane as an exact 64-bit integer; the division and the logarithm happen on the host (ccd_quality_psnr).
+ * MS-SSIM (Wang, Simoncelli, Bovik 2003) per plane on x = sample / (2^bitdepth - 1): 5 scales, 11-tap Gaussian window
+ * (sigma 1.5) applied separably without padding, C1 = 0.01^2, C2 = 0.03^2, 2 x 2 mean with stride 2 between scales (a trailing
+ * odd row or column is dropped); the device returns the spatial means of cs and ssim per scale, ccd_quality_ms_ssim
+ * combines them.  A plane whose shorter side is below 176 has n_scales = 0 (its MS-SSIM is NaN): a result, not an error.
+ * The results of a picture do not depend on what else is in the batch, and the same batch gives the same bits every time.
+ * ccd_quality_score_batch only enqueues on `stream` (the planes must stay valid until the finish); ccd_quality_finish_batch
+ * synchronises and fills results[n] (n = the count given to the score).  One scoring may be in flight per handle; a handle
+ * is reusable; ccd_quality_destroy drains the streams the handle was given.  CCD_ERR_ARG - before the device is touched -
+ * for a NULL argument, n <= 0, a bit depth outside 8..16, a side outside 1..16383, a `what` of 0 or with unknown bits. */
+typedef struct ccd_quality ccd_quality;
+typedef struct {
+    const void* dec[3];      /* device planes, u8 if bitdepth == 8 else u16 (ccd_batch_plane) */
+    const void* src[3];      /* device planes of the source, same types and sizes */
+    int32_t h, w, ch, cw;    /* luma size, chroma size (== h, w unless yuv420) */
+    int32_t bitdepth;        /* 8..16 */
+} ccd_quality_item;
+typedef struct {
+    uint64_t sse[3], n[3];
+    int32_t  n_scales[3];    /* 5, or 0 when the plane is too small (or MS-SSIM was not asked for) */
+    double   cs[3][5], ssim[3][5];   /* spatial means per scale */
+} ccd_quality_result;
+enum { CCD_QUALITY_PSNR = 1, CCD_QUALITY_MS_SSIM = 2 };
+int ccd_quality_create(int device, ccd_quality** out);
+void ccd_quality_destroy(ccd_quality* q);
+int ccd_quality_score_batch(ccd_quality* q, const ccd_quality_item* items, int n, int what, void* stream);
+int ccd_quality_finish_batch(ccd_quality* q, void* stream, ccd_quality_result* results, int n);
+/* Host only, no device needed.  psnr: -10 log10(sum sse / (sum n * maxv^2)) over one plane or, plane = -1, the whole frame
+ * (+inf for identical pictures; NaN for a NULL result, a bad plane or bit depth).  ms_ssim: prod_{j<4} max(cs[j], 0)^w_j *
+ * max(ssim[4], 0)^w_4 of one plane, NaN when n_scales is 0. */
+double ccd_quality_psnr(const ccd_quality_result* r, int bitdepth, int plane);
+double ccd_quality_ms_ssim(const ccd_quality_result* r, int plane);
+/* Host only: validates like ccd_quality_score_batch (pointers are compared with NULL, never read) and returns the bytes of
+ * device scratch the scoring takes from the block cache, or CCD_ERR_ARG. */
+int64_t ccd_quality_scratch_bytes(const ccd_quality_item* items, int n, int what);
+
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):
  * left[i], right[i] as the entropy kernel sees them (exhaustive parity tests of the f64 CDF). */
 int ccd_debug_laplace_bounds(int device, const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* s,
