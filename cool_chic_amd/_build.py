@@ -4,8 +4,8 @@ import shutil
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["ccd_format.cpp", "ccd_writer.cpp", "ccd_api.cpp", "ccd_entropy.hip", "ccd_entropy_pipe.hip", "ccd_float.hip", "ccd_synth_fused.hip", "ccd_fused.hip", "ccd_fused_pre.hip", "ccd_fused_cr.hip", "ccd_inter.hip", "ccd_png.hip", "ccd_rate.hip", "ccd_encode.hip", "ccd_quality.hip"]
-HEADERS = ["ccd_format.hpp", "ccd_device.hpp", "ccd_laplace.hpp", "ccd_quality.hpp", "ccd_fused_kernel.inc", "ccd_exp_table.inc", "ccd_dec_block16p.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "../../include/ccd.h", "../../include/ccd_scale_table.inc"]
+SOURCES = ["ccd_format.cpp", "ccd_writer.cpp", "ccd_runtime.cpp", "ccd_batch_plan.cpp", "ccd_batch.cpp", "ccd_video.cpp", "ccd_enc_api.cpp", "ccd_quality_api.cpp", "ccd_entropy.hip", "ccd_entropy_pipe.hip", "ccd_float.hip", "ccd_synth_fused.hip", "ccd_fused.hip", "ccd_fused_pre.hip", "ccd_fused_cr.hip", "ccd_inter.hip", "ccd_png.hip", "ccd_rate.hip", "ccd_encode.hip", "ccd_quality.hip"]
+HEADERS = ["ccd_format.hpp", "ccd_device.hpp", "ccd_host.hpp", "ccd_kernels.hpp", "ccd_laplace.hpp", "ccd_quality.hpp", "ccd_fused_kernel.inc", "ccd_exp_table.inc", "ccd_dec_block16p.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "../../include/ccd.h", "../../include/ccd_scale_table.inc"]
 LIB = os.path.join(_HERE, "libccd.so")
 
 
@@ -65,7 +65,8 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, SOURCES))
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    # --no-undefined: a launcher whose definition drifted from ccd_kernels.hpp fails here, not at its first call
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -92,7 +93,7 @@ def build_variant(name: str, extra_flags: str) -> str:
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, SOURCES))
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs)
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", out] + objs)
     return out
 
 

@@ -1,0 +1,288 @@
+// ccd_enc_api.cpp - ccd_enc_* of include/ccd.h: the host side of the device writer.
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "ccd_host.hpp"
+#include "ccd_kernels.hpp"
+
+using namespace ccd;
+
+extern "C" {
+
+// ---- device writer (ccd_encode.hip) ---------------------------------------------------------
+namespace {
+constexpr int kEncStatusWords = 8;  // per slot: error, words written, inverted runs begun, resolved with / without a carry
+
+struct EncSlot {
+    ccd_cc_header hdr;             // re-derived from the template, nn_n_bytes = size of `nn`
+    std::vector<uint8_t> nn;
+    EncodeParams ep;               // ep.ep.status is set when the handle's table is built
+    Block params;                  // device: ARM | IFCE | step prefix tables | latents given as host pointers
+    Block pairs, out;
+    bool ran = false;              // part of a run that was waited for
+    int status = CCD_OK;
+    uint32_t n_words = 0;
+};
+}  // namespace
+
+struct ccd_enc {
+    int device = 0;
+    DeviceShared* sh = nullptr;
+    std::vector<std::unique_ptr<EncSlot>> slots;
+    Block table, table_host, status_dev, status_host;  // EncodeParams[n] (device, pinned), int32 [n][8] (device, pinned)
+    size_t table_slots = 0;        // slots the four blocks above describe
+    hipStream_t last_stream = nullptr;
+    bool in_flight = false;
+    size_t n_run = 0;              // slots of the run in flight / last waited for
+    std::vector<hipStream_t> streams;  // every stream a run was enqueued on (drained by destroy)
+};
+
+size_t ccd_enc_payload_bound(int64_t n_symbols) {
+    if (n_symbols < 0) return 0;
+    // the leaky model gives every symbol at least 1 / 2^24 of the interval: at most 24 bits each, plus the two words of the seal
+    return 4 * ((static_cast<size_t>(n_symbols) * kRcPrecision + 31) / 32 + 2);
+}
+
+int ccd_enc_create(int device, ccd_enc** out) {
+    if (!out) return CCD_ERR_ARG;
+    *out = nullptr;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return CCD_ERR_HIP;
+    HIP_TRY(hipSetDevice(device));
+    DeviceShared* sh = nullptr;
+    const int rc = device_shared(device, &sh);
+    if (rc < 0) return rc;
+    ccd_enc* e = new (std::nothrow) ccd_enc();
+    if (!e) return CCD_ERR_NOMEM;
+    e->device = device;
+    e->sh = sh;
+    *out = e;
+    return CCD_OK;
+}
+
+void ccd_enc_destroy(ccd_enc* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    for (hipStream_t st : e->streams) (void)hipStreamSynchronize(st);
+    for (auto& s : e->slots) { s->params.drop(); s->pairs.drop(); s->out.drop(); }
+    e->table.drop(); e->table_host.drop(); e->status_dev.drop(); e->status_host.drop();
+    delete e;
+}
+
+int ccd_enc_size(const ccd_enc* e) { return e ? static_cast<int>(e->slots.size()) : CCD_ERR_ARG; }
+
+int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                int latents_on_device) {
+    if (!e || !tmpl || !bytes_nn || !latents) return CCD_ERR_ARG;
+    std::unique_ptr<EncSlot> sp(new (std::nothrow) EncSlot());
+    if (!sp) return CCD_ERR_NOMEM;
+    EncSlot& s = *sp;
+    // ---- everything the host can refuse, before the device is touched ----
+    {   // re-derive the geometry from the transmitted fields by a serialise / parse round trip, like ccd_encode_coolchic
+        ccd_cc_header t = *tmpl;
+        t.nn_n_bytes = static_cast<int32_t>(n_nn);
+        uint8_t hb[256];
+        const int n_hb = (t.n_layer_synthesis >= 0 && t.n_layer_synthesis <= CCD_MAX_SYN_LAYERS) ? ccd_write_cc_header(&t, hb, sizeof(hb)) : -1;
+        if (n_hb < 0 || read_cc_header(hb, static_cast<size_t>(n_hb), &s.hdr) < 0) return CCD_ERR_VALUE;
+    }
+    const ccd_cc_header& h = s.hdr;
+    if (!grids_nest(h)) return CCD_ERR_VALUE;
+    Network net;
+    int rc = decode_network(h, bytes_nn, n_nn, net);
+    if (rc < 0) return rc;
+    const int n = h.n_grids;
+    for (int g = 0; g < n; ++g) if (!latents[g]) return CCD_ERR_ARG;
+    if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;
+    if (!latents_on_device)
+        for (int g = 0; g < n; ++g) {
+            const size_t cnt = static_cast<size_t>(h.grid_h[g]) * h.grid_w[g];
+            for (size_t i = 0; i < cnt; ++i)
+                if (latents[g][i] < kAcLo || latents[g][i] > kAcLo + kAlphabet - 1) return CCD_ERR_VALUE;
+        }
+    IntNetBlobs blobs;
+    pack_int_networks(h, net, blobs);
+    EncodeParams& Q = s.ep;
+    std::memset(&Q, 0, sizeof(Q));
+    EntropyParams& E = Q.ep;
+    fill_entropy_model(h, net, blobs, E);
+    {   // the shapes the kernel indexes by: dim x dim hidden layers, dim x 2 output and stabiliser, one IFCE layer per grid
+        const int dim = E.dim, n_if = E.has_ifce ? E.n_ifce_out : 0;
+        bool ok = dim >= 1 && dim == E.n_spatial + n_if && E.n_spatial <= kMaxCtx && net.arm.dim == dim &&
+                  static_cast<int>(net.arm.layers.size()) == E.n_layers &&
+                  E.arm_len == (E.n_layers - 1) * (dim * dim + dim) + 2 * (2 * dim + 2) &&
+                  encode_contexts_lds_bytes(dim) <= 160 * 1024;
+        for (int g = 0; g < n && ok; ++g) {
+            const int fin = E.ifce_in[g];
+            if (fin == 0) continue;
+            ok = n_if > 0 && (g == n - 1 || g + fin < n) && net.ifce[g].layers.size() == 1 &&
+                 static_cast<int>(net.ifce[g].layers[0].w.size()) == fin * n_if &&
+                 static_cast<int>(net.ifce[g].layers[0].b.size()) == n_if;
+        }
+        if (!ok) return CCD_ERR_UNSUPPORTED;
+    }
+    // ---- where every pixel goes: grids n-1 .. 0; raster when W <= 9, else wavefront steps (ccd_writer.cpp:349-361) ----
+    const uint32_t threads = static_cast<uint32_t>(encode_block_threads());
+    std::vector<std::vector<uint32_t>> prefix(n);
+    uint32_t first = 0;
+    for (int g = n - 1; g >= 0; --g) {
+        const int H = h.grid_h[g], W = h.grid_w[g];
+        Q.grid_first[g] = first;
+        first += static_cast<uint32_t>(H) * static_cast<uint32_t>(W);
+        if (W <= 9 || H < 1) continue;
+        const long n_steps = W + 10L * (H - 1);
+        prefix[g].resize(static_cast<size_t>(n_steps));
+        uint32_t before = 0;
+        for (long c = 0; c < n_steps; ++c) {
+            int y0, x0;
+            if (c < W) { y0 = 0; x0 = static_cast<int>(c); }
+            else { y0 = static_cast<int>((c - W) / 10) + 1; x0 = W - 10 + static_cast<int>((c - W) % 10); }
+            prefix[g][static_cast<size_t>(c)] = before;
+            before += static_cast<uint32_t>(std::min(H - y0, x0 / 10 + 1));
+        }
+    }
+    Q.n_symbols = first;
+    uint32_t blocks = 0;
+    for (int g = 0; g < n; ++g) {
+        Q.block_first[g] = blocks;
+        blocks += (static_cast<uint32_t>(h.grid_h[g]) * static_cast<uint32_t>(h.grid_w[g]) + threads - 1) / threads;
+    }
+    Q.n_blocks = blocks;
+    Q.cap_words = static_cast<uint32_t>(ccd_enc_payload_bound(first) / 4);
+
+    // ---- device image: ARM | IFCE | step prefix tables | host latents ----
+    auto align = [](size_t v) { return (v + 255) & ~size_t{255}; };
+    const size_t o_arm = 0;
+    const size_t o_ifce = align(o_arm + blobs.arm.size() * 8);
+    size_t pos = align(o_ifce + blobs.ifce.size() * 8);
+    std::vector<size_t> o_prefix(n, 0), o_lat(n, 0);
+    for (int g = 0; g < n; ++g) { o_prefix[g] = pos; pos = align(pos + prefix[g].size() * 4); }
+    if (!latents_on_device)
+        for (int g = 0; g < n; ++g) { o_lat[g] = pos; pos = align(pos + static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]); }
+    std::vector<uint8_t> image(std::max<size_t>(pos, 256), 0);
+    std::memcpy(image.data() + o_arm, blobs.arm.data(), blobs.arm.size() * 8);
+    if (!blobs.ifce.empty()) std::memcpy(image.data() + o_ifce, blobs.ifce.data(), blobs.ifce.size() * 8);
+    for (int g = 0; g < n; ++g) {
+        if (!prefix[g].empty()) std::memcpy(image.data() + o_prefix[g], prefix[g].data(), prefix[g].size() * 4);
+        if (!latents_on_device) std::memcpy(image.data() + o_lat[g], latents[g], static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]);
+    }
+
+    HIP_TRY(hipSetDevice(e->device));
+    auto fail = [&](int code) { s.params.drop(); s.pairs.drop(); s.out.drop(); return code; };
+    if (!s.params.get(e->device, BlockPool::kDevice, image.size()) ||
+        !s.pairs.get(e->device, BlockPool::kDevice, std::max<size_t>(static_cast<size_t>(first) * sizeof(EncodePair), 256)) ||
+        !s.out.get(e->device, BlockPool::kDevice, static_cast<size_t>(Q.cap_words) * 4))
+        return fail(CCD_ERR_NOMEM);
+    if (hipMemcpy(s.params.p, image.data(), image.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(CCD_ERR_HIP);
+    char* base = s.params.as<char>();
+    E.arm = reinterpret_cast<const int64_t*>(base + o_arm);
+    E.ifce = reinterpret_cast<const int64_t*>(base + o_ifce);
+    E.scale_table = e->sh->d_scale_table;
+    E.rcp_table = e->sh->d_rcp_table;
+    for (int g = 0; g < n; ++g) {
+        E.latent[g] = latents_on_device ? const_cast<int8_t*>(latents[g]) : reinterpret_cast<int8_t*>(base + o_lat[g]);  // read-only here
+        Q.step_prefix[g] = prefix[g].empty() ? nullptr : reinterpret_cast<const uint32_t*>(base + o_prefix[g]);
+    }
+    Q.pairs = s.pairs.as<EncodePair>();
+    Q.out = s.out.as<uint32_t>();
+    s.nn.assign(bytes_nn, bytes_nn + n_nn);
+    e->slots.push_back(std::move(sp));
+    return static_cast<int>(e->slots.size()) - 1;
+}
+
+int ccd_enc_run(ccd_enc* e, void* stream) {
+    if (!e) return CCD_ERR_ARG;
+    const size_t n = e->slots.size();
+    if (n == 0) return CCD_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (e->in_flight) HIP_TRY(hipStreamSynchronize(e->last_stream));  // one run in flight: its tables are about to be reused
+    e->in_flight = false;
+    if (e->table_slots != n) {
+        e->table_slots = 0;
+        if (!e->table.get(e->device, BlockPool::kDevice, n * sizeof(EncodeParams)) ||
+            !e->table_host.get(e->device, BlockPool::kPinned, n * sizeof(EncodeParams)) ||
+            !e->status_dev.get(e->device, BlockPool::kDevice, n * kEncStatusWords * sizeof(int32_t)) ||
+            !e->status_host.get(e->device, BlockPool::kPinned, n * kEncStatusWords * sizeof(int32_t)))
+            return CCD_ERR_NOMEM;
+        for (size_t i = 0; i < n; ++i) {
+            e->slots[i]->ep.ep.status = e->status_dev.as<int32_t>() + i * kEncStatusWords;
+            e->table_host.as<EncodeParams>()[i] = e->slots[i]->ep;
+        }
+        e->table_slots = n;
+    }
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    for (auto& s : e->slots) {
+        max_blocks = std::max<unsigned>(max_blocks, s->ep.n_blocks);
+        lds = std::max(lds, encode_contexts_lds_bytes(s->ep.ep.dim));
+    }
+    HIP_TRY(hipMemcpyAsync(e->table.p, e->table_host.p, n * sizeof(EncodeParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(e->status_dev.p, 0, n * kEncStatusWords * sizeof(int32_t), st));
+    HIP_TRY(launch_encode(e->table.as<EncodeParams>(), static_cast<int>(n), max_blocks, lds, st));
+    HIP_TRY(hipMemcpyAsync(e->status_host.p, e->status_dev.p, n * kEncStatusWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    e->last_stream = st;
+    e->in_flight = true;
+    e->n_run = n;
+    if (std::find(e->streams.begin(), e->streams.end(), st) == e->streams.end()) e->streams.push_back(st);
+    return CCD_OK;
+}
+
+int ccd_enc_wait(ccd_enc* e, void* stream) {
+    if (!e) return CCD_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    if (e->in_flight) {
+        if (e->last_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        e->in_flight = false;
+        const int32_t* hs = e->status_host.as<int32_t>();
+        for (size_t i = 0; i < e->n_run; ++i) {
+            EncSlot& s = *e->slots[i];
+            s.ran = true;
+            s.status = hs[i * kEncStatusWords];
+            s.n_words = s.status == CCD_OK ? static_cast<uint32_t>(hs[i * kEncStatusWords + 1]) : 0;
+        }
+    }
+    for (size_t i = 0; i < e->n_run; ++i) if (e->slots[i]->status < 0) return e->slots[i]->status;
+    return CCD_OK;
+}
+
+int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8) {
+    if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    if (out8) std::memcpy(out8, e->status_host.as<int32_t>() + static_cast<size_t>(slot) * kEncStatusWords, kEncStatusWords * sizeof(int32_t));
+    return e->slots[slot]->status;
+}
+
+int64_t ccd_enc_slot_payload(const ccd_enc* e, int slot, const uint8_t** device_ptr) {
+    if (!e || !device_ptr || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    const EncSlot& s = *e->slots[slot];
+    if (s.status < 0) return s.status;
+    *device_ptr = s.out.as<uint8_t>();
+    return static_cast<int64_t>(s.n_words) * 4;
+}
+
+int64_t ccd_enc_slot_bytes(ccd_enc* e, int slot, uint8_t** out) {
+    if (!e || !out || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    const EncSlot& s = *e->slots[slot];
+    if (s.status < 0) return s.status;
+    ccd_cc_header h = s.hdr;
+    h.n_bytes_latent = static_cast<int32_t>(s.n_words * 4);
+    uint8_t hb[256];
+    const int n_hb = ccd_write_cc_header(&h, hb, sizeof(hb));
+    if (n_hb < 0) return n_hb;
+    const size_t n_lat = static_cast<size_t>(s.n_words) * 4, total = static_cast<size_t>(n_hb) + s.nn.size() + n_lat;
+    uint8_t* p = static_cast<uint8_t*>(std::malloc(total + 4));
+    if (!p) return CCD_ERR_NOMEM;
+    std::memcpy(p, hb, static_cast<size_t>(n_hb));
+    std::memcpy(p + n_hb, s.nn.data(), s.nn.size());
+    // (the words are little-endian in memory, which is the byte order of the stream)
+    if (hipSetDevice(e->device) != hipSuccess ||
+        (n_lat && hipMemcpy(p + n_hb + s.nn.size(), s.out.p, n_lat, hipMemcpyDeviceToHost) != hipSuccess)) {
+        std::free(p);
+        return CCD_ERR_HIP;
+    }
+    *out = p;
+    return static_cast<int64_t>(total);
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ccd_device.hpp"
+#include "ccd_kernels.hpp"
 #include "ccd_laplace.hpp"
 
 namespace ccd {

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "ccd_device.hpp"
+#include "ccd_kernels.hpp"
 #include "ccd_laplace.hpp"
 
 namespace ccd {
@@ -1055,7 +1056,7 @@ __device__ __forceinline__ void mad64(int64_t& acc, int32_t x, int32_t w) {
 // byte products with i + j = s accumulate in one i32 tile (|partial| < 2^21) and the tiles are recombined with 64-bit
 // shift-adds, so the result is the int64 sum of armint.py:180-203 exactly.  Lane l = 16 g + n holds pixel n; the accumulator
 // of rows 4 g + r lands in lane group g, register r - which is where the next layer's B operand wants it when tile 1 puts
-// neurons 16..19 at rows 0, 4, 8, 12: no cross-lane movement between layers.  Envelope (host: ccd_api.cpp): `narrow`
+// neurons 16..19 at rows 0, 4, 8, 12: no cross-lane movement between layers.  Envelope (host: ccd_batch_plan.cpp): `narrow`
 // (so |IFCE feature| < 2^15: two bytes), dim <= 20, <= 8 IFCE features, |weight| < 2^23 (three bytes).  Hidden activations
 // travel as three bytes; a task that meets one >= 2^23 (128.0 in Q16; never seen on real streams; EntropyParams::mfma holds
 // the exponent so that tests can lower it) is redone

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "ccd_device.hpp"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
 

@@ -1,10 +1,9 @@
 // ccd_fused.hip - host side of the fused float kernel (ccd_fused_kernel.inc) and its kFdWhole instantiations (the whole
 // pyramid per tile); the kFdPre / kFdPyr instantiations (level-1 stack from a pyramid launch) live in ccd_fused_pre.hip.
 #include "ccd_fused_kernel.inc"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
-
-int fused_dec_profile_pre(unsigned long long* out16, int reset);  // ccd_fused_pre.hip
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 int fused_dec_profile(unsigned long long* out16, int reset) {
@@ -59,8 +58,6 @@ static hipError_t launch_fd_c(int c, const FusedDec* d_frames, const FdWork* d_w
         default: return hipErrorInvalidValue;
     }
 }
-
-hipError_t launch_fused_dec_pre(const FusedDec* d_frames, const void* d_work, int n_work, int c_in, int c, size_t lds_bytes, hipStream_t stream);  // ccd_fused_pre.hip
 
 // All frames of one launch share (c_in, c, pre); `d_work` lists (frame, first tile, tile count) per workgroup.
 hipError_t launch_fused_dec(const FusedDec* d_frames, const void* d_work, int n_work, int c_in, int c, int pre, size_t lds_bytes, hipStream_t stream) {

@@ -3,6 +3,7 @@
 // 17-54; the planes themselves come from ccd_float.hip::cr_noise_kernel + the bicubic x2 chain in stage 1).  Three output
 // channels (pictures), 5 .. 9 levels.  A translation unit of its own: compiles next to the other two.
 #include "ccd_fused_kernel.inc"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
 

@@ -3,6 +3,7 @@
 // level-1 footprint and run level 0 + synthesis.  A translation unit of its own so that the sets of instantiations compile in
 // parallel.
 #include "ccd_fused_kernel.inc"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
 

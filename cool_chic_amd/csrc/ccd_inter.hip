@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ccd_device.hpp"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
 
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(256) void inter_recon_kernel(InterParams p) {
 // everything then waits for the I frames.  The f64 sin / cos of the sinc window - 64 evaluations per pixel and reference pair - only
 // depend on the flows, so ccd_decode_video CAN compute them in that gap (CCD_VIDEO_COEF_MB: inter_coef8_kernel, 16 coefficients per
 // pixel and reference, 64 B) and only gather behind the references (inter_apply8_kernel).  Same functions, same operation order:
-// bit-identical to the one-kernel form.  Measured: the gather alone is 0.26 of the 0.34 ms - off by default (ccd_api.cpp).
+// bit-identical to the one-kernel form.  Measured: the gather alone is 0.26 of the 0.34 ms - off by default (ccd_video.cpp).
 // coef layout: float4 [ref][4][H * W] - quad 0 / 1 = cx[0..3] / cx[4..7], quad 2 / 3 = cy: every access a coalesced 16 bytes per lane.
 __global__ __launch_bounds__(256) void inter_coef8_kernel(const float* __restrict__ motion, int H, int W, int n_refs, float4* __restrict__ coef) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -383,7 +384,7 @@ hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const in
     return hipGetLastError();
 }
 
-// ---- a kernel that only takes time: ccd_api.cpp measures with it which of the library's side streams run concurrently
+// ---- a kernel that only takes time: ccd_runtime.cpp measures with it which of the library's side streams run concurrently
 __global__ void spin_kernel(unsigned long long ticks) {
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     while (__builtin_amdgcn_s_memtime() - t0 < ticks) __builtin_amdgcn_s_sleep(8);

@@ -1,0 +1,73 @@
+// ccd_kernels.hpp - the one declaration of every host-callable function a .hip file defines (launch_quality: ccd_quality.hpp).
+// Included by the host files that call them AND by the .hip files that define them, so that a definition which drifts from its
+// declaration no longer matches it: the call site is left with an undefined symbol and the link (-Wl,--no-undefined) fails.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "ccd_device.hpp"
+
+namespace ccd {
+// ccd_entropy.hip
+size_t entropy_lds_bytes(int dim, int arm_len);
+hipError_t launch_entropy(const EntropyParams* d_slots, int n_slots, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_laplace_bounds(const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* sym,
+                                 const float* scale_table, int64_t n, uint32_t* left, uint32_t* right, hipStream_t stream);
+hipError_t launch_laplace_sweep_generic(const float* scale_table, int scale_first, int n_scales, uint32_t* out, hipStream_t stream);
+// ccd_entropy_pipe.hip
+size_t entropy_pipe_lds_bytes(int dim, int n_layers, int ring_rows, int mfma);
+int entropy_pipe_ring_rows(int max_grid_w);
+bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narrow, int max_grid_w, long long max_abs_weight);
+bool entropy_pipe_supports(int dim, int n_layers, int narrow, int max_grid_w);
+hipError_t launch_entropy_pipe(const EntropyParams* d_slots, int n_slots, int nv, int mfma, int dyn, int shape, size_t lds_bytes, hipStream_t stream);
+int entropy_pipe_fixed_shape(int dim, int n_layers, int n_spatial);
+hipError_t launch_laplace_sweep_pipe(const float* scale_table, const double* rcp_table, int scale_first, int n_scales, uint32_t* out, hipStream_t stream);
+// ccd_float.hip
+hipError_t launch_upsample_step(const UpsampleLevel* d_levels, const uint32_t* d_zmap, int n_z, int max_w, int max_h, hipStream_t stream);
+hipError_t launch_i8_to_f32(const int8_t* in, float* out, size_t n, hipStream_t stream);
+hipError_t launch_syn_layer(const float* in, const float* in2, const float* wt, const float* bias, float* out, int c_in,
+                            int c_out, int k, int residual, int relu, int h, int w, hipStream_t stream);
+hipError_t launch_resize_nearest(const float* in, float* out, int c, int h_in, int w_in, int h_out, int w_out,
+                                 hipStream_t stream);
+hipError_t launch_resize_interp(const float* in, float* out, int c, int h_in, int w_in, int h_out, int w_out, int cubic,
+                                float scale_y, float scale_x, hipStream_t stream);
+hipError_t launch_final_resize(const float* in, float* out, int c, int h_in, int w_in, int h_out, int w_out, int mode,
+                               hipStream_t stream);
+hipError_t launch_cr_noise(float* out, size_t n, hipStream_t stream);
+hipError_t launch_planes(const float* src, void* p0, void* p1, void* p2, int h, int w, int bitdepth, int frame_data_type,
+                         hipStream_t stream);
+hipError_t launch_widen_u8(const uint8_t* in, uint16_t* out, size_t n, hipStream_t stream);
+// ccd_synth_fused.hip
+bool syn_fused_supports(int c_in, int c, int halo);
+void syn_fused_tiles(int h, int w, int halo, int* tiles_x, int* tiles_y);
+hipError_t launch_syn_fused(const SynthFused* d_frames, int n_frames, int c_in, int c, int max_tiles_x, int max_tiles_y,
+                            hipStream_t stream);
+// ccd_fused.hip, ccd_fused_pre.hip, ccd_fused_cr.hip
+bool fused_dec_supports(int c_in, int c);
+size_t fused_dec_lds_bytes(int n_lv, int c, int n_conv, int n_params, int pre);
+void fused_dec_param_shape(int c_in, int c, int* nwv, int* nws, int* nwc, int* nwo);
+hipError_t launch_fused_dec(const FusedDec* d_frames, const void* d_work, int n_work, int c_in, int c, int pre, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_fused_dec_pre(const FusedDec* d_frames, const void* d_work, int n_work, int c_in, int c, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_fused_pyramid(const FusedDec* d_frames, const void* d_work, int n_work, int levels, size_t lds_bytes, hipStream_t stream);
+size_t fused_pyr_lds_bytes(int n_lv);
+bool fused_dec_cr_supports(int c_in, int c);
+hipError_t launch_fused_dec_cr(const FusedDec* d_frames, const void* d_work, int n_work, int c_in, int c, size_t lds_bytes, hipStream_t stream);
+int fused_dec_profile(unsigned long long* out16, int reset);
+int fused_dec_profile_pre(unsigned long long* out16, int reset);
+// ccd_inter.hip
+hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, float* out, int h, int w, int bitdepth,
+                                int frame_data_type, hipStream_t stream);
+hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const int* gflow, const float* residue, const float* motion,
+                              const float* ref0, const float* ref1, float* out, hipStream_t stream);
+size_t inter_coef_bytes(int frame_type, int h, int w);
+hipError_t launch_inter_coef8(int frame_type, int h, int w, const float* motion, void* coef, hipStream_t stream);
+hipError_t launch_inter_apply8(int frame_type, int h, int w, const int* gflow, const float* residue, const float* motion, const float* ref0,
+                               const float* ref1, const void* coef, float* out, hipStream_t stream);
+hipError_t launch_spin(unsigned long long ticks, hipStream_t stream);
+// ccd_encode.hip
+size_t encode_contexts_lds_bytes(int dim);
+int encode_block_threads();
+hipError_t launch_encode(const EncodeParams* d_slots, int n_slots, unsigned max_blocks, size_t lds_bytes, hipStream_t stream);
+}  // namespace ccd

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(64) void quality_final_kernel(QualityBatch B) {
 
 }  // namespace
 
-// Enqueues the scoring of a planned batch (ccd_api.cpp builds the tables).  n_sse_tiles == 0: no squared error asked for.
+// Enqueues the scoring of a planned batch (ccd_quality_api.cpp builds the tables).  n_sse_tiles == 0: no squared error asked for.
 hipError_t launch_quality(const QualityBatch& B, uint32_t n_sse_tiles, hipStream_t stream) {
     if (n_sse_tiles) hipLaunchKernelGGL(quality_sse_kernel, dim3(n_sse_tiles), dim3(kThreads), 0, stream, B);
     for (int j = 0; j < kQScales; ++j) {

@@ -1,5 +1,6 @@
-// ccd_quality.hpp - tables shared between ccd_quality_* (ccd_api.cpp) and the kernels of ccd_quality.hip.
+// ccd_quality.hpp - tables shared between ccd_quality_* (ccd_quality_api.cpp) and the kernels of ccd_quality.hip.
 #pragma once
+#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 
@@ -42,5 +43,7 @@ struct QualityBatch {    // kernel argument
     QualityOut* out;             // [n_planes]
     double g[kQWin];             // the window, normalised to sum 1
 };
+
+hipError_t launch_quality(const QualityBatch& B, uint32_t n_sse_tiles, hipStream_t stream);  // ccd_quality.hip
 
 }  // namespace ccd

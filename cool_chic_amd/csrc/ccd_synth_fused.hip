@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ccd_device.hpp"
+#include "ccd_kernels.hpp"
 
 namespace ccd {
 

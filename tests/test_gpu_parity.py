@@ -1555,7 +1555,7 @@ def test_bench_plain_run_and_dumped_outputs(tmp_path, oracle):
 
 def test_pooled_blocks_are_recycled_and_results_stay_exact(gpu, oracle):
     """A batch per image set is the normal use: arenas and pinned staging blocks of destroyed batches serve the next one
-    (BlockPool, ccd_api.cpp).  Thirty create / add / run / all_planes / destroy cycles over streams of different sizes and
+    (BlockPool, ccd_runtime.cpp).  Thirty create / add / run / all_planes / destroy cycles over streams of different sizes and
     kinds, a failed decode (its blocks must come back too) and ccd_pool_trim in between: planes always equal the oracle's,
     device memory does not grow, and a batch may be grown and re-run after a first run."""
     import torch
