@@ -16,15 +16,17 @@
 //
 // Kernels (all HBM traffic is one read of the planes, one write + one read of the scanlines, one write of the file):
 //   png_filter_huff_kernel  one workgroup per deflate block: filter choice, scanlines, per-row Adler sums, histogram in
-//                           LDS, bitonic sort of the used symbols, code lengths + canonical codes, bits of the block
-//   png_emit_kernel         one workgroup per deflate block: block start = sum of the previous blocks' bits; scanlines
-//                           staged in LDS, per-thread bit counts, scan, bit packing (whole words stored, the two
-//                           boundary words of a thread merged with atomicOr into the zeroed file)
+//                           LDS, code lengths + canonical codes (huff_code), bits of the block
+//   png_emit_kernel         one workgroup per deflate block (emit_block): block start = sum of the previous blocks'
+//                           bits; scanlines staged in LDS, per-thread bit counts, scan, bit packing (BitWriter: whole
+//                           words stored, the two boundary words of a thread merged with atomicOr into the zeroed file)
 //   (level 1: png_lz77_match_kernel + png_lz77_parse_kernel between these two, png_emit_lz77_kernel after the second;
 //    see the level-1 section below)
 //   png_trailer_kernel      container bytes, Adler-32 from the row sums
 //   png_crc_kernel          CRC-32 of the IDAT chunk as XOR of 512-byte chunk CRCs multiplied by x^(8 * bytes behind)
 //   png_crc_final_kernel    stores the CRC, the IEND chunk and the file size
+// Shared by both levels, each written once: the block of a workgroup (block_ctx), the length-limited canonical code
+// (huff_code), the block header (emit_block_header), the token codes (for_token_codes) and the bit packer (BitWriter).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -86,6 +88,29 @@ __device__ __forceinline__ int find_image(const uint32_t* prefix, int n, uint32_
     return lo;
 }
 
+// the deflate block of this workgroup (the five per-block kernels run one workgroup per block of every picture)
+struct BlockCtx {
+    PngJob J;
+    int k;           // block of the picture
+    int N;           // bytes per scanline
+    int y_lo, y_hi;  // rows of the block
+    int nb;          // bytes of the block
+    size_t off;      // first byte of the block in scan / prev / lz
+};
+
+__device__ __forceinline__ BlockCtx block_ctx(const PngBatch& B) {
+    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
+    BlockCtx C;
+    C.J = B.img[im];
+    C.k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
+    C.N = 3 * C.J.w + 1;
+    C.y_lo = C.k * C.J.rows;
+    C.y_hi = min(C.J.h, C.y_lo + C.J.rows);
+    C.nb = (C.y_hi - C.y_lo) * C.N;
+    C.off = static_cast<size_t>(C.y_lo) * C.N;
+    return C;
+}
+
 __device__ __forceinline__ int abs_res(int v) { v &= 255; return v < 128 ? v : 256 - v; }
 
 __device__ __forceinline__ int paeth(int a, int b, int c) {
@@ -106,35 +131,161 @@ __device__ __forceinline__ int filt_one(int f, int x, int a, int b, int c) {
 
 __device__ __forceinline__ uint32_t rev_bits(uint32_t v, int n) { return __brev(v) >> (32 - n); }
 
+// ---- length-limited canonical Huffman code over up to 512 symbols: the one construction of both levels ------------------
+struct HuffLds {
+    uint32_t key[512], A[512], par[512], dep[512], cnt[514];
+    uint32_t num[kMaxBits + 1], first[kMaxBits + 1], base[kMaxBits + 1];
+    uint32_t m;
+};
+
+// ascending sort of key[512] in LDS by the whole workgroup (behind a barrier that completes key; ends with one)
+template <int kThreads>
+__device__ __forceinline__ void bitonic_sort_512(uint32_t* key) {
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= 512; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < 512; t += kThreads) {
+                const int partner = t ^ stride;
+                if (partner > t) {
+                    const uint32_t a = key[t], b = key[partner];
+                    const bool up = (t & size) == 0;
+                    if ((a > b) == up) { key[t] = b; key[partner] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// hist[nsym] -> lens[nsym], codes[nsym] (bit-reversed code | length << 16).  Called by every thread of the workgroup,
+// behind a barrier that completes hist; lens must be in LDS, codes may be anywhere.  The tree's depths take one
+// internal node per thread: at most kThreads + 1 symbols may be used (level 0: 257 with 256 threads, exactly the limit).
+template <int kThreads>
+__device__ void huff_code(const uint32_t* hist, int nsym, uint32_t* lens, uint32_t* codes, HuffLds& S) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 514; i += kThreads) S.cnt[i] = 0;
+    for (int i = tid; i < nsym; i += kThreads) lens[i] = 0;
+    if (tid <= kMaxBits) S.num[tid] = 0;
+    if (tid == 0) S.m = 0;
+    __syncthreads();
+    // ---- used symbols sorted by (count, symbol)
+    for (int t = tid; t < 512; t += kThreads) {
+        uint32_t key = 0xFFFFFFFFu;
+        if (t < nsym && hist[t] > 0) { key = (hist[t] << 9) | static_cast<uint32_t>(t); atomicAdd(&S.m, 1u); }
+        S.key[t] = key;
+    }
+    __syncthreads();
+    bitonic_sort_512<kThreads>(S.key);
+    const int m = static_cast<int>(S.m);
+    if (m >= 2) {
+        // ---- Huffman tree over the sorted symbols (one lane: the two-queue merge is sequential; at most 512 symbols).
+        // Moffat-Katajainen phase 1, in place on the ascending counts: afterwards A[i] is the parent of internal node i.
+        if (tid == 0) {
+            uint32_t* A = S.A;
+            for (int i = 0; i < m; ++i) A[i] = S.key[i] >> 9;
+            A[0] += A[1];
+            int root = 0, leaf = 2;
+            for (int nxt = 1; nxt < m - 1; ++nxt) {
+                if (leaf >= m || A[root] < A[leaf]) { A[nxt] = A[root]; A[root++] = nxt; }
+                else A[nxt] = A[leaf++];
+                if (leaf >= m || (root < nxt && A[root] < A[leaf])) { A[nxt] += A[root]; A[root++] = nxt; }
+                else A[nxt] += A[leaf++];
+            }
+        }
+        __syncthreads();
+        // ---- depth of the internal nodes 0 .. m-2 (node m-2 is the root) by pointer jumping, one node per thread
+        const int ni = m - 1;
+        uint32_t par = 0, dep = 0;
+        if (tid < ni) {
+            par = tid == ni - 1 ? static_cast<uint32_t>(tid) : S.A[tid];
+            dep = tid == ni - 1 ? 0u : 1u;
+            S.par[tid] = par; S.dep[tid] = dep;
+        }
+        __syncthreads();
+        for (int r = 0; r < 9; ++r) {  // 2^9 > 511 levels
+            uint32_t pd = 0, pp = 0;
+            if (tid < ni) { pd = S.dep[par]; pp = S.par[par]; }
+            __syncthreads();
+            if (tid < ni) { dep += pd; par = pp; S.dep[tid] = dep; S.par[tid] = par; }
+            __syncthreads();
+        }
+        // ---- leaves per depth: the two children of every internal node at depth d - 1 are the internal nodes and the
+        // leaves at depth d.  Sorted by count the leaves have non-increasing depths, so the counts per length are all
+        // that is needed.  Limit to 15 bits: longer codes are folded into the limit here, the Kraft excess is worked
+        // off below.
+        if (tid < ni) atomicAdd(&S.cnt[dep], 1u);
+        __syncthreads();
+        for (int t = tid; t < 512; t += kThreads) {
+            const int d = t + 1;
+            const uint32_t leaves = 2u * S.cnt[d - 1] - S.cnt[d];
+            if (leaves) atomicAdd(&S.num[min(d, kMaxBits)], leaves);
+        }
+        __syncthreads();
+    } else if (tid == 0 && m == 1) {
+        S.num[1] = 1;  // a single symbol: one code of length 1 (RFC 1951 allows an incomplete distance code)
+    }
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int l = 1; l <= kMaxBits; ++l) total += S.num[l] << (kMaxBits - l);
+        while (m >= 2 && total != (1u << kMaxBits)) {
+            S.num[kMaxBits]--;
+            for (int l = kMaxBits - 1; l > 0; --l)
+                if (S.num[l]) { S.num[l]--; S.num[l + 1] += 2; break; }
+            --total;
+        }
+        // rarest symbols take the longest codes: sorted positions [first[l], first[l] + num[l]) get length l;
+        // canonical codes (RFC 1951 3.2.2): first code of every length
+        uint32_t first = 0, code = 0;
+        for (int l = kMaxBits; l > 0; --l) { S.first[l] = first; first += S.num[l]; }
+        for (int bits = 1; bits <= kMaxBits; ++bits) {
+            code = (code + (bits > 1 ? S.num[bits - 1] : 0u)) << 1;
+            S.base[bits] = code;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < m; j += kThreads) {
+        int l = kMaxBits;
+        while (static_cast<uint32_t>(j) >= S.first[l] + S.num[l]) --l;
+        lens[S.key[j] & 511u] = static_cast<uint32_t>(l);
+    }
+    __syncthreads();
+    // ---- canonical codes: within a length, symbols in increasing order
+    for (int sy = tid; sy < nsym; sy += kThreads) {
+        const uint32_t l = lens[sy];
+        uint32_t v = 0;
+        if (l) {
+            uint32_t rank = 0;
+            for (int q = 0; q < sy; ++q) rank += lens[q] == l ? 1u : 0u;
+            v = rev_bits(S.base[l] + rank, static_cast<int>(l)) | (l << 16);
+        }
+        codes[sy] = v;
+    }
+    __syncthreads();
+}
+
 // ---- kernel A -----------------------------------------------------------------------------------------------------
 constexpr int kThreadsA = 256;   // 1024 threads: single pictures 10-20 % faster, batches and 4K 2x slower (occupancy; measured)
 
 __global__ __launch_bounds__(kThreadsA) void png_filter_huff_kernel(PngBatch B) {
     __shared__ uint32_t s_hist[257];
-    __shared__ uint32_t s_key[512];
     __shared__ uint32_t s_len[257];
-    __shared__ uint32_t s_A[257];   // scratch of the code-length construction
     __shared__ unsigned long long s_red[kThreadsA / 64][8];
-    __shared__ uint32_t s_m, s_sum;
-    __shared__ uint32_t s_num[kMaxBits + 1], s_first[kMaxBits + 1], s_base[kMaxBits + 1];
-    __shared__ uint32_t s_par[256], s_dep[256], s_cnt[258];
+    __shared__ uint32_t s_sum;
+    __shared__ HuffLds s_h;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
-    const PngJob J = B.img[im];
-    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
-    const int w = J.w, n = 3 * w, N = n + 1;
+    const BlockCtx C = block_ctx(B);
+    const PngJob& J = C.J;
+    const int k = C.k, w = J.w, N = C.N;
     {   // this block's share of the file is cleared here (the bit packer of the next kernel merges into zeroed words)
         const uint32_t share = (J.zero_words + J.nblk - 1) / J.nblk;
         const uint32_t z_lo = min(J.zero_words, static_cast<uint32_t>(k) * share), z_hi = min(J.zero_words, z_lo + share);
         for (uint32_t i = z_lo + tid; i < z_hi; i += kThreadsA) J.out[i] = 0;
         if (k == 0 && tid < 8) J.meta[tid] = 0;
     }
-    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
-    for (int i = tid; i < 258; i += kThreadsA) { s_cnt[i] = 0; if (i < 257) { s_hist[i] = 0; s_len[i] = 0; } }
-    if (tid == 0) { s_m = 0; s_sum = 0; }
-    if (tid <= kMaxBits) s_num[tid] = 0;
+    for (int i = tid; i < 257; i += kThreadsA) s_hist[i] = 0;
+    if (tid == 0) s_sum = 0;
     __syncthreads();
-    for (int y = y_lo; y < y_hi; ++y) {
+    for (int y = C.y_lo; y < C.y_hi; ++y) {
         // ---- pass 1: cost of the five filters
         unsigned long long cost[5] = {0, 0, 0, 0, 0};
         for (int x = tid; x < w; x += kThreadsA) {
@@ -206,199 +357,15 @@ __global__ __launch_bounds__(kThreadsA) void png_filter_huff_kernel(PngBatch B) 
         }
         __syncthreads();
     }
-    // ---- used symbols sorted by (count, symbol)
+    // ---- code of the block's 257 symbols (a filter byte and end-of-block at least: never fewer than two used symbols)
     if (tid == 0) s_hist[256] = 1;
     __syncthreads();
-    for (int t = tid; t < 512; t += kThreadsA) {
-        uint32_t key = 0xFFFFFFFFu;
-        if (t < 257 && s_hist[t] > 0) { key = (s_hist[t] << 9) | static_cast<uint32_t>(t); atomicAdd(&s_m, 1u); }
-        s_key[t] = key;
-    }
-    __syncthreads();
-    for (int size = 2; size <= 512; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < 512; t += kThreadsA) {
-                const int partner = t ^ stride;
-                if (partner > t) {
-                    const uint32_t a = s_key[t], b = s_key[partner];
-                    const bool up = (t & size) == 0;
-                    if ((a > b) == up) { s_key[t] = b; s_key[partner] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // ---- Huffman tree over the sorted symbols (one lane: the two-queue merge is sequential; at most 257 symbols).
-    // Moffat-Katajainen phase 1, in place on the ascending counts: afterwards s_A[i] is the parent of internal node i.
-    const int m = static_cast<int>(s_m);
-    if (tid == 0) {
-        uint32_t* A = s_A;
-        for (int i = 0; i < m; ++i) A[i] = s_key[i] >> 9;
-        A[0] += A[1];
-        int root = 0, leaf = 2;
-        for (int nxt = 1; nxt < m - 1; ++nxt) {
-            if (leaf >= m || A[root] < A[leaf]) { A[nxt] = A[root]; A[root++] = nxt; }
-            else A[nxt] = A[leaf++];
-            if (leaf >= m || (root < nxt && A[root] < A[leaf])) { A[nxt] += A[root]; A[root++] = nxt; }
-            else A[nxt] += A[leaf++];
-        }
-    }
-    __syncthreads();
-    // ---- depth of the internal nodes 0 .. m-2 (node m-2 is the root) by pointer jumping, one node per thread
-    const int ni = m - 1;
-    uint32_t par = 0, dep = 0;
-    if (tid < ni) {
-        par = tid == ni - 1 ? static_cast<uint32_t>(tid) : s_A[tid];
-        dep = tid == ni - 1 ? 0u : 1u;
-        s_par[tid] = par; s_dep[tid] = dep;
-    }
-    __syncthreads();
-    for (int r = 0; r < 9; ++r) {  // 2^9 > 256 levels
-        uint32_t pd = 0, pp = 0;
-        if (tid < ni) { pd = s_dep[par]; pp = s_par[par]; }
-        __syncthreads();
-        if (tid < ni) { dep += pd; par = pp; s_dep[tid] = dep; s_par[tid] = par; }
-        __syncthreads();
-    }
-    // ---- leaves per depth: the two children of every internal node at depth d - 1 are the internal nodes and the leaves at
-    // depth d.  Sorted by count the leaves have non-increasing depths, so the counts per length are all that is needed.
-    // Limit to 15 bits: longer codes are folded into the limit, then the Kraft excess is worked off.
-    if (tid < ni) atomicAdd(&s_cnt[dep], 1u);
-    __syncthreads();
-    if (tid < 256) {
-        const int d = tid + 1;  // 1 .. 256
-        const uint32_t leaves = 2u * s_cnt[d - 1] - s_cnt[d];
-        if (leaves) atomicAdd(&s_num[min(d, kMaxBits)], leaves);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int l = 1; l <= kMaxBits; ++l) total += s_num[l] << (kMaxBits - l);
-        while (total != (1u << kMaxBits)) {
-            s_num[kMaxBits]--;
-            for (int l = kMaxBits - 1; l > 0; --l)
-                if (s_num[l]) { s_num[l]--; s_num[l + 1] += 2; break; }
-            --total;
-        }
-        // rarest symbols take the longest codes: sorted positions [s_first[l], s_first[l] + num[l]) get length l;
-        // canonical codes (RFC 1951 3.2.2): first code of every length
-        uint32_t first = 0, code = 0;
-        for (int l = kMaxBits; l > 0; --l) { s_first[l] = first; first += s_num[l]; }
-        for (int bits = 1; bits <= kMaxBits; ++bits) {
-            code = (code + (bits > 1 ? s_num[bits - 1] : 0u)) << 1;
-            s_base[bits] = code;
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < m; j += kThreadsA) {
-        int l = kMaxBits;
-        while (static_cast<uint32_t>(j) >= s_first[l] + s_num[l]) --l;
-        s_len[s_key[j] & 511u] = static_cast<uint32_t>(l);
-    }
-    __syncthreads();
-    // ---- canonical codes: within a length, symbols in increasing order
-    for (int sy = tid; sy < 257; sy += kThreadsA) {
-        const uint32_t l = s_len[sy];
-        uint32_t v = 0;
-        if (l) {
-            uint32_t rank = 0;
-            for (int q = 0; q < sy; ++q) rank += s_len[q] == l ? 1u : 0u;
-            v = rev_bits(s_base[l] + rank, static_cast<int>(l)) | (l << 16);
-        }
-        J.codes[static_cast<size_t>(k) * 257 + sy] = v;
-        atomicAdd(&s_sum, s_hist[sy] * l);
-    }
+    huff_code<kThreadsA>(s_hist, 257, s_len, J.codes + static_cast<size_t>(k) * 257, s_h);
+    uint32_t part = 0;
+    for (int sy = tid; sy < 257; sy += kThreadsA) part += s_hist[sy] * s_len[sy];
+    atomicAdd(&s_sum, part);
     __syncthreads();
     if (tid == 0) J.blk_bits[k] = kHeaderBits + s_sum;
-}
-
-// ---- kernel B -----------------------------------------------------------------------------------------------------
-constexpr int kThreadsB = 256;
-
-__device__ __forceinline__ void or_bits(uint32_t* out, uint64_t pos, uint32_t value, int nbits) {
-    if (nbits == 0) return;
-    const uint64_t v = static_cast<uint64_t>(value) << (pos & 31);
-    atomicOr(&out[pos >> 5], static_cast<uint32_t>(v));
-    if ((pos & 31) + nbits > 32) atomicOr(&out[(pos >> 5) + 1], static_cast<uint32_t>(v >> 32));
-}
-
-__global__ __launch_bounds__(kThreadsB) void png_emit_kernel(PngBatch B) {
-    __shared__ uint8_t s_data[kStageBytes];
-    __shared__ uint32_t s_code[257];
-    __shared__ unsigned long long s_part[kThreadsB / 64];
-    __shared__ uint32_t s_scan[kThreadsB];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
-    const PngJob J = B.img[im];
-    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
-    const int N = 3 * J.w + 1;
-    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
-    const int nb = (y_hi - y_lo) * N;
-    // start of the block = bits of all blocks before it
-    unsigned long long before = 0;
-    for (int i = tid; i < k; i += kThreadsB) before += J.blk_bits[i];
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
-    if (lane == 0) s_part[wave] = before;
-    for (int i = tid; i < 257; i += kThreadsB) s_code[i] = J.codes[static_cast<size_t>(k) * 257 + i];
-    {   // scanlines of the block -> LDS (4-byte words where the block start allows it)
-        const uint8_t* src = J.scan + static_cast<size_t>(y_lo) * N;
-        for (int i = tid; i < nb; i += kThreadsB) s_data[i] = src[i];
-    }
-    __syncthreads();
-    before = 0;
-    for (int q = 0; q < kThreadsB / 64; ++q) before += s_part[q];
-    const uint32_t my_bits = J.blk_bits[k];
-    const uint64_t start = static_cast<uint64_t>(kDataStart) * 8 + before;
-    if (k == J.nblk - 1 && tid == 0) J.meta[0] = static_cast<uint32_t>(before + my_bits);
-    if (start + my_bits + 256 > J.cap_bits) {  // 20 container bytes follow the last block
-        if (tid == 0) J.meta[4] = 1;  // never with a buffer of ccd_png_bound() bytes
-        return;
-    }
-    if (J.lz_flag && J.lz_flag[k]) return;  // level 1: png_emit_lz77_kernel writes this block
-    // ---- block header
-    if (tid == 0) {
-        const uint32_t final_blk = k == J.nblk - 1 ? 1u : 0u;
-        or_bits(J.out, start, final_blk | (2u << 1) | (0u << 3) | (0u << 8) | (15u << 13), 17);
-        const uint32_t eob = s_code[256];
-        or_bits(J.out, start + my_bits - (eob >> 16), eob & 0xFFFFu, static_cast<int>(eob >> 16));
-    }
-    if (tid < 19) or_bits(J.out, start + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);  // lengths of the code-length codes 16, 17, 18, then 0..15
-    for (int s = tid; s < 258; s += kThreadsB)
-        or_bits(J.out, start + 74 + 4 * s, rev_bits(s < 257 ? (s_code[s] >> 16) : 0u, 4), 4);
-    // ---- literals: contiguous chunk per thread
-    const int cb = (nb + kThreadsB - 1) / kThreadsB;
-    const int lo = min(nb, tid * cb), hi = min(nb, lo + cb);
-    uint32_t bits = 0;
-    for (int i = lo; i < hi; ++i) bits += s_code[s_data[i]] >> 16;
-    // exclusive scan over the workgroup
-    uint32_t incl = bits;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_scan[wave] = incl;
-    __syncthreads();
-    uint32_t offset = incl - bits;
-    for (int q = 0; q < wave; ++q) offset += s_scan[q];
-    uint64_t pos = start + kHeaderBits + offset;
-    uint32_t wi = static_cast<uint32_t>(pos >> 5);
-    int nacc = static_cast<int>(pos & 31);
-    uint64_t acc = 0;
-    bool first = true;
-    for (int i = lo; i < hi; ++i) {
-        const uint32_t c = s_code[s_data[i]];
-        acc |= static_cast<uint64_t>(c & 0xFFFFu) << nacc;
-        nacc += static_cast<int>(c >> 16);
-        if (nacc >= 32) {
-            if (first) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
-            else J.out[wi] = static_cast<uint32_t>(acc);  // every bit of this word belongs to this thread
-            first = false;
-            ++wi;
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-    if (nacc > 0 && acc != 0) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
 }
 
 // ---- level 1: LZ77 inside each deflate block --------------------------------------------------------------------
@@ -409,13 +376,14 @@ __global__ __launch_bounds__(kThreadsB) void png_emit_kernel(PngBatch B) {
 //           the nearest; < 3 is no match, length 3 farther than kFar3 is dropped.
 //   parse   lazy-1: next(i) = i + L(i) if L(i) >= 3 and L(i + 1) <= L(i), else i + 1 (a literal).
 //   code    dynamic Huffman, HLIT = 286, HDIST = 30, level 0's code-length code; both trees limited to 15 bits (the
-//           construction of png_filter_huff_kernel on up to 286 symbols; a single distance symbol gets length 1).
+//           construction of huff_code on up to 286 symbols; a single distance symbol gets length 1).
 //   choice  a block whose exact bit count is not below its level-0 count keeps the level-0 coding (png_emit_kernel).
-// Kernels, one workgroup per block, all between png_filter_huff_kernel and png_trailer_kernel:
+// Kernels, one workgroup per block, all between png_filter_huff_kernel and png_trailer_kernel (png_emit_kernel, the
+// level-0 half of emit_block below, runs between the second and the third):
 //   png_lz77_match_kernel  hash chains (prev[] in HBM scratch) and the best match of every position
 //   png_lz77_parse_kernel  lazy parse by pointer jumping over next(i), histograms, both code constructions, exact bit
 //                          counts, choice of the coding; the token of every position replaces its match
-//   png_emit_lz77_kernel   header, tokens (per-thread bit counts, scan, word packing as png_emit_kernel), end-of-block
+//   png_emit_lz77_kernel   emit_block for the blocks that take the matches: header, tokens, end-of-block
 constexpr int kCand = 8;
 constexpr int kWindow = 32768;
 constexpr int kFar3 = 4096;
@@ -456,13 +424,10 @@ __global__ __launch_bounds__(kThreadsM) void png_lz77_match_kernel(PngBatch B) {
     __shared__ uint8_t s_data[kStageBytes];
     __shared__ uint16_t s_head[kSegs][kBuckets];  // last position of every bucket in the wave's segment so far
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
-    const PngJob J = B.img[im];
-    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
-    const int N = 3 * J.w + 1;
-    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
-    const int n = (y_hi - y_lo) * N;
-    const size_t off = static_cast<size_t>(y_lo) * N;
+    const BlockCtx C = block_ctx(B);
+    const PngJob& J = C.J;
+    const int n = C.nb;
+    const size_t off = C.off;
     uint16_t* prev = J.prev + off;
     uint32_t* mt = J.lz + off;
     for (int i = tid; i < n; i += kThreadsM) s_data[i] = J.scan[off + i];
@@ -523,118 +488,6 @@ __global__ __launch_bounds__(kThreadsM) void png_lz77_match_kernel(PngBatch B) {
     }
 }
 
-// ---- length-limited canonical code over up to 512 symbols (png_filter_huff_kernel's construction, any alphabet)
-struct HuffLds {
-    uint32_t key[512], A[512], par[512], dep[512], cnt[514];
-    uint32_t num[kMaxBits + 1], first[kMaxBits + 1], base[kMaxBits + 1];
-    uint32_t m;
-};
-
-// hist[nsym] -> lens[nsym], codes[nsym] (bit-reversed code | length << 16).  Called by every thread of the workgroup.
-template <int kThreads>
-__device__ void huff_code(const uint32_t* hist, int nsym, uint32_t* lens, uint32_t* codes, HuffLds& S) {
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 514; i += kThreads) S.cnt[i] = 0;
-    for (int i = tid; i < nsym; i += kThreads) lens[i] = 0;
-    if (tid <= kMaxBits) S.num[tid] = 0;
-    if (tid == 0) S.m = 0;
-    __syncthreads();
-    for (int t = tid; t < 512; t += kThreads) {
-        uint32_t key = 0xFFFFFFFFu;
-        if (t < nsym && hist[t] > 0) { key = (hist[t] << 9) | static_cast<uint32_t>(t); atomicAdd(&S.m, 1u); }
-        S.key[t] = key;
-    }
-    __syncthreads();
-    for (int size = 2; size <= 512; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < 512; t += kThreads) {
-                const int partner = t ^ stride;
-                if (partner > t) {
-                    const uint32_t a = S.key[t], b = S.key[partner];
-                    const bool up = (t & size) == 0;
-                    if ((a > b) == up) { S.key[t] = b; S.key[partner] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int m = static_cast<int>(S.m);
-    if (m >= 2) {
-        if (tid == 0) {  // Moffat-Katajainen phase 1 (one lane), as in png_filter_huff_kernel
-            uint32_t* A = S.A;
-            for (int i = 0; i < m; ++i) A[i] = S.key[i] >> 9;
-            A[0] += A[1];
-            int root = 0, leaf = 2;
-            for (int nxt = 1; nxt < m - 1; ++nxt) {
-                if (leaf >= m || A[root] < A[leaf]) { A[nxt] = A[root]; A[root++] = nxt; }
-                else A[nxt] = A[leaf++];
-                if (leaf >= m || (root < nxt && A[root] < A[leaf])) { A[nxt] += A[root]; A[root++] = nxt; }
-                else A[nxt] += A[leaf++];
-            }
-        }
-        __syncthreads();
-        const int ni = m - 1;
-        uint32_t par = 0, dep = 0;
-        if (tid < ni) {
-            par = tid == ni - 1 ? static_cast<uint32_t>(tid) : S.A[tid];
-            dep = tid == ni - 1 ? 0u : 1u;
-            S.par[tid] = par; S.dep[tid] = dep;
-        }
-        __syncthreads();
-        for (int r = 0; r < 9; ++r) {  // 2^9 > 511 levels
-            uint32_t pd = 0, pp = 0;
-            if (tid < ni) { pd = S.dep[par]; pp = S.par[par]; }
-            __syncthreads();
-            if (tid < ni) { dep += pd; par = pp; S.dep[tid] = dep; S.par[tid] = par; }
-            __syncthreads();
-        }
-        if (tid < ni) atomicAdd(&S.cnt[dep], 1u);
-        __syncthreads();
-        for (int t = tid; t < 512; t += kThreads) {
-            const int d = t + 1;
-            const uint32_t leaves = 2u * S.cnt[d - 1] - S.cnt[d];
-            if (leaves) atomicAdd(&S.num[min(d, kMaxBits)], leaves);
-        }
-        __syncthreads();
-    } else if (tid == 0 && m == 1) {
-        S.num[1] = 1;  // a single symbol: one code of length 1 (RFC 1951 allows an incomplete distance code)
-    }
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int l = 1; l <= kMaxBits; ++l) total += S.num[l] << (kMaxBits - l);
-        while (m >= 2 && total != (1u << kMaxBits)) {
-            S.num[kMaxBits]--;
-            for (int l = kMaxBits - 1; l > 0; --l)
-                if (S.num[l]) { S.num[l]--; S.num[l + 1] += 2; break; }
-            --total;
-        }
-        uint32_t first = 0, code = 0;
-        for (int l = kMaxBits; l > 0; --l) { S.first[l] = first; first += S.num[l]; }
-        for (int bits = 1; bits <= kMaxBits; ++bits) {
-            code = (code + (bits > 1 ? S.num[bits - 1] : 0u)) << 1;
-            S.base[bits] = code;
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < m; j += kThreads) {
-        int l = kMaxBits;
-        while (static_cast<uint32_t>(j) >= S.first[l] + S.num[l]) --l;
-        lens[S.key[j] & 511u] = static_cast<uint32_t>(l);
-    }
-    __syncthreads();
-    for (int sy = tid; sy < nsym; sy += kThreads) {
-        const uint32_t l = lens[sy];
-        uint32_t v = 0;
-        if (l) {
-            uint32_t rank = 0;
-            for (int q = 0; q < sy; ++q) rank += lens[q] == l ? 1u : 0u;
-            v = rev_bits(S.base[l] + rank, static_cast<int>(l)) | (l << 16);
-        }
-        codes[sy] = v;
-    }
-    __syncthreads();
-}
-
 constexpr int kThreadsP = 1024;
 constexpr int kPerThreadP = kStageBytes / kThreadsP;  // positions per thread in the pointer jumping (48, in 24 pairs)
 constexpr int kJumpRounds = 16;                       // 2^16 > kStageBytes steps of next()
@@ -648,13 +501,10 @@ __global__ __launch_bounds__(kThreadsP) void png_lz77_parse_kernel(PngBatch B) {
     __shared__ HuffLds s_h;
     __shared__ uint32_t s_bits, s_lit_bits;  // bits of the LZ77 coding; of the level-0 coding (png_filter_huff_kernel)
     const int tid = threadIdx.x;
-    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
-    const PngJob J = B.img[im];
-    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
-    const int N = 3 * J.w + 1;
-    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
-    const int n = (y_hi - y_lo) * N;
-    const size_t off = static_cast<size_t>(y_lo) * N;
+    const BlockCtx C = block_ctx(B);
+    const PngJob& J = C.J;
+    const int k = C.k, n = C.nb;
+    const size_t off = C.off;
     uint32_t* mt = J.lz + off;
     for (int i = tid; i < kStageBytes / 32; i += kThreadsP) { s_mark[i] = i == 0 ? 1u : 0u; s_take[i] = 0; }
     __syncthreads();
@@ -741,104 +591,153 @@ __global__ __launch_bounds__(kThreadsP) void png_lz77_parse_kernel(PngBatch B) {
     }
 }
 
-__global__ __launch_bounds__(kThreadsB) void png_emit_lz77_kernel(PngBatch B) {
-    __shared__ uint8_t s_data[kStageBytes];
-    __shared__ uint32_t s_code[kNLL + kNDist];
-    __shared__ unsigned long long s_part[kThreadsB / 64];
-    __shared__ uint32_t s_scan[kThreadsB];
+// ---- kernel B: the bits of a block, both levels -------------------------------------------------------------------
+constexpr int kThreadsB = 256;
+
+// merges the low nbits of value into the zeroed file at bit pos (any thread, any position)
+__device__ __forceinline__ void or_bits(uint32_t* out, uint64_t pos, uint32_t value, int nbits) {
+    if (nbits == 0) return;
+    const uint64_t v = static_cast<uint64_t>(value) << (pos & 31);
+    atomicOr(&out[pos >> 5], static_cast<uint32_t>(v));
+    if ((pos & 31) + nbits > 32) atomicOr(&out[(pos >> 5) + 1], static_cast<uint32_t>(v >> 32));
+}
+
+// Bits of the deflate stream in front of block k = bits of all blocks before it.  Called by every thread; its barrier
+// also publishes what the caller staged in LDS before the call.
+__device__ __forceinline__ unsigned long long block_start_bits(const PngJob& J, int k, unsigned long long* s_part) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int im = __builtin_amdgcn_readfirstlane(find_image(B.blk_prefix, B.n, blockIdx.x));
-    const PngJob J = B.img[im];
-    const int k = static_cast<int>(blockIdx.x - B.blk_prefix[im]);
-    if (!J.lz_flag[k]) return;  // written by png_emit_kernel
-    const int N = 3 * J.w + 1;
-    const int y_lo = k * J.rows, y_hi = min(J.h, y_lo + J.rows);
-    const int nb = (y_hi - y_lo) * N;
-    const size_t off = static_cast<size_t>(y_lo) * N;
-    const uint32_t* tk = J.lz + off;
     unsigned long long before = 0;
     for (int i = tid; i < k; i += kThreadsB) before += J.blk_bits[i];
     for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
     if (lane == 0) s_part[wave] = before;
-    for (int i = tid; i < kNLL + kNDist; i += kThreadsB) s_code[i] = J.lz_codes[static_cast<size_t>(k) * (kNLL + kNDist) + i];
-    for (int i = tid; i < nb; i += kThreadsB) s_data[i] = J.scan[off + i];
     __syncthreads();
     before = 0;
     for (int q = 0; q < kThreadsB / 64; ++q) before += s_part[q];
-    const uint32_t my_bits = J.blk_bits[k];
-    const uint64_t start = static_cast<uint64_t>(kDataStart) * 8 + before;
-    if (start + my_bits + 256 > J.cap_bits) return;  // png_emit_kernel flags the overflow
-    const uint32_t* dcode = s_code + kNLL;
-    // ---- block header: HLIT = 286, HDIST = 30, 19 code-length codes
+    return before;
+}
+
+// Header of a dynamic-Huffman block at bit `start`: BFINAL, BTYPE = 2, HLIT, HDIST, HCLEN = 19; the code-length code
+// (3-bit lengths in the order 16, 17, 18, 0, 8, ...: none for the run-length symbols, 4 bits for each of the lengths
+// 0..15); the hlit + hdist lengths, 4 bits each (those of code[n_codes], zero behind them).  The end-of-block code goes
+// in front of bit `end`, the first bit behind the block.
+__device__ __forceinline__ void emit_block_header(uint32_t* out, uint64_t start, uint64_t end, bool final_blk, uint32_t hlit,
+                                                  uint32_t hdist, const uint32_t* code, int n_codes) {
+    const int tid = threadIdx.x;
     if (tid == 0) {
-        const uint32_t final_blk = k == J.nblk - 1 ? 1u : 0u;
-        or_bits(J.out, start, final_blk | (2u << 1) | ((kNLL - 257u) << 3) | ((kNDist - 1u) << 8) | (15u << 13), 17);
-        const uint32_t eob = s_code[256];
-        or_bits(J.out, start + my_bits - (eob >> 16), eob & 0xFFFFu, static_cast<int>(eob >> 16));
+        or_bits(out, start, (final_blk ? 1u : 0u) | (2u << 1) | ((hlit - 257u) << 3) | ((hdist - 1u) << 8) | (15u << 13), 17);
+        const uint32_t eob = code[256];
+        or_bits(out, end - (eob >> 16), eob & 0xFFFFu, static_cast<int>(eob >> 16));
     }
-    if (tid < 19) or_bits(J.out, start + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);
-    for (int s = tid; s < kNLL + kNDist; s += kThreadsB) or_bits(J.out, start + 74 + 4 * s, rev_bits(s_code[s] >> 16, 4), 4);
-    // ---- tokens starting in a contiguous chunk of positions per thread
-    const int cb = (nb + kThreadsB - 1) / kThreadsB;
-    const int lo = min(nb, tid * cb), hi = min(nb, lo + cb);
-    uint32_t bits = 0;
-    for (int i = lo; i < hi; ++i) {
-        const uint32_t t = tk[i];
-        if (!t) continue;
-        if (t >> 16) {
-            uint32_t sym, ne, ev;
-            len_code(t >> 16, sym, ne, ev);
-            bits += (s_code[sym] >> 16) + ne;
-            dist_code(t & 0xFFFFu, sym, ne, ev);
-            bits += (dcode[sym] >> 16) + ne;
-        } else {
-            bits += s_code[s_data[i]] >> 16;
-        }
-    }
-    uint32_t incl = bits;
+    if (tid < 19) or_bits(out, start + 17 + 3 * tid, tid < 3 ? 0u : 4u, 3);
+    for (int s = tid; s < static_cast<int>(hlit + hdist); s += kThreadsB)
+        or_bits(out, start + 74 + 4 * s, rev_bits(s < n_codes ? code[s] >> 16 : 0u, 4), 4);
+}
+
+// exclusive scan of one value per thread over the workgroup (s_scan: one word per wave; holds a barrier)
+__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t* s_scan) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t incl = v;
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t t = __shfl_up(incl, o);
         if (lane >= o) incl += t;
     }
     if (lane == 63) s_scan[wave] = incl;
     __syncthreads();
-    uint32_t offset = incl - bits;
+    uint32_t offset = incl - v;
     for (int q = 0; q < wave; ++q) offset += s_scan[q];
-    const uint64_t pos = start + kHeaderBitsLz + offset;
-    uint32_t wi = static_cast<uint32_t>(pos >> 5);
-    int nacc = static_cast<int>(pos & 31);
+    return offset;
+}
+
+// Packs the consecutive codes of one thread into the zeroed file from bit `pos` on.  The one place that decides how an
+// output word is written: the first word a thread completes and its last, partial word may hold bits of its
+// neighbours and are merged with atomicOr; every bit of a word between them belongs to this thread, which stores it.
+struct BitWriter {
+    uint32_t* out;
+    uint32_t wi;
+    int nacc;
     uint64_t acc = 0;
     bool first = true;
-    auto put = [&](uint32_t value, int n) {  // n <= 15
+    __device__ BitWriter(uint32_t* o, uint64_t pos) : out(o), wi(static_cast<uint32_t>(pos >> 5)), nacc(static_cast<int>(pos & 31)) {}
+    __device__ void put(uint32_t value, int n) {  // n <= 15
         acc |= static_cast<uint64_t>(value) << nacc;
         nacc += n;
         if (nacc >= 32) {
-            if (first) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
-            else J.out[wi] = static_cast<uint32_t>(acc);  // every bit of this word belongs to this thread
+            if (first) atomicOr(&out[wi], static_cast<uint32_t>(acc));
+            else out[wi] = static_cast<uint32_t>(acc);
             first = false;
             ++wi;
             acc >>= 32;
             nacc -= 32;
         }
-    };
-    for (int i = lo; i < hi; ++i) {
-        const uint32_t t = tk[i];
-        if (!t) continue;
-        if (t >> 16) {
-            uint32_t sym, ne, ev;
-            len_code(t >> 16, sym, ne, ev);
-            put(s_code[sym] & 0xFFFFu, static_cast<int>(s_code[sym] >> 16));
-            put(ev, static_cast<int>(ne));
-            dist_code(t & 0xFFFFu, sym, ne, ev);
-            put(dcode[sym] & 0xFFFFu, static_cast<int>(dcode[sym] >> 16));
-            put(ev, static_cast<int>(ne));
-        } else {
-            const uint32_t c = s_code[s_data[i]];
-            put(c & 0xFFFFu, static_cast<int>(c >> 16));
-        }
     }
-    if (nacc > 0 && acc != 0) atomicOr(&J.out[wi], static_cast<uint32_t>(acc));
+    __device__ void flush() {
+        if (nacc > 0 && acc != 0) atomicOr(&out[wi], static_cast<uint32_t>(acc));
+    }
+};
+
+// The codes of the token that starts at position i of the block, in stream order, as put(value, nbits).  Level 0: every
+// position is a literal.  Level 1: tk[i] is 0 inside a match, 1 for a literal, else length << 16 | distance.
+template <bool LZ, typename Put>
+__device__ __forceinline__ void for_token_codes(const uint32_t* tk, const uint8_t* data, const uint32_t* code, int i, Put&& put) {
+    const uint32_t t = LZ ? tk[i] : 1u;
+    if (!t) return;
+    if (t >> 16) {
+        const uint32_t* dcode = code + kNLL;
+        uint32_t sym, ne, ev;
+        len_code(t >> 16, sym, ne, ev);
+        put(code[sym] & 0xFFFFu, static_cast<int>(code[sym] >> 16));
+        put(ev, static_cast<int>(ne));
+        dist_code(t & 0xFFFFu, sym, ne, ev);
+        put(dcode[sym] & 0xFFFFu, static_cast<int>(dcode[sym] >> 16));
+        put(ev, static_cast<int>(ne));
+    } else {
+        const uint32_t c = code[data[i]];
+        put(c & 0xFFFFu, static_cast<int>(c >> 16));
+    }
 }
+
+// One workgroup writes one block.  Level 0 (png_emit_kernel) runs for every block, keeps the stream's bit count and the
+// overflow flag, and leaves the blocks that png_lz77_parse_kernel flagged to level 1 (png_emit_lz77_kernel), which
+// writes those alone.
+template <bool LZ>
+__device__ __forceinline__ void emit_block(const PngBatch& B) {
+    constexpr int kCodes = LZ ? kNLL + kNDist : 257;
+    __shared__ uint8_t s_data[kStageBytes];
+    __shared__ uint32_t s_code[kCodes];
+    __shared__ unsigned long long s_part[kThreadsB / 64];
+    __shared__ uint32_t s_scan[kThreadsB / 64];
+    const int tid = threadIdx.x;
+    const BlockCtx C = block_ctx(B);
+    const PngJob& J = C.J;
+    const int k = C.k, nb = C.nb;
+    if (LZ && !J.lz_flag[k]) return;
+    const uint32_t* codes = (LZ ? J.lz_codes : J.codes) + static_cast<size_t>(k) * kCodes;
+    for (int i = tid; i < kCodes; i += kThreadsB) s_code[i] = codes[i];
+    for (int i = tid; i < nb; i += kThreadsB) s_data[i] = J.scan[C.off + i];
+    const unsigned long long before = block_start_bits(J, k, s_part);  // the barrier behind s_code and s_data
+    const uint32_t my_bits = J.blk_bits[k];
+    const uint64_t start = static_cast<uint64_t>(kDataStart) * 8 + before;
+    if (!LZ && k == J.nblk - 1 && tid == 0) J.meta[0] = static_cast<uint32_t>(before + my_bits);
+    if (start + my_bits + 256 > J.cap_bits) {  // 20 container bytes follow the last block
+        if (!LZ && tid == 0) J.meta[4] = 1;    // never with a buffer of ccd_png_bound() bytes
+        return;
+    }
+    if (!LZ && J.lz_flag && J.lz_flag[k]) return;
+    emit_block_header(J.out, start, start + my_bits, k == J.nblk - 1, LZ ? kNLL : 257, LZ ? kNDist : 1, s_code, kCodes);
+    // ---- tokens starting in a contiguous chunk of positions per thread: bit counts, scan, packing
+    const uint32_t* tk = LZ ? J.lz + C.off : nullptr;
+    const int cb = (nb + kThreadsB - 1) / kThreadsB;
+    const int lo = min(nb, tid * cb), hi = min(nb, lo + cb);
+    uint32_t bits = 0;
+    for (int i = lo; i < hi; ++i) for_token_codes<LZ>(tk, s_data, s_code, i, [&](uint32_t, int n) { bits += n; });
+    BitWriter bw(J.out, start + (LZ ? kHeaderBitsLz : kHeaderBits) + wg_exclusive_scan(bits, s_scan));
+    for (int i = lo; i < hi; ++i) for_token_codes<LZ>(tk, s_data, s_code, i, [&](uint32_t v, int n) { bw.put(v, n); });
+    bw.flush();
+}
+
+__global__ __launch_bounds__(kThreadsB) void png_emit_kernel(PngBatch B) { emit_block<false>(B); }
+
+__global__ __launch_bounds__(kThreadsB) void png_emit_lz77_kernel(PngBatch B) { emit_block<true>(B); }
 
 // ---- kernel C -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v) {
@@ -994,6 +893,16 @@ bool grow(T** buf, size_t* cap, size_t need) {  // device buffer of at least `ne
     return true;
 }
 
+template <typename T>
+bool regrow_pinned(T** buf, size_t need) {  // pinned host buffer of `need` elements (contents are scratch)
+    if (*buf) (void)hipHostFree(*buf);
+    *buf = nullptr;
+    return hipHostMalloc(reinterpret_cast<void**>(buf), need * sizeof(T), hipHostMallocDefault) == hipSuccess;
+}
+
+// bytes of a picture's scanlines in the workspace (every picture starts on a multiple of 16)
+inline size_t scan_bytes(int h, int w) { return (static_cast<size_t>(h) * (3 * static_cast<size_t>(w) + 1) + 15) & ~static_cast<size_t>(15); }
+
 }  // namespace
 
 struct ccd_png {
@@ -1023,6 +932,111 @@ struct ccd_png {
     uint32_t* d_lz_flag = nullptr;   // [blocks]
 };
 
+namespace {
+
+struct PackSize { size_t scan = 0, blocks = 0, rows = 0; };  // of all pictures of a pack: scanline bytes, deflate blocks, rows
+
+bool validate_and_size(const ccd_png_item* items, int n, PackSize* sz) {
+    for (int i = 0; i < n; ++i) {
+        const ccd_png_item& it = items[i];
+        if (!it.r || !it.g || !it.b || !it.out || it.h <= 0 || it.w <= 0 || it.h > kMaxDim || it.w > kMaxDim) return false;
+        if ((reinterpret_cast<uintptr_t>(it.out) & 3u) || it.cap < ccd_png_bound(it.h, it.w)) return false;
+        const int rpb = rows_per_block(it.w);
+        sz->scan += scan_bytes(it.h, it.w);
+        sz->blocks += (it.h + rpb - 1) / rpb;
+        sz->rows += it.h;
+    }
+    return true;
+}
+
+// Workspace for a pack of n pictures.  Before a buffer is replaced the stream is drained: the previous pack may still use it.
+int ensure_workspace(ccd_png* p, int n, const PackSize& sz, bool lz, hipStream_t st) {
+    const size_t pics = static_cast<size_t>(n), lz_codes = sz.blocks * (kNLL + kNDist);
+    if (lz && (sz.scan > p->prev_cap || sz.scan > p->lz_cap || lz_codes > p->lzc_cap || sz.blocks > p->flag_cap)) {
+        if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;
+        if (!grow(&p->d_prev, &p->prev_cap, sz.scan) || !grow(&p->d_lz, &p->lz_cap, sz.scan) ||
+            !grow(&p->d_lz_codes, &p->lzc_cap, lz_codes) || !grow(&p->d_lz_flag, &p->flag_cap, sz.blocks))
+            return CCD_ERR_NOMEM;
+    }
+    if (sz.scan > p->scan_cap || sz.blocks * 257 > p->codes_cap || sz.blocks > p->bits_cap || sz.rows * 2 > p->adler_cap ||
+        pics > p->jobs_cap || pics * 8 > p->meta_cap) {
+        if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;
+        if (pics * 8 > p->meta_cap && !regrow_pinned(&p->h_meta, pics * 8)) return CCD_ERR_NOMEM;
+        if (!grow(&p->d_scan, &p->scan_cap, sz.scan) || !grow(&p->d_codes, &p->codes_cap, sz.blocks * 257) ||
+            !grow(&p->d_blk_bits, &p->bits_cap, sz.blocks) || !grow(&p->d_row_adler, &p->adler_cap, sz.rows * 2) ||
+            !grow(&p->d_meta, &p->meta_cap, pics * 8))
+            return CCD_ERR_NOMEM;
+        if (pics > p->jobs_cap) {
+            for (int k = 0; k < 2; ++k) {
+                size_t cap = p->jobs_cap;
+                if (!grow(&p->d_jobs[k], &cap, pics) || !regrow_pinned(&p->h_jobs[k], pics)) return CCD_ERR_NOMEM;
+                if (!p->ev[k] && hipEventCreateWithFlags(&p->ev[k], hipEventDisableTiming) != hipSuccess) return CCD_ERR_HIP;
+                p->ev_used[k] = false;  // the stream was drained above
+            }
+            p->jobs_cap = pics;
+        }
+    }
+    return CCD_OK;
+}
+
+// the job table of a pack: every picture gets its slice of each workspace buffer
+void fill_jobs(const ccd_png* p, PngJob* jobs, const ccd_png_item* items, int n, bool lz) {
+    size_t scan_off = 0, blk_off = 0, row_off = 0;
+    for (int i = 0; i < n; ++i) {
+        const ccd_png_item& it = items[i];
+        PngJob& J = jobs[i];
+        std::memset(&J, 0, sizeof(J));
+        J.plane[0] = it.r; J.plane[1] = it.g; J.plane[2] = it.b;
+        J.out = reinterpret_cast<uint32_t*>(it.out);
+        J.cap_bits = static_cast<uint64_t>(it.cap) * 8;
+        J.h = it.h; J.w = it.w; J.rows = rows_per_block(it.w); J.nblk = (it.h + J.rows - 1) / J.rows;
+        J.scan = p->d_scan + scan_off;
+        J.codes = p->d_codes + blk_off * 257;
+        J.blk_bits = p->d_blk_bits + blk_off;
+        J.row_adler = p->d_row_adler + row_off * 2;
+        J.meta = p->d_meta + static_cast<size_t>(i) * 8;
+        if (lz) {
+            J.prev = p->d_prev + scan_off;
+            J.lz = p->d_lz + scan_off;
+            J.lz_codes = p->d_lz_codes + blk_off * (kNLL + kNDist);
+            J.lz_flag = p->d_lz_flag + blk_off;
+        }
+        const size_t bound = ccd_png_bound(it.h, it.w);
+        J.zero_words = static_cast<uint32_t>(std::min(it.cap & ~static_cast<size_t>(3), (bound + 3) & ~static_cast<size_t>(3)) / 4);
+        scan_off += scan_bytes(it.h, it.w);
+        blk_off += J.nblk;
+        row_off += it.h;
+    }
+}
+
+// one set of launches for cnt <= kMaxBatch pictures (jobs: their entries of the host table, d_jobs: of the device table)
+int launch_set(const ccd_png* p, const PngJob* jobs, const PngJob* d_jobs, int cnt, bool lz, hipStream_t st) {
+    PngBatch B;
+    std::memset(&B, 0, sizeof(B));
+    B.img = d_jobs;
+    B.n = cnt;
+    std::memcpy(B.x2n, p->x2n, sizeof(B.x2n));
+    for (int i = 0; i < cnt; ++i) {
+        B.blk_prefix[i + 1] = B.blk_prefix[i] + static_cast<uint32_t>(jobs[i].nblk);
+        const size_t chunks = ccd_png_bound(jobs[i].h, jobs[i].w) / kCrcChunk + 1;
+        B.crc_prefix[i + 1] = B.crc_prefix[i] + static_cast<uint32_t>((chunks + 255) / 256);
+    }
+    const dim3 blocks(B.blk_prefix[cnt]);
+    hipLaunchKernelGGL(png_filter_huff_kernel, blocks, dim3(kThreadsA), 0, st, B);
+    if (lz) {
+        hipLaunchKernelGGL(png_lz77_match_kernel, blocks, dim3(kThreadsM), 0, st, B);
+        hipLaunchKernelGGL(png_lz77_parse_kernel, blocks, dim3(kThreadsP), 0, st, B);
+    }
+    hipLaunchKernelGGL(png_emit_kernel, blocks, dim3(kThreadsB), 0, st, B);
+    if (lz) hipLaunchKernelGGL(png_emit_lz77_kernel, blocks, dim3(kThreadsB), 0, st, B);
+    hipLaunchKernelGGL(png_trailer_kernel, dim3(cnt), dim3(256), 0, st, B);
+    hipLaunchKernelGGL(png_crc_kernel, dim3(B.crc_prefix[cnt]), dim3(256), 0, st, B);
+    hipLaunchKernelGGL(png_crc_final_kernel, dim3(cnt), dim3(64), 0, st, B);
+    return hipGetLastError() == hipSuccess ? CCD_OK : CCD_ERR_HIP;
+}
+
+}  // namespace
+
 extern "C" {
 
 size_t ccd_png_bound(int h, int w) {
@@ -1048,21 +1062,12 @@ int ccd_png_create(int device, ccd_png** out) {
 void ccd_png_destroy(ccd_png* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    if (p->d_scan) (void)hipFree(p->d_scan);
-    if (p->d_codes) (void)hipFree(p->d_codes);
-    if (p->d_blk_bits) (void)hipFree(p->d_blk_bits);
-    if (p->d_row_adler) (void)hipFree(p->d_row_adler);
-    if (p->d_meta) (void)hipFree(p->d_meta);
-    if (p->d_prev) (void)hipFree(p->d_prev);
-    if (p->d_lz) (void)hipFree(p->d_lz);
-    if (p->d_lz_codes) (void)hipFree(p->d_lz_codes);
-    if (p->d_lz_flag) (void)hipFree(p->d_lz_flag);
-    for (int k = 0; k < 2; ++k) {
-        if (p->d_jobs[k]) (void)hipFree(p->d_jobs[k]);
-        if (p->h_jobs[k]) (void)hipHostFree(p->h_jobs[k]);
-        if (p->ev[k]) (void)hipEventDestroy(p->ev[k]);
-    }
-    if (p->h_meta) (void)hipHostFree(p->h_meta);
+    void* const device_bufs[] = {p->d_scan, p->d_codes, p->d_blk_bits, p->d_row_adler, p->d_meta, p->d_prev, p->d_lz,
+                                 p->d_lz_codes, p->d_lz_flag, p->d_jobs[0], p->d_jobs[1]};
+    void* const pinned_bufs[] = {p->h_meta, p->h_jobs[0], p->h_jobs[1]};
+    for (void* b : device_bufs) if (b) (void)hipFree(b);
+    for (void* b : pinned_bufs) if (b) (void)hipHostFree(b);
+    for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
     delete p;
 }
 
@@ -1074,110 +1079,23 @@ int ccd_png_set_level(ccd_png* p, int level) {
 
 int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* stream) {
     if (!p || !items || n <= 0) return CCD_ERR_ARG;
-    size_t scan_need = 0, blocks = 0, rows = 0;
-    for (int i = 0; i < n; ++i) {
-        const ccd_png_item& it = items[i];
-        if (!it.r || !it.g || !it.b || !it.out || it.h <= 0 || it.w <= 0 || it.h > kMaxDim || it.w > kMaxDim) return CCD_ERR_ARG;
-        if ((reinterpret_cast<uintptr_t>(it.out) & 3u) || it.cap < ccd_png_bound(it.h, it.w)) return CCD_ERR_ARG;
-        const int rpb = rows_per_block(it.w);
-        scan_need += (static_cast<size_t>(it.h) * (3 * static_cast<size_t>(it.w) + 1) + 15) & ~static_cast<size_t>(15);
-        blocks += (it.h + rpb - 1) / rpb;
-        rows += it.h;
-    }
+    PackSize sz;
+    if (!validate_and_size(items, n, &sz)) return CCD_ERR_ARG;
     if (hipSetDevice(p->device) != hipSuccess) return CCD_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool lz = p->level == CCD_PNG_LZ77;
-    if (lz && (scan_need > p->prev_cap || scan_need > p->lz_cap || blocks * (kNLL + kNDist) > p->lzc_cap || blocks > p->flag_cap)) {
-        if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;  // the previous pack may still use the old workspace
-        if (!grow(&p->d_prev, &p->prev_cap, scan_need) || !grow(&p->d_lz, &p->lz_cap, scan_need) ||
-            !grow(&p->d_lz_codes, &p->lzc_cap, blocks * (kNLL + kNDist)) || !grow(&p->d_lz_flag, &p->flag_cap, blocks))
-            return CCD_ERR_NOMEM;
-    }
-    if (scan_need > p->scan_cap || blocks * 257 > p->codes_cap || blocks > p->bits_cap || rows * 2 > p->adler_cap ||
-        static_cast<size_t>(n) > p->jobs_cap || static_cast<size_t>(n) * 8 > p->meta_cap) {
-        if (hipStreamSynchronize(st) != hipSuccess) return CCD_ERR_HIP;  // the previous pack may still use the old workspace
-        if (static_cast<size_t>(n) * 8 > p->meta_cap) {
-            if (p->h_meta) (void)hipHostFree(p->h_meta);
-            p->h_meta = nullptr;
-            if (hipHostMalloc(reinterpret_cast<void**>(&p->h_meta), static_cast<size_t>(n) * 8 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-                return CCD_ERR_NOMEM;
-        }
-        if (!grow(&p->d_scan, &p->scan_cap, scan_need) || !grow(&p->d_codes, &p->codes_cap, blocks * 257) ||
-            !grow(&p->d_blk_bits, &p->bits_cap, blocks) || !grow(&p->d_row_adler, &p->adler_cap, rows * 2) ||
-            !grow(&p->d_meta, &p->meta_cap, static_cast<size_t>(n) * 8))
-            return CCD_ERR_NOMEM;
-        if (static_cast<size_t>(n) > p->jobs_cap) {
-            for (int k = 0; k < 2; ++k) {
-                size_t cap = p->jobs_cap;
-                if (!grow(&p->d_jobs[k], &cap, static_cast<size_t>(n))) return CCD_ERR_NOMEM;
-                if (p->h_jobs[k]) (void)hipHostFree(p->h_jobs[k]);
-                p->h_jobs[k] = nullptr;
-                if (hipHostMalloc(reinterpret_cast<void**>(&p->h_jobs[k]), static_cast<size_t>(n) * sizeof(PngJob), hipHostMallocDefault) != hipSuccess)
-                    return CCD_ERR_NOMEM;
-                if (!p->ev[k] && hipEventCreateWithFlags(&p->ev[k], hipEventDisableTiming) != hipSuccess) return CCD_ERR_HIP;
-                p->ev_used[k] = false;  // the stream was drained above
-            }
-            p->jobs_cap = static_cast<size_t>(n);
-        }
-    }
+    int rc = ensure_workspace(p, n, sz, lz, st);
+    if (rc != CCD_OK) return rc;
     const int jk = p->flip;
     p->flip ^= 1;
     // this copy of the table was last read two packs ago: normally long finished
     if (p->ev_used[jk] && hipEventSynchronize(p->ev[jk]) != hipSuccess) return CCD_ERR_HIP;
     PngJob* jobs = p->h_jobs[jk];
-    size_t scan_off = 0, blk_off = 0, row_off = 0;
-    for (int i = 0; i < n; ++i) {
-        const ccd_png_item& it = items[i];
-        PngJob& J = jobs[i];
-        std::memset(&J, 0, sizeof(J));
-        J.plane[0] = it.r; J.plane[1] = it.g; J.plane[2] = it.b;
-        J.out = reinterpret_cast<uint32_t*>(it.out);
-        J.cap_bits = static_cast<uint64_t>(it.cap) * 8;
-        J.h = it.h; J.w = it.w; J.rows = rows_per_block(it.w); J.nblk = (it.h + J.rows - 1) / J.rows;
-        J.scan = p->d_scan + scan_off;
-        J.codes = p->d_codes + blk_off * 257;
-        J.blk_bits = p->d_blk_bits + blk_off;
-        J.row_adler = p->d_row_adler + row_off * 2;
-        J.meta = p->d_meta + static_cast<size_t>(i) * 8;
-        if (lz) {
-            J.prev = p->d_prev + scan_off;
-            J.lz = p->d_lz + scan_off;
-            J.lz_codes = p->d_lz_codes + blk_off * (kNLL + kNDist);
-            J.lz_flag = p->d_lz_flag + blk_off;
-        }
-        const size_t bound = ccd_png_bound(it.h, it.w);
-        J.zero_words = static_cast<uint32_t>(std::min(it.cap & ~static_cast<size_t>(3), (bound + 3) & ~static_cast<size_t>(3)) / 4);
-        scan_off += (static_cast<size_t>(it.h) * (3 * static_cast<size_t>(it.w) + 1) + 15) & ~static_cast<size_t>(15);
-        blk_off += J.nblk;
-        row_off += it.h;
-    }
-    hipError_t e = hipMemcpyAsync(p->d_jobs[jk], jobs, static_cast<size_t>(n) * sizeof(PngJob), hipMemcpyHostToDevice, st);
-    int rc = e == hipSuccess ? CCD_OK : CCD_ERR_HIP;
-    for (int first = 0; first < n && rc == CCD_OK; first += kMaxBatch) {
-        const int cnt = std::min(kMaxBatch, n - first);
-        PngBatch B;
-        std::memset(&B, 0, sizeof(B));
-        B.img = p->d_jobs[jk] + first;
-        B.n = cnt;
-        std::memcpy(B.x2n, p->x2n, sizeof(B.x2n));
-        for (int i = 0; i < cnt; ++i) {
-            const PngJob& J = jobs[first + i];
-            B.blk_prefix[i + 1] = B.blk_prefix[i] + static_cast<uint32_t>(J.nblk);
-            const size_t chunks = ccd_png_bound(J.h, J.w) / kCrcChunk + 1;
-            B.crc_prefix[i + 1] = B.crc_prefix[i] + static_cast<uint32_t>((chunks + 255) / 256);
-        }
-        hipLaunchKernelGGL(png_filter_huff_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsA), 0, st, B);
-        if (lz) {
-            hipLaunchKernelGGL(png_lz77_match_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsM), 0, st, B);
-            hipLaunchKernelGGL(png_lz77_parse_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsP), 0, st, B);
-        }
-        hipLaunchKernelGGL(png_emit_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsB), 0, st, B);
-        if (lz) hipLaunchKernelGGL(png_emit_lz77_kernel, dim3(B.blk_prefix[cnt]), dim3(kThreadsB), 0, st, B);
-        hipLaunchKernelGGL(png_trailer_kernel, dim3(cnt), dim3(256), 0, st, B);
-        hipLaunchKernelGGL(png_crc_kernel, dim3(B.crc_prefix[cnt]), dim3(256), 0, st, B);
-        hipLaunchKernelGGL(png_crc_final_kernel, dim3(cnt), dim3(64), 0, st, B);
-        if (hipGetLastError() != hipSuccess) rc = CCD_ERR_HIP;
-    }
+    fill_jobs(p, jobs, items, n, lz);
+    if (hipMemcpyAsync(p->d_jobs[jk], jobs, static_cast<size_t>(n) * sizeof(PngJob), hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = CCD_ERR_HIP;
+    for (int first = 0; first < n && rc == CCD_OK; first += kMaxBatch)
+        rc = launch_set(p, jobs + first, p->d_jobs[jk] + first, std::min(kMaxBatch, n - first), lz, st);
     if (hipEventRecord(p->ev[jk], st) != hipSuccess) rc = CCD_ERR_HIP;
     p->ev_used[jk] = true;
     if (rc != CCD_OK) return rc;

@@ -3,37 +3,12 @@
 PNG bytes are not normative, so the bar has two parts: (1) the picture an independent reader (PIL / zlib - the
 reference's own writer library) decodes is pixel-exact, at every size; (2) the device's bytes equal those of the CPU
 restatement oracle/png_pack.py (filter choice, code lengths, block layout and checksums are integer and deterministic)."""
-import io
 import zlib
 
 import numpy as np
 import pytest
 
-
-def _pictures(h, w, seed=0):
-    rng = np.random.default_rng(seed + 7919 * h + w)
-    yy, xx = np.mgrid[0:h, 0:w]
-    smooth = np.stack([(yy * 3 + xx) % 256, (yy + xx * 2) % 256, (yy * xx) % 256]).astype(np.uint8)
-    photo = np.clip(smooth.astype(np.int32) // 2 + rng.normal(0, 6, (3, h, w)).round().astype(np.int32) + 40, 0, 255).astype(np.uint8)
-    return {
-        "random": rng.integers(0, 256, (3, h, w), dtype=np.uint8),
-        "smooth": smooth,
-        "photo": photo,
-        "zeros": np.zeros((3, h, w), np.uint8),
-        # counts falling off geometrically: optimal codes longer than 15 bits, the length limiter runs
-        "skewed": np.minimum(rng.geometric(0.55, (3, h, w)) * 3, 255).astype(np.uint8),
-    }
-
-
-def _read_png(png: bytes) -> np.ndarray:
-    from PIL import Image
-
-    im = Image.open(io.BytesIO(png))
-    assert im.mode == "RGB"
-    return np.asarray(im).transpose(2, 0, 1)
-
-
-SIZES = [(1, 1), (1, 7), (7, 1), (2, 3), (17, 33), (64, 64), (100, 300), (33, 1111)]
+from png_pictures import SIZES, _fibonacci_row, _pictures, _read_png, _unlimited_depths
 
 
 # ------------------------------------------------------------------------------------------------ CPU: the restatement itself
@@ -107,6 +82,26 @@ def test_device_png_equals_oracle_and_reads_back(packer, h, w):
         png = packer.pack(torch.from_numpy(planes).cuda())
         assert np.array_equal(_read_png(png), planes), (h, w, kind)
         assert png == png_pack.pack_rgb8(planes), (h, w, kind)
+
+
+@pytest.mark.gpu
+def test_device_png_of_a_block_deeper_than_15_bits(packer):
+    """None of the pictures above has a block whose optimal code is deeper than 15 bits (checked on the CPU: their deepest
+    is 15).  This one is one block of 6.7 KB whose tree is 17 deep, so the fold to 15 bits and the Kraft repair run."""
+    import torch
+
+    from oracle import png_pack
+
+    planes = _fibonacci_row()
+    scan, _ = png_pack.filter_rows(np.ascontiguousarray(planes.transpose(1, 2, 0)))
+    assert scan.size <= png_pack.BLOCK_TARGET  # one block
+    hist = np.bincount(scan.reshape(-1), minlength=257)
+    hist[256] = 1
+    assert _unlimited_depths(png_pack.code_lengths, hist).max() > png_pack.MAX_BITS
+    assert png_pack.code_lengths(hist).max() == png_pack.MAX_BITS
+    png = packer.pack(torch.from_numpy(planes).cuda())
+    assert np.array_equal(_read_png(png), planes)
+    assert png == png_pack.pack_rgb8(planes)
 
 
 @pytest.mark.gpu

@@ -14,34 +14,10 @@ import numpy as np
 import pytest
 
 import png_lz77_ref as R
+from png_pictures import SIZES, _deep_litlen_row, _pictures, _read_png, _unlimited_depths
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CCD_ERR_ARG = -7
-
-
-def _pictures(h, w, seed=0):  # the generator of tests/test_png.py
-    rng = np.random.default_rng(seed + 7919 * h + w)
-    yy, xx = np.mgrid[0:h, 0:w]
-    smooth = np.stack([(yy * 3 + xx) % 256, (yy + xx * 2) % 256, (yy * xx) % 256]).astype(np.uint8)
-    photo = np.clip(smooth.astype(np.int32) // 2 + rng.normal(0, 6, (3, h, w)).round().astype(np.int32) + 40, 0, 255).astype(np.uint8)
-    return {
-        "random": rng.integers(0, 256, (3, h, w), dtype=np.uint8),
-        "smooth": smooth,
-        "photo": photo,
-        "zeros": np.zeros((3, h, w), np.uint8),
-        "skewed": np.minimum(rng.geometric(0.55, (3, h, w)) * 3, 255).astype(np.uint8),
-    }
-
-
-SIZES = [(1, 1), (1, 7), (7, 1), (2, 3), (17, 33), (64, 64), (100, 300), (33, 1111)]
-
-
-def _read_png(png: bytes) -> np.ndarray:
-    from PIL import Image
-
-    im = Image.open(io.BytesIO(png))
-    assert im.mode == "RGB"
-    return np.asarray(im).transpose(2, 0, 1)
 
 
 def _idat(png: bytes) -> bytes:
@@ -230,6 +206,31 @@ def test_device_level1_equals_restatement(packer, h, w):
         png = packer.pack(torch.from_numpy(planes).cuda())
         assert np.array_equal(_read_png(png), planes), (h, w, kind)
         assert png == R.pack_rgb8(planes), (h, w, kind)
+
+
+@pytest.mark.gpu
+def test_device_png_lz77_of_a_litlen_tree_deeper_than_15_bits(packer):
+    """No other byte-compared picture has a block that takes the LZ77 coding with a literal/length tree deeper than 15 bits
+    (their deepest is 12): here the fold to 15 bits and the Kraft repair run on the 286-symbol alphabet and show."""
+    import torch
+
+    from oracle import png_pack
+
+    planes = _deep_litlen_row()
+    data = np.frombuffer(_scanlines(planes), np.uint8)
+    assert planes.shape[1] == 1 and data[0] == 1  # one row = one block, Sub filter
+    _, (lens_ll, *_), (pos, L, _) = R.lz77_block(data)
+    sym = np.where(L == 0, data[pos].astype(np.int64), R.len_sym(np.where(L == 0, 3, L))[0])
+    hll = np.bincount(sym, minlength=R.NLL)
+    hll[256] += 1
+    assert _unlimited_depths(R.code_lengths, hll).max() > png_pack.MAX_BITS
+    assert lens_ll.max() == png_pack.MAX_BITS
+    info = []
+    want = R.pack_rgb8(planes, info=info)
+    assert [c for _, c in info] == ["lz"]
+    png = packer.pack(torch.from_numpy(planes).cuda())
+    assert np.array_equal(_read_png(png), planes)
+    assert png == want
 
 
 @pytest.mark.gpu
