@@ -16,9 +16,12 @@ if __name__ == "__main__":
                         help="Source of the stream (.png, .ppm or planar .yuv): every decoded frame is scored against it on the GPU.")
     parser.add_argument("--results", type=str, default=None,
                         help="With --source: tab-separated file with the rate, PSNR and MS-SSIM of every frame and of the sequence.")
+    parser.add_argument("--rate-breakdown", type=str, default=None, metavar="FILE",
+                        help="Tab-separated file with the model bits of every latent grid of every cool-chic (measured on the GPU).")
     parser.add_argument("--no-ms-ssim", action="store_true", help="With --source: PSNR only.")
     args = parser.parse_args()
     if args.results is not None and args.source is None:
         parser.error("--results needs --source")
     decode_video(args.input, decoded_path=args.output, verbosity=args.verbosity, device=args.device,
-                 png_level=args.png_level, source_path=args.source, ms_ssim=not args.no_ms_ssim, results_path=args.results)
+                 png_level=args.png_level, source_path=args.source, ms_ssim=not args.no_ms_ssim, results_path=args.results,
+                 rate_breakdown_path=args.rate_breakdown)

@@ -78,6 +78,12 @@ class QualityResult(C.Structure):
                 ("ssim", (C.c_double * 5) * 3)]
 
 
+class EncRate(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_grids", C.c_int32), ("n_symbols", C.c_int64 * MAX_GRIDS),
+                ("sum_width", C.c_uint64 * MAX_GRIDS), ("bits", C.c_double * MAX_GRIDS), ("total_bits", C.c_double),
+                ("n_bytes_nn", C.c_int64), ("n_bytes_header", C.c_int64)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -168,6 +174,9 @@ SIGNATURES = {
     "ccd_enc_slot_payload": (C.c_int64, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_enc_slot_status": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ccd_enc_payload_bound": (C.c_size_t, [C.c_int64]),
+    "ccd_enc_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "ccd_enc_slot_rate": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EncRate)]),
+    "ccd_enc_slot_rate_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

@@ -80,11 +80,18 @@ def decode_frame(bitstream_bytes: bytes, reference_frames: List[FrameData], verb
 @torch.no_grad()
 def decode_video(bitstream_path: str, decoded_path: Optional[str] = None, max_decoding_order: int = -1,
                  verbosity: int = 0, device: int = 0, png_level: int = 0, source_path: Optional[str] = None,
-                 results_path: Optional[str] = None, ms_ssim: bool = True) -> Dict[str, FrameData]:
+                 results_path: Optional[str] = None, ms_ssim: bool = True,
+                 rate_breakdown_path: Optional[str] = None) -> Dict[str, FrameData]:
     """decode.py:26-91: decode a .cool file; returns {display index as str: FrameData}.  png_level: level of the
     device PNG packer when decoded_path is a .png (0 literal-only, 1 with LZ77 matches).
     source_path: the pictures the stream was encoded from; every decoded frame is then scored against them on the device
-    (decode_video_scored, which also returns the scores) and results_path, if given, receives one row per frame."""
+    (decode_video_scored, which also returns the scores) and results_path, if given, receives one row per frame.
+    rate_breakdown_path: receives the table of write_rate_breakdown (model bits per latent grid of every cool-chic)."""
+    if rate_breakdown_path is not None:
+        all_frames = decode_video(bitstream_path, decoded_path, max_decoding_order, verbosity, device, png_level, source_path,
+                                  results_path, ms_ssim)
+        write_rate_breakdown(bitstream_path, rate_breakdown_path, max_decoding_order, device)
+        return all_frames
     if source_path is not None or results_path is not None:
         return decode_video_scored(bitstream_path, source_path, decoded_path, max_decoding_order, verbosity, device, png_level,
                                    results_path, ms_ssim)[0]
@@ -177,6 +184,54 @@ def decode_video_scored(bitstream_path: str, source_path: str, decoded_path: Opt
         write_results(results_path, [(d, taken[d][0], fd.n_pixels, taken[d][1], q) for d, fd, q in zip(shown, frames, qualities)],
                       n_bytes_video_header)
     return all_frames, qualities
+
+
+def rate_breakdown(bitstream_path: str, max_decoding_order: int = -1, device: int = 0):
+    """Where the bits of a stream are: [(display index, cool-chic index in the frame, CCHeader, n_bytes_latent of the stream,
+    SlotRate)] for every cool-chic of the first max_decoding_order + 1 frames, in coding order.  The latents of all of them
+    are entropy-decoded in one DecodeBatch and handed to one EncodeBatch where they lie (add_from_decode: nothing crosses
+    PCIe), which prices them in one measure()."""
+    from ..encoder import EncodeBatch
+
+    with open(bitstream_path, "rb") as f:
+        rest = f.read()
+    vh = VideoHeader()
+    rest = vh.read_header(rest)
+    structure = vh.get_coding_structure()
+    n_decode = vh.get_value("n_frames") if max_decoding_order == -1 else max_decoding_order + 1
+    dec, enc = DecodeBatch(device), EncodeBatch(device)
+    try:
+        which = []
+        for k in range(n_decode):
+            _fh, ccs, rest = _split_frame(rest)
+            for i, (ch, nn, lat) in enumerate(ccs):
+                dec.add(ch.raw, nn, lat, 0, 0)
+                which.append((structure[k]["display_order"], i, ch.get_value("n_bytes_latent")))
+        stream = torch.cuda.current_stream(device).cuda_stream
+        dec.run(stream)
+        dec.wait(stream)
+        for slot in range(len(which)):
+            enc.add_from_decode(dec, slot)
+        enc.measure(stream)
+        enc.wait(stream)
+        return [(d, i, dec.header(slot), n_lat, enc.rate(slot)) for slot, (d, i, n_lat) in enumerate(which)]
+    finally:
+        enc.close()
+        dec.close()
+
+
+def write_rate_breakdown(bitstream_path: str, path: str, max_decoding_order: int = -1, device: int = 0):
+    """Tab-separated: one row per (display index, cool-chic, grid) with h, w, symbols and model_bits (24 - log2 of the coder's
+    interval width, summed over the grid; repr of the float64), then one row per cool-chic (grid "all") with the totals and
+    the bytes the stream spends on it: bytes_header, bytes_nn, bytes_latent (the header's n_bytes_latent)."""
+    rows = rate_breakdown(bitstream_path, max_decoding_order, device)
+    with open(path, "w") as f:
+        f.write("display\tcool_chic\tgrid\th\tw\tsymbols\tmodel_bits\tbytes_header\tbytes_nn\tbytes_latent\n")
+        for d, i, h, n_lat, r in rows:
+            for g in range(h.n_grids):
+                f.write(f"{d}\t{i}\t{g}\t{h.grid_h[g]}\t{h.grid_w[g]}\t{int(r.n_symbols[g])}\t{float(r.bits[g])!r}\t-\t-\t-\n")
+            f.write(f"{d}\t{i}\tall\t-\t-\t{int(r.n_symbols.sum())}\t{r.total_bits!r}\t{r.n_bytes_header}\t{r.n_bytes_nn}\t{n_lat}\n")
+    return rows
 
 
 def _decode_gop(rest: bytes, n_decode: int, device: int, group, verbosity: int = 0, collect: Optional[int] = 0,

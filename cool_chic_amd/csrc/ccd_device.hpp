@@ -63,6 +63,18 @@ struct EncodeParams {
     uint32_t cap_words;                          // ccd_enc_payload_bound(n_symbols) / 4
 };
 
+// The rate meter of the device writer (encode_rate_kernel / encode_rate_final_kernel, DESIGN.md 4.10 "rate meter"): what a slot
+// of a measure writes, next to the EncodeParams of the same index.  A symbol with the interval (left, width) costs
+// 24 - log2(width) bits; sum_width is the exact integer checksum of the intervals.
+struct RatePartial { double bits; uint64_t sum_width; };                  // one per workgroup of the rate kernel
+struct RateGrid { double bits; uint64_t sum_width; int64_t n_symbols; };  // one per grid
+struct RateParams {
+    RatePartial* partial;         // [n_blocks], indexed like the rate kernel's blockIdx.x
+    RateGrid* grids;              // [n_grids], followed by one double: the sum of bits over the grids 0 .. n_grids - 1
+    float* map[CCD_MAX_GRIDS];    // per grid [h][w] bits of every latent, raster; null without a map
+    int32_t* status;              // [0] error code of the slot
+};
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

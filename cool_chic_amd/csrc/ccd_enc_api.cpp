@@ -23,7 +23,11 @@ struct EncSlot {
     bool ran = false;              // part of a run that was waited for
     int status = CCD_OK;
     uint32_t n_words = 0;
+    bool measured = false;         // part of a measure that was waited for; `rate` and `map_off` are that measure's
+    ccd_enc_rate rate{};
+    size_t map_off = 0;            // floats before this slot's planes in the handle's map block
 };
+enum { kIdle = 0, kRun = 1, kMeasure = 2 };  // what ccd_enc::in_flight holds
 }  // namespace
 
 struct ccd_enc {
@@ -33,8 +37,16 @@ struct ccd_enc {
     Block table, table_host, status_dev, status_host;  // EncodeParams[n] (device, pinned), int32 [n][8] (device, pinned)
     size_t table_slots = 0;        // slots the four blocks above describe
     hipStream_t last_stream = nullptr;
-    bool in_flight = false;
+    int in_flight = kIdle;         // one run OR one measure at a time
+    int last_kind = kRun;          // what the last wait ended: whose per-slot errors an idle wait reports
     size_t n_run = 0;              // slots of the run in flight / last waited for
+    // the rate meter's own buffers: a run and a measure never write to the same place
+    Block rate_table, rate_table_host;     // RateParams[n] (device, pinned)
+    Block rate_slab, rate_out, rate_out_host, rate_map;  // partials; per slot RateGrid[n_grids] + total, then int32 status [n]
+    size_t rate_slots = 0, rate_out_bytes = 0, rate_status_off = 0;
+    bool rate_has_map = false;     // rate_table describes a map (the last measure asked for one)
+    size_t n_measured = 0;         // slots of the measure in flight / last waited for
+    bool map_valid = false;        // the last finished measure wrote a map
     std::vector<hipStream_t> streams;  // every stream a run was enqueued on (drained by destroy)
 };
 
@@ -67,6 +79,7 @@ void ccd_enc_destroy(ccd_enc* e) {
     for (hipStream_t st : e->streams) (void)hipStreamSynchronize(st);
     for (auto& s : e->slots) { s->params.drop(); s->pairs.drop(); s->out.drop(); }
     e->table.drop(); e->table_host.drop(); e->status_dev.drop(); e->status_host.drop();
+    e->rate_table.drop(); e->rate_table_host.drop(); e->rate_slab.drop(); e->rate_out.drop(); e->rate_out_host.drop(); e->rate_map.drop();
     delete e;
 }
 
@@ -190,14 +203,52 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
     return static_cast<int>(e->slots.size()) - 1;
 }
 
-int ccd_enc_run(ccd_enc* e, void* stream) {
-    if (!e) return CCD_ERR_ARG;
+namespace {
+// Takes in what the run or measure in flight left in the pinned buffers; the caller has synchronised its stream.
+void harvest(ccd_enc* e) {
+    if (e->in_flight == kRun) {
+        const int32_t* hs = e->status_host.as<int32_t>();
+        for (size_t i = 0; i < e->n_run; ++i) {
+            EncSlot& s = *e->slots[i];
+            s.ran = true;
+            s.status = hs[i * kEncStatusWords];
+            s.n_words = s.status == CCD_OK ? static_cast<uint32_t>(hs[i * kEncStatusWords + 1]) : 0;
+        }
+    } else if (e->in_flight == kMeasure) {
+        const char* out = e->rate_out_host.as<char>();
+        const int32_t* hs = reinterpret_cast<const int32_t*>(out + e->rate_status_off);
+        size_t off = 0;
+        for (size_t i = 0; i < e->n_measured; ++i) {
+            EncSlot& s = *e->slots[i];
+            const int n = s.hdr.n_grids;
+            ccd_enc_rate& r = s.rate;
+            std::memset(&r, 0, sizeof(r));
+            r.status = hs[i];
+            r.n_grids = n;
+            r.n_bytes_nn = static_cast<int64_t>(s.nn.size());
+            r.n_bytes_header = s.hdr.n_bytes_header;
+            if (r.status == CCD_OK) {  // a slot with an error reports no numbers
+                const RateGrid* rg = reinterpret_cast<const RateGrid*>(out + off);
+                for (int g = 0; g < n; ++g) { r.n_symbols[g] = rg[g].n_symbols; r.sum_width[g] = rg[g].sum_width; r.bits[g] = rg[g].bits; }
+                std::memcpy(&r.total_bits, rg + n, sizeof(double));
+            }
+            off += static_cast<size_t>(n) * sizeof(RateGrid) + sizeof(double);
+            s.measured = true;
+        }
+        e->map_valid = e->rate_has_map;
+    }
+    e->last_kind = e->in_flight;
+    e->in_flight = kIdle;
+}
+
+// What run and measure share: at most one of them in flight, and the EncodeParams table of the handle's slots.
+int prepare_launch(ccd_enc* e, hipStream_t st, unsigned* max_blocks, size_t* lds) {
     const size_t n = e->slots.size();
-    if (n == 0) return CCD_OK;
     HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (e->in_flight) HIP_TRY(hipStreamSynchronize(e->last_stream));  // one run in flight: its tables are about to be reused
-    e->in_flight = false;
+    if (e->in_flight != kIdle) {  // its tables are about to be reused
+        HIP_TRY(hipStreamSynchronize(e->last_stream));
+        harvest(e);
+    }
     if (e->table_slots != n) {
         e->table_slots = 0;
         if (!e->table.get(e->device, BlockPool::kDevice, n * sizeof(EncodeParams)) ||
@@ -211,20 +262,96 @@ int ccd_enc_run(ccd_enc* e, void* stream) {
         }
         e->table_slots = n;
     }
-    unsigned max_blocks = 0;
-    size_t lds = 0;
+    *max_blocks = 0;
+    *lds = 0;
     for (auto& s : e->slots) {
-        max_blocks = std::max<unsigned>(max_blocks, s->ep.n_blocks);
-        lds = std::max(lds, encode_contexts_lds_bytes(s->ep.ep.dim));
+        *max_blocks = std::max<unsigned>(*max_blocks, s->ep.n_blocks);
+        *lds = std::max(*lds, encode_contexts_lds_bytes(s->ep.ep.dim));
     }
     HIP_TRY(hipMemcpyAsync(e->table.p, e->table_host.p, n * sizeof(EncodeParams), hipMemcpyHostToDevice, st));
+    return CCD_OK;
+}
+
+void launched(ccd_enc* e, hipStream_t st, int kind) {
+    e->last_stream = st;
+    e->in_flight = kind;
+    if (std::find(e->streams.begin(), e->streams.end(), st) == e->streams.end()) e->streams.push_back(st);
+}
+}  // namespace
+
+int ccd_enc_run(ccd_enc* e, void* stream) {
+    if (!e) return CCD_ERR_ARG;
+    const size_t n = e->slots.size();
+    if (n == 0) return CCD_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    const int rc = prepare_launch(e, st, &max_blocks, &lds);
+    if (rc < 0) return rc;
     HIP_TRY(hipMemsetAsync(e->status_dev.p, 0, n * kEncStatusWords * sizeof(int32_t), st));
     HIP_TRY(launch_encode(e->table.as<EncodeParams>(), static_cast<int>(n), max_blocks, lds, st));
     HIP_TRY(hipMemcpyAsync(e->status_host.p, e->status_dev.p, n * kEncStatusWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    e->last_stream = st;
-    e->in_flight = true;
     e->n_run = n;
-    if (std::find(e->streams.begin(), e->streams.end(), st) == e->streams.end()) e->streams.push_back(st);
+    launched(e, st, kRun);
+    return CCD_OK;
+}
+
+int ccd_enc_measure(ccd_enc* e, void* stream, int want_map) {
+    if (!e) return CCD_ERR_ARG;
+    const size_t n = e->slots.size();
+    if (n == 0) return CCD_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    const int rc = prepare_launch(e, st, &max_blocks, &lds);
+    if (rc < 0) return rc;
+    const bool map = want_map != 0;
+    e->map_valid = false;  // the planes of the last measure are about to be overwritten or given back
+    if (e->rate_slots != n || e->rate_has_map != map) {
+        e->rate_slots = 0;
+        size_t n_blocks = 0, out_bytes = 0, n_map = 0;
+        for (auto& s : e->slots) {
+            n_blocks += s->ep.n_blocks;
+            out_bytes += static_cast<size_t>(s->hdr.n_grids) * sizeof(RateGrid) + sizeof(double);
+            n_map += s->ep.n_symbols;
+        }
+        e->rate_status_off = out_bytes;
+        e->rate_out_bytes = out_bytes + n * sizeof(int32_t);
+        if (!map) e->rate_map.drop();
+        if (!e->rate_table.get(e->device, BlockPool::kDevice, n * sizeof(RateParams)) ||
+            !e->rate_table_host.get(e->device, BlockPool::kPinned, n * sizeof(RateParams)) ||
+            !e->rate_slab.get(e->device, BlockPool::kDevice, std::max<size_t>(n_blocks * sizeof(RatePartial), 256)) ||
+            !e->rate_out.get(e->device, BlockPool::kDevice, e->rate_out_bytes) ||
+            !e->rate_out_host.get(e->device, BlockPool::kPinned, e->rate_out_bytes) ||
+            (map && !e->rate_map.get(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256))))
+            return CCD_ERR_NOMEM;
+        size_t block = 0, off = 0, cell = 0;
+        for (size_t i = 0; i < n; ++i) {
+            EncSlot& s = *e->slots[i];
+            RateParams& R = e->rate_table_host.as<RateParams>()[i];
+            std::memset(&R, 0, sizeof(R));
+            R.partial = e->rate_slab.as<RatePartial>() + block;
+            R.grids = reinterpret_cast<RateGrid*>(e->rate_out.as<char>() + off);
+            R.status = reinterpret_cast<int32_t*>(e->rate_out.as<char>() + e->rate_status_off) + i;
+            s.map_off = cell;
+            for (int g = 0; g < s.hdr.n_grids; ++g) {
+                if (map) R.map[g] = e->rate_map.as<float>() + cell;
+                cell += static_cast<size_t>(s.hdr.grid_h[g]) * s.hdr.grid_w[g];
+            }
+            block += s.ep.n_blocks;
+            off += static_cast<size_t>(s.hdr.n_grids) * sizeof(RateGrid) + sizeof(double);
+        }
+        e->rate_slots = n;
+        e->rate_has_map = map;
+    }
+    int max_grids = 0;
+    for (auto& s : e->slots) max_grids = std::max<int>(max_grids, s->hdr.n_grids);
+    HIP_TRY(hipMemcpyAsync(e->rate_table.p, e->rate_table_host.p, n * sizeof(RateParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(e->rate_out.p, 0, e->rate_out_bytes, st));
+    HIP_TRY(launch_encode_rate(e->table.as<EncodeParams>(), e->rate_table.as<RateParams>(), static_cast<int>(n), max_blocks, max_grids, lds, st));
+    HIP_TRY(hipMemcpyAsync(e->rate_out_host.p, e->rate_out.p, e->rate_out_bytes, hipMemcpyDeviceToHost, st));
+    e->n_measured = n;
+    launched(e, st, kMeasure);
     return CCD_OK;
 }
 
@@ -232,29 +359,46 @@ int ccd_enc_wait(ccd_enc* e, void* stream) {
     if (!e) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    if (e->in_flight) {
+    if (e->in_flight != kIdle) {
         if (e->last_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        e->in_flight = false;
-        const int32_t* hs = e->status_host.as<int32_t>();
-        for (size_t i = 0; i < e->n_run; ++i) {
-            EncSlot& s = *e->slots[i];
-            s.ran = true;
-            s.status = hs[i * kEncStatusWords];
-            s.n_words = s.status == CCD_OK ? static_cast<uint32_t>(hs[i * kEncStatusWords + 1]) : 0;
-        }
+        harvest(e);
+    }
+    if (e->last_kind == kMeasure) {
+        for (size_t i = 0; i < e->n_measured; ++i) if (e->slots[i]->rate.status < 0) return e->slots[i]->rate.status;
+        return CCD_OK;
     }
     for (size_t i = 0; i < e->n_run; ++i) if (e->slots[i]->status < 0) return e->slots[i]->status;
     return CCD_OK;
 }
 
+int ccd_enc_slot_rate(const ccd_enc* e, int slot, ccd_enc_rate* out) {
+    if (!e || !out || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kMeasure || !e->slots[slot]->measured)
+        return CCD_ERR_ARG;
+    *out = e->slots[slot]->rate;
+    return out->status;
+}
+
+int64_t ccd_enc_slot_rate_map(const ccd_enc* e, int slot, int grid, const float** device_ptr) {
+    if (!e || !device_ptr || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kMeasure || !e->map_valid ||
+        static_cast<size_t>(slot) >= e->n_measured || !e->slots[slot]->measured)
+        return CCD_ERR_ARG;
+    const EncSlot& s = *e->slots[slot];
+    if (grid < 0 || grid >= s.hdr.n_grids) return CCD_ERR_ARG;
+    if (s.rate.status < 0) return s.rate.status;
+    size_t off = s.map_off;
+    for (int g = 0; g < grid; ++g) off += static_cast<size_t>(s.hdr.grid_h[g]) * s.hdr.grid_w[g];
+    *device_ptr = e->rate_map.as<float>() + off;
+    return static_cast<int64_t>(s.hdr.grid_h[grid]) * s.hdr.grid_w[grid];
+}
+
 int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8) {
-    if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kRun || !e->slots[slot]->ran) return CCD_ERR_ARG;
     if (out8) std::memcpy(out8, e->status_host.as<int32_t>() + static_cast<size_t>(slot) * kEncStatusWords, kEncStatusWords * sizeof(int32_t));
     return e->slots[slot]->status;
 }
 
 int64_t ccd_enc_slot_payload(const ccd_enc* e, int slot, const uint8_t** device_ptr) {
-    if (!e || !device_ptr || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    if (!e || !device_ptr || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kRun || !e->slots[slot]->ran) return CCD_ERR_ARG;
     const EncSlot& s = *e->slots[slot];
     if (s.status < 0) return s.status;
     *device_ptr = s.out.as<uint8_t>();
@@ -262,7 +406,7 @@ int64_t ccd_enc_slot_payload(const ccd_enc* e, int slot, const uint8_t** device_
 }
 
 int64_t ccd_enc_slot_bytes(ccd_enc* e, int slot, uint8_t** out) {
-    if (!e || !out || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight || !e->slots[slot]->ran) return CCD_ERR_ARG;
+    if (!e || !out || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kRun || !e->slots[slot]->ran) return CCD_ERR_ARG;
     const EncSlot& s = *e->slots[slot];
     if (s.status < 0) return s.status;
     ccd_cc_header h = s.hdr;

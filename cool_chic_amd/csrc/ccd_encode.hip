@@ -15,6 +15,8 @@
 //   2. encode_chain_kernel: one wave per slot walks those intervals and runs the range encoder.  The intervals are
 //      fetched 64 at a time by the whole wave; the recurrence is wave-uniform and runs on the scalar unit; words leave
 //      through ordinary vector stores of lane 0.
+// The rate meter (encode_rate_kernel, encode_rate_final_kernel) shares stage 1's per-pixel work and sums 24 - log2(width)
+// per grid instead of running the chain.
 #include <hip/hip_runtime.h>
 
 #include "ccd_device.hpp"
@@ -25,30 +27,18 @@ namespace ccd {
 
 constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever reads the LDS column it wrote (no barrier)
 
-// ---- stage 1: contexts ------------------------------------------------------------------------------------------
-// blockIdx.y = slot, blockIdx.x = index into the slot's blocks: every grid owns ceil(H * W / 64) consecutive blocks
-// (EncodeParams::block_first), so the grid - and with it every network offset - is uniform in a workgroup.
-__global__ __launch_bounds__(kEncThreads) void encode_contexts_kernel(const EncodeParams* slots) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const EncodeParams& Q = slots[blockIdx.y];
-    const EntropyParams& P = Q.ep;
-    if (blockIdx.x >= Q.n_blocks) return;
-    const int lane = threadIdx.x;
-    const int n_grids = P.n_grids;
-    int g = 0;
-    while (g + 1 < n_grids && blockIdx.x >= Q.block_first[g + 1]) ++g;  // block_first grows with g
-    const int H = P.grid_h[g], W = P.grid_w[g];
-    const int p = static_cast<int>(blockIdx.x - Q.block_first[g]) * kEncThreads + lane;
-    if (p >= H * W) return;
-    const int y = p / W, x = p - y * W;
+// ---- what both stage-1 kernels do for one pixel -----------------------------------------------------------------
+// The interval [left, right) of symbol `sym` (already checked to be in the alphabet) at (y, x) of grid g: neighbour gather,
+// IFCE features of (y >> 1, x >> 1), the wrapping 64-bit ARM, the clamp to table indices, window_left of sym and sym + 1.
+// g is wave-uniform, so every weight is a scalar load; `smem_raw` holds the activations as [k][lane] columns and a lane only
+// touches its own column.  No cross-lane operation in here: a caller may skip it for some lanes.
+__device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, int g, int y, int x, int sym, int lane,
+                                                      unsigned char* smem_raw, uint32_t& left, uint32_t& right) {
     const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
     int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
     int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
     const int8_t* __restrict__ lat = P.latent[g];
-
-    // the pixel's own symbol: checked before anything depends on it (the host writer: CCD_ERR_VALUE)
-    const int sym = lat[p];
-    if (sym < kAcLo || sym > kAcLo + kAlphabet - 1) { P.status[0] = CCD_ERR_VALUE; return; }
+    const int n_grids = P.n_grids, W = P.grid_w[g];
 
     // ---- contexts, already << 16 (armint.py:193) ----
     for (int k = 0; k < n_sp; ++k) {
@@ -133,8 +123,32 @@ __global__ __launch_bounds__(kEncThreads) void encode_contexts_kernel(const Enco
     // ---- the symbol's interval under the leaky quantised Laplace model ----
     const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
     const double rcp = P.rcp_table[sc_idx];
-    const uint32_t left = window_left(mu, rcp, sym, kExpTab);           // 0 for -64
-    const uint32_t right = window_left(mu, rcp, sym + 1, kExpTab);      // 2^24 for 63
+    left = window_left(mu, rcp, sym, kExpTab);           // 0 for -64
+    right = window_left(mu, rcp, sym + 1, kExpTab);      // 2^24 for 63
+}
+
+// ---- stage 1: contexts ------------------------------------------------------------------------------------------
+// blockIdx.y = slot, blockIdx.x = index into the slot's blocks: every grid owns ceil(H * W / 64) consecutive blocks
+// (EncodeParams::block_first), so the grid - and with it every network offset - is uniform in a workgroup.
+__global__ __launch_bounds__(kEncThreads) void encode_contexts_kernel(const EncodeParams* slots) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.y];
+    const EntropyParams& P = Q.ep;
+    if (blockIdx.x >= Q.n_blocks) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    int g = 0;
+    while (g + 1 < n_grids && blockIdx.x >= Q.block_first[g + 1]) ++g;  // block_first grows with g
+    const int H = P.grid_h[g], W = P.grid_w[g];
+    const int p = static_cast<int>(blockIdx.x - Q.block_first[g]) * kEncThreads + lane;
+    if (p >= H * W) return;
+    const int y = p / W, x = p - y * W;
+
+    // the pixel's own symbol: checked before anything depends on it (the host writer: CCD_ERR_VALUE)
+    const int sym = P.latent[g][p];
+    if (sym < kAcLo || sym > kAcLo + kAlphabet - 1) { P.status[0] = CCD_ERR_VALUE; return; }
+    uint32_t left, right;
+    encode_pixel_interval(P, g, y, x, sym, lane, smem_raw, left, right);
 
     // ---- position in coding order (latent.py:66-140): raster if W <= 9, else steps c = x + 10 y, increasing y ----
     uint32_t idx = Q.grid_first[g];
@@ -218,6 +232,81 @@ __global__ __launch_bounds__(kEncThreads) void encode_chain_kernel(const EncodeP
     }
 }
 
+// ---- the rate meter: what the latents cost under the ARM, without the chain -----------------------------------------
+// A symbol whose interval has width w out of 2^24 costs 24 - log2(w) bits; the chain only turns the intervals into bytes.
+// Sums are formed in an order that depends on nothing but the grid's own size: 64 lanes through wave_sum's fixed tree, the
+// workgroups' partials lane-strided in block order and through the same tree.  No atomics, so a slot gives the same 64 bits
+// alone and inside any batch.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kEncThreads);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += static_cast<uint64_t>(__shfl_xor(static_cast<unsigned long long>(v), off, kEncThreads));
+    return v;
+}
+
+// Same grid as encode_contexts_kernel.  Tail lanes and lanes with a symbol outside the alphabet contribute 0 but stay
+// for the reduction: no lane leaves before the shuffles (the early return below is for a whole workgroup).
+__global__ __launch_bounds__(kEncThreads) void encode_rate_kernel(const EncodeParams* slots, const RateParams* rate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.y];
+    const EntropyParams& P = Q.ep;
+    const RateParams& R = rate[blockIdx.y];
+    if (blockIdx.x >= Q.n_blocks) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    int g = 0;
+    while (g + 1 < n_grids && blockIdx.x >= Q.block_first[g + 1]) ++g;
+    const int H = P.grid_h[g], W = P.grid_w[g];
+    const int p = static_cast<int>(blockIdx.x - Q.block_first[g]) * kEncThreads + lane;
+    double bits = 0.0;
+    uint64_t width = 0;
+    if (p < H * W) {
+        const int sym = P.latent[g][p];
+        if (sym < kAcLo || sym > kAcLo + kAlphabet - 1) R.status[0] = CCD_ERR_VALUE;
+        else {
+            const int y = p / W, x = p - y * W;
+            uint32_t left, right;
+            encode_pixel_interval(P, g, y, x, sym, lane, smem_raw, left, right);
+            width = right - left;  // 1 .. 2^24
+            bits = 24.0 - log2(static_cast<double>(width));
+            if (R.map[g]) R.map[g][p] = static_cast<float>(bits);
+        }
+    }
+    const double block_bits = wave_sum(bits);
+    const uint64_t block_width = wave_sum(width);
+    if (lane == 0) R.partial[blockIdx.x] = RatePartial{block_bits, block_width};
+}
+
+// One wave per (slot, grid): blockIdx.x = grid, blockIdx.y = slot.  Grid 0's wave also adds the per-grid sums up to the
+// slot's total, so it walks every grid's partials itself (a total that waited for the other waves would need a second
+// launch or a spin); the per-grid value it forms is the one that grid's own wave writes, addition for addition.
+__device__ __forceinline__ RatePartial rate_grid_sum(const RatePartial* __restrict__ partial, uint32_t first, uint32_t last, int lane) {
+    double bits = 0.0;
+    uint64_t width = 0;
+    for (uint32_t b = first + lane; b < last; b += kEncThreads) { bits += partial[b].bits; width += partial[b].sum_width; }
+    return RatePartial{wave_sum(bits), wave_sum(width)};
+}
+__global__ __launch_bounds__(kEncThreads) void encode_rate_final_kernel(const EncodeParams* slots, const RateParams* rate) {
+    const EncodeParams& Q = slots[blockIdx.y];
+    const RateParams& R = rate[blockIdx.y];
+    const int n_grids = Q.ep.n_grids, lane = threadIdx.x, g = blockIdx.x;
+    if (g >= n_grids) return;
+    const uint32_t last = g + 1 < n_grids ? Q.block_first[g + 1] : Q.n_blocks;
+    const RatePartial s = rate_grid_sum(R.partial, Q.block_first[g], last, lane);
+    if (lane == 0) R.grids[g] = RateGrid{s.bits, s.sum_width, static_cast<int64_t>(Q.ep.grid_h[g]) * Q.ep.grid_w[g]};
+    if (g != 0) return;
+    double total = s.bits;
+    for (int m = 1; m < n_grids; ++m) {  // bounded by CCD_MAX_GRIDS
+        const uint32_t end = m + 1 < n_grids ? Q.block_first[m + 1] : Q.n_blocks;
+        total += rate_grid_sum(R.partial, Q.block_first[m], end, lane).bits;
+    }
+    if (lane == 0) *reinterpret_cast<double*>(R.grids + n_grids) = total;
+}
+
 size_t encode_contexts_lds_bytes(int dim) { return static_cast<size_t>(2) * dim * kEncThreads * sizeof(int64_t); }
 int encode_block_threads() { return kEncThreads; }
 
@@ -234,6 +323,24 @@ hipError_t launch_encode(const EncodeParams* d_slots, int n_slots, unsigned max_
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(encode_chain_kernel, dim3(n_slots), dim3(kEncThreads), 0, stream, d_slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_rate(const EncodeParams* d_slots, const RateParams* d_rate, int n_slots, unsigned max_blocks, int max_grids,
+                              size_t lds_bytes, hipStream_t stream) {
+    if (n_slots <= 0) return hipSuccess;
+    if (max_blocks > 0) {
+        if (lds_bytes > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_rate_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(encode_rate_kernel, dim3(max_blocks, n_slots), dim3(kEncThreads), lds_bytes, stream, d_slots, d_rate);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (max_grids <= 0) return hipSuccess;
+    hipLaunchKernelGGL(encode_rate_final_kernel, dim3(max_grids, n_slots), dim3(kEncThreads), 0, stream, d_slots, d_rate);
     return hipGetLastError();
 }
 

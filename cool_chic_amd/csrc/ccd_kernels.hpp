@@ -70,4 +70,6 @@ hipError_t launch_spin(unsigned long long ticks, hipStream_t stream);
 size_t encode_contexts_lds_bytes(int dim);
 int encode_block_threads();
 hipError_t launch_encode(const EncodeParams* d_slots, int n_slots, unsigned max_blocks, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_encode_rate(const EncodeParams* d_slots, const RateParams* d_rate, int n_slots, unsigned max_blocks, int max_grids,
+                              size_t lds_bytes, hipStream_t stream);
 }  // namespace ccd

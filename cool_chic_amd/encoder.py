@@ -4,22 +4,34 @@ The bytes are those of writer.encode_coolchic (cool-chic header + NN payload + r
 bitstream/encode.py:83-92); the contexts of every pixel are evaluated at once and one wave per slot runs the range
 encoder's interval chain."""
 import ctypes as C
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import CCHeader, check, lib
+from ._lib import CcdError, CCHeader, EncRate, check, lib
 from .batch import DecodeBatch, _DevArray
 
 
+class SlotRate(NamedTuple):
+    """What measure() found for one slot: model bits (24 - log2 of the coder's interval width, summed) per latent grid."""
+    status: int             # 0, or the slot's error (the arrays are then zero)
+    bits: np.ndarray        # float64 [n_grids]
+    sum_width: np.ndarray   # uint64 [n_grids]: exact sum of the interval widths
+    n_symbols: np.ndarray   # int64 [n_grids]
+    total_bits: float       # bits summed in grid order on the device
+    n_bytes_nn: int
+    n_bytes_header: int
+
+
 class EncodeBatch:
-    """One slot per cool-chic; run() encodes all of them in the same two launches."""
+    """One slot per cool-chic; run() encodes all of them in the same two launches, measure() prices them without the chain."""
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
         check(lib().ccd_enc_create(int(device), C.byref(self._h)), "ccd_enc_create")
         self.device = int(device)
         self._owners: List[object] = []  # decode batches whose device latents the slots read at run()
+        self._grid_shapes: List[List[Tuple[int, int]]] = []  # per slot, per grid (h, w): the shape of a rate map
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -40,12 +52,15 @@ class EncodeBatch:
         """Host latents (index 0 = finest grid, values in [-64, 63]); returns the slot."""
         arrs = [np.ascontiguousarray(a, dtype=np.int8) for a in latents]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        return check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptrs, 0), "ccd_enc_add")
+        slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptrs, 0), "ccd_enc_add")
+        self._grid_shapes.append([a.shape[-2:] for a in arrs])
+        return slot
 
     def add_device(self, arch: CCHeader, bytes_nn: bytes, latent_ptrs: Sequence[int], owner=None) -> int:
         """Latents that already sit on the device (int8 [h][w] per grid); they are read when run() executes."""
         ptrs = (C.c_void_p * len(latent_ptrs))(*[int(p) for p in latent_ptrs])
         slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptrs, 1), "ccd_enc_add")
+        self._grid_shapes.append([(int(arch.grid_h[g]), int(arch.grid_w[g])) for g in range(len(latent_ptrs))])
         if owner is not None:
             self._owners.append(owner)
         return slot
@@ -62,6 +77,29 @@ class EncodeBatch:
 
     def wait(self, stream: int = 0):
         check(lib().ccd_enc_wait(self._h, C.c_void_p(stream or None)), "ccd_enc_wait")
+
+    def measure(self, stream: int = 0, rate_map: bool = False):
+        """Enqueues the rate meter for every slot (takes the place of a run in flight; wait() ends it)."""
+        check(lib().ccd_enc_measure(self._h, C.c_void_p(stream or None), int(bool(rate_map))), "ccd_enc_measure")
+
+    def rate(self, slot: int) -> SlotRate:
+        """After measure() + wait().  A slot with a poisoned device latent comes back with its status set, not as an exception."""
+        r = EncRate()
+        rc = lib().ccd_enc_slot_rate(self._h, int(slot), C.byref(r))
+        if rc < 0 and rc != r.status:
+            raise CcdError(rc, "ccd_enc_slot_rate")
+        n = r.n_grids
+        return SlotRate(int(r.status), np.array(r.bits[:n], np.float64), np.array(r.sum_width[:n], np.uint64),
+                        np.array(r.n_symbols[:n], np.int64), float(r.total_bits), int(r.n_bytes_nn), int(r.n_bytes_header))
+
+    def rate_map(self, slot: int, grid: int) -> _DevArray:
+        """Bits of every latent of a grid where measure(rate_map=True) left them (float32 [h][w], valid until the next
+        measure / close)."""
+        ptr = C.c_void_p()
+        n = check(lib().ccd_enc_slot_rate_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_enc_slot_rate_map")
+        h, w = self._grid_shapes[int(slot)][int(grid)]
+        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
+        return _DevArray(ptr.value or 0, (h, w), "<f4", self)
 
     def slot_status(self, slot: int) -> Tuple[int, np.ndarray]:
         """(status, counters) after wait(): counters[1] payload words, [2] inverted runs begun by the coder, [3] resolved

@@ -379,6 +379,32 @@ int64_t ccd_enc_slot_payload(const ccd_enc* e, int slot, const uint8_t** device_
  * exercised: [2] "inverted" runs begun (the interval straddled 2^64 at a word boundary), [3] runs resolved with a carry,
  * [4] resolved without one. */
 int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8);
+/* ---- rate meter: what a slot's latents cost under its ARM, without the range coder's serial chain.
+ * A symbol whose interval is (left, right) out of 2^24 costs 24 - log2(right - left) bits; a measure evaluates every
+ * interval like a run does and sums per latent grid, in float64, in an order that depends only on the grid's size: a slot
+ * gives the same 64 bits alone and inside any batch.  sum_width is the exact integer sum of (right - left) over the grid.
+ * ccd_enc_measure only enqueues on `stream`; it counts as the handle's one run in flight: ccd_enc_wait ends it and returns
+ * the first per-slot error, ccd_enc_destroy drains it.  want_map != 0 also leaves float32 bits of every latent on the device.
+ * Results of a measure and of a run live in separate buffers: a later ccd_enc_run does not invalidate ccd_enc_slot_rate, a
+ * later ccd_enc_measure does not invalidate ccd_enc_slot_bytes / _payload / _status.
+ * ccd_enc_slot_rate: the slot's status (0, or CCD_ERR_VALUE for a device latent outside [-64, 63]: out->status says the same
+ * and no numbers are reported; the other slots are unaffected); CCD_ERR_ARG for a NULL handle or `out`, a bad slot, or a slot
+ * no finished measure covered.
+ * ccd_enc_slot_rate_map: device pointer to grid_h[grid] * grid_w[grid] floats in raster order and their count; valid until
+ * the next measure / destroy.  CCD_ERR_ARG when the last measure had want_map == 0, for a bad slot or grid, a NULL argument.
+ * NULL handles are found before the device is touched. */
+typedef struct {
+    int32_t status;                      /* 0 or the slot's error */
+    int32_t n_grids;
+    int64_t n_symbols[CCD_MAX_GRIDS];
+    uint64_t sum_width[CCD_MAX_GRIDS];   /* exact: sum of (right - left) over the grid */
+    double bits[CCD_MAX_GRIDS];          /* sum of 24 - log2(width) over the grid */
+    double total_bits;                   /* sum of bits[] in grid order 0 .. n_grids - 1, added on the device */
+    int64_t n_bytes_nn, n_bytes_header;  /* what the slot's other bytes are: known at add */
+} ccd_enc_rate;
+int ccd_enc_measure(ccd_enc* e, void* stream, int want_map);
+int ccd_enc_slot_rate(const ccd_enc* e, int slot, ccd_enc_rate* out);
+int64_t ccd_enc_slot_rate_map(const ccd_enc* e, int slot, int grid, const float** device_ptr);
 /* Size of a slot's payload buffer: every symbol has a width of at least 1 / 2^24, so n symbols give at most
  * 4 * (ceil(24 n / 32) + 2) bytes.  0 for n < 0. */
 size_t ccd_enc_payload_bound(int64_t n_symbols);

@@ -3,7 +3,8 @@ kodim14 alone, the 24 streams of `kodak24` in one run, one 4K stream.  Device ti
 runs on, after warm-up runs, median of --runs; host times are wall clock of the same process.  Prints one JSON line.
 
 Per-kernel times (contexts / chain) come from a run of their own:
-    rocprofv3 --kernel-trace --stats -- python tools/encode_bench.py --runs 3 --no-host"""
+    rocprofv3 --kernel-trace --stats -- python tools/encode_bench.py --runs 3 --no-host
+--measure adds the rate meter (EncodeBatch.measure + wait, with and without the map) on the same handles."""
 import argparse
 import json
 import statistics
@@ -41,7 +42,7 @@ def decoded(streams, bitdepth=8):
     return dec
 
 
-def measure(streams, runs, host):
+def measure(streams, runs, host, rate=False):
     st = torch.cuda.current_stream().cuda_stream
     dec = decoded(streams)
     n_sym = sum(dec.header(s).n_symbols for s in range(len(streams)))
@@ -64,6 +65,17 @@ def measure(streams, runs, host):
     for s, bs in enumerate(streams):
         assert enc.bytes(s) == b"".join(synth.split_image_stream(bs)), s
     res["device_ns_per_symbol"] = round(res["device_encode_ms"] * 1e6 / n_sym, 2)
+    if rate:  # the rate meter on the same handle: measure() + wait(), without and with the per-latent map
+        for key, want_map in (("measure_ms", False), ("measure_map_ms", True)):
+            def rate_step():
+                enc.measure(st, rate_map=want_map)
+                enc.wait(st)
+
+            res[key] = round(event_ms(rate_step, runs), 3)
+        words = sum(int(enc.slot_status(s)[1][1]) for s in range(len(streams)))
+        res["model_bits"] = round(sum(enc.rate(s).total_bits for s in range(len(streams))), 3)
+        res["payload_bits"] = 32 * words
+        res["run_over_measure"] = round(res["device_encode_ms"] / res["measure_ms"], 1)
     if host:
         jobs = []
         for s in range(len(streams)):
@@ -88,13 +100,14 @@ def main():
     ap.add_argument("--runs", type=int, default=9)
     ap.add_argument("--no-host", action="store_true", help="skip the host writer (profiling runs)")
     ap.add_argument("--no-4k", action="store_true")
+    ap.add_argument("--measure", action="store_true", help="also time the rate meter (EncodeBatch.measure) beside every run")
     a = ap.parse_args()
     k24 = synth.workload("kodak24")["streams"]
     out = {"tool": "encode_bench", "runs": a.runs,
-           "kodim14": measure(k24[:1], a.runs, not a.no_host),
-           "kodak24": measure(k24, a.runs, not a.no_host)}
+           "kodim14": measure(k24[:1], a.runs, not a.no_host, a.measure),
+           "kodak24": measure(k24, a.runs, not a.no_host, a.measure)}
     if not a.no_4k:
-        out["uhd4k_one"] = measure([synth.image_stream(2160, 3840)], a.runs, not a.no_host)
+        out["uhd4k_one"] = measure([synth.image_stream(2160, 3840)], a.runs, not a.no_host, a.measure)
     print(json.dumps(out))
 
 
