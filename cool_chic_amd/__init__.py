@@ -14,11 +14,20 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    io.save_frame_data_to_file, io.FrameData
     bitstream.encode.encode_frame (range-coding of the latents, encode.py:83-92)
                                                    encoder.EncodeBatch, writer.encode_coolchic(device=...)
+    training.loss.loss_function on a candidate (distortion + lmbda * rate, training/loss.py:158)
+                                                   rd.RdEvaluator (exact integer ARM and integer planes, no search)
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
 from .encoder import EncodeBatch  # noqa: F401
 
+
+def __getattr__(name):
+    if name == "RdEvaluator":  # (rd.py needs torch at import: loaded when first asked for)
+        from .rd import RdEvaluator
+
+        return RdEvaluator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def pool_trim(device: int = 0) -> None:

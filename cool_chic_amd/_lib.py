@@ -103,6 +103,8 @@ SIGNATURES = {
     "ccd_batch_destroy": (None, [C.c_void_p]),
     "ccd_batch_add": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                 C.c_int, C.c_int]),
+    "ccd_batch_add_latents": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_int,
+                                        C.c_int, C.c_int]),
     "ccd_batch_size": (C.c_int, [C.c_void_p]),
     "ccd_batch_header": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CCHeader)]),
     "ccd_batch_prepare": (C.c_int, [C.c_void_p, C.c_void_p]),

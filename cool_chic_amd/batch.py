@@ -1,6 +1,6 @@
 """DecodeBatch: many cool-chics in flight on one MI355X (wraps the ccd_batch_* C ABI)."""
 import ctypes as C
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -55,11 +55,13 @@ class DecodeBatch:
             check(lib().ccd_batch_set_option(self._h, self.OPT_OVERLAP, int(bool(overlap))), "ccd_batch_set_option")
         self._meta: List[Tuple[int, int]] = []
         self._nn: List[bytes] = []
+        self._owners: List[object] = []  # whatever holds the device latents that given slots read at every run()
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().ccd_batch_destroy(self._h)
             self._h = C.c_void_p()
+            self._owners = []
 
     def __del__(self):
         try:
@@ -77,6 +79,42 @@ class DecodeBatch:
         self._meta.append((int(bitdepth), int(frame_data_type)))
         self._nn.append(bytes(bytes_nn))
         return slot
+
+    def _add_given(self, arch: CCHeader, bytes_nn: bytes, ptrs: Sequence[int], on_device: int, bitdepth: int, frame_data_type: int) -> int:
+        arr = (C.c_void_p * len(ptrs))(*[int(p) for p in ptrs])
+        slot = check(lib().ccd_batch_add_latents(self._h, C.byref(arch), bytes_nn, len(bytes_nn), arr, on_device, int(bitdepth),
+                                                 int(frame_data_type)), "ccd_batch_add_latents")
+        self._meta.append((int(bitdepth), int(frame_data_type)))
+        self._nn.append(bytes(bytes_nn))
+        return slot
+
+    def add_latents(self, arch: CCHeader, bytes_nn: bytes, latents: Sequence[np.ndarray], bitdepth: int = 0,
+                    frame_data_type: int = 0) -> int:
+        """A slot whose latents are GIVEN (host arrays, index 0 = finest grid, values in [-64, 63]) instead of range-coded: no
+        entropy work is launched for it, everything else is a coded slot's (ccd.h, ccd_batch_add_latents)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.int8) for a in latents]
+        return self._add_given(arch, bytes_nn, [a.ctypes.data for a in arrs], 0, bitdepth, frame_data_type)
+
+    def add_latents_device(self, arch: CCHeader, bytes_nn: bytes, latent_ptrs: Sequence[int], bitdepth: int = 0,
+                           frame_data_type: int = 0, owner=None) -> int:
+        """Latents that already sit on the device (int8 [h][w] per grid).  They are read at EVERY run(): change them in place,
+        run again, and the planes follow.  `owner` is kept alive with this batch."""
+        slot = self._add_given(arch, bytes_nn, latent_ptrs, 1, bitdepth, frame_data_type)
+        if owner is not None:
+            self._owners.append(owner)
+        return slot
+
+    def add_latents_from(self, batch: "DecodeBatch", slot: int, arch: Optional[CCHeader] = None, bytes_nn: Optional[bytes] = None,
+                         bitdepth: int = 0, frame_data_type: int = 0) -> int:
+        """The device latents of `slot` of `batch` (which has run, and is kept alive) under its own header and network or,
+        with `arch` / `bytes_nn`, under a candidate network over the same latents."""
+        return self.add_latents_device(arch if arch is not None else batch.header(slot),
+                                       bytes_nn if bytes_nn is not None else batch.network_bytes(slot),
+                                       batch.latent_ptrs(slot), bitdepth, frame_data_type, owner=batch)
+
+    def latent_ptrs(self, slot: int) -> List[int]:
+        """Device addresses of the slot's latent grids (int8 [h][w], index 0 = finest), valid while the batch lives."""
+        return [lib().ccd_batch_latent(self._h, slot, g) for g in range(self.header(slot).n_grids)]
 
     def network_bytes(self, slot: int) -> bytes:
         """The NN payload the slot was added with (what EncodeBatch.add_from_decode re-frames)."""
@@ -132,7 +170,8 @@ class DecodeBatch:
         """bit 0: pipelined entropy kernel, bit 1: fused synthesis kernel, bit 2: fused upsampling + synthesis kernel,
         bit 3: the ARM on the matrix cores, bit 4: the pipelined kernel's instantiation with the device check of IFCE features,
         bit 5: its instantiation with a compile-time ARM shape (HOP), bit 6: the fused float kernel behind the pyramid launch,
-        bit 7: the network is outside the finite envelope of the float stages (vector-ALU float kernels only, see ccd.h)."""
+        bit 7: the network is outside the finite envelope of the float stages (vector-ALU float kernels only, see ccd.h),
+        bit 8: the latents were given (add_latents*): no entropy kernel, bits 0, 3, 4, 5 clear."""
         return check(lib().ccd_batch_slot_kernels(self._h, slot), "ccd_batch_slot_kernels")
 
     def latent(self, slot: int, grid: int) -> np.ndarray:

@@ -289,6 +289,15 @@ static int run_prologue(ccd_batch* b, hipStream_t st) {
     return CCD_OK;
 }
 
+// head of stage 0: the grids of the slots whose latents are device pointers are read NOW, into the slots' arenas - one launch
+static int launch_ingest(ccd_batch* b, hipStream_t st) {
+    if (!b->n_ingest) return CCD_OK;
+    const int word = (b->ingest_runs & 1) ? kIngestWordB : 0;
+    HIP_TRY(launch_latent_ingest(b->d_ingest, b->d_ingest_prefix, b->n_ingest, b->n_ingest_blocks, b->d_status_all, word, st));
+    ++b->ingest_runs;
+    return CCD_OK;
+}
+
 int ccd_batch_run_stage(ccd_batch* b, void* stream, int stage) {
     if (!b || stage < 0 || stage > 2) return CCD_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -297,7 +306,10 @@ int ccd_batch_run_stage(ccd_batch* b, void* stream, int stage) {
     // stage 0: one launch per kernel instantiation and chain group in use.  The first goes to the caller's stream; the others fork
     // to side streams and join again, so that they overlap (each stream of a launch occupies one CU for its whole serial chain:
     // queued on one stream, a GOP whose I frames need another instantiation than its B frames took the SUM of the two).
-    if (stage == 0) return launch_entropy_groups(b, st, false);
+    if (stage == 0) {
+        const int ri = launch_ingest(b, st);
+        return ri < 0 ? ri : launch_entropy_groups(b, st, false);
+    }
     return launch_float_stage(b, st, stage, false);
 }
 
@@ -318,6 +330,8 @@ int ccd_batch_run(ccd_batch* b, void* stream) {
     int rc = run_prologue(b, st);
     if (rc < 0) return rc;
     const bool overlap = b->opt_overlap && b->pipe_groups.size() + (b->n_generic > 0 ? 1 : 0) > 1;
+    rc = launch_ingest(b, st);  // given slots: their float launches are keyed to no entropy launch and follow on `st`
+    if (rc < 0) return rc;
     rc = launch_entropy_groups(b, st, overlap);
     if (rc < 0) return rc;
     for (int stage = 1; stage <= 2; ++stage) {
@@ -345,6 +359,10 @@ int ccd_batch_wait(ccd_batch* b, void* stream) {
         for (size_t i = 0; i < n; ++i) {
             Slot& sl = *b->slots[i];
             std::memcpy(sl.host_status, hs + i * 64, sizeof(sl.host_status));
+            if (sl.given_device && b->ingest_runs) {  // the word the LAST ingest launch reported into (ccd_ingest.hip)
+                sl.host_status[0] = sl.host_status[((b->ingest_runs - 1) & 1) ? kIngestWordB : 0];
+                sl.host_status[kIngestWordB] = 0;
+            }
             sl.status = sl.host_status[0];
             if (first == CCD_OK && sl.status != CCD_OK) first = sl.status;
         }
@@ -388,7 +406,7 @@ int ccd_batch_entropy_launches(const ccd_batch* b) {
 int ccd_batch_slot_kernels(const ccd_batch* b, int slot) {
     if (!b || slot < 0 || slot >= static_cast<int>(b->slots.size())) return CCD_ERR_ARG;
     const Slot& s = *b->slots[slot];
-    return (s.use_pipe ? 1 : 0) | (s.use_fused_syn ? 2 : 0) | (s.use_fused_dec ? 4 : 0) | (s.use_mfma ? 8 : 0) | (s.use_dyn ? 16 : 0) | (s.fixed_shape ? 32 : 0) | (s.fdec_pre ? 64 : 0) | (s.float_finite ? 0 : 128);
+    return (s.use_pipe ? 1 : 0) | (s.use_fused_syn ? 2 : 0) | (s.use_fused_dec ? 4 : 0) | (s.use_mfma ? 8 : 0) | (s.use_dyn ? 16 : 0) | (s.fixed_shape ? 32 : 0) | (s.fdec_pre ? 64 : 0) | (s.float_finite ? 0 : 128) | (s.given ? 256 : 0);
 }
 
 const float* ccd_batch_output(const ccd_batch* b, int slot) {

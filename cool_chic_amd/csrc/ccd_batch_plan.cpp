@@ -77,6 +77,7 @@ struct SlotPlan {
     int n_levels = 0, max_c = 0;
     bool need_resize = false;
     std::vector<float> syn_blob;   // synthesis parameters: the layers as transmitted, then the fused kernels' own copies
+    const int8_t* const* host_latents = nullptr;  // given latents on the host: they go up with the head
     SlotLayout at;
 };
 
@@ -328,7 +329,9 @@ void layout_arena(const ccd_batch* b, Slot& s, SlotPlan& p) {
     at.head_bytes = A.total();
     at.lat.resize(h.n_grids);
     for (int g = 0; g < h.n_grids; ++g) at.lat[g] = A.reserve(static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]);
+    if (p.host_latents) at.head_bytes = A.total();  // given on the host: the grids are part of what is uploaded
     // int32 planes (generic kernel) or int16 planes + int32 side planes in the second half (pipelined kernel)
+    if (s.given) feat_px = 1;  // no entropy kernel, no IFCE features
     at.feat_elems = feat_px * std::max(h.output_feature_ifce, 1);
     at.feat = A.reserve(at.feat_elems * 8);
     if (s.cr) {
@@ -375,9 +378,11 @@ int upload_head(ccd_batch* b, Slot& s, const SlotPlan& p, const uint8_t* bytes_l
     std::memset(st + at.status, 0, 512);
     if (p.n_words) std::memcpy(st + at.words, bytes_latent, p.n_words * 4);
     std::memset(st + at.words + p.n_words * 4, 0, 8);
-    std::memcpy(st + at.arm, p.blobs.arm.data(), p.blobs.arm.size() * 8);
+    if (!p.blobs.arm.empty()) std::memcpy(st + at.arm, p.blobs.arm.data(), p.blobs.arm.size() * 8);
     if (!p.blobs.ifce.empty()) std::memcpy(st + at.ifce, p.blobs.ifce.data(), p.blobs.ifce.size() * 8);
     if (!p.syn_blob.empty()) std::memcpy(st + at.synp, p.syn_blob.data(), p.syn_blob.size() * 4);
+    if (p.host_latents)
+        for (int g = 0; g < s.hdr.n_grids; ++g) std::memcpy(st + at.lat[g], p.host_latents[g], static_cast<size_t>(s.hdr.grid_h[g]) * s.hdr.grid_w[g]);
     if (hipMemcpyAsync(A.at<void>(0), st, at.head_bytes, hipMemcpyHostToDevice, b->up_stream) != hipSuccess) return fail(CCD_ERR_HIP);
     if (hipEventRecord(b->up_done, b->up_stream) != hipSuccess) return fail(CCD_ERR_HIP);
     b->uploads_unconfirmed = true;
@@ -500,6 +505,31 @@ void bind_float_path(const ccd_batch* b, Slot& s, const SlotPlan& p) {
 }
 }  // namespace
 
+// ---- 8. what ccd_batch_add and ccd_batch_add_latents share once the slot is parsed: plan, lay out, upload, bind ------------
+static int place_slot(ccd_batch* b, std::unique_ptr<Slot> sp, SlotPlan& p, const uint8_t* bytes_latent) {
+    Slot& s = *sp;
+    int rc = CCD_OK;
+    if (s.given) pack_int_networks(s.hdr, s.net, p.blobs);  // (the arena keeps its layout; no entropy kernel is chosen)
+    else rc = choose_entropy_kernel(b, s, p);
+    if (rc >= 0) rc = float_geometry(s, p);
+    if (rc < 0) return rc;
+    layout_synthesis(b, s, p);
+    layout_fused_dec(b, s, p);
+    layout_arena(b, s, p);
+    HIP_TRY(hipSetDevice(b->device));
+    rc = s.arena.commit(b->device);
+    if (rc >= 0) rc = upload_head(b, s, p, bytes_latent);
+    if (rc < 0) return rc;
+    bind_entropy_and_levels(b, s, p);
+    bind_float_path(b, s, p);
+    if (!s.given) {
+        if (s.use_pipe) b->lds_pipe = std::max(b->lds_pipe, s.lds_pipe);
+        else b->lds_generic = std::max(b->lds_generic, s.lds_generic);
+    }
+    b->slots.push_back(std::move(sp));
+    return static_cast<int>(b->slots.size()) - 1;
+}
+
 extern "C" int ccd_batch_add(ccd_batch* b, const uint8_t* cc_header, size_t n_hdr, const uint8_t* bytes_nn, size_t n_nn,
                              const uint8_t* bytes_latent, size_t n_lat, int bitdepth, int frame_data_type) {
     if (!b || !cc_header || !bytes_nn || (!bytes_latent && n_lat)) return CCD_ERR_ARG;
@@ -507,25 +537,49 @@ extern "C" int ccd_batch_add(ccd_batch* b, const uint8_t* cc_header, size_t n_hd
     HIP_TRY(hipSetDevice(b->device));
     std::unique_ptr<Slot> sp(new (std::nothrow) Slot());
     if (!sp) return CCD_ERR_NOMEM;
-    Slot& s = *sp;
     SlotPlan p;
     p.n_words = n_lat / 4;
-    int rc = parse_slot(s, cc_header, n_hdr, bytes_nn, n_nn, n_lat, bitdepth, frame_data_type);
-    if (rc >= 0) rc = choose_entropy_kernel(b, s, p);
-    if (rc >= 0) rc = float_geometry(s, p);
+    const int rc = parse_slot(*sp, cc_header, n_hdr, bytes_nn, n_nn, n_lat, bitdepth, frame_data_type);
     if (rc < 0) return rc;
-    layout_synthesis(b, s, p);
-    layout_fused_dec(b, s, p);
-    layout_arena(b, s, p);
-    rc = s.arena.commit(b->device);
-    if (rc >= 0) rc = upload_head(b, s, p, bytes_latent);
+    return place_slot(b, std::move(sp), p, bytes_latent);
+}
+
+extern "C" int ccd_batch_add_latents(ccd_batch* b, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn,
+                                     const int8_t* const* latents, int on_device, int bitdepth, int frame_data_type) {
+    if (!b || !arch || !bytes_nn || !latents) return CCD_ERR_ARG;
+    if (bitdepth != 0 && (bitdepth < 8 || bitdepth > 16)) return CCD_ERR_ARG;
+    std::unique_ptr<Slot> sp(new (std::nothrow) Slot());
+    if (!sp) return CCD_ERR_NOMEM;
+    Slot& s = *sp;
+    // ---- everything the host can refuse, before the device is touched ----
+    uint8_t hb[256];
+    int n_hb = -1;
+    {   // the header a coded slot would have brought: the transmitted fields, serialised (like ccd_enc_add) with an empty payload
+        ccd_cc_header t = *arch;
+        t.nn_n_bytes = static_cast<int32_t>(n_nn);
+        t.n_bytes_latent = 0;
+        if (t.n_layer_synthesis >= 0 && t.n_layer_synthesis <= CCD_MAX_SYN_LAYERS) n_hb = ccd_write_cc_header(&t, hb, sizeof(hb));
+        if (n_hb < 0) return CCD_ERR_VALUE;
+    }
+    const int rc = parse_slot(s, hb, static_cast<size_t>(n_hb), bytes_nn, n_nn, 0, bitdepth, frame_data_type);
     if (rc < 0) return rc;
-    bind_entropy_and_levels(b, s, p);
-    bind_float_path(b, s, p);
-    if (s.use_pipe) b->lds_pipe = std::max(b->lds_pipe, s.lds_pipe);
-    else b->lds_generic = std::max(b->lds_generic, s.lds_generic);
-    b->slots.push_back(std::move(sp));
-    return static_cast<int>(b->slots.size()) - 1;
+    const ccd_cc_header& h = s.hdr;
+    if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;  // (a segment's length is 32 bits)
+    for (int g = 0; g < h.n_grids; ++g) if (!latents[g]) return CCD_ERR_ARG;
+    SlotPlan p;
+    s.given = true;
+    s.given_device = on_device != 0;
+    if (on_device) {
+        for (int g = 0; g < h.n_grids; ++g) s.given_src[g] = latents[g];
+    } else {
+        for (int g = 0; g < h.n_grids; ++g) {
+            const size_t cnt = static_cast<size_t>(h.grid_h[g]) * h.grid_w[g];
+            for (size_t i = 0; i < cnt; ++i)
+                if (latents[g][i] < kAcLo || latents[g][i] > kAcLo + kAlphabet - 1) return CCD_ERR_VALUE;
+        }
+        p.host_latents = latents;
+    }
+    return place_slot(b, std::move(sp), p, nullptr);
 }
 
 // Chain groups of a batch (pure: ccd_debug_chain_groups exposes it to the CPU tests).  est[i]: expected chain of slot i; inst[i]: its
@@ -606,6 +660,8 @@ struct LaunchTables {
     std::vector<Work> work, pyr_work;
     std::vector<UpsampleLevel> levels;
     std::vector<uint32_t> zmap;
+    std::vector<IngestSeg> ingest;
+    std::vector<uint32_t> ingest_prefix;  // [segments + 1]
 };
 
 // Entropy launches.  The pipelined kernel is instantiated per input width nv = ceil(dim / 4): one launch per width.
@@ -623,9 +679,13 @@ void plan_entropy_groups(ccd_batch* b, LaunchTables& t) {
     std::vector<double> est(n, 0.0);
     std::vector<int> cg_of(n, 0), inst_of(n, -1);
     {
+        // the slots whose latents are range-coded: a slot with GIVEN latents belongs to no entropy launch and is not planned for
+        std::vector<int> coded;
         std::vector<std::array<int, 3>> insts;
         for (int i = 0; i < n; ++i) {
             const Slot& sl = *b->slots[i];
+            if (sl.given) continue;
+            coded.push_back(i);
             est[i] = chain_estimate(sl.ep);
             if (!sl.use_pipe) continue;  // (-1: the generic launch)
             const std::array<int, 3> key{(sl.ep.dim + 3) / 4, sl.use_mfma ? 2 : (sl.use_dyn ? 1 : 0), sl.fixed_shape};
@@ -636,7 +696,12 @@ void plan_entropy_groups(ccd_batch* b, LaunchTables& t) {
         // as many launches as streams really run at once (DeviceShared::n_conc, measured), shared between the instantiations
         int n_conc = 1, n_cu = 256;
         { DeviceShared* shd = nullptr; if (device_shared(b->device, &shd) >= 0) { n_conc = shd->n_conc; n_cu = shd->n_cu; } }
-        plan_chain_groups(est.data(), inst_of.data(), n, b->opt_overlap ? n_conc : 1, n_cu, cg_of.data());
+        const int nc = static_cast<int>(coded.size());
+        std::vector<double> est_c(nc);
+        std::vector<int> inst_c(nc), cg_c(nc, 0);
+        for (int k = 0; k < nc; ++k) { est_c[k] = est[coded[k]]; inst_c[k] = inst_of[coded[k]]; }
+        plan_chain_groups(est_c.data(), inst_c.data(), nc, b->opt_overlap ? n_conc : 1, n_cu, cg_c.data());
+        for (int k = 0; k < nc; ++k) cg_of[coded[k]] = cg_c[k];
     }
     for (int nv = 1; nv <= 8; ++nv)
         for (int var = 0; var < 3; ++var)  // vector ALU without / with the device check of the features, matrix cores
@@ -663,8 +728,28 @@ void plan_entropy_groups(ccd_batch* b, LaunchTables& t) {
         sl.fl = (b->opt_overlap && sl.use_pipe) ? sl.lg : -1;
     }
     b->n_pipe = static_cast<int>(host.size());
-    for (int i = 0; i < n; ++i) if (!b->slots[i]->use_pipe) { host.push_back(b->slots[i]->ep); host_slot.push_back(i); }
-    b->n_generic = n - b->n_pipe;
+    for (int i = 0; i < n; ++i) if (!b->slots[i]->use_pipe && !b->slots[i]->given) { host.push_back(b->slots[i]->ep); host_slot.push_back(i); }
+    b->n_generic = static_cast<int>(host.size()) - b->n_pipe;
+}
+
+// the ingest launch (ccd_ingest.hip): a segment per grid of every slot whose latents are device pointers, and the first
+// workgroup of each segment
+void plan_ingest(ccd_batch* b, LaunchTables& t) {
+    uint32_t blocks = 0;
+    for (size_t i = 0; i < b->slots.size(); ++i) {
+        const Slot& s = *b->slots[i];
+        if (!s.given_device) continue;
+        for (int g = 0; g < s.hdr.n_grids; ++g) {
+            const uint32_t cnt = static_cast<uint32_t>(s.hdr.grid_h[g]) * static_cast<uint32_t>(s.hdr.grid_w[g]);
+            if (!cnt) continue;
+            t.ingest.push_back({s.given_src[g], s.ep.latent[g], cnt, static_cast<int32_t>(i)});
+            t.ingest_prefix.push_back(blocks);
+            blocks += (cnt + kIngestChunk - 1) / kIngestChunk;
+        }
+    }
+    if (!t.ingest.empty()) t.ingest_prefix.push_back(blocks);
+    b->n_ingest = static_cast<int>(t.ingest.size());
+    b->n_ingest_blocks = blocks;
 }
 
 // fused synthesis: one launch per (CP, C) group over all of its frames
@@ -809,7 +894,10 @@ int pack_and_upload(ccd_batch* b, LaunchTables& t, hipStream_t st) {
     const size_t o_pyr = o_zmap + up256(sizeof(uint32_t) * std::max<size_t>(t.zmap.size(), 1));
     const size_t o_pyrw = o_pyr + up256(sizeof(FusedDec) * std::max<size_t>(t.pyr_frames.size(), 1));
     const size_t o_stat = o_pyrw + up256(sizeof(Work) * std::max<size_t>(t.pyr_work.size(), 1));
-    const size_t total = o_stat + up256(static_cast<size_t>(std::max(n, 1)) * 64 * sizeof(int32_t));
+    // (the ingest tables come last and only exist with device-latent slots: every other batch keeps the layout it had)
+    const size_t o_ingest = o_stat + up256(static_cast<size_t>(std::max(n, 1)) * 64 * sizeof(int32_t));
+    const size_t o_ingestp = o_ingest + (t.ingest.empty() ? 0 : up256(sizeof(IngestSeg) * t.ingest.size()));
+    const size_t total = o_ingestp + (t.ingest.empty() ? 0 : up256(sizeof(uint32_t) * t.ingest_prefix.size()));
     // the previous tables may still be read by launches in flight on the caller's stream (a batch that grew between runs)
     if (b->tables.p && b->drain_streams() < 0) return CCD_ERR_HIP;
     if (!b->tables.get(b->device, BlockPool::kDevice, total) || !b->tables_staging.get(b->device, BlockPool::kPinned, total) ||
@@ -826,14 +914,15 @@ int pack_and_upload(ccd_batch* b, LaunchTables& t, hipStream_t st) {
     b->d_pyr = reinterpret_cast<FusedDec*>(dev + o_pyr);
     b->d_pyr_work = dev + o_pyrw;
     b->d_status_all = reinterpret_cast<int32_t*>(dev + o_stat);
-    for (int k = 0; k < n; ++k) {
-        t.params[k].status = b->d_status_all + static_cast<size_t>(t.params_slot[k]) * 64;
-        b->slots[t.params_slot[k]]->d_status = t.params[k].status;
-    }
+    b->d_ingest = reinterpret_cast<IngestSeg*>(dev + o_ingest);
+    b->d_ingest_prefix = reinterpret_cast<uint32_t*>(dev + o_ingestp);
+    for (size_t k = 0; k < t.params.size(); ++k) t.params[k].status = b->d_status_all + static_cast<size_t>(t.params_slot[k]) * 64;
+    for (int i = 0; i < n; ++i) b->slots[i]->d_status = b->d_status_all + static_cast<size_t>(i) * 64;
     const auto put = [&](size_t off, const auto& v) { if (!v.empty()) std::memcpy(stg + off, v.data(), sizeof(v[0]) * v.size()); };
     put(o_params, t.params); put(o_fusedt, t.fused); put(o_fdec, t.frames); put(o_work, t.work);
     put(o_levels, t.levels); put(o_zmap, t.zmap); put(o_pyr, t.pyr_frames); put(o_pyrw, t.pyr_work);
-    std::memset(stg + o_stat, 0, total - o_stat);
+    std::memset(stg + o_stat, 0, o_ingest - o_stat);  // every status word starts as CCD_OK: a given slot's is never written unless a latent is refused
+    put(o_ingest, t.ingest); put(o_ingestp, t.ingest_prefix);
     HIP_TRY(hipMemcpyAsync(dev, stg, total, hipMemcpyHostToDevice, st));
     // a later run on ANOTHER stream (ccd_batch_prepare on one, ccd_batch_run on the next) orders itself behind this copy
     if (!b->params_up) HIP_TRY(hipEventCreateWithFlags(&b->params_up, hipEventDisableTiming));
@@ -849,6 +938,7 @@ int ccd::build_launch_tables(ccd_batch* b, hipStream_t st) {
     b->regroup = false;
     LaunchTables t;
     plan_entropy_groups(b, t);
+    plan_ingest(b, t);
     plan_fused_syn_groups(b, t);
     plan_fdec_groups(b, t);
     plan_pyr_groups(b, t);

@@ -75,6 +75,17 @@ struct RateParams {
     int32_t* status;              // [0] error code of the slot
 };
 
+// One copy of the ingest launch (ccd_ingest.hip): latent grid `src` of a slot whose latents were GIVEN as device pointers
+// (ccd_batch_add_latents) goes to `dst`, where the entropy kernel would have left it.  The segments of one slot are adjacent.
+struct IngestSeg {
+    const int8_t* src;
+    int8_t* dst;
+    uint32_t n;       // bytes = grid_h * grid_w
+    int32_t slot;     // its status words are [64 slot, 64 slot + 64) of the batch's status array
+};
+constexpr uint32_t kIngestChunk = 4096;  // bytes one 64-lane workgroup of the ingest launch copies
+constexpr int kIngestWordB = 4;          // the second of the two status words a given slot alternates between (ccd_ingest.hip)
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

@@ -137,6 +137,10 @@ struct Slot {
     size_t lds_generic = 0, lds_pipe = 0;
     int lg = -1;             // entropy launch of the batch this slot is decoded by (index into ccd_batch::pipe_groups; -1: the generic launch)
     int fl = -1;             // launch group its float-path launches are keyed by (= lg while ccd_batch_run overlaps; -1: not keyed)
+    // latents GIVEN instead of range-coded (ccd_batch_add_latents): no entropy launch holds the slot.  Host latents went up with
+    // the head; device latents are copied from given_src[g] at the head of every run (ccd_ingest.hip)
+    bool given = false, given_device = false;
+    const int8_t* given_src[CCD_MAX_GRIDS] = {};
     int status = CCD_OK;
     int32_t host_status[64] = {0};
 };
@@ -225,4 +229,10 @@ struct ccd_batch {
     std::vector<UpsStep> ups_steps;
     ccd::UpsampleLevel* d_levels = nullptr;
     uint32_t* d_zmap = nullptr;
+    // the ingest launch of the slots whose latents are device pointers: one segment per grid, a prefix of 64-lane workgroups
+    ccd::IngestSeg* d_ingest = nullptr;
+    uint32_t* d_ingest_prefix = nullptr;
+    int n_ingest = 0;
+    uint32_t n_ingest_blocks = 0;
+    unsigned ingest_runs = 0;            // ingest launches so far: launch k reports into status word (k & 1) * kIngestWordB
 };

@@ -1,0 +1,114 @@
+"""RdEvaluator: rate, distortion and D + lambda R of candidate (latents, networks) on one MI355X, without a serial chain.
+
+The three device meters behind one call: the candidates' planes come from the float path over GIVEN
+latents (DecodeBatch.add_latents*, ccd_batch_add_latents), their rate from the rate meter (EncodeBatch.measure) and their
+distortion from the quality meter (QualityMeter.score_planes).  Neither the range encoder's nor the range decoder's chain runs.
+
+The cost has the shape of the reference's loss (training/loss.py:158 loss_function: distortion + lmbda * rate in bits per
+pixel, the frame's MSE weighted by plane size for 4:2:0, loss.py:88-118):
+
+    mse      = sum of squared errors over all planes / (n_samples * (2^bitdepth - 1)^2)
+    bits     = total_bits + 8 * (n_bytes_nn + n_bytes_header)
+    cost     = mse + lmbda * bits / n_pixels            (n_pixels: the luma size)
+
+It differs from the reference's in two stated ways.  The distortion is that of the INTEGER planes a decoder writes (the
+reference trains on the float synthesis output and only its final test pass quantises to the bit depth), and the rate of the
+latents is the decoder's exact integer ARM priced as model bits, 24 - log2(interval width) per symbol, not the float rate
+estimate of training and not the coded bytes (the payload is 0 to 3 words above ceil(total_bits / 32)).  The
+cost is computed on the host in float64 from the device's exact integer squared error and its total_bits.
+
+Intra frames only: one cool-chic per frame.  P / B frames (two cool-chics and a reconstruction) are not evaluated here;
+ccd_batch_add_latents itself takes any cool-chic."""
+from typing import List, NamedTuple, Sequence, Union
+
+import numpy as np
+import torch
+
+from ._lib import CCHeader
+from .batch import FRAME_DATA_TYPES, DecodeBatch
+from .encoder import EncodeBatch, SlotRate
+from .io import FrameData
+from .quality import FrameQuality, QualityMeter, _frame_planes
+
+
+class Candidate(NamedTuple):
+    rate: SlotRate
+    quality: FrameQuality
+    mse: float
+    bits: float
+    cost: float
+
+
+def rd_cost(sse: Sequence[int], n: Sequence[int], bitdepth: int, total_bits: float, n_bytes_nn: int, n_bytes_header: int,
+            n_pixels: int, lmbda: float):
+    """(mse, bits, cost) in float64 from the device's integers: the definition in this module's docstring."""
+    maxv = float(2 ** bitdepth - 1)
+    mse = float(sum(int(v) for v in sse)) / (float(sum(int(v) for v in n)) * maxv * maxv)
+    bits = float(total_bits) + 8.0 * float(int(n_bytes_nn) + int(n_bytes_header))
+    return mse, bits, mse + float(lmbda) * bits / float(n_pixels)
+
+
+class RdEvaluator:
+    """add() candidates, then evaluate(lmbda): one DecodeBatch of given latents, one EncodeBatch over the same device grids,
+    one scoring.  evaluate() may be called again (another lambda, or after device latents were changed in place)."""
+
+    def __init__(self, device: int = 0):
+        self.device = int(device)
+        self._dec = DecodeBatch(self.device)
+        self._enc = EncodeBatch(self.device)
+        self._meter = QualityMeter(self.device)
+        self._sources: List[List[torch.Tensor]] = []
+        self._frames: List[FrameData] = []
+
+    def close(self):
+        self._enc.close()
+        self._dec.close()
+        self._meter.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self._frames)
+
+    def add(self, arch: CCHeader, bytes_nn: bytes, latents_or_ptrs: Sequence[Union[np.ndarray, int]], source: FrameData, owner=None) -> int:
+        """A candidate: host latent arrays (uploaded once, here) or device addresses (int8 [h][w] per grid, read at every
+        evaluate(); `owner` keeps them alive), and the frame it is scored against."""
+        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
+            raise ValueError(f"cannot score a {source.frame_data_type} frame")
+        fdt = FRAME_DATA_TYPES.index(source.frame_data_type)
+        if all(isinstance(x, (int, np.integer)) for x in latents_or_ptrs):
+            slot = self._dec.add_latents_device(arch, bytes_nn, latents_or_ptrs, source.bitdepth, fdt, owner=owner)
+        else:
+            slot = self._dec.add_latents(arch, bytes_nn, latents_or_ptrs, source.bitdepth, fdt)
+        h = self._dec.header(slot)
+        if tuple(h.img_size) != tuple(source.img_size):
+            raise ValueError(f"the candidate decodes to {h.img_size[0]}x{h.img_size[1]}, its source is {source.img_size[0]}x{source.img_size[1]}")
+        # the rate meter reads the grids where the decode batch keeps them: host latents crossed PCIe once
+        self._enc.add_device(arch, bytes_nn, self._dec.latent_ptrs(slot), owner=self._dec)
+        self._sources.append(_frame_planes(source, torch.device(f"cuda:{self.device}")))
+        self._frames.append(source)
+        return slot
+
+    def evaluate(self, lmbda: float, ms_ssim: bool = False) -> List[Candidate]:
+        n = len(self._frames)
+        if n == 0:
+            return []
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        self._dec.run(st)           # ingest of device latents, then the float path: the grids are in the arenas behind this
+        self._enc.measure(st)       # same stream: reads the arenas' grids
+        decoded = [[torch.as_tensor(self._dec.plane_device(s, p), device=f"cuda:{self.device}") for p in range(3)] for s in range(n)]
+        self._meter.score_planes_async(decoded, self._sources, [f.bitdepth for f in self._frames], ms_ssim, stream=st)
+        results = self._meter.finish()
+        self._dec.wait(st)          # a refused device latent raises here (CCD_ERR_VALUE)
+        self._enc.wait(st)
+        out = []
+        for s, (r, f) in enumerate(zip(results, self._frames)):
+            rate = self._enc.rate(s)
+            q = FrameQuality.from_result(r, f.bitdepth, f.frame_data_type)
+            mse, bits, cost = rd_cost(q.sse, q.n, f.bitdepth, rate.total_bits, rate.n_bytes_nn, rate.n_bytes_header, f.n_pixels, lmbda)
+            out.append(Candidate(rate, q, mse, bits, cost))
+        return out

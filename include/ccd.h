@@ -135,6 +135,30 @@ void ccd_batch_destroy(ccd_batch* b);
  * the integer output planes (decode.py:191-206); pass bitdepth 0 to skip integer planes. */
 int ccd_batch_add(ccd_batch* b, const uint8_t* cc_header, size_t n_hdr, const uint8_t* bytes_nn, size_t n_nn,
                   const uint8_t* bytes_latent, size_t n_lat, int bitdepth, int frame_data_type);
+/* A slot whose latent grids are GIVEN instead of range-coded: no entropy work is launched for it.  What a caller that holds
+ * candidate latents and networks (an encoder's search, a test pass) needs to see the planes they decode to, without writing a
+ * payload (ccd_enc_run) and entropy-decoding it again.  `arch`, `bytes_nn` and `latents` are those of ccd_enc_add: the
+ * transmitted fields of `arch` are read, latents[g] = int8 [grid_h[g]][grid_w[g]], index 0 the finest grid; bitdepth and
+ * frame_data_type are those of ccd_batch_add.  Returns the slot index.
+ * The slot is parsed, planned and run like a coded one (same float kernels, same options, same final resize, same planes bit
+ * for bit as the coded slot that holds these latents); its header (ccd_batch_header) has n_bytes_latent = 0.  The grids sit
+ * where the entropy kernel would have left them: ccd_batch_latent / ccd_batch_copy_latent work as for any slot.
+ *   on_device == 0  host pointers, read during the call.  A value outside the coder's alphabet [-64, 63] is CCD_ERR_VALUE
+ *                   and no slot is created.  The grids are uploaded with the slot's other inputs.
+ *   on_device != 0  device pointers.  They are remembered and the grids are read EVERY time the batch runs (one copy launch
+ *                   at the head of ccd_batch_run / ccd_batch_run_stage(.., 0), on the caller's stream), so a caller that
+ *                   changes its latents in place and runs again sees the new planes, and nothing crosses PCIe.  The
+ *                   pointers must stay valid while the batch may run: the contract of ccd_enc_add(..., 1), and the
+ *                   lifetime rule of the note on ccd_batch_plane pointers at ccd_pool_trim.  A value outside [-64, 63]
+ *                   makes ccd_batch_wait report CCD_ERR_VALUE for that slot (its planes are then unspecified and never
+ *                   handed out by the copies); the other slots are unaffected, and the status is CCD_OK again after a run
+ *                   that found the latents repaired.
+ * ccd_batch_entropy_launches counts coded slots only (0 for a batch of given slots); coded and given slots may share a
+ * batch.  ccd_batch_slot_stats words [1..3] are 0 for a given slot.  NULL b / arch / bytes_nn / latents and a bad bitdepth
+ * are CCD_ERR_ARG, found before anything else is looked at; a NULL latents[g] is CCD_ERR_ARG, an `arch` that does not
+ * re-parse CCD_ERR_VALUE. */
+int ccd_batch_add_latents(ccd_batch* b, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn,
+                          const int8_t* const* latents, int on_device, int bitdepth, int frame_data_type);
 int ccd_batch_size(const ccd_batch* b);
 int ccd_batch_header(const ccd_batch* b, int slot, ccd_cc_header* h);
 /* Optional: builds and uploads the launch tables of the slots added so far (entropy descriptors, work lists of the float
@@ -188,7 +212,8 @@ int ccd_batch_entropy_launches(const ccd_batch* b);
  * bit 7 = the network is OUTSIDE the finite envelope of the float stages (some latents could drive an intermediate value of the
  *         pyramid or the synthesis beyond float32: crafted or corrupt parameter payloads) - such a slot never runs the
  *         matrix-core kernel (bit 2 clear) but the vector-ALU kernels, which stay bit-identical with the reference
- *         arithmetic for inf and propagate NaN like torch.relu. */
+ *         arithmetic for inf and propagate NaN like torch.relu,
+ * bit 8 = the latents were given (ccd_batch_add_latents): no entropy kernel serves the slot, bits 0, 3, 4, 5 are clear. */
 int ccd_batch_slot_kernels(const ccd_batch* b, int slot);
 
 /* Batch options, to be set before the slots they concern are added:
