@@ -179,6 +179,8 @@ SIGNATURES = {
     "ccd_enc_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "ccd_enc_slot_rate": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EncRate)]),
     "ccd_enc_slot_rate_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_enc_measure_deltas": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_enc_slot_delta_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

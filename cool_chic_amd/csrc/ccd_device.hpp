@@ -75,6 +75,25 @@ struct RateParams {
     int32_t* status;              // [0] error code of the slot
 };
 
+// Rate sensitivity (encode_delta_ifce_kernel / encode_delta_kernel, DESIGN.md 4.10 "Rate sensitivity"): what a slot of a
+// measure_deltas writes.  The IFCE stage works on 8 x 8 tiles of every fine grid g that has coarser sources (ifce_in[g] > 0,
+// g != n_grids - 1).  Source channel c of such a grid is grid g + 1 + c, sh = level[g + 1 + c] - level[g + 1]; one latent of it
+// is read by an aligned square of side 2^(sh + 1) of grid g.  The stage leaves one float64 cell per aligned square of side
+// 2^s, s = delta_cell_shift(sh) (a whole dependent block, or an 8 x 8 piece of one), per sign: plane (g, c) is
+// [2][ceil(H / 2^s)][ceil(W / 2^s)], the planes of a grid follow each other from part_first[g].
+constexpr int kDeltaTile = 8, kDeltaTileLog = 3;
+constexpr int delta_cell_shift(int sh) { return sh + 1 < kDeltaTileLog ? sh + 1 : kDeltaTileLog; }
+constexpr uint32_t delta_cells(int h, int w, int s) {  // one sign of one plane
+    return static_cast<uint32_t>((h + (1 << s) - 1) >> s) * static_cast<uint32_t>((w + (1 << s) - 1) >> s);
+}
+struct DeltaParams {
+    double* partial;                      // the IFCE stage's cells
+    uint32_t part_first[CCD_MAX_GRIDS];   // first cell of fine grid g
+    uint32_t tile_first[CCD_MAX_GRIDS];   // first workgroup of the IFCE stage that belongs to grid g (grows with g)
+    uint32_t n_tiles;
+    float* map[CCD_MAX_GRIDS];            // per grid [2][h][w]: plane 0 the change for v - 1, plane 1 for v + 1
+};
+
 // One copy of the ingest launch (ccd_ingest.hip): latent grid `src` of a slot whose latents were GIVEN as device pointers
 // (ccd_batch_add_latents) goes to `dst`, where the entropy kernel would have left it.  The segments of one slot are adjacent.
 struct IngestSeg {

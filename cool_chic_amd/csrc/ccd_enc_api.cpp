@@ -26,6 +26,7 @@ struct EncSlot {
     bool measured = false;         // part of a measure that was waited for; `rate` and `map_off` are that measure's
     ccd_enc_rate rate{};
     size_t map_off = 0;            // floats before this slot's planes in the handle's map block
+    size_t delta_off = 0;          // floats before this slot's delta maps in the handle's delta map block
 };
 enum { kIdle = 0, kRun = 1, kMeasure = 2 };  // what ccd_enc::in_flight holds
 }  // namespace
@@ -47,6 +48,11 @@ struct ccd_enc {
     bool rate_has_map = false;     // rate_table describes a map (the last measure asked for one)
     size_t n_measured = 0;         // slots of the measure in flight / last waited for
     bool map_valid = false;        // the last finished measure wrote a map
+    // rate sensitivity (ccd_enc_measure_deltas): a measure whose two extra launches write here
+    Block delta_table, delta_table_host, delta_slab, delta_map;  // DeltaParams[n] (device, pinned), f64 cells, f32 [2][h][w] per grid
+    size_t delta_slots = 0;        // slots the four blocks above describe
+    bool delta_pending = false;    // the measure in flight is a measure_deltas
+    bool delta_valid = false;      // the last finished measure was one
     std::vector<hipStream_t> streams;  // every stream a run was enqueued on (drained by destroy)
 };
 
@@ -80,6 +86,7 @@ void ccd_enc_destroy(ccd_enc* e) {
     for (auto& s : e->slots) { s->params.drop(); s->pairs.drop(); s->out.drop(); }
     e->table.drop(); e->table_host.drop(); e->status_dev.drop(); e->status_host.drop();
     e->rate_table.drop(); e->rate_table_host.drop(); e->rate_slab.drop(); e->rate_out.drop(); e->rate_out_host.drop(); e->rate_map.drop();
+    e->delta_table.drop(); e->delta_table_host.drop(); e->delta_slab.drop(); e->delta_map.drop();
     delete e;
 }
 
@@ -236,6 +243,8 @@ void harvest(ccd_enc* e) {
             s.measured = true;
         }
         e->map_valid = e->rate_has_map;
+        e->delta_valid = e->delta_pending;
+        e->delta_pending = false;
     }
     e->last_kind = e->in_flight;
     e->in_flight = kIdle;
@@ -296,17 +305,18 @@ int ccd_enc_run(ccd_enc* e, void* stream) {
     return CCD_OK;
 }
 
-int ccd_enc_measure(ccd_enc* e, void* stream, int want_map) {
-    if (!e) return CCD_ERR_ARG;
+namespace {
+// The meter's launches and the copy of its results, enqueued on `st`: what ccd_enc_measure and ccd_enc_measure_deltas share.
+int enqueue_measure(ccd_enc* e, hipStream_t st, bool map, unsigned* max_blocks_out, size_t* lds_out) {
     const size_t n = e->slots.size();
-    if (n == 0) return CCD_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned max_blocks = 0;
     size_t lds = 0;
     const int rc = prepare_launch(e, st, &max_blocks, &lds);
     if (rc < 0) return rc;
-    const bool map = want_map != 0;
+    *max_blocks_out = max_blocks;
+    *lds_out = lds;
     e->map_valid = false;  // the planes of the last measure are about to be overwritten or given back
+    e->delta_valid = false;
     if (e->rate_slots != n || e->rate_has_map != map) {
         e->rate_slots = 0;
         size_t n_blocks = 0, out_bytes = 0, n_map = 0;
@@ -351,7 +361,87 @@ int ccd_enc_measure(ccd_enc* e, void* stream, int want_map) {
     HIP_TRY(launch_encode_rate(e->table.as<EncodeParams>(), e->rate_table.as<RateParams>(), static_cast<int>(n), max_blocks, max_grids, lds, st));
     HIP_TRY(hipMemcpyAsync(e->rate_out_host.p, e->rate_out.p, e->rate_out_bytes, hipMemcpyDeviceToHost, st));
     e->n_measured = n;
+    return CCD_OK;
+}
+}  // namespace
+
+int ccd_enc_measure(ccd_enc* e, void* stream, int want_map) {
+    if (!e) return CCD_ERR_ARG;
+    if (e->slots.empty()) return CCD_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    const int rc = enqueue_measure(e, st, want_map != 0, &max_blocks, &lds);
+    if (rc < 0) return rc;
     launched(e, st, kMeasure);
+    return CCD_OK;
+}
+
+int ccd_enc_measure_deltas(ccd_enc* e, void* stream) {
+    if (!e) return CCD_ERR_ARG;
+    const size_t n = e->slots.size();
+    if (n == 0) return CCD_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->in_flight != kIdle) {  // the delta tables below may be rebuilt: nothing of this handle may still read them
+        HIP_TRY(hipStreamSynchronize(e->last_stream));
+        harvest(e);
+    }
+    e->delta_valid = false;  // the maps of the last call are about to be overwritten or given back
+    // which fine grids have IFCE sources, their tiles and their cells: the geometry the kernels re-derive (ccd_device.hpp)
+    auto has_sources = [](const EntropyParams& E, int g) { return E.ifce_in[g] > 0 && g != E.n_grids - 1; };
+    if (e->delta_slots != n) {
+        e->delta_slots = 0;
+        size_t n_cells = 0, n_map = 0;
+        for (auto& s : e->slots) {
+            const EntropyParams& E = s->ep.ep;
+            for (int g = 0; g < E.n_grids; ++g) {
+                if (!has_sources(E, g)) continue;
+                for (int c = 0; c < E.ifce_in[g]; ++c)
+                    n_cells += 2 * static_cast<size_t>(delta_cells(E.grid_h[g], E.grid_w[g], delta_cell_shift(E.level[g + 1 + c] - E.level[g + 1])));
+            }
+            n_map += 2 * static_cast<size_t>(s->ep.n_symbols);
+        }
+        if (n_cells > 0xffffffffu) return CCD_ERR_UNSUPPORTED;
+        if (!e->delta_table.get(e->device, BlockPool::kDevice, n * sizeof(DeltaParams)) ||
+            !e->delta_table_host.get(e->device, BlockPool::kPinned, n * sizeof(DeltaParams)) ||
+            !e->delta_slab.get(e->device, BlockPool::kDevice, std::max<size_t>(n_cells * sizeof(double), 256)) ||
+            !e->delta_map.get(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256)))
+            return CCD_ERR_NOMEM;
+        size_t cell = 0, at = 0;
+        for (size_t i = 0; i < n; ++i) {
+            EncSlot& s = *e->slots[i];
+            const EntropyParams& E = s.ep.ep;
+            DeltaParams& D = e->delta_table_host.as<DeltaParams>()[i];
+            std::memset(&D, 0, sizeof(D));
+            D.partial = e->delta_slab.as<double>() + cell;
+            s.delta_off = at;
+            uint32_t first = 0, tiles = 0;
+            for (int g = 0; g < E.n_grids; ++g) {
+                const int H = E.grid_h[g], W = E.grid_w[g];
+                D.part_first[g] = first;
+                D.tile_first[g] = tiles;
+                D.map[g] = e->delta_map.as<float>() + at;
+                at += 2 * static_cast<size_t>(H) * W;
+                if (!has_sources(E, g)) continue;
+                for (int c = 0; c < E.ifce_in[g]; ++c) first += 2 * delta_cells(H, W, delta_cell_shift(E.level[g + 1 + c] - E.level[g + 1]));
+                tiles += delta_cells(H, W, kDeltaTileLog);
+            }
+            D.n_tiles = tiles;
+            cell += first;
+        }
+        e->delta_slots = n;
+    }
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    const int rc = enqueue_measure(e, st, false, &max_blocks, &lds);  // the meter's two launches first: its results are its own
+    if (rc < 0) return rc;
+    launched(e, st, kMeasure);
+    unsigned max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) max_tiles = std::max<unsigned>(max_tiles, e->delta_table_host.as<DeltaParams>()[i].n_tiles);
+    HIP_TRY(hipMemcpyAsync(e->delta_table.p, e->delta_table_host.p, n * sizeof(DeltaParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_encode_deltas(e->table.as<EncodeParams>(), e->delta_table.as<DeltaParams>(), static_cast<int>(n), max_blocks, max_tiles, lds, st));
+    e->delta_pending = true;
     return CCD_OK;
 }
 
@@ -389,6 +479,19 @@ int64_t ccd_enc_slot_rate_map(const ccd_enc* e, int slot, int grid, const float*
     for (int g = 0; g < grid; ++g) off += static_cast<size_t>(s.hdr.grid_h[g]) * s.hdr.grid_w[g];
     *device_ptr = e->rate_map.as<float>() + off;
     return static_cast<int64_t>(s.hdr.grid_h[grid]) * s.hdr.grid_w[grid];
+}
+
+int ccd_enc_slot_delta_map(const ccd_enc* e, int slot, int grid, void** dev_ptr) {
+    if (!e || !dev_ptr || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kMeasure || !e->delta_valid ||
+        static_cast<size_t>(slot) >= e->n_measured || !e->slots[slot]->measured)
+        return CCD_ERR_ARG;
+    const EncSlot& s = *e->slots[slot];
+    if (grid < 0 || grid >= s.hdr.n_grids) return CCD_ERR_ARG;
+    if (s.rate.status < 0) return s.rate.status;
+    size_t off = s.delta_off;
+    for (int g = 0; g < grid; ++g) off += 2 * static_cast<size_t>(s.hdr.grid_h[g]) * s.hdr.grid_w[g];
+    *dev_ptr = e->delta_map.as<float>() + off;
+    return s.hdr.grid_h[grid] * s.hdr.grid_w[grid];
 }
 
 int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8) {

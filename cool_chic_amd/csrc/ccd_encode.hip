@@ -27,13 +27,18 @@ namespace ccd {
 
 constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever reads the LDS column it wrote (no barrier)
 
-// ---- what both stage-1 kernels do for one pixel -----------------------------------------------------------------
-// The interval [left, right) of symbol `sym` (already checked to be in the alphabet) at (y, x) of grid g: neighbour gather,
-// IFCE features of (y >> 1, x >> 1), the wrapping 64-bit ARM, the clamp to table indices, window_left of sym and sym + 1.
-// g is wave-uniform, so every weight is a scalar load; `smem_raw` holds the activations as [k][lane] columns and a lane only
-// touches its own column.  No cross-lane operation in here: a caller may skip it for some lanes.
-__device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, int g, int y, int x, int sym, int lane,
-                                                      unsigned char* smem_raw, uint32_t& left, uint32_t& right) {
+// ---- what every stage-1 kernel does for one pixel ---------------------------------------------------------------
+// The Laplace parameters (mu, 1 / scale) of the pixel (y, x) of grid g: neighbour gather, IFCE features of (y >> 1, x >> 1),
+// the wrapping 64-bit ARM, the clamp to table indices.  g is wave-uniform, so every weight is a scalar load; `smem_raw` holds
+// the activations as [k][lane] columns and a lane only touches its own column.  No cross-lane operation in here: a caller
+// may skip it for some lanes.
+// kOverride: the one latent `ov` names is taken as ov.val wherever the pixel reads it (a spatial tap when ov.grid == g, an
+// IFCE source when ov.grid > g), memory stays as it is - the delta kernels' "what if".  Without it `ov` is not looked at and
+// the function is what it was before it had the parameter.
+struct LatentOverride { int grid, y, x, val; };
+template <bool kOverride>
+__device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g, int y, int x, int lane, unsigned char* smem_raw,
+                                                   const LatentOverride& ov, double& mu, double& rcp) {
     const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
     int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
     int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
@@ -43,7 +48,8 @@ __device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, in
     // ---- contexts, already << 16 (armint.py:193) ----
     for (int k = 0; k < n_sp; ++k) {
         const int yy = y - P.ctx_dy[k], xx = x + P.ctx_dx[k];
-        const int64_t v = (yy >= 0 && xx >= 0 && xx < W) ? lat[yy * W + xx] : 0;
+        int64_t v = (yy >= 0 && xx >= 0 && xx < W) ? lat[yy * W + xx] : 0;
+        if (kOverride && g == ov.grid && yy == ov.y && xx == ov.x) v = ov.val;
         xa[k * kEncThreads] = static_cast<int64_t>(static_cast<uint64_t>(v) << 16);
     }
     // IFCE features of (y >> 1, x >> 1) at the coarser neighbour's size (coolchic.py:94-146).  Evaluated here, per
@@ -62,7 +68,8 @@ __device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, in
                 for (int c = 0; c < fin; ++c) {
                     const int m = g + 1 + c;
                     const int sh = P.level[m] - base_level;
-                    const int64_t v = P.latent[m][(fy >> sh) * P.grid_w[m] + (fx >> sh)];
+                    int64_t v = P.latent[m][(fy >> sh) * P.grid_w[m] + (fx >> sh)];
+                    if (kOverride && m == ov.grid && (fy >> sh) == ov.y && (fx >> sh) == ov.x) v = ov.val;
                     acc += static_cast<uint64_t>(v << 16) * static_cast<uint64_t>(fw_[c * n_if + o]);
                 }
             }
@@ -120,9 +127,16 @@ __device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, in
     const int mu_idx = static_cast<int>(mi < 0 ? 0 : (mi > kNumMu - 1 ? kNumMu - 1 : mi));
     const int sc_idx = static_cast<int>(si < 0 ? 0 : (si > kNumScale - 1 ? kNumScale - 1 : si));
 
-    // ---- the symbol's interval under the leaky quantised Laplace model ----
-    const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
-    const double rcp = P.rcp_table[sc_idx];
+    mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
+    rcp = P.rcp_table[sc_idx];
+}
+
+// The interval [left, right) of symbol `sym` (already checked to be in the alphabet) at (y, x) of grid g under the leaky
+// quantised Laplace model: window_left of sym and sym + 1.
+__device__ __forceinline__ void encode_pixel_interval(const EntropyParams& P, int g, int y, int x, int sym, int lane,
+                                                      unsigned char* smem_raw, uint32_t& left, uint32_t& right) {
+    double mu, rcp;
+    encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
     left = window_left(mu, rcp, sym, kExpTab);           // 0 for -64
     right = window_left(mu, rcp, sym + 1, kExpTab);      // 2^24 for 63
 }
@@ -307,6 +321,153 @@ __global__ __launch_bounds__(kEncThreads) void encode_rate_final_kernel(const En
     if (lane == 0) *reinterpret_cast<double*>(R.grids + n_grids) = total;
 }
 
+// ---- rate sensitivity: what the slot's model bits would change by if ONE latent were v - 1 or v + 1 ---------------------
+// DESIGN.md 4.10 "Rate sensitivity".  A latent p is read by its own symbol's model, by the pixels of its grid that hold it in a
+// spatial tap, and by the pixels of finer grids whose IFCE feature reads it; each of them has p in exactly one context entry.
+// Two launches behind the meter's, no atomics:
+//   1. encode_delta_ifce_kernel: one wave per 8 x 8 tile of a fine grid, a lane per fine pixel.  For each of the pixel's
+//      ifce_in sources the lane prices its own symbol with the source at v - 1 and v + 1 (the whole feature is recomputed,
+//      float round trip included) against the price as it is; a fixed shuffle tree adds the lanes that share a source (or the
+//      whole tile when the source's block is larger) and one lane stores the cell.
+//   2. encode_delta_kernel: the grid of the contexts kernel, a lane per latent.  Own term from window_left at v - 1 .. v + 2
+//      under the pixel's own (mu, rcp); then the spatial dependents in tap order, three model evaluations each; then the IFCE
+//      cells of its block, fine grids in ascending order, cells in raster order.  float64 all the way, one float32 store.
+__device__ __forceinline__ double log2_width(double mu, double rcp, int sym) {
+    return log2(static_cast<double>(window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab)));
+}
+__device__ __forceinline__ bool in_alphabet(int sym) { return sym >= kAcLo && sym <= kAcLo + kAlphabet - 1; }
+
+__global__ __launch_bounds__(kEncThreads) void encode_delta_ifce_kernel(const EncodeParams* slots, const DeltaParams* delta) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EntropyParams& P = slots[blockIdx.y].ep;
+    const DeltaParams& D = delta[blockIdx.y];
+    if (blockIdx.x >= D.n_tiles) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    int g = 0;
+    while (g + 1 < n_grids && blockIdx.x >= D.tile_first[g + 1]) ++g;  // tile_first grows with g; a grid without tiles owns none
+    const int H = P.grid_h[g], W = P.grid_w[g];
+    const int tiles_x = (W + kDeltaTile - 1) >> kDeltaTileLog;
+    const int t = static_cast<int>(blockIdx.x - D.tile_first[g]);
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int qy = ty * kDeltaTile + (lane >> kDeltaTileLog), qx = tx * kDeltaTile + (lane & (kDeltaTile - 1));  // lane = y2 y1 y0 x2 x1 x0
+    const bool inside = qy < H && qx < W;
+    const int sym = inside ? P.latent[g][qy * W + qx] : 0;
+    const bool ok = inside && in_alphabet(sym);  // the others hold 0 and stay for the shuffles
+    double mu, rcp, base = 0.0;
+    if (ok) {
+        encode_pixel_model<false>(P, g, qy, qx, lane, smem_raw, LatentOverride{}, mu, rcp);
+        base = log2_width(mu, rcp, sym);
+    }
+    const int fin = P.ifce_in[g], base_level = P.level[g + 1];
+    double* cell = D.partial + D.part_first[g];
+#pragma unroll 1
+    for (int c = 0; c < fin; ++c) {
+        const int m = g + 1 + c, sh = P.level[m] - base_level, s = delta_cell_shift(sh);
+        double dm = 0.0, dp = 0.0;  // bits(q | source - 1) - bits(q), bits(q | source + 1) - bits(q)
+        if (ok) {
+            LatentOverride ov{m, (qy >> 1) >> sh, (qx >> 1) >> sh, 0};
+            const int v = P.latent[m][ov.y * P.grid_w[m] + ov.x];
+#pragma unroll 1
+            for (int sign = -1; sign <= 1; sign += 2) {
+                ov.val = v + sign;
+                if (!in_alphabet(ov.val)) continue;  // the move does not exist: encode_delta_kernel stores +inf there
+                encode_pixel_model<true>(P, g, qy, qx, lane, smem_raw, ov, mu, rcp);
+                const double d = base - log2_width(mu, rcp, sym);
+                if (sign < 0) dm = d; else dp = d;
+            }
+        }
+        for (int j = 0; j < s; ++j) {  // s is wave-uniform: x0, y0, x1, y1, ..
+            dm += __shfl_xor(dm, 1 << j, kEncThreads);
+            dp += __shfl_xor(dp, 1 << j, kEncThreads);
+            dm += __shfl_xor(dm, kDeltaTile << j, kEncThreads);
+            dp += __shfl_xor(dp, kDeltaTile << j, kEncThreads);
+        }
+        const uint32_t n_cells = delta_cells(H, W, s);
+        const int low = (1 << s) - 1;
+        if (inside && (qy & low) == 0 && (qx & low) == 0) {  // the square's first pixel: inside whenever any of it is
+            const uint32_t at = static_cast<uint32_t>(qy >> s) * static_cast<uint32_t>((W + low) >> s) + static_cast<uint32_t>(qx >> s);
+            cell[at] = dm;
+            cell[n_cells + at] = dp;
+        }
+        cell += 2 * n_cells;
+    }
+}
+
+__global__ __launch_bounds__(kEncThreads) void encode_delta_kernel(const EncodeParams* slots, const DeltaParams* delta) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.y];
+    const EntropyParams& P = Q.ep;
+    const DeltaParams& D = delta[blockIdx.y];
+    if (blockIdx.x >= Q.n_blocks) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    int g = 0;
+    while (g + 1 < n_grids && blockIdx.x >= Q.block_first[g + 1]) ++g;
+    const int H = P.grid_h[g], W = P.grid_w[g], n = H * W;
+    const int p = static_cast<int>(blockIdx.x - Q.block_first[g]) * kEncThreads + lane;
+    if (p >= n) return;  // no cross-lane operation below
+    const int8_t* __restrict__ lat = P.latent[g];
+    float* __restrict__ out = D.map[g];
+    const float inf = __builtin_inff();
+    const int v = lat[p];
+    if (!in_alphabet(v)) { out[p] = inf; out[n + p] = inf; return; }  // (the meter's launch set the slot's status)
+    const int y = p / W, x = p - y * W;
+    const bool has_m = v > kAcLo, has_p = v < kAcLo + kAlphabet - 1;
+
+    // ---- its own symbol: the neighbouring symbols' intervals under the same (mu, rcp) ----
+    double mu, rcp;
+    encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+    double am, ap;  // the sums for v - 1 and v + 1
+    {
+        const uint32_t l0 = window_left(mu, rcp, v - 1, kExpTab), l1 = window_left(mu, rcp, v, kExpTab);
+        const uint32_t l2 = window_left(mu, rcp, v + 1, kExpTab), l3 = window_left(mu, rcp, v + 2, kExpTab);
+        const double own = log2(static_cast<double>(l2 - l1));
+        am = has_m ? own - log2(static_cast<double>(l1 - l0)) : 0.0;
+        ap = has_p ? own - log2(static_cast<double>(l3 - l2)) : 0.0;
+    }
+    // ---- the pixels that have it as spatial tap k: (y + dy[k], x - dx[k]), the gather's signs turned round ----
+    const int n_sp = P.n_spatial;
+#pragma unroll 1
+    for (int k = 0; k < n_sp; ++k) {
+        const int qy = y + P.ctx_dy[k], qx = x - P.ctx_dx[k];
+        if (qy < 0 || qy >= H || qx < 0 || qx >= W) continue;
+        const int sq = lat[qy * W + qx];
+        if (!in_alphabet(sq)) continue;
+        LatentOverride ov{g, y, x, v};
+        double base = 0.0;
+#pragma unroll 1
+        for (int t = 0; t < 3; ++t) {  // as it is, v - 1, v + 1
+            if ((t == 1 && !has_m) || (t == 2 && !has_p)) continue;
+            ov.val = v + (t == 0 ? 0 : 2 * t - 3);
+            encode_pixel_model<true>(P, g, qy, qx, lane, smem_raw, ov, mu, rcp);
+            const double l = log2_width(mu, rcp, sq);
+            if (t == 0) base = l;
+            else if (t == 1) am += base - l;
+            else ap += base - l;
+        }
+    }
+    // ---- the finer grids whose IFCE feature reads it: grid gf has it as source channel g - gf - 1 ----
+    for (int gf = 0; gf < g; ++gf) {
+        const int c = g - gf - 1;
+        if (P.ifce_in[gf] <= c) continue;
+        const int hf = P.grid_h[gf], wf = P.grid_w[gf], base_level = P.level[gf + 1];
+        const double* cell = D.partial + D.part_first[gf];
+        for (int cc = 0; cc < c; ++cc) cell += 2 * delta_cells(hf, wf, delta_cell_shift(P.level[gf + 1 + cc] - base_level));
+        const int sh = P.level[g] - base_level, s = delta_cell_shift(sh), r = sh + 1 - s;  // its block: 2^r x 2^r cells
+        const int64_t nby = (hf + (1 << s) - 1) >> s, nbx = (wf + (1 << s) - 1) >> s;
+        const int64_t by1 = min((static_cast<int64_t>(y) + 1) << r, nby), bx0 = static_cast<int64_t>(x) << r;
+        const int64_t bx1 = min((static_cast<int64_t>(x) + 1) << r, nbx);
+        for (int64_t by = static_cast<int64_t>(y) << r; by < by1; ++by)
+            for (int64_t bx = bx0; bx < bx1; ++bx) {
+                am += cell[by * nbx + bx];
+                ap += cell[(nby + by) * nbx + bx];
+            }
+    }
+    out[p] = has_m ? static_cast<float>(am) : inf;
+    out[n + p] = has_p ? static_cast<float>(ap) : inf;
+}
+
 size_t encode_contexts_lds_bytes(int dim) { return static_cast<size_t>(2) * dim * kEncThreads * sizeof(int64_t); }
 int encode_block_threads() { return kEncThreads; }
 
@@ -341,6 +502,26 @@ hipError_t launch_encode_rate(const EncodeParams* d_slots, const RateParams* d_r
     }
     if (max_grids <= 0) return hipSuccess;
     hipLaunchKernelGGL(encode_rate_final_kernel, dim3(max_grids, n_slots), dim3(kEncThreads), 0, stream, d_slots, d_rate);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* d_delta, int n_slots, unsigned max_blocks,
+                                unsigned max_tiles, size_t lds_bytes, hipStream_t stream) {
+    if (n_slots <= 0 || max_blocks == 0) return hipSuccess;
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_delta_ifce_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_delta_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(lds_bytes));
+        if (e != hipSuccess) return e;
+    }
+    if (max_tiles > 0) {
+        hipLaunchKernelGGL(encode_delta_ifce_kernel, dim3(max_tiles, n_slots), dim3(kEncThreads), lds_bytes, stream, d_slots, d_delta);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(encode_delta_kernel, dim3(max_blocks, n_slots), dim3(kEncThreads), lds_bytes, stream, d_slots, d_delta);
     return hipGetLastError();
 }
 

@@ -101,6 +101,20 @@ class EncodeBatch:
         assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
         return _DevArray(ptr.value or 0, (h, w), "<f4", self)
 
+    def measure_deltas(self, stream: int = 0):
+        """measure() followed by the rate sensitivity launches: rate() as after measure(), and delta_map() of every grid."""
+        check(lib().ccd_enc_measure_deltas(self._h, C.c_void_p(stream or None)), "ccd_enc_measure_deltas")
+
+    def delta_map(self, slot: int, grid: int) -> _DevArray:
+        """After measure_deltas() + wait(): float32 [2][h][w], the exact change of the slot's model bits if the latent at
+        (y, x) alone were v - 1 (plane 0) or v + 1 (plane 1); +inf where that leaves [-64, 63].  Valid until the next measure /
+        measure_deltas / close."""
+        ptr = C.c_void_p()
+        n = check(lib().ccd_enc_slot_delta_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_enc_slot_delta_map")
+        h, w = self._grid_shapes[int(slot)][int(grid)]
+        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
+        return _DevArray(ptr.value or 0, (2, h, w), "<f4", self)
+
     def slot_status(self, slot: int) -> Tuple[int, np.ndarray]:
         """(status, counters) after wait(): counters[1] payload words, [2] inverted runs begun by the coder, [3] resolved
         with a carry, [4] resolved without one (include/ccd.h)."""

@@ -93,13 +93,18 @@ class RdEvaluator:
         self._frames.append(source)
         return slot
 
-    def evaluate(self, lmbda: float, ms_ssim: bool = False) -> List[Candidate]:
+    def evaluate(self, lmbda: float, ms_ssim: bool = False, rate_deltas: bool = False) -> List[Candidate]:
+        """rate_deltas: the rate comes from EncodeBatch.measure_deltas, which leaves the same numbers and, for
+        rate_delta_map(), what every latent's +-1 would do to them."""
         n = len(self._frames)
         if n == 0:
             return []
         st = torch.cuda.current_stream(self.device).cuda_stream
         self._dec.run(st)           # ingest of device latents, then the float path: the grids are in the arenas behind this
-        self._enc.measure(st)       # same stream: reads the arenas' grids
+        if rate_deltas:             # same stream: reads the arenas' grids
+            self._enc.measure_deltas(st)
+        else:
+            self._enc.measure(st)
         decoded = [[torch.as_tensor(self._dec.plane_device(s, p), device=f"cuda:{self.device}") for p in range(3)] for s in range(n)]
         self._meter.score_planes_async(decoded, self._sources, [f.bitdepth for f in self._frames], ms_ssim, stream=st)
         results = self._meter.finish()
@@ -112,3 +117,7 @@ class RdEvaluator:
             mse, bits, cost = rd_cost(q.sse, q.n, f.bitdepth, rate.total_bits, rate.n_bytes_nn, rate.n_bytes_header, f.n_pixels, lmbda)
             out.append(Candidate(rate, q, mse, bits, cost))
         return out
+
+    def rate_delta_map(self, slot: int, grid: int):
+        """After evaluate(rate_deltas=True): EncodeBatch.delta_map of the candidate (device, float32 [2][h][w])."""
+        return self._enc.delta_map(slot, grid)

@@ -430,6 +430,19 @@ typedef struct {
 int ccd_enc_measure(ccd_enc* e, void* stream, int want_map);
 int ccd_enc_slot_rate(const ccd_enc* e, int slot, ccd_enc_rate* out);
 int64_t ccd_enc_slot_rate_map(const ccd_enc* e, int slot, int grid, const float** device_ptr);
+/* ---- rate sensitivity: the exact change of a slot's model bits if ONE latent were v - 1 or v + 1 (DESIGN.md section 4.10,
+ * "Rate sensitivity").  Changing the latent p changes its own interval, the intervals of the later pixels of its grid that
+ * hold it in their spatial context and those of the finer-grid pixels whose IFCE feature reads it; the map holds the sum of
+ * 24 - log2(width) over exactly those pixels with the changed latent, minus the same sum with the latents as they are.
+ * ccd_enc_measure_deltas is a ccd_enc_measure(e, stream, 0) - same ccd_enc_slot_rate results, word for word, same rule of
+ * one operation in flight, ended by ccd_enc_wait - followed by the two delta launches.
+ * Its own buffers are taken before anything is enqueued: CCD_ERR_NOMEM / CCD_ERR_UNSUPPORTED leave the handle idle.
+ * ccd_enc_slot_delta_map: device pointer to float32 [2][grid_h][grid_w] (plane 0: v - 1, plane 1: v + 1; +inf where the move
+ * leaves [-64, 63]) and grid_h * grid_w; valid until the next measure, measure_deltas or destroy (a run does not touch it).
+ * A slot with a latent outside the alphabet has the status CCD_ERR_VALUE, which is returned in place of a map.  CCD_ERR_ARG for
+ * a NULL argument, a bad slot or grid, or when the last finished measure was not a measure_deltas that covered the slot. */
+int ccd_enc_measure_deltas(ccd_enc* e, void* stream);
+int ccd_enc_slot_delta_map(const ccd_enc* e, int slot, int grid, void** dev_ptr);
 /* Size of a slot's payload buffer: every symbol has a width of at least 1 / 2^24, so n symbols give at most
  * 4 * (ceil(24 n / 32) + 2) bytes.  0 for n < 0. */
 size_t ccd_enc_payload_bound(int64_t n_symbols);

@@ -4,7 +4,9 @@ runs on, after warm-up runs, median of --runs; host times are wall clock of the 
 
 Per-kernel times (contexts / chain) come from a run of their own:
     rocprofv3 --kernel-trace --stats -- python tools/encode_bench.py --runs 3 --no-host
---measure adds the rate meter (EncodeBatch.measure + wait, with and without the map) on the same handles."""
+--measure adds the rate meter (EncodeBatch.measure + wait, with and without the map) on the same handles.
+--deltas adds the rate sensitivity maps (EncodeBatch.measure_deltas + wait) beside measure + wait on the same handles and
+prints their ratio next to the count of ARM evaluations per pixel it is made of."""
 import argparse
 import json
 import statistics
@@ -42,7 +44,7 @@ def decoded(streams, bitdepth=8):
     return dec
 
 
-def measure(streams, runs, host, rate=False):
+def measure(streams, runs, host, rate=False, deltas=False):
     st = torch.cuda.current_stream().cuda_stream
     dec = decoded(streams)
     n_sym = sum(dec.header(s).n_symbols for s in range(len(streams)))
@@ -76,6 +78,27 @@ def measure(streams, runs, host, rate=False):
         res["model_bits"] = round(sum(enc.rate(s).total_bits for s in range(len(streams))), 3)
         res["payload_bits"] = 32 * words
         res["run_over_measure"] = round(res["device_encode_ms"] / res["measure_ms"], 1)
+    if deltas:  # measure_deltas() + wait() beside measure() + wait(), same handle, same inputs
+        def meter_step():
+            enc.measure(st)
+            enc.wait(st)
+
+        def deltas_step():
+            enc.measure_deltas(st)
+            enc.wait(st)
+
+        res["measure_ms"] = round(event_ms(meter_step, runs), 3)
+        res["measure_deltas_ms"] = round(event_ms(deltas_step, runs), 3)
+        res["deltas_over_measure"] = round(res["measure_deltas_ms"] / res["measure_ms"], 1)
+        # ARM evaluations per pixel as launched: the meter's 1, own + 3 per spatial tap, base + 2 per IFCE source on the
+        # grids that have sources (an upper count: taps cut by a border are not evaluated)
+        evals = 0
+        for s in range(len(streams)):
+            h = dec.header(s)
+            for g in range(h.n_grids):
+                fin = h.input_features_ifce[g] if g != h.n_grids - 1 else 0
+                evals += h.grid_h[g] * h.grid_w[g] * (2 + 3 * h.spatial_context_arm + ((1 + 2 * fin) if fin else 0))
+        res["arm_evaluations_per_symbol"] = round(evals / n_sym, 1)
     if host:
         jobs = []
         for s in range(len(streams)):
@@ -101,13 +124,14 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the host writer (profiling runs)")
     ap.add_argument("--no-4k", action="store_true")
     ap.add_argument("--measure", action="store_true", help="also time the rate meter (EncodeBatch.measure) beside every run")
+    ap.add_argument("--deltas", action="store_true", help="also time the rate sensitivity maps (EncodeBatch.measure_deltas) beside measure")
     a = ap.parse_args()
     k24 = synth.workload("kodak24")["streams"]
     out = {"tool": "encode_bench", "runs": a.runs,
-           "kodim14": measure(k24[:1], a.runs, not a.no_host, a.measure),
-           "kodak24": measure(k24, a.runs, not a.no_host, a.measure)}
+           "kodim14": measure(k24[:1], a.runs, not a.no_host, a.measure, a.deltas),
+           "kodak24": measure(k24, a.runs, not a.no_host, a.measure, a.deltas)}
     if not a.no_4k:
-        out["uhd4k_one"] = measure([synth.image_stream(2160, 3840)], a.runs, not a.no_host, a.measure)
+        out["uhd4k_one"] = measure([synth.image_stream(2160, 3840)], a.runs, not a.no_host, a.measure, a.deltas)
     print(json.dumps(out))
 
 
