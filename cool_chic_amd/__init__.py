@@ -16,6 +16,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    encoder.EncodeBatch, writer.encode_coolchic(device=...)
     training.loss.loss_function on a candidate (distortion + lmbda * rate, training/loss.py:158)
                                                    rd.RdEvaluator (exact integer ARM and integer planes, no search)
+    (no counterpart: what moving one latent by +-1 does to the squared error of the decoded planes)
+                                                   dsens.DistortionDeltas, RdEvaluator.cost_delta_map
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -27,6 +29,10 @@ def __getattr__(name):
         from .rd import RdEvaluator
 
         return RdEvaluator
+    if name == "DistortionDeltas":
+        from .dsens import DistortionDeltas
+
+        return DistortionDeltas
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -181,6 +181,16 @@ SIGNATURES = {
     "ccd_enc_slot_rate_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_enc_measure_deltas": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_enc_slot_delta_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_latent_footprint": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.POINTER(C.c_int32)]),
+    "ccd_latent_probe_stride": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.c_int]),
+    "ccd_dsens_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_dsens_destroy": (None, [C.c_void_p]),
+    "ccd_dsens_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                C.c_int, C.c_int]),
+    "ccd_dsens_run": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_dsens_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_dsens_slot_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_dsens_passes": (C.c_int, [C.c_void_p, C.c_int]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

@@ -105,6 +105,44 @@ struct IngestSeg {
 constexpr uint32_t kIngestChunk = 4096;  // bytes one 64-lane workgroup of the ingest launch copies
 constexpr int kIngestWordB = 4;          // the second of the two status words a given slot alternates between (ccd_ingest.hip)
 
+// ---- distortion deltas (ccd_dsens.hip, ccd_dsens_api.cpp) ----
+// One grid of one probe slot's private latent copy, written by dsens_apply_kernel: the caller's grid `src` goes to `dst`, and the
+// latents on the lattice (y % stride == py, x % stride == px) go there as v + move where that stays inside [-64, 63].
+// move == 0: a plain copy (the grid the slot probed in the round before, or every grid at the head of a run).
+struct DsensSeg {
+    const int8_t* src;
+    int8_t* dst;
+    uint32_t n;            // bytes = h * w
+    int32_t w;
+    int32_t stride, py, px;
+    int32_t move;          // -1, 0, +1
+};
+// One pass as dsens_sse_kernel sees it: the probes (py + i stride, px + j stride), i < ny, j < nx, of a grid, the planes they
+// were decoded to and where their entries go.  The box of the probe (y, x) is, in luma samples,
+//   rows [(y * num_y) / den_y + box[0], (y * num_y) / den_y + box[2]], columns [(x * num_x) / den_x + box[1], .. + box[3]]
+// clipped to the picture (ccd_latent_footprint); the 4:2:0 chroma planes take it halved, rounded outwards.  A probe's box is
+// cut into `upp` bands of `rows` rows; a workgroup sums one band over the three planes into the round's slab.  ny == h, nx == w,
+// stride == 1 and empty == 1 describe a hyperlatent grid: no samples, zeros and sentinels only.
+struct DsensPass {
+    const int8_t* lat;       // the caller's grid [h][w]: where v + move leaves the alphabet the entry is INT64_MIN
+    int64_t* map;            // [2][h][w] of the grid
+    const void* base[3];     // planes decoded from the latents as given
+    const void* probe[3];    // planes of the probe slot that ran this pass
+    const void* src[3];      // source planes
+    int32_t h, w;            // of the grid
+    int32_t stride, py, px, ny, nx;
+    int32_t move;            // -1 / +1
+    int32_t box[4];          // top, left, bottom, right
+    uint32_t num_y, den_y, num_x, den_x;
+    int32_t H, W;            // luma size
+    int32_t chroma_shift;    // 1 for yuv420
+    int32_t wide;            // samples are u16
+    int32_t upp, rows;       // bands per probe, luma rows per band
+    int32_t empty;
+};
+constexpr uint32_t kDsensChunk = 4096;   // bytes one 64-lane workgroup of dsens_apply_kernel writes
+constexpr int kDsensBandSamples = 4096;  // luma samples of a band, about
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

@@ -1,0 +1,420 @@
+// ccd_dsens_api.cpp - ccd_dsens_* and ccd_latent_footprint of include/ccd.h: the host side of the distortion deltas
+// (DESIGN.md section 4.13).  Built on the public ccd_batch_* calls: the float path is the decode batch's, untouched.
+#include <cstring>
+#include <new>
+
+#include "ccd_host.hpp"
+#include "ccd_kernels.hpp"
+
+using namespace ccd;
+
+namespace {
+int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0 && ((a < 0) != (b < 0))) ? 1 : 0); }  // b > 0
+int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+
+// The transmitted fields of `arch` with the geometry they imply (what ccd_batch_add_latents does with them).
+int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out) {
+    uint8_t hb[256];
+    ccd_cc_header t = *arch;
+    t.nn_n_bytes = static_cast<int32_t>(n_nn);
+    t.n_bytes_latent = 0;
+    if (t.n_layer_synthesis < 0 || t.n_layer_synthesis > CCD_MAX_SYN_LAYERS) return CCD_ERR_VALUE;
+    const int n_hb = ccd_write_cc_header(&t, hb, sizeof(hb));
+    if (n_hb < 0 || ccd_read_cc_header(hb, static_cast<size_t>(n_hb), out) < 0) return CCD_ERR_VALUE;
+    return CCD_OK;
+}
+
+// Where a move of one latent of `grid` can reach (supports only).  Per axis a (0 rows, 1 columns): the samples
+// [s + lo[a], s + hi[a]] with s = floor(i * num[a] / den[a]) for the latent index i.  Returns 1 for a hyperlatent grid.
+struct Footprint { int32_t lo[2], hi[2]; uint32_t num[2], den[2]; };
+int footprint(const ccd_cc_header& h, int grid, Footprint& f) {
+    if (grid < 0 || grid >= h.n_grids) return CCD_ERR_ARG;
+    if (h.is_hyperlatent[grid]) return 1;
+    int lat[CCD_MAX_GRIDS], n_lv = 0, lv = -1;
+    for (int g = 0; g < h.n_grids; ++g)
+        if (!h.is_hyperlatent[g]) { if (g == grid) lv = n_lv; lat[n_lv++] = g; }
+    int64_t lo = 0, hi = 0;  // in samples of the grid's own level, around the latent
+    if (lv != n_lv - 1) {    // the pre-concatenation filter: output y reads y + ky - k / 2, ky < k (the coarsest grid has none)
+        const int k = h.ups_preconcat_k_size;
+        lo -= (k - 1) - k / 2;  // so the source s reaches y = s + k / 2 - (k - 1) .. s + k / 2: (k - 1) / 2 on either side for odd k
+        hi += k / 2;
+    }
+    for (int step = 0; step < lv; ++step) {  // x2 transposed convolution: input s reaches outputs 2s + 1 - k/2 .. 2s + k - k/2
+        const int k = h.ups_k_size;
+        lo = 2 * lo + 1 - k / 2;
+        hi = 2 * hi + k - k / 2;
+    }
+    for (int l = 0; l < h.n_layer_synthesis; ++l) {  // replicate-padded k x k layers; the stabiliser and the output transform are 1 x 1
+        const int pad = h.syn_layer[l].k_size / 2;
+        lo -= pad;
+        hi += pad;
+    }
+    const int g0 = lat[0];
+    for (int a = 0; a < 2; ++a) {
+        const int64_t in = a ? h.grid_w[g0] : h.grid_h[g0], out = h.img_size[a], pitch = int64_t{1} << lv;
+        if (in == out) {  // every final resize is the identity at equal sizes
+            f.lo[a] = static_cast<int32_t>(lo); f.hi[a] = static_cast<int32_t>(hi);
+            f.num[a] = static_cast<uint32_t>(pitch); f.den[a] = 1;
+            continue;
+        }
+        // output Y reads sources around Y' = (Y + c/2) in / out - c/2 (c = 1: bilinear, bicubic; c = 0: nearest): floor(Y') for
+        // nearest, floor(Y') and the next for bilinear, floor(Y') - 1 .. floor(Y') + 2 for bicubic (index clamps only move reads
+        // towards the picture).  So a source interval [a, b] is read where a - m_lo <= Y' < b + m_hi with (m_lo, m_hi) = (0, 1),
+        // (1, 1), (2, 2), that is (2a - 2 m_lo + c) out - c in <= 2 in Y < (2b + 2 m_hi + c) out - c in.  One more half source sample
+        // on each side pays for the float32 evaluation of Y' (an error far below 1/2 at sides up to 16383).
+        const int c = h.final_upsampling_type == 0 ? 0 : 1;
+        const int64_t m_lo = h.final_upsampling_type, m_hi = h.final_upsampling_type == 2 ? 2 : 1;
+        const int64_t mlo = 2 * m_lo - c + 1, mhi = 2 * m_hi + c + 1;
+        // Y >= ((2 lo - mlo) out - c in) / (2 in) relative to i pitch out / in, whose floor is s: floor(a + b) >= floor(a) + floor(b)
+        f.lo[a] = static_cast<int32_t>(floor_div((2 * lo - mlo) * out - c * in, 2 * in));
+        // ... and ceil(a + b) <= floor(a) + 1 + ceil(b)
+        f.hi[a] = static_cast<int32_t>(ceil_div((2 * hi + mhi) * out - c * in, 2 * in) + 1);
+        f.num[a] = static_cast<uint32_t>(pitch * out); f.den[a] = static_cast<uint32_t>(in);
+    }
+    return CCD_OK;
+}
+
+// Smallest stride at which the intervals of two latents `stride` apart are disjoint along one axis of n latents and N samples
+// (and, chroma_shift = 1, their halves rounded outwards).
+int axis_stride(const Footprint& f, int a, int n, int N, int chroma_shift) {
+    for (int S = 1; S < n; ++S) {
+        bool ok = true;
+        for (int i = 0; ok && i + S < n; ++i) {
+            const int64_t s0 = static_cast<int64_t>(i) * f.num[a] / f.den[a], s1 = static_cast<int64_t>(i + S) * f.num[a] / f.den[a];
+            const int64_t end0 = std::min<int64_t>(s0 + f.hi[a], N - 1), begin1 = std::max<int64_t>(s1 + f.lo[a], 0);
+            ok = (begin1 >> chroma_shift) > (end0 >> chroma_shift);
+        }
+        if (ok) return S;
+    }
+    return std::max(n, 1);
+}
+
+int probe_stride(const ccd_cc_header& h, const Footprint& f, int grid, int frame_data_type) {
+    const int sh = frame_data_type == 1 ? 1 : 0;
+    return std::max(axis_stride(f, 0, h.grid_h[grid], h.img_size[0], sh), axis_stride(f, 1, h.grid_w[grid], h.img_size[1], sh));
+}
+
+struct PassPlan { int grid, py, px, move; };
+
+struct Candidate {
+    ccd_cc_header hdr;
+    int bitdepth = 0, frame_data_type = 0;
+    const int8_t* lat[CCD_MAX_GRIDS] = {};
+    const void* src[3] = {};
+    int base_slot = -1, first_probe = -1;
+    Block priv, maps;                        // K private copies of every grid; the int64 maps
+    size_t grid_off[CCD_MAX_GRIDS] = {};     // of grid g inside one private copy
+    size_t copy_bytes = 0;                   // of one private copy
+    size_t map_off[CCD_MAX_GRIDS] = {};
+    Footprint fp[CCD_MAX_GRIDS];
+    int stride[CCD_MAX_GRIDS] = {};          // 0: hyperlatent
+    std::vector<PassPlan> passes;            // the float passes, grid by grid
+    int status = CCD_OK;
+    bool covered = false;                    // by a finished run
+    int8_t* copy(int k, int g) const { return priv.as<int8_t>() + static_cast<size_t>(k) * copy_bytes + grid_off[g]; }
+    int64_t* map(int g) const { return reinterpret_cast<int64_t*>(maps.as<char>() + map_off[g]); }
+};
+
+struct Round {  // offsets into the tables block
+    size_t segs = 0, seg_prefix = 0, passes = 0, unit_prefix = 0, probe_prefix = 0;
+    int n_segs = 0, n_passes = 0;
+    uint32_t n_blocks = 0, n_units = 0, n_probes = 0;
+};
+}  // namespace
+
+struct ccd_dsens {
+    int device = 0, K = 0;
+    ccd_batch* batch = nullptr;
+    std::vector<std::unique_ptr<Candidate>> cands;
+    std::vector<Round> rounds;
+    Block tables, tables_host, slab;
+    bool planned = false;   // the tables describe every candidate
+    int pending = 0;        // a run is in flight
+    int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
+    std::vector<hipStream_t> streams;
+};
+
+namespace {
+DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPlan& pp, bool empty) {
+    const ccd_cc_header& h = c.hdr;
+    DsensPass P;
+    std::memset(&P, 0, sizeof(P));
+    const int g = pp.grid;
+    P.lat = c.lat[g];
+    P.map = c.map(g);
+    P.h = h.grid_h[g]; P.w = h.grid_w[g];
+    P.move = pp.move;
+    P.H = h.img_size[0]; P.W = h.img_size[1];
+    P.chroma_shift = c.frame_data_type == 1 ? 1 : 0;
+    P.wide = c.bitdepth > 8;
+    P.num_y = P.den_y = P.num_x = P.den_x = 1;
+    if (empty) {
+        P.empty = 1; P.stride = 1; P.ny = P.h; P.nx = P.w; P.upp = 1; P.rows = 1;
+        return P;
+    }
+    const Footprint& f = c.fp[g];
+    for (int p = 0; p < 3; ++p) {
+        int ph = 0, pw = 0;
+        P.base[p] = ccd_batch_plane(d->batch, c.base_slot, p, &ph, &pw);
+        P.probe[p] = ccd_batch_plane(d->batch, c.first_probe + k, p, &ph, &pw);
+        P.src[p] = c.src[p];
+    }
+    P.stride = c.stride[g]; P.py = pp.py; P.px = pp.px;
+    P.ny = (P.h - 1 - pp.py) / P.stride + 1;
+    P.nx = (P.w - 1 - pp.px) / P.stride + 1;
+    P.box[0] = f.lo[0]; P.box[1] = f.lo[1]; P.box[2] = f.hi[0]; P.box[3] = f.hi[1];
+    P.num_y = f.num[0]; P.den_y = f.den[0]; P.num_x = f.num[1]; P.den_x = f.den[1];
+    const int box_w = std::min<int64_t>(P.W, static_cast<int64_t>(f.hi[1]) - f.lo[1] + 1);
+    const int box_h = std::min<int64_t>(P.H, static_cast<int64_t>(f.hi[0]) - f.lo[0] + 1);
+    P.rows = std::max(1, kDsensBandSamples / std::max(1, box_w));
+    P.upp = (box_h + P.rows - 1) / P.rows;
+    return P;
+}
+
+// Every round's segments and passes, one block, one copy.
+int build_tables(ccd_dsens* d, hipStream_t st) {
+    const int K = d->K;
+    size_t n_rounds = 1;
+    for (const auto& c : d->cands) n_rounds = std::max(n_rounds, (c->passes.size() + K - 1) / K);
+    std::vector<char> buf;
+    auto put = [&buf](const void* p, size_t bytes) {
+        const size_t at = (buf.size() + 255) & ~size_t{255};
+        buf.resize(at + bytes);
+        if (bytes) std::memcpy(buf.data() + at, p, bytes);
+        return at;
+    };
+    d->rounds.assign(n_rounds, Round{});
+    uint32_t max_units = 1;
+    for (size_t r = 0; r < n_rounds; ++r) {
+        std::vector<DsensSeg> segs;
+        std::vector<DsensPass> passes;
+        for (const auto& cp : d->cands) {
+            const Candidate& c = *cp;
+            const ccd_cc_header& h = c.hdr;
+            auto seg = [&](int k, int g, const PassPlan* pp) {
+                DsensSeg S;
+                std::memset(&S, 0, sizeof(S));
+                S.src = c.lat[g];
+                S.dst = c.copy(k, g);
+                S.n = static_cast<uint32_t>(h.grid_h[g]) * static_cast<uint32_t>(h.grid_w[g]);
+                S.w = h.grid_w[g];
+                S.stride = 1;
+                if (pp) { S.stride = c.stride[g]; S.py = pp->py; S.px = pp->px; S.move = pp->move; }
+                segs.push_back(S);
+            };
+            for (int k = 0; k < K; ++k) {
+                const size_t i = r * K + k;
+                const PassPlan* cur = i < c.passes.size() ? &c.passes[i] : nullptr;
+                const PassPlan* prev = (r > 0 && i - K < c.passes.size()) ? &c.passes[i - K] : nullptr;
+                if (r == 0) {
+                    for (int g = 0; g < h.n_grids; ++g) seg(k, g, (cur && cur->grid == g) ? cur : nullptr);
+                } else {
+                    if (cur) seg(k, cur->grid, cur);
+                    if (prev && (!cur || cur->grid != prev->grid)) seg(k, prev->grid, nullptr);  // the grid moves on: restore
+                }
+                if (cur) passes.push_back(make_pass(d, c, k, *cur, false));
+            }
+            if (r == 0)
+                for (int g = 0; g < h.n_grids; ++g)
+                    if (h.is_hyperlatent[g])
+                        for (int move = -1; move <= 1; move += 2) passes.push_back(make_pass(d, c, 0, PassPlan{g, 0, 0, move}, true));
+        }
+        Round& R = d->rounds[r];
+        std::vector<uint32_t> seg_prefix(segs.size() + 1, 0), unit_prefix(passes.size() + 1, 0), probe_prefix(passes.size() + 1, 0);
+        uint64_t blocks = 0, units = 0, probes = 0;
+        for (size_t i = 0; i < segs.size(); ++i) { blocks += (segs[i].n + kDsensChunk - 1) / kDsensChunk; seg_prefix[i + 1] = static_cast<uint32_t>(blocks); }
+        for (size_t i = 0; i < passes.size(); ++i) {
+            const uint64_t n = static_cast<uint64_t>(passes[i].ny) * passes[i].nx;
+            probes += n;
+            units += n * passes[i].upp;
+            if (units > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+            unit_prefix[i + 1] = static_cast<uint32_t>(units);
+            probe_prefix[i + 1] = static_cast<uint32_t>(probes);
+        }
+        if (blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+        R.n_segs = static_cast<int>(segs.size()); R.n_passes = static_cast<int>(passes.size());
+        R.n_blocks = static_cast<uint32_t>(blocks); R.n_units = static_cast<uint32_t>(units); R.n_probes = static_cast<uint32_t>(probes);
+        R.segs = put(segs.data(), segs.size() * sizeof(DsensSeg));
+        R.seg_prefix = put(seg_prefix.data(), seg_prefix.size() * sizeof(uint32_t));
+        R.passes = put(passes.data(), passes.size() * sizeof(DsensPass));
+        R.unit_prefix = put(unit_prefix.data(), unit_prefix.size() * sizeof(uint32_t));
+        R.probe_prefix = put(probe_prefix.data(), probe_prefix.size() * sizeof(uint32_t));
+        max_units = std::max(max_units, R.n_units);
+    }
+    // nothing of an earlier run is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
+    if (d->tables.cls < buf.size() && !d->tables.get(d->device, BlockPool::kDevice, buf.size())) return CCD_ERR_NOMEM;
+    if (d->tables_host.cls < buf.size() && !d->tables_host.get(d->device, BlockPool::kPinned, buf.size())) return CCD_ERR_NOMEM;
+    if (d->slab.cls < max_units * sizeof(int64_t) && !d->slab.get(d->device, BlockPool::kDevice, max_units * sizeof(int64_t))) return CCD_ERR_NOMEM;
+    std::memcpy(d->tables_host.p, buf.data(), buf.size());
+    HIP_TRY(hipMemcpyAsync(d->tables.p, d->tables_host.p, buf.size(), hipMemcpyHostToDevice, st));
+    d->planned = true;
+    return CCD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ccd_latent_footprint(const ccd_cc_header* arch, int grid, int32_t box[4]) {
+    if (!arch || !box) return CCD_ERR_ARG;
+    ccd_cc_header h;
+    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
+    Footprint f;
+    const int rc = footprint(h, grid, f);
+    if (rc < 0) return rc;
+    if (rc == 1) { box[0] = box[1] = 0; box[2] = box[3] = -1; return 1; }
+    box[0] = f.lo[0]; box[1] = f.lo[1]; box[2] = f.hi[0]; box[3] = f.hi[1];
+    return CCD_OK;
+}
+
+int ccd_latent_probe_stride(const ccd_cc_header* arch, int grid, int frame_data_type) {
+    if (!arch || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
+    ccd_cc_header h;
+    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
+    Footprint f;
+    const int rc = footprint(h, grid, f);
+    if (rc < 0) return rc;
+    return rc == 1 ? 0 : probe_stride(h, f, grid, frame_data_type);
+}
+
+int ccd_dsens_create(int device, int n_probe_slots, ccd_dsens** out) {
+    if (!out) return CCD_ERR_ARG;
+    *out = nullptr;
+    if (n_probe_slots < 1 || n_probe_slots > 64) return CCD_ERR_ARG;
+    ccd_dsens* d = new (std::nothrow) ccd_dsens();
+    if (!d) return CCD_ERR_NOMEM;
+    d->device = device;
+    d->K = n_probe_slots;
+    const int rc = ccd_batch_create(device, &d->batch);
+    if (rc < 0) { delete d; return rc; }
+    // the float output is not looked at: slots that can write integer planes alone do
+    (void)ccd_batch_set_option(d->batch, CCD_OPT_KEEP_FLOAT, 0);
+    *out = d;
+    return CCD_OK;
+}
+
+void ccd_dsens_destroy(ccd_dsens* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    for (hipStream_t st : d->streams) (void)hipStreamSynchronize(st);
+    ccd_batch_destroy(d->batch);  // drains the streams it was run on
+    for (auto& c : d->cands) { c->priv.drop(); c->maps.drop(); }
+    d->tables.drop(); d->tables_host.drop(); d->slab.drop();
+    delete d;
+}
+
+int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                  const void* const* src, int bitdepth, int frame_data_type) {
+    if (!d || !arch || !bytes_nn || !latents || !src || !src[0] || !src[1] || !src[2]) return CCD_ERR_ARG;
+    if (bitdepth < 8 || bitdepth > 16 || frame_data_type < 0 || frame_data_type > 2 || d->pending) return CCD_ERR_ARG;
+    if (d->dead < 0) return d->dead;
+    std::unique_ptr<Candidate> cp(new (std::nothrow) Candidate());
+    if (!cp) return CCD_ERR_NOMEM;
+    Candidate& c = *cp;
+    if (reparse(arch, n_nn, &c.hdr) < 0) return CCD_ERR_VALUE;
+    const ccd_cc_header& h = c.hdr;
+    if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;
+    c.bitdepth = bitdepth;
+    c.frame_data_type = frame_data_type;
+    size_t map_bytes = 0;
+    for (int g = 0; g < h.n_grids; ++g) {
+        if (!latents[g]) return CCD_ERR_ARG;
+        c.lat[g] = latents[g];
+        const size_t n = static_cast<size_t>(h.grid_h[g]) * h.grid_w[g];
+        c.grid_off[g] = c.copy_bytes;
+        c.copy_bytes += (n + 255) & ~size_t{255};
+        c.map_off[g] = map_bytes;
+        map_bytes += (2 * n * sizeof(int64_t) + 255) & ~size_t{255};
+        const int rc = footprint(h, g, c.fp[g]);
+        if (rc < 0) return rc;
+        if (rc == 1) continue;
+        const int S = c.stride[g] = probe_stride(h, c.fp[g], g, frame_data_type);
+        for (int move = -1; move <= 1; move += 2)
+            for (int py = 0; py < std::min(S, h.grid_h[g]); ++py)
+                for (int px = 0; px < std::min(S, h.grid_w[g]); ++px) c.passes.push_back(PassPlan{g, py, px, move});
+    }
+    for (int p = 0; p < 3; ++p) c.src[p] = src[p];
+    // ---- the device from here on ----
+    HIP_TRY(hipSetDevice(d->device));
+    if (!c.priv.get(d->device, BlockPool::kDevice, std::max<size_t>(256, c.copy_bytes * d->K)) ||
+        !c.maps.get(d->device, BlockPool::kDevice, std::max<size_t>(256, map_bytes))) {
+        c.priv.drop(); c.maps.drop();
+        return CCD_ERR_NOMEM;
+    }
+    c.base_slot = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, latents, 1, bitdepth, frame_data_type);
+    if (c.base_slot < 0) { c.priv.drop(); c.maps.drop(); return c.base_slot; }  // (nothing was added to the batch)
+    for (int k = 0; k < d->K; ++k) {
+        const int8_t* ptrs[CCD_MAX_GRIDS];
+        for (int g = 0; g < h.n_grids; ++g) ptrs[g] = c.copy(k, g);
+        const int s = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, ptrs, 1, bitdepth, frame_data_type);
+        if (s < 0) { c.priv.drop(); c.maps.drop(); d->dead = s; return s; }
+        if (k == 0) c.first_probe = s;
+    }
+    d->planned = false;
+    d->cands.push_back(std::move(cp));
+    return static_cast<int>(d->cands.size()) - 1;
+}
+
+int ccd_dsens_run(ccd_dsens* d, void* stream) {
+    if (!d || d->pending) return CCD_ERR_ARG;
+    if (d->dead < 0) return d->dead;
+    if (d->cands.empty()) return CCD_OK;
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (std::find(d->streams.begin(), d->streams.end(), st) == d->streams.end()) d->streams.push_back(st);
+    if (!d->planned) {
+        const int rc = build_tables(d, st);
+        if (rc < 0) return rc;
+    }
+    const char* base = d->tables.as<char>();
+    d->pending = 1;
+    for (const Round& R : d->rounds) {
+        HIP_TRY(launch_dsens_apply(reinterpret_cast<const DsensSeg*>(base + R.segs), reinterpret_cast<const uint32_t*>(base + R.seg_prefix), R.n_segs,
+                                   R.n_blocks, st));
+        const int rc = ccd_batch_run(d->batch, stream);
+        if (rc < 0) return rc;
+        HIP_TRY(launch_dsens_sse(reinterpret_cast<const DsensPass*>(base + R.passes), reinterpret_cast<const uint32_t*>(base + R.unit_prefix),
+                                 reinterpret_cast<const uint32_t*>(base + R.probe_prefix), R.n_passes, R.n_units, R.n_probes,
+                                 d->slab.as<int64_t>(), st));
+    }
+    return CCD_OK;
+}
+
+int ccd_dsens_wait(ccd_dsens* d, void* stream) {
+    if (!d) return CCD_ERR_ARG;
+    if (d->cands.empty() || !d->planned) {
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+        d->pending = 0;
+        return CCD_OK;
+    }
+    const int rc = ccd_batch_wait(d->batch, stream);  // synchronises; the first error of the batch's slots
+    const bool ran = d->pending != 0;
+    d->pending = 0;
+    if (rc < 0 && rc != CCD_ERR_VALUE) return rc;
+    if (!ran) return CCD_OK;
+    int first = CCD_OK;
+    for (auto& cp : d->cands) {
+        Candidate& c = *cp;
+        c.status = ccd_batch_slot_status(d->batch, c.base_slot);
+        for (int k = 0; c.status == CCD_OK && k < d->K; ++k) c.status = ccd_batch_slot_status(d->batch, c.first_probe + k);
+        c.covered = true;
+        if (first == CCD_OK && c.status != CCD_OK) first = c.status;
+    }
+    return first;
+}
+
+int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr) {
+    if (!d || !dev_ptr || slot < 0 || slot >= static_cast<int>(d->cands.size())) return CCD_ERR_ARG;
+    const Candidate& c = *d->cands[slot];
+    if (grid < 0 || grid >= c.hdr.n_grids || !c.covered || d->pending) return CCD_ERR_ARG;
+    if (c.status != CCD_OK) return c.status;
+    *dev_ptr = c.map(grid);
+    return static_cast<int64_t>(c.hdr.grid_h[grid]) * c.hdr.grid_w[grid];
+}
+
+int ccd_dsens_passes(const ccd_dsens* d, int slot) {
+    if (!d || slot < 0 || slot >= static_cast<int>(d->cands.size())) return CCD_ERR_ARG;
+    return static_cast<int>(d->cands[slot]->passes.size());
+}
+
+}  // extern "C"

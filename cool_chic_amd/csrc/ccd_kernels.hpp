@@ -77,4 +77,8 @@ hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* 
 // ccd_ingest.hip
 hipError_t launch_latent_ingest(const IngestSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, int32_t* d_status_all,
                                 int word, hipStream_t stream);
+// ccd_dsens.hip
+hipError_t launch_dsens_apply(const DsensSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, hipStream_t stream);
+hipError_t launch_dsens_sse(const DsensPass* d_passes, const uint32_t* d_unit_prefix, const uint32_t* d_probe_prefix, int n_passes,
+                            uint32_t n_units, uint32_t n_probes, int64_t* d_slab, hipStream_t stream);
 }  // namespace ccd

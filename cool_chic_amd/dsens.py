@@ -1,0 +1,89 @@
+"""DistortionDeltas: what moving ONE latent by -1 / +1 does to the squared error of the decoded planes, for every latent of
+every grid, on one MI355X (wraps the ccd_dsens_* C ABI).
+
+The numbers are those of one decode per moved latent (DecodeBatch.add_latents + QualityMeter), as integers; they come from a
+few thousand passes of the float path per picture, each of which moves every latent of one lattice at once."""
+import ctypes as C
+from typing import List, Sequence, Tuple
+
+from ._lib import CCHeader, check, lib
+from .batch import _DevArray
+
+SENTINEL = -2 ** 63  # the entry where v - 1 / v + 1 leaves [-64, 63] (INT64_MIN)
+
+
+def latent_footprint(arch: CCHeader, grid: int):
+    """(top, left, bottom, right) in luma samples around the latent (0, 0) of `grid` (include/ccd.h: ccd_latent_footprint),
+    or None for a hyperlatent grid.  Host only."""
+    box = (C.c_int32 * 4)()
+    rc = check(lib().ccd_latent_footprint(C.byref(arch), int(grid), box), "ccd_latent_footprint")
+    return None if rc == 1 else tuple(int(v) for v in box)
+
+
+def probe_stride(arch: CCHeader, grid: int, frame_data_type: int = 0) -> int:
+    """The lattice stride of the grid's passes (ccd_latent_probe_stride); 0 for a hyperlatent grid.  Host only."""
+    return check(lib().ccd_latent_probe_stride(C.byref(arch), int(grid), int(frame_data_type)), "ccd_latent_probe_stride")
+
+
+class DistortionDeltas:
+    """One slot per candidate; run() enqueues every pass of every slot, wait() ends it, delta_map() hands out the maps."""
+
+    def __init__(self, device: int = 0, n_probe_slots: int = 16):
+        self._h = C.c_void_p()
+        check(lib().ccd_dsens_create(int(device), int(n_probe_slots), C.byref(self._h)), "ccd_dsens_create")
+        self.device = int(device)
+        self._owners: List[object] = []  # whatever owns the device latents and source planes the slots read at run()
+        self._grid_shapes: List[List[Tuple[int, int]]] = []
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().ccd_dsens_destroy(self._h)
+            self._h = C.c_void_p()
+            self._owners = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self._grid_shapes)
+
+    def add(self, arch: CCHeader, bytes_nn: bytes, latent_ptrs: Sequence[int], source_ptrs: Sequence[int], bitdepth: int,
+            frame_data_type: int, owner=None) -> int:
+        """Device latents (int8 [h][w] per grid, read at every run, never written) and the three device planes of the source
+        (uint8 at 8 bits, else uint16; half-size chroma for yuv420).  Returns the slot."""
+        lat = (C.c_void_p * len(latent_ptrs))(*[int(p) for p in latent_ptrs])
+        src = (C.c_void_p * 3)(*[int(p) for p in source_ptrs])
+        slot = check(lib().ccd_dsens_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), lat, src, int(bitdepth), int(frame_data_type)),
+                     "ccd_dsens_add")
+        self._grid_shapes.append([(int(arch.grid_h[g]), int(arch.grid_w[g])) for g in range(len(latent_ptrs))])
+        if owner is not None:
+            self._owners.append(owner)
+        return slot
+
+    def run(self, stream: int = 0):
+        check(lib().ccd_dsens_run(self._h, C.c_void_p(stream or None)), "ccd_dsens_run")
+
+    def wait(self, stream: int = 0):
+        check(lib().ccd_dsens_wait(self._h, C.c_void_p(stream or None)), "ccd_dsens_wait")
+
+    def passes(self, slot: int) -> int:
+        """Passes of the float path one run spends on the slot."""
+        return check(lib().ccd_dsens_passes(self._h, int(slot)), "ccd_dsens_passes")
+
+    def delta_map(self, slot: int, grid: int) -> _DevArray:
+        """After run() + wait(): int64 [2][h][w], the change of the frame's squared error if the latent at (y, x) alone were
+        v - 1 (plane 0) or v + 1 (plane 1); SENTINEL where that leaves [-64, 63].  Valid until the next run / close."""
+        ptr = C.c_void_p()
+        n = check(lib().ccd_dsens_slot_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_dsens_slot_map")
+        h, w = self._grid_shapes[int(slot)][int(grid)]
+        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
+        return _DevArray(ptr.value or 0, (2, h, w), "<i8", self)

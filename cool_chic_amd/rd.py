@@ -26,6 +26,7 @@ import torch
 
 from ._lib import CCHeader
 from .batch import FRAME_DATA_TYPES, DecodeBatch
+from .dsens import SENTINEL, DistortionDeltas
 from .encoder import EncodeBatch, SlotRate
 from .io import FrameData
 from .quality import FrameQuality, QualityMeter, _frame_planes
@@ -52,8 +53,12 @@ class RdEvaluator:
     """add() candidates, then evaluate(lmbda): one DecodeBatch of given latents, one EncodeBatch over the same device grids,
     one scoring.  evaluate() may be called again (another lambda, or after device latents were changed in place)."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, n_probe_slots: int = 16):
+        """n_probe_slots: float-path passes in flight per candidate when distortion deltas are asked for (DistortionDeltas)."""
         self.device = int(device)
+        self._n_probe_slots = int(n_probe_slots)
+        self._dd = None             # DistortionDeltas over the candidates, made when first asked for
+        self._jobs: List[tuple] = []  # (arch, bytes_nn) per candidate, for it
         self._dec = DecodeBatch(self.device)
         self._enc = EncodeBatch(self.device)
         self._meter = QualityMeter(self.device)
@@ -61,6 +66,9 @@ class RdEvaluator:
         self._frames: List[FrameData] = []
 
     def close(self):
+        if self._dd is not None:
+            self._dd.close()
+            self._dd = None
         self._enc.close()
         self._dec.close()
         self._meter.close()
@@ -91,11 +99,13 @@ class RdEvaluator:
         self._enc.add_device(arch, bytes_nn, self._dec.latent_ptrs(slot), owner=self._dec)
         self._sources.append(_frame_planes(source, torch.device(f"cuda:{self.device}")))
         self._frames.append(source)
+        self._jobs.append((arch, bytes_nn))
         return slot
 
-    def evaluate(self, lmbda: float, ms_ssim: bool = False, rate_deltas: bool = False) -> List[Candidate]:
+    def evaluate(self, lmbda: float, ms_ssim: bool = False, rate_deltas: bool = False, distortion_deltas: bool = False) -> List[Candidate]:
         """rate_deltas: the rate comes from EncodeBatch.measure_deltas, which leaves the same numbers and, for
-        rate_delta_map(), what every latent's +-1 would do to them."""
+        rate_delta_map(), what every latent's +-1 would do to them.  distortion_deltas: a DistortionDeltas run over the same
+        device grids follows, for distortion_delta_map() and cost_delta_map(); the candidates returned are the same."""
         n = len(self._frames)
         if n == 0:
             return []
@@ -110,6 +120,16 @@ class RdEvaluator:
         results = self._meter.finish()
         self._dec.wait(st)          # a refused device latent raises here (CCD_ERR_VALUE)
         self._enc.wait(st)
+        if distortion_deltas:       # reads the grids in the decode batch's arenas and the sources the meter read
+            if self._dd is None:
+                self._dd = DistortionDeltas(self.device, self._n_probe_slots)
+            for s in range(len(self._dd), n):
+                arch, bytes_nn = self._jobs[s]
+                f = self._frames[s]
+                self._dd.add(arch, bytes_nn, self._dec.latent_ptrs(s), [t.data_ptr() for t in self._sources[s]], f.bitdepth,
+                             FRAME_DATA_TYPES.index(f.frame_data_type), owner=self._dec)
+            self._dd.run(st)
+            self._dd.wait(st)
         out = []
         for s, (r, f) in enumerate(zip(results, self._frames)):
             rate = self._enc.rate(s)
@@ -121,3 +141,25 @@ class RdEvaluator:
     def rate_delta_map(self, slot: int, grid: int):
         """After evaluate(rate_deltas=True): EncodeBatch.delta_map of the candidate (device, float32 [2][h][w])."""
         return self._enc.delta_map(slot, grid)
+
+    def distortion_delta_map(self, slot: int, grid: int):
+        """After evaluate(distortion_deltas=True): DistortionDeltas.delta_map of the candidate (device, int64 [2][h][w])."""
+        if self._dd is None:
+            raise RuntimeError("no evaluate(distortion_deltas=True) has run")
+        return self._dd.delta_map(slot, grid)
+
+    def cost_delta_map(self, slot: int, grid: int, lmbda: float) -> torch.Tensor:
+        """After evaluate(rate_deltas=True, distortion_deltas=True): what moving the latent (y, x) of `grid` by -1 (plane 0) or
+        +1 (plane 1) does to the candidate's cost, the module's definition applied to the move - float64 [2][h][w] on the device,
+
+            dD / (n_samples * (2^bitdepth - 1)^2) + lmbda * dBits / n_pixels
+
+        and +inf where the move leaves [-64, 63]."""
+        dev = f"cuda:{self.device}"
+        f = self._frames[slot]
+        n_samples = sum(int(t.numel()) for t in self._sources[slot])
+        maxv = float(2 ** f.bitdepth - 1)
+        dd = torch.as_tensor(self.distortion_delta_map(slot, grid), device=dev)
+        db = torch.as_tensor(self.rate_delta_map(slot, grid), device=dev).to(torch.float64)
+        cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(f.n_pixels)
+        return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)

@@ -492,6 +492,64 @@ double ccd_quality_ms_ssim(const ccd_quality_result* r, int plane);
  * device scratch the scoring takes from the block cache, or CCD_ERR_ARG. */
 int64_t ccd_quality_scratch_bytes(const ccd_quality_item* items, int n, int what);
 
+/* ---- distortion deltas: the exact change of a frame's squared error if ONE latent were v - 1 or v + 1
+ * Take a candidate (arch, networks, latents) and a source frame.  For grid g, position (y, x) and sign s in {-1, +1}:
+ *
+ *     dD[s][g][y][x] = SSE(planes decoded with latent[g][y][x] + s, everything else unchanged)
+ *                    - SSE(planes decoded with the latents as given)
+ *
+ * SSE is the sum over all three integer planes of (decoded - source)^2, the quality meter's definition (section 4.11); the
+ * value is a signed 64-bit integer.  Where v + s leaves [-64, 63] the entry is INT64_MIN (the +inf of the rate deltas).  A
+ * hyperlatent grid (is_hyperlatent[g]) does not feed the synthesis: its map is all zeros (the sentinel at the alphabet's ends)
+ * and costs no passes.  Layout: int64 [2][h][w] per grid on the device, s = -1 first, like ccd_enc_slot_delta_map.  Intra
+ * frames only: frame_data_type 0 rgb, 1 yuv420, 2 yuv444 at 8..16 bits.
+ *
+ * No float arithmetic of its own: the planes of a moved latent come from given-latent slots of a decode batch the handle owns
+ * (per candidate one base slot that reads the caller's latents and n_probe_slots slots that read private copies, all with
+ * on_device = 1).  One pass of the float path moves every latent of one lattice (y % S == py, x % S == px) of one grid by s: the
+ * stride S is wide enough that the samples two of them can change do not overlap, and the squared-error change inside a
+ * probe's own box is its entry - the number one decode per latent would give.
+ *
+ * ccd_latent_footprint (host only): box = {top, left, bottom, right}, offsets in luma samples for the latent (0, 0) of `grid`.
+ * A move of the latent (y, x) can only change the samples in rows [sy + top, sy + bottom] and columns [sx + left, sx + right],
+ * clipped to the picture, where sy = floor(y * 2^l * img_size[0] / grid_h[g0]) and sx = floor(x * 2^l * img_size[1] / grid_w[g0]):
+ * g0 is the finest latent grid (the resolution of the synthesis), l the number of latent grids finer than `grid` (the grid's
+ * pixel pitch is 2^l when there is no final resize).  The 4:2:0 chroma planes take the box halved, rounded outwards.  Derived
+ * from the supports of the filters alone; it may be conservative, never too small.  Returns 0; 1 for a
+ * hyperlatent grid, which has no footprint (box = {0, 0, -1, -1}); CCD_ERR_ARG for NULL or a bad grid, CCD_ERR_VALUE for an
+ * `arch` whose transmitted fields do not re-parse.
+ * ccd_latent_probe_stride (host only): the stride S the passes of `grid` use for a frame of this frame_data_type: the smallest
+ * for which the boxes (and, 4:2:0, the chroma boxes) of two latents S apart in either direction are disjoint.  0 for a
+ * hyperlatent grid; errors as above, and CCD_ERR_ARG for a frame_data_type other than 0, 1, 2.
+ *
+ * ccd_dsens_add: `arch`, `bytes_nn` as for ccd_batch_add_latents; latents[g] = DEVICE int8 [grid_h[g]][grid_w[g]], read at
+ * every run and never written; src[p] = DEVICE planes of the source (u8 if bitdepth == 8 else u16, half-size chroma for
+ * yuv420), read at every run.  Both must stay valid while the handle may run.  Returns the slot index.  CCD_ERR_ARG - before
+ * the device is touched - for a NULL argument (a NULL latents[g] or src[p] included), a bit depth outside 8..16, a
+ * frame_data_type other than 0, 1, 2, a run in flight; CCD_ERR_VALUE for an `arch` that does not re-parse.
+ * ccd_dsens_create: n_probe_slots outside 1..64 and a NULL `out` are CCD_ERR_ARG, found before the device is touched.  The
+ * maps do not depend on n_probe_slots, nor on what else the handle holds.
+ * ccd_dsens_run enqueues, on `stream`, rounds of up to n_probe_slots passes per candidate: apply (ccd_dsens.hip), ccd_batch_run,
+ * squared-error split.  ccd_dsens_wait synchronises and returns the first per-slot error: a base latent outside [-64, 63] is
+ * that slot's CCD_ERR_VALUE, the other slots are unaffected.  One run may be in flight per handle; a handle can be run again
+ * (after the caller changed its latents in place, say) and can take more slots after a wait.
+ * ccd_dsens_slot_map: device pointer to int64 [2][grid_h][grid_w] and grid_h * grid_w as the return value; valid until the next
+ * run / destroy.  The slot's error in place of a map; CCD_ERR_ARG for a NULL argument, a bad slot or grid, a slot no finished
+ * run covered.
+ * ccd_dsens_passes: float-path passes one run spends on the slot, 2 * sum over its latent grids of min(S, h) * min(S, w)
+ * (known at add).  ccd_dsens_destroy drains the streams the handle was given. */
+typedef struct ccd_dsens ccd_dsens;
+int ccd_latent_footprint(const ccd_cc_header* arch, int grid, int32_t box[4]);
+int ccd_latent_probe_stride(const ccd_cc_header* arch, int grid, int frame_data_type);
+int ccd_dsens_create(int device, int n_probe_slots, ccd_dsens** out);
+void ccd_dsens_destroy(ccd_dsens* d);
+int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                  const void* const* src, int bitdepth, int frame_data_type);
+int ccd_dsens_run(ccd_dsens* d, void* stream);
+int ccd_dsens_wait(ccd_dsens* d, void* stream);
+int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr);
+int ccd_dsens_passes(const ccd_dsens* d, int slot);
+
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):
  * left[i], right[i] as the entropy kernel sees them (exhaustive parity tests of the f64 CDF). */
 int ccd_debug_laplace_bounds(int device, const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* s,
