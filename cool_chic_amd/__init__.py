@@ -15,9 +15,11 @@ package is the thin host-side mirror of the reference's decode surface:
     bitstream.encode.encode_frame (range-coding of the latents, encode.py:83-92)
                                                    encoder.EncodeBatch, writer.encode_coolchic(device=...)
     training.loss.loss_function on a candidate (distortion + lmbda * rate, training/loss.py:158)
-                                                   rd.RdEvaluator (exact integer ARM and integer planes, no search)
+                                                   rd.RdEvaluator (exact integer ARM and integer planes)
     (no counterpart: what moving one latent by +-1 does to the squared error of the decoded planes)
                                                    dsens.DistortionDeltas, RdEvaluator.cost_delta_map
+    (no counterpart: a requantisation step that moves latents by +-1 where the moves provably add)
+                                                   rdoq.RdoqStep, RdEvaluator.descend
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -33,6 +35,10 @@ def __getattr__(name):
         from .dsens import DistortionDeltas
 
         return DistortionDeltas
+    if name == "RdoqStep":
+        from .rdoq import RdoqStep
+
+        return RdoqStep
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -84,6 +84,11 @@ class EncRate(C.Structure):
                 ("n_bytes_nn", C.c_int64), ("n_bytes_header", C.c_int64)]
 
 
+class RdoqResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_grids", C.c_int32), ("n_candidates", C.c_int64), ("n_moves", C.c_int64),
+                ("n_moves_grid", C.c_int64 * MAX_GRIDS), ("d_sse", C.c_int64), ("d_bits", C.c_double), ("d_cost", C.c_double)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -191,6 +196,17 @@ SIGNATURES = {
     "ccd_dsens_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_dsens_slot_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_dsens_passes": (C.c_int, [C.c_void_p, C.c_int]),
+    "ccd_rdoq_cell": (C.c_int, []),
+    "ccd_rdoq_influence_box": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "ccd_rdoq_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_destroy": (None, [C.c_void_p]),
+    "ccd_rdoq_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_set_maps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                C.c_void_p]),
+    "ccd_rdoq_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_rdoq_slot_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RdoqResult)]),
+    "ccd_rdoq_slot_moves": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

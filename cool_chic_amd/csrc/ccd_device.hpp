@@ -143,6 +143,35 @@ struct DsensPass {
 constexpr uint32_t kDsensChunk = 4096;   // bytes one 64-lane workgroup of dsens_apply_kernel writes
 constexpr int kDsensBandSamples = 4096;  // luma samples of a band, about
 
+// ---- RDOQ step (ccd_rdoq.hip, ccd_rdoq_api.cpp) ----
+constexpr int kRdoqCell = 8;             // luma samples per side of a claim-raster cell (even: a 4:2:0 chroma sample lies in one cell)
+constexpr uint32_t kRdoqLaneCells = 32;  // a box of up to this many cells is walked by its latent's lane, a larger one by a wave
+constexpr uint32_t kRdoqChunk = 1024;    // latents one workgroup of the reduce launch sums
+// The influence box of a latent in cells of the claim raster, inclusive (ccd_rdoq_influence_box).
+struct RdoqBox { uint16_t top, left, bottom, right; };
+// One grid of one slot.  The latents of a slot are numbered uid = first + y * w + x over its grids.
+struct RdoqGrid {
+    int8_t* lat;             // the caller's grid [h][w]: the only memory of the caller's a step writes
+    const int64_t* dd;       // [2][h][w], nullptr: zeros
+    const float* db;         // [2][h][w]
+    int8_t* moves;           // [h][w]: -1, 0, +1
+    uint8_t* pick;           // [h][w]: 0 no candidate, 1 candidate for -1, 2 candidate for +1 (claim -> select, reduce)
+    const RdoqBox* box;      // [h][w]
+    const uint32_t* big;     // indices y * w + x of the latents whose box has more than kRdoqLaneCells cells, ascending
+    uint32_t n, first;       // h * w; uid of (0, 0)
+    int32_t slot, grid;
+};
+struct RdoqSlot {
+    unsigned long long* raster;  // [cells_h][cells_w] claim words, all ones between two steps
+    int32_t cells_h, cells_w;
+    double kD, kR, min_gain;
+    uint64_t grid_mask;          // bit g admits the candidates of grid g
+    int32_t first_grid, n_grids; // its entries of the grid table
+    uint32_t raster_units;       // 16-byte units of the raster block
+};
+// What one workgroup of the reduce launch leaves for a chunk of kRdoqChunk latents of one grid.
+struct RdoqPartial { int64_t n_candidates, n_moves, d_sse; double d_bits; };
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

@@ -11,7 +11,9 @@ using namespace ccd;
 namespace {
 int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0 && ((a < 0) != (b < 0))) ? 1 : 0); }  // b > 0
 int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+}  // namespace
 
+namespace ccd {
 // The transmitted fields of `arch` with the geometry they imply (what ccd_batch_add_latents does with them).
 int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out) {
     uint8_t hb[256];
@@ -26,7 +28,6 @@ int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out) {
 
 // Where a move of one latent of `grid` can reach (supports only).  Per axis a (0 rows, 1 columns): the samples
 // [s + lo[a], s + hi[a]] with s = floor(i * num[a] / den[a]) for the latent index i.  Returns 1 for a hyperlatent grid.
-struct Footprint { int32_t lo[2], hi[2]; uint32_t num[2], den[2]; };
 int footprint(const ccd_cc_header& h, int grid, Footprint& f) {
     if (grid < 0 || grid >= h.n_grids) return CCD_ERR_ARG;
     if (h.is_hyperlatent[grid]) return 1;
@@ -73,7 +74,9 @@ int footprint(const ccd_cc_header& h, int grid, Footprint& f) {
     }
     return CCD_OK;
 }
+}  // namespace ccd
 
+namespace {
 // Smallest stride at which the intervals of two latents `stride` apart are disjoint along one axis of n latents and N samples
 // (and, chroma_shift = 1, their halves rounded outwards).
 int axis_stride(const Footprint& f, int a, int n, int N, int chroma_shift) {

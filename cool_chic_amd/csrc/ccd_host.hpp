@@ -157,6 +157,12 @@ void fill_entropy_model(const ccd_cc_header& h, const Network& net, const IntNet
 bool grids_nest(const ccd_cc_header& h);
 // Plans every launch of the batch and uploads the tables they read, when slots were added since the last call (or `regroup`).
 int build_launch_tables(ccd_batch* b, hipStream_t st);
+// (ccd_dsens_api.cpp) The transmitted fields of `arch` with the geometry they imply, and where a move of one latent of `grid`
+// can reach: per axis a (0 rows, 1 columns) the samples [s + lo[a], s + hi[a]], s = floor(i * num[a] / den[a]) for the latent
+// index i, before clipping to the picture.  footprint() returns 1 for a hyperlatent grid.
+struct Footprint { int32_t lo[2], hi[2]; uint32_t num[2], den[2]; };
+int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out);
+int footprint(const ccd_cc_header& h, int grid, Footprint& f);
 
 }  // namespace ccd
 

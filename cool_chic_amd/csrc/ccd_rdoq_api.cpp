@@ -1,0 +1,373 @@
+// ccd_rdoq_api.cpp - ccd_rdoq_* of include/ccd.h: the host side of one RDOQ step.  The geometry of the
+// influence boxes is stated once, in influence_box() below: ccd_rdoq_influence_box answers from it and ccd_rdoq_add builds the
+// device tables from it.
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "ccd_host.hpp"
+#include "ccd_kernels.hpp"
+
+using namespace ccd;
+
+namespace {
+// What the boxes of a cool-chic follow from.
+struct Geometry {
+    ccd_cc_header h;
+    int level[CCD_MAX_GRIDS];          // size changes between grid 0 and grid g
+    int dy[kMaxCtx], dx[kMaxCtx];      // context k of (y, x) is the latent (y - dy[k], x + dx[k])
+    bool has_foot[CCD_MAX_GRIDS];
+    Footprint fp[CCD_MAX_GRIDS];
+    int chroma_shift;
+    int cells_h, cells_w;
+};
+
+int make_geometry(const ccd_cc_header* arch, int frame_data_type, Geometry& G) {
+    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &G.h) < 0) return CCD_ERR_VALUE;
+    const ccd_cc_header& h = G.h;
+    if (h.n_grids < 1 || h.grid_h[0] < 1 || h.grid_w[0] < 1 || h.img_size[0] < 1 || h.img_size[1] < 1) return CCD_ERR_VALUE;
+    if (h.spatial_context_arm < 0 || h.spatial_context_arm > kMaxCtx) return CCD_ERR_VALUE;
+    int level = 0;
+    for (int g = 0; g < h.n_grids; ++g) {
+        if (g > 0 && (h.grid_h[g] != h.grid_h[g - 1] || h.grid_w[g] != h.grid_w[g - 1])) ++level;
+        if (level > 30) return CCD_ERR_UNSUPPORTED;
+        G.level[g] = level;
+        const int rc = footprint(h, g, G.fp[g]);
+        if (rc < 0) return rc;
+        G.has_foot[g] = rc == 0;
+    }
+    context_offsets(h.spatial_context_arm, G.dy, G.dx);
+    G.chroma_shift = frame_data_type == 1 ? 1 : 0;
+    G.cells_h = (h.img_size[0] + kRdoqCell - 1) / kRdoqCell;
+    G.cells_w = (h.img_size[1] + kRdoqCell - 1) / kRdoqCell;
+    if (G.cells_h > 0xffff || G.cells_w > 0xffff) return CCD_ERR_UNSUPPORTED;
+    return CCD_OK;
+}
+
+// A rectangle of luma samples that grows: {top, left, bottom, right}, inclusive.
+struct Rect {
+    int64_t r[4] = {INT64_MAX, INT64_MAX, -1, -1};
+    void add(int64_t top, int64_t left, int64_t bottom, int64_t right) {
+        if (top > bottom || left > right) return;
+        r[0] = std::min(r[0], top); r[1] = std::min(r[1], left);
+        r[2] = std::max(r[2], bottom); r[3] = std::max(r[3], right);
+    }
+};
+
+// area() of the pixels rows qy0 .. qy1, columns qx0 .. qx1 of grid g (the union of their areas is a rectangle: area is monotone
+// in the pixel's index along each axis).
+void add_area(const Geometry& G, int g, int64_t qy0, int64_t qy1, int64_t qx0, int64_t qx1, Rect& R) {
+    const ccd_cc_header& h = G.h;
+    int64_t lo[2], hi[2];
+    for (int a = 0; a < 2; ++a) {
+        const int64_t n0 = a ? h.grid_w[0] : h.grid_h[0], N = h.img_size[a];
+        const int64_t q0 = a ? qx0 : qy0, q1 = a ? qx1 : qy1;
+        lo[a] = ((q0 << G.level[g]) * N) / n0;
+        const int64_t end = std::min((q1 + 1) << G.level[g], n0);
+        hi[a] = (end * N + n0 - 1) / n0 - 1;
+        lo[a] = std::min(lo[a], N - 1);
+        hi[a] = std::max(lo[a], std::min(hi[a], N - 1));  // never empty, inside the picture
+    }
+    R.add(lo[0], lo[1], hi[0], hi[1]);
+}
+
+// The influence box of the latent (y, x) of grid m, in cells.
+RdoqBox influence_box(const Geometry& G, int m, int y, int x) {
+    const ccd_cc_header& h = G.h;
+    Rect R;
+    add_area(G, m, y, y, x, x, R);
+    // dep(p), DESIGN.md 4.10 "Rate sensitivity": the spatial dependents ...
+    for (int k = 0; k < h.spatial_context_arm; ++k) {
+        const int qy = y + G.dy[k], qx = x - G.dx[k];
+        if (qy >= 0 && qy < h.grid_h[m] && qx >= 0 && qx < h.grid_w[m]) add_area(G, m, qy, qy, qx, qx, R);
+    }
+    // ... and the IFCE blocks of the finer grids
+    for (int g = 0; g < m; ++g) {
+        if (!(h.input_features_ifce[g] > 0 && g != h.n_grids - 1 && m - g - 1 < h.input_features_ifce[g])) continue;
+        const int64_t side = int64_t{2} << (G.level[m] - G.level[g + 1]);
+        const int64_t r0 = y * side, r1 = std::min<int64_t>((y + 1) * side, h.grid_h[g]) - 1;
+        const int64_t c0 = x * side, c1 = std::min<int64_t>((x + 1) * side, h.grid_w[g]) - 1;
+        if (r0 <= r1 && c0 <= c1) add_area(G, g, r0, r1, c0, c1, R);
+    }
+    if (G.has_foot[m]) {  // the clipped footprint; with 4:2:0 the halved box too, in luma samples
+        const Footprint& f = G.fp[m];
+        int64_t lo[2], hi[2];
+        for (int a = 0; a < 2; ++a) {
+            const int64_t s = static_cast<int64_t>(a ? x : y) * f.num[a] / f.den[a], N = h.img_size[a];
+            lo[a] = std::max<int64_t>(s + f.lo[a], 0);
+            hi[a] = std::min<int64_t>(s + f.hi[a], N - 1);
+            if (G.chroma_shift && lo[a] <= hi[a]) {
+                lo[a] = (lo[a] >> 1) << 1;
+                hi[a] = std::min<int64_t>(((hi[a] >> 1) << 1) + 1, N - 1);
+            }
+        }
+        R.add(lo[0], lo[1], hi[0], hi[1]);
+    }
+    RdoqBox b;
+    b.top = static_cast<uint16_t>(R.r[0] / kRdoqCell); b.left = static_cast<uint16_t>(R.r[1] / kRdoqCell);
+    b.bottom = static_cast<uint16_t>(R.r[2] / kRdoqCell); b.right = static_cast<uint16_t>(R.r[3] / kRdoqCell);
+    return b;
+}
+
+size_t up256(size_t n) { return (n + 255) & ~size_t{255}; }
+
+struct RSlot {
+    Geometry geo;
+    int n_grids = 0;
+    int8_t* lat[CCD_MAX_GRIDS] = {};
+    const int64_t* dd[CCD_MAX_GRIDS] = {};
+    const float* db[CCD_MAX_GRIDS] = {};
+    bool have_maps = false;
+    Block mem;                               // boxes, big lists, move maps, pick bytes, raster
+    size_t box_off[CCD_MAX_GRIDS] = {}, big_off[CCD_MAX_GRIDS] = {}, moves_off[CCD_MAX_GRIDS] = {}, pick_off[CCD_MAX_GRIDS] = {};
+    size_t raster_off = 0;
+    uint32_t n[CCD_MAX_GRIDS] = {}, n_big[CCD_MAX_GRIDS] = {}, first[CCD_MAX_GRIDS] = {};
+    uint32_t raster_units = 0;
+    double kD = 0, kR = 0;
+    ccd_rdoq_result result;
+    bool covered = false;                    // by a finished step
+};
+}  // namespace
+
+struct ccd_rdoq {
+    int device = 0;
+    std::vector<std::unique_ptr<RSlot>> slots;
+    Block tables, tables_host, partial, results, results_host;
+    int pending = 0;       // a step is in flight
+    int n_stepped = 0;     // slots the step in flight covers
+    hipStream_t step_stream = nullptr;  // ... and the stream it was enqueued on
+    std::vector<hipStream_t> streams;
+};
+
+extern "C" {
+
+int ccd_rdoq_cell(void) { return kRdoqCell; }
+
+int ccd_rdoq_influence_box(const ccd_cc_header* arch, int frame_data_type, int grid, int y, int x, int32_t cells[4]) {
+    if (!arch || !cells || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
+    std::unique_ptr<Geometry> G(new (std::nothrow) Geometry());
+    if (!G) return CCD_ERR_NOMEM;
+    const int rc = make_geometry(arch, frame_data_type, *G);
+    if (rc < 0) return rc;
+    if (grid < 0 || grid >= G->h.n_grids || y < 0 || y >= G->h.grid_h[grid] || x < 0 || x >= G->h.grid_w[grid]) return CCD_ERR_ARG;
+    const RdoqBox b = influence_box(*G, grid, y, x);
+    cells[0] = b.top; cells[1] = b.left; cells[2] = b.bottom; cells[3] = b.right;
+    return CCD_OK;
+}
+
+int ccd_rdoq_create(int device, ccd_rdoq** out) {
+    if (!out) return CCD_ERR_ARG;
+    *out = nullptr;
+    ccd_rdoq* r = new (std::nothrow) ccd_rdoq();
+    if (!r) return CCD_ERR_NOMEM;
+    r->device = device;
+    *out = r;
+    return CCD_OK;
+}
+
+void ccd_rdoq_destroy(ccd_rdoq* r) {
+    if (!r) return;
+    if (!r->slots.empty()) {
+        (void)hipSetDevice(r->device);
+        for (hipStream_t st : r->streams) (void)hipStreamSynchronize(st);
+    }
+    for (auto& s : r->slots) s->mem.drop();
+    r->tables.drop(); r->tables_host.drop(); r->partial.drop(); r->results.drop(); r->results_host.drop();
+    delete r;
+}
+
+int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, int8_t* const* latents) {
+    if (!r || !arch || !latents || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
+    if (r->pending) return CCD_ERR_ARG;
+    std::unique_ptr<RSlot> sp(new (std::nothrow) RSlot());
+    if (!sp) return CCD_ERR_NOMEM;
+    RSlot& s = *sp;
+    const int rc = make_geometry(arch, frame_data_type, s.geo);
+    if (rc < 0) return rc;
+    const ccd_cc_header& h = s.geo.h;
+    s.n_grids = h.n_grids;
+    uint64_t total = 0;
+    for (int g = 0; g < h.n_grids; ++g) {
+        if (!latents[g]) return CCD_ERR_ARG;
+        s.lat[g] = latents[g];
+        s.first[g] = static_cast<uint32_t>(total);
+        total += static_cast<uint64_t>(h.grid_h[g]) * h.grid_w[g];
+        if (total > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+        s.n[g] = static_cast<uint32_t>(h.grid_h[g]) * static_cast<uint32_t>(h.grid_w[g]);
+    }
+    // the boxes of every latent and the lists of those a wave walks, laid out as they go to the device
+    std::vector<std::vector<RdoqBox>> boxes(h.n_grids);
+    std::vector<std::vector<uint32_t>> big(h.n_grids);
+    size_t bytes = 0;
+    for (int g = 0; g < h.n_grids; ++g) {
+        boxes[g].resize(s.n[g]);
+        for (int y = 0; y < h.grid_h[g]; ++y)
+            for (int x = 0; x < h.grid_w[g]; ++x) {
+                const uint32_t i = static_cast<uint32_t>(y) * h.grid_w[g] + x;
+                const RdoqBox b = boxes[g][i] = influence_box(s.geo, g, y, x);
+                if (static_cast<uint32_t>(b.bottom - b.top + 1) * static_cast<uint32_t>(b.right - b.left + 1) > kRdoqLaneCells) big[g].push_back(i);
+            }
+        s.n_big[g] = static_cast<uint32_t>(big[g].size());
+        s.box_off[g] = bytes; bytes += up256(s.n[g] * sizeof(RdoqBox));
+        s.big_off[g] = bytes; bytes += up256(big[g].size() * sizeof(uint32_t));
+    }
+    const size_t upload = bytes;
+    for (int g = 0; g < h.n_grids; ++g) {
+        s.moves_off[g] = bytes; bytes += up256(s.n[g]);
+        s.pick_off[g] = bytes; bytes += up256(s.n[g]);
+    }
+    s.raster_off = bytes;
+    const size_t raster_bytes = up256(static_cast<size_t>(s.geo.cells_h) * s.geo.cells_w * sizeof(unsigned long long));
+    s.raster_units = static_cast<uint32_t>(raster_bytes / 16);
+    bytes += raster_bytes;
+    std::vector<char> host(upload, 0);
+    for (int g = 0; g < h.n_grids; ++g) {
+        std::memcpy(host.data() + s.box_off[g], boxes[g].data(), boxes[g].size() * sizeof(RdoqBox));
+        if (!big[g].empty()) std::memcpy(host.data() + s.big_off[g], big[g].data(), big[g].size() * sizeof(uint32_t));
+    }
+    // ---- the device from here on ----
+    HIP_TRY(hipSetDevice(r->device));
+    if (!s.mem.get(r->device, BlockPool::kDevice, bytes)) return CCD_ERR_NOMEM;
+    if (hipMemcpy(s.mem.p, host.data(), upload, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(s.mem.as<char>() + s.raster_off, 0xff, raster_bytes) != hipSuccess ||  // what the first step's claim needs
+        hipDeviceSynchronize() != hipSuccess) {
+        s.mem.drop();
+        return CCD_ERR_HIP;
+    }
+    r->slots.push_back(std::move(sp));
+    return static_cast<int>(r->slots.size()) - 1;
+}
+
+int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const float* const* dbits) {
+    if (!r || !dd || !dbits || slot < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    RSlot& s = *r->slots[slot];
+    for (int g = 0; g < s.n_grids; ++g)
+        if (!dbits[g]) return CCD_ERR_ARG;
+    for (int g = 0; g < s.n_grids; ++g) { s.dd[g] = dd[g]; s.db[g] = dbits[g]; }
+    s.have_maps = true;
+    return CCD_OK;
+}
+
+int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream) {
+    if (!r || !kD || !kR || !min_gain || !grid_mask) return CCD_ERR_ARG;
+    if (r->pending) return CCD_ERR_ARG;
+    const int n_slots = static_cast<int>(r->slots.size());
+    int n_grids = 0;
+    for (int k = 0; k < n_slots; ++k) {
+        if (!(std::isfinite(kD[k]) && kD[k] >= 0 && std::isfinite(kR[k]) && kR[k] >= 0 && std::isfinite(min_gain[k]) && min_gain[k] >= 0))
+            return CCD_ERR_ARG;
+        if (!r->slots[k]->have_maps) return CCD_ERR_ARG;
+        n_grids += r->slots[k]->n_grids;
+    }
+    if (n_slots == 0) return CCD_OK;
+    // the tables of this step: grids, slots and the three prefix tables, one block, one copy
+    std::vector<RdoqGrid> grids;
+    std::vector<RdoqSlot> slots(n_slots);
+    std::vector<uint32_t> lane_prefix(n_grids + 1, 0), big_prefix(n_grids + 1, 0), chunk_prefix(n_grids + 1, 0);
+    uint64_t lanes = 0, bigs = 0, chunks = 0;
+    for (int k = 0; k < n_slots; ++k) {
+        RSlot& s = *r->slots[k];
+        char* base = s.mem.as<char>();
+        RdoqSlot& S = slots[k];
+        std::memset(&S, 0, sizeof(S));
+        S.raster = reinterpret_cast<unsigned long long*>(base + s.raster_off);
+        S.cells_h = s.geo.cells_h; S.cells_w = s.geo.cells_w;
+        S.kD = s.kD = kD[k]; S.kR = s.kR = kR[k]; S.min_gain = min_gain[k];
+        S.grid_mask = grid_mask[k];
+        S.first_grid = static_cast<int32_t>(grids.size()); S.n_grids = s.n_grids;
+        S.raster_units = s.raster_units;
+        for (int g = 0; g < s.n_grids; ++g) {
+            RdoqGrid G;
+            std::memset(&G, 0, sizeof(G));
+            G.lat = s.lat[g]; G.dd = s.dd[g]; G.db = s.db[g];
+            G.moves = reinterpret_cast<int8_t*>(base + s.moves_off[g]);
+            G.pick = reinterpret_cast<uint8_t*>(base + s.pick_off[g]);
+            G.box = reinterpret_cast<const RdoqBox*>(base + s.box_off[g]);
+            G.big = reinterpret_cast<const uint32_t*>(base + s.big_off[g]);
+            G.n = s.n[g]; G.first = s.first[g]; G.slot = k; G.grid = g;
+            lanes += (G.n + 63) / 64; bigs += s.n_big[g]; chunks += (G.n + kRdoqChunk - 1) / kRdoqChunk;
+            if (lanes + bigs > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+            const size_t e = grids.size();
+            lane_prefix[e + 1] = static_cast<uint32_t>(lanes); big_prefix[e + 1] = static_cast<uint32_t>(bigs);
+            chunk_prefix[e + 1] = static_cast<uint32_t>(chunks);
+            grids.push_back(G);
+        }
+    }
+    std::vector<char> buf;
+    auto put = [&buf](const void* p, size_t bytes) {
+        const size_t at = up256(buf.size());
+        buf.resize(at + bytes);
+        if (bytes) std::memcpy(buf.data() + at, p, bytes);
+        return at;
+    };
+    const size_t o_grids = put(grids.data(), grids.size() * sizeof(RdoqGrid)), o_slots = put(slots.data(), slots.size() * sizeof(RdoqSlot));
+    const size_t o_lane = put(lane_prefix.data(), lane_prefix.size() * 4), o_big = put(big_prefix.data(), big_prefix.size() * 4);
+    const size_t o_chunk = put(chunk_prefix.data(), chunk_prefix.size() * 4);
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (std::find(r->streams.begin(), r->streams.end(), st) == r->streams.end()) r->streams.push_back(st);
+    // nothing of an earlier step is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
+    const size_t res_bytes = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
+    if ((r->tables.cls < buf.size() && !r->tables.get(r->device, BlockPool::kDevice, buf.size())) ||
+        (r->tables_host.cls < buf.size() && !r->tables_host.get(r->device, BlockPool::kPinned, buf.size())) ||
+        (r->partial.cls < chunks * sizeof(RdoqPartial) && !r->partial.get(r->device, BlockPool::kDevice, chunks * sizeof(RdoqPartial))) ||
+        (r->results.cls < res_bytes && !r->results.get(r->device, BlockPool::kDevice, res_bytes)) ||
+        (r->results_host.cls < res_bytes && !r->results_host.get(r->device, BlockPool::kPinned, res_bytes)))
+        return CCD_ERR_NOMEM;
+    std::memcpy(r->tables_host.p, buf.data(), buf.size());
+    const char* base = r->tables.as<char>();
+    const bool ok =
+        hipMemcpyAsync(r->tables.p, r->tables_host.p, buf.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+        launch_rdoq_step(reinterpret_cast<const RdoqGrid*>(base + o_grids), reinterpret_cast<const RdoqSlot*>(base + o_slots),
+                         reinterpret_cast<const uint32_t*>(base + o_lane), reinterpret_cast<const uint32_t*>(base + o_big),
+                         reinterpret_cast<const uint32_t*>(base + o_chunk), n_grids, n_slots, static_cast<uint32_t>(lanes),
+                         static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks), r->partial.as<RdoqPartial>(),
+                         r->results.as<ccd_rdoq_result>(), st) == hipSuccess &&
+        hipMemcpyAsync(r->results_host.p, r->results.p, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (!ok) {  // part of the step may have been enqueued: drain it; no slot has a result, no step is in flight
+        (void)hipStreamSynchronize(st);
+        for (auto& s : r->slots) s->covered = false;
+        return CCD_ERR_HIP;
+    }
+    r->pending = 1;  // everything is enqueued
+    r->n_stepped = n_slots;
+    r->step_stream = st;
+    return CCD_OK;
+}
+
+int ccd_rdoq_wait(ccd_rdoq* r, void* stream) {
+    if (!r) return CCD_ERR_ARG;
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    if (!r->pending) return CCD_OK;
+    // the results are behind the step on the stream the step was given, whichever stream this call names
+    if (r->step_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(r->step_stream));
+    r->pending = 0;
+    const ccd_rdoq_result* res = r->results_host.as<ccd_rdoq_result>();
+    for (int k = 0; k < r->n_stepped; ++k) {
+        RSlot& s = *r->slots[k];
+        s.result = res[k];
+        s.result.d_cost = s.kD * static_cast<double>(s.result.d_sse) + s.kR * s.result.d_bits;
+        s.covered = true;
+    }
+    return CCD_OK;
+}
+
+int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out) {
+    if (!r || !out || slot < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
+    *out = r->slots[slot]->result;
+    return CCD_OK;
+}
+
+int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {
+    if (!r || !dev_ptr || slot < 0 || grid < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    const RSlot& s = *r->slots[slot];
+    if (grid >= s.n_grids || !s.covered) return CCD_ERR_ARG;
+    *dev_ptr = s.mem.as<char>() + s.moves_off[grid];
+    return static_cast<int64_t>(s.n[grid]);
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@ cost is computed on the host in float64 from the device's exact integer squared 
 
 Intra frames only: one cool-chic per frame.  P / B frames (two cool-chics and a reconstruction) are not evaluated here;
 ccd_batch_add_latents itself takes any cool-chic."""
-from typing import List, NamedTuple, Sequence, Union
+from typing import List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -30,6 +30,7 @@ from .dsens import SENTINEL, DistortionDeltas
 from .encoder import EncodeBatch, SlotRate
 from .io import FrameData
 from .quality import FrameQuality, QualityMeter, _frame_planes
+from .rdoq import RdoqStep, StepResult
 
 
 class Candidate(NamedTuple):
@@ -38,6 +39,12 @@ class Candidate(NamedTuple):
     mse: float
     bits: float
     cost: float
+
+
+class StepReport(NamedTuple):
+    """One candidate in one step of RdEvaluator.descend: what it was before the step, and what the step did to it."""
+    before: Candidate
+    step: StepResult
 
 
 def rd_cost(sse: Sequence[int], n: Sequence[int], bitdepth: int, total_bits: float, n_bytes_nn: int, n_bytes_header: int,
@@ -59,6 +66,8 @@ class RdEvaluator:
         self._n_probe_slots = int(n_probe_slots)
         self._dd = None             # DistortionDeltas over the candidates, made when first asked for
         self._jobs: List[tuple] = []  # (arch, bytes_nn) per candidate, for it
+        self._rdoq = None           # RdoqStep over the candidates, made by the first descend()
+        self._caller_ptrs: List[Optional[List[int]]] = []  # the caller's device latents per candidate; None: host arrays
         self._dec = DecodeBatch(self.device)
         self._enc = EncodeBatch(self.device)
         self._meter = QualityMeter(self.device)
@@ -66,6 +75,9 @@ class RdEvaluator:
         self._frames: List[FrameData] = []
 
     def close(self):
+        if self._rdoq is not None:
+            self._rdoq.close()
+            self._rdoq = None
         if self._dd is not None:
             self._dd.close()
             self._dd = None
@@ -88,7 +100,8 @@ class RdEvaluator:
         if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
             raise ValueError(f"cannot score a {source.frame_data_type} frame")
         fdt = FRAME_DATA_TYPES.index(source.frame_data_type)
-        if all(isinstance(x, (int, np.integer)) for x in latents_or_ptrs):
+        on_device = all(isinstance(x, (int, np.integer)) for x in latents_or_ptrs)
+        if on_device:
             slot = self._dec.add_latents_device(arch, bytes_nn, latents_or_ptrs, source.bitdepth, fdt, owner=owner)
         else:
             slot = self._dec.add_latents(arch, bytes_nn, latents_or_ptrs, source.bitdepth, fdt)
@@ -100,6 +113,7 @@ class RdEvaluator:
         self._sources.append(_frame_planes(source, torch.device(f"cuda:{self.device}")))
         self._frames.append(source)
         self._jobs.append((arch, bytes_nn))
+        self._caller_ptrs.append([int(p) for p in latents_or_ptrs] if on_device else None)
         return slot
 
     def evaluate(self, lmbda: float, ms_ssim: bool = False, rate_deltas: bool = False, distortion_deltas: bool = False) -> List[Candidate]:
@@ -163,3 +177,59 @@ class RdEvaluator:
         db = torch.as_tensor(self.rate_delta_map(slot, grid), device=dev).to(torch.float64)
         cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(f.n_pixels)
         return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)
+
+    def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids: Optional[Sequence[int]] = None) -> List[List[StepReport]]:
+        """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True), then
+        one RdoqStep over the evaluator's own device maps that moves latents of the candidates IN PLACE by +-1 where that lowers
+        the cost by more than `min_gain` and the moves do not interact.  `grids`: the grids that may move (all by default).
+        With every grid admitted a step of a real picture is usually ONE move: a candidate of the coarsest grids reaches the
+        whole picture, is worth thousands of squared-error units and so beats and blocks everything else.  Pass the fine grids
+        (for instance grids=(0, 1, 2)) for steps of hundreds of moves, and admit the coarse ones in a later call.
+        Stops when no candidate moved or after `max_steps` steps; returns one list of StepReport per step (one per candidate:
+        the candidate before the step, and what the step did).  After a step the cost of candidate s is before.cost + step.d_cost
+        (its distortion part exactly, its rate part within the rate deltas' bound).
+
+        Every candidate must have been added with DEVICE latents: they are the caller's memory, changed in place and seen by the
+        next evaluate().  A candidate added from host arrays raises ValueError before anything runs."""
+        n = len(self._frames)
+        for s, ptrs in enumerate(self._caller_ptrs):
+            if ptrs is None:
+                raise ValueError(f"candidate {s} was added from host arrays: descend() moves device latents the caller owns")
+        if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
+            raise ValueError("lmbda and min_gain must be finite and not negative")
+        if n == 0:
+            return []
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        if self._rdoq is None:
+            self._rdoq = RdoqStep(self.device)
+        for s in range(len(self._rdoq), n):
+            f = self._frames[s]
+            self._rdoq.add(self._jobs[s][0], FRAME_DATA_TYPES.index(f.frame_data_type), self._caller_ptrs[s])
+        kD, kR, masks = [], [], []
+        for s, f in enumerate(self._frames):
+            n_samples = sum(int(t.numel()) for t in self._sources[s])
+            maxv = float(2 ** f.bitdepth - 1)
+            kD.append(1.0 / (float(n_samples) * maxv * maxv))
+            kR.append(float(lmbda) / float(f.n_pixels))
+            n_grids = int(self._jobs[s][0].n_grids)
+            masks.append(sum(1 << g for g in (range(n_grids) if grids is None else grids) if 0 <= g < n_grids))
+        reports: List[List[StepReport]] = []
+        for _ in range(int(max_steps)):
+            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True)
+            for s in range(n):  # the maps' addresses are those of this evaluate()
+                n_grids = int(self._jobs[s][0].n_grids)
+                self._rdoq.set_maps(s, [self._dd.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
+                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
+            self._rdoq.step(kD, kR, [float(min_gain)] * n, masks, st)
+            self._rdoq.wait(st)
+            results = [self._rdoq.result(s) for s in range(n)]
+            reports.append([StepReport(b, r) for b, r in zip(before, results)])
+            if not any(r.n_moves for r in results):
+                break
+        return reports
+
+    def step_moves(self, slot: int, grid: int):
+        """After descend(): the last step's move (-1, 0, +1) at every latent of the grid (device, int8 [h][w])."""
+        if self._rdoq is None:
+            raise RuntimeError("no descend() has run")
+        return self._rdoq.moves(slot, grid)

@@ -550,6 +550,55 @@ int ccd_dsens_wait(ccd_dsens* d, void* stream);
 int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr);
 int ccd_dsens_passes(const ccd_dsens* d, int slot);
 
+/* ---- One RDOQ step: choose and apply +-1 moves that do not interact (ccd_rdoq.hip, ccd_rdoq_api.cpp) ----
+ * From the two delta maps of every grid - the distortion deltas of ccd_dsens_slot_map and the rate deltas of
+ * ccd_enc_slot_delta_map, or any maps of those shapes - a step picks on the device a set of moves whose deltas add, and applies
+ * them to the caller's device latents in place.
+ * Two moves are independent when neither a symbol of the rate model reads both latents (p itself, its spatial dependents and
+ * the IFCE blocks of the finer grids: DESIGN.md 4.10 "Rate sensitivity") nor a sample of the planes is reached by both
+ * (ccd_latent_footprint, 4:2:0 chroma included).  The step tests a superset of that relation: the INFLUENCE BOX of a latent is
+ * the bounding rectangle, in luma samples, of its clipped footprint and of area(r) for every symbol r of its rate set, where
+ * area(g, qy, qx) = rows floor((qy << level[g]) H / h0) .. ceil(min((qy + 1) << level[g], h0) H / h0) - 1 (columns alike; h0 x w0
+ * is grid 0, level[g] the number of size changes between grid 0 and grid g), expressed in cells of ccd_rdoq_cell() x
+ * ccd_rdoq_cell() luma samples.  Latents whose boxes share no cell are independent.
+ * ccd_rdoq_influence_box (host only): cells = {top, left, bottom, right}, inclusive, of the latent (y, x) of `grid`.  CCD_ERR_ARG
+ * for NULL, a bad grid or position or a frame_data_type other than 0, 1, 2; CCD_ERR_VALUE for an `arch` that does not re-parse.
+ * ccd_rdoq_add: latents[g] = DEVICE int8 [grid_h[g]][grid_w[g]], READ AND WRITTEN by every step; returns the slot.  CCD_ERR_ARG -
+ * before the handle or the device is looked at - for a NULL argument or a frame_data_type other than 0, 1, 2; for a step in flight.
+ * ccd_rdoq_set_maps: dd[g] = device int64 [2][h][w] (plane 0: the change of the squared error for v - 1, plane 1 for v + 1;
+ * INT64_MIN: no such move; a NULL dd[g] stands for zeros, as a hyperlatent grid's map is), dbits[g] = device float32 [2][h][w]
+ * (a non-finite entry: no such move).  Read by every later step.
+ * ccd_rdoq_step: per-slot arrays.  The cost of a move is c = dD * kD + dBits * kR in float64 (two products, one sum, each
+ * rounded once); a latent's better move (-1 on a tie of the costs as float32) is a candidate when its grid's bit of grid_mask is
+ * set, the latent as it is now plus the move stays in [-64, 63] and c < -min_gain.  Candidates are ordered by the key
+ * (cost as float32, then slot-wide index first[g] + y w + x); a candidate is selected when it has the smallest key of all
+ * candidates whose boxes share a cell with its own, and the candidate with the slot's smallest key always is.  Selected latents
+ * are stored as v + s.  Negative or non-finite kD, kR, min_gain, NULL arrays, a slot without maps and a step in flight are
+ * CCD_ERR_ARG.  The call only enqueues; ccd_rdoq_wait synchronises.  One step may be in flight per handle.
+ * ccd_rdoq_slot_result: what the last finished step did; d_bits is a float64 sum in an order that depends on the geometry only
+ * (the same words on a second call), d_cost = kD * d_sse + kR * d_bits.  ccd_rdoq_slot_moves: device int8 [h][w], the step's
+ * move (-1, 0, +1) at every latent, and h * w as the return value; valid until the next step / destroy.  Both CCD_ERR_ARG for a
+ * NULL argument, a bad slot or grid, a slot no finished step covered. */
+typedef struct ccd_rdoq ccd_rdoq;
+typedef struct {
+    int32_t status, n_grids;
+    int64_t n_candidates, n_moves;
+    int64_t n_moves_grid[CCD_MAX_GRIDS];
+    int64_t d_sse;      /* exact: sum of the chosen dD */
+    double d_bits;      /* sum of the chosen dBits */
+    double d_cost;
+} ccd_rdoq_result;
+int ccd_rdoq_cell(void);
+int ccd_rdoq_influence_box(const ccd_cc_header* arch, int frame_data_type, int grid, int y, int x, int32_t cells[4]);
+int ccd_rdoq_create(int device, ccd_rdoq** out);
+void ccd_rdoq_destroy(ccd_rdoq* r);
+int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, int8_t* const* latents);
+int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const float* const* dbits);
+int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream);
+int ccd_rdoq_wait(ccd_rdoq* r, void* stream);
+int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out);
+int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr);
+
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):
  * left[i], right[i] as the entropy kernel sees them (exhaustive parity tests of the f64 CDF). */
 int ccd_debug_laplace_bounds(int device, const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* s,

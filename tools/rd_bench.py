@@ -8,6 +8,10 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
   --ddeltas         instead of the above: the distortion deltas (DistortionDeltas) of the same sets -
                     passes of the float path per run, run + wait, the time per pass next to given_float_ms
 
+  --rdoq            instead of the above: one requantisation step (RdoqStep) next to the
+                    evaluate(rate_deltas, distortion_deltas) that feeds it, candidates and moves per step for three grid
+                    masks, and for kodim14 the cost after 1, 2, 4, 8 steps of RdEvaluator.descend
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -150,14 +154,107 @@ def measure_ddeltas(streams, runs, n_probe_slots):
     return res
 
 
+def measure_rdoq(streams, runs, lmbda, trajectory):
+    """The streams' own latents with a seeded tenth of the positions moved by +-1, scored against the frames the own latents
+    decode to: the time of evaluate(rate_deltas, distortion_deltas), of one step over its maps (latents restored before every
+    step, outside the timed region), candidates and moves for three masks, and the cost along a descent."""
+    import numpy as np
+
+    from cool_chic_amd import RdoqStep
+
+    st = torch.cuda.current_stream().cuda_stream
+    n = len(streams)
+    dec = DecodeBatch(0)
+    for bs in streams:
+        dec.add(*synth.split_image_stream(bs), 8, 0)
+    dec.run(st)
+    dec.wait(st)
+    sources = [_planes_to_frame_data(dec.planes(s), 8, "rgb") for s in range(n)]
+    rng = np.random.default_rng(14)
+    start, work = [], []
+    ev = RdEvaluator(0)
+    for s in range(n):
+        h = dec.header(s)
+        grids = []
+        for g in range(h.n_grids):
+            a = dec.latent(s, g).astype(np.int64)
+            a = a + np.where(rng.random(a.shape) < 0.1, rng.choice([-1, 1], size=a.shape), 0)
+            grids.append(torch.from_numpy(np.clip(a, -64, 63).astype(np.int8)).cuda())
+        start.append(grids)
+        work.append([t.clone() for t in grids])
+        ev.add(h, dec.network_bytes(s), [t.data_ptr() for t in work[s]], sources[s], owner=work[s])
+    n_grids = [dec.header(s).n_grids for s in range(n)]
+
+    def restore():
+        for a, b in zip(work, start):
+            for t, u in zip(a, b):
+                t.copy_(u)
+
+    out = []
+
+    def evaluate_step():
+        out[:] = ev.evaluate(lmbda, rate_deltas=True, distortion_deltas=True)
+
+    res = {"streams": n, "symbols": int(sum(dec.header(s).n_symbols for s in range(n))), "lmbda": lmbda}
+    res["evaluate_deltas_ms"] = round(event_ms(evaluate_step, runs), 3)
+    res["cost_before"] = [c.cost for c in out][:2]
+    step = RdoqStep(0)
+    kD, kR = [], []
+    for s in range(n):
+        step.add(dec.header(s), 0, [t.data_ptr() for t in work[s]], owner=work[s])
+        step.set_maps(s, [ev.distortion_delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids[s])],
+                      [ev.rate_delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids[s])], owner=ev)
+        kD.append(1.0 / (3.0 * sources[s].n_pixels * 255.0 * 255.0))
+        kR.append(lmbda / sources[s].n_pixels)
+    for label, mask_of in (("all_grids", lambda k: (1 << k) - 1), ("grids_0_2", lambda k: 7), ("grid_0", lambda k: 1)):
+        masks = [mask_of(k) for k in n_grids]
+        times = []
+        for it in range(3 + runs):
+            restore()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step.step(kD, kR, [0.0] * n, masks, st)
+            e1.record()
+            step.wait(st)
+            if it >= 3:
+                times.append(e0.elapsed_time(e1))
+        results = [step.result(s) for s in range(n)]
+        res[label] = {"step_ms": round(statistics.median(times), 4), "candidates": sum(r.n_candidates for r in results),
+                      "moves": sum(r.n_moves for r in results), "d_cost_slot0": results[0].d_cost}
+    step.close()
+    if trajectory:
+        restore()
+        torch.cuda.synchronize()
+        reports = ev.descend(lmbda, max_steps=8, grids=(0, 1, 2))  # coarse candidates own the raster: one move per step
+        costs = [rep[0].before.cost for rep in reports] + [ev.evaluate(lmbda)[0].cost]
+        res["descent_grids_0_2"] = {"cost_after_steps": {str(k): costs[k] for k in (0, 1, 2, 4, 8) if k < len(costs)},
+                          "moves_per_step": [rep[0].step.n_moves for rep in reports],
+                          "candidates_per_step": [rep[0].step.n_candidates for rep in reports],
+                          "bits": [reports[0][0].before.bits, ev.evaluate(lmbda)[0].bits]}
+    ev.close()
+    dec.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
     ap.add_argument("--no-replaced", action="store_true", help="skip the replaced route (profiling runs)")
     ap.add_argument("--ddeltas", action="store_true", help="time the distortion deltas instead")
     ap.add_argument("--probe-slots", type=int, default=16)
+    ap.add_argument("--rdoq", action="store_true", help="time one requantisation step and the evaluation that feeds it instead")
+    ap.add_argument("--lmbda", type=float, default=1e-3)
+    ap.add_argument("--sets", default="kodim14,kodak24", help="with --rdoq: which of the two sets to measure")
     a = ap.parse_args()
     k24 = synth.workload("kodak24")["streams"]
+    if a.rdoq:
+        line = {"tool": "rd_bench --rdoq", "runs": a.runs}
+        if "kodim14" in a.sets.split(","):
+            line["kodim14"] = measure_rdoq(k24[:1], a.runs, a.lmbda, True)
+        if "kodak24" in a.sets.split(","):
+            line["kodak24"] = measure_rdoq(k24, a.runs, a.lmbda, False)
+        print(json.dumps(line))
+        return
     if a.ddeltas:
         print(json.dumps({"tool": "rd_bench --ddeltas", "runs": a.runs, "kodim14": measure_ddeltas(k24[:1], a.runs, a.probe_slots),
                           "kodak24": measure_ddeltas(k24, a.runs, a.probe_slots)}))
