@@ -5,27 +5,20 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._handle import _DevArray, _Handle, ptr_array
 from ._lib import CCHeader, check, lib
 
 FRAME_DATA_TYPES = ["rgb", "yuv420", "yuv444", "flow"]
 
 
-class _DevArray:
-    """Zero-copy view of library-owned device memory for torch.as_tensor(..., device='cuda')."""
-
-    def __init__(self, ptr: int, shape: Tuple[int, ...], typestr: str, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-        self._owner = owner  # keeps the batch (and its arena) alive
-
-
-class DecodeBatch:
+class DecodeBatch(_Handle):
     """One slot per cool-chic; all slots decode concurrently in run().
 
     Inputs (latent payload words, network parameters) are uploaded to HBM by add(); run() only
     enqueues kernels on `stream` (a hipStream_t handle, e.g. torch.cuda.current_stream().cuda_stream).
     """
 
+    _destroy = "ccd_batch_destroy"
     OPT_FUSED_DEC, OPT_KEEP_FLOAT, OPT_MFMA_ARM, OPT_RANGE_BITS, OPT_OVERLAP, OPT_TIME_LAUNCHES = 1, 2, 3, 4, 5, 6  # include/ccd.h
 
     def __init__(self, device: int = 0, fused_dec: Optional[bool] = None, keep_float: Optional[bool] = None,
@@ -38,9 +31,7 @@ class DecodeBatch:
         frames whose streams finish early are synthesised while the longest chains still decode (ccd.h, ccd_batch_run).
         None = library default: fused_dec on, keep_float on, mfma_arm OFF (the vector-ALU ARM is the faster one),
         production limit (15 bits), overlap on."""
-        self._h = C.c_void_p()
-        check(lib().ccd_batch_create(int(device), C.byref(self._h)), "ccd_batch_create")
-        self.device = int(device)
+        self._open("ccd_batch_create", device)
         if fused_dec is not None:
             # False / True, or 2: the fused kernel behind the batch's pyramid steps (level-1 stack pre-computed once per frame)
             # True = "the fused float path" = the library's default form of it (2); 0 / 1 / 2 select a form explicitly (ccd.h)
@@ -55,19 +46,6 @@ class DecodeBatch:
             check(lib().ccd_batch_set_option(self._h, self.OPT_OVERLAP, int(bool(overlap))), "ccd_batch_set_option")
         self._meta: List[Tuple[int, int]] = []
         self._nn: List[bytes] = []
-        self._owners: List[object] = []  # whatever holds the device latents that given slots read at every run()
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_batch_destroy(self._h)
-            self._h = C.c_void_p()
-            self._owners = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return len(self._meta)
@@ -81,7 +59,7 @@ class DecodeBatch:
         return slot
 
     def _add_given(self, arch: CCHeader, bytes_nn: bytes, ptrs: Sequence[int], on_device: int, bitdepth: int, frame_data_type: int) -> int:
-        arr = (C.c_void_p * len(ptrs))(*[int(p) for p in ptrs])
+        arr = ptr_array(ptrs)
         slot = check(lib().ccd_batch_add_latents(self._h, C.byref(arch), bytes_nn, len(bytes_nn), arr, on_device, int(bitdepth),
                                                  int(frame_data_type)), "ccd_batch_add_latents")
         self._meta.append((int(bitdepth), int(frame_data_type)))
@@ -100,8 +78,7 @@ class DecodeBatch:
         """Latents that already sit on the device (int8 [h][w] per grid).  They are read at EVERY run(): change them in place,
         run again, and the planes follow.  `owner` is kept alive with this batch."""
         slot = self._add_given(arch, bytes_nn, latent_ptrs, 1, bitdepth, frame_data_type)
-        if owner is not None:
-            self._owners.append(owner)
+        self._keep(owner)  # (the device latents that the slot reads at every run())
         return slot
 
     def add_latents_from(self, batch: "DecodeBatch", slot: int, arch: Optional[CCHeader] = None, bytes_nn: Optional[bytes] = None,

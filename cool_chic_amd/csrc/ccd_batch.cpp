@@ -8,9 +8,8 @@
 
 using namespace ccd;
 
-int ccd_batch::drain_streams() {
-    int rc = CCD_OK;
-    for (hipStream_t st : streams_used) if (hipStreamSynchronize(st) != hipSuccess) rc = CCD_ERR_HIP;
+int ccd_batch::drain() {
+    int rc = streams.drain();
     // the device's SHARED side streams are not drained (another batch in flight may be launching on them: draining would
     // make this batch's destroy wait for that batch's entropy chains) - this batch's own work on them ends at its events
     for (int k = 0; k < DeviceShared::kSide; ++k)
@@ -52,7 +51,7 @@ void ccd_batch_destroy(ccd_batch* b) {
     (void)hipSetDevice(b->device);
     // blocks go back to the pool for the next batch: nothing of this one may still be in flight
     if (b->up_done) { (void)hipEventSynchronize(b->up_done); (void)hipEventDestroy(b->up_done); }
-    (void)b->drain_streams();  // launches and copies on EVERY stream the caller used with this batch
+    (void)b->drain();  // launches and copies on EVERY stream the caller used with this batch
     if (b->fork) (void)hipEventDestroy(b->fork);
     if (b->params_up) (void)hipEventDestroy(b->params_up);
     for (hipEvent_t e : b->lg_done) if (e) (void)hipEventDestroy(e);
@@ -282,7 +281,7 @@ static int launch_float_stage(ccd_batch* b, hipStream_t st, int stage, bool keye
 static int run_prologue(ccd_batch* b, hipStream_t st) {
     HIP_TRY(hipSetDevice(b->device));
     if (b->uploads_unconfirmed) HIP_TRY(hipStreamWaitEvent(st, b->up_done, 0));  // the slots' uploads (ccd_batch_add) come first
-    b->note_stream(st);
+    b->streams.note(st);
     const int rc = build_launch_tables(b, st);
     if (rc < 0) return rc;
     if (b->params_up && b->params_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->params_up, 0));
@@ -317,7 +316,7 @@ int ccd_batch_prepare(ccd_batch* b, void* stream) {
     if (!b) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    b->note_stream(st);
+    b->streams.note(st);
     return build_launch_tables(b, st);
 }
 
@@ -345,7 +344,7 @@ int ccd_batch_wait(ccd_batch* b, void* stream) {
     if (!b) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    b->note_stream(st);
+    b->streams.note(st);
     // slots added after the last run have no status yet: the words of the slots that DID run are refreshed all the same (their
     // array and its pinned copy were sized for them)
     const size_t n = std::min(b->slots.size(), static_cast<size_t>(b->n_params_uploaded));
@@ -459,7 +458,7 @@ static int copy_out(ccd_batch* b, const void* src, void* dst, size_t bytes, void
     if (!src || !dst) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    b->note_stream(st);
+    b->streams.note(st);
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return CCD_OK;
@@ -492,7 +491,7 @@ int ccd_batch_copy_planes_async(ccd_batch* b, int first_slot, int n_slots, void*
     if (!b || !host_blocks || first_slot < 0 || n_slots < 0 || first_slot + n_slots > static_cast<int>(b->slots.size())) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    b->note_stream(st);  // the copies read the arenas: drained before the blocks are recycled (ccd_batch_destroy)
+    b->streams.note(st);  // the copies read the arenas: drained before the blocks are recycled (ccd_batch_destroy)
     int rc = CCD_OK;
     for (int i = 0; i < n_slots; ++i) {
         const Slot& s = *b->slots[first_slot + i];

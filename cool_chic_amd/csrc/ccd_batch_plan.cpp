@@ -360,7 +360,7 @@ void layout_arena(const ccd_batch* b, Slot& s, SlotPlan& p) {
             s.plane_h[pl] = chroma420 ? H / 2 : H;
             s.plane_w[pl] = chroma420 ? W / 2 : W;
             s.plane_off[pl] = off;
-            off += (static_cast<size_t>(s.plane_h[pl]) * s.plane_w[pl] * sample_bytes + 16 + 255) & ~size_t{255};
+            off += align256(static_cast<size_t>(s.plane_h[pl]) * s.plane_w[pl] * sample_bytes + 16);
         }
         s.planes_bytes = off;
         at.planes = A.reserve(off);
@@ -552,16 +552,9 @@ extern "C" int ccd_batch_add_latents(ccd_batch* b, const ccd_cc_header* arch, co
     if (!sp) return CCD_ERR_NOMEM;
     Slot& s = *sp;
     // ---- everything the host can refuse, before the device is touched ----
-    uint8_t hb[256];
-    int n_hb = -1;
-    {   // the header a coded slot would have brought: the transmitted fields, serialised (like ccd_enc_add) with an empty payload
-        ccd_cc_header t = *arch;
-        t.nn_n_bytes = static_cast<int32_t>(n_nn);
-        t.n_bytes_latent = 0;
-        if (t.n_layer_synthesis >= 0 && t.n_layer_synthesis <= CCD_MAX_SYN_LAYERS) n_hb = ccd_write_cc_header(&t, hb, sizeof(hb));
-        if (n_hb < 0) return CCD_ERR_VALUE;
-    }
-    const int rc = parse_slot(s, hb, static_cast<size_t>(n_hb), bytes_nn, n_nn, 0, bitdepth, frame_data_type);
+    std::vector<uint8_t> hb;  // the header a coded slot would have brought: the transmitted fields, serialised with an empty payload
+    int rc = rederive_cc_header(*arch, n_nn, &s.hdr, &hb);
+    if (rc >= 0) rc = parse_slot(s, hb.data(), hb.size(), bytes_nn, n_nn, 0, bitdepth, frame_data_type);
     if (rc < 0) return rc;
     const ccd_cc_header& h = s.hdr;
     if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;  // (a segment's length is 32 bits)
@@ -884,22 +877,21 @@ int plan_ups_steps(ccd_batch* b, LaunchTables& t) {
 // ---- one pooled device block for every table and the status words of all slots, filled by ONE copy from ONE pinned block
 int pack_and_upload(ccd_batch* b, LaunchTables& t, hipStream_t st) {
     const int n = static_cast<int>(b->slots.size());
-    auto up256 = [](size_t v) { return (v + 255) & ~size_t{255}; };
     const size_t o_params = 0;
-    const size_t o_fusedt = o_params + up256(sizeof(EntropyParams) * std::max(n, 1));
-    const size_t o_fdec = o_fusedt + up256(sizeof(SynthFused) * std::max<size_t>(t.fused.size(), 1));
-    const size_t o_work = o_fdec + up256(sizeof(FusedDec) * std::max<size_t>(t.frames.size(), 1));
-    const size_t o_levels = o_work + up256(sizeof(Work) * std::max<size_t>(t.work.size(), 1));
-    const size_t o_zmap = o_levels + up256(sizeof(UpsampleLevel) * std::max<size_t>(t.levels.size(), 1));
-    const size_t o_pyr = o_zmap + up256(sizeof(uint32_t) * std::max<size_t>(t.zmap.size(), 1));
-    const size_t o_pyrw = o_pyr + up256(sizeof(FusedDec) * std::max<size_t>(t.pyr_frames.size(), 1));
-    const size_t o_stat = o_pyrw + up256(sizeof(Work) * std::max<size_t>(t.pyr_work.size(), 1));
+    const size_t o_fusedt = o_params + align256(sizeof(EntropyParams) * std::max(n, 1));
+    const size_t o_fdec = o_fusedt + align256(sizeof(SynthFused) * std::max<size_t>(t.fused.size(), 1));
+    const size_t o_work = o_fdec + align256(sizeof(FusedDec) * std::max<size_t>(t.frames.size(), 1));
+    const size_t o_levels = o_work + align256(sizeof(Work) * std::max<size_t>(t.work.size(), 1));
+    const size_t o_zmap = o_levels + align256(sizeof(UpsampleLevel) * std::max<size_t>(t.levels.size(), 1));
+    const size_t o_pyr = o_zmap + align256(sizeof(uint32_t) * std::max<size_t>(t.zmap.size(), 1));
+    const size_t o_pyrw = o_pyr + align256(sizeof(FusedDec) * std::max<size_t>(t.pyr_frames.size(), 1));
+    const size_t o_stat = o_pyrw + align256(sizeof(Work) * std::max<size_t>(t.pyr_work.size(), 1));
     // (the ingest tables come last and only exist with device-latent slots: every other batch keeps the layout it had)
-    const size_t o_ingest = o_stat + up256(static_cast<size_t>(std::max(n, 1)) * 64 * sizeof(int32_t));
-    const size_t o_ingestp = o_ingest + (t.ingest.empty() ? 0 : up256(sizeof(IngestSeg) * t.ingest.size()));
-    const size_t total = o_ingestp + (t.ingest.empty() ? 0 : up256(sizeof(uint32_t) * t.ingest_prefix.size()));
+    const size_t o_ingest = o_stat + align256(static_cast<size_t>(std::max(n, 1)) * 64 * sizeof(int32_t));
+    const size_t o_ingestp = o_ingest + (t.ingest.empty() ? 0 : align256(sizeof(IngestSeg) * t.ingest.size()));
+    const size_t total = o_ingestp + (t.ingest.empty() ? 0 : align256(sizeof(uint32_t) * t.ingest_prefix.size()));
     // the previous tables may still be read by launches in flight on the caller's stream (a batch that grew between runs)
-    if (b->tables.p && b->drain_streams() < 0) return CCD_ERR_HIP;
+    if (b->tables.p && b->drain() < 0) return CCD_ERR_HIP;
     if (!b->tables.get(b->device, BlockPool::kDevice, total) || !b->tables_staging.get(b->device, BlockPool::kPinned, total) ||
         !b->status_host.get(b->device, BlockPool::kPinned, static_cast<size_t>(std::max(n, 1)) * 64 * sizeof(int32_t)))
         return CCD_ERR_NOMEM;

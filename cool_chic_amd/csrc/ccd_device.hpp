@@ -1,5 +1,6 @@
 // ccd_device.hpp - structures shared between the host API and the HIP kernels.
 #pragma once
+#include <hip/hip_runtime.h>
 
 #include <cstdint>
 
@@ -14,6 +15,17 @@ constexpr int kRcPrecision = 24;     // constriction default range-coder precisi
 constexpr int kMuOffset = 16384;     // -MU_MIN_FIXED_POINT (constants.py:31)
 constexpr int kScaleOffset = 1280;   // -LOG_SCALE_MIN_FIXED_POINT (constants.py:36)
 constexpr int kNumMu = 32768, kNumScale = 2561;
+
+// Which entry owns work item i of a launch over n entries (ingest segments, passes, planes, grids): the entry s with
+// prefix[s] <= i < prefix[s + 1] (entries without work have prefix[s] == prefix[s + 1]).
+__device__ __forceinline__ int entry_of(const uint32_t* prefix, int n, uint32_t i) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid + 1] <= i) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 
 // Per-slot description of the entropy stage (device memory, read-only for the kernel).
 struct EntropyParams {

@@ -14,18 +14,6 @@ int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 }  // namespace
 
 namespace ccd {
-// The transmitted fields of `arch` with the geometry they imply (what ccd_batch_add_latents does with them).
-int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out) {
-    uint8_t hb[256];
-    ccd_cc_header t = *arch;
-    t.nn_n_bytes = static_cast<int32_t>(n_nn);
-    t.n_bytes_latent = 0;
-    if (t.n_layer_synthesis < 0 || t.n_layer_synthesis > CCD_MAX_SYN_LAYERS) return CCD_ERR_VALUE;
-    const int n_hb = ccd_write_cc_header(&t, hb, sizeof(hb));
-    if (n_hb < 0 || ccd_read_cc_header(hb, static_cast<size_t>(n_hb), out) < 0) return CCD_ERR_VALUE;
-    return CCD_OK;
-}
-
 // Where a move of one latent of `grid` can reach (supports only).  Per axis a (0 rows, 1 columns): the samples
 // [s + lo[a], s + hi[a]] with s = floor(i * num[a] / den[a]) for the latent index i.  Returns 1 for a hyperlatent grid.
 int footprint(const ccd_cc_header& h, int grid, Footprint& f) {
@@ -130,11 +118,12 @@ struct ccd_dsens {
     ccd_batch* batch = nullptr;
     std::vector<std::unique_ptr<Candidate>> cands;
     std::vector<Round> rounds;
-    Block tables, tables_host, slab;
+    Mirror tables;
+    Block slab;
     bool planned = false;   // the tables describe every candidate
     int pending = 0;        // a run is in flight
     int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
-    std::vector<hipStream_t> streams;
+    StreamSet streams;
 };
 
 namespace {
@@ -179,13 +168,7 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
     const int K = d->K;
     size_t n_rounds = 1;
     for (const auto& c : d->cands) n_rounds = std::max(n_rounds, (c->passes.size() + K - 1) / K);
-    std::vector<char> buf;
-    auto put = [&buf](const void* p, size_t bytes) {
-        const size_t at = (buf.size() + 255) & ~size_t{255};
-        buf.resize(at + bytes);
-        if (bytes) std::memcpy(buf.data() + at, p, bytes);
-        return at;
-    };
+    TableImage img;
     d->rounds.assign(n_rounds, Round{});
     uint32_t max_units = 1;
     for (size_t r = 0; r < n_rounds; ++r) {
@@ -237,19 +220,15 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
         if (blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
         R.n_segs = static_cast<int>(segs.size()); R.n_passes = static_cast<int>(passes.size());
         R.n_blocks = static_cast<uint32_t>(blocks); R.n_units = static_cast<uint32_t>(units); R.n_probes = static_cast<uint32_t>(probes);
-        R.segs = put(segs.data(), segs.size() * sizeof(DsensSeg));
-        R.seg_prefix = put(seg_prefix.data(), seg_prefix.size() * sizeof(uint32_t));
-        R.passes = put(passes.data(), passes.size() * sizeof(DsensPass));
-        R.unit_prefix = put(unit_prefix.data(), unit_prefix.size() * sizeof(uint32_t));
-        R.probe_prefix = put(probe_prefix.data(), probe_prefix.size() * sizeof(uint32_t));
+        R.segs = img.put(segs); R.seg_prefix = img.put(seg_prefix);
+        R.passes = img.put(passes); R.unit_prefix = img.put(unit_prefix); R.probe_prefix = img.put(probe_prefix);
         max_units = std::max(max_units, R.n_units);
     }
     // nothing of an earlier run is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
-    if (d->tables.cls < buf.size() && !d->tables.get(d->device, BlockPool::kDevice, buf.size())) return CCD_ERR_NOMEM;
-    if (d->tables_host.cls < buf.size() && !d->tables_host.get(d->device, BlockPool::kPinned, buf.size())) return CCD_ERR_NOMEM;
-    if (d->slab.cls < max_units * sizeof(int64_t) && !d->slab.get(d->device, BlockPool::kDevice, max_units * sizeof(int64_t))) return CCD_ERR_NOMEM;
-    std::memcpy(d->tables_host.p, buf.data(), buf.size());
-    HIP_TRY(hipMemcpyAsync(d->tables.p, d->tables_host.p, buf.size(), hipMemcpyHostToDevice, st));
+    const std::vector<char>& buf = img.bytes;
+    if (!d->tables.ensure(d->device, buf.size()) || !d->slab.ensure(d->device, BlockPool::kDevice, max_units * sizeof(int64_t))) return CCD_ERR_NOMEM;
+    std::memcpy(d->tables.host.p, buf.data(), buf.size());
+    HIP_TRY(d->tables.upload(buf.size(), st));
     d->planned = true;
     return CCD_OK;
 }
@@ -260,7 +239,7 @@ extern "C" {
 int ccd_latent_footprint(const ccd_cc_header* arch, int grid, int32_t box[4]) {
     if (!arch || !box) return CCD_ERR_ARG;
     ccd_cc_header h;
-    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
+    if (rederive_cc_header(*arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
     Footprint f;
     const int rc = footprint(h, grid, f);
     if (rc < 0) return rc;
@@ -272,7 +251,7 @@ int ccd_latent_footprint(const ccd_cc_header* arch, int grid, int32_t box[4]) {
 int ccd_latent_probe_stride(const ccd_cc_header* arch, int grid, int frame_data_type) {
     if (!arch || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
     ccd_cc_header h;
-    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
+    if (rederive_cc_header(*arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
     Footprint f;
     const int rc = footprint(h, grid, f);
     if (rc < 0) return rc;
@@ -298,10 +277,10 @@ int ccd_dsens_create(int device, int n_probe_slots, ccd_dsens** out) {
 void ccd_dsens_destroy(ccd_dsens* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    for (hipStream_t st : d->streams) (void)hipStreamSynchronize(st);
+    (void)d->streams.drain();
     ccd_batch_destroy(d->batch);  // drains the streams it was run on
     for (auto& c : d->cands) { c->priv.drop(); c->maps.drop(); }
-    d->tables.drop(); d->tables_host.drop(); d->slab.drop();
+    d->tables.drop(); d->slab.drop();
     delete d;
 }
 
@@ -313,7 +292,7 @@ int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_
     std::unique_ptr<Candidate> cp(new (std::nothrow) Candidate());
     if (!cp) return CCD_ERR_NOMEM;
     Candidate& c = *cp;
-    if (reparse(arch, n_nn, &c.hdr) < 0) return CCD_ERR_VALUE;
+    if (rederive_cc_header(*arch, n_nn, &c.hdr) < 0) return CCD_ERR_VALUE;
     const ccd_cc_header& h = c.hdr;
     if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;
     c.bitdepth = bitdepth;
@@ -324,9 +303,9 @@ int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_
         c.lat[g] = latents[g];
         const size_t n = static_cast<size_t>(h.grid_h[g]) * h.grid_w[g];
         c.grid_off[g] = c.copy_bytes;
-        c.copy_bytes += (n + 255) & ~size_t{255};
+        c.copy_bytes += align256(n);
         c.map_off[g] = map_bytes;
-        map_bytes += (2 * n * sizeof(int64_t) + 255) & ~size_t{255};
+        map_bytes += align256(2 * n * sizeof(int64_t));
         const int rc = footprint(h, g, c.fp[g]);
         if (rc < 0) return rc;
         if (rc == 1) continue;
@@ -363,12 +342,12 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
     if (d->cands.empty()) return CCD_OK;
     HIP_TRY(hipSetDevice(d->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (std::find(d->streams.begin(), d->streams.end(), st) == d->streams.end()) d->streams.push_back(st);
+    d->streams.note(st);
     if (!d->planned) {
         const int rc = build_tables(d, st);
         if (rc < 0) return rc;
     }
-    const char* base = d->tables.as<char>();
+    const char* base = d->tables.dev.as<char>();
     d->pending = 1;
     for (const Round& R : d->rounds) {
         HIP_TRY(launch_dsens_apply(reinterpret_cast<const DsensSeg*>(base + R.segs), reinterpret_cast<const uint32_t*>(base + R.seg_prefix), R.n_segs,

@@ -35,25 +35,26 @@ struct ccd_enc {
     int device = 0;
     DeviceShared* sh = nullptr;
     std::vector<std::unique_ptr<EncSlot>> slots;
-    Block table, table_host, status_dev, status_host;  // EncodeParams[n] (device, pinned), int32 [n][8] (device, pinned)
-    size_t table_slots = 0;        // slots the four blocks above describe
+    Mirror table, status;          // EncodeParams[n], int32 [n][8]
+    size_t table_slots = 0;        // slots the two above describe
     hipStream_t last_stream = nullptr;
     int in_flight = kIdle;         // one run OR one measure at a time
     int last_kind = kRun;          // what the last wait ended: whose per-slot errors an idle wait reports
     size_t n_run = 0;              // slots of the run in flight / last waited for
     // the rate meter's own buffers: a run and a measure never write to the same place
-    Block rate_table, rate_table_host;     // RateParams[n] (device, pinned)
-    Block rate_slab, rate_out, rate_out_host, rate_map;  // partials; per slot RateGrid[n_grids] + total, then int32 status [n]
+    Mirror rate_table, rate_out;   // RateParams[n]; per slot RateGrid[n_grids] + total, then int32 status [n]
+    Block rate_slab, rate_map;     // partials; the planes of a map
     size_t rate_slots = 0, rate_out_bytes = 0, rate_status_off = 0;
     bool rate_has_map = false;     // rate_table describes a map (the last measure asked for one)
     size_t n_measured = 0;         // slots of the measure in flight / last waited for
     bool map_valid = false;        // the last finished measure wrote a map
     // rate sensitivity (ccd_enc_measure_deltas): a measure whose two extra launches write here
-    Block delta_table, delta_table_host, delta_slab, delta_map;  // DeltaParams[n] (device, pinned), f64 cells, f32 [2][h][w] per grid
-    size_t delta_slots = 0;        // slots the four blocks above describe
+    Mirror delta_table;            // DeltaParams[n]
+    Block delta_slab, delta_map;   // f64 cells, f32 [2][h][w] per grid
+    size_t delta_slots = 0;        // slots the three above describe
     bool delta_pending = false;    // the measure in flight is a measure_deltas
     bool delta_valid = false;      // the last finished measure was one
-    std::vector<hipStream_t> streams;  // every stream a run was enqueued on (drained by destroy)
+    StreamSet streams;             // every stream a run was enqueued on
 };
 
 size_t ccd_enc_payload_bound(int64_t n_symbols) {
@@ -82,11 +83,11 @@ int ccd_enc_create(int device, ccd_enc** out) {
 void ccd_enc_destroy(ccd_enc* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    for (hipStream_t st : e->streams) (void)hipStreamSynchronize(st);
+    (void)e->streams.drain();
     for (auto& s : e->slots) { s->params.drop(); s->pairs.drop(); s->out.drop(); }
-    e->table.drop(); e->table_host.drop(); e->status_dev.drop(); e->status_host.drop();
-    e->rate_table.drop(); e->rate_table_host.drop(); e->rate_slab.drop(); e->rate_out.drop(); e->rate_out_host.drop(); e->rate_map.drop();
-    e->delta_table.drop(); e->delta_table_host.drop(); e->delta_slab.drop(); e->delta_map.drop();
+    e->table.drop(); e->status.drop();
+    e->rate_table.drop(); e->rate_slab.drop(); e->rate_out.drop(); e->rate_map.drop();
+    e->delta_table.drop(); e->delta_slab.drop(); e->delta_map.drop();
     delete e;
 }
 
@@ -99,13 +100,7 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
     if (!sp) return CCD_ERR_NOMEM;
     EncSlot& s = *sp;
     // ---- everything the host can refuse, before the device is touched ----
-    {   // re-derive the geometry from the transmitted fields by a serialise / parse round trip, like ccd_encode_coolchic
-        ccd_cc_header t = *tmpl;
-        t.nn_n_bytes = static_cast<int32_t>(n_nn);
-        uint8_t hb[256];
-        const int n_hb = (t.n_layer_synthesis >= 0 && t.n_layer_synthesis <= CCD_MAX_SYN_LAYERS) ? ccd_write_cc_header(&t, hb, sizeof(hb)) : -1;
-        if (n_hb < 0 || read_cc_header(hb, static_cast<size_t>(n_hb), &s.hdr) < 0) return CCD_ERR_VALUE;
-    }
+    if (rederive_cc_header(*tmpl, n_nn, &s.hdr) < 0) return CCD_ERR_VALUE;
     const ccd_cc_header& h = s.hdr;
     if (!grids_nest(h)) return CCD_ERR_VALUE;
     Network net;
@@ -171,21 +166,14 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
     Q.cap_words = static_cast<uint32_t>(ccd_enc_payload_bound(first) / 4);
 
     // ---- device image: ARM | IFCE | step prefix tables | host latents ----
-    auto align = [](size_t v) { return (v + 255) & ~size_t{255}; };
-    const size_t o_arm = 0;
-    const size_t o_ifce = align(o_arm + blobs.arm.size() * 8);
-    size_t pos = align(o_ifce + blobs.ifce.size() * 8);
+    TableImage img;
+    const size_t o_arm = img.put(blobs.arm), o_ifce = img.put(blobs.ifce);
     std::vector<size_t> o_prefix(n, 0), o_lat(n, 0);
-    for (int g = 0; g < n; ++g) { o_prefix[g] = pos; pos = align(pos + prefix[g].size() * 4); }
+    for (int g = 0; g < n; ++g) o_prefix[g] = img.put(prefix[g]);
     if (!latents_on_device)
-        for (int g = 0; g < n; ++g) { o_lat[g] = pos; pos = align(pos + static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]); }
-    std::vector<uint8_t> image(std::max<size_t>(pos, 256), 0);
-    std::memcpy(image.data() + o_arm, blobs.arm.data(), blobs.arm.size() * 8);
-    if (!blobs.ifce.empty()) std::memcpy(image.data() + o_ifce, blobs.ifce.data(), blobs.ifce.size() * 8);
-    for (int g = 0; g < n; ++g) {
-        if (!prefix[g].empty()) std::memcpy(image.data() + o_prefix[g], prefix[g].data(), prefix[g].size() * 4);
-        if (!latents_on_device) std::memcpy(image.data() + o_lat[g], latents[g], static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]);
-    }
+        for (int g = 0; g < n; ++g) o_lat[g] = img.put(latents[g], static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]);
+    std::vector<char>& image = img.bytes;
+    image.resize(std::max<size_t>(align256(image.size()), 256));  // whole 256-byte units, never empty
 
     HIP_TRY(hipSetDevice(e->device));
     auto fail = [&](int code) { s.params.drop(); s.pairs.drop(); s.out.drop(); return code; };
@@ -214,7 +202,7 @@ namespace {
 // Takes in what the run or measure in flight left in the pinned buffers; the caller has synchronised its stream.
 void harvest(ccd_enc* e) {
     if (e->in_flight == kRun) {
-        const int32_t* hs = e->status_host.as<int32_t>();
+        const int32_t* hs = e->status.host.as<int32_t>();
         for (size_t i = 0; i < e->n_run; ++i) {
             EncSlot& s = *e->slots[i];
             s.ran = true;
@@ -222,7 +210,7 @@ void harvest(ccd_enc* e) {
             s.n_words = s.status == CCD_OK ? static_cast<uint32_t>(hs[i * kEncStatusWords + 1]) : 0;
         }
     } else if (e->in_flight == kMeasure) {
-        const char* out = e->rate_out_host.as<char>();
+        const char* out = e->rate_out.host.as<char>();
         const int32_t* hs = reinterpret_cast<const int32_t*>(out + e->rate_status_off);
         size_t off = 0;
         for (size_t i = 0; i < e->n_measured; ++i) {
@@ -258,16 +246,13 @@ int prepare_launch(ccd_enc* e, hipStream_t st, unsigned* max_blocks, size_t* lds
         HIP_TRY(hipStreamSynchronize(e->last_stream));
         harvest(e);
     }
-    if (e->table_slots != n) {
+    if (e->table_slots != n) {  // (the blocks only grow; the loop below rewrites every entry of the table, so what a kept block held is gone)
         e->table_slots = 0;
-        if (!e->table.get(e->device, BlockPool::kDevice, n * sizeof(EncodeParams)) ||
-            !e->table_host.get(e->device, BlockPool::kPinned, n * sizeof(EncodeParams)) ||
-            !e->status_dev.get(e->device, BlockPool::kDevice, n * kEncStatusWords * sizeof(int32_t)) ||
-            !e->status_host.get(e->device, BlockPool::kPinned, n * kEncStatusWords * sizeof(int32_t)))
+        if (!e->table.ensure(e->device, n * sizeof(EncodeParams)) || !e->status.ensure(e->device, n * kEncStatusWords * sizeof(int32_t)))
             return CCD_ERR_NOMEM;
         for (size_t i = 0; i < n; ++i) {
-            e->slots[i]->ep.ep.status = e->status_dev.as<int32_t>() + i * kEncStatusWords;
-            e->table_host.as<EncodeParams>()[i] = e->slots[i]->ep;
+            e->slots[i]->ep.ep.status = e->status.dev.as<int32_t>() + i * kEncStatusWords;
+            e->table.host.as<EncodeParams>()[i] = e->slots[i]->ep;
         }
         e->table_slots = n;
     }
@@ -277,14 +262,14 @@ int prepare_launch(ccd_enc* e, hipStream_t st, unsigned* max_blocks, size_t* lds
         *max_blocks = std::max<unsigned>(*max_blocks, s->ep.n_blocks);
         *lds = std::max(*lds, encode_contexts_lds_bytes(s->ep.ep.dim));
     }
-    HIP_TRY(hipMemcpyAsync(e->table.p, e->table_host.p, n * sizeof(EncodeParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(e->table.upload(n * sizeof(EncodeParams), st));
     return CCD_OK;
 }
 
 void launched(ccd_enc* e, hipStream_t st, int kind) {
     e->last_stream = st;
     e->in_flight = kind;
-    if (std::find(e->streams.begin(), e->streams.end(), st) == e->streams.end()) e->streams.push_back(st);
+    e->streams.note(st);
 }
 }  // namespace
 
@@ -297,9 +282,9 @@ int ccd_enc_run(ccd_enc* e, void* stream) {
     size_t lds = 0;
     const int rc = prepare_launch(e, st, &max_blocks, &lds);
     if (rc < 0) return rc;
-    HIP_TRY(hipMemsetAsync(e->status_dev.p, 0, n * kEncStatusWords * sizeof(int32_t), st));
-    HIP_TRY(launch_encode(e->table.as<EncodeParams>(), static_cast<int>(n), max_blocks, lds, st));
-    HIP_TRY(hipMemcpyAsync(e->status_host.p, e->status_dev.p, n * kEncStatusWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(e->status.dev.p, 0, n * kEncStatusWords * sizeof(int32_t), st));
+    HIP_TRY(launch_encode(e->table.dev.as<EncodeParams>(), static_cast<int>(n), max_blocks, lds, st));
+    HIP_TRY(e->status.download(n * kEncStatusWords * sizeof(int32_t), st));
     e->n_run = n;
     launched(e, st, kRun);
     return CCD_OK;
@@ -328,21 +313,20 @@ int enqueue_measure(ccd_enc* e, hipStream_t st, bool map, unsigned* max_blocks_o
         e->rate_status_off = out_bytes;
         e->rate_out_bytes = out_bytes + n * sizeof(int32_t);
         if (!map) e->rate_map.drop();
-        if (!e->rate_table.get(e->device, BlockPool::kDevice, n * sizeof(RateParams)) ||
-            !e->rate_table_host.get(e->device, BlockPool::kPinned, n * sizeof(RateParams)) ||
-            !e->rate_slab.get(e->device, BlockPool::kDevice, std::max<size_t>(n_blocks * sizeof(RatePartial), 256)) ||
-            !e->rate_out.get(e->device, BlockPool::kDevice, e->rate_out_bytes) ||
-            !e->rate_out_host.get(e->device, BlockPool::kPinned, e->rate_out_bytes) ||
-            (map && !e->rate_map.get(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256))))
+        // (grow only: every entry of the table is rewritten below and the results are cleared before each launch)
+        if (!e->rate_table.ensure(e->device, n * sizeof(RateParams)) ||
+            !e->rate_slab.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_blocks * sizeof(RatePartial), 256)) ||
+            !e->rate_out.ensure(e->device, e->rate_out_bytes) ||
+            (map && !e->rate_map.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256))))
             return CCD_ERR_NOMEM;
         size_t block = 0, off = 0, cell = 0;
         for (size_t i = 0; i < n; ++i) {
             EncSlot& s = *e->slots[i];
-            RateParams& R = e->rate_table_host.as<RateParams>()[i];
+            RateParams& R = e->rate_table.host.as<RateParams>()[i];
             std::memset(&R, 0, sizeof(R));
             R.partial = e->rate_slab.as<RatePartial>() + block;
-            R.grids = reinterpret_cast<RateGrid*>(e->rate_out.as<char>() + off);
-            R.status = reinterpret_cast<int32_t*>(e->rate_out.as<char>() + e->rate_status_off) + i;
+            R.grids = reinterpret_cast<RateGrid*>(e->rate_out.dev.as<char>() + off);
+            R.status = reinterpret_cast<int32_t*>(e->rate_out.dev.as<char>() + e->rate_status_off) + i;
             s.map_off = cell;
             for (int g = 0; g < s.hdr.n_grids; ++g) {
                 if (map) R.map[g] = e->rate_map.as<float>() + cell;
@@ -356,10 +340,10 @@ int enqueue_measure(ccd_enc* e, hipStream_t st, bool map, unsigned* max_blocks_o
     }
     int max_grids = 0;
     for (auto& s : e->slots) max_grids = std::max<int>(max_grids, s->hdr.n_grids);
-    HIP_TRY(hipMemcpyAsync(e->rate_table.p, e->rate_table_host.p, n * sizeof(RateParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(e->rate_out.p, 0, e->rate_out_bytes, st));
-    HIP_TRY(launch_encode_rate(e->table.as<EncodeParams>(), e->rate_table.as<RateParams>(), static_cast<int>(n), max_blocks, max_grids, lds, st));
-    HIP_TRY(hipMemcpyAsync(e->rate_out_host.p, e->rate_out.p, e->rate_out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(e->rate_table.upload(n * sizeof(RateParams), st));
+    HIP_TRY(hipMemsetAsync(e->rate_out.dev.p, 0, e->rate_out_bytes, st));
+    HIP_TRY(launch_encode_rate(e->table.dev.as<EncodeParams>(), e->rate_table.dev.as<RateParams>(), static_cast<int>(n), max_blocks, max_grids, lds, st));
+    HIP_TRY(e->rate_out.download(e->rate_out_bytes, st));
     e->n_measured = n;
     return CCD_OK;
 }
@@ -403,16 +387,15 @@ int ccd_enc_measure_deltas(ccd_enc* e, void* stream) {
             n_map += 2 * static_cast<size_t>(s->ep.n_symbols);
         }
         if (n_cells > 0xffffffffu) return CCD_ERR_UNSUPPORTED;
-        if (!e->delta_table.get(e->device, BlockPool::kDevice, n * sizeof(DeltaParams)) ||
-            !e->delta_table_host.get(e->device, BlockPool::kPinned, n * sizeof(DeltaParams)) ||
-            !e->delta_slab.get(e->device, BlockPool::kDevice, std::max<size_t>(n_cells * sizeof(double), 256)) ||
-            !e->delta_map.get(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256)))
+        if (!e->delta_table.ensure(e->device, n * sizeof(DeltaParams)) ||  // (grow only: every entry is rewritten below)
+            !e->delta_slab.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_cells * sizeof(double), 256)) ||
+            !e->delta_map.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_map * sizeof(float), 256)))
             return CCD_ERR_NOMEM;
         size_t cell = 0, at = 0;
         for (size_t i = 0; i < n; ++i) {
             EncSlot& s = *e->slots[i];
             const EntropyParams& E = s.ep.ep;
-            DeltaParams& D = e->delta_table_host.as<DeltaParams>()[i];
+            DeltaParams& D = e->delta_table.host.as<DeltaParams>()[i];
             std::memset(&D, 0, sizeof(D));
             D.partial = e->delta_slab.as<double>() + cell;
             s.delta_off = at;
@@ -438,9 +421,9 @@ int ccd_enc_measure_deltas(ccd_enc* e, void* stream) {
     if (rc < 0) return rc;
     launched(e, st, kMeasure);
     unsigned max_tiles = 0;
-    for (size_t i = 0; i < n; ++i) max_tiles = std::max<unsigned>(max_tiles, e->delta_table_host.as<DeltaParams>()[i].n_tiles);
-    HIP_TRY(hipMemcpyAsync(e->delta_table.p, e->delta_table_host.p, n * sizeof(DeltaParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_encode_deltas(e->table.as<EncodeParams>(), e->delta_table.as<DeltaParams>(), static_cast<int>(n), max_blocks, max_tiles, lds, st));
+    for (size_t i = 0; i < n; ++i) max_tiles = std::max<unsigned>(max_tiles, e->delta_table.host.as<DeltaParams>()[i].n_tiles);
+    HIP_TRY(e->delta_table.upload(n * sizeof(DeltaParams), st));
+    HIP_TRY(launch_encode_deltas(e->table.dev.as<EncodeParams>(), e->delta_table.dev.as<DeltaParams>(), static_cast<int>(n), max_blocks, max_tiles, lds, st));
     e->delta_pending = true;
     return CCD_OK;
 }
@@ -496,7 +479,7 @@ int ccd_enc_slot_delta_map(const ccd_enc* e, int slot, int grid, void** dev_ptr)
 
 int ccd_enc_slot_status(const ccd_enc* e, int slot, int32_t* out8) {
     if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kRun || !e->slots[slot]->ran) return CCD_ERR_ARG;
-    if (out8) std::memcpy(out8, e->status_host.as<int32_t>() + static_cast<size_t>(slot) * kEncStatusWords, kEncStatusWords * sizeof(int32_t));
+    if (out8) std::memcpy(out8, e->status.host.as<int32_t>() + static_cast<size_t>(slot) * kEncStatusWords, kEncStatusWords * sizeof(int32_t));
     return e->slots[slot]->status;
 }
 

@@ -43,6 +43,11 @@ struct CodedFrame {
 int coding_structure(const ccd_video_header& h, std::vector<CodedFrame>& out);
 int read_frame_header(const uint8_t* p, size_t n, ccd_frame_header* h);
 int read_cc_header(const uint8_t* p, size_t n, ccd_cc_header* h);  // also fills the derived geometry
+// The header a cool-chic with the transmitted fields of `tmpl`, an NN payload of n_nn bytes and no latent payload would carry,
+// parsed into `out` (a serialise / parse round trip: the derived geometry follows from the transmitted fields alone) and, with
+// `bytes`, as serialised.  CCD_ERR_VALUE for n_layer_synthesis outside 1 .. CCD_MAX_SYN_LAYERS, before anything indexes
+// syn_layer[]; else what read_cc_header refuses, or CCD_OK.  (ccd_writer.cpp)
+int rederive_cc_header(const ccd_cc_header& tmpl, size_t n_nn, ccd_cc_header* out, std::vector<uint8_t>* bytes = nullptr);
 
 // One linear layer in fixed point, weights stored [in][out] (already transposed like armint.py:127).
 struct FixedLayer {

@@ -1,8 +1,10 @@
-// ccd_host.hpp - what the host files behind the C ABI share (host only): the block pool, per-device state, a batch and its slots.
+// ccd_host.hpp - what the host files behind the C ABI share (host only): the block pool and what every handle builds on it (Block,
+// Mirror, TableImage, StreamSet), per-device state, a batch and its slots.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -50,8 +52,46 @@ struct Block {
     int device = 0;
     BlockPool::Kind kind = BlockPool::kDevice;
     bool get(int dev, BlockPool::Kind k, size_t bytes) { drop(); device = dev; kind = k; p = pool().acquire(dev, k, bytes, &cls); return p != nullptr; }
+    // grows only: a block that is large enough stays (nothing of it may be in flight when it is exchanged)
+    bool ensure(int dev, BlockPool::Kind k, size_t bytes) { return cls >= bytes || get(dev, k, bytes); }
     void drop() { if (p) pool().release(device, kind, p, cls); p = nullptr; cls = 0; }
     template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// A device block and the pinned block it is staged through: tables go up, results come down, `bytes` of them.
+struct Mirror {
+    Block dev, host;
+    bool ensure(int device, size_t bytes) { return dev.ensure(device, BlockPool::kDevice, bytes) && host.ensure(device, BlockPool::kPinned, bytes); }
+    hipError_t upload(size_t bytes, hipStream_t st) const { return hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, st); }
+    hipError_t download(size_t bytes, hipStream_t st) const { return hipMemcpyAsync(host.p, dev.p, bytes, hipMemcpyDeviceToHost, st); }
+    void drop() { dev.drop(); host.drop(); }
+};
+
+// Everything placed in a device block starts on a 256-byte boundary.
+inline size_t align256(size_t v) { return (v + 255) & ~size_t{255}; }
+
+// Host image of tables that go to the device in one copy; put() returns the aligned offset of what it appended.
+struct TableImage {
+    std::vector<char> bytes;
+    size_t put(const void* p, size_t n) {
+        const size_t at = align256(bytes.size());
+        bytes.resize(at + n);
+        if (n) std::memcpy(bytes.data() + at, p, n);
+        return at;
+    }
+    template <typename T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size() * sizeof(T)); }
+};
+
+// Every stream work of a handle was enqueued on: all of them are drained before a block of the handle goes back to the pool,
+// not only the last one.
+struct StreamSet {
+    std::vector<hipStream_t> used;
+    void note(hipStream_t st) { if (std::find(used.begin(), used.end(), st) == used.end()) used.push_back(st); }
+    int drain() const {
+        int rc = CCD_OK;
+        for (hipStream_t st : used) if (hipStreamSynchronize(st) != hipSuccess) rc = CCD_ERR_HIP;
+        return rc;
+    }
 };
 
 // Per device, for the life of the process: the two Laplace-scale tables and the stream uploads run on (so that parsing
@@ -80,7 +120,7 @@ int device_shared(int device, DeviceShared** out);  // ccd_runtime.cpp
 // Bump allocator over one pooled device block: every slot's buffers live in a single arena.
 class Arena {
 public:
-    size_t reserve(size_t bytes) { size_t off = total_; total_ += (bytes + 255) & ~size_t{255}; return off; }
+    size_t reserve(size_t bytes) { size_t off = total_; total_ += align256(bytes); return off; }
     int commit(int device) {
         if (total_ == 0) total_ = 256;
         return blk_.get(device, BlockPool::kDevice, total_) ? CCD_OK : CCD_ERR_NOMEM;
@@ -157,11 +197,10 @@ void fill_entropy_model(const ccd_cc_header& h, const Network& net, const IntNet
 bool grids_nest(const ccd_cc_header& h);
 // Plans every launch of the batch and uploads the tables they read, when slots were added since the last call (or `regroup`).
 int build_launch_tables(ccd_batch* b, hipStream_t st);
-// (ccd_dsens_api.cpp) The transmitted fields of `arch` with the geometry they imply, and where a move of one latent of `grid`
-// can reach: per axis a (0 rows, 1 columns) the samples [s + lo[a], s + hi[a]], s = floor(i * num[a] / den[a]) for the latent
-// index i, before clipping to the picture.  footprint() returns 1 for a hyperlatent grid.
+// (ccd_dsens_api.cpp) Where a move of one latent of `grid` can reach: per axis a (0 rows, 1 columns) the samples
+// [s + lo[a], s + hi[a]], s = floor(i * num[a] / den[a]) for the latent index i, before clipping to the picture.  footprint()
+// returns 1 for a hyperlatent grid.
 struct Footprint { int32_t lo[2], hi[2]; uint32_t num[2], den[2]; };
-int reparse(const ccd_cc_header* arch, size_t n_nn, ccd_cc_header* out);
 int footprint(const ccd_cc_header& h, int grid, Footprint& f);
 
 }  // namespace ccd
@@ -178,11 +217,10 @@ struct ccd_batch {
     int32_t* d_status_all = nullptr;     // [slots][64]
     hipEvent_t up_done = nullptr;        // recorded on the upload stream behind the last ccd_batch_add
     hipStream_t up_stream = nullptr;     // the device's shared upload stream
-    // every stream the caller handed to ccd_batch_run_stage / ccd_batch_wait / ccd_batch_copy_*: all of them are drained before a
-    // block of this batch goes back to the pool (or its tables are replaced), not only the last one
-    std::vector<hipStream_t> streams_used;
-    void note_stream(hipStream_t st) { if (std::find(streams_used.begin(), streams_used.end(), st) == streams_used.end()) streams_used.push_back(st); }
-    int drain_streams();                 // (ccd_batch.cpp)
+    // every stream the caller handed to ccd_batch_run_stage / ccd_batch_wait / ccd_batch_copy_*: drained before a block of this
+    // batch goes back to the pool (or its tables are replaced)
+    ccd::StreamSet streams;
+    int drain();                         // ... with this batch's launches on the shared side streams (ccd_batch.cpp)
     // fork / join of the entropy launches over the device's side streams: the EVENTS belong to the batch (two host threads
     // running two batches on one GPU share the side streams, which only serialises their launches, but never an event)
     hipEvent_t fork = nullptr;

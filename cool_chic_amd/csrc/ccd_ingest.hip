@@ -18,23 +18,13 @@
 
 namespace ccd {
 namespace {
-// Segment of workgroup `blk`: the s with prefix[s] <= blk < prefix[s + 1].
-__device__ __forceinline__ int segment_of_block(const uint32_t* prefix, int n, uint32_t blk) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid + 1] <= blk) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // A byte is inside [-64, 63] exactly when its two top bits are equal; per byte of a dword: bit 7 of x ^ (x << 1).
 __device__ __forceinline__ uint32_t outside4(uint32_t x) { return (x ^ (x << 1)) & 0x80808080u; }
 
 __global__ __launch_bounds__(64) void latent_ingest_kernel(const IngestSeg* __restrict__ segs, const uint32_t* __restrict__ prefix, int n_segs,
                                                            int32_t* __restrict__ status_all, int word) {
     const uint32_t blk = blockIdx.x;
-    const int s = segment_of_block(prefix, n_segs, blk);
+    const int s = entry_of(prefix, n_segs, blk);
     const IngestSeg S = segs[s];
     const uint32_t chunk = blk - prefix[s];
     const uint32_t lane = threadIdx.x;

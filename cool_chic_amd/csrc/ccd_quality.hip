@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "ccd_device.hpp"
 #include "ccd_quality.hpp"
 
 namespace ccd {
@@ -28,16 +29,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kSX = kQStage + 1;   // row stride of the staged samples (floats): odd, so a column walk spreads over the banks
 constexpr int kHS = kQTile + 1;    // row stride of the horizontally filtered maps (doubles)
-
-// Plane of tile `t`: the p with prefix[p] <= t < prefix[p + 1] (planes without tiles have prefix[p] == prefix[p + 1]).
-__device__ __forceinline__ int plane_of_tile(const uint32_t* prefix, int n, uint32_t t) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid + 1] <= t) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ uint32_t sq_diff_u8x4(uint32_t a, uint32_t b) {
     uint32_t s = 0;
@@ -70,7 +61,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {  // fixed tree: the s
 __global__ __launch_bounds__(kThreads) void quality_sse_kernel(QualityBatch B) {
     __shared__ uint64_t wave_part[kThreads / 64];
     const uint32_t tile = blockIdx.x;
-    const int p = plane_of_tile(B.sse_prefix, B.n_planes, tile);
+    const int p = entry_of(B.sse_prefix, B.n_planes, tile);
     const QualityPlane& P = B.planes[p];
     const int wide = P.wide;
     const size_t bytes = (static_cast<size_t>(P.h) * static_cast<size_t>(P.w)) << wide;
@@ -122,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void quality_msssim_kernel(QualityBatch B
     __shared__ double wave_part[2][kThreads / 64];
     const uint32_t* prefix = B.ms_prefix + static_cast<size_t>(scale) * (B.n_planes + 1);
     const uint32_t tile = blockIdx.x;
-    const int p = plane_of_tile(prefix, B.n_planes, tile);
+    const int p = entry_of(prefix, B.n_planes, tile);
     const QualityPlane& P = B.planes[p];
     const int h = P.h >> scale, w = P.w >> scale;
     const int oh = h - (kQWin - 1), ow = w - (kQWin - 1);  // window positions ("valid"); >= 1 for a plane that has tiles

@@ -37,11 +37,10 @@ int quality_plan(const ccd_quality_item* items, int n, int what, QualityPlan& q)
     q.pool_off.assign(np * 2 * (kQScales - 1), 0);
     q.sse_prefix.assign(np + 1, 0);
     q.ms_prefix.assign(kQScales * (np + 1), 0);
-    auto align = [](size_t v) { return (v + 255) & ~size_t{255}; };
     size_t at = 0;
-    q.off_planes = at; at = align(at + np * sizeof(QualityPlane));
-    q.off_sse_prefix = at; at = align(at + (np + 1) * sizeof(uint32_t));
-    q.off_ms_prefix = at; at = align(at + kQScales * (np + 1) * sizeof(uint32_t));
+    q.off_planes = at; at = align256(at + np * sizeof(QualityPlane));
+    q.off_sse_prefix = at; at = align256(at + (np + 1) * sizeof(uint32_t));
+    q.off_ms_prefix = at; at = align256(at + kQScales * (np + 1) * sizeof(uint32_t));
     q.head_bytes = at;
     size_t pool_at = 0;  // relative to the start of the pooled pictures, placed last
     uint64_t sse_tiles = 0, ms_tiles[kQScales] = {0};
@@ -66,7 +65,7 @@ int quality_plan(const ccd_quality_item* items, int n, int what, QualityPlan& q)
             if (j) {
                 for (int s = 0; s < 2; ++s) {
                     q.pool_off[(k * 2 + s) * (kQScales - 1) + (j - 1)] = pool_at;
-                    pool_at = align(pool_at + static_cast<size_t>(hj) * wj * sizeof(float));
+                    pool_at = align256(pool_at + static_cast<size_t>(hj) * wj * sizeof(float));
                 }
             }
         }
@@ -78,9 +77,9 @@ int quality_plan(const ccd_quality_item* items, int n, int what, QualityPlan& q)
         }
     }
     for (int j = 0; j < kQScales; ++j) q.scale_first[j + 1] = q.scale_first[j] + static_cast<uint32_t>(ms_tiles[j]);
-    q.off_sse_part = at; at = align(at + static_cast<size_t>(sse_tiles) * sizeof(uint64_t));
-    q.off_ms_part = at; at = align(at + static_cast<size_t>(q.scale_first[kQScales]) * 2 * sizeof(double));
-    q.off_out = at; at = align(at + np * sizeof(QualityOut));
+    q.off_sse_part = at; at = align256(at + static_cast<size_t>(sse_tiles) * sizeof(uint64_t));
+    q.off_ms_part = at; at = align256(at + static_cast<size_t>(q.scale_first[kQScales]) * 2 * sizeof(double));
+    q.off_out = at; at = align256(at + np * sizeof(QualityOut));
     for (auto& o : q.pool_off) o += at;
     q.total = at + pool_at;
     return CCD_OK;
@@ -95,7 +94,7 @@ struct ccd_quality {
     QualityPlan plan;                  // of the scoring in flight / last finished
     int pending = 0;                   // items of the scoring in flight
     double g[kQWin];
-    std::vector<hipStream_t> streams;  // every stream a scoring was enqueued on (drained by destroy)
+    StreamSet streams;                 // every stream a scoring was enqueued on
 };
 
 int64_t ccd_quality_scratch_bytes(const ccd_quality_item* items, int n, int what) {
@@ -123,7 +122,7 @@ int ccd_quality_create(int device, ccd_quality** out) {
 void ccd_quality_destroy(ccd_quality* q) {
     if (!q) return;
     (void)hipSetDevice(q->device);
-    for (hipStream_t st : q->streams) (void)hipStreamSynchronize(st);
+    (void)q->streams.drain();
     q->dev.drop(); q->head_host.drop(); q->out_host.drop();
     delete q;
 }
@@ -137,9 +136,9 @@ int ccd_quality_score_batch(ccd_quality* q, const ccd_quality_item* items, int n
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t np = P.planes.size();
     // nothing of an earlier scoring is in flight (its finish synchronised), so the blocks may be exchanged for larger ones
-    if (q->dev.cls < P.total && !q->dev.get(q->device, BlockPool::kDevice, P.total)) return CCD_ERR_NOMEM;
-    if (q->head_host.cls < P.head_bytes && !q->head_host.get(q->device, BlockPool::kPinned, P.head_bytes)) return CCD_ERR_NOMEM;
-    if (q->out_host.cls < np * sizeof(QualityOut) && !q->out_host.get(q->device, BlockPool::kPinned, np * sizeof(QualityOut))) return CCD_ERR_NOMEM;
+    if (!q->dev.ensure(q->device, BlockPool::kDevice, P.total) || !q->head_host.ensure(q->device, BlockPool::kPinned, P.head_bytes) ||
+        !q->out_host.ensure(q->device, BlockPool::kPinned, np * sizeof(QualityOut)))
+        return CCD_ERR_NOMEM;
     char* base = q->dev.as<char>();
     for (size_t k = 0; k < np; ++k)
         for (int s = 0; s < 2; ++s)
@@ -161,7 +160,7 @@ int ccd_quality_score_batch(ccd_quality* q, const ccd_quality_item* items, int n
     B.ms_part = reinterpret_cast<double*>(base + P.off_ms_part);
     B.out = reinterpret_cast<QualityOut*>(base + P.off_out);
     std::memcpy(B.g, q->g, sizeof(B.g));
-    if (std::find(q->streams.begin(), q->streams.end(), st) == q->streams.end()) q->streams.push_back(st);
+    q->streams.note(st);
     HIP_TRY(launch_quality(B, P.sse_prefix[np], st));
     HIP_TRY(hipMemcpyAsync(q->out_host.p, B.out, np * sizeof(QualityOut), hipMemcpyDeviceToHost, st));
     q->pending = n;

@@ -28,16 +28,6 @@
 
 namespace ccd {
 namespace {
-// The entry s with prefix[s] <= i < prefix[s + 1] (entries without work have prefix[s] == prefix[s + 1]).
-__device__ __forceinline__ int entry_of(const uint32_t* prefix, int n, uint32_t i) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid + 1] <= i) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ bool in_alphabet(int v) { return v >= kAcLo && v < kAcLo + kAlphabet; }
 
 // Floats in the order of their values as unsigned integers.

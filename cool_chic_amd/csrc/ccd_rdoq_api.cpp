@@ -23,7 +23,7 @@ struct Geometry {
 };
 
 int make_geometry(const ccd_cc_header* arch, int frame_data_type, Geometry& G) {
-    if (reparse(arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &G.h) < 0) return CCD_ERR_VALUE;
+    if (rederive_cc_header(*arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &G.h) < 0) return CCD_ERR_VALUE;
     const ccd_cc_header& h = G.h;
     if (h.n_grids < 1 || h.grid_h[0] < 1 || h.grid_w[0] < 1 || h.img_size[0] < 1 || h.img_size[1] < 1) return CCD_ERR_VALUE;
     if (h.spatial_context_arm < 0 || h.spatial_context_arm > kMaxCtx) return CCD_ERR_VALUE;
@@ -109,8 +109,6 @@ RdoqBox influence_box(const Geometry& G, int m, int y, int x) {
     return b;
 }
 
-size_t up256(size_t n) { return (n + 255) & ~size_t{255}; }
-
 struct RSlot {
     Geometry geo;
     int n_grids = 0;
@@ -132,11 +130,12 @@ struct RSlot {
 struct ccd_rdoq {
     int device = 0;
     std::vector<std::unique_ptr<RSlot>> slots;
-    Block tables, tables_host, partial, results, results_host;
+    Mirror tables, results;
+    Block partial;
     int pending = 0;       // a step is in flight
     int n_stepped = 0;     // slots the step in flight covers
     hipStream_t step_stream = nullptr;  // ... and the stream it was enqueued on
-    std::vector<hipStream_t> streams;
+    StreamSet streams;
 };
 
 extern "C" {
@@ -167,12 +166,10 @@ int ccd_rdoq_create(int device, ccd_rdoq** out) {
 
 void ccd_rdoq_destroy(ccd_rdoq* r) {
     if (!r) return;
-    if (!r->slots.empty()) {
-        (void)hipSetDevice(r->device);
-        for (hipStream_t st : r->streams) (void)hipStreamSynchronize(st);
-    }
+    (void)hipSetDevice(r->device);
+    (void)r->streams.drain();
     for (auto& s : r->slots) s->mem.drop();
-    r->tables.drop(); r->tables_host.drop(); r->partial.drop(); r->results.drop(); r->results_host.drop();
+    r->tables.drop(); r->partial.drop(); r->results.drop();
     delete r;
 }
 
@@ -198,7 +195,7 @@ int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, in
     // the boxes of every latent and the lists of those a wave walks, laid out as they go to the device
     std::vector<std::vector<RdoqBox>> boxes(h.n_grids);
     std::vector<std::vector<uint32_t>> big(h.n_grids);
-    size_t bytes = 0;
+    TableImage img;
     for (int g = 0; g < h.n_grids; ++g) {
         boxes[g].resize(s.n[g]);
         for (int y = 0; y < h.grid_h[g]; ++y)
@@ -208,23 +205,21 @@ int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, in
                 if (static_cast<uint32_t>(b.bottom - b.top + 1) * static_cast<uint32_t>(b.right - b.left + 1) > kRdoqLaneCells) big[g].push_back(i);
             }
         s.n_big[g] = static_cast<uint32_t>(big[g].size());
-        s.box_off[g] = bytes; bytes += up256(s.n[g] * sizeof(RdoqBox));
-        s.big_off[g] = bytes; bytes += up256(big[g].size() * sizeof(uint32_t));
+        s.box_off[g] = img.put(boxes[g]);
+        s.big_off[g] = img.put(big[g]);
     }
-    const size_t upload = bytes;
+    std::vector<char>& host = img.bytes;
+    host.resize(align256(host.size()));
+    const size_t upload = host.size();
+    size_t bytes = upload;
     for (int g = 0; g < h.n_grids; ++g) {
-        s.moves_off[g] = bytes; bytes += up256(s.n[g]);
-        s.pick_off[g] = bytes; bytes += up256(s.n[g]);
+        s.moves_off[g] = bytes; bytes += align256(s.n[g]);
+        s.pick_off[g] = bytes; bytes += align256(s.n[g]);
     }
     s.raster_off = bytes;
-    const size_t raster_bytes = up256(static_cast<size_t>(s.geo.cells_h) * s.geo.cells_w * sizeof(unsigned long long));
+    const size_t raster_bytes = align256(static_cast<size_t>(s.geo.cells_h) * s.geo.cells_w * sizeof(unsigned long long));
     s.raster_units = static_cast<uint32_t>(raster_bytes / 16);
     bytes += raster_bytes;
-    std::vector<char> host(upload, 0);
-    for (int g = 0; g < h.n_grids; ++g) {
-        std::memcpy(host.data() + s.box_off[g], boxes[g].data(), boxes[g].size() * sizeof(RdoqBox));
-        if (!big[g].empty()) std::memcpy(host.data() + s.big_off[g], big[g].data(), big[g].size() * sizeof(uint32_t));
-    }
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(r->device));
     if (!s.mem.get(r->device, BlockPool::kDevice, bytes)) return CCD_ERR_NOMEM;
@@ -294,37 +289,28 @@ int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double*
             grids.push_back(G);
         }
     }
-    std::vector<char> buf;
-    auto put = [&buf](const void* p, size_t bytes) {
-        const size_t at = up256(buf.size());
-        buf.resize(at + bytes);
-        if (bytes) std::memcpy(buf.data() + at, p, bytes);
-        return at;
-    };
-    const size_t o_grids = put(grids.data(), grids.size() * sizeof(RdoqGrid)), o_slots = put(slots.data(), slots.size() * sizeof(RdoqSlot));
-    const size_t o_lane = put(lane_prefix.data(), lane_prefix.size() * 4), o_big = put(big_prefix.data(), big_prefix.size() * 4);
-    const size_t o_chunk = put(chunk_prefix.data(), chunk_prefix.size() * 4);
+    TableImage img;
+    const size_t o_grids = img.put(grids), o_slots = img.put(slots);
+    const size_t o_lane = img.put(lane_prefix), o_big = img.put(big_prefix), o_chunk = img.put(chunk_prefix);
+    const std::vector<char>& buf = img.bytes;
     HIP_TRY(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (std::find(r->streams.begin(), r->streams.end(), st) == r->streams.end()) r->streams.push_back(st);
+    r->streams.note(st);
     // nothing of an earlier step is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
     const size_t res_bytes = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
-    if ((r->tables.cls < buf.size() && !r->tables.get(r->device, BlockPool::kDevice, buf.size())) ||
-        (r->tables_host.cls < buf.size() && !r->tables_host.get(r->device, BlockPool::kPinned, buf.size())) ||
-        (r->partial.cls < chunks * sizeof(RdoqPartial) && !r->partial.get(r->device, BlockPool::kDevice, chunks * sizeof(RdoqPartial))) ||
-        (r->results.cls < res_bytes && !r->results.get(r->device, BlockPool::kDevice, res_bytes)) ||
-        (r->results_host.cls < res_bytes && !r->results_host.get(r->device, BlockPool::kPinned, res_bytes)))
+    if (!r->tables.ensure(r->device, buf.size()) || !r->partial.ensure(r->device, BlockPool::kDevice, chunks * sizeof(RdoqPartial)) ||
+        !r->results.ensure(r->device, res_bytes))
         return CCD_ERR_NOMEM;
-    std::memcpy(r->tables_host.p, buf.data(), buf.size());
-    const char* base = r->tables.as<char>();
+    std::memcpy(r->tables.host.p, buf.data(), buf.size());
+    const char* base = r->tables.dev.as<char>();
     const bool ok =
-        hipMemcpyAsync(r->tables.p, r->tables_host.p, buf.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+        r->tables.upload(buf.size(), st) == hipSuccess &&
         launch_rdoq_step(reinterpret_cast<const RdoqGrid*>(base + o_grids), reinterpret_cast<const RdoqSlot*>(base + o_slots),
                          reinterpret_cast<const uint32_t*>(base + o_lane), reinterpret_cast<const uint32_t*>(base + o_big),
                          reinterpret_cast<const uint32_t*>(base + o_chunk), n_grids, n_slots, static_cast<uint32_t>(lanes),
                          static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks), r->partial.as<RdoqPartial>(),
-                         r->results.as<ccd_rdoq_result>(), st) == hipSuccess &&
-        hipMemcpyAsync(r->results_host.p, r->results.p, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+                         r->results.dev.as<ccd_rdoq_result>(), st) == hipSuccess &&
+        r->results.download(res_bytes, st) == hipSuccess;
     if (!ok) {  // part of the step may have been enqueued: drain it; no slot has a result, no step is in flight
         (void)hipStreamSynchronize(st);
         for (auto& s : r->slots) s->covered = false;
@@ -344,7 +330,7 @@ int ccd_rdoq_wait(ccd_rdoq* r, void* stream) {
     // the results are behind the step on the stream the step was given, whichever stream this call names
     if (r->step_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(r->step_stream));
     r->pending = 0;
-    const ccd_rdoq_result* res = r->results_host.as<ccd_rdoq_result>();
+    const ccd_rdoq_result* res = r->results.host.as<ccd_rdoq_result>();
     for (int k = 0; k < r->n_stepped; ++k) {
         RSlot& s = *r->slots[k];
         s.result = res[k];

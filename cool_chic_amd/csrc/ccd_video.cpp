@@ -270,8 +270,8 @@ int ccd_decode_video(const uint8_t* bs, size_t n, int device, ccd_video* v) {
             }
             if (rc < 0) break;
             const size_t sb = d.bitdepth == 8 ? 1 : 2;
-            const size_t luma = (static_cast<size_t>(d.h) * d.w * sb + 16 + 255) & ~size_t{255};
-            const size_t chroma = (static_cast<size_t>(d.ch) * d.cw * sb + 16 + 255) & ~size_t{255};
+            const size_t luma = align256(static_cast<size_t>(d.h) * d.w * sb + 16);
+            const size_t chroma = align256(static_cast<size_t>(d.ch) * d.cw * sb + 16);
             if (!d.own.get(device, BlockPool::kDevice, luma + 2 * chroma)) { rc = CCD_ERR_NOMEM; break; }
             d.plane[0] = d.own.as<char>(); d.plane[1] = d.own.as<char>() + luma; d.plane[2] = d.own.as<char>() + luma + chroma;
             const size_t need = static_cast<size_t>(9) * d.h * d.w;

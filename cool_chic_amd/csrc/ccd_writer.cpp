@@ -174,12 +174,6 @@ std::vector<uint8_t> video_header_bytes_one_intra() {
     return video_header_bytes(v);
 }
 
-// Serialise / parse round trip: fills the derived geometry from the transmitted fields of `tmpl`.
-int rederive(const ccd_cc_header& tmpl, ccd_cc_header* h) {
-    const std::vector<uint8_t> hb = cc_header_bytes(tmpl, 0);
-    return read_cc_header(hb.data(), hb.size(), h);
-}
-
 // armint.py:180-203 on the host (writer side only).
 void mlp_forward(const FixedArm& a, const int64_t* ctx, int output_shift, int64_t* out) {
     int64_t x[128], y[128], stab[64];
@@ -209,6 +203,16 @@ void mlp_forward(const FixedArm& a, const int64_t* ctx, int output_shift, int64_
 }
 
 }  // namespace
+
+int rederive_cc_header(const ccd_cc_header& tmpl, size_t n_nn, ccd_cc_header* out, std::vector<uint8_t>* bytes) {
+    if (tmpl.n_layer_synthesis < 1 || tmpl.n_layer_synthesis > CCD_MAX_SYN_LAYERS) return CCD_ERR_VALUE;
+    ccd_cc_header t = tmpl;
+    t.nn_n_bytes = static_cast<int32_t>(n_nn);
+    std::vector<uint8_t> hb = cc_header_bytes(t, 0);
+    const int rc = read_cc_header(hb.data(), hb.size(), out);
+    if (bytes) bytes->swap(hb);
+    return rc < 0 ? rc : CCD_OK;
+}
 }  // namespace ccd
 
 using namespace ccd;
@@ -231,7 +235,7 @@ int64_t ccd_range_encode(const int8_t* symbols, const int32_t* mu_idx, const int
 int ccd_network_layout(const ccd_cc_header* arch, int64_t n_values[8]) {
     if (!arch || !n_values) return CCD_ERR_ARG;
     ccd_cc_header h;
-    int rc = rederive(*arch, &h);
+    int rc = rederive_cc_header(*arch, static_cast<size_t>(arch->nn_n_bytes), &h);  // (the field as it stands: 14 bits of it are written)
     if (rc < 0) return rc;
     size_t n_kind[8];
     rc = network_layout(h, n_kind);
@@ -304,16 +308,11 @@ int ccd_write_video_header(const ccd_video_header* v, uint8_t* out, size_t cap) 
 int64_t ccd_encode_coolchic(const ccd_cc_header* tmpl, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
                             uint8_t** out) {
     if (!tmpl || !bytes_nn || !latents || !out) return CCD_ERR_ARG;
-    // Re-derive the geometry from the transmitted fields by a serialise/parse round trip.
     ccd_cc_header h;
-    {
-        ccd_cc_header t = *tmpl;
-        t.nn_n_bytes = static_cast<int32_t>(n_nn);
-        const int rc = rederive(t, &h);
-        if (rc < 0) return rc;
-    }
+    int rc = rederive_cc_header(*tmpl, n_nn, &h);
+    if (rc < 0) return rc;
     Network net;
-    int rc = decode_network(h, bytes_nn, n_nn, net);
+    rc = decode_network(h, bytes_nn, n_nn, net);
     if (rc < 0) return rc;
     const int n = h.n_grids, n_sp = h.spatial_context_arm, n_if = h.has_ifce_resolution ? h.output_feature_ifce : 0;
     int dy[kMaxCtx], dx[kMaxCtx];

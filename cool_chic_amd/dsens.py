@@ -4,10 +4,10 @@ every grid, on one MI355X (wraps the ccd_dsens_* C ABI).
 The numbers are those of one decode per moved latent (DecodeBatch.add_latents + QualityMeter), as integers; they come from a
 few thousand passes of the float path per picture, each of which moves every latent of one lattice at once."""
 import ctypes as C
-from typing import List, Sequence, Tuple
+from typing import Sequence
 
+from ._handle import _DevArray, _Handle, ptr_array
 from ._lib import CCHeader, check, lib
-from .batch import _DevArray
 
 SENTINEL = -2 ** 63  # the entry where v - 1 / v + 1 leaves [-64, 63] (INT64_MIN)
 
@@ -25,33 +25,13 @@ def probe_stride(arch: CCHeader, grid: int, frame_data_type: int = 0) -> int:
     return check(lib().ccd_latent_probe_stride(C.byref(arch), int(grid), int(frame_data_type)), "ccd_latent_probe_stride")
 
 
-class DistortionDeltas:
+class DistortionDeltas(_Handle):
     """One slot per candidate; run() enqueues every pass of every slot, wait() ends it, delta_map() hands out the maps."""
 
+    _destroy = "ccd_dsens_destroy"
+
     def __init__(self, device: int = 0, n_probe_slots: int = 16):
-        self._h = C.c_void_p()
-        check(lib().ccd_dsens_create(int(device), int(n_probe_slots), C.byref(self._h)), "ccd_dsens_create")
-        self.device = int(device)
-        self._owners: List[object] = []  # whatever owns the device latents and source planes the slots read at run()
-        self._grid_shapes: List[List[Tuple[int, int]]] = []
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_dsens_destroy(self._h)
-            self._h = C.c_void_p()
-            self._owners = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._open("ccd_dsens_create", device, int(n_probe_slots))
 
     def __len__(self):
         return len(self._grid_shapes)
@@ -60,13 +40,11 @@ class DistortionDeltas:
             frame_data_type: int, owner=None) -> int:
         """Device latents (int8 [h][w] per grid, read at every run, never written) and the three device planes of the source
         (uint8 at 8 bits, else uint16; half-size chroma for yuv420).  Returns the slot."""
-        lat = (C.c_void_p * len(latent_ptrs))(*[int(p) for p in latent_ptrs])
         src = (C.c_void_p * 3)(*[int(p) for p in source_ptrs])
-        slot = check(lib().ccd_dsens_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), lat, src, int(bitdepth), int(frame_data_type)),
-                     "ccd_dsens_add")
-        self._grid_shapes.append([(int(arch.grid_h[g]), int(arch.grid_w[g])) for g in range(len(latent_ptrs))])
-        if owner is not None:
-            self._owners.append(owner)
+        slot = check(lib().ccd_dsens_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptr_array(latent_ptrs), src, int(bitdepth),
+                                         int(frame_data_type)), "ccd_dsens_add")
+        self._note_grids(arch, len(latent_ptrs))
+        self._keep(owner)  # (the device latents and source planes the slot reads at run())
         return slot
 
     def run(self, stream: int = 0):
@@ -82,8 +60,4 @@ class DistortionDeltas:
     def delta_map(self, slot: int, grid: int) -> _DevArray:
         """After run() + wait(): int64 [2][h][w], the change of the frame's squared error if the latent at (y, x) alone were
         v - 1 (plane 0) or v + 1 (plane 1); SENTINEL where that leaves [-64, 63].  Valid until the next run / close."""
-        ptr = C.c_void_p()
-        n = check(lib().ccd_dsens_slot_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_dsens_slot_map")
-        h, w = self._grid_shapes[int(slot)][int(grid)]
-        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
-        return _DevArray(ptr.value or 0, (2, h, w), "<i8", self)
+        return self._grid_map("ccd_dsens_slot_map", slot, grid, "<i8", (2,))

@@ -4,12 +4,13 @@ The bytes are those of writer.encode_coolchic (cool-chic header + NN payload + r
 bitstream/encode.py:83-92); the contexts of every pixel are evaluated at once and one wave per slot runs the range
 encoder's interval chain."""
 import ctypes as C
-from typing import List, NamedTuple, Sequence, Tuple
+from typing import NamedTuple, Sequence, Tuple
 
 import numpy as np
 
+from ._handle import _DevArray, _Handle, ptr_array
 from ._lib import CcdError, CCHeader, EncRate, check, lib
-from .batch import DecodeBatch, _DevArray
+from .batch import DecodeBatch
 
 
 class SlotRate(NamedTuple):
@@ -23,27 +24,13 @@ class SlotRate(NamedTuple):
     n_bytes_header: int
 
 
-class EncodeBatch:
+class EncodeBatch(_Handle):
     """One slot per cool-chic; run() encodes all of them in the same two launches, measure() prices them without the chain."""
 
+    _destroy = "ccd_enc_destroy"
+
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        check(lib().ccd_enc_create(int(device), C.byref(self._h)), "ccd_enc_create")
-        self.device = int(device)
-        self._owners: List[object] = []  # decode batches whose device latents the slots read at run()
-        self._grid_shapes: List[List[Tuple[int, int]]] = []  # per slot, per grid (h, w): the shape of a rate map
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_enc_destroy(self._h)
-            self._h = C.c_void_p()
-            self._owners = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open("ccd_enc_create", device)
 
     def __len__(self):
         return check(lib().ccd_enc_size(self._h), "ccd_enc_size")
@@ -51,18 +38,15 @@ class EncodeBatch:
     def add(self, arch: CCHeader, bytes_nn: bytes, latents: Sequence[np.ndarray]) -> int:
         """Host latents (index 0 = finest grid, values in [-64, 63]); returns the slot."""
         arrs = [np.ascontiguousarray(a, dtype=np.int8) for a in latents]
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptrs, 0), "ccd_enc_add")
+        slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptr_array([a.ctypes.data for a in arrs]), 0), "ccd_enc_add")
         self._grid_shapes.append([a.shape[-2:] for a in arrs])
         return slot
 
     def add_device(self, arch: CCHeader, bytes_nn: bytes, latent_ptrs: Sequence[int], owner=None) -> int:
         """Latents that already sit on the device (int8 [h][w] per grid); they are read when run() executes."""
-        ptrs = (C.c_void_p * len(latent_ptrs))(*[int(p) for p in latent_ptrs])
-        slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptrs, 1), "ccd_enc_add")
-        self._grid_shapes.append([(int(arch.grid_h[g]), int(arch.grid_w[g])) for g in range(len(latent_ptrs))])
-        if owner is not None:
-            self._owners.append(owner)
+        slot = check(lib().ccd_enc_add(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptr_array(latent_ptrs), 1), "ccd_enc_add")
+        self._note_grids(arch, len(latent_ptrs))
+        self._keep(owner)  # (the decode batch whose device latents the slot reads at run())
         return slot
 
     def add_from_decode(self, batch: DecodeBatch, slot: int) -> int:
@@ -95,11 +79,7 @@ class EncodeBatch:
     def rate_map(self, slot: int, grid: int) -> _DevArray:
         """Bits of every latent of a grid where measure(rate_map=True) left them (float32 [h][w], valid until the next
         measure / close)."""
-        ptr = C.c_void_p()
-        n = check(lib().ccd_enc_slot_rate_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_enc_slot_rate_map")
-        h, w = self._grid_shapes[int(slot)][int(grid)]
-        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
-        return _DevArray(ptr.value or 0, (h, w), "<f4", self)
+        return self._grid_map("ccd_enc_slot_rate_map", slot, grid, "<f4")
 
     def measure_deltas(self, stream: int = 0):
         """measure() followed by the rate sensitivity launches: rate() as after measure(), and delta_map() of every grid."""
@@ -109,11 +89,7 @@ class EncodeBatch:
         """After measure_deltas() + wait(): float32 [2][h][w], the exact change of the slot's model bits if the latent at
         (y, x) alone were v - 1 (plane 0) or v + 1 (plane 1); +inf where that leaves [-64, 63].  Valid until the next measure /
         measure_deltas / close."""
-        ptr = C.c_void_p()
-        n = check(lib().ccd_enc_slot_delta_map(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_enc_slot_delta_map")
-        h, w = self._grid_shapes[int(slot)][int(grid)]
-        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
-        return _DevArray(ptr.value or 0, (2, h, w), "<f4", self)
+        return self._grid_map("ccd_enc_slot_delta_map", slot, grid, "<f4", (2,))
 
     def slot_status(self, slot: int) -> Tuple[int, np.ndarray]:
         """(status, counters) after wait(): counters[1] payload words, [2] inverted runs begun by the coder, [3] resolved

@@ -9,18 +9,18 @@ import ctypes as C
 
 import torch
 
+from .._handle import _Handle
 from .._lib import PngItem, check, lib
 
 
-class PngPacker:
+class PngPacker(_Handle):
     """One packer = one workspace in HBM; packs are enqueued on the caller's stream."""
 
+    _destroy = "ccd_png_destroy"
     LEVELS = (0, 1)  # CCD_PNG_LITERAL, CCD_PNG_LZ77
 
     def __init__(self, device: int = 0, level: int = 0):
-        self._h = C.c_void_p()
-        check(lib().ccd_png_create(int(device), C.byref(self._h)), "ccd_png_create")
-        self.device = int(device)
+        self._open("ccd_png_create", device)
         self.level = 0
         try:
             self.set_level(level)
@@ -34,17 +34,6 @@ class PngPacker:
             raise ValueError(f"PNG level must be 0 or 1, got {level!r}")
         check(lib().ccd_png_set_level(self._h, int(level)), "ccd_png_set_level")
         self.level = int(level)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_png_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def bound(h: int, w: int) -> int:

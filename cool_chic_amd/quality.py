@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ._handle import _Handle
 from ._lib import QualityItem, QualityResult, check, lib
 from .io import FrameData
 
@@ -92,30 +93,13 @@ def _frame_planes(fd: FrameData, device: torch.device) -> List[torch.Tensor]:
     return _integer_planes(fd, device)
 
 
-class QualityMeter:
+class QualityMeter(_Handle):
     """One meter = one handle; a scoring is enqueued on the current stream of its device and waited for."""
 
+    _destroy = "ccd_quality_destroy"
+
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        check(lib().ccd_quality_create(int(device), C.byref(self._h)), "ccd_quality_create")
-        self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_quality_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open("ccd_quality_create", device)
 
     def score_planes_async(self, decoded: Sequence[Sequence[torch.Tensor]], sources: Sequence[Sequence[torch.Tensor]],
                            bitdepths: Sequence[int], ms_ssim: bool = True, stream: Optional[int] = None) -> None:

@@ -4,10 +4,10 @@ that provably do not interact and apply them to the device latents in place (wra
 After a step the frame's squared error has changed by exactly `d_sse` and the model bits by `d_bits` (within the rate deltas'
 own bound): the sums of the chosen entries of the two maps."""
 import ctypes as C
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
+from ._handle import _DevArray, _Handle, ptr_array
 from ._lib import CCHeader, RdoqResult, check, lib
-from .batch import _DevArray
 
 
 class StepResult(NamedTuple):
@@ -32,46 +32,24 @@ def influence_box(arch: CCHeader, frame_data_type: int, grid: int, y: int, x: in
     return tuple(int(v) for v in box)
 
 
-class RdoqStep:
+class RdoqStep(_Handle):
     """One slot per candidate: add() its device latents, set_maps() the device maps, step() + wait(), then result() and moves()."""
 
     influence_box = staticmethod(influence_box)
 
+    _destroy = "ccd_rdoq_destroy"
+
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        check(lib().ccd_rdoq_create(int(device), C.byref(self._h)), "ccd_rdoq_create")
-        self.device = int(device)
-        self._owners: List[object] = []  # whatever owns the device latents and maps the slots use at step()
-        self._grid_shapes: List[List[Tuple[int, int]]] = []
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().ccd_rdoq_destroy(self._h)
-            self._h = C.c_void_p()
-            self._owners = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._open("ccd_rdoq_create", device)
 
     def __len__(self):
         return len(self._grid_shapes)
 
     def add(self, arch: CCHeader, frame_data_type: int, latent_ptrs: Sequence[int], owner=None) -> int:
         """Device latents (int8 [h][w] per grid), read AND WRITTEN by every step.  Returns the slot."""
-        lat = (C.c_void_p * len(latent_ptrs))(*[int(p) for p in latent_ptrs])
-        slot = check(lib().ccd_rdoq_add(self._h, C.byref(arch), int(frame_data_type), lat), "ccd_rdoq_add")
-        self._grid_shapes.append([(int(arch.grid_h[g]), int(arch.grid_w[g])) for g in range(len(latent_ptrs))])
-        if owner is not None:
-            self._owners.append(owner)
+        slot = check(lib().ccd_rdoq_add(self._h, C.byref(arch), int(frame_data_type), ptr_array(latent_ptrs)), "ccd_rdoq_add")
+        self._note_grids(arch, len(latent_ptrs))
+        self._keep(owner)  # (the device latents the slot uses at step())
         return slot
 
     def set_maps(self, slot: int, dd_ptrs: Sequence[Optional[int]], dbits_ptrs: Sequence[int], owner=None):
@@ -79,11 +57,8 @@ class RdoqStep:
         n = len(self._grid_shapes[int(slot)])
         if len(dd_ptrs) != n or len(dbits_ptrs) != n:
             raise ValueError(f"slot {slot} has {n} grids")
-        dd = (C.c_void_p * n)(*[int(p) if p else None for p in dd_ptrs])
-        db = (C.c_void_p * n)(*[int(p) if p else None for p in dbits_ptrs])
-        check(lib().ccd_rdoq_set_maps(self._h, int(slot), dd, db), "ccd_rdoq_set_maps")
-        if owner is not None:
-            self._owners.append(owner)
+        check(lib().ccd_rdoq_set_maps(self._h, int(slot), ptr_array(dd_ptrs), ptr_array(dbits_ptrs)), "ccd_rdoq_set_maps")
+        self._keep(owner)
 
     def step(self, kD: Sequence[float], kR: Sequence[float], min_gain: Sequence[float], grid_mask: Sequence[int], stream: int = 0):
         """Per-slot factors of the cost dD * kD + dBits * kR, the least gain of a candidate and the grids that may move (bit g).
@@ -107,8 +82,4 @@ class RdoqStep:
     def moves(self, slot: int, grid: int) -> _DevArray:
         """After step() + wait(): int8 [h][w] on the device, the move (-1, 0, +1) the step applied at every latent of the grid.
         Valid until the next step / close."""
-        ptr = C.c_void_p()
-        n = check(lib().ccd_rdoq_slot_moves(self._h, int(slot), int(grid), C.byref(ptr)), "ccd_rdoq_slot_moves")
-        h, w = self._grid_shapes[int(slot)][int(grid)]
-        assert h * w == n, "the architecture given to add() does not describe the grids the library derived"
-        return _DevArray(ptr.value or 0, (h, w), "|i1", self)
+        return self._grid_map("ccd_rdoq_slot_moves", slot, grid, "|i1")

@@ -542,3 +542,137 @@ def test_bench_refuses_a_variant_library_and_build_cleans_variants(tmp_path):
     assert lib_a in gone and obj_a in gone and lib_b not in gone
     assert not os.path.exists(lib_a) and not os.path.exists(obj_a) and os.path.exists(lib_b)
     assert os.path.exists(os.path.join(here, "libccd.so")) and os.path.isdir(os.path.join(here, "csrc", "_obj"))  # the product itself is never touched
+
+
+# What test_header_rederivation_refuses_a_layer_count_out_of_range runs in a fresh interpreter (an out-of-range count used to end
+# the process): per layer count one line with the codes of the six host-only entry points that re-derive a header from its
+# transmitted fields; "keep" = the fixture's own count, whose line also carries what the calls computed.
+_REDERIVE_CHILD = r"""
+import ctypes as C, json, sys
+import numpy as np
+from conftest import load_golden
+from oracle import oracle_py
+from cool_chic_amd import writer
+from cool_chic_amd._lib import CCHeader, lib
+
+bs, z, _ = load_golden("rgb192")
+hdr, nn, _lat = oracle_py.split_stream(bs)[1][0][1][0]
+arch = writer.parse_cc_header(hdr)
+lats = [np.ascontiguousarray(z[f"cc0.latent{g}"], dtype=np.int8) for g in range(arch.n_grids)]
+lat_ptrs = (C.c_void_p * len(lats))(*[a.ctypes.data for a in lats])
+L = lib()
+for n in sys.argv[1:]:
+    a = CCHeader.from_buffer_copy(arch)
+    if n != "keep":
+        a.n_layer_synthesis = int(n)
+    counts = (C.c_int64 * 8)()
+    codes = [L.ccd_network_layout(C.byref(a), counts)]
+    total = sum(counts) if codes[0] >= 0 else 1
+    values = np.zeros(total, np.int32)
+    pad, out = C.c_int32(-1), C.POINTER(C.c_uint8)()
+    codes.append(L.ccd_encode_network(C.byref(a), values.ctypes.data, total, C.byref(pad), C.byref(out)))
+    if codes[-1] >= 0:
+        L.ccd_free(out)
+    out = C.POINTER(C.c_uint8)()
+    codes.append(L.ccd_encode_coolchic(C.byref(a), nn, len(nn), lat_ptrs, C.byref(out)))
+    if codes[-1] >= 0:
+        L.ccd_free(out)
+    box, cells = (C.c_int32 * 4)(), (C.c_int32 * 4)()
+    codes.append(L.ccd_latent_footprint(C.byref(a), 0, box))
+    codes.append(L.ccd_latent_probe_stride(C.byref(a), 0, 0))
+    codes.append(L.ccd_rdoq_influence_box(C.byref(a), 0, 0, 3, 5, cells))
+    print(json.dumps({"n": n, "codes": codes, "counts": list(counts), "pad": pad.value, "box": list(box), "cells": list(cells)}), flush=True)
+"""
+
+
+def test_header_rederivation_refuses_a_layer_count_out_of_range():
+    """The entry points that re-derive a header from its transmitted fields (rederive_cc_header) refuse n_layer_synthesis outside
+    1 .. CCD_MAX_SYN_LAYERS before anything walks syn_layer[8] - the three writer calls used to read past the array, and
+    2147483647 ended the process - and answer a valid header as before: the values below were recorded from the commit before
+    the shared function existed."""
+    import json
+    import subprocess
+    import sys
+
+    bad = ["-1", "0", "9", "1000", "2147483647"]
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    r = subprocess.run([sys.executable, "-s", "-c", _REDERIVE_CHILD, "keep"] + bad, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
+    lines = [json.loads(s) for s in r.stdout.splitlines() if s.startswith("{")]
+    assert [d["n"] for d in lines] == ["keep"] + bad
+    for d in lines[1:]:
+        assert len(d["codes"]) == 6 and all(c < 0 for c in d["codes"]), d
+    keep = lines[0]
+    # layout OK; 284 bytes of network for all-zero values, 4 bits of padding; 3066 bytes of cool-chic; footprint OK; stride 9; box OK
+    assert keep["codes"] == [0, 284, 3066, 0, 9, 0]
+    assert keep["counts"] == [160, 20, 48, 6, 48, 12, 191, 20]
+    assert keep["pad"] == 4 and keep["box"] == [-4, -4, 4, 4] and keep["cells"] == [0, 0, 0, 1]
+
+
+def test_handle_base_closes_once_and_releases_its_owners():
+    """_Handle, the base of the six handle wrappers, without a device: create and destroy are stubs that count their calls."""
+    import gc
+    import weakref
+
+    from cool_chic_amd._handle import _Handle, ptr_array
+
+    class Library:
+        created, destroyed = [], []
+
+        def stub_create(self, device, extra, ref):
+            ref._obj.value = 0x1000 + len(self.created)  # (what C.byref wraps: the wrapper's own c_void_p)
+            self.created.append((device, extra))
+            return 0
+
+        def stub_destroy(self, h):
+            self.destroyed.append(h.value)
+
+    fake = Library()
+
+    class Owner:
+        pass
+
+    class Stub(_Handle):
+        _destroy = "stub_destroy"
+        _library = staticmethod(lambda: fake)
+
+        def __init__(self, device=0, fail_early=False):
+            if fail_early:
+                raise ValueError("before the handle exists")
+            self._open("stub_create", device, 7)
+
+    s = Stub(3)
+    assert fake.created == [(3, 7)] and s.device == 3 and s._h.value == 0x1000
+    owner = Owner()
+    alive = weakref.ref(owner)
+    s._keep(owner)
+    s._keep(None)
+    del owner
+    gc.collect()
+    assert alive() is not None and len(s._owners) == 1
+    s.close()
+    s.close()
+    assert fake.destroyed == [0x1000] and not s._h.value
+    gc.collect()
+    assert alive() is None and s._owners == []  # close() let go of what the handle kept alive
+    with Stub(1) as t:
+        assert t._h.value == 0x1001 and fake.destroyed == [0x1000]
+    assert fake.destroyed == [0x1000, 0x1001]
+    del t, s
+    gc.collect()
+    assert fake.destroyed == [0x1000, 0x1001]  # collecting a closed handle destroys nothing again
+    u = Stub(2)
+    del u
+    gc.collect()
+    assert fake.destroyed == [0x1000, 0x1001, 0x1002]  # ... and an open one is closed
+    with pytest.raises(ValueError):
+        Stub(fail_early=True)
+    broken = Stub.__new__(Stub)  # what such an __init__ leaves behind: no _h at all
+    broken.close()
+    broken.__del__()
+    del broken
+    gc.collect()
+    assert len(fake.destroyed) == 3
+    arr = ptr_array([5, None, 0, 9])
+    assert len(arr) == 4 and [arr[i] for i in range(4)] == [5, None, None, 9]  # (ctypes reads a NULL c_void_p back as None)
+    assert len(ptr_array([])) == 0
