@@ -54,39 +54,13 @@ def configs():
 
 
 def build_stream(donor, donor_ints, latents, dim, n_hidden, n_ifce, seed):
-    """Stream with `dim` ARM inputs (dim - n_ifce spatial contexts), `n_hidden` hidden layers, IFCE on every grid pair or off."""
-    rng = np.random.default_rng(seed)
+    """Stream with `dim` ARM inputs (dim - n_ifce spatial contexts), `n_hidden` hidden layers, IFCE on every grid pair or off.
+    The drawing rule lives in tests/arm_layouts.py, which the layout tests build their cases with as well."""
+    import arm_layouts
+
     # 32 x 320: wavefront steps of up to 32 / 16 / 8 pixels on the three finest grids, i.e. the producers' 8-, 4- and 2-pixel tasks
     # all run (ccd_entropy_pipe.hip: n_max >= 25 / >= 9 / else), with 13.6 k symbols per stream
-    changes = dict(spatial_context_arm=dim - n_ifce, n_hidden_layers_arm=n_hidden, output_feature_ifce=n_ifce, img_size=IMG_SIZE)
-    if n_ifce == 0:
-        changes.update(has_ifce_resolution=0)
-    arch = writer.derive_arch(donor, **changes)
-    assert arch.total_context_arm == dim
-    dl, al = writer.network_layout(donor), writer.network_layout(arch)
-    d = np.split(np.asarray(donor_ints, dtype=np.int64), np.cumsum(dl)[:-1])
-    out = []
-    for k in range(8):
-        if k >= 4:  # upsampling / synthesis: the donor's trained float path, unchanged
-            assert al[k] == dl[k]
-            out.append(d[k])
-        elif al[k] == 0:
-            out.append(np.zeros(0, np.int64))
-        else:
-            # values drawn from the trained parameters of the same kind; hidden-layer weights shrink with the width so that the
-            # residual layers keep activations (and so mu / scale) in the trained range
-            v = rng.choice(d[k], size=al[k]).astype(np.float64)
-            if k == 0:
-                v *= 0.2 * min(1.0, (donor.total_context_arm / dim) ** 0.5)
-            if k == 1:  # arm.b = hidden layers, output layer (mu, log-scale), stabiliser: the trained output biases keep the
-                # predicted distributions (and so the stream sizes) near the donor's
-                n_tail = 4 if arch.linear_stabiliser_arm else 2
-                v[-n_tail:] = d[k][-n_tail:]
-            out.append(np.round(v).astype(np.int64))
-    ints = np.concatenate(out).astype(np.int32)
-    nn = writer.encode_network(arch, ints)
-    lat = writer.tile_latents(latents, donor, arch)
-    stream = writer.encode_stream(writer.cc_header_bytes(arch), nn, lat, bitdepth=8, frame_data_type=0)
+    stream, lat, _ = arm_layouts.build_stream(donor, donor_ints, latents, dim, n_hidden, n_ifce, seed, img_size=IMG_SIZE)
     return stream, lat
 
 

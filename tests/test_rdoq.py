@@ -29,12 +29,26 @@ PRIORITY = [38, 35, 30, 25, 23, 31, 36, 37, 39, 33, 28, 21, 20, 6, 15, 22, 29, 3
             12, 10, 5, 9, 14, 19, 27, 24, 13, 8, 2, 1, 3, 11, 17, 26, 16, 7, 4, 0]
 
 
+# architectures derived from rgb192 (tests/arm_layouts.py): (spatial contexts, IFCE features), (H, W), ifce_resolution (None: the
+# donor's (0, 2)) - 1 .. 40 contexts with 0 .. 31 features at two odd sizes, and IFCE on the coarse grids / on one level's pair
+DERIVED = {f"s{sp}_i{fe}_{h}x{w}": ((sp, fe), (h, w), None) for sp, fe in ((1, 0), (24, 7), (40, 31), (40, 0)) for h, w in ((37, 100), (65, 18))}
+DERIVED.update({"s6_i3_37x100_ifce3_15": ((6, 3), (37, 100), (3, 15)), "s9_i7_65x18_ifce4_4": ((9, 7), (65, 18), (4, 4))})
+
+
 def _arch(name):
-    """(arch with derived geometry, NN payload, bitdepth, frame_data_type, latent payload, header bytes) of an image fixture."""
+    """(arch with derived geometry, NN payload, bitdepth, frame_data_type, latent payload, header bytes) of an image fixture or
+    of a derived architecture of DERIVED."""
     from cool_chic_amd import writer
     from oracle import oracle_py
 
-    _, frames = oracle_py.split_stream(load_golden(name)[0])
+    if name in DERIVED:
+        import arm_layouts
+
+        (n_sp, n_if), size, res = DERIVED[name]
+        stream, _, _ = arm_layouts.build_stream(*arm_layouts.donor(), n_sp + n_if, 1, n_if, seed=len(name), img_size=size, ifce_resolution=res)
+    else:
+        stream = load_golden(name)[0]
+    _, frames = oracle_py.split_stream(stream)
     (fh, ccs), = frames
     hdr, nn, payload = ccs[0]
     return writer.parse_cc_header(hdr), nn, fh.bitdepth, fh.frame_data_type, payload, hdr
@@ -240,7 +254,7 @@ def _pairs(geo, g1, g2, rng):
     return [(divmod(i, w1), divmod(j, w2)) for i, j in pairs if g1 != g2 or i != j]
 
 
-@pytest.mark.parametrize("name", GEOMETRY)
+@pytest.mark.parametrize("name", GEOMETRY + list(DERIVED))
 def test_boxes_without_a_common_cell_are_independent(name):
     geo = _geo(name)
     boxes = geo.boxes()
@@ -275,7 +289,7 @@ def test_boxes_without_a_common_cell_are_independent(name):
     assert n_disjoint >= 1 and n_meeting >= 1 and n_adjacent >= 1
 
 
-@pytest.mark.parametrize("name", GEOMETRY)
+@pytest.mark.parametrize("name", GEOMETRY + list(DERIVED))
 def test_boxes_are_the_contract_clipped_not_shifted(name):
     geo = _geo(name)
     boxes = geo.boxes()
