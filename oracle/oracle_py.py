@@ -114,6 +114,10 @@ def lib():
         L.ora_inter_reconstruct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int,
                                             C.POINTER(C.c_void_p)]
+        L.ora_debug_cr_noise.argtypes = [C.c_void_p, C.c_size_t]
+        L.ora_debug_cr_noise.restype = None
+        L.ora_debug_resize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+        L.ora_debug_resize.restype = None
         L.ora_rc_encoder_new.restype = C.c_void_p
         L.ora_rc_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.ora_rc_encode.restype = None
@@ -282,6 +286,25 @@ def inter_reconstruct(frame_type, residue: np.ndarray, motion: np.ndarray, ref0,
         err = OracleError(f"ora_inter_reconstruct failed: {rc}")
         err.code = rc
         raise err
+    return out
+
+
+def debug_cr_noise(n: int) -> np.ndarray:
+    """The first n common-randomness samples (section 9c of cc_oracle.c), float32."""
+    out = np.zeros(int(n), np.float32)
+    lib().ora_debug_cr_noise(out.ctypes.data, int(n))
+    return out
+
+
+def debug_resize(x: np.ndarray, size, cubic: bool, scale=None) -> np.ndarray:
+    """resize_interp of cc_oracle.c (section 9b) on [c][h][w] float32: bilinear / bicubic to `size`, scale = in / out per axis
+    unless given (the x2 steps of the noise chain pass (0.5, 0.5))."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    c, h, w = x.shape
+    H, W = int(size[0]), int(size[1])
+    sy, sx = scale if scale is not None else (np.float32(h) / np.float32(H), np.float32(w) / np.float32(W))
+    out = np.zeros((c, H, W), np.float32)
+    lib().ora_debug_resize(x.ctypes.data, c, h, w, out.ctypes.data, H, W, int(bool(cubic)), float(sy), float(sx))
     return out
 
 

@@ -32,7 +32,8 @@ def main():
     variants = {
         # noise planes next to the latent planes (coolchic.py:179-183)
         "cr192": dict(flag_common_randomness=1),
-        # finest latent at 1/2 resolution, odd picture size: bicubic resize with a non-integer scale
+        # finest latent at 1/2 resolution: bicubic resize of the 63 x 95 dense grid to 126 x 190, exactly x2 on both axes
+        # (non-integer scales: bilinear190 below, and the derived pictures of tests/float_tail.py)
         "bicubic190": dict(img_size=(126, 190), latent_resolution=(1, 6), n_latent_grids=9, final_upsampling_type=2),
         # finest latent at 1/4 resolution, bilinear resize
         "bilinear190": dict(img_size=(126, 190), latent_resolution=(2, 6), n_latent_grids=8, final_upsampling_type=1),
