@@ -125,6 +125,14 @@ static_assert(offsetof(RowMeta, cell) - offsetof(RowMeta, top) == 520 && offseto
 extern __shared__ __attribute__((aligned(16))) unsigned char ccd_pipe_smem[];
 template <typename T>
 __device__ __forceinline__ T* smem_at(uint32_t off) { return reinterpret_cast<T*>(ccd_pipe_smem + off); }
+// An LDS address as a 32-bit value (one that can be pinned in a VGPR ahead of its use), and back
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
+}
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(3))) T* lds_at(uint32_t addr) {
+    return reinterpret_cast<__attribute__((address_space(3))) T*>(static_cast<uintptr_t>(addr));
+}
 template <typename T>
 struct LdsRef {
     uint32_t off;
@@ -1040,6 +1048,11 @@ __device__ __forceinline__ void mad64(int64_t& acc, int32_t x, int32_t w) {
     acc += static_cast<int64_t>(x) * static_cast<int64_t>(w);
     asm("" : "+v"(acc));
 }
+// ReLU of a Q16 accumulator as the next layer's input, (a < 0 ? 0 : a) >> 16 in 32 bits, with the sign as an and-mask: a compare
+// goes through VCC, and the select that reads VCC within two slots of the compare gets s_nop from the hazard recogniser
+__device__ __forceinline__ int32_t relu_q16(int64_t a) {
+    return static_cast<int32_t>(a >> 16) & ~static_cast<int32_t>(a >> 63);
+}
 #define CCD_MAD4(ACC, X, Wv, NCH)                                                   \
     _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64(ACC[g_], (X).x, Wv[g_].x); \
     _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64(ACC[g_], (X).y, Wv[g_].y); \
@@ -1048,6 +1061,25 @@ __device__ __forceinline__ void mad64(int64_t& acc, int32_t x, int32_t w) {
 // one output per lane (2-pixel tasks): a second partial sum, so that no multiply-add directly follows the one it depends on
 #define CCD_MAD4_PAIR(ACC, ACC2, X, Wv)                                             \
     mad64(ACC[0], (X).x, Wv[0].x); mad64(ACC2, (X).y, Wv[0].y); mad64(ACC[0], (X).z, Wv[0].z); mad64(ACC2, (X).w, Wv[0].w);
+// The late path (the layers behind the first one, the output layer) pays an issue slot for every s_nop.  The hazard recogniser
+// treats the empty asm as an instruction of unknown kind that wrote the accumulator and wants one instruction between it and the
+// next reader; the scheduler, free to move the asm statements, bunches them in front of a multiply-add that then gets its
+// s_nop (about one per three multiply-adds, whatever the number of chains).  mad64_seq fixes the order instead: multiply-add,
+// its pin, then the next chain's - with two or more chains in rotation no multiply-add stands right behind its own pin.
+__device__ __forceinline__ void mad64_seq(int64_t& acc, int32_t x, int32_t w) {
+    mad64(acc, x, w);
+    __builtin_amdgcn_sched_barrier(0);
+}
+#define CCD_MAD4_SEQ(ACC, X, Wv, NCH)                                               \
+    _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64_seq(ACC[g_], (X).x, Wv[g_].x); \
+    _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64_seq(ACC[g_], (X).y, Wv[g_].y); \
+    _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64_seq(ACC[g_], (X).z, Wv[g_].z); \
+    _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64_seq(ACC[g_], (X).w, Wv[g_].w);
+#define CCD_MAD4_PAIR_SEQ(ACC, ACC2, X, Wv)                                         \
+    mad64_seq(ACC[0], (X).x, Wv[0].x); mad64_seq(ACC2, (X).y, Wv[0].y); mad64_seq(ACC[0], (X).z, Wv[0].z); mad64_seq(ACC2, (X).w, Wv[0].w);
+// four partial sums, one per component (the output layer; wrapping int64 addition is associative: the same bits)
+#define CCD_MAD4_QUAD_SEQ(A4, X, W4)                                                \
+    mad64_seq(A4[0], (X).x, (W4).x); mad64_seq(A4[1], (X).y, (W4).y); mad64_seq(A4[2], (X).z, (W4).z); mad64_seq(A4[3], (X).w, (W4).w);
 
 
 // ---- the ARM on the matrix cores (MF = true) ---------------------------------------------------------------------------
@@ -1447,6 +1479,12 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 unsigned long long lt_a = 0, lt_b = 0, lt_c = 0, lt_d = 0;  // level-2 profile stamps
                 (void)lt_a; (void)lt_b; (void)lt_c; (void)lt_d;
                 unsigned narrow_mask = 0;  // matrix-core path: bit i: pixel i of the task is narrow (wave-uniform)
+                // vector-ALU path: the LDS addresses this lane's window passes read (mu index, reciprocal) and write (table entry, top
+                // symbol), pass k = pixels 4 k .. 4 k + 3 of the task; worked out before the late wait
+                constexpr int kPasses = (kTaskPix + 3) / 4;
+                uint32_t win_mu[kPasses] = {}, win_rcp[kPasses] = {}, win_ent[kPasses] = {}, win_top[kPasses] = {};
+                uint32_t win_left_m = 0, win_keep_m = 0, win_e0 = 0, win_e1 = 0;  // the entry's role (sentinel, window top) as masks / addend
+                (void)win_mu; (void)win_rcp; (void)win_ent; (void)win_top; (void)win_left_m; (void)win_keep_m; (void)win_e0; (void)win_e1;
                 unsigned long long wide_lanes = 0ull;  // vector-ALU path: ballot of the log-scale lanes of the pixels that are not
                 RowMeta& meta = *C.s_meta;
                 if constexpr (MF) {
@@ -1763,6 +1801,38 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // reached `need_px` vouches for the cell read behind it; otherwise both are read again in the polling loop.
                 // Unconditional read (cell of column -1 for x = 0: in bounds, dropped by the select), no exec mask.
                 int32_t xleft = 0;
+                // Role constants of the output tail, as VGPRs and BEFORE the late wait: where this lane's table index and reciprocal
+                // go (the dummy entry kRows for a lane that has nothing to say), what it reads the reciprocal table with, and the
+                // scale index above which it reports a wide window.  Left to the compiler they were SGPR-pair masks (q == 0,
+                // q == 1, live) that did not fit the scalar file: spilled, and reloaded with v_readlane on the late path.
+                const int mpx = slot * kBpx + half * kTaskPix + px;  // table row of the pixel
+                uint32_t mu_dst = lds_addr(&meta.mu_idx[px < cnt && q == 0 ? mpx : kRows]);
+                uint32_t rcp_dst = lds_addr(&meta.rcp[px < cnt && q == 1 ? mpx : kRows]);
+                int32_t rcp_lanes = q == 1 ? -1 : 0, wide_above = px < cnt && q == 1 ? kNarrowMaxScale : 0x7fffffff;
+                asm volatile("" : "+v"(mu_dst), "+v"(rcp_dst), "+v"(rcp_lanes), "+v"(wide_above));
+                // ... and of the window passes: the selects and address arithmetic of a pass (which pixel, does it exist, its rows)
+                // were a fifth of its instructions, all of them known here.  Sub-wave u = lane >> 4 builds pixel 4 k + u, entry
+                // e = lane & 15; a lane whose pixel does not exist reads the pass's first pixel and stores to the dummy rows
+                // (address selects instead of exec-masked stores, see RowMeta).
+#pragma unroll
+                for (int k = 0; k < kPasses; ++k) {
+                    const int u = lane >> 4, e = lane & 15;
+                    const int mine = 4 * k + u;
+                    const bool valid = mine < cnt;
+                    const int mi = slot * kBpx + half * kTaskPix + (valid ? mine : 4 * k);
+                    win_mu[k] = lds_addr(&meta.mu_idx[mi]);
+                    win_rcp[k] = lds_addr(&meta.rcp[mi]);
+                    win_ent[k] = lds_addr(&C.s_tab[static_cast<size_t>(valid ? mi : kRows) * 64 + e]);
+                    win_top[k] = lds_addr(&meta.top[valid && e == 0 ? mi : kRows]);
+                    asm volatile("" : "+v"(win_mu[k]), "+v"(win_rcp[k]), "+v"(win_ent[k]), "+v"(win_top[k]));
+                }
+                // entry 15 is the lower sentinel (left = 0), entries 0 and 15 have P = 0, entry 0 is the upper sentinel (2^24 - 1 when
+                // its symbol is 64), entry 1 the window's top symbol
+                win_left_m = (lane & 15) == 15 ? 0u : ~0u;
+                win_keep_m = ((lane & 15) == 0 || (lane & 15) == 15) ? 0u : ~0u;
+                win_e0 = (lane & 15) == 0 ? (1u << kRcPrecision) - 1u : 0u;
+                win_e1 = (lane & 15) == 1 ? 1u : 0u;
+                asm volatile("" : "+v"(win_left_m), "+v"(win_keep_m), "+v"(win_e0), "+v"(win_e1));
                 lt_c = LPROF_T(pw == 0);
                 if (split) {
                     const unsigned long long t0 = PROF_T();
@@ -1802,9 +1872,10 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     for (int t = 0; t < NOUT; ++t) {
                         mad64(acc0[t], xleft, wleft[t]);
                         const int o = q + kLpp * t;
-                        const int64_t a = acc0[t] < 0 ? 0 : acc0[t];
-                        int32_t* const dst = o < in_pad ? act + px * in_pad + o : act_dummy;
-                        *dst = o < dim ? static_cast<int32_t>(a >> 16) : 0;
+                        // a lane without a real output stores to the dummy words (address select, constant over the grid): the
+                        // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
+                        int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
+                        *dst = relu_q16(acc0[t]);
                     }
 #pragma unroll
                     for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
@@ -1830,7 +1901,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
 #pragma unroll
                             for (int t = 0; t < NOUT; ++t) wn[t] = wr[t][v + 1];
                         }
-                        if constexpr (NOUT == 1) { CCD_MAD4_PAIR(acc, acc_b, xv[v], w) } else { CCD_MAD4(acc, xv[v], w, NOUT) }
+                        if constexpr (NOUT == 1) { CCD_MAD4_PAIR_SEQ(acc, acc_b, xv[v], w) } else { CCD_MAD4_SEQ(acc, xv[v], w, NOUT) }
 #pragma unroll
                         for (int t = 0; t < NOUT; ++t) w[t] = wn[t];
                     }
@@ -1838,9 +1909,10 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
 #pragma unroll
                     for (int t = 0; t < NOUT; ++t) {
                         const int o = q + kLpp * t;
-                        const int64_t a = acc[t] < 0 ? 0 : acc[t];
-                        int32_t* const dst = o < in_pad ? act + px * in_pad + o : act_dummy;
-                        *dst = o < dim ? static_cast<int32_t>(a >> 16) : 0;
+                        // a lane without a real output stores to the dummy words (address select, constant over the grid): the
+                        // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
+                        int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
+                        *dst = relu_q16(acc[t]);
                     }
 #pragma unroll
                     for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
@@ -1848,28 +1920,23 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 PROF_ADD(prof[6], t_h);
                 const unsigned long long t_o = PROF_T();
                 // output layer (q = 0: mu, q = 1: log-scale) -> table indices -> per-pixel table parameters
-                const int mpx = slot * kBpx + half * kTaskPix + px;  // table row of the pixel
                 int32_t idx = 0;
                 {   // (every lane: lanes q >= 2 compute a discarded copy of row 1, like the stabiliser - no exec mask around the block)
                     const int4* wr = reinterpret_cast<const int4*>(C.s_w + C.n_w_hidden + qs * in_pad);
-                    int64_t ao[2] = {C.s_b[(n_layers - 1) * dim + qs] + stab, 0};
+                    int64_t ao[4] = {C.s_b[(n_layers - 1) * dim + qs] + stab, 0, 0, 0};
                     int4 wv[NV];
 #pragma unroll
                     for (int v = 0; v < NV; ++v) wv[v] = wr[v];
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) {
-                        const int4 w = wv[v];
-                        mad64(ao[0], xv[v].x, w.x); mad64(ao[1], xv[v].y, w.y); mad64(ao[0], xv[v].z, w.z); mad64(ao[1], xv[v].w, w.w);
-                    }
-                    const int64_t acc = ao[0] + ao[1];
+                    for (int v = 0; v < NV; ++v) { CCD_MAD4_QUAD_SEQ(ao, xv[v], wv[v]) }
+                    const int64_t acc = (ao[0] + ao[1]) + (ao[2] + ao[3]);
                     const int64_t q8 = acc >> 24;
                     const int64_t off = q8 + (q == 0 ? kMuOffset : kScaleOffset);
                     const int64_t hi = q == 0 ? kNumMu - 1 : kNumScale - 1;
                     idx = static_cast<int32_t>(off < 0 ? 0 : (off > hi ? hi : off));
                     // both stores by address select (dummy entry kRows for the lanes that have nothing to say): no exec mask, no branch
-                    const bool live = px < cnt;
-                    meta.mu_idx[live && q == 0 ? mpx : kRows] = idx;
-                    meta.rcp[live && q == 1 ? mpx : kRows] = C.s_rcp[q == 1 ? idx : 0];
+                    *lds_at<int32_t>(mu_dst) = idx;
+                    *lds_at<double>(rcp_dst) = C.s_rcp[idx & rcp_lanes];
                 }
                 // ---- a feature of some pixel was not exact in 16 bits (never on the streams seen so far): that pixel again,
                 // in plain int64; its table parameters replace what the lines above wrote from the sentinel
@@ -1902,7 +1969,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // bit (px * kLpp + 1) of the ballot: pixel px of the task takes a narrow window (wave-uniform, no LDS trip)
                 // lanes (px * kLpp + 1) of pixels that need the wide window (scale index above kNarrowMaxScale: 0.7 % of the symbols);
                 // the common path only tests the ballot for zero
-                wide_lanes = __ballot(q == 1 && px < cnt && idx > kNarrowMaxScale);
+                wide_lanes = __ballot(idx > wide_above);
                 PROF_ADD(prof[2], t_m);
                 PROF_ADD(prof[7], t_o);
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE >= 3
@@ -1918,31 +1985,34 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 if constexpr (!MF) {
                     // Static layout: pass k builds the 14-symbol windows of pixels 4 k .. 4 k + 3, narrow or not (99.3 % are;
                     // the row of a wide pixel is rewritten in full below) - no bit-scanning of the mask on the late path.
-                    for (int p4 = 0; p4 < cnt; p4 += 4) {
-                        const int u = lane >> 4, e = lane & 15;
-                        const int mine = p4 + u;
-                        const bool valid = mine < cnt;
-                        const int mi = base + (valid ? mine : p4);
-                        const int mu_idx = meta.mu_idx[mi];
+#pragma unroll
+                    for (int k = 0; k < kPasses; ++k) {
+                        if (k > 0 && 4 * k >= cnt) break;
+                        const int e = lane & 15;
+                        const int mu_idx = *lds_at<int32_t>(win_mu[k]);
+                        const double rcp256 = window_rcp256(*lds_at<double>(win_rcp[k]));
                         int top = ((mu_idx + 128) >> 8) - 64 + 6;  // round(mu) + 6: window = [round(mu) - 7, round(mu) + 6]
                         top = max(kAcLo + 13, min(kAcLo + kAlphabet - 1, top));
-                        const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
                         const int ssym = top - (e - 1);  // e = 0 -> top + 1: its left bound is the window's upper edge
-                        uint32_t left = min(window_left(mu, meta.rcp[mi], ssym, C.s_exp), (1u << kRcPrecision) - 1u);
-                        left = e == 15 ? 0u : left;
+                        // window_left's edge cases from integers, ahead of the f64 chain and without compares next to their selects:
+                        // symbols <= -64 (and the lower sentinel) give 0; symbol 64 - entry 0 of a window that reaches symbol 63 -
+                        // gives 2^24, stored as 2^24 - 1 (every stored bound must fit 24 bits, see the wide pass)
+                        const uint32_t lo_m = static_cast<uint32_t>((kAcLo - ssym) >> 31) & win_left_m;
+                        const bool at_top = top == kAcLo + kAlphabet - 1;
+                        const uint32_t hi_f = at_top ? win_e0 : 0u, to_full = at_top ? win_e1 : 0u;
+                        uint32_t left = window_cum_d256(window_d256(mu_idx, ssym), rcp256, C.s_exp) + static_cast<uint32_t>(ssym - kAcLo);
+                        left = (min(left, (1u << kRcPrecision) - 1u) | hi_f) & lo_m;
                         // entry e - 1 of the same 16-lane row (DPP row_shr:1; entry 0 does not use it)
                         const uint32_t right = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(left), 0x111, 0xf, 0xf, false));
                         uint2 ent;
                         ent.x = left;
-                        // P = right - left; the window's top entry of a window that reaches symbol 63 runs to 2^24; the two sentinels
-                        // get 0 - as arithmetic on selects (written with ?: inside ?: this compiled to three nested skip branches)
-                        const uint32_t to_full = (e == 1 && ssym == kAcLo + kAlphabet - 1) ? (1u << kRcPrecision) - right : 0u;
-                        const uint32_t keep = (e == 0 || e == 15) ? 0u : ~0u;
-                        ent.y = (right - left + to_full) & keep;
-                        // (address selects instead of exec-masked stores, see RowMeta)
-                        uint2* const row = valid ? tab + mine * 64 : C.s_tab + kRows * 64;
-                        row[e] = ent;
-                        meta.top[valid && e == 0 ? mi : kRows] = top;
+                        // P = right - left; the window's top entry of a window that reaches symbol 63 runs to 2^24: its right
+                        // neighbour (entry 0, symbol 64) holds the clamped 2^24 - 1, so the entry gets 1 more; the two sentinels get 0
+                        ent.y = (right - left + to_full) & win_keep_m;
+                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                        const u32x2 ent2 = {ent.x, ent.y};
+                        *lds_at<u32x2>(win_ent[k]) = ent2;
+                        *lds_at<int32_t>(win_top[k]) = top;
                     }
                 }
                 unsigned rest = MF ? narrow_mask : 0u;
@@ -2000,11 +2070,10 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     const int mu_idx = meta.mu_idx[mi];
                     int top = ((mu_idx + 128) >> 8) - 64 + 30;  // round(mu) + 30: window = [round(mu) - 31, round(mu) + 30]
                     top = max(kAcLo + 61, min(kAcLo + kAlphabet - 1, top));
-                    const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
                     const int ssym = top - (lane - 1);
                     // every stored bound must fit 24 bits (v_mad_u32_u24 in the decoder): the upper sentinel of a window that
                     // reaches symbol 63 is clamped to 2^24 - 1; a hit on it only costs a detour through the slow path
-                    uint32_t left = min(window_left(mu, meta.rcp[mi], ssym, C.s_exp), (1u << kRcPrecision) - 1u);
+                    uint32_t left = min(window_left_d256(window_d256(mu_idx, ssym), window_rcp256(meta.rcp[mi]), ssym, C.s_exp), (1u << kRcPrecision) - 1u);
                     left = lane == 63 ? 0u : left;
                     const uint32_t right = __shfl_up(left, 1);  // lane k-1 holds symbol s+1: its left bound is our right bound
                     uint2 ent;
@@ -2436,7 +2505,7 @@ bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narro
 }
 
 // ---- debug: every left cumulative the producers can compute for a run of scale indices -------------------------------
-// out[(c - scale_first) * 32768 * 127 + mu_idx * 127 + (s + 63)] = window_left(mu, b, rcp, s) for s = -63 .. 63 (s = -64 is 0
+// out[(c - scale_first) * 32768 * 127 + mu_idx * 127 + (s + 63)] = window_left_d256(256 (x - mu), rcp / 256, s) for s = -63 .. 63 (s = -64 is 0
 // and the right bound of s is the left bound of s + 1): 32768 x 2561 x 127 = 1.0658e10 values in all (tools/cdf_sweep.py).
 __global__ void laplace_sweep_pipe_kernel(const float* scale_table, const double* rcp_table, int scale_first, int n_scales, uint32_t* out) {
     const int64_t n = static_cast<int64_t>(n_scales) * kNumMu * 127;
@@ -2444,8 +2513,7 @@ __global__ void laplace_sweep_pipe_kernel(const float* scale_table, const double
         const int s = static_cast<int>(i % 127) - 63;
         const int64_t r = i / 127;
         const int mu_idx = static_cast<int>(r % kNumMu), c = scale_first + static_cast<int>(r / kNumMu);
-        const double mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
-        out[i] = window_left(mu, rcp_table[c], s, kExpTab);
+        out[i] = window_left_d256(window_d256(mu_idx, s), window_rcp256(rcp_table[c]), s, kExpTab);  // what the producers run
     }
 }
 hipError_t launch_laplace_sweep_pipe(const float* scale_table, const double* rcp_table, int scale_first, int n_scales, uint32_t* out, hipStream_t stream) {

@@ -64,4 +64,22 @@ __device__ __forceinline__ uint32_t window_left(double mu, double rcp, int s, co
     return s <= kAcLo ? 0u : (s > kAcLo + kAlphabet - 1 ? (1u << kRcPrecision) : v);
 }
 
+// The same boundary from integers, for the production kernel's table builder (the producers' late path pays per issued
+// instruction).  mu = -64 + mu_idx / 256 and x = s - 0.5, so d = x - mu = (256 s + 16256 - mu_idx) / 256: window_left forms mu,
+// x and d in f64 without a single rounding (every one a multiple of 2^-8 below 2^8), this forms 256 d with one integer
+// subtraction.  With rcp256 = rcp * 2^-8 (exact: rcp >= RN(1 / b_max) is nowhere near the subnormals) the product
+// |256 d| * rcp256 is RN of the same real number as |d| * rcp: same bits, and everything behind it is window_left's.
+__device__ __forceinline__ int window_d256(int mu_idx, int s) { return 256 * s + (256 * 64 - 128) - mu_idx; }
+__device__ __forceinline__ double window_rcp256(double rcp) { return ldexp(rcp, -8); }
+// floor(16777088 cdf) alone: a caller that knows where its symbols lie applies window_left's edge cases (s <= -64, s > 63) itself
+__device__ __forceinline__ uint32_t window_cum_d256(int d256, double rcp256, const double* exp_tab) {
+    const double e = exp_nonpos(-fabs(static_cast<double>(d256)) * rcp256, exp_tab);  // e^(-|x - mu| / b) / 2
+    const double cdf = d256 <= 0 ? e : 1.0 - e;
+    return static_cast<uint32_t>(16777088.0 * cdf);
+}
+__device__ __forceinline__ uint32_t window_left_d256(int d256, double rcp256, int s, const double* exp_tab) {
+    const uint32_t v = window_cum_d256(d256, rcp256, exp_tab) + static_cast<uint32_t>(s - kAcLo);
+    return s <= kAcLo ? 0u : (s > kAcLo + kAlphabet - 1 ? (1u << kRcPrecision) : v);
+}
+
 }  // namespace ccd
