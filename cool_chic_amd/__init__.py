@@ -20,6 +20,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    dsens.DistortionDeltas, RdEvaluator.cost_delta_map
     (no counterpart: a requantisation step that moves latents by +-1 where the moves provably add)
                                                    rdoq.RdoqStep, RdEvaluator.descend
+    (the same for the two cool-chics of a P / B frame, scored through the reconstruction against its references)
+                                                   DistortionDeltas.add_inter, rd_inter.InterRdEvaluator
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -31,6 +33,10 @@ def __getattr__(name):
         from .rd import RdEvaluator
 
         return RdEvaluator
+    if name == "InterRdEvaluator":
+        from .rd_inter import InterRdEvaluator
+
+        return InterRdEvaluator
     if name == "DistortionDeltas":
         from .dsens import DistortionDeltas
 

@@ -89,6 +89,11 @@ class RdoqResult(C.Structure):
                 ("n_moves_grid", C.c_int64 * MAX_GRIDS), ("d_sse", C.c_int64), ("d_bits", C.c_double), ("d_cost", C.c_double)]
 
 
+class DsensInter(C.Structure):
+    _fields_ = [("frame_type", C.c_int32), ("role", C.c_int32), ("partner", C.c_void_p), ("ref0", C.c_void_p * 3), ("ref1", C.c_void_p * 3),
+                ("global_flow", C.c_int32 * 4), ("warp_filter_size", C.c_int32)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -192,6 +197,8 @@ SIGNATURES = {
     "ccd_dsens_destroy": (None, [C.c_void_p]),
     "ccd_dsens_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.c_int, C.c_int]),
+    "ccd_dsens_add_inter": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                      C.c_int, C.c_int, C.POINTER(DsensInter)]),
     "ccd_dsens_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_dsens_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_dsens_slot_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

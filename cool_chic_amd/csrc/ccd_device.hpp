@@ -152,6 +152,26 @@ struct DsensPass {
     int32_t upp, rows;       // bands per probe, luma rows per band
     int32_t empty;
 };
+// One slot of an inter candidate as dsens_inter_kernel sees it (ccd_inter.hip): the float outputs of the frame's
+// two cool-chics - one of them a slot of the handle's batch, the other the caller's partner - go through the reconstruction of
+// inter_recon_kernel and the integer step of planes_kernel into planes the handle owns.  A workgroup is 64 x 4 units, a unit one
+// luma sample or, 4:2:0, one 2 x 2 luma quad and its chroma sample; the jobs of a launch share a prefix table of workgroups.
+struct DsensInterJob {
+    const float* residue;    // [4 | 5][H][W]
+    const float* motion;     // [2 | 4][H][W]
+    const float* ref0;       // [3][H][W] f32, launch_planes_to_444 of the reference's planes
+    const float* ref1;       // B frames
+    float* w0;               // [3][H][W] the warped reference: written by mode 0 (null: not kept), read by mode 1
+    float* w1;               // B frames
+    void* plane[3];          // u8 / u16 planes out
+    int32_t mode;            // 0 base: warp and keep, 1 residue probe: the kept warps, 2 motion probe: warp
+    int32_t frame_type, H, W, n_taps;
+    int32_t gflow[4];
+    int32_t chroma_shift;    // 1 for yuv420
+    int32_t wide;            // samples are u16
+    int32_t tiles_x;         // workgroups per row of workgroups
+    float maxv;              // 2^bitdepth - 1
+};
 constexpr uint32_t kDsensChunk = 4096;   // bytes one 64-lane workgroup of dsens_apply_kernel writes
 constexpr int kDsensBandSamples = 4096;  // luma samples of a band, about
 

@@ -1,5 +1,7 @@
 // ccd_dsens_api.cpp - ccd_dsens_* and ccd_latent_footprint of include/ccd.h: the host side of the distortion deltas
-// (DESIGN.md section 4.13).  Built on the public ccd_batch_* calls: the float path is the decode batch's, untouched.
+// (DESIGN.md sections 4.13, and 4.15 for the cool-chics of P / B frames).  Built on the public ccd_batch_* calls: the float path is
+// the decode batch's, untouched.
+#include <array>
 #include <cstring>
 #include <new>
 
@@ -102,14 +104,28 @@ struct Candidate {
     std::vector<PassPlan> passes;            // the float passes, grid by grid
     int status = CCD_OK;
     bool covered = false;                    // by a finished run
+    // one cool-chic of a P / B frame: its slots have no integer planes of their own, dsens_inter_kernel writes
+    // those of the FRAME into `inter_buf`, which also holds the references as f32 and, for a residue candidate, the warped ones
+    bool is_inter = false;
+    ccd_dsens_inter inter = {};
+    Block inter_buf;
+    float* ref_f32[2] = {};
+    float* warped[2] = {};
+    std::vector<std::array<void*, 3>> inter_planes;  // [0] base, [1 + k] probe slot k
     int8_t* copy(int k, int g) const { return priv.as<int8_t>() + static_cast<size_t>(k) * copy_bytes + grid_off[g]; }
     int64_t* map(int g) const { return reinterpret_cast<int64_t*>(maps.as<char>() + map_off[g]); }
 };
 
+struct InterLaunch {  // one launch of dsens_inter_kernel: offsets into the tables block
+    size_t jobs = 0, prefix = 0;
+    int n_jobs = 0;
+    uint32_t n_blocks = 0;
+};
 struct Round {  // offsets into the tables block
     size_t segs = 0, seg_prefix = 0, passes = 0, unit_prefix = 0, probe_prefix = 0;
     int n_segs = 0, n_passes = 0;
     uint32_t n_blocks = 0, n_units = 0, n_probes = 0;
+    InterLaunch probes[2];  // by kernel instantiation: [0] run-time taps, [1] sinc-8
 };
 }  // namespace
 
@@ -120,9 +136,11 @@ struct ccd_dsens {
     std::vector<Round> rounds;
     Mirror tables;
     Block slab;
+    InterLaunch inter_base[2];  // the base slots of the inter candidates, behind the first round's float path
     bool planned = false;   // the tables describe every candidate
     int pending = 0;        // a run is in flight
     int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
+    int stages = 7;         // ccd_dsens_debug_stages
     StreamSet streams;
 };
 
@@ -147,8 +165,8 @@ DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPla
     const Footprint& f = c.fp[g];
     for (int p = 0; p < 3; ++p) {
         int ph = 0, pw = 0;
-        P.base[p] = ccd_batch_plane(d->batch, c.base_slot, p, &ph, &pw);
-        P.probe[p] = ccd_batch_plane(d->batch, c.first_probe + k, p, &ph, &pw);
+        P.base[p] = c.is_inter ? c.inter_planes[0][p] : ccd_batch_plane(d->batch, c.base_slot, p, &ph, &pw);
+        P.probe[p] = c.is_inter ? c.inter_planes[1 + k][p] : ccd_batch_plane(d->batch, c.first_probe + k, p, &ph, &pw);
         P.src[p] = c.src[p];
     }
     P.stride = c.stride[g]; P.py = pp.py; P.px = pp.px;
@@ -163,7 +181,43 @@ DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPla
     return P;
 }
 
-// Every round's segments and passes, one block, one copy.
+// slot `which` (-1: the base slot, else probe slot k) of an inter candidate as dsens_inter_kernel reconstructs it
+DsensInterJob make_inter_job(const ccd_dsens* d, const Candidate& c, int which) {
+    DsensInterJob J;
+    std::memset(&J, 0, sizeof(J));
+    const float* own = ccd_batch_output(d->batch, which < 0 ? c.base_slot : c.first_probe + which);
+    J.residue = c.inter.role == 0 ? own : c.inter.partner;
+    J.motion = c.inter.role == 0 ? c.inter.partner : own;
+    const bool two = c.inter.frame_type == 2;
+    J.ref0 = c.ref_f32[0]; J.ref1 = two ? c.ref_f32[1] : c.ref_f32[0];
+    J.w0 = c.warped[0]; J.w1 = c.warped[1];
+    for (int p = 0; p < 3; ++p) J.plane[p] = c.inter_planes[which + 1][p];
+    J.mode = which < 0 ? 0 : (c.inter.role == 0 ? 1 : 2);
+    J.frame_type = c.inter.frame_type;
+    J.H = c.hdr.img_size[0]; J.W = c.hdr.img_size[1];
+    J.n_taps = c.inter.warp_filter_size;
+    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? c.inter.global_flow[i] : 0;
+    J.chroma_shift = c.frame_data_type == 1 ? 1 : 0;
+    J.wide = c.bitdepth > 8;
+    J.tiles_x = ((J.W >> J.chroma_shift) + 63) / 64;
+    J.maxv = static_cast<float>((1 << c.bitdepth) - 1);
+    return J;
+}
+
+int put_inter_launch(TableImage& img, const std::vector<DsensInterJob>& jobs, InterLaunch& L) {
+    std::vector<uint32_t> prefix(jobs.size() + 1, 0);
+    uint64_t blocks = 0;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        blocks += static_cast<uint64_t>(jobs[i].tiles_x) * (((jobs[i].H >> jobs[i].chroma_shift) + 3) / 4);
+        if (blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+        prefix[i + 1] = static_cast<uint32_t>(blocks);
+    }
+    L.n_jobs = static_cast<int>(jobs.size()); L.n_blocks = static_cast<uint32_t>(blocks);
+    L.jobs = img.put(jobs); L.prefix = img.put(prefix);
+    return CCD_OK;
+}
+
+// Every round's segments, passes and reconstruction jobs, one block, one copy.
 int build_tables(ccd_dsens* d, hipStream_t st) {
     const int K = d->K;
     size_t n_rounds = 1;
@@ -171,9 +225,19 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
     TableImage img;
     d->rounds.assign(n_rounds, Round{});
     uint32_t max_units = 1;
+    {
+        std::vector<DsensInterJob> base[2];
+        for (const auto& cp : d->cands)
+            if (cp->is_inter) base[cp->inter.warp_filter_size == 8].push_back(make_inter_job(d, *cp, -1));
+        for (int i = 0; i < 2; ++i) {
+            const int rc = put_inter_launch(img, base[i], d->inter_base[i]);
+            if (rc < 0) return rc;
+        }
+    }
     for (size_t r = 0; r < n_rounds; ++r) {
         std::vector<DsensSeg> segs;
         std::vector<DsensPass> passes;
+        std::vector<DsensInterJob> jobs[2];
         for (const auto& cp : d->cands) {
             const Candidate& c = *cp;
             const ccd_cc_header& h = c.hdr;
@@ -199,6 +263,7 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
                     if (prev && (!cur || cur->grid != prev->grid)) seg(k, prev->grid, nullptr);  // the grid moves on: restore
                 }
                 if (cur) passes.push_back(make_pass(d, c, k, *cur, false));
+                if (cur && c.is_inter) jobs[c.inter.warp_filter_size == 8].push_back(make_inter_job(d, c, k));
             }
             if (r == 0)
                 for (int g = 0; g < h.n_grids; ++g)
@@ -206,6 +271,10 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
                         for (int move = -1; move <= 1; move += 2) passes.push_back(make_pass(d, c, 0, PassPlan{g, 0, 0, move}, true));
         }
         Round& R = d->rounds[r];
+        for (int i = 0; i < 2; ++i) {
+            const int rc = put_inter_launch(img, jobs[i], R.probes[i]);
+            if (rc < 0) return rc;
+        }
         std::vector<uint32_t> seg_prefix(segs.size() + 1, 0), unit_prefix(passes.size() + 1, 0), probe_prefix(passes.size() + 1, 0);
         uint64_t blocks = 0, units = 0, probes = 0;
         for (size_t i = 0; i < segs.size(); ++i) { blocks += (segs[i].n + kDsensChunk - 1) / kDsensChunk; seg_prefix[i + 1] = static_cast<uint32_t>(blocks); }
@@ -279,14 +348,14 @@ void ccd_dsens_destroy(ccd_dsens* d) {
     (void)hipSetDevice(d->device);
     (void)d->streams.drain();
     ccd_batch_destroy(d->batch);  // drains the streams it was run on
-    for (auto& c : d->cands) { c->priv.drop(); c->maps.drop(); }
+    for (auto& c : d->cands) { c->priv.drop(); c->maps.drop(); c->inter_buf.drop(); }
     d->tables.drop(); d->slab.drop();
     delete d;
 }
 
-int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
-                  const void* const* src, int bitdepth, int frame_data_type) {
-    if (!d || !arch || !bytes_nn || !latents || !src || !src[0] || !src[1] || !src[2]) return CCD_ERR_ARG;
+// ccd_dsens_add and ccd_dsens_add_inter behind their pointer checks (inter: null for an intra candidate)
+static int add_candidate(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                         const void* const* src, int bitdepth, int frame_data_type, const ccd_dsens_inter* inter) {
     if (bitdepth < 8 || bitdepth > 16 || frame_data_type < 0 || frame_data_type > 2 || d->pending) return CCD_ERR_ARG;
     if (d->dead < 0) return d->dead;
     std::unique_ptr<Candidate> cp(new (std::nothrow) Candidate());
@@ -295,6 +364,15 @@ int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_
     if (rederive_cc_header(*arch, n_nn, &c.hdr) < 0) return CCD_ERR_VALUE;
     const ccd_cc_header& h = c.hdr;
     if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;
+    if (inter) {
+        const int taps = inter->warp_filter_size;
+        if (taps < 2 || taps > 16 || (taps & 1)) return CCD_ERR_VALUE;  // as ccd_inter_reconstruct
+        if (frame_data_type == 1 && ((h.img_size[0] | h.img_size[1]) & 1)) return CCD_ERR_VALUE;
+        const int want = inter->role == 0 ? (inter->frame_type == 2 ? 5 : 4) : (inter->frame_type == 2 ? 4 : 2);
+        if (h.out_channels != want) return CCD_ERR_VALUE;
+        c.is_inter = true;
+        c.inter = *inter;
+    }
     c.bitdepth = bitdepth;
     c.frame_data_type = frame_data_type;
     size_t map_bytes = 0;
@@ -317,23 +395,57 @@ int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_
     for (int p = 0; p < 3; ++p) c.src[p] = src[p];
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(d->device));
+    auto drop = [&c] { c.priv.drop(); c.maps.drop(); c.inter_buf.drop(); };
     if (!c.priv.get(d->device, BlockPool::kDevice, std::max<size_t>(256, c.copy_bytes * d->K)) ||
         !c.maps.get(d->device, BlockPool::kDevice, std::max<size_t>(256, map_bytes))) {
-        c.priv.drop(); c.maps.drop();
+        drop();
         return CCD_ERR_NOMEM;
     }
-    c.base_slot = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, latents, 1, bitdepth, frame_data_type);
-    if (c.base_slot < 0) { c.priv.drop(); c.maps.drop(); return c.base_slot; }  // (nothing was added to the batch)
+    if (inter) {  // [references as f32][warped references, residue candidates][planes of the base and the K probe slots]
+        const size_t hw = static_cast<size_t>(h.img_size[0]) * h.img_size[1], sample = bitdepth > 8 ? 2 : 1;
+        const size_t chw = frame_data_type == 1 ? static_cast<size_t>(h.img_size[0] / 2) * (h.img_size[1] / 2) : hw;
+        const size_t f32_3 = align256(3 * hw * sizeof(float)), luma = align256(hw * sample), chroma = align256(chw * sample);
+        const int n_refs = inter->frame_type == 2 ? 2 : 1, n_warped = inter->role == 0 ? n_refs : 0;
+        const size_t total = (n_refs + n_warped) * f32_3 + static_cast<size_t>(d->K + 1) * (luma + 2 * chroma);
+        if (!c.inter_buf.get(d->device, BlockPool::kDevice, total)) { drop(); return CCD_ERR_NOMEM; }
+        char* at = c.inter_buf.as<char>();
+        for (int r = 0; r < n_refs; ++r, at += f32_3) c.ref_f32[r] = reinterpret_cast<float*>(at);
+        for (int r = 0; r < n_warped; ++r, at += f32_3) c.warped[r] = reinterpret_cast<float*>(at);
+        c.inter_planes.resize(d->K + 1);
+        for (auto& pl : c.inter_planes) {
+            pl[0] = at; pl[1] = at + luma; pl[2] = at + luma + chroma;
+            at += luma + 2 * chroma;
+        }
+    }
+    // the slots of an inter cool-chic produce its float output only (as the decoder adds them): the planes are the frame's
+    const int slot_bitdepth = inter ? 0 : bitdepth;
+    c.base_slot = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, latents, 1, slot_bitdepth, frame_data_type);
+    if (c.base_slot < 0) { drop(); return c.base_slot; }  // (nothing was added to the batch)
     for (int k = 0; k < d->K; ++k) {
         const int8_t* ptrs[CCD_MAX_GRIDS];
         for (int g = 0; g < h.n_grids; ++g) ptrs[g] = c.copy(k, g);
-        const int s = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, ptrs, 1, bitdepth, frame_data_type);
-        if (s < 0) { c.priv.drop(); c.maps.drop(); d->dead = s; return s; }
+        const int s = ccd_batch_add_latents(d->batch, arch, bytes_nn, n_nn, ptrs, 1, slot_bitdepth, frame_data_type);
+        if (s < 0) { drop(); d->dead = s; return s; }
         if (k == 0) c.first_probe = s;
     }
     d->planned = false;
     d->cands.push_back(std::move(cp));
     return static_cast<int>(d->cands.size()) - 1;
+}
+
+int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                  const void* const* src, int bitdepth, int frame_data_type) {
+    if (!d || !arch || !bytes_nn || !latents || !src || !src[0] || !src[1] || !src[2]) return CCD_ERR_ARG;
+    return add_candidate(d, arch, bytes_nn, n_nn, latents, src, bitdepth, frame_data_type, nullptr);
+}
+
+int ccd_dsens_add_inter(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                        const void* const* src, int bitdepth, int frame_data_type, const ccd_dsens_inter* inter) {
+    if (!d || !arch || !bytes_nn || !latents || !src || !src[0] || !src[1] || !src[2] || !inter) return CCD_ERR_ARG;
+    if (inter->frame_type < 1 || inter->frame_type > 2 || inter->role < 0 || inter->role > 1 || !inter->partner) return CCD_ERR_ARG;
+    for (int p = 0; p < 3; ++p)
+        if (!inter->ref0[p] || (inter->frame_type == 2 && !inter->ref1[p])) return CCD_ERR_ARG;
+    return add_candidate(d, arch, bytes_nn, n_nn, latents, src, bitdepth, frame_data_type, inter);
 }
 
 int ccd_dsens_run(ccd_dsens* d, void* stream) {
@@ -349,15 +461,46 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
     }
     const char* base = d->tables.dev.as<char>();
     d->pending = 1;
-    for (const Round& R : d->rounds) {
-        HIP_TRY(launch_dsens_apply(reinterpret_cast<const DsensSeg*>(base + R.segs), reinterpret_cast<const uint32_t*>(base + R.seg_prefix), R.n_segs,
-                                   R.n_blocks, st));
-        const int rc = ccd_batch_run(d->batch, stream);
-        if (rc < 0) return rc;
-        HIP_TRY(launch_dsens_sse(reinterpret_cast<const DsensPass*>(base + R.passes), reinterpret_cast<const uint32_t*>(base + R.unit_prefix),
-                                 reinterpret_cast<const uint32_t*>(base + R.probe_prefix), R.n_passes, R.n_units, R.n_probes,
-                                 d->slab.as<int64_t>(), st));
+    auto reconstruct = [&](const InterLaunch (&L)[2]) -> int {  // one launch per kernel instantiation in use
+        for (int i = 0; i < 2; ++i)
+            if (launch_dsens_inter(reinterpret_cast<const DsensInterJob*>(base + L[i].jobs), reinterpret_cast<const uint32_t*>(base + L[i].prefix),
+                                   L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess) return CCD_ERR_HIP;
+        return CCD_OK;
+    };
+    for (const auto& cp : d->cands) {  // the references of the inter candidates as the warp reads them
+        const Candidate& c = *cp;
+        for (int r = 0; c.is_inter && r < (c.inter.frame_type == 2 ? 2 : 1); ++r) {
+            const void* const* pl = r ? c.inter.ref1 : c.inter.ref0;
+            HIP_TRY(launch_planes_to_444(pl[0], pl[1], pl[2], c.ref_f32[r], c.hdr.img_size[0], c.hdr.img_size[1], c.bitdepth, c.frame_data_type, st));
+        }
     }
+    bool first = true;
+    for (const Round& R : d->rounds) {
+        int rc = CCD_OK;
+        if (d->stages & 1) {
+            HIP_TRY(launch_dsens_apply(reinterpret_cast<const DsensSeg*>(base + R.segs), reinterpret_cast<const uint32_t*>(base + R.seg_prefix), R.n_segs,
+                                       R.n_blocks, st));
+            if ((rc = ccd_batch_run(d->batch, stream)) < 0) return rc;
+        }
+        if (first && (d->stages & 2) && (rc = reconstruct(d->inter_base)) < 0) return rc;  // the base planes, and the warped references they leave
+        first = false;
+        if ((d->stages & 2) && (rc = reconstruct(R.probes)) < 0) return rc;
+        if (d->stages & 4) {
+            HIP_TRY(launch_dsens_sse(reinterpret_cast<const DsensPass*>(base + R.passes), reinterpret_cast<const uint32_t*>(base + R.unit_prefix),
+                                     reinterpret_cast<const uint32_t*>(base + R.probe_prefix), R.n_passes, R.n_units, R.n_probes,
+                                     d->slab.as<int64_t>(), st));
+        }
+    }
+    return CCD_OK;
+}
+
+// Not part of include/ccd.h: the measurement hook of tools/rd_bench.py --inter, which looks the symbol up by name.  Which stages of
+// every round the following runs enqueue - bit 0 the float path (apply + ccd_batch_run), bit 1 the reconstruction launches of inter
+// candidates, bit 2 the squared-error split; 7 by default.  A run with another mask covers no slot: ccd_dsens_slot_map refuses
+// (CCD_ERR_ARG) until a full run has finished.
+int ccd_dsens_debug_stages(ccd_dsens* d, int mask) {
+    if (!d || d->pending || mask < 0 || mask > 7) return CCD_ERR_ARG;
+    d->stages = mask;
     return CCD_OK;
 }
 
@@ -379,7 +522,7 @@ int ccd_dsens_wait(ccd_dsens* d, void* stream) {
         Candidate& c = *cp;
         c.status = ccd_batch_slot_status(d->batch, c.base_slot);
         for (int k = 0; c.status == CCD_OK && k < d->K; ++k) c.status = ccd_batch_slot_status(d->batch, c.first_probe + k);
-        c.covered = true;
+        c.covered = d->stages == 7;
         if (first == CCD_OK && c.status != CCD_OK) first = c.status;
     }
     return first;

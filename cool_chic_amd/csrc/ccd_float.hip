@@ -18,6 +18,7 @@
 
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
+#include "ccd_planes.hpp"
 
 namespace ccd {
 
@@ -429,14 +430,7 @@ hipError_t launch_cr_noise(float* out, size_t n, hipStream_t stream) {
 // -------------------------------------------------------------------------------------------------
 // Integer planes of an intra frame (decode.py:191-206 + png.py:57-58 / yuv.py:152-160).
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float round_to_grid(float x, float maxv) { return rintf(maxv * x) / maxv; }
-
-__device__ __forceinline__ unsigned quantise_sample(float x, float maxv) {
-    float q = round_to_grid(x, maxv);
-    q = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
-    q = rintf(q * maxv) / maxv;
-    return static_cast<unsigned>(rintf(q * maxv));
-}
+// round_to_grid, quantise_sample: ccd_planes.hpp
 
 template <typename T>
 __global__ void planes_kernel(const float* __restrict__ src, T* p0, T* p1, T* p2, int h, int w, int yuv420, float maxv) {

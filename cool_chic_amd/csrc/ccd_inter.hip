@@ -14,6 +14,7 @@
 
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
+#include "ccd_planes.hpp"
 
 namespace ccd {
 
@@ -381,6 +382,114 @@ hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const in
     dim3 grid((w + 63) / 64, (h + 3) / 4);
     if (n_taps == 8) hipLaunchKernelGGL(inter_recon_kernel<8>, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(inter_recon_kernel<0>, grid, dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// ---- distortion deltas of P / B frames (ccd_dsens_add_inter): reconstruction and integer planes of every probe
+// slot of a round in one launch.  A job is one slot; its workgroups find it in a prefix table (entry_of), as the other dsens kernels
+// find their entries.  Per sample the operations of inter_recon_kernel (same device functions, multiply and add of the blend
+// separate) followed by those of planes_kernel (ccd_float.hip; the sample helpers are shared, ccd_planes.hpp: round to the bit-depth grid, clamp, round; 4:2:0 chroma = the
+// sequential f32 sum of the quad's rounded samples, / 4, clamp, round): the f32 that inter_recon_kernel stores and planes_kernel
+// loads is the register in between, so the planes are those of ccd_inter_reconstruct bit for bit.  What a residue probe cannot
+// change - the warped references - is computed by the base job of a run (mode 0), kept as f32 and only read by residue probes
+// (mode 1); a motion probe (mode 2) warps.  Every output word has one writer: a thread owns one luma sample or, 4:2:0, one 2 x 2
+// quad and its chroma sample.  Plain vector stores; no atomics, no waits, no LDS.
+__device__ __forceinline__ void di_store(void* plane, size_t at, unsigned v, int wide) {
+    if (wide) static_cast<uint16_t*>(plane)[at] = static_cast<uint16_t>(v);
+    else static_cast<uint8_t*>(plane)[at] = static_cast<uint8_t>(v);
+}
+
+template <int NT>
+__device__ __forceinline__ void di_warp(const DsensInterJob& J, const float* __restrict__ ref, int gx, int gy, float fx, float fy, int y, int x,
+                                        float out[3]) {
+    if constexpr (NT > 0) ic_warp_pixel_t<NT>(ref, J.H, J.W, gx, gy, fx, fy, y, x, out);
+    else if (J.n_taps < 6) ic_warp_pixel_native(ref, J.H, J.W, gx, gy, J.n_taps, fx, fy, y, x, out);
+    else ic_warp_pixel(ref, J.H, J.W, gx, gy, J.n_taps, fx, fy, y, x, out);
+}
+
+// the frame's float sample (y, x) of the three channels: inter_recon_kernel's body
+template <int NT>
+__device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, float out[3]) {
+    const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
+    float a = J.residue[3 * plane + i] + 0.5f;
+    a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
+    const bool two = J.frame_type == 2;
+    float w0[3] = {0.0f, 0.0f, 0.0f}, w1[3] = {0.0f, 0.0f, 0.0f}, pred[3];
+    if (J.mode == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { w0[c] = J.w0[c * plane + i]; if (two) w1[c] = J.w1[c * plane + i]; }
+    } else {
+        // one body for both references (the straight-line f64 evaluations of two inlined warps cost twice the registers); the
+        // selects keep w0 / w1 out of indexed private memory
+        const int n_refs = two ? 2 : 1;
+#pragma unroll 1
+        for (int r = 0; r < n_refs; ++r) {
+            float w[3];
+            di_warp<NT>(J, r ? J.ref1 : J.ref0, r ? J.gflow[2] : J.gflow[0], r ? J.gflow[3] : J.gflow[1], J.motion[(2 * r) * plane + i],
+                        J.motion[(2 * r + 1) * plane + i], y, x, w);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { w0[c] = r == 0 ? w[c] : w0[c]; w1[c] = r == 1 ? w[c] : w1[c]; }
+        }
+        if (J.mode == 0 && J.w0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { J.w0[c * plane + i] = w0[c]; if (two) J.w1[c * plane + i] = w1[c]; }
+        }
+    }
+    if (two) {
+        float b = J.residue[4 * plane + i] + 0.5f;
+        b = b < 0.0f ? 0.0f : (b > 1.0f ? 1.0f : b);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { const float t0 = b * w0[c], t1 = (1.0f - b) * w1[c]; pred[c] = t0 + t1; }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pred[c] = w0[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { const float m = a * pred[c]; out[c] = m + J.residue[c * plane + i]; }
+}
+
+template <int NT>  // as inter_recon_kernel: 8 = the sinc-8 warp of every preset, 0 = a run-time tap count and the native paths
+__global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+    const uint32_t blk = blockIdx.x;
+    const int j = entry_of(prefix, n_jobs, blk);
+    const DsensInterJob J = jobs[j];  // (uniform: scalar registers)
+    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
+    const int ux = static_cast<int>(local % tiles_x) * 64 + (threadIdx.x & 63);
+    const int uy = static_cast<int>(local / tiles_x) * 4 + (threadIdx.x >> 6);
+    const int cs = J.chroma_shift;
+    if (ux >= (J.W >> cs) || uy >= (J.H >> cs)) return;  // (4:2:0 frames have even sides)
+    const float maxv = J.maxv;
+    float v[3], sum1 = 0.0f, sum2 = 0.0f;  // planes_kernel's order over the quad: dy outer, dx inner
+    const int n = cs ? 4 : 1;              // one loop body for both shapes: the warp is instantiated once
+#pragma unroll 1
+    for (int q = 0; q < n; ++q) {
+        const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
+        di_pixel<NT>(J, y, x, v);
+        const size_t i = static_cast<size_t>(y) * J.W + x;
+        di_store(J.plane[0], i, quantise_sample(v[0], maxv), J.wide);
+        if (!cs) {
+            di_store(J.plane[1], i, quantise_sample(v[1], maxv), J.wide);
+            di_store(J.plane[2], i, quantise_sample(v[2], maxv), J.wide);
+        } else {
+            sum1 += round_to_grid(v[1], maxv);
+            sum2 += round_to_grid(v[2], maxv);
+        }
+    }
+    if (!cs) return;
+    const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
+#pragma unroll
+    for (int c = 1; c < 3; ++c) {
+        float a = (c == 1 ? sum1 : sum2) / 4.0f;
+        a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
+        a = rintf(a * maxv) / maxv;
+        di_store(J.plane[c], ci, static_cast<unsigned>(rintf(a * maxv)), J.wide);
+    }
+}
+
+hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    if (sinc8) hipLaunchKernelGGL(dsens_inter_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
+    else hipLaunchKernelGGL(dsens_inter_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
     return hipGetLastError();
 }
 

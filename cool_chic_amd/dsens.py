@@ -4,10 +4,10 @@ every grid, on one MI355X (wraps the ccd_dsens_* C ABI).
 The numbers are those of one decode per moved latent (DecodeBatch.add_latents + QualityMeter), as integers; they come from a
 few thousand passes of the float path per picture, each of which moves every latent of one lattice at once."""
 import ctypes as C
-from typing import Sequence
+from typing import Optional, Sequence
 
 from ._handle import _DevArray, _Handle, ptr_array
-from ._lib import CCHeader, check, lib
+from ._lib import CCHeader, DsensInter, check, lib
 
 SENTINEL = -2 ** 63  # the entry where v - 1 / v + 1 leaves [-64, 63] (INT64_MIN)
 
@@ -45,6 +45,26 @@ class DistortionDeltas(_Handle):
                                          int(frame_data_type)), "ccd_dsens_add")
         self._note_grids(arch, len(latent_ptrs))
         self._keep(owner)  # (the device latents and source planes the slot reads at run())
+        return slot
+
+    def add_inter(self, arch: CCHeader, bytes_nn: bytes, latent_ptrs: Sequence[int], source_ptrs: Sequence[int], bitdepth: int,
+                  frame_data_type: int, frame_type: int, role: int, partner_ptr: int, ref0_ptrs: Sequence[int],
+                  ref1_ptrs: Optional[Sequence[int]] = None, global_flow: Sequence[int] = (0, 0, 0, 0), warp_filter_size: int = 8,
+                  owner=None) -> int:
+        """One cool-chic of a P / B frame (ccd_dsens_add_inter): `role` 0 the frame's residue cool-chic,
+        1 its motion cool-chic; `partner_ptr` the device f32 synthesis output of the OTHER one (read at every run, held fixed);
+        ref0_ptrs / ref1_ptrs the device planes of the references (ref1: B frames, frame_type 2); source planes, bitdepth and
+        frame_data_type are the FRAME's.  The maps are those of one ccd_inter_reconstruct per moved latent.  Returns the slot."""
+        src = (C.c_void_p * 3)(*[int(p) for p in source_ptrs])
+        gf = [int(v) for v in global_flow] + [0] * 4
+        it = DsensInter(frame_type=int(frame_type), role=int(role), partner=int(partner_ptr) or None,
+                        ref0=(C.c_void_p * 3)(*[int(p) or None for p in ref0_ptrs]),
+                        ref1=(C.c_void_p * 3)(*[int(p) or None for p in (ref1_ptrs or (0, 0, 0))]),
+                        global_flow=(C.c_int32 * 4)(*gf[:4]), warp_filter_size=int(warp_filter_size))
+        slot = check(lib().ccd_dsens_add_inter(self._h, C.byref(arch), bytes_nn, len(bytes_nn), ptr_array(latent_ptrs), src, int(bitdepth),
+                                               int(frame_data_type), C.byref(it)), "ccd_dsens_add_inter")
+        self._note_grids(arch, len(latent_ptrs))
+        self._keep(owner)  # (latents, source, partner and reference planes: all read at run())
         return slot
 
     def run(self, stream: int = 0):

@@ -1,0 +1,303 @@
+"""InterRdEvaluator: rate, distortion and D + lambda R of P / B frames on one MI355X, and their requantisation by descent
+(DESIGN.md section 4.15).  The counterpart of rd.RdEvaluator for frames that are decoded from TWO cool-chics, residue and motion,
+and a reconstruction against reference frames (ccd_inter_reconstruct).
+
+Per frame one evaluation is: the float outputs of both cool-chics from given latents (one DecodeBatch, no integer planes of their
+own, as the decoder adds them), ccd_inter_reconstruct for the frame's planes, QualityMeter for their squared error,
+EncodeBatch.measure[_deltas] over both cool-chics.  The cost is rd.rd_cost with the model bits, network bytes and cool-chic
+header bytes of BOTH cool-chics summed.
+
+The distortion deltas of a cool-chic are taken with the other one's output held fixed (DistortionDeltas.add_inter): the
+reconstruction is pointwise, so the footprints, lattice passes and influence boxes of an intra cool-chic hold for either.  A
+descent step therefore moves ONE role; inside one cool-chic the influence boxes make the chosen moves independent, and after the
+step the frame's squared error has changed by exactly the sum of the chosen entries."""
+import ctypes as C
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from ._lib import CCHeader, check, lib
+from .batch import FRAME_DATA_TYPES, DecodeBatch
+from .dsens import SENTINEL, DistortionDeltas
+from .encoder import EncodeBatch, SlotRate
+from .io import FrameData
+from .quality import FrameQuality, QualityMeter, _frame_planes
+from .rd import rd_cost
+from .rdoq import RdoqStep, StepResult
+
+ROLES = ("residue", "motion")
+
+
+def _role(role: Union[str, int]) -> int:
+    if role in ROLES:
+        return ROLES.index(role)
+    if role in (0, 1):
+        return int(role)
+    raise ValueError(f"role must be 'residue' / 'motion' (0 / 1), not {role!r}")
+
+
+class InterCandidate(NamedTuple):
+    rates: Tuple[SlotRate, SlotRate]   # residue, motion
+    quality: FrameQuality
+    mse: float
+    bits: float                        # of both cool-chics: model bits + 8 * (network and cool-chic header bytes)
+    cost: float
+
+
+class InterStepReport(NamedTuple):
+    """One frame in one step of InterRdEvaluator.descend: the frame before the step, the role that could move, what the step did."""
+    before: InterCandidate
+    role: str
+    step: StepResult
+
+
+class _Frame(NamedTuple):
+    frame_type: int                    # 1 P, 2 B
+    archs: Tuple[CCHeader, CCHeader]
+    nns: Tuple[bytes, bytes]
+    caller_ptrs: Tuple[List[int], List[int]]
+    refs: List[List[torch.Tensor]]
+    global_flow: List[int]
+    warp_filter_size: int
+    source: FrameData
+    src: List[torch.Tensor]
+    planes: List[torch.Tensor]         # what the last evaluate() reconstructed
+
+
+class InterRdEvaluator:
+    """add() frames, then evaluate(lmbda) or descend(...).  Frame f owns the slots 2 f (residue) and 2 f + 1 (motion) of every
+    handle inside."""
+
+    def __init__(self, device: int = 0, n_probe_slots: int = 16):
+        self.device = int(device)
+        self._n_probe_slots = int(n_probe_slots)
+        self._dec = DecodeBatch(self.device)
+        self._enc = EncodeBatch(self.device)
+        self._meter = QualityMeter(self.device)
+        self._dd: Dict[int, DistortionDeltas] = {}   # per role: a step reads the moving role's maps only
+        self._dd_frames: Dict[int, int] = {0: 0, 1: 0}
+        self._rdoq: Optional[RdoqStep] = None
+        self._frames: List[_Frame] = []
+        self._owners = []
+
+    def close(self):
+        if self._rdoq is not None:
+            self._rdoq.close()
+            self._rdoq = None
+        for d in self._dd.values():
+            d.close()
+        self._dd = {}
+        self._enc.close()
+        self._dec.close()
+        self._meter.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self._frames)
+
+    def add(self, frame_type: Union[str, int], residue, motion, references: Sequence, global_flow: Sequence[int], warp_filter_size: int,
+            source: FrameData, owner=None) -> int:
+        """A P / B frame.  residue, motion: (arch, bytes_nn, device addresses of the int8 latent grids) - the caller's memory, read
+        at every evaluate() and moved in place by descend(); `owner` keeps it alive.  references: one (P) or two (B) reference
+        frames, each a FrameData or three integer device planes (torch tensors, kept and read at every evaluate()); source: the
+        frame it is scored against, which also gives the bit depth and the sample format.  Returns the frame index."""
+        ft = {"P": 1, "B": 2}.get(frame_type, frame_type)
+        if ft not in (1, 2):
+            raise ValueError(f"frame_type must be 'P' / 'B' (1 / 2), not {frame_type!r}")
+        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
+            raise ValueError(f"cannot score a {source.frame_data_type} frame")
+        if len(references) < ft:
+            raise ValueError(f"a {'PB'[ft - 1]} frame needs {ft} reference frame(s)")
+        dev = torch.device(f"cuda:{self.device}")
+        src = _frame_planes(source, dev)
+        refs = []
+        for r in list(references)[:ft]:
+            planes = _frame_planes(r, dev) if isinstance(r, FrameData) else [p for p in r]
+            if [tuple(p.shape) for p in planes] != [tuple(p.shape) for p in src] or any(p.dtype != s.dtype or not p.is_cuda or
+                                                                                       not p.is_contiguous() for p, s in zip(planes, src)):
+                raise ValueError("a reference must have the frame's plane sizes and sample type, on the device")
+            refs.append(planes)
+        archs, nns, ptrs = [], [], []
+        for role, (arch, nn, latent_ptrs) in enumerate((residue, motion)):
+            if not all(isinstance(x, (int, np.integer)) for x in latent_ptrs):
+                raise ValueError("only device latents are accepted: descend() moves them in place")
+            if tuple(arch.img_size) != tuple(source.img_size):
+                raise ValueError(f"the {ROLES[role]} cool-chic decodes to {arch.img_size[0]}x{arch.img_size[1]}, the frame is "
+                                 f"{source.img_size[0]}x{source.img_size[1]}")
+            want = (5 if ft == 2 else 4) if role == 0 else (4 if ft == 2 else 2)
+            if arch.out_channels not in (0, want):  # (0: an arch without derived geometry; ccd_dsens_add_inter checks it then)
+                raise ValueError(f"the {ROLES[role]} cool-chic of a {'PB'[ft - 1]} frame has {want} output channels, not {arch.out_channels}")
+            archs.append(arch); nns.append(bytes(nn)); ptrs.append([int(p) for p in latent_ptrs])
+        for role in range(2):
+            slot = self._dec.add_latents_device(archs[role], nns[role], ptrs[role], 0, 0)
+            # the rate meter reads the grids where the decode batch keeps them
+            self._enc.add_device(archs[role], nns[role], self._dec.latent_ptrs(slot), owner=self._dec)
+        planes = [torch.empty_like(p) for p in src]
+        gf = ([int(v) for v in global_flow] + [0, 0, 0, 0])[:4]
+        self._frames.append(_Frame(ft, tuple(archs), tuple(nns), tuple(ptrs), refs, gf, int(warp_filter_size), source, src, planes))
+        self._owners.append(owner)
+        return len(self._frames) - 1
+
+    def planes(self, frame: int) -> List[torch.Tensor]:
+        """The integer device planes of the frame as the last evaluate() reconstructed them."""
+        return self._frames[frame].planes
+
+    def _fdt(self, f: _Frame) -> int:
+        return FRAME_DATA_TYPES.index(f.source.frame_data_type)
+
+    def _reconstruct(self, k: int, st: int):
+        f = self._frames[k]
+        h, w = f.source.img_size
+
+        def ptrs(planes):
+            return (C.c_void_p * 3)(*[p.data_ptr() for p in planes])
+
+        out = [self._dec.output_device(2 * k + r).__cuda_array_interface__["data"][0] for r in range(2)]
+        check(lib().ccd_inter_reconstruct(self.device, C.c_void_p(st or None), f.frame_type, h, w, f.source.bitdepth, self._fdt(f),
+                                          C.c_void_p(out[0]), C.c_void_p(out[1]), ptrs(f.refs[0]), ptrs(f.refs[1]) if f.frame_type == 2 else None,
+                                          (C.c_int32 * 4)(*f.global_flow), f.warp_filter_size, ptrs(f.planes)), "ccd_inter_reconstruct")
+
+    def _deltas(self, role: int) -> DistortionDeltas:
+        if role not in self._dd:
+            self._dd[role] = DistortionDeltas(self.device, self._n_probe_slots)
+        d = self._dd[role]
+        for k in range(self._dd_frames[role], len(self._frames)):
+            f = self._frames[k]
+            partner = self._dec.output_device(2 * k + 1 - role).__cuda_array_interface__["data"][0]
+            d.add_inter(f.archs[role], f.nns[role], self._dec.latent_ptrs(2 * k + role), [t.data_ptr() for t in f.src], f.source.bitdepth,
+                        self._fdt(f), f.frame_type, role, partner, [t.data_ptr() for t in f.refs[0]],
+                        [t.data_ptr() for t in f.refs[1]] if f.frame_type == 2 else None, f.global_flow, f.warp_filter_size, owner=self._dec)
+        self._dd_frames[role] = len(self._frames)
+        return d
+
+    def evaluate(self, lmbda: float, rate_deltas: bool = False, distortion_deltas: bool = False,
+                 roles: Sequence[Union[str, int]] = ROLES) -> List[InterCandidate]:
+        """One InterCandidate per frame.  rate_deltas: EncodeBatch.measure_deltas in place of measure (same numbers, and the maps
+        of rate_delta_map()).  distortion_deltas: a DistortionDeltas run per role of `roles` follows - two slots per frame, each
+        with the other cool-chic's device output as its partner - for distortion_delta_map() and cost_delta_map()."""
+        n = len(self._frames)
+        if n == 0:
+            return []
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        self._dec.run(st)
+        if rate_deltas:
+            self._enc.measure_deltas(st)
+        else:
+            self._enc.measure(st)
+        for k in range(n):
+            self._reconstruct(k, st)
+        self._meter.score_planes_async([f.planes for f in self._frames], [f.src for f in self._frames],
+                                       [f.source.bitdepth for f in self._frames], False, stream=st)
+        results = self._meter.finish()
+        self._dec.wait(st)          # a refused device latent raises here (CCD_ERR_VALUE)
+        self._enc.wait(st)
+        if distortion_deltas:       # read the grids in the decode batch's arenas and its float outputs, as they are now
+            for role in sorted({_role(r) for r in roles}):
+                d = self._deltas(role)
+                d.run(st)
+                d.wait(st)
+        out = []
+        for k, (r, f) in enumerate(zip(results, self._frames)):
+            rates = (self._enc.rate(2 * k), self._enc.rate(2 * k + 1))
+            q = FrameQuality.from_result(r, f.source.bitdepth, f.source.frame_data_type)
+            mse, bits, cost = rd_cost(q.sse, q.n, f.source.bitdepth, rates[0].total_bits + rates[1].total_bits,
+                                      rates[0].n_bytes_nn + rates[1].n_bytes_nn, rates[0].n_bytes_header + rates[1].n_bytes_header,
+                                      f.source.n_pixels, lmbda)
+            out.append(InterCandidate(rates, q, mse, bits, cost))
+        return out
+
+    def rate_delta_map(self, frame: int, role, grid: int):
+        """After evaluate(rate_deltas=True): device float32 [2][h][w] of the role's cool-chic."""
+        return self._enc.delta_map(2 * int(frame) + _role(role), grid)
+
+    def distortion_delta_map(self, frame: int, role, grid: int):
+        """After evaluate(distortion_deltas=True): device int64 [2][h][w], the change of the FRAME's squared error."""
+        r = _role(role)
+        if r not in self._dd or int(frame) >= self._dd_frames[r]:
+            raise RuntimeError("no evaluate(distortion_deltas=True) has covered this frame and role")
+        return self._dd[r].delta_map(int(frame), grid)
+
+    def cost_delta_map(self, frame: int, role, grid: int, lmbda: float) -> torch.Tensor:
+        """RdEvaluator.cost_delta_map for one cool-chic of the frame: float64 [2][h][w] on the device,
+
+            dD / (n_samples * (2^bitdepth - 1)^2) + lmbda * dBits / n_pixels
+
+        and +inf where the move leaves [-64, 63]."""
+        dev = f"cuda:{self.device}"
+        f = self._frames[frame]
+        n_samples = sum(int(t.numel()) for t in f.src)
+        maxv = float(2 ** f.source.bitdepth - 1)
+        dd = torch.as_tensor(self.distortion_delta_map(frame, role, grid), device=dev)
+        db = torch.as_tensor(self.rate_delta_map(frame, role, grid), device=dev).to(torch.float64)
+        cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(f.source.n_pixels)
+        return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)
+
+    def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids=None,
+                roles: Sequence[Union[str, int]] = ROLES) -> List[List[InterStepReport]]:
+        """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True) for the moving role, then
+        one RdoqStep that moves latents of THAT role's cool-chic of every frame in place by +-1 where the cost falls by more than
+        `min_gain` and the moves do not interact; the other role's grid mask is 0.  The moving role alternates over `roles`; the
+        descent stops after `max_steps` steps or when a full cycle over `roles` moved nothing.  `grids`: the grids that may move
+        (all by default), or a dict of them per role.  Returns one list of InterStepReport (one per frame) per step.  After a step
+        the frame's squared error is before + step.d_sse exactly; its bits within the rate deltas' bound of step.d_bits."""
+        n = len(self._frames)
+        order = [_role(r) for r in roles]
+        if not order:
+            raise ValueError("no role may move")
+        if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
+            raise ValueError("lmbda and min_gain must be finite and not negative")
+        if n == 0:
+            return []
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        if self._rdoq is None:
+            self._rdoq = RdoqStep(self.device)
+        for s in range(len(self._rdoq), 2 * n):
+            f = self._frames[s // 2]
+            self._rdoq.add(f.archs[s % 2], self._fdt(f), f.caller_ptrs[s % 2])
+
+        def grids_of(role):
+            g = grids.get(ROLES[role], grids.get(role)) if isinstance(grids, dict) else grids
+            return g
+
+        kD, kR = [], []
+        for s in range(2 * n):
+            f = self._frames[s // 2]
+            maxv = float(2 ** f.source.bitdepth - 1)
+            kD.append(1.0 / (float(sum(int(t.numel()) for t in f.src)) * maxv * maxv))
+            kR.append(float(lmbda) / float(f.source.n_pixels))
+        reports: List[List[InterStepReport]] = []
+        idle = 0
+        for step in range(int(max_steps)):
+            role = order[step % len(order)]
+            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=(role,))
+            masks = []
+            for s in range(2 * n):
+                n_grids = int(self._frames[s // 2].archs[s % 2].n_grids)
+                if s % 2 != role:
+                    masks.append(0)
+                    self._rdoq.set_maps(s, [None] * n_grids, [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
+                    continue
+                g_ok = grids_of(role)
+                masks.append(sum(1 << g for g in (range(n_grids) if g_ok is None else g_ok) if 0 <= g < n_grids))
+                self._rdoq.set_maps(s, [self._dd[role].delta_map(s // 2, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
+                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
+            self._rdoq.step(kD, kR, [float(min_gain)] * (2 * n), masks, st)
+            self._rdoq.wait(st)
+            results = [self._rdoq.result(2 * k + role) for k in range(n)]
+            reports.append([InterStepReport(b, ROLES[role], r) for b, r in zip(before, results)])
+            idle = 0 if any(r.n_moves for r in results) else idle + 1
+            if idle >= len(order):
+                break
+        return reports
+
+    def step_moves(self, frame: int, role, grid: int):
+        """After descend(): the last step's move (-1, 0, +1) at every latent of the grid (device, int8 [h][w])."""
+        if self._rdoq is None:
+            raise RuntimeError("no descend() has run")
+        return self._rdoq.moves(2 * int(frame) + _role(role), grid)

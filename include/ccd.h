@@ -501,8 +501,9 @@ int64_t ccd_quality_scratch_bytes(const ccd_quality_item* items, int n, int what
  * SSE is the sum over all three integer planes of (decoded - source)^2, the quality meter's definition (section 4.11); the
  * value is a signed 64-bit integer.  Where v + s leaves [-64, 63] the entry is INT64_MIN (the +inf of the rate deltas).  A
  * hyperlatent grid (is_hyperlatent[g]) does not feed the synthesis: its map is all zeros (the sentinel at the alphabet's ends)
- * and costs no passes.  Layout: int64 [2][h][w] per grid on the device, s = -1 first, like ccd_enc_slot_delta_map.  Intra
- * frames only: frame_data_type 0 rgb, 1 yuv420, 2 yuv444 at 8..16 bits.
+ * and costs no passes.  Layout: int64 [2][h][w] per grid on the device, s = -1 first, like ccd_enc_slot_delta_map.
+ * frame_data_type 0 rgb, 1 yuv420, 2 yuv444 at 8..16 bits.  ccd_dsens_add takes the one cool-chic of an intra frame,
+ * ccd_dsens_add_inter one of the two of a P / B frame.
  *
  * No float arithmetic of its own: the planes of a moved latent come from given-latent slots of a decode batch the handle owns
  * (per candidate one base slot that reads the caller's latents and n_probe_slots slots that read private copies, all with
@@ -545,6 +546,39 @@ int ccd_dsens_create(int device, int n_probe_slots, ccd_dsens** out);
 void ccd_dsens_destroy(ccd_dsens* d);
 int ccd_dsens_add(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
                   const void* const* src, int bitdepth, int frame_data_type);
+/* One cool-chic of a P / B frame as a candidate.  A P / B frame is decoded from two cool-chics, residue
+ * and motion, whose synthesis outputs go through ccd_inter_reconstruct; the candidate is ONE of them (`role`), the other one's
+ * output is given (`partner`) and held fixed.  Everything is as for ccd_dsens_add - layout, sentinels, hyperlatent zeros, maps
+ * that do not depend on n_probe_slots or on what else the handle holds - and an entry is
+ *
+ *     dD[s][g][y][x] = SSE(reconstruct(output of this cool-chic with latent[g][y][x] + s, partner as given, references))
+ *                    - SSE(reconstruct(output of this cool-chic as given, partner, references))
+ *
+ * where reconstruct is exactly ccd_inter_reconstruct.  The reconstruction is pointwise (sample (y, x) reads both outputs at (y, x)
+ * only), so ccd_latent_footprint and ccd_latent_probe_stride hold for both cool-chics of the frame.  `arch`, `bytes_nn`, `latents`:
+ * the candidate cool-chic; `src`, `bitdepth`, `frame_data_type` (0, 1, 2): the FRAME's; the frame's size is arch->img_size.
+ * `partner`, the references and `src` are read at every run and never written; they must stay valid while the handle may run (a
+ * caller that changed the partner's buffer between runs is followed, like latents changed in place).  The two cool-chics of a
+ * frame are two independent slots; intra and inter candidates may share a handle.  ccd_dsens_passes counts as for ccd_dsens_add.
+ * Per run the references are converted once, the base slots of all inter candidates are reconstructed by one launch (two when
+ * both the sinc-8 and another filter size are in use) behind the first round's float path - it keeps the warped references of
+ * residue candidates, which their probes only read - and every round reconstructs its probe slots by one such launch.
+ * CCD_ERR_ARG - before the device is touched - for a NULL argument, `inter`, partner, ref0[p] or (B frames) ref1[p], a frame_type
+ * outside 1..2, a role outside 0..1, a bit depth outside 8..16, a frame_data_type other than 0, 1, 2, a run in flight;
+ * CCD_ERR_VALUE - also before the device is touched - for an `arch` that does not re-parse, a filter size ccd_inter_reconstruct
+ * refuses, yuv420 with an odd side, an `arch` whose out_channels is not what the role needs (residue: 4 for P, 5 for B; motion:
+ * 2 for P, 4 for B). */
+typedef struct {
+    int32_t frame_type;         /* 1 P, 2 B (as ccd_inter_reconstruct) */
+    int32_t role;               /* 0: the candidate is the frame's residue cool-chic, 1: its motion cool-chic */
+    const float* partner;       /* DEVICE f32 synthesis output of the OTHER cool-chic: role 0: motion [2|4][h][w]; role 1: residue [4|5][h][w] */
+    const void* ref0[3];        /* DEVICE integer planes of the references, layout of ccd_inter_reconstruct */
+    const void* ref1[3];        /* B frames */
+    int32_t global_flow[4];
+    int32_t warp_filter_size;   /* 2, 4, 6..16 even */
+} ccd_dsens_inter;
+int ccd_dsens_add_inter(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, const int8_t* const* latents,
+                        const void* const* src, int bitdepth, int frame_data_type, const ccd_dsens_inter* inter);
 int ccd_dsens_run(ccd_dsens* d, void* stream);
 int ccd_dsens_wait(ccd_dsens* d, void* stream);
 int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr);

@@ -12,6 +12,11 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     evaluate(rate_deltas, distortion_deltas) that feeds it, candidates and moves per step for three grid
                     masks, and for kodim14 the cost after 1, 2, 4, 8 steps of RdEvaluator.descend
 
+  --inter           instead of the above: the distortion deltas of P / B frames (DistortionDeltas.add_inter, DESIGN.md section
+                    4.15) - one P and one B frame of the `vid5` fixture and a 1080p B frame of synth.gop1080p, both roles: passes,
+                    run + wait, the time per round split into float path, probe reconstruction and squared-error split (each
+                    stage run alone through the library's measurement hook), next to K plain ccd_inter_reconstruct calls on the same frame
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -236,6 +241,88 @@ def measure_rdoq(streams, runs, lmbda, trajectory):
     return res
 
 
+def measure_inter(stream_bytes, coding_index, runs, n_probe_slots):
+    """Both candidates of one P / B frame of a video stream, scored against the frame itself, its references as decode_video
+    gives them."""
+    import ctypes as C
+    import os
+    import tempfile
+
+    from cool_chic_amd import DistortionDeltas
+    from cool_chic_amd._lib import check, lib
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+    from cool_chic_amd.bitstream.intercoding import _integer_planes
+
+    st = torch.cuda.current_stream().cuda_stream
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    for k in range(coding_index + 1):
+        fh, ccs, rest = _split_frame(rest)
+    frame_type = "IPB".index(fh.get_value("frame_type"))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    dev = torch.device("cuda:0")
+    refs = [_integer_planes(frames[str(int(r))], dev) for r in structure[coding_index]["index_references"]][:frame_type]
+    src = _integer_planes(frames[str(int(structure[coding_index]["display_order"]))], dev)
+    h, w = src[0].shape
+    gflow = (list(fh.get_value("global_flow")) + [0] * 4)[:4]
+    bitdepth, fdt = fh.get_value("bitdepth"), ["rgb", "yuv420", "yuv444"].index(fh.get_value("frame_data_type"))
+    stages = lib().ccd_dsens_debug_stages  # exported, not part of include/ccd.h: which stages of a round the next runs enqueue
+    stages.restype, stages.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    taps = fh.get_value("warp_filter_size")
+    dec = DecodeBatch(0)
+    for ch, nn, lat in ccs:
+        dec.add(ch.raw, nn, lat, 0, 0)
+    dec.run(st); dec.wait(st)
+    outs = [torch.as_tensor(dec.output_device(s), device="cuda") for s in range(2)]
+    res = {"frame": "PB"[frame_type - 1], "size": [int(h), int(w)], "probe_slots": n_probe_slots, "warp_filter_size": int(taps)}
+
+    def ptrs(planes):
+        return (C.c_void_p * 3)(*[p.data_ptr() for p in planes])
+
+    out_planes = [torch.empty_like(p) for p in src]
+
+    def plain(n):  # the parent's entry point, n times: what a round of n probes would cost through it
+        for _ in range(n):
+            check(lib().ccd_inter_reconstruct(0, C.c_void_p(st or None), frame_type, h, w, bitdepth, fdt, C.c_void_p(outs[0].data_ptr()),
+                                              C.c_void_p(outs[1].data_ptr()), ptrs(refs[0]), ptrs(refs[1]) if frame_type == 2 else None,
+                                              (C.c_int32 * 4)(*gflow), taps, ptrs(out_planes)), "ccd_inter_reconstruct")
+
+    res["plain_reconstruct_ms"] = round(event_ms(lambda: plain(1), runs), 4)
+    res["plain_reconstruct_x_slots_ms"] = round(event_ms(lambda: plain(n_probe_slots), runs), 4)
+    assert all(torch.equal(a, b) for a, b in zip(out_planes, src))
+    for role, name in enumerate(("residue", "motion")):
+        dd = DistortionDeltas(0, n_probe_slots)
+        dd.add_inter(dec.header(role), dec.network_bytes(role), dec.latent_ptrs(role), [t.data_ptr() for t in src], bitdepth, fdt, frame_type, role,
+                     outs[1 - role].data_ptr(), [t.data_ptr() for t in refs[0]], [t.data_ptr() for t in refs[1]] if frame_type == 2 else None,
+                     gflow, taps, owner=(dec, src, refs, outs))
+
+        def step():
+            dd.run(st)
+            dd.wait(st)
+
+        passes = dd.passes(0)
+        rounds = -(-passes // n_probe_slots)
+        r = {"passes": passes, "rounds": rounds, "run_wait_ms": round(event_ms(step, runs), 3)}
+        m = torch.as_tensor(dd.delta_map(0, 0), device="cuda")  # the frame is its own source: no move lowers the squared error
+        assert int((m[m != -2 ** 63] < 0).sum()) == 0
+        for label, mask in (("float_path", 1), ("probe_reconstruction", 2), ("sse", 4)):
+            check(stages(dd._h, mask), "ccd_dsens_debug_stages")
+            r[label + "_ms_per_round"] = round(event_ms(step, runs) / rounds, 5)
+        check(stages(dd._h, 7), "ccd_dsens_debug_stages")
+        r["ms_per_round"] = round(r["run_wait_ms"] / rounds, 5)
+        r["plain_over_probe_reconstruction"] = round(res["plain_reconstruct_x_slots_ms"] / r["probe_reconstruction_ms_per_round"], 2)
+        res[name] = r
+        dd.close()
+    dec.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
@@ -245,7 +332,19 @@ def main():
     ap.add_argument("--rdoq", action="store_true", help="time one requantisation step and the evaluation that feeds it instead")
     ap.add_argument("--lmbda", type=float, default=1e-3)
     ap.add_argument("--sets", default="kodim14,kodak24", help="with --rdoq: which of the two sets to measure")
+    ap.add_argument("--inter", action="store_true", help="time the distortion deltas of P / B frames instead")
+    ap.add_argument("--inter-sets", default="vid5,1080p", help="with --inter: which of the two sets to measure")
     a = ap.parse_args()
+    if a.inter:
+        line = {"tool": "rd_bench --inter", "runs": a.runs}
+        if "vid5" in a.inter_sets.split(","):
+            vid5 = synth._golden("vid5")[0]
+            line["vid5_P"] = measure_inter(vid5, 1, a.runs, a.probe_slots)
+            line["vid5_B"] = measure_inter(vid5, 3, a.runs, a.probe_slots)
+        if "1080p" in a.inter_sets.split(","):
+            line["gop1080p_B"] = measure_inter(synth.gop1080p(2)[0], 2, a.runs, a.probe_slots)
+        print(json.dumps(line))
+        return
     k24 = synth.workload("kodak24")["streams"]
     if a.rdoq:
         line = {"tool": "rd_bench --rdoq", "runs": a.runs}
