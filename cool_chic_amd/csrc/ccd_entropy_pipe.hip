@@ -1298,6 +1298,49 @@ __device__ __forceinline__ ExactOut exact_pixel(const ExactArgs& A, int y, int x
     return r;
 }
 
+// Sum of a 64-bit value over the 8 or 16 lanes of a pixel's group, in every lane of the group: pairs (quad_perm [1,0,3,2]),
+// quads (quad_perm [2,3,0,1]), the other quad of the 8 (row_half_mirror), the other half of the 16 (row_mirror).  A group of 32
+// lanes is two DPP rows: row_bcast:15 hands the even row's sum (its lane 15 holds it like every other) to the odd row, so the
+// UPPER 16 lanes of the group end up with the whole sum and the lower 16 with their own row's.  Wrapping int64
+// addition is associative and commutative: the same bits as any serial sum.  (The DPP reads are the compiler's: it keeps the
+// wait states between a VALU write and a DPP read of the same register; two sums reduced side by side fill them.)
+template <int CTRL>
+__device__ __forceinline__ int64_t dpp_add64(int64_t v) {
+    // (every lane of these permutations has a source lane: bound_ctrl only spares the destination's initialisation)
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), CTRL, 0xf, 0xf, true));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v >> 32), CTRL, 0xf, 0xf, true));
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 other = {lo, hi};  // (a register pair as it stands: shifts and ors made two 64-bit additions of it)
+    return v + __builtin_bit_cast(int64_t, other);
+}
+// the even row's lane 15 into every lane of the odd row behind it (rows 1 and 3 only: an even row adds zero)
+__device__ __forceinline__ int64_t dpp_add64_row_below(int64_t v) {
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v >> 32), 0x142, 0xa, 0xf, false));
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 other = {lo, hi};
+    return v + __builtin_bit_cast(int64_t, other);
+}
+template <int LANES>
+__device__ __forceinline__ void group_sum2(int64_t& a, int64_t& b) {
+    static_assert(LANES == 8 || LANES == 16 || LANES == 32, "a pixel's lane group: part of a DPP row, a row, or two rows");
+    a = dpp_add64<0xB1>(a); b = dpp_add64<0xB1>(b);
+    a = dpp_add64<0x4E>(a); b = dpp_add64<0x4E>(b);
+    a = dpp_add64<0x141>(a); b = dpp_add64<0x141>(b);
+    if constexpr (LANES >= 16) { a = dpp_add64<0x140>(a); b = dpp_add64<0x140>(b); }
+    if constexpr (LANES == 32) { a = dpp_add64_row_below(a); b = dpp_add64_row_below(b); }
+}
+// clamp((sum >> 24) + off, 0, hi) of an output-layer sum, in 32 bits.  sum >> 24 has 40 bits; with the high word clamped to
+// +-2^22 first it fits 32 (|x| <= 2^30 + 255, |off| < 2^30) and saturates the same way: a high word outside +-2^22 puts
+// sum >> 24 beyond +-2^30, past both ends of any table.
+__device__ __forceinline__ int32_t table_index(int64_t sum, int32_t off, int32_t hi) {
+    const int32_t h = min(max(static_cast<int32_t>(sum >> 32), -(1 << 22)), 1 << 22);
+    const int32_t x = static_cast<int32_t>((static_cast<uint32_t>(h) << 8) | (static_cast<uint32_t>(sum) >> 24));
+    return min(max(x + off, 0), hi);
+}
+static_assert(kMuOffset < (1 << 29) && kScaleOffset < (1 << 29) && kMuOffset >= 0 && kScaleOffset >= 0, "table_index: offsets");
+static_assert(offsetof(RowMeta, top) - offsetof(RowMeta, mu_idx) == (kRows + 2) * 4, "a pixel's top symbol is stored (kRows + 2) words behind its mu index");
+
 // MF: this grid's tasks run the ARM on the matrix cores; DYN_RING: the kernel's ring of decoded symbols has
 // EntropyParams::ring_rows rows instead of kRingRows (every grid of a matrix-core kernel, whichever producer serves it).
 template <int NV, int kLpp, bool MF, bool DYN_RING, bool DYN, class SH>
@@ -1479,12 +1522,23 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 unsigned long long lt_a = 0, lt_b = 0, lt_c = 0, lt_d = 0;  // level-2 profile stamps
                 (void)lt_a; (void)lt_b; (void)lt_c; (void)lt_d;
                 unsigned narrow_mask = 0;  // matrix-core path: bit i: pixel i of the task is narrow (wave-uniform)
-                // vector-ALU path: the LDS addresses this lane's window passes read (mu index, reciprocal) and write (table entry, top
-                // symbol), pass k = pixels 4 k .. 4 k + 3 of the task; worked out before the late wait
-                constexpr int kPasses = (kTaskPix + 3) / 4;
-                uint32_t win_mu[kPasses] = {}, win_rcp[kPasses] = {}, win_ent[kPasses] = {}, win_top[kPasses] = {};
-                uint32_t win_left_m = 0, win_keep_m = 0, win_e0 = 0, win_e1 = 0;  // the entry's role (sentinel, window top) as masks / addend
-                (void)win_mu; (void)win_rcp; (void)win_ent; (void)win_top; (void)win_left_m; (void)win_keep_m; (void)win_e0; (void)win_e1;
+                // vector-ALU path: the entry's role in its window (sentinel, window top) as masks / addends, worked out before the late wait
+                uint32_t win_left_m = 0, win_keep_m = 0, win_e0 = 0, win_e1 = 0;
+                (void)win_left_m; (void)win_keep_m; (void)win_e0; (void)win_e1;
+                // vector-ALU path: the output layer runs on the activations the lanes hold, summed over the pixel's lanes, and the
+                // pixel's lanes build its window themselves from the indices they then have.  The WINDOW LANES of a pixel are
+                // all of its lanes on 8- and 4-pixel tasks and the upper 16 of its 32 on 2-pixel tasks (group_sum2); kQ0 is the
+                // first of them.
+                constexpr int kQ0 = kLpp == 32 ? 16 : 0;
+                constexpr int kEpl = kLpp == 8 ? 2 : 1;  // window entries per lane
+                const int e0 = kEpl * (q & 15);          // the lane's first entry
+                int32_t idx_mu = 0, idx_sc = 0;  // the pixel's table indices, in every window lane of the pixel
+                double own_rcp = 0.0;            // s_rcp[idx_sc]
+                uint32_t own_ent = 0;            // where the lane's table entries go
+                uint32_t mu_dst = 0, rcp_dst = 0;  // where the lane's table index and reciprocal go (RowMeta; see the role constants below)
+                (void)idx_mu; (void)idx_sc; (void)own_rcp; (void)own_ent; (void)mu_dst; (void)rcp_dst;
+                uint32_t rdy_addr = 0, rdy_val = 0;  // the ready bit's word and value
+                (void)rdy_addr; (void)rdy_val;
                 unsigned long long wide_lanes = 0ull;  // vector-ALU path: ballot of the log-scale lanes of the pixels that are not
                 RowMeta& meta = *C.s_meta;
                 if constexpr (MF) {
@@ -1668,6 +1722,9 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2
                 if (pw == 0 && lt_prev_end) prof[4] += lt_a - lt_prev_end;
 #endif
+                // what lane q holds of the layer in front of the output layer: its units o = q + kLpp t (the raw inputs of a network
+                // without a hidden layer): the output layer's inputs
+                int32_t hid[NOUT];
                 {
                     const unsigned long long t0 = PROF_T();
                     // (the early wait includes "slot free again": true long ago whenever it is looked at - the slot was last used
@@ -1731,6 +1788,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         const int32_t v = k < n_sp ? ((yy >= 0 && xx >= 0 && xx < W && !(split && k == k_left)) ? rr[t] : 0) : fv[t];
                         int32_t* const dst = k < in_pad ? act + px * in_pad + k : act_dummy;
                         *dst = v << 16;  // armint.py:193
+                        hid[t] = v << 16;
                     }
                 }
                 PROF_ADD(prof[1], t_g);
@@ -1802,37 +1860,63 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // Unconditional read (cell of column -1 for x = 0: in bounds, dropped by the select), no exec mask.
                 int32_t xleft = 0;
                 // Role constants of the output tail, as VGPRs and BEFORE the late wait: where this lane's table index and reciprocal
-                // go (the dummy entry kRows for a lane that has nothing to say), what it reads the reciprocal table with, and the
-                // scale index above which it reports a wide window.  Left to the compiler they were SGPR-pair masks (q == 0,
-                // q == 1, live) that did not fit the scalar file: spilled, and reloaded with v_readlane on the late path.
+                // go in the row meta (first window lane of the pixel: mu index and, next to it, the top symbol; second: reciprocal;
+                // the dummy entry kRows for a lane that has nothing to say), and the scale index above which the second window lane
+                // reports a wide window.  Left to the compiler they were SGPR-pair masks (q == 0, q == 1, live) that did not fit the
+                // scalar file: spilled, and reloaded with v_readlane on the late path.
+                // (an opaque copy of the lane's index in its group: what is derived from it below is worked out per task, off the late
+                // path - not hoisted out of the task loop and kept, or spilled, over the whole grid)
+                int qo = q;
+                asm volatile("" : "+v"(qo));
                 const int mpx = slot * kBpx + half * kTaskPix + px;  // table row of the pixel
-                uint32_t mu_dst = lds_addr(&meta.mu_idx[px < cnt && q == 0 ? mpx : kRows]);
-                uint32_t rcp_dst = lds_addr(&meta.rcp[px < cnt && q == 1 ? mpx : kRows]);
-                int32_t rcp_lanes = q == 1 ? -1 : 0, wide_above = px < cnt && q == 1 ? kNarrowMaxScale : 0x7fffffff;
-                asm volatile("" : "+v"(mu_dst), "+v"(rcp_dst), "+v"(rcp_lanes), "+v"(wide_above));
-                // ... and of the window passes: the selects and address arithmetic of a pass (which pixel, does it exist, its rows)
-                // were a fifth of its instructions, all of them known here.  Sub-wave u = lane >> 4 builds pixel 4 k + u, entry
-                // e = lane & 15; a lane whose pixel does not exist reads the pass's first pixel and stores to the dummy rows
-                // (address selects instead of exec-masked stores, see RowMeta).
+                mu_dst = lds_addr(&meta.mu_idx[px < cnt && qo == kQ0 ? mpx : kRows]);
+                rcp_dst = lds_addr(&meta.rcp[px < cnt && qo == kQ0 + 1 ? mpx : kRows]);
+                int32_t wide_above = px < cnt && qo == kQ0 + 1 ? kNarrowMaxScale : 0x7fffffff;
+                asm volatile("" : "+v"(mu_dst), "+v"(rcp_dst), "+v"(wide_above));
+                // The output layer's operands of this lane.  Its two partial sums (mu row, log-scale row) start from the
+                // stabiliser output and the bias in the one lane that holds that row (q = 0: mu, q = 1: log-scale) and from zero
+                // everywhere else, so that the sum over the pixel's lanes takes each once; the left neighbour's stabiliser weight
+                // likewise.  The output weights of the lane's units o = q + kLpp t, both rows: ZERO for a unit past the layer
+                // (such a lane computes a copy of unit dim - 1 in the hidden layers; the tile path drops it at the store).
+                int64_t out_m = 0, out_l = 0;
+                int32_t wl_m = 0, wl_l = 0, wo_m[NOUT], wo_l[NOUT];
+                (void)wl_m; (void)wl_l; (void)wo_m; (void)wo_l;
+                {
+                    const int64_t s = so[0] + so[1] + C.s_b[(n_layers - 1) * dim + qs];
+                    const int64_t keep_m = qo == 0 ? -1 : 0, keep_l = qo == 1 ? -1 : 0;
+                    out_m = s & keep_m;
+                    out_l = s & keep_l;
+                    wl_m = wleft_stab & static_cast<int32_t>(keep_m);
+                    wl_l = wleft_stab & static_cast<int32_t>(keep_l);
+                    asm volatile("" : "+v"(out_m), "+v"(out_l), "+v"(wl_m), "+v"(wl_l));
+                    const int32_t* const w_out = C.s_w + C.n_w_hidden;
 #pragma unroll
-                for (int k = 0; k < kPasses; ++k) {
-                    const int u = lane >> 4, e = lane & 15;
-                    const int mine = 4 * k + u;
-                    const bool valid = mine < cnt;
-                    const int mi = slot * kBpx + half * kTaskPix + (valid ? mine : 4 * k);
-                    win_mu[k] = lds_addr(&meta.mu_idx[mi]);
-                    win_rcp[k] = lds_addr(&meta.rcp[mi]);
-                    win_ent[k] = lds_addr(&C.s_tab[static_cast<size_t>(valid ? mi : kRows) * 64 + e]);
-                    win_top[k] = lds_addr(&meta.top[valid && e == 0 ? mi : kRows]);
-                    asm volatile("" : "+v"(win_mu[k]), "+v"(win_rcp[k]), "+v"(win_ent[k]), "+v"(win_top[k]));
+                    for (int t = 0; t < NOUT; ++t) {
+                        const int o = qo + kLpp * t, oc = min(o, in_pad - 1);
+                        const int32_t keep = (o - dim) >> 31;  // all ones for a unit of the layer
+                        wo_m[t] = w_out[oc] & keep;
+                        wo_l[t] = w_out[in_pad + oc] & keep;
+                        asm volatile("" : "+v"(wo_m[t]), "+v"(wo_l[t]));
+                    }
                 }
-                // entry 15 is the lower sentinel (left = 0), entries 0 and 15 have P = 0, entry 0 is the upper sentinel (2^24 - 1 when
-                // its symbol is 64), entry 1 the window's top symbol
-                win_left_m = (lane & 15) == 15 ? 0u : ~0u;
-                win_keep_m = ((lane & 15) == 0 || (lane & 15) == 15) ? 0u : ~0u;
-                win_e0 = (lane & 15) == 0 ? (1u << kRcPrecision) - 1u : 0u;
-                win_e1 = (lane & 15) == 1 ? 1u : 0u;
-                asm volatile("" : "+v"(win_left_m), "+v"(win_keep_m), "+v"(win_e0), "+v"(win_e1));
+                // the ready bit's word and value: wave-uniform and known here, as VGPRs for the one ds_or_b32 behind the table stores
+                rdy_addr = lds_addr(&C.s_ready[slot]);
+                rdy_val = 1u << half;
+                asm volatile("" : "+v"(rdy_addr), "+v"(rdy_val));
+                // The pixel's window lanes build its 14-symbol window.  4- and 2-pixel tasks: window lane e builds entry e.  8-pixel
+                // tasks: lane q builds entries 2 q and 2 q + 1, one after the other, and stores them as one 16-byte vector.
+                // A lane whose pixel does not exist - or, on 2-pixel tasks, one of the lower 16 - stores to the dummy row (address
+                // selects instead of exec-masked stores, see RowMeta).
+                const int e0o = kEpl * (qo & 15);
+                own_ent = lds_addr(&C.s_tab[static_cast<size_t>(px < cnt && qo >= kQ0 ? mpx : kRows) * 64 + e0o]);
+                // entry 0 is the upper sentinel (P = 0, left = 2^24 - 1 when its symbol is 64), entry 1 the window's top symbol,
+                // entry 15 the lower sentinel (left = 0, P = 0).  win_left_m masks the left bound of the lane's LAST entry,
+                // win_keep_m the P of its FIRST one (and of entry 15 where that is the same entry)
+                win_left_m = e0o + kEpl - 1 == 15 ? 0u : ~0u;
+                win_keep_m = (e0o == 0 || e0o == 15) ? 0u : ~0u;
+                win_e0 = e0o == 0 ? (1u << kRcPrecision) - 1u : 0u;
+                win_e1 = (e0o <= 1 && e0o + kEpl > 1) ? 1u : 0u;
+                asm volatile("" : "+v"(own_ent), "+v"(win_left_m), "+v"(win_keep_m), "+v"(win_e0), "+v"(win_e1));
                 lt_c = LPROF_T(pw == 0);
                 if (split) {
                     const unsigned long long t0 = PROF_T();
@@ -1865,20 +1949,28 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // decoder runs at priority 3).  41.03 -> 40.84 ms on kodak24 (profiles/r04/ab_entropy_late_prio.txt)
                 // (priority 2 for the first task of a step, the head of its chain: no further gain)
                 __builtin_amdgcn_s_setprio(1);
-                mad64(so[0], xleft, wleft_stab);
-                const int64_t stab = so[0] + so[1];
+                mad64(out_m, xleft, wl_m);
+                mad64(out_l, xleft, wl_l);
+                // A layer's activations go through the tile only when another hidden layer reads them; the layer in front of the
+                // output layer stays in `hid`.
                 if (n_layers >= 2) {
 #pragma unroll
                     for (int t = 0; t < NOUT; ++t) {
                         mad64(acc0[t], xleft, wleft[t]);
-                        const int o = q + kLpp * t;
-                        // a lane without a real output stores to the dummy words (address select, constant over the grid): the
-                        // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
-                        int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
-                        *dst = relu_q16(acc0[t]);
+                        hid[t] = relu_q16(acc0[t]);
                     }
+                    if (n_layers > 2) {
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
+                        for (int t = 0; t < NOUT; ++t) {
+                            const int o = q + kLpp * t;
+                            // a lane without a real output stores to the dummy words (address select, constant over the grid): the
+                            // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
+                            int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
+                            *dst = hid[t];
+                        }
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
+                    }
                 }
                 for (int l = 1; l < n_layers - 1; ++l) {
                     const int32_t* wl = C.s_w + l * dim * in_pad;
@@ -1908,36 +2000,33 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     if constexpr (NOUT == 1) acc[0] += acc_b;
 #pragma unroll
                     for (int t = 0; t < NOUT; ++t) {
-                        const int o = q + kLpp * t;
-                        // a lane without a real output stores to the dummy words (address select, constant over the grid): the
-                        // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
-                        int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
-                        *dst = relu_q16(acc[t]);
+                        hid[t] = relu_q16(acc[t]);
+                        asm("" : "+v"(hid[t]));
                     }
+                    if (l + 2 < n_layers) {
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
+                        for (int t = 0; t < NOUT; ++t) {
+                            const int o = q + kLpp * t;
+                            // a lane without a real output stores to the dummy words (address select, constant over the grid): the
+                            // padding inputs dim .. in_pad - 1 of the tile keep the zeros the gather put there
+                            int32_t* const dst = o < dim ? act + px * in_pad + o : act_dummy;
+                            *dst = hid[t];
+                        }
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
+                    }
                 }
                 PROF_ADD(prof[6], t_h);
                 const unsigned long long t_o = PROF_T();
-                // output layer (q = 0: mu, q = 1: log-scale) -> table indices -> per-pixel table parameters
-                int32_t idx = 0;
-                {   // (every lane: lanes q >= 2 compute a discarded copy of row 1, like the stabiliser - no exec mask around the block)
-                    const int4* wr = reinterpret_cast<const int4*>(C.s_w + C.n_w_hidden + qs * in_pad);
-                    int64_t ao[4] = {C.s_b[(n_layers - 1) * dim + qs] + stab, 0, 0, 0};
-                    int4 wv[NV];
+                // output layer -> table indices.  From registers: the lane's units times their two output weights (two chains in
+                // rotation), then the sum over the pixel's lanes - every window lane of the pixel ends up with both sums (stabiliser
+                // and bias came in through the chains' start values), no trip through the activation tile
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) wv[v] = wr[v];
-#pragma unroll
-                    for (int v = 0; v < NV; ++v) { CCD_MAD4_QUAD_SEQ(ao, xv[v], wv[v]) }
-                    const int64_t acc = (ao[0] + ao[1]) + (ao[2] + ao[3]);
-                    const int64_t q8 = acc >> 24;
-                    const int64_t off = q8 + (q == 0 ? kMuOffset : kScaleOffset);
-                    const int64_t hi = q == 0 ? kNumMu - 1 : kNumScale - 1;
-                    idx = static_cast<int32_t>(off < 0 ? 0 : (off > hi ? hi : off));
-                    // both stores by address select (dummy entry kRows for the lanes that have nothing to say): no exec mask, no branch
-                    *lds_at<int32_t>(mu_dst) = idx;
-                    *lds_at<double>(rcp_dst) = C.s_rcp[idx & rcp_lanes];
-                }
+                for (int t = 0; t < NOUT; ++t) { mad64_seq(out_m, hid[t], wo_m[t]); mad64_seq(out_l, hid[t], wo_l[t]); }
+                group_sum2<kLpp>(out_m, out_l);
+                idx_mu = table_index(out_m, kMuOffset, kNumMu - 1);
+                idx_sc = table_index(out_l, kScaleOffset, kNumScale - 1);
+                own_rcp = C.s_rcp[idx_sc];  // the one LDS trip between the output layer and the first f64 multiply
                 // ---- a feature of some pixel was not exact in 16 bits (never on the streams seen so far): that pixel again,
                 // in plain int64; its table parameters replace what the lines above wrote from the sentinel
                 if (DYN && __builtin_expect(bad_lanes != 0ull, 0)) {
@@ -1952,24 +2041,18 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         asm volatile("" : "+s"(A.P), "+s"(A.s_w), "+s"(A.s_b), "+s"(A.s_ring), "+s"(A.n_w_hidden), "+s"(A.dim), "+s"(A.n_layers));
                         asm volatile("" : "+s"(A.n_sp), "+s"(A.W), "+s"(A.fin), "+s"(A.fw), "+s"(A.feat_plane), "+s"(A.ring_mask), "+s"(A.fstride));
                         const ExactOut r = exact_pixel(A, __builtin_amdgcn_readlane(y, MF ? p : p * kLpp), __builtin_amdgcn_readlane(x, MF ? p : p * kLpp));
-                        if (px == p && q < 2) {
-                            const int64_t off = ((q == 0 ? r.mu : r.ls) >> 24) + (q == 0 ? kMuOffset : kScaleOffset);
-                            const int64_t hi = q == 0 ? kNumMu - 1 : kNumScale - 1;
-                            idx = static_cast<int32_t>(off < 0 ? 0 : (off > hi ? hi : off));
-                            if (q == 0) {
-                                meta.mu_idx[mpx] = idx;
-                            } else {
-                                    meta.rcp[mpx] = C.s_rcp[idx];
-                            }
+                        if (px == p) {  // (the window lanes write the row meta from these below)
+                            idx_mu = table_index(r.mu, kMuOffset, kNumMu - 1);
+                            idx_sc = table_index(r.ls, kScaleOffset, kNumScale - 1);
+                            own_rcp = C.s_rcp[idx_sc];
                         }
                         ++n_redo;
                     }
                     if (lane == 0) atomicAdd(reinterpret_cast<int*>(P.status) + 39, n_redo);  // status[39]: pixels redone (tests)
                 }
-                // bit (px * kLpp + 1) of the ballot: pixel px of the task takes a narrow window (wave-uniform, no LDS trip)
-                // lanes (px * kLpp + 1) of pixels that need the wide window (scale index above kNarrowMaxScale: 0.7 % of the symbols);
+                // lanes (px * kLpp + kQ0 + 1) of pixels that need the wide window (scale index above kNarrowMaxScale: 0.7 % of the symbols);
                 // the common path only tests the ballot for zero
-                wide_lanes = __ballot(idx > wide_above);
+                wide_lanes = __ballot(idx_sc > wide_above);
                 PROF_ADD(prof[2], t_m);
                 PROF_ADD(prof[7], t_o);
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE >= 3
@@ -1978,41 +2061,53 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 }
                 const unsigned long long t_t = PROF_T();
                 // ---- window tables (lanes hold symbols in DESCENDING order; entry 0 = upper sentinel, trailing entries =
-                // lower sentinels, both with P = 0).  Narrow pixels (small scale): 14 real symbols, four pixels per pass.
-                // Wide pixels: 62 real symbols, one pixel per pass.
+                // lower sentinels, both with P = 0).  Narrow pixels (small scale): 14 real symbols, built by the pixel's window lanes
+                // (matrix-core path: four pixels per pass of the wave).  Wide pixels: 62 real symbols, one pixel per pass.
                 const int base = slot * kBpx + half * kTaskPix;  // first table row of the task
                 uint2* tab = C.s_tab + static_cast<size_t>(base) * 64;
                 if constexpr (!MF) {
-                    // Static layout: pass k builds the 14-symbol windows of pixels 4 k .. 4 k + 3, narrow or not (99.3 % are;
-                    // the row of a wide pixel is rewritten in full below) - no bit-scanning of the mask on the late path.
-#pragma unroll
-                    for (int k = 0; k < kPasses; ++k) {
-                        if (k > 0 && 4 * k >= cnt) break;
-                        const int e = lane & 15;
-                        const int mu_idx = *lds_at<int32_t>(win_mu[k]);
-                        const double rcp256 = window_rcp256(*lds_at<double>(win_rcp[k]));
-                        int top = ((mu_idx + 128) >> 8) - 64 + 6;  // round(mu) + 6: window = [round(mu) - 7, round(mu) + 6]
+                    // Static layout: every pixel gets its 14-symbol window from its own window lanes, narrow or not (99.3 % are; the
+                    // row of a wide pixel is rewritten in full below) - no bit-scanning of the mask on the late path.
+                    {
+                        int top = ((idx_mu + 128) >> 8) - 64 + 6;  // round(mu) + 6: window = [round(mu) - 7, round(mu) + 6]
                         top = max(kAcLo + 13, min(kAcLo + kAlphabet - 1, top));
-                        const int ssym = top - (e - 1);  // e = 0 -> top + 1: its left bound is the window's upper edge
-                        // window_left's edge cases from integers, ahead of the f64 chain and without compares next to their selects:
-                        // symbols <= -64 (and the lower sentinel) give 0; symbol 64 - entry 0 of a window that reaches symbol 63 -
-                        // gives 2^24, stored as 2^24 - 1 (every stored bound must fit 24 bits, see the wide pass)
-                        const uint32_t lo_m = static_cast<uint32_t>((kAcLo - ssym) >> 31) & win_left_m;
+                        // the row meta is for the decoder's rare path and the wide pass: plain stores by address select (the pixel's
+                        // first window lane: mu index and top symbol, the second: reciprocal), nothing on this path waits for them
+                        lds_at<int32_t>(mu_dst)[0] = idx_mu;
+                        lds_at<int32_t>(mu_dst)[kRows + 2] = top;
+                        const double rcp256 = window_rcp256(own_rcp);
+                        *lds_at<double>(rcp_dst) = own_rcp;
                         const bool at_top = top == kAcLo + kAlphabet - 1;
                         const uint32_t hi_f = at_top ? win_e0 : 0u, to_full = at_top ? win_e1 : 0u;
-                        uint32_t left = window_cum_d256(window_d256(mu_idx, ssym), rcp256, C.s_exp) + static_cast<uint32_t>(ssym - kAcLo);
-                        left = (min(left, (1u << kRcPrecision) - 1u) | hi_f) & lo_m;
-                        // entry e - 1 of the same 16-lane row (DPP row_shr:1; entry 0 does not use it)
-                        const uint32_t right = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(left), 0x111, 0xf, 0xf, false));
-                        uint2 ent;
-                        ent.x = left;
-                        // P = right - left; the window's top entry of a window that reaches symbol 63 runs to 2^24: its right
-                        // neighbour (entry 0, symbol 64) holds the clamped 2^24 - 1, so the entry gets 1 more; the two sentinels get 0
-                        ent.y = (right - left + to_full) & win_keep_m;
-                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                        const u32x2 ent2 = {ent.x, ent.y};
-                        *lds_at<u32x2>(win_ent[k]) = ent2;
-                        *lds_at<int32_t>(win_top[k]) = top;
+                        uint32_t left[kEpl];
+#pragma unroll
+                        for (int j = 0; j < kEpl; ++j) {
+                            const int ssym = top - (e0 + j - 1);  // entry 0 -> top + 1: its left bound is the window's upper edge
+                            // window_left's edge cases from integers, ahead of the f64 chain and without compares next to their selects:
+                            // symbols <= -64 (and the lower sentinel) give 0; symbol 64 - entry 0 of a window that reaches symbol 63 -
+                            // gives 2^24, stored as 2^24 - 1 (every stored bound must fit 24 bits, see the wide pass)
+                            uint32_t lo_m = static_cast<uint32_t>((kAcLo - ssym) >> 31);
+                            if (j == kEpl - 1) lo_m &= win_left_m;
+                            uint32_t l = window_cum_d256(window_d256(idx_mu, ssym), rcp256, C.s_exp) + static_cast<uint32_t>(ssym - kAcLo);
+                            l = min(l, (1u << kRcPrecision) - 1u);
+                            if (j == 0) l |= hi_f;
+                            left[j] = l & lo_m;
+                            // one chain after the other: a pass is bound by the issue rate of its f64 instructions, not by their
+                            // latency, and two chains side by side only hold twice the registers
+                            if (j + 1 < kEpl) __builtin_amdgcn_sched_barrier(0);
+                        }
+                        // the entry in front of the lane's first one: the last entry of lane q - 1 (DPP row_shr:1; entry 0 does not use it)
+                        const uint32_t right = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(left[kEpl - 1]), 0x111, 0xf, 0xf, false));
+                        if constexpr (kEpl == 1) {
+                            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                            const u32x2 ent = {left[0], (right - left[0] + to_full) & win_keep_m};
+                            *lds_at<u32x2>(own_ent) = ent;
+                        } else {
+                            // entry 2 q + 1 is never entry 0, entry 2 q never entry 15 or 1
+                            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                            const u32x4 ent = {left[0], (right - left[0]) & win_keep_m, left[1], (left[0] - left[1] + to_full) & win_left_m};
+                            *lds_at<u32x4>(own_ent) = ent;
+                        }
                     }
                 }
                 unsigned rest = MF ? narrow_mask : 0u;
@@ -2086,7 +2181,14 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // LDS requests of one wave are performed in order: a relaxed add issued behind the table stores is enough for the
                 // decoder (a release would first wait for every outstanding LDS and global access of the wave)
                 asm volatile("" ::: "memory");
-                if (lane == 0) __hip_atomic_fetch_or(&C.s_ready[slot], 1u << half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (!MF) {
+                    // one ds_or_b32 from lane 0, address and value formed before the late wait; no lane election, no branch
+                    unsigned long long exec_all;
+                    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_or_b32 %1, %2\n\ts_mov_b64 exec, %0"
+                                 : "=&s"(exec_all) : "v"(rdy_addr), "v"(rdy_val) : "memory");
+                } else {
+                    if (lane == 0) __hip_atomic_fetch_or(&C.s_ready[slot], 1u << half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
                 __builtin_amdgcn_s_setprio(0);
                 asm volatile("" ::: "memory");
                 PROF_ADD(prof[3], t_t);
