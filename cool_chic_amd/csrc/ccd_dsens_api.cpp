@@ -365,11 +365,8 @@ static int add_candidate(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t*
     const ccd_cc_header& h = c.hdr;
     if (h.n_symbols < 0 || h.n_symbols > 0x7fffffff) return CCD_ERR_UNSUPPORTED;
     if (inter) {
-        const int taps = inter->warp_filter_size;
-        if (taps < 2 || taps > 16 || (taps & 1)) return CCD_ERR_VALUE;  // as ccd_inter_reconstruct
-        if (frame_data_type == 1 && ((h.img_size[0] | h.img_size[1]) & 1)) return CCD_ERR_VALUE;
-        const int want = inter->role == 0 ? (inter->frame_type == 2 ? 5 : 4) : (inter->frame_type == 2 ? 4 : 2);
-        if (h.out_channels != want) return CCD_ERR_VALUE;
+        if (!warp_filter_ok(inter->warp_filter_size) || !yuv420_sides_ok(frame_data_type, h.img_size[0], h.img_size[1])) return CCD_ERR_VALUE;
+        if (h.out_channels != inter_channels(inter->frame_type, inter->role)) return CCD_ERR_VALUE;
         c.is_inter = true;
         c.inter = *inter;
     }

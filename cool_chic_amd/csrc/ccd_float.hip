@@ -19,6 +19,7 @@
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
 #include "ccd_planes.hpp"
+#include "ccd_trig.hpp"
 
 namespace ccd {
 
@@ -359,29 +360,6 @@ hipError_t launch_final_resize(const float* in, float* out, int c, int h_in, int
 // exactly like the oracle (section 9c: fixed fma sequences for log and cos), one thread per sample with a
 // jump-ahead of the generator: sample i uses draws 2i+1 and 2i+2, seed_k = a^k seed_0 mod m.
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double cr_sin_core(double r) {
-    const double r2 = r * r;
-    double p = -7.6471637318198164759e-13;
-    p = fma(p, r2, 1.6059043836821614599e-10);
-    p = fma(p, r2, -2.5052108385441718775e-08);
-    p = fma(p, r2, 2.7557319223985890653e-06);
-    p = fma(p, r2, -1.9841269841269841270e-04);
-    p = fma(p, r2, 8.3333333333333333333e-03);
-    p = fma(p, r2, -1.6666666666666666667e-01);
-    return fma(p * r2, r, r);
-}
-__device__ __forceinline__ double cr_cos_core(double r) {
-    const double r2 = r * r;
-    double p = 4.7794773323873852974e-14;
-    p = fma(p, r2, -1.1470745597729724714e-11);
-    p = fma(p, r2, 2.0876756987868098979e-09);
-    p = fma(p, r2, -2.7557319223985890653e-07);
-    p = fma(p, r2, 2.4801587301587301587e-05);
-    p = fma(p, r2, -1.3888888888888888889e-03);
-    p = fma(p, r2, 4.1666666666666666667e-02);
-    p = fma(p, r2, -0.5);
-    return fma(p, r2, 1.0);
-}
 __device__ __forceinline__ double cr_log(double x) {
     unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(x));
     int e = static_cast<int>((bits >> 52) & 0x7ff) - 1022;
@@ -397,12 +375,10 @@ __device__ __forceinline__ double cr_log(double x) {
     const double ed = static_cast<double>(e);
     return fma(ed, 6.93147180369123816490e-01, fma(ed, 1.90821492927058770002e-10, r));
 }
-__device__ __forceinline__ double cr_cos(double x) {
-    const double q = rint(x * 6.36619772367581382433e-01);
-    double r = fma(-q, 1.57079632679489655800e+00, x);
-    r = fma(-q, 6.12323399573676603587e-17, r);
-    const int n = static_cast<int>(q) & 3;
-    const double v = (n & 1) ? cr_sin_core(r) : cr_cos_core(r);
+__device__ __forceinline__ double cr_cos(double x) {  // sin / cos cores and the reduction: ccd_trig.hpp
+    int n;
+    const double r = trig_reduce(x, &n);
+    const double v = (n & 1) ? trig_sin_core(r) : trig_cos_core(r);
     return (n == 1 || n == 2) ? -v : v;
 }
 
@@ -430,7 +406,7 @@ hipError_t launch_cr_noise(float* out, size_t n, hipStream_t stream) {
 // -------------------------------------------------------------------------------------------------
 // Integer planes of an intra frame (decode.py:191-206 + png.py:57-58 / yuv.py:152-160).
 // -------------------------------------------------------------------------------------------------
-// round_to_grid, quantise_sample: ccd_planes.hpp
+// round_to_grid, quantise_sample, quantise_chroma420: ccd_planes.hpp
 
 template <typename T>
 __global__ void planes_kernel(const float* __restrict__ src, T* p0, T* p1, T* p2, int h, int w, int yuv420, float maxv) {
@@ -452,11 +428,8 @@ __global__ void planes_kernel(const float* __restrict__ src, T* p0, T* p1, T* p2
             float sum = 0.0f;  // sequential f32 sum over the 2x2 window of samples already on the bit-depth grid
             for (int dy = 0; dy < 2; ++dy)
                 for (int dx = 0; dx < 2; ++dx) sum += round_to_grid(s[static_cast<size_t>(2 * y + dy) * w + 2 * x + dx], maxv);
-            float a = sum / 4.0f;
-            a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
-            a = rintf(a * maxv) / maxv;
             T* dst = c == 1 ? p1 : p2;
-            dst[static_cast<size_t>(y) * cw + x] = static_cast<T>(static_cast<unsigned>(rintf(a * maxv)));
+            dst[static_cast<size_t>(y) * cw + x] = static_cast<T>(quantise_chroma420(sum, maxv));
         }
     }
 }

@@ -70,6 +70,16 @@ struct Mirror {
 // Everything placed in a device block starts on a 256-byte boundary.
 inline size_t align256(size_t v) { return (v + 255) & ~size_t{255}; }
 
+// The rules of P / B frames that every entry point checks (ccd_inter_reconstruct, ccd_decode_video, ccd_dsens_add_inter).
+// 2 / 4 taps = grid_sample bilinear / bicubic, 6.. = sinc (warp.py:49-56); odd or < 2 fails the reference's asserts (warp.py:41-47)
+inline bool warp_filter_ok(int taps) { return taps >= 2 && taps <= 16 && !(taps & 1); }
+// output channels of the cool-chics of a P (1) / B (2) frame (decode.py:156-189): role 0, the residue, has three colours, alpha and
+// for B beta; role 1, the motion, one flow per reference
+inline int inter_channels(int frame_type, int role) { return role == 0 ? (frame_type == 2 ? 5 : 4) : (frame_type == 2 ? 4 : 2); }
+// 4:2:0 needs even sides: F.avg_pool2d(2) drops the odd row / column and write_yuv's chroma planes are h/2 x w/2, the reference's
+// 4:4:4 round trip (yuv.py:303-316) no longer matches the luma size, and planes_to_444_kernel would read past such a chroma plane
+inline bool yuv420_sides_ok(int frame_data_type, int h, int w) { return frame_data_type != 1 || !((h | w) & 1); }
+
 // Host image of tables that go to the device in one copy; put() returns the aligned offset of what it appended.
 struct TableImage {
     std::vector<char> bytes;

@@ -15,41 +15,20 @@
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
 #include "ccd_planes.hpp"
+#include "ccd_trig.hpp"
 
 namespace ccd {
 
 __device__ __forceinline__ int ic_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-__device__ __forceinline__ double ic_sin_core(double r) {
-    const double r2 = r * r;
-    double p = -7.6471637318198164759e-13;
-    p = fma(p, r2, 1.6059043836821614599e-10);
-    p = fma(p, r2, -2.5052108385441718775e-08);
-    p = fma(p, r2, 2.7557319223985890653e-06);
-    p = fma(p, r2, -1.9841269841269841270e-04);
-    p = fma(p, r2, 8.3333333333333333333e-03);
-    p = fma(p, r2, -1.6666666666666666667e-01);
-    return fma(p * r2, r, r);
-}
-__device__ __forceinline__ double ic_cos_core(double r) {
-    const double r2 = r * r;
-    double p = 4.7794773323873852974e-14;
-    p = fma(p, r2, -1.1470745597729724714e-11);
-    p = fma(p, r2, 2.0876756987868098979e-09);
-    p = fma(p, r2, -2.7557319223985890653e-07);
-    p = fma(p, r2, 2.4801587301587301587e-05);
-    p = fma(p, r2, -1.3888888888888888889e-03);
-    p = fma(p, r2, 4.1666666666666666667e-02);
-    p = fma(p, r2, -0.5);
-    return fma(p, r2, 1.0);
-}
-__device__ __forceinline__ void ic_sincos(float a, float* s_out, float* c_out) {
-    const double x = static_cast<double>(a);
-    const double q = rint(x * 6.36619772367581382433e-01);
-    double r = fma(-q, 1.57079632679489655800e+00, x);
-    r = fma(-q, 6.12323399573676603587e-17, r);
-    const int n = static_cast<int>(q) & 3;
-    const double sn = ic_sin_core(r), cs = ic_cos_core(r);
+// A 256-thread workgroup owns a 64 x 4 tile of pixels: the thread's pixel in tile (tx, ty), and the grid whose tiles cover h x w.
+__device__ __forceinline__ void tile_pixel(unsigned tx, unsigned ty, int* x, int* y) { *x = tx * 64 + (threadIdx.x & 63); *y = ty * 4 + (threadIdx.x >> 6); }
+static dim3 tile_grid(int h, int w) { return dim3((w + 63) / 64, (h + 3) / 4); }
+
+__device__ __forceinline__ void ic_sincos(float a, float* s_out, float* c_out) {  // cores and reduction: ccd_trig.hpp
+    int n;
+    const double r = trig_reduce(static_cast<double>(a), &n);
+    const double sn = trig_sin_core(r), cs = trig_cos_core(r);
     double sv = (n & 1) ? cs : sn, cv = (n & 1) ? sn : cs;
     if (n & 2) sv = -sv;
     if (n == 1 || n == 2) cv = -cv;
@@ -57,27 +36,12 @@ __device__ __forceinline__ void ic_sincos(float a, float* s_out, float* c_out) {
     *c_out = static_cast<float>(cv);
 }
 
-constexpr int kMaxTaps = 16;
-
-// warp.py:238-243
-__device__ __forceinline__ void ic_coeffs(float s, int n_taps, float* coef) {
-    const float pi_f = 3.14159265358979323846f;
-    for (int j = 0; j < n_taps; ++j) {
-        const float d = s - static_cast<float>(j - n_taps / 2 + 1);
-        float sn, unused_c, unused_s, win;
-        ic_sincos(pi_f * d / static_cast<float>(n_taps), &unused_s, &win);
-        float snc = 1.0f;
-        if (d != 0.0f) { const float a = pi_f * d; ic_sincos(a, &sn, &unused_c); snc = sn / a; }
-        coef[j] = win * snc;
-    }
-}
-
 // Integer planes of a decoded frame -> the [3][H][W] float tensor the warper reads (value = q / (2^bd - 1),
 // 4:2:0 chroma repeated 2x2).
 template <typename T>
 __global__ void planes_to_444_kernel(const T* p0, const T* p1, const T* p2, float* out, int h, int w, int chroma_half, float maxv) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    tile_pixel(blockIdx.x, blockIdx.y, &x, &y);
     if (x >= w || y >= h) return;
     const size_t plane = static_cast<size_t>(h) * w, i = static_cast<size_t>(y) * w + x;
     out[i] = static_cast<float>(p0[i]) / maxv;
@@ -89,7 +53,7 @@ __global__ void planes_to_444_kernel(const T* p0, const T* p1, const T* p2, floa
 
 hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, float* out, int h, int w, int bitdepth,
                                 int frame_data_type, hipStream_t stream) {
-    dim3 grid((w + 63) / 64, (h + 3) / 4);
+    const dim3 grid = tile_grid(h, w);
     const float maxv = static_cast<float>((1 << bitdepth) - 1);
     const int half = frame_data_type == 1;
     if (bitdepth == 8)
@@ -107,45 +71,29 @@ __device__ __forceinline__ int ic_tap_offset(float f, int size) {
     return static_cast<int>(fminf(fmaxf(f, -static_cast<float>(size + 16)), static_cast<float>(size + 16)));
 }
 
-__device__ __forceinline__ void ic_warp_pixel(const float* __restrict__ ref, int H, int W, int gx, int gy, int n_taps, float fx,
-                                              float fy, int y, int x, float out[3]) {
-    const float rxf = floorf(fx), ryf = floorf(fy);
-    const float sx = fx - rxf, sy = fy - ryf;
-    const int rx = ic_tap_offset(rxf, W), ry = ic_tap_offset(ryf, H);
-    float cx[kMaxTaps], cy[kMaxTaps];
-    ic_coeffs(sx, n_taps, cx);
-    ic_coeffs(sy, n_taps, cy);
-    const int lo = -(n_taps / 2) + 1;
-    const size_t plane = static_cast<size_t>(H) * W;
-    int xs[kMaxTaps];
-    for (int j = 0; j < n_taps; ++j) xs[j] = ic_clamp(ic_clamp(x + lo + j + rx, 0, W - 1) + gx, 0, W - 1);
-    for (int c = 0; c < 3; ++c) {
-        float acc = 0.0f;
-        for (int i = 0; i < n_taps; ++i) {
-            const int yy = ic_clamp(ic_clamp(y + lo + i + ry, 0, H - 1) + gy, 0, H - 1);
-            const float* row = ref + c * plane + static_cast<size_t>(yy) * W;
-            float line = 0.0f;
-            for (int j = 0; j < n_taps; ++j) line = __fmaf_rn(row[xs[j]], cx[j], line);
-            acc = __fmaf_rn(line, cy[i], acc);
-        }
-        out[c] = acc;
-    }
-}
-
-// The same with a compile-time tap count (r06): the runtime-sized version keeps cx / cy / xs in scratch memory (dynamic indexing
-// of per-thread arrays) and spent 0.5 ms per 1080p frame there - ccd_decode_video's 31 inter frames were 21 ms of a 190 ms call
-// (profiles/r06/gop_timing_before.txt).  Same operations in the same order: bit-identical.
+// ---- the sinc-windowed warp, templated on the tap count.  NT > 0: known at compile time, arrays of NT, every loop fully unrolled;
+// NT == 0: n_taps at run time, arrays of kMaxTaps, loops rolled.  r06: the run-time version keeps cx / cy / xs in scratch memory
+// (dynamic indexing of per-thread arrays) and spent 0.5 ms per 1080p frame there - ccd_decode_video's 31 inter frames were 21 ms of a
+// 190 ms call (profiles/r06/gop_timing_before.txt) - so the sinc-8 warp of every preset has its own instantiation.  Same operations
+// in the same order: bit-identical.
 // (r06, measured and dropped: evaluating only the polynomial the quadrant needs where a wave agrees on it - the window's cos does,
 // per tap - behind a ballot: bit-exact, and 0.55 ms per 1080p frame instead of 0.34: the scalar branches serialise what the
 // scheduler interleaves when all 32 evaluations of a pixel are straight-line code.)
+constexpr int kMaxTaps = 16;
+template <int NT> constexpr int kTapCap = NT > 0 ? NT : kMaxTaps;  // size of an array over the taps
+template <int NT> constexpr int kTapUnroll = NT > 0 ? NT : 1;       // unroll count of a loop over them (a bare `unroll` half-unrolls NT == 0)
+
+// warp.py:238-243
 template <int NT>
-__device__ __forceinline__ void ic_coeffs_t(float s, float (&coef)[NT]) {
+__device__ __forceinline__ void ic_coeffs(float s, int n_taps, float (&coef)[kTapCap<NT>]) {
+    constexpr int kUnroll = kTapUnroll<NT>;
+    const int nt = NT > 0 ? NT : n_taps;
     const float pi_f = 3.14159265358979323846f;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const float d = s - static_cast<float>(j - NT / 2 + 1);
+#pragma unroll kUnroll
+    for (int j = 0; j < nt; ++j) {
+        const float d = s - static_cast<float>(j - nt / 2 + 1);
         float sn, unused_c, unused_s, win;
-        ic_sincos(pi_f * d / static_cast<float>(NT), &unused_s, &win);
+        ic_sincos(pi_f * d / static_cast<float>(nt), &unused_s, &win);
         float snc = 1.0f;
         if (d != 0.0f) { const float a = pi_f * d; ic_sincos(a, &sn, &unused_c); snc = sn / a; }
         coef[j] = win * snc;
@@ -153,37 +101,30 @@ __device__ __forceinline__ void ic_coeffs_t(float s, float (&coef)[NT]) {
 }
 // the N x N taps of one pixel from its coefficients (rows accumulate in ascending order per channel: the oracle's chain)
 template <int NT>
-__device__ __forceinline__ void ic_taps_t(const float* __restrict__ ref, int H, int W, int gx, int gy, int rx, int ry, const float (&cx)[NT],
-                                          const float (&cy)[NT], int y, int x, float out[3]) {
-    constexpr int lo = -(NT / 2) + 1;
+__device__ __forceinline__ void ic_taps(const float* __restrict__ ref, int H, int W, int gx, int gy, int n_taps, int rx, int ry,
+                                        const float (&cx)[kTapCap<NT>], const float (&cy)[kTapCap<NT>], int y, int x, float out[3]) {
+    constexpr int kUnroll = kTapUnroll<NT>;
+    const int nt = NT > 0 ? NT : n_taps;
+    const int lo = -(nt / 2) + 1;
     const size_t plane = static_cast<size_t>(H) * W;
-    int xs[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) xs[j] = ic_clamp(ic_clamp(x + lo + j + rx, 0, W - 1) + gx, 0, W - 1);
+    int xs[kTapCap<NT>];
+#pragma unroll kUnroll
+    for (int j = 0; j < nt; ++j) xs[j] = ic_clamp(ic_clamp(x + lo + j + rx, 0, W - 1) + gx, 0, W - 1);
     float acc[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
+#pragma unroll kUnroll
+    for (int i = 0; i < nt; ++i) {
         const int yy = ic_clamp(ic_clamp(y + lo + i + ry, 0, H - 1) + gy, 0, H - 1);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* row = ref + c * plane + static_cast<size_t>(yy) * W;
             float line = 0.0f;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) line = __fmaf_rn(row[xs[j]], cx[j], line);
+#pragma unroll kUnroll
+            for (int j = 0; j < nt; ++j) line = __fmaf_rn(row[xs[j]], cx[j], line);
             acc[c] = __fmaf_rn(line, cy[i], acc[c]);
         }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = acc[c];
-}
-template <int NT>
-__device__ __forceinline__ void ic_warp_pixel_t(const float* __restrict__ ref, int H, int W, int gx, int gy, float fx, float fy, int y, int x, float out[3]) {
-    const float rxf = floorf(fx), ryf = floorf(fy);
-    const float sx = fx - rxf, sy = fy - ryf;
-    float cx[NT], cy[NT];
-    ic_coeffs_t<NT>(sx, cx);
-    ic_coeffs_t<NT>(sy, cy);
-    ic_taps_t<NT>(ref, H, W, gx, gy, ic_tap_offset(rxf, W), ic_tap_offset(ryf, H), cx, cy, y, x, out);
 }
 
 // ---- warp_filter_size 2 / 4: the Warper's native path = F.grid_sample(bilinear | bicubic, border, align_corners=True)
@@ -263,6 +204,27 @@ __device__ __forceinline__ void ic_warp_pixel_native(const float* __restrict__ r
     }
 }
 
+// one reference warped to pixel (y, x).  NT = 8: the sinc-8 warp of every preset; NT = 0: a run-time tap count - the native path for
+// 2 / 4 taps, the sinc warp for any even size from 6
+template <int NT>
+__device__ __forceinline__ void ic_warp(const float* __restrict__ ref, int H, int W, int gx, int gy, int n_taps, float fx, float fy, int y, int x,
+                                        float out[3]) {
+    if (NT == 0 && n_taps < 6) return ic_warp_pixel_native(ref, H, W, gx, gy, n_taps, fx, fy, y, x, out);
+    const float rxf = floorf(fx), ryf = floorf(fy);
+    const float sx = fx - rxf, sy = fy - ryf;
+    float cx[kTapCap<NT>], cy[kTapCap<NT>];
+    ic_coeffs<NT>(sx, n_taps, cx);
+    ic_coeffs<NT>(sy, n_taps, cy);
+    ic_taps<NT>(ref, H, W, gx, gy, n_taps, ic_tap_offset(rxf, W), ic_tap_offset(ryf, H), cx, cy, y, x, out);
+}
+
+// ---- the blend (decode.py:170-189): weight = clamp(alpha | beta + 0.5, 0, 1), prediction = beta w0 + (1 - beta) w1 (B frames),
+// sample = alpha prediction + residue.  Every multiply and every add is an operation of its own, never an fma: bit parity with
+// oracle/cc_oracle.c section 11.
+__device__ __forceinline__ float ic_weight(float v) { const float a = v + 0.5f; return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }
+__device__ __forceinline__ float ic_mix(float b, float w0, float w1) { const float t0 = b * w0, t1 = (1.0f - b) * w1; return t0 + t1; }
+__device__ __forceinline__ float ic_sample(float a, float pred, float residue) { const float m = a * pred; return m + residue; }
+
 struct InterParams {
     const float* residue;  // [4 | 5][H][W]
     const float* motion;   // [2 | 4][H][W]
@@ -272,34 +234,13 @@ struct InterParams {
     int frame_type, H, W, n_taps;
     int gflow[4];
 };
-
-template <int NT>  // 0: run-time tap count (any even size, and the native 2- / 4-tap paths); 8: the sinc-8 warp of every preset
-__global__ __launch_bounds__(256) void inter_recon_kernel(InterParams p) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= p.W || y >= p.H) return;
-    const size_t plane = static_cast<size_t>(p.H) * p.W, i = static_cast<size_t>(y) * p.W + x;
-    float a = p.residue[3 * plane + i] + 0.5f;
-    a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
-    float w0[3], pred[3];
-    if constexpr (NT > 0) ic_warp_pixel_t<NT>(p.ref0, p.H, p.W, p.gflow[0], p.gflow[1], p.motion[i], p.motion[plane + i], y, x, w0);
-    else if (p.n_taps < 6) ic_warp_pixel_native(p.ref0, p.H, p.W, p.gflow[0], p.gflow[1], p.n_taps, p.motion[i], p.motion[plane + i], y, x, w0);
-    else ic_warp_pixel(p.ref0, p.H, p.W, p.gflow[0], p.gflow[1], p.n_taps, p.motion[i], p.motion[plane + i], y, x, w0);
-    if (p.frame_type == 2) {
-        float b = p.residue[4 * plane + i] + 0.5f;
-        b = b < 0.0f ? 0.0f : (b > 1.0f ? 1.0f : b);
-        float w1[3];
-        if constexpr (NT > 0) ic_warp_pixel_t<NT>(p.ref1, p.H, p.W, p.gflow[2], p.gflow[3], p.motion[2 * plane + i], p.motion[3 * plane + i], y, x, w1);
-        else if (p.n_taps < 6) ic_warp_pixel_native(p.ref1, p.H, p.W, p.gflow[2], p.gflow[3], p.n_taps, p.motion[2 * plane + i], p.motion[3 * plane + i], y, x, w1);
-        else ic_warp_pixel(p.ref1, p.H, p.W, p.gflow[2], p.gflow[3], p.n_taps, p.motion[2 * plane + i], p.motion[3 * plane + i], y, x, w1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { const float t0 = b * w0[c], t1 = (1.0f - b) * w1[c]; pred[c] = t0 + t1; }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pred[c] = w0[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { const float m = a * pred[c]; p.out[c * plane + i] = m + p.residue[c * plane + i]; }
+static InterParams inter_params(int frame_type, int h, int w, int n_taps, const int* gflow, const float* residue, const float* motion,
+                                const float* ref0, const float* ref1, float* out) {
+    InterParams p;
+    p.residue = residue; p.motion = motion; p.ref0 = ref0; p.ref1 = ref1; p.out = out;
+    p.frame_type = frame_type; p.H = h; p.W = w; p.n_taps = n_taps;
+    for (int i = 0; i < 4; ++i) p.gflow[i] = gflow[i];
+    return p;
 }
 
 // ---- r06: the warp's coefficients ahead of the references.  A frame's flows (the motion cool-chic's output) are known long before
@@ -310,16 +251,16 @@ __global__ __launch_bounds__(256) void inter_recon_kernel(InterParams p) {
 // bit-identical to the one-kernel form.  Measured: the gather alone is 0.26 of the 0.34 ms - off by default (ccd_video.cpp).
 // coef layout: float4 [ref][4][H * W] - quad 0 / 1 = cx[0..3] / cx[4..7], quad 2 / 3 = cy: every access a coalesced 16 bytes per lane.
 __global__ __launch_bounds__(256) void inter_coef8_kernel(const float* __restrict__ motion, int H, int W, int n_refs, float4* __restrict__ coef) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    tile_pixel(blockIdx.x, blockIdx.y, &x, &y);
     if (x >= W || y >= H) return;
     const size_t plane = static_cast<size_t>(H) * W, i = static_cast<size_t>(y) * W + x;
     for (int r = 0; r < n_refs; ++r) {
         const float fx = motion[(2 * r) * plane + i], fy = motion[(2 * r + 1) * plane + i];
         const float sx = fx - floorf(fx), sy = fy - floorf(fy);
         float cx[8], cy[8];
-        ic_coeffs_t<8>(sx, cx);
-        ic_coeffs_t<8>(sy, cy);
+        ic_coeffs<8>(sx, 8, cx);
+        ic_coeffs<8>(sy, 8, cy);
         float4* o = coef + static_cast<size_t>(r) * 4 * plane + i;
         o[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
         o[plane] = make_float4(cx[4], cx[5], cx[6], cx[7]);
@@ -331,65 +272,70 @@ __device__ __forceinline__ void ic_warp_pixel_coef8(const float* __restrict__ re
                                                     int gy, float fx, float fy, int y, int x, float out[3]) {
     const float4 a = coef[i], b = coef[plane + i], c = coef[2 * plane + i], d = coef[3 * plane + i];
     const float cx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, cy[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-    ic_taps_t<8>(ref, H, W, gx, gy, ic_tap_offset(floorf(fx), W), ic_tap_offset(floorf(fy), H), cx, cy, y, x, out);
+    ic_taps<8>(ref, H, W, gx, gy, 8, ic_tap_offset(floorf(fx), W), ic_tap_offset(floorf(fy), H), cx, cy, y, x, out);
 }
-__global__ __launch_bounds__(256) void inter_apply8_kernel(InterParams p, const float4* __restrict__ coef) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+
+// reference r of the frame warped to pixel (y, x); AHEAD: the sinc-8 coefficients come from the `coef` block
+template <int NT, bool AHEAD>
+__device__ __forceinline__ void inter_warp_ref(const InterParams& p, const float4* __restrict__ coef, int r, size_t plane, size_t i, int y, int x,
+                                               float out[3]) {
+    const float* ref = r ? p.ref1 : p.ref0;
+    const float fx = p.motion[(2 * r) * plane + i], fy = p.motion[(2 * r + 1) * plane + i];
+    if constexpr (AHEAD) ic_warp_pixel_coef8(ref, coef + static_cast<size_t>(r) * 4 * plane, plane, i, p.H, p.W, p.gflow[2 * r], p.gflow[2 * r + 1], fx, fy, y, x, out);
+    else ic_warp<NT>(ref, p.H, p.W, p.gflow[2 * r], p.gflow[2 * r + 1], p.n_taps, fx, fy, y, x, out);
+}
+// One pixel of a P / B frame.  The mix stays inside the B branch, behind the second warp: hoisted behind both warps, the 8-tap
+// kernels need 256 registers and run one wave per SIMD.
+template <int NT, bool AHEAD>
+__device__ __forceinline__ void inter_recon_body(const InterParams& p, const float4* __restrict__ coef) {
+    int x, y;
+    tile_pixel(blockIdx.x, blockIdx.y, &x, &y);
     if (x >= p.W || y >= p.H) return;
     const size_t plane = static_cast<size_t>(p.H) * p.W, i = static_cast<size_t>(y) * p.W + x;
-    float a = p.residue[3 * plane + i] + 0.5f;
-    a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
+    const float a = ic_weight(p.residue[3 * plane + i]);
     float w0[3], pred[3];
-    ic_warp_pixel_coef8(p.ref0, coef, plane, i, p.H, p.W, p.gflow[0], p.gflow[1], p.motion[i], p.motion[plane + i], y, x, w0);
+    inter_warp_ref<NT, AHEAD>(p, coef, 0, plane, i, y, x, w0);
     if (p.frame_type == 2) {
-        float b = p.residue[4 * plane + i] + 0.5f;
-        b = b < 0.0f ? 0.0f : (b > 1.0f ? 1.0f : b);
+        const float b = ic_weight(p.residue[4 * plane + i]);
         float w1[3];
-        ic_warp_pixel_coef8(p.ref1, coef + 4 * plane, plane, i, p.H, p.W, p.gflow[2], p.gflow[3], p.motion[2 * plane + i], p.motion[3 * plane + i], y, x, w1);
+        inter_warp_ref<NT, AHEAD>(p, coef, 1, plane, i, y, x, w1);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { const float t0 = b * w0[c], t1 = (1.0f - b) * w1[c]; pred[c] = t0 + t1; }
+        for (int c = 0; c < 3; ++c) pred[c] = ic_mix(b, w0[c], w1[c]);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) pred[c] = w0[c];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { const float m = a * pred[c]; p.out[c * plane + i] = m + p.residue[c * plane + i]; }
+    for (int c = 0; c < 3; ++c) p.out[c * plane + i] = ic_sample(a, pred[c], p.residue[c * plane + i]);
 }
+template <int NT>  // 0: run-time tap count (any even size, and the native 2- / 4-tap paths); 8: the sinc-8 warp of every preset
+__global__ __launch_bounds__(256) void inter_recon_kernel(InterParams p) { inter_recon_body<NT, false>(p, nullptr); }
+__global__ __launch_bounds__(256) void inter_apply8_kernel(InterParams p, const float4* __restrict__ coef) { inter_recon_body<8, true>(p, coef); }
+
 size_t inter_coef_bytes(int frame_type, int h, int w) { return static_cast<size_t>(frame_type == 2 ? 2 : 1) * 4 * h * w * sizeof(float4); }
 hipError_t launch_inter_coef8(int frame_type, int h, int w, const float* motion, void* coef, hipStream_t stream) {
-    dim3 grid((w + 63) / 64, (h + 3) / 4);
-    hipLaunchKernelGGL(inter_coef8_kernel, grid, dim3(256), 0, stream, motion, h, w, frame_type == 2 ? 2 : 1, static_cast<float4*>(coef));
+    hipLaunchKernelGGL(inter_coef8_kernel, tile_grid(h, w), dim3(256), 0, stream, motion, h, w, frame_type == 2 ? 2 : 1, static_cast<float4*>(coef));
     return hipGetLastError();
 }
 hipError_t launch_inter_apply8(int frame_type, int h, int w, const int* gflow, const float* residue, const float* motion, const float* ref0,
                                const float* ref1, const void* coef, float* out, hipStream_t stream) {
-    InterParams p;
-    p.residue = residue; p.motion = motion; p.ref0 = ref0; p.ref1 = ref1; p.out = out;
-    p.frame_type = frame_type; p.H = h; p.W = w; p.n_taps = 8;
-    for (int i = 0; i < 4; ++i) p.gflow[i] = gflow[i];
-    dim3 grid((w + 63) / 64, (h + 3) / 4);
-    hipLaunchKernelGGL(inter_apply8_kernel, grid, dim3(256), 0, stream, p, static_cast<const float4*>(coef));
+    const InterParams p = inter_params(frame_type, h, w, 8, gflow, residue, motion, ref0, ref1, out);
+    hipLaunchKernelGGL(inter_apply8_kernel, tile_grid(h, w), dim3(256), 0, stream, p, static_cast<const float4*>(coef));
     return hipGetLastError();
 }
-
 hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const int* gflow, const float* residue, const float* motion,
                               const float* ref0, const float* ref1, float* out, hipStream_t stream) {
-    InterParams p;
-    p.residue = residue; p.motion = motion; p.ref0 = ref0; p.ref1 = ref1; p.out = out;
-    p.frame_type = frame_type; p.H = h; p.W = w; p.n_taps = n_taps;
-    for (int i = 0; i < 4; ++i) p.gflow[i] = gflow[i];
-    dim3 grid((w + 63) / 64, (h + 3) / 4);
-    if (n_taps == 8) hipLaunchKernelGGL(inter_recon_kernel<8>, grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(inter_recon_kernel<0>, grid, dim3(256), 0, stream, p);
+    const InterParams p = inter_params(frame_type, h, w, n_taps, gflow, residue, motion, ref0, ref1, out);
+    if (n_taps == 8) hipLaunchKernelGGL(inter_recon_kernel<8>, tile_grid(h, w), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(inter_recon_kernel<0>, tile_grid(h, w), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 
 // ---- distortion deltas of P / B frames (ccd_dsens_add_inter): reconstruction and integer planes of every probe
 // slot of a round in one launch.  A job is one slot; its workgroups find it in a prefix table (entry_of), as the other dsens kernels
-// find their entries.  Per sample the operations of inter_recon_kernel (same device functions, multiply and add of the blend
-// separate) followed by those of planes_kernel (ccd_float.hip; the sample helpers are shared, ccd_planes.hpp: round to the bit-depth grid, clamp, round; 4:2:0 chroma = the
-// sequential f32 sum of the quad's rounded samples, / 4, clamp, round): the f32 that inter_recon_kernel stores and planes_kernel
+// find their entries.  Per sample the operations of inter_recon_kernel (same device functions: ic_warp and the blend
+// pieces) followed by those of planes_kernel (ccd_float.hip; the sample helpers are shared, ccd_planes.hpp: round to the bit-depth grid, clamp, round; 4:2:0 chroma = the
+// sequential f32 sum of the quad's rounded samples, then quantise_chroma420): the f32 that inter_recon_kernel stores and planes_kernel
 // loads is the register in between, so the planes are those of ccd_inter_reconstruct bit for bit.  What a residue probe cannot
 // change - the warped references - is computed by the base job of a run (mode 0), kept as f32 and only read by residue probes
 // (mode 1); a motion probe (mode 2) warps.  Every output word has one writer: a thread owns one luma sample or, 4:2:0, one 2 x 2
@@ -399,20 +345,11 @@ __device__ __forceinline__ void di_store(void* plane, size_t at, unsigned v, int
     else static_cast<uint8_t*>(plane)[at] = static_cast<uint8_t>(v);
 }
 
-template <int NT>
-__device__ __forceinline__ void di_warp(const DsensInterJob& J, const float* __restrict__ ref, int gx, int gy, float fx, float fy, int y, int x,
-                                        float out[3]) {
-    if constexpr (NT > 0) ic_warp_pixel_t<NT>(ref, J.H, J.W, gx, gy, fx, fy, y, x, out);
-    else if (J.n_taps < 6) ic_warp_pixel_native(ref, J.H, J.W, gx, gy, J.n_taps, fx, fy, y, x, out);
-    else ic_warp_pixel(ref, J.H, J.W, gx, gy, J.n_taps, fx, fy, y, x, out);
-}
-
-// the frame's float sample (y, x) of the three channels: inter_recon_kernel's body
+// the frame's float sample (y, x) of the three channels: what inter_recon_body stores, from the same pieces
 template <int NT>
 __device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, float out[3]) {
     const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
-    float a = J.residue[3 * plane + i] + 0.5f;
-    a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
+    const float a = ic_weight(J.residue[3 * plane + i]);
     const bool two = J.frame_type == 2;
     float w0[3] = {0.0f, 0.0f, 0.0f}, w1[3] = {0.0f, 0.0f, 0.0f}, pred[3];
     if (J.mode == 1) {
@@ -425,8 +362,8 @@ __device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, f
 #pragma unroll 1
         for (int r = 0; r < n_refs; ++r) {
             float w[3];
-            di_warp<NT>(J, r ? J.ref1 : J.ref0, r ? J.gflow[2] : J.gflow[0], r ? J.gflow[3] : J.gflow[1], J.motion[(2 * r) * plane + i],
-                        J.motion[(2 * r + 1) * plane + i], y, x, w);
+            ic_warp<NT>(r ? J.ref1 : J.ref0, J.H, J.W, r ? J.gflow[2] : J.gflow[0], r ? J.gflow[3] : J.gflow[1], J.n_taps,
+                        J.motion[(2 * r) * plane + i], J.motion[(2 * r + 1) * plane + i], y, x, w);
 #pragma unroll
             for (int c = 0; c < 3; ++c) { w0[c] = r == 0 ? w[c] : w0[c]; w1[c] = r == 1 ? w[c] : w1[c]; }
         }
@@ -436,16 +373,15 @@ __device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, f
         }
     }
     if (two) {
-        float b = J.residue[4 * plane + i] + 0.5f;
-        b = b < 0.0f ? 0.0f : (b > 1.0f ? 1.0f : b);
+        const float b = ic_weight(J.residue[4 * plane + i]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { const float t0 = b * w0[c], t1 = (1.0f - b) * w1[c]; pred[c] = t0 + t1; }
+        for (int c = 0; c < 3; ++c) pred[c] = ic_mix(b, w0[c], w1[c]);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) pred[c] = w0[c];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { const float m = a * pred[c]; out[c] = m + J.residue[c * plane + i]; }
+    for (int c = 0; c < 3; ++c) out[c] = ic_sample(a, pred[c], J.residue[c * plane + i]);
 }
 
 template <int NT>  // as inter_recon_kernel: 8 = the sinc-8 warp of every preset, 0 = a run-time tap count and the native paths
@@ -454,8 +390,8 @@ __global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* _
     const int j = entry_of(prefix, n_jobs, blk);
     const DsensInterJob J = jobs[j];  // (uniform: scalar registers)
     const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
-    const int ux = static_cast<int>(local % tiles_x) * 64 + (threadIdx.x & 63);
-    const int uy = static_cast<int>(local / tiles_x) * 4 + (threadIdx.x >> 6);
+    int ux, uy;
+    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
     const int cs = J.chroma_shift;
     if (ux >= (J.W >> cs) || uy >= (J.H >> cs)) return;  // (4:2:0 frames have even sides)
     const float maxv = J.maxv;
@@ -477,13 +413,8 @@ __global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* _
     }
     if (!cs) return;
     const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
-#pragma unroll
-    for (int c = 1; c < 3; ++c) {
-        float a = (c == 1 ? sum1 : sum2) / 4.0f;
-        a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
-        a = rintf(a * maxv) / maxv;
-        di_store(J.plane[c], ci, static_cast<unsigned>(rintf(a * maxv)), J.wide);
-    }
+    di_store(J.plane[1], ci, quantise_chroma420(sum1, maxv), J.wide);
+    di_store(J.plane[2], ci, quantise_chroma420(sum2, maxv), J.wide);
 }
 
 hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {

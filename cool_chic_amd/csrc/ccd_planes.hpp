@@ -1,5 +1,6 @@
 // ccd_planes.hpp - the sample step of the integer planes (decode.py:191-206 + png.py:57-58 / yuv.py:152-160), shared by the kernels
-// that must agree bit for bit: planes_kernel (ccd_float.hip) and dsens_inter_kernel (ccd_inter.hip).
+// that must agree bit for bit: planes_kernel (ccd_float.hip), syn_fused_kernel (ccd_synth_fused.hip) and dsens_inter_kernel
+// (ccd_inter.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,5 +12,14 @@ __device__ __forceinline__ unsigned quantise_sample(float x, float maxv) {
     q = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
     q = rintf(q * maxv) / maxv;
     return static_cast<unsigned>(rintf(q * maxv));
+}
+
+// a 4:2:0 chroma sample from `sum`, the sequential f32 sum of the 2 x 2 window's round_to_grid samples (dy outer, dx inner):
+// F.avg_pool2d(kernel 2, stride 2), yuv.py:295, then clamp, round to the grid, round
+__device__ __forceinline__ unsigned quantise_chroma420(float sum, float maxv) {
+    float a = sum / 4.0f;
+    a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);
+    a = rintf(a * maxv) / maxv;
+    return static_cast<unsigned>(rintf(a * maxv));
 }
 }  // namespace ccd

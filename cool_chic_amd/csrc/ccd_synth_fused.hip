@@ -21,6 +21,7 @@
 
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
+#include "ccd_planes.hpp"
 
 namespace ccd {
 
@@ -31,14 +32,6 @@ constexpr int kSfPerThread = kSfPos / kSfThreads;  // 8
 constexpr int kSfGroup = 4;                        // pixels evaluated together in phase 1
 
 __device__ __forceinline__ int sf_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ float sf_round_to_grid(float x, float maxv) { return rintf(maxv * x) / maxv; }
-__device__ __forceinline__ unsigned sf_quantise(float x, float maxv) {
-    float q = sf_round_to_grid(x, maxv);
-    q = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
-    q = rintf(q * maxv) / maxv;
-    return static_cast<unsigned>(rintf(q * maxv));
-}
 
 // CP = input channels padded to a multiple of 4 (extra inputs are 0 with 0 weights: fma(0, 0, acc) == acc),
 // C = channels after the second 1x1 layer (= channels of the conv layers and of the output).
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(kSfThreads) void syn_fused_kernel(const SynthFused*
         if (p.write_planes) {  // rgb / yuv444 integer samples (decode.py:191-206); yuv420 goes through planes_kernel
 #pragma unroll
             for (int j = 0; j < (C < 3 ? C : 3); ++j) {
-                const unsigned q = sf_quantise(out[j], maxv);
+                const unsigned q = quantise_sample(out[j], maxv);
                 if (p.bitdepth == 8) ((uint8_t __attribute__((address_space(1)))*)p.plane[j])[idx] = static_cast<uint8_t>(q);
                 else ((uint16_t __attribute__((address_space(1)))*)p.plane[j])[idx] = static_cast<uint16_t>(q);
             }

@@ -56,6 +56,20 @@ def rd_cost(sse: Sequence[int], n: Sequence[int], bitdepth: int, total_bits: flo
     return mse, bits, mse + float(lmbda) * bits / float(n_pixels)
 
 
+def move_scales(n_samples: int, bitdepth: int, n_pixels: int, lmbda: float):
+    """(kD, kR): what one unit of squared error and one bit add to rd_cost's cost."""
+    maxv = float(2 ** bitdepth - 1)
+    return 1.0 / (float(n_samples) * maxv * maxv), float(lmbda) / float(n_pixels)
+
+
+def move_cost_map(dd: torch.Tensor, db: torch.Tensor, n_samples: int, bitdepth: int, n_pixels: int, lmbda: float) -> torch.Tensor:
+    """rd_cost's definition applied to the +-1 moves of a grid (dd: int64 distortion deltas, db: float64 rate deltas), in float64;
+    +inf where the move leaves [-64, 63]."""
+    maxv = float(2 ** bitdepth - 1)
+    cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(n_pixels)
+    return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)
+
+
 class RdEvaluator:
     """add() candidates, then evaluate(lmbda): one DecodeBatch of given latents, one EncodeBatch over the same device grids,
     one scoring.  evaluate() may be called again (another lambda, or after device latents were changed in place)."""
@@ -172,11 +186,9 @@ class RdEvaluator:
         dev = f"cuda:{self.device}"
         f = self._frames[slot]
         n_samples = sum(int(t.numel()) for t in self._sources[slot])
-        maxv = float(2 ** f.bitdepth - 1)
         dd = torch.as_tensor(self.distortion_delta_map(slot, grid), device=dev)
         db = torch.as_tensor(self.rate_delta_map(slot, grid), device=dev).to(torch.float64)
-        cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(f.n_pixels)
-        return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)
+        return move_cost_map(dd, db, n_samples, f.bitdepth, f.n_pixels, lmbda)
 
     def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids: Optional[Sequence[int]] = None) -> List[List[StepReport]]:
         """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True), then
@@ -207,10 +219,9 @@ class RdEvaluator:
             self._rdoq.add(self._jobs[s][0], FRAME_DATA_TYPES.index(f.frame_data_type), self._caller_ptrs[s])
         kD, kR, masks = [], [], []
         for s, f in enumerate(self._frames):
-            n_samples = sum(int(t.numel()) for t in self._sources[s])
-            maxv = float(2 ** f.bitdepth - 1)
-            kD.append(1.0 / (float(n_samples) * maxv * maxv))
-            kR.append(float(lmbda) / float(f.n_pixels))
+            d, r = move_scales(sum(int(t.numel()) for t in self._sources[s]), f.bitdepth, f.n_pixels, lmbda)
+            kD.append(d)
+            kR.append(r)
             n_grids = int(self._jobs[s][0].n_grids)
             masks.append(sum(1 << g for g in (range(n_grids) if grids is None else grids) if 0 <= g < n_grids))
         reports: List[List[StepReport]] = []

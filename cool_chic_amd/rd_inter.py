@@ -19,11 +19,11 @@ import torch
 
 from ._lib import CCHeader, check, lib
 from .batch import FRAME_DATA_TYPES, DecodeBatch
-from .dsens import SENTINEL, DistortionDeltas
+from .dsens import DistortionDeltas
 from .encoder import EncodeBatch, SlotRate
 from .io import FrameData
 from .quality import FrameQuality, QualityMeter, _frame_planes
-from .rd import rd_cost
+from .rd import move_cost_map, move_scales, rd_cost
 from .rdoq import RdoqStep, StepResult
 
 ROLES = ("residue", "motion")
@@ -232,11 +232,9 @@ class InterRdEvaluator:
         dev = f"cuda:{self.device}"
         f = self._frames[frame]
         n_samples = sum(int(t.numel()) for t in f.src)
-        maxv = float(2 ** f.source.bitdepth - 1)
         dd = torch.as_tensor(self.distortion_delta_map(frame, role, grid), device=dev)
         db = torch.as_tensor(self.rate_delta_map(frame, role, grid), device=dev).to(torch.float64)
-        cost = dd.to(torch.float64) / (float(n_samples) * maxv * maxv) + float(lmbda) * db / float(f.source.n_pixels)
-        return torch.where((dd == SENTINEL) | torch.isinf(db), torch.full_like(cost, float("inf")), cost)
+        return move_cost_map(dd, db, n_samples, f.source.bitdepth, f.source.n_pixels, lmbda)
 
     def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids=None,
                 roles: Sequence[Union[str, int]] = ROLES) -> List[List[InterStepReport]]:
@@ -268,9 +266,9 @@ class InterRdEvaluator:
         kD, kR = [], []
         for s in range(2 * n):
             f = self._frames[s // 2]
-            maxv = float(2 ** f.source.bitdepth - 1)
-            kD.append(1.0 / (float(sum(int(t.numel()) for t in f.src)) * maxv * maxv))
-            kR.append(float(lmbda) / float(f.source.n_pixels))
+            d, r = move_scales(sum(int(t.numel()) for t in f.src), f.source.bitdepth, f.source.n_pixels, lmbda)
+            kD.append(d)
+            kR.append(r)
         reports: List[List[InterStepReport]] = []
         idle = 0
         for step in range(int(max_steps)):
