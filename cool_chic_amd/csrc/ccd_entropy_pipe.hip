@@ -56,7 +56,7 @@ namespace ccd {
 #define PROF_ADD(var, t0) (void)(t0)
 #define PROF_SUB(var, t0) (void)(t0)
 #endif
-// level 2 only: stamps per task of producer 0 (idle before the early wait, early work, late wait, late work)
+// level 2 only, matrix-core body: a stamp of TaskClock (the vector-ALU body's stamps are its methods)
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2 && defined(CCD_PIPE_TRACE)
 #define LPROF_T(cond) __builtin_amdgcn_s_memtime()
 #elif defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2
@@ -74,6 +74,9 @@ constexpr int kTraceTasks = 512;  // (16 KB: the kernel's own regions take ~128 
 constexpr uint32_t kTraceLdsBytes = kTraceTasks * 32u;
 __device__ unsigned int g_trace[kTraceTasks * 8];
 __device__ unsigned int g_trace_cfg[2];
+constexpr bool kProfTrace = true;
+#else
+constexpr bool kProfTrace = false;
 #endif
 
 // widest step of a grid >= CCD_T8 pixels: 8-pixel tasks; >= CCD_T4: 4-pixel tasks; else 2-pixel tasks (tunable at build time)
@@ -230,14 +233,6 @@ struct DecState {
 
 __device__ __forceinline__ void lds_write_release(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// LDS requests of one wave are performed in order, so a relaxed flag store issued after the payload
-// stores is enough for hand-over inside the workgroup; unlike a release it does not also wait for the
-// wave's outstanding GLOBAL stores (the decoder's writes to the latent grid).
-__device__ __forceinline__ void lds_write_ordered(uint32_t* p, uint32_t v) {
-    asm volatile("" ::: "memory");
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    asm volatile("" ::: "memory");
 }
 // All lanes read the same word; readfirstlane tells the compiler the result is wave-uniform so that the
 // control flow hanging off it (and every value defined inside) stays scalar.
@@ -1036,11 +1031,6 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
 // =================================================================================================
 // PRODUCERS (waves 1..): one grid.  NV = in_pad / 4.
 // =================================================================================================
-__device__ __forceinline__ int64_t dot4(int4 x, int4 w) {
-    return static_cast<int64_t>(x.x) * w.x + static_cast<int64_t>(x.y) * w.y + static_cast<int64_t>(x.z) * w.z +
-           static_cast<int64_t>(x.w) * w.w;
-}
-
 // One v_mad_i64_i32 per multiply-add.  The empty asm pins every partial sum: without it the optimiser re-associates
 // the wrapping int64 sums into one long dependent chain per output and expands part of the products into 64 x 64
 // multiplies (an asm statement holding the instruction itself makes the hazard recogniser pad every one with s_nop).
@@ -1077,10 +1067,6 @@ __device__ __forceinline__ void mad64_seq(int64_t& acc, int32_t x, int32_t w) {
     _Pragma("unroll") for (int g_ = 0; g_ < (NCH); ++g_) mad64_seq(ACC[g_], (X).w, Wv[g_].w);
 #define CCD_MAD4_PAIR_SEQ(ACC, ACC2, X, Wv)                                         \
     mad64_seq(ACC[0], (X).x, Wv[0].x); mad64_seq(ACC2, (X).y, Wv[0].y); mad64_seq(ACC[0], (X).z, Wv[0].z); mad64_seq(ACC2, (X).w, Wv[0].w);
-// four partial sums, one per component (the output layer; wrapping int64 addition is associative: the same bits)
-#define CCD_MAD4_QUAD_SEQ(A4, X, W4)                                                \
-    mad64_seq(A4[0], (X).x, (W4).x); mad64_seq(A4[1], (X).y, (W4).y); mad64_seq(A4[2], (X).z, (W4).z); mad64_seq(A4[3], (X).w, (W4).w);
-
 
 // ---- the ARM on the matrix cores (MF = true) ---------------------------------------------------------------------------
 // v_mfma_i32_16x16x64_i8 with N = the (<= 16) pixels of a task, M = output neurons, K = (input, signed-digit byte):
@@ -1341,8 +1327,65 @@ __device__ __forceinline__ int32_t table_index(int64_t sum, int32_t off, int32_t
 static_assert(kMuOffset < (1 << 29) && kScaleOffset < (1 << 29) && kMuOffset >= 0 && kScaleOffset >= 0, "table_index: offsets");
 static_assert(offsetof(RowMeta, top) - offsetof(RowMeta, mu_idx) == (kRows + 2) * 4, "a pixel's top symbol is stored (kRows + 2) words behind its mu index");
 
-// MF: this grid's tasks run the ARM on the matrix cores; DYN_RING: the kernel's ring of decoded symbols has
-// EntropyParams::ring_rows rows instead of kRingRows (every grid of a matrix-core kernel, whichever producer serves it).
+#if defined(CCD_PIPE_PROFILE)
+constexpr int kProfLevel = CCD_PIPE_PROFILE;
+#else
+constexpr int kProfLevel = 0;
+#endif
+// The profile of a producer's tasks (CCD_PIPE_PROFILE 2 / 3 and the trace, see the top of the file), out of the task bodies: in
+// a production build every method is empty.  Level 2: stamps a .. d and the task's end, summed into prof[0..3] (idle / early
+// work / late wait / late work), prof[4] (between tasks), prof[8] (tasks).  Level 3: begin(phase) ... add / sub(counter,
+// phase): prof[0] waits, [1] gather, [2] the MLP without its late wait, [3] window tables, [4..7] parts of the MLP, [8] tasks.
+struct TaskClock {
+    enum Phase { kWait, kGather, kMlp, kStab, kHidden, kOut, kTables, kPhases };
+    unsigned long long* prof;
+    bool p0;  // this wave is producer 0
+    unsigned long long a = 0, b = 0, c = 0, d = 0, prev_end = 0, t[kPhases];
+    __device__ __forceinline__ TaskClock(unsigned long long* prof_, int pw) : prof(prof_), p0(pw == 0) {}
+    __device__ __forceinline__ unsigned long long stamp() const { return (kProfTrace || p0) ? __builtin_amdgcn_s_memtime() : 0ull; }
+    __device__ __forceinline__ void task_begin() { if constexpr (kProfLevel == 2) { a = stamp(); if (p0 && prev_end) prof[4] += a - prev_end; } }
+    __device__ __forceinline__ void early_wait_end() { if constexpr (kProfLevel == 2) b = stamp(); }
+    __device__ __forceinline__ void late_wait_begin() { if constexpr (kProfLevel == 2) c = stamp(); }
+    __device__ __forceinline__ void late_wait_end() { if constexpr (kProfLevel == 2) d = stamp(); }
+    __device__ __forceinline__ void task_end(const PipeCtx& C, uint32_t W, uint32_t steps_left, uint32_t gidx, uint32_t word0, uint32_t px_ahead) {
+        if constexpr (kProfLevel == 2) {
+            const unsigned long long e = __builtin_amdgcn_s_memtime();
+#if defined(CCD_PIPE_TRACE)
+            if ((threadIdx.x & 63) == 0 && W == uni(g_trace_cfg[0]) && uni(g_trace_cfg[1]) - steps_left < 64u) {
+                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                u32x4* r = reinterpret_cast<u32x4*>(ccd_pipe_smem + C.trace_off + (gidx % kTraceTasks) * 32u);
+                r[0] = u32x4{word0, static_cast<uint32_t>(a), static_cast<uint32_t>(b), static_cast<uint32_t>(c)};
+                r[1] = u32x4{static_cast<uint32_t>(d), static_cast<uint32_t>(e), px_ahead, static_cast<uint32_t>(a >> 32)};
+            }
+#endif
+            if (p0) { prof[0] += b - a; prof[1] += c - b; prof[2] += d - c; prof[3] += e - d; prof[8] += 1; prev_end = e; }
+        }
+    }
+    __device__ __forceinline__ void begin(Phase p) { if constexpr (kProfLevel >= 3) t[p] = __builtin_amdgcn_s_memtime(); }
+    __device__ __forceinline__ void add(int k, Phase p) { if constexpr (kProfLevel >= 3) prof[k] += __builtin_amdgcn_s_memtime() - t[p]; }
+    __device__ __forceinline__ void sub(int k, Phase p) { if constexpr (kProfLevel >= 3) prof[k] -= __builtin_amdgcn_s_memtime() - t[p]; }
+    __device__ __forceinline__ void count_task() { if constexpr (kProfLevel >= 3) prof[8] += 1; }
+};
+// ---- two pieces of the vector-ALU task body that compile to the same code as functions --------------------------------------
+// Where the decoder puts the pixel's symbol (RowMeta::cell / goff), written right behind the early wait (`row`: kRows = dummy)
+__device__ __forceinline__ void store_row_position(RowMeta& meta, int row, int y, int x, int W, int ring_mask) {
+    meta.cell[row] = static_cast<uint32_t>(((y & ring_mask) << 6) | ((x + 10 * y) & 63));
+    meta.goff[row] = static_cast<uint32_t>(y * W + x);
+}
+// The task's ready bit, behind its table stores: LDS requests of one wave are performed in order, so a relaxed or is enough (a
+// release would wait for every outstanding access of the wave).  One ds_or_b32 from lane 0, operands in VGPRs; no election, no branch
+__device__ __forceinline__ void publish_ready(uint32_t rdy_addr, uint32_t rdy_val) {
+    asm volatile("" ::: "memory");
+    unsigned long long exec_all;
+    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_or_b32 %1, %2\n\ts_mov_b64 exec, %0"
+                 : "=&s"(exec_all) : "v"(rdy_addr), "v"(rdy_val) : "memory");
+}
+// One segment of a grid (all of it, or a ramp / the streamed body: GridSeg): the walk over its steps and tasks and, in the task
+// loop, the vector-ALU task body (production) phase by phase.  MF: this grid's tasks run the ARM on the matrix cores instead
+// (the branch in front of it); DYN_RING: the kernel's ring of decoded symbols has EntropyParams::ring_rows rows instead of
+// kRingRows (every grid of a matrix-core kernel, whichever producer serves it).  Returns the batch number behind the segment.
+// The vector-ALU body stands in the loop as it is: at the register limit, a phase moved into a function of its own compiles to
+// other code (profiles/r10/extractions.txt, tools/isa_compare.py).
 template <int NV, int kLpp, bool MF, bool DYN_RING, bool DYN, class SH>
 __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned long long* prof, const GridSeg& seg) {
     constexpr int in_pad = 4 * NV;
@@ -1379,17 +1422,14 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
     // (the tile's size is the KERNEL's - DYN_RING = its MF - not this instantiation's: since r04 the producers of one grid may be in
     // different instantiations at the same time, the 4-pixel one on a ramp while another wave is already in the 8-pixel body)
     int32_t* act = C.s_act + pw * ((DYN_RING ? 16 : 8) * in_pad + 4);
-    int32_t* const act_dummy = act + (DYN_RING ? 16 : 8) * in_pad;
-    (void)act_dummy;
+    [[maybe_unused]] int32_t* const act_dummy = act + (DYN_RING ? 16 : 8) * in_pad;
     const int px = MF ? (lane & 15) : lane / kLpp;   // pixel of the task
     const int q = MF ? (lane >> 4) : lane % kLpp;    // lane within the pixel's group (MF: K-slot group of the matrix operands)
-    const int ring_mask = DYN_RING ? uni(C.ring_mask) : kRingRows - 1, n_if = uni(C.n_if), mf_bits = uni(P.mfma);
-    (void)n_if; (void)mf_bits;
+    const int ring_mask = DYN_RING ? uni(C.ring_mask) : kRingRows - 1;
+    [[maybe_unused]] const int n_if = uni(C.n_if), mf_bits = uni(P.mfma);
     const int4* act_row = reinterpret_cast<const int4*>(act + px * in_pad);
     // Per-lane constants of the gather: the lane always fetches inputs k = q + kLpp t.  Read through the parameter block
     // inside the task loop they were global loads on every task's path.
-    unsigned long long lt_prev_end = 0;  // level-1 profile: end of producer 0's previous task
-    (void)lt_prev_end;
     int ctx_dy_l[NOUT], ctx_dx_l[NOUT];
 #pragma unroll
     for (int t = 0; t < NOUT; ++t) {
@@ -1403,7 +1443,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
     const int fstride = SH::fixed ? feat_stride(SH::dim - SH::n_sp) : uni(C.fstride);
     // MF: the lane's context offsets (k = q + 4 t, dy << 16 | dx) and the left neighbour's weights of the lane's rows
     // (neurons 4 q .. 4 q + 3 and 16 + q, then the two stabiliser outputs)
-    int32_t mf_dxy[8], mf_wl[7];
+    [[maybe_unused]] int32_t mf_dxy[8], mf_wl[7];
     if constexpr (MF) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -1421,7 +1461,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
             mf_wl[r] = w;
         }
     }
-    (void)mf_dxy; (void)mf_wl;
+    TaskClock clk(prof, pw);
     constexpr uint32_t kTaskShift = kTaskPix == 8 ? 3 : (kTaskPix == 4 ? 2 : 1), kBpxShift = kBpx == 32 ? 5 : (kBpx == 16 ? 4 : 3), kHalvesShift = kBpxShift - kTaskShift;
     StepWalk it;
     it.init(static_cast<uint32_t>(uni(C.H)), static_cast<uint32_t>(W));
@@ -1461,7 +1501,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
         const uint32_t seq0 = seq;
         uint32_t t_first = static_cast<uint32_t>(pw) - phase;
         t_first += static_cast<int32_t>(t_first) < 0 ? kProducers : 0;
-        {
+        {   // the task: its position, then its body (matrix cores or vector ALU), then the shared tail
             for (uint32_t task = t_first; task < n_tasks; task += kProducers) {
                 const uint32_t j = task >> kHalvesShift;
                 const int half = static_cast<int>(task & (kHalves - 1));
@@ -1482,7 +1522,8 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 const int y = static_cast<int>(in_b ? by0 : it.y0) + ii, x = static_cast<int>(in_b ? bx0 : it.x0) - 10 * ii;
                 const uint32_t dy1 = it.moved, dy2 = it.moved + prev_moved;
                 const uint32_t prev_n = pix0 - prev_pix0, prev2_n = prev_pix0 - prev2_pix0;
-                // ---- IFCE features do not depend on this grid: REQUEST them before waiting on the decoder, use them in the gather.
+                // ---- vector-ALU body, feature request.  IFCE features do not depend on this grid: REQUEST them before waiting on the
+                // decoder, use them in the gather.
                 // (r04: the selects stood right behind the loads, so every task began with s_waitcnt vmcnt(0) - an L2 round trip of
                 // ~700 ticks on the path between two tasks.  The raw values now stay untouched until the gather, behind the early
                 // wait and the tail stores.)
@@ -1505,7 +1546,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // dynamic operand check (see exact_pixel): a sentinel among the task's features - known at the gather, BEFORE the late
                 // wait, so the critical path only carries one scalar test of this mask.
                 unsigned long long bad_lanes = 0ull;
-                // ---- Two waits.  Of all contexts only the left neighbour (y, x - 1) lies in the previous step (pixel i of this
+                // ---- both bodies: two waits.  Of all contexts only the left neighbour (y, x - 1) lies in the previous step (pixel i of this
                 // step reads pixel i of that one, pixel i + 1 when the step start moved down a row in between); (y, x - 2) lies
                 // two steps back, everything else at least five.  So the task gathers every other input, runs the stabiliser and
                 // the first layer on them BEFORE the left neighbour is decoded, and only adds that one term afterwards: the
@@ -1519,13 +1560,10 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 const uint32_t need_px = ends_in_b ? pix0 + min(last1 + b_moved, it.n) : prev_pix0 + min(last1 + dy1, prev_n);  // ... the left neighbours
                 const uint32_t need_early_px = ends_in_b ? prev_pix0 + min(last1 + b_moved + dy1, prev_n)
                                                          : prev2_pix0 + min(last1 + dy2, prev2_n);                        // ... the pixels two to the left
-                unsigned long long lt_a = 0, lt_b = 0, lt_c = 0, lt_d = 0;  // level-2 profile stamps
-                (void)lt_a; (void)lt_b; (void)lt_c; (void)lt_d;
-                unsigned narrow_mask = 0;  // matrix-core path: bit i: pixel i of the task is narrow (wave-uniform)
-                // vector-ALU path: the entry's role in its window (sentinel, window top) as masks / addends, worked out before the late wait
+                // ---- vector-ALU body: what it works out before the late wait and uses behind it.  The entry's role in its window
+                // (sentinel, window top) as masks / addends
                 uint32_t win_left_m = 0, win_keep_m = 0, win_e0 = 0, win_e1 = 0;
-                (void)win_left_m; (void)win_keep_m; (void)win_e0; (void)win_e1;
-                // vector-ALU path: the output layer runs on the activations the lanes hold, summed over the pixel's lanes, and the
+                // the output layer runs on the activations the lanes hold, summed over the pixel's lanes, and the
                 // pixel's lanes build its window themselves from the indices they then have.  The WINDOW LANES of a pixel are
                 // all of its lanes on 8- and 4-pixel tasks and the upper 16 of its 32 on 2-pixel tasks (group_sum2); kQ0 is the
                 // first of them.
@@ -1536,10 +1574,9 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 double own_rcp = 0.0;            // s_rcp[idx_sc]
                 uint32_t own_ent = 0;            // where the lane's table entries go
                 uint32_t mu_dst = 0, rcp_dst = 0;  // where the lane's table index and reciprocal go (RowMeta; see the role constants below)
-                (void)idx_mu; (void)idx_sc; (void)own_rcp; (void)own_ent; (void)mu_dst; (void)rcp_dst;
                 uint32_t rdy_addr = 0, rdy_val = 0;  // the ready bit's word and value
-                (void)rdy_addr; (void)rdy_val;
-                unsigned long long wide_lanes = 0ull;  // vector-ALU path: ballot of the log-scale lanes of the pixels that are not
+                unsigned narrow_mask = 0;  // matrix-core path: bit i: pixel i of the task is narrow (wave-uniform)
+                unsigned long long wide_lanes = 0ull;  // both bodies: the pixels that need the wide window (ballot of their log-scale lanes / MF: a bit each)
                 RowMeta& meta = *C.s_meta;
                 if constexpr (MF) {
                     const int n = px, g = q;  // lane = 16 g + n: pixel n of the task, K-slot group g of the matrix operands
@@ -1551,16 +1588,16 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         if (g < n_if) f0 = ifce_feat[fo * fstride + g];
                         if (g + 4 < n_if) f1 = ifce_feat[fo * fstride + g + 4];
                     }
-                    lt_a = LPROF_T(pw == 0);
+                    clk.a = LPROF_T(pw == 0);
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2
-                    if (pw == 0 && lt_prev_end) prof[4] += lt_a - lt_prev_end;
+                    if (pw == 0 && clk.prev_end) prof[4] += clk.a - clk.prev_end;
 #endif
                     {
                         const unsigned long long t0 = PROF_T();
                         if (!wait_ge2(C.s_consumed, need_slot, split ? need_early_px : need_px, C.s_abort)) return seq;  // (abort / lost hand-over: the kernel stops behind this grid, the count is not used)
                         PROF_ADD(prof[0], t0);
                     }
-                    lt_b = LPROF_T(pw == 0);
+                    clk.b = LPROF_T(pw == 0);
                     const unsigned long long t_g = PROF_T();
                     {   // where the decoder puts the pixel's symbol (RowMeta::cell / goff)
                         const int mi = (g == 0 && live) ? slot * kBpx + half * kTaskPix + n : kRows;
@@ -1631,7 +1668,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     PROF_ADD(prof[4], t_m);  // first layer
                     // ---- the left neighbour: wait for it (and for the slot), add its term as a rank-1 update
                     int32_t xleft = 0;
-                    lt_c = LPROF_T(pw == 0);
+                    clk.c = LPROF_T(pw == 0);
                     if (split) {
                         const unsigned long long t0 = PROF_T();
                         if (!wait_ge(C.s_consumed + 1, need_px, C.s_abort)) return seq;  // (abort / lost hand-over: the kernel stops behind this grid, the count is not used)
@@ -1640,7 +1677,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         PROF_ADD(prof[5], t0);  // late wait
                         if (live && x >= 1) xleft = static_cast<int32_t>(C.s_ring[(y & ring_mask) * 64 + ((x - 1 + 10 * y) & 63)]) << 16;
                     }
-                    lt_d = LPROF_T(pw == 0);
+                    clk.d = LPROF_T(pw == 0);
                     const unsigned long long t_h = PROF_T();
                     int32_t av[5];
                     uint32_t big = 0;  // OR of every hidden activation of the lane (they are >= 0)
@@ -1717,28 +1754,21 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
 #if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE >= 3
                     prof[8] += 1;
 #endif
+                    clk.begin(TaskClock::kTables);
                 } else {
-                lt_a = LPROF_T(pw == 0);
-#if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2
-                if (pw == 0 && lt_prev_end) prof[4] += lt_a - lt_prev_end;
-#endif
+                // ======================== the vector-ALU task body: early wait, gather ========================
+                clk.task_begin();
                 // what lane q holds of the layer in front of the output layer: its units o = q + kLpp t (the raw inputs of a network
                 // without a hidden layer): the output layer's inputs
                 int32_t hid[NOUT];
-                {
-                    const unsigned long long t0 = PROF_T();
-                    // (the early wait includes "slot free again": true long ago whenever it is looked at - the slot was last used
-                    // kNSlots batches back - and it lets the table rows' tails be cleared before the late wait, see below)
-                    if (!wait_ge2(C.s_consumed, need_slot, split ? need_early_px : need_px, C.s_abort)) return seq;  // (abort / lost hand-over: the kernel stops behind this grid, the count is not used)
-                    PROF_ADD(prof[0], t0);
-                }
-                lt_b = LPROF_T(pw == 0);
-                const unsigned long long t_g = PROF_T();
-                {   // where the decoder puts the pixel's symbol (RowMeta::cell / goff): position only, so it is written here
-                    const int mi = (q == 0 && px < cnt) ? slot * kBpx + half * kTaskPix + px : kRows;
-                    meta.cell[mi] = static_cast<uint32_t>(((y & ring_mask) << 6) | ((x + 10 * y) & 63));
-                    meta.goff[mi] = static_cast<uint32_t>(y * W + x);
-                }
+                clk.begin(TaskClock::kWait);
+                // (the early wait includes "slot free again": true long ago whenever it is looked at - the slot was last used
+                // kNSlots batches back - and it lets the table rows' tails be cleared before the late wait, see below)
+                if (!wait_ge2(C.s_consumed, need_slot, split ? need_early_px : need_px, C.s_abort)) return seq;  // (abort / lost hand-over: the kernel stops behind this grid, the count is not used)
+                clk.add(0, TaskClock::kWait);
+                clk.early_wait_end();
+                clk.begin(TaskClock::kGather);
+                store_row_position(meta, (q == 0 && px < cnt) ? slot * kBpx + half * kTaskPix + px : kRows, y, x, W, ring_mask);
                 // ---- entries 16..63 of the task's table rows: lower sentinels of a narrow window (P = 0).  Written now, off the
                 // late path: a row that turns out wide overwrites all 64 entries later.  cnt rows x 24 16-byte stores.
                 {
@@ -1791,19 +1821,19 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         hid[t] = v << 16;
                     }
                 }
-                PROF_ADD(prof[1], t_g);
-                const unsigned long long t_m = PROF_T();
+                clk.add(1, TaskClock::kGather);
+                clk.begin(TaskClock::kMlp);
                 // ---- MLP: lane computes outputs o = q + 8 t of its pixel ------------------------------------------
                 int4 xv[NV];
 #pragma unroll
                 for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
                 // Lane q owns outputs q, q + kLpp, ...: their accumulators advance in lock-step (independent chains), one
                 // 16-byte weight vector per output and step; every multiply-add is a single v_mad_i64_i32.
-                PROF_ADD(prof[4], t_m);  // activation reload
-                const unsigned long long t_s = PROF_T();
+                clk.add(4, TaskClock::kMlp);  // activation reload
+                clk.begin(TaskClock::kStab);
                 int64_t so[2];  // [0]: stabiliser output (lanes q < 2), [1]: scratch second chain
                 const int qs = q < 2 ? q : 1;  // lanes q >= 2 compute a discarded copy of row 1
-                {   // stabiliser branch on the raw inputs
+                {   // ---- stabiliser branch on the raw inputs
                     const int4* wr = reinterpret_cast<const int4*>(C.s_w + C.n_w_hidden + 2 * in_pad + qs * in_pad);
                     so[0] = C.s_b[(n_layers - 1) * dim + 2 + qs];
                     so[1] = 0;
@@ -1818,12 +1848,12 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         mad64(so[0], xv[v].x, w.x); mad64(so[1], xv[v].y, w.y); mad64(so[0], xv[v].z, w.z); mad64(so[1], xv[v].w, w.w);
                     }
                 }
-                PROF_ADD(prof[5], t_s);
-                const unsigned long long t_h = PROF_T();
-                // first hidden layer on the early inputs (the only layer when the late wait does not apply is handled alike:
+                clk.add(5, TaskClock::kStab);
+                clk.begin(TaskClock::kHidden);
+                // ---- first hidden layer on the early inputs (the only layer when the late wait does not apply is handled alike:
                 // the left term is then simply zero and the gather above already took the neighbour)
-                int64_t acc0[NOUT], acc0_b = 0;
-                (void)acc0_b;
+                int64_t acc0[NOUT];
+                [[maybe_unused]] int64_t acc0_b = 0;
                 int32_t wleft[NOUT], wleft_stab = 0;
                 if (n_layers >= 2) {
                     const int32_t* wl = C.s_w;
@@ -1859,7 +1889,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // reached `need_px` vouches for the cell read behind it; otherwise both are read again in the polling loop.
                 // Unconditional read (cell of column -1 for x = 0: in bounds, dropped by the select), no exec mask.
                 int32_t xleft = 0;
-                // Role constants of the output tail, as VGPRs and BEFORE the late wait: where this lane's table index and reciprocal
+                // ---- role constants of the output tail, as VGPRs and BEFORE the late wait: where this lane's table index and reciprocal
                 // go in the row meta (first window lane of the pixel: mu index and, next to it, the top symbol; second: reciprocal;
                 // the dummy entry kRows for a lane that has nothing to say), and the scale index above which the second window lane
                 // reports a wide window.  Left to the compiler they were SGPR-pair masks (q == 0, q == 1, live) that did not fit the
@@ -1877,10 +1907,9 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // stabiliser output and the bias in the one lane that holds that row (q = 0: mu, q = 1: log-scale) and from zero
                 // everywhere else, so that the sum over the pixel's lanes takes each once; the left neighbour's stabiliser weight
                 // likewise.  The output weights of the lane's units o = q + kLpp t, both rows: ZERO for a unit past the layer
-                // (such a lane computes a copy of unit dim - 1 in the hidden layers; the tile path drops it at the store).
+                // (such a lane computes a copy of unit dim - 1 in the hidden layers; the store into the activation tile drops it).
                 int64_t out_m = 0, out_l = 0;
                 int32_t wl_m = 0, wl_l = 0, wo_m[NOUT], wo_l[NOUT];
-                (void)wl_m; (void)wl_l; (void)wo_m; (void)wo_l;
                 {
                     const int64_t s = so[0] + so[1] + C.s_b[(n_layers - 1) * dim + qs];
                     const int64_t keep_m = qo == 0 ? -1 : 0, keep_l = qo == 1 ? -1 : 0;
@@ -1917,9 +1946,9 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 win_e0 = e0o == 0 ? (1u << kRcPrecision) - 1u : 0u;
                 win_e1 = (e0o <= 1 && e0o + kEpl > 1) ? 1u : 0u;
                 asm volatile("" : "+v"(own_ent), "+v"(win_left_m), "+v"(win_keep_m), "+v"(win_e0), "+v"(win_e1));
-                lt_c = LPROF_T(pw == 0);
+                clk.late_wait_begin();
                 if (split) {
-                    const unsigned long long t0 = PROF_T();
+                    clk.begin(TaskClock::kWait);
                     const uint32_t want = uni(need_px);
                     const uint32_t cell = static_cast<uint32_t>((y & ring_mask) * 64 + ((x - 1 + 10 * y) & 63));
                     uint32_t seen_v;
@@ -1939,12 +1968,12 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                                          : "=&v"(seen_v), "=&v"(r) : "v"(C.s_consumed.off), "v"(C.s_ring.off + cell) : "memory");
                         } while (static_cast<int32_t>(uni(seen_v) - want) < 0);
                     }
-                    PROF_ADD(prof[0], t0);
-                    PROF_SUB(prof[2], t0);  // the MLP's stamps bracket this wait: take it out of them
-                    PROF_SUB(prof[6], t0);
+                    clk.add(0, TaskClock::kWait);
+                    clk.sub(2, TaskClock::kWait);  // the MLP's stamps bracket this wait: take it out of them
+                    clk.sub(6, TaskClock::kWait);
                     xleft = (px < cnt && x >= 1) ? r << 16 : 0;
                 }
-                lt_d = LPROF_T(pw == 0);
+                clk.late_wait_end();
                 // the late path is on the chain "symbol decoded -> table ready": it goes ahead of a SIMD neighbour's early work (the
                 // decoder runs at priority 3).  41.03 -> 40.84 ms on kodak24 (profiles/r04/ab_entropy_late_prio.txt)
                 // (priority 2 for the first task of a step, the head of its chain: no further gain)
@@ -1975,8 +2004,8 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 for (int l = 1; l < n_layers - 1; ++l) {
                     const int32_t* wl = C.s_w + l * dim * in_pad;
                     const int64_t* bl = C.s_b + l * dim;
-                    int64_t acc[NOUT], acc_b = 0;
-                    (void)acc_b;
+                    int64_t acc[NOUT];
+                    [[maybe_unused]] int64_t acc_b = 0;
                     const int4* wr[NOUT];
 #pragma unroll
                     for (int t = 0; t < NOUT; ++t) {
@@ -2016,9 +2045,9 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         for (int v = 0; v < NV; ++v) xv[v] = act_row[v];
                     }
                 }
-                PROF_ADD(prof[6], t_h);
-                const unsigned long long t_o = PROF_T();
-                // output layer -> table indices.  From registers: the lane's units times their two output weights (two chains in
+                clk.add(6, TaskClock::kHidden);
+                clk.begin(TaskClock::kOut);
+                // ---- output layer -> table indices.  From registers: the lane's units times their two output weights (two chains in
                 // rotation), then the sum over the pixel's lanes - every window lane of the pixel ends up with both sums (stabiliser
                 // and bias came in through the chains' start values), no trip through the activation tile
 #pragma unroll
@@ -2053,13 +2082,11 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 // lanes (px * kLpp + kQ0 + 1) of pixels that need the wide window (scale index above kNarrowMaxScale: 0.7 % of the symbols);
                 // the common path only tests the ballot for zero
                 wide_lanes = __ballot(idx_sc > wide_above);
-                PROF_ADD(prof[2], t_m);
-                PROF_ADD(prof[7], t_o);
-#if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE >= 3
-                prof[8] += 1;
-#endif
+                clk.add(2, TaskClock::kMlp);
+                clk.add(7, TaskClock::kOut);
+                clk.count_task();
+                clk.begin(TaskClock::kTables);
                 }
-                const unsigned long long t_t = PROF_T();
                 // ---- window tables (lanes hold symbols in DESCENDING order; entry 0 = upper sentinel, trailing entries =
                 // lower sentinels, both with P = 0).  Narrow pixels (small scale): 14 real symbols, built by the pixel's window lanes
                 // (matrix-core path: four pixels per pass of the wave).  Wide pixels: 62 real symbols, one pixel per pass.
@@ -2178,41 +2205,16 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     tab[i * 64 + lane] = ent;
                     if (lane == 0) meta.top[mi] = top;
                 }
-                // LDS requests of one wave are performed in order: a relaxed add issued behind the table stores is enough for the
-                // decoder (a release would first wait for every outstanding LDS and global access of the wave)
-                asm volatile("" ::: "memory");
-                if constexpr (!MF) {
-                    // one ds_or_b32 from lane 0, address and value formed before the late wait; no lane election, no branch
-                    unsigned long long exec_all;
-                    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_or_b32 %1, %2\n\ts_mov_b64 exec, %0"
-                                 : "=&s"(exec_all) : "v"(rdy_addr), "v"(rdy_val) : "memory");
-                } else {
+                if constexpr (!MF) publish_ready(rdy_addr, rdy_val);
+                else {
+                    asm volatile("" ::: "memory");
                     if (lane == 0) __hip_atomic_fetch_or(&C.s_ready[slot], 1u << half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 asm volatile("" ::: "memory");
-                PROF_ADD(prof[3], t_t);
-#if defined(CCD_PIPE_PROFILE) && CCD_PIPE_PROFILE == 2
-#if defined(CCD_PIPE_TRACE)
-                {
-                    const unsigned long long lt_e = __builtin_amdgcn_s_memtime();
-                    const uint32_t gidx = seq0 * kHalves + task;
-                    if (lane == 0 && static_cast<uint32_t>(W) == uni(g_trace_cfg[0]) && uni(g_trace_cfg[1]) - it.left < 64u) {
-                        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                                                u32x4* r = reinterpret_cast<u32x4*>(ccd_pipe_smem + C.trace_off + (gidx % kTraceTasks) * 32u);
-                        const u32x4 r0 = {(it.left << 12) | ((task & 15u) << 8) | (static_cast<uint32_t>(pw) << 4) | static_cast<uint32_t>(cnt), static_cast<uint32_t>(lt_a),
-                                          static_cast<uint32_t>(lt_b), static_cast<uint32_t>(lt_c)};
-                        const u32x4 r1 = {static_cast<uint32_t>(lt_d), static_cast<uint32_t>(lt_e), need_px - pix0, static_cast<uint32_t>(lt_a >> 32)};
-                        r[0] = r0; r[1] = r1;
-                    }
-                }
-#endif
-                if (pw == 0) {
-                    const unsigned long long lt_e = __builtin_amdgcn_s_memtime();
-                    prof[0] += lt_b - lt_a; prof[1] += lt_c - lt_b; prof[2] += lt_d - lt_c; prof[3] += lt_e - lt_d; prof[8] += 1;
-                    lt_prev_end = lt_e;
-                }
-#endif
+                clk.add(3, TaskClock::kTables);
+                clk.task_end(C, static_cast<uint32_t>(W), it.left, seq0 * kHalves + task,
+                             (it.left << 12) | ((task & 15u) << 8) | (static_cast<uint32_t>(pw) << 4) | static_cast<uint32_t>(cnt), need_px - pix0);
             }
         }
         seq = seq0 + nb;
@@ -2637,6 +2639,22 @@ int entropy_pipe_fixed_shape(int dim, int n_layers, int n_spatial) {
     return (dim == ShapeHop::dim && n_layers == ShapeHop::n_layers && n_spatial == ShapeHop::n_sp) ? 1 : 0;
 }
 
+// One kernel per width nv: the matrix-core variant serves nv = 1 .. 5 (dim <= 20), the others 1 .. 8.
+template <bool MF, bool DYN>
+static hipError_t launch_pipe(int nv, const EntropyParams* d_slots, int n_slots, size_t lds_bytes, hipStream_t stream) {
+    if (MF && nv > 5) return hipErrorInvalidValue;
+    switch (nv) {
+        case 1: return launch_pipe_nv<1, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 2: return launch_pipe_nv<2, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 3: return launch_pipe_nv<3, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 4: return launch_pipe_nv<4, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 5: return launch_pipe_nv<5, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 6: return launch_pipe_nv<MF ? 5 : 6, MF, DYN>(d_slots, n_slots, lds_bytes, stream);  // (MF: not reached, and no sixth kernel)
+        case 7: return launch_pipe_nv<MF ? 5 : 7, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        case 8: return launch_pipe_nv<MF ? 5 : 8, MF, DYN>(d_slots, n_slots, lds_bytes, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
 // All `n_slots` descriptors must share nv = ceil(dim / 4), the mfma flag, the dyn flag and the fixed shape (the host groups the
 // slots of a batch by all four).  The matrix-core variant's envelope implies dyn = 0 and shape = 0.
 hipError_t launch_entropy_pipe(const EntropyParams* d_slots, int n_slots, int nv, int mfma, int dyn, int shape, size_t lds_bytes, hipStream_t stream) {
@@ -2645,40 +2663,8 @@ hipError_t launch_entropy_pipe(const EntropyParams* d_slots, int n_slots, int nv
         return dyn ? launch_pipe_nv<5, false, true, ShapeHop>(d_slots, n_slots, lds_bytes, stream)
                    : launch_pipe_nv<5, false, false, ShapeHop>(d_slots, n_slots, lds_bytes, stream);
     if (shape != 0) return hipErrorInvalidValue;
-    if (mfma) {
-        switch (nv) {
-            case 1: return launch_pipe_nv<1, true, false>(d_slots, n_slots, lds_bytes, stream);
-            case 2: return launch_pipe_nv<2, true, false>(d_slots, n_slots, lds_bytes, stream);
-            case 3: return launch_pipe_nv<3, true, false>(d_slots, n_slots, lds_bytes, stream);
-            case 4: return launch_pipe_nv<4, true, false>(d_slots, n_slots, lds_bytes, stream);
-            case 5: return launch_pipe_nv<5, true, false>(d_slots, n_slots, lds_bytes, stream);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (dyn) {
-        switch (nv) {
-            case 1: return launch_pipe_nv<1, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 2: return launch_pipe_nv<2, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 3: return launch_pipe_nv<3, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 4: return launch_pipe_nv<4, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 5: return launch_pipe_nv<5, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 6: return launch_pipe_nv<6, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 7: return launch_pipe_nv<7, false, true>(d_slots, n_slots, lds_bytes, stream);
-            case 8: return launch_pipe_nv<8, false, true>(d_slots, n_slots, lds_bytes, stream);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (nv) {
-        case 1: return launch_pipe_nv<1, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 2: return launch_pipe_nv<2, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 3: return launch_pipe_nv<3, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 4: return launch_pipe_nv<4, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 5: return launch_pipe_nv<5, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 6: return launch_pipe_nv<6, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 7: return launch_pipe_nv<7, false, false>(d_slots, n_slots, lds_bytes, stream);
-        case 8: return launch_pipe_nv<8, false, false>(d_slots, n_slots, lds_bytes, stream);
-        default: return hipErrorInvalidValue;
-    }
+    if (mfma) return launch_pipe<true, false>(nv, d_slots, n_slots, lds_bytes, stream);
+    return dyn ? launch_pipe<false, true>(nv, d_slots, n_slots, lds_bytes, stream) : launch_pipe<false, false>(nv, d_slots, n_slots, lds_bytes, stream);
 }
 
 }  // namespace ccd

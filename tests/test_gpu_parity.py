@@ -204,6 +204,44 @@ def test_arm_sweep_every_instantiation(gpu, oracle, variant):
         b.close()
 
 
+def test_arm_sweep_matrix_core_producers(gpu, oracle):
+    """The matrix-core producers at every width they are built for: the sweep's streams with at most 20 ARM inputs (NV = 1 .. 5) and at least one
+    hidden layer, in one batch with mfma_arm = 1.  Their 32 x 320 pictures run 8-, 4- and 2-pixel tasks, the 8-pixel ones on the
+    matrix cores.  Same bars as test_arm_sweep_every_instantiation: latents == what the REFERENCE decoder decoded (sha256 per
+    grid in the fixture), status 0; a stream outside the matrix-core envelope decodes on the vector ALU and still has to match."""
+    import hashlib
+    import re
+
+    from conftest import load_arm_sweep
+    from cool_chic_amd._lib import lib
+
+    sweep = load_arm_sweep()
+    shape = {n: [int(v) for v in re.match(r"d(\d+)_h(\d+)_", n).groups()] for n in sweep}  # d<ARM inputs>_h<hidden layers>_i<IFCE features>
+    names = [n for n in sweep if shape[n][0] <= 20 and shape[n][1] >= 1]
+    assert names
+    b = gpu(0, mfma_arm=1)
+    try:
+        triples = [oracle.split_stream(sweep[n][0])[1][0][1][0] for n in names]
+        for hdr, nn, lat in triples:
+            b.add(hdr, nn, lat, 8, 0)
+        b.run()
+        b.wait()
+        on_matrix_cores = set()
+        for i, n in enumerate(names):
+            hdr, nn, lat = triples[i]
+            k = b.slot_kernels(i)
+            assert b.slot_status(i) == 0, n
+            assert k & 1, f"{n}: the pipelined entropy kernel must serve every shape of the sweep"
+            if k & 8:
+                on_matrix_cores.add((lib().ccd_network_kernel_class(hdr, len(hdr), nn, len(nn)) >> 8) & 15)
+            got = [hashlib.sha256(np.ascontiguousarray(b.latent(i, g)).tobytes()).hexdigest() for g in range(b.header(i).n_grids)]
+            assert got == sweep[n][1], f"{n}: latents vs the reference decoder (kernels {k})"
+        print("widths on the matrix cores:", sorted(on_matrix_cores))
+        assert on_matrix_cores == {1, 2, 3, 4, 5}
+    finally:
+        b.close()
+
+
 @pytest.mark.parametrize("name", ["rgb192", "yuv420_10b"])
 def test_generic_fallback_kernels(gpu, oracle, name, monkeypatch):
     """The barrier-phased int64 entropy kernel and the per-layer synthesis kernels (used for networks
