@@ -7,6 +7,7 @@
 
 #include "ccd_host.hpp"
 #include "ccd_kernels.hpp"
+#include "ccd_wavefront.hpp"
 
 using namespace ccd;
 
@@ -631,13 +632,13 @@ static void plan_chain_groups(const double* est, const int* inst, int n, int n_c
 }
 
 // Expected length of a slot's serial chain in decoder ticks (only the ORDER and rough ratios matter: it decides which streams
-// share an entropy launch).  Per grid ~120 ticks per symbol + ~1.8 k per wavefront step (latent.py:66-140: W + 10 (H - 1) steps):
+// share an entropy launch).  Per grid ~120 ticks per symbol + ~1.8 k per step of the coding order (ccd_wavefront.hpp):
 // profiles/r06/prof_grids_base.txt - a portrait Kodak stream comes out 1.09 x a landscape one (measured 1.06).
 static double chain_estimate(const EntropyParams& ep) {
     double t = 0.0;
     for (int g = 0; g < ep.n_grids; ++g) {
-        const double h = ep.grid_h[g], w = ep.grid_w[g];
-        t += 120.0 * h * w + 1800.0 * (w > 9.0 ? w + 10.0 * (h - 1.0) : h * w);
+        const int h = ep.grid_h[g], w = ep.grid_w[g];
+        t += 120.0 * h * w + 1800.0 * wf_n_steps(h, w);
     }
     return t;
 }

@@ -5,6 +5,7 @@
 
 #include "ccd_host.hpp"
 #include "ccd_kernels.hpp"
+#include "ccd_wavefront.hpp"
 
 using namespace ccd;
 
@@ -136,7 +137,8 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
         }
         if (!ok) return CCD_ERR_UNSUPPORTED;
     }
-    // ---- where every pixel goes: grids n-1 .. 0; raster when W <= 9, else wavefront steps (ccd_writer.cpp:349-361) ----
+    // ---- where every pixel goes: grids n-1 .. 0, each in coding order (ccd_wavefront.hpp); wavefront grids get a table of
+    // the pixels in front of every step ----
     const uint32_t threads = static_cast<uint32_t>(encode_block_threads());
     std::vector<std::vector<uint32_t>> prefix(n);
     uint32_t first = 0;
@@ -144,16 +146,14 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
         const int H = h.grid_h[g], W = h.grid_w[g];
         Q.grid_first[g] = first;
         first += static_cast<uint32_t>(H) * static_cast<uint32_t>(W);
-        if (W <= 9 || H < 1) continue;
-        const long n_steps = W + 10L * (H - 1);
+        if (wf_raster(W) || H < 1) continue;
+        const int n_steps = wf_n_steps(H, W);
         prefix[g].resize(static_cast<size_t>(n_steps));
         uint32_t before = 0;
-        for (long c = 0; c < n_steps; ++c) {
+        for (int c = 0; c < n_steps; ++c) {
             int y0, x0;
-            if (c < W) { y0 = 0; x0 = static_cast<int>(c); }
-            else { y0 = static_cast<int>((c - W) / 10) + 1; x0 = W - 10 + static_cast<int>((c - W) % 10); }
             prefix[g][static_cast<size_t>(c)] = before;
-            before += static_cast<uint32_t>(std::min(H - y0, x0 / 10 + 1));
+            before += static_cast<uint32_t>(wf_step(H, W, c, y0, x0));
         }
     }
     Q.n_symbols = first;

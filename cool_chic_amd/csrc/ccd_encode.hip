@@ -2,7 +2,7 @@
 // host writer (ccd_writer.cpp, ccd_encode_coolchic) produces.  DESIGN.md section 4.10.
 //
 // Reference behaviour restated here (paths relative to /root/reference/coolchic):
-//   bitstream/component/latent.py:142-173    the encoder walks the decoder's integer path, wavefront order x + 10 y
+//   bitstream/component/latent.py:142-173    the encoder walks the decoder's integer path in coding order (ccd_wavefront.hpp)
 //   bitstream/component/coolchic.py:94-146   IFCE features on the nearest-upsampled stack of the coarser grids
 //   bitstream/component/armint.py:180-203    fixed-point MLP (int64, wrap-around)
 //   bitstream/component/rangecoder.py:46-76  -> constriction 0.4.2 RangeEncoder + QuantizedLaplace(-64,63)
@@ -22,6 +22,7 @@
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
 #include "ccd_laplace.hpp"
+#include "ccd_wavefront.hpp"
 
 namespace ccd {
 
@@ -164,12 +165,12 @@ __global__ __launch_bounds__(kEncThreads) void encode_contexts_kernel(const Enco
     uint32_t left, right;
     encode_pixel_interval(P, g, y, x, sym, lane, smem_raw, left, right);
 
-    // ---- position in coding order (latent.py:66-140): raster if W <= 9, else steps c = x + 10 y, increasing y ----
+    // ---- position in coding order (ccd_wavefront.hpp): the pixels in front of its step, then the rows of the step above it ----
     uint32_t idx = Q.grid_first[g];
-    if (W <= 9) idx += static_cast<uint32_t>(p);
+    if (wf_raster(W)) idx += static_cast<uint32_t>(p);
     else {
-        const int c = x + 10 * y;
-        const int y0 = c < W ? 0 : (c - W) / 10 + 1;  // first row of the step
+        const int c = wf_step_of(y, x);
+        const int y0 = wf_first_row(W, c);
         idx += Q.step_prefix[g][c] + static_cast<uint32_t>(y - y0);
     }
     Q.pairs[idx] = EncodePair{left, right - left};

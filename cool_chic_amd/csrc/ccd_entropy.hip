@@ -3,7 +3,7 @@
 //
 // Reference behaviour restated here (paths relative to /root/reference/coolchic):
 //   bitstream/component/coolchic.py:89-169   per-grid loop, IFCE on the nearest-upsampled stack
-//   bitstream/component/latent.py:18-187     wavefront order x + 10 y, context gather, scatter
+//   bitstream/component/latent.py:18-187     coding order (stated in ccd_wavefront.hpp), context gather, scatter
 //   bitstream/component/armint.py:180-203    fixed-point MLP (int64, wrap-around)
 //   bitstream/component/rangecoder.py:80-94  -> constriction 0.4.2 RangeDecoder + QuantizedLaplace(-64,63)
 //
@@ -20,6 +20,7 @@
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
 #include "ccd_laplace.hpp"
+#include "ccd_wavefront.hpp"
 
 namespace ccd {
 
@@ -127,24 +128,18 @@ __device__ void entropy_decode_slot(const EntropyParams& P, unsigned char* smem_
         }
         __syncthreads();
 
-        // ---- wavefront walk (latent.py:66-140): coding order x + 10 y, raster if W <= 9 -------------
-        const bool raster = W <= 9;
-        const int n_steps = raster ? H * W : W + 10 * (H - 1);
+        // ---- the steps of the grid in coding order (ccd_wavefront.hpp) ---------------------------
+        const int n_steps = wf_n_steps(H, W);
         for (int c = 0; c < n_steps; ++c) {
-            int y0, x0, n;
-            if (raster) { y0 = c / W; x0 = c - y0 * W; n = 1; }
-            else {
-                if (c < W) { y0 = 0; x0 = c; }
-                else { y0 = (c - W) / 10 + 1; x0 = W - 10 + (c - W) % 10; }
-                n = min(H - y0, x0 / 10 + 1);  // pixels (y0 + i, x0 - 10 i) inside the grid
-            }
+            int y0, x0;
+            const int n = wf_step(H, W, c, y0, x0);  // pixels (y0 + i, x0 - kWfSlope i)
             for (int i0 = 0; i0 < n; i0 += kChunk) {
                 const int cnt = min(kChunk, n - i0);
                 GP_START();
                 // ---- A1: gather contexts (already << 16, armint.py:193) ---------------------------
                 for (int it = tid; it < cnt * dim; it += kEntThreads) {
                     const int k = it / cnt, i = it - k * cnt;
-                    const int y = y0 + i0 + i, x = x0 - 10 * (i0 + i);
+                    const int y = y0 + i0 + i, x = x0 - kWfSlope * (i0 + i);
                     int64_t v = 0;
                     if (k < n_sp) {
                         const int yy = y - P.ctx_dy[k], xx = x + P.ctx_dx[k];

@@ -35,12 +35,15 @@
 //
 // Reference behaviour restated: bitstream/component/latent.py:18-187, armint.py:180-203,
 // coolchic.py:89-169, rangecoder.py:80-94 (constriction RangeDecoder + QuantizedLaplace(-64,63)).
+// The coding order (latent.py:66-140) and its walks - StepWalk, StepIter, StreamBody, grid_segments, ring_cell - are stated in
+// ccd_wavefront.hpp.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
 #include "ccd_device.hpp"
 #include "ccd_kernels.hpp"
 #include "ccd_laplace.hpp"
+#include "ccd_wavefront.hpp"
 
 namespace ccd {
 
@@ -288,112 +291,6 @@ __device__ __forceinline__ bool wait_ge2(const uint32_t* p, uint32_t want_batche
     return true;
 }
 
-// The producers' walk over the steps of a grid (same order as StepIter below), kept incremental and unsigned: a producer
-// passes every step on the way to its next task, so this is on the path between two tasks.
-struct StepWalk {
-    uint32_t H, W, raster, left;
-    uint32_t y0, x0, n, moved;  // moved: the step's first row is one below the previous step's
-    __device__ void init(uint32_t h, uint32_t w) {
-        H = h; W = w; raster = w <= 9u; left = raster ? h * w : w + 10u * (h - 1u);
-        y0 = 0; x0 = ~0u; n = 0; moved = 0;
-    }
-    __device__ bool next() {
-        if (left == 0) return false;
-        --left;
-        ++x0;
-        moved = x0 == W;
-        if (moved) { x0 = raster ? 0u : W - 10u; ++y0; }
-        n = raster ? 1u : min(H - y0, ((x0 * 0xcccdu) >> 19) + 1u);  // x0 / 10 + 1 (exact below 43699)
-        return true;
-    }
-    // length of step c / whether its start lies a row below step c - 1's (wavefront order)
-    __device__ uint32_t len_of(uint32_t c) const {
-        const uint32_t yy = c < W ? 0u : (c - W) / 10u + 1u, xx = c < W ? c : W - 10u + (c - W) % 10u;
-        return min(H - yy, xx / 10u + 1u);
-    }
-    __device__ uint32_t moved_at(uint32_t c) const { return (c >= W && (c - W) % 10u == 0u) ? 1u : 0u; }
-    // the state of step c - 1 (c >= 1, wavefront order): next() then arrives at step c
-    __device__ void seek_before(uint32_t c) {
-        const uint32_t p = c - 1u;
-        y0 = p < W ? 0u : (p - W) / 10u + 1u;
-        x0 = p < W ? p : W - 10u + (p - W) % 10u;
-        n = len_of(p); moved = moved_at(p);
-        left = W + 10u * (H - 1u) - c;
-    }
-};
-
-// Iterates the wavefront steps of one grid (latent.py:66-140).
-struct StepIter {
-    int H, W, raster, n_steps;
-    int c, y0, x0, n;
-    __device__ void init(int h, int w) { H = h; W = w; raster = w <= 9; n_steps = raster ? h * w : w + 10 * (h - 1); c = -1; }
-    __device__ bool seek(int step) { c = step - 1; return next(); }
-    __device__ bool next() {
-        if (++c >= n_steps) return false;
-        if (raster) { y0 = c / W; x0 = c - y0 * W; n = 1; }
-        else {
-            if (c < W) { y0 = 0; x0 = c; }
-            else { y0 = (c - W) / 10 + 1; x0 = W - 10 + (c - W) % 10; }
-            n = min(H - y0, x0 / 10 + 1);
-        }
-        return true;
-    }
-};
-
-// ---- The BODY of a wide grid as one stream of pixels (r04).  Steps of the wavefront order are independent of batch boundaries as
-// soon as a pixel's left neighbour (same index in the previous step) lies at least a task + a batch behind it in decoding order,
-// i.e. for steps of >= 18 pixels.  So the steps [first, end) whose length is >= kStreamMinStep - 1 - all of a grid but the ramps at
-// its two corners - are cut into 16-pixel batches / 8-pixel tasks WITHOUT regard to step ends: every batch but the last is full
-// (the unrolled block), no 3-pixel tail batch and no step hand-over per step, 6.4 instead of 7 tasks per step of a portrait
-// Kodak picture.  A task then holds pixels of up to two steps (per-lane position select), the decoder sees ONE step of n_body
-// symbols (it takes each pixel's ring cell and latent offset from the row meta the producers write).
-//   ramp-up:  steps c < first = 10 (T - 1): y0 = 0, n = c / 10 + 1 < T, together 5 T (T - 1) pixels;
-//   ramp-down: steps c >= end = W + 10 (H - T): fewer than T rows left, again 5 T (T - 1) pixels (the mirror image);
-//   in between n = min(H - y0, x0 / 10 + 1) >= T - 1 (x0 >= W - 10 >= 10 (T - 1) - 9 behind the first row).
-#ifndef CCD_STREAM_MIN_STEP
-#define CCD_STREAM_MIN_STEP 24
-#endif
-constexpr uint32_t kStreamMinStep = CCD_STREAM_MIN_STEP;
-static_assert(kStreamMinStep >= 19, "a streamed task must find its left neighbours in an EARLIER batch: steps of >= 18 pixels");
-struct StreamBody {
-    uint32_t first, end, n_pix, pix_before;  // steps [first, end), pixels of the body, pixels of the grid in front of it
-    bool on;
-    __device__ void init(uint32_t H, uint32_t W, int task_pix) {
-        const uint32_t T = kStreamMinStep;
-        on = task_pix == 8 && W > 10u * (T - 1u) && H >= T;  // (4-pixel tasks streamed: measured slower, r04 and r06)
-        {   // where it pays: long steps (the decoder is the limit: its per-step costs go away) or steps whose last task is mostly empty.
-            // Elsewhere - 39-pixel steps = 8 + 8 + 8 + 8 + 7 - the tasks of step-aligned batches wait for ONE earlier task each instead
-            // of two (profiles/r04/ab_entropy_stream.txt: grid 1 of a landscape Kodak picture 16.8 -> 17.3 M ticks when streamed).
-            const uint32_t n_pl = (W - 1u) / 10u + 1u, tail = n_pl & 7u;
-            on = on && (n_pl >= 48u || (tail >= 1u && tail <= 4u));
-        }
-        first = 10u * (T - 1u);
-        end = on ? W + 10u * (H - T) : 0u;
-        pix_before = 5u * T * (T - 1u);
-        n_pix = on ? H * W - 2u * pix_before : 0u;
-    }
-};
-
-// Segments of a grid, the same list for the decoder and for every producer: all steps - or, around a streamed body, the ramp in
-// front of it, the body (ONE step of n_pix symbols for the decoder), the ramp behind it.  The ramps of a streamed grid - 230 steps
-// of 1 .. 23 pixels at each of two corners, every one a full "late work + hand-overs + one part" chain - run 4-pixel tasks
-// (shorter late path, 4 symbols instead of 8 between "ready" and "published"); same batches of 16, so nothing drains in between.
-#ifndef CCD_RAMP_TASK_PIX
-#define CCD_RAMP_TASK_PIX 4
-#endif
-static_assert(CCD_RAMP_TASK_PIX == 4 || CCD_RAMP_TASK_PIX == 8, "ramps and body share the 16-pixel batches: 2-pixel tasks (8-pixel batches) would need the slots drained between segments");
-struct GridSeg { uint32_t first, steps, pix_before, n_pix; int task_pix; bool body; };  // steps [first, first + steps), pixels in front of / in them
-__device__ __forceinline__ int grid_segments(uint32_t H, uint32_t W, int task_pix, GridSeg* out) {
-    StreamBody b;
-    b.init(H, W, task_pix);
-    const uint32_t total = W <= 9u ? H * W : W + 10u * (H - 1u);
-    if (!b.on) { out[0] = GridSeg{0u, total, 0u, H * W, task_pix, false}; return 1; }
-    out[0] = GridSeg{0u, b.first, 0u, b.pix_before, CCD_RAMP_TASK_PIX, false};
-    out[1] = GridSeg{b.first, b.end - b.first, b.pix_before, b.n_pix, task_pix, true};
-    out[2] = GridSeg{b.end, total - b.end, H * W - b.pix_before, b.pix_before, CCD_RAMP_TASK_PIX, false};
-    return 3;
-}
-
 // =================================================================================================
 // DECODER (wave 0): one grid.  Returns the batch sequence number after the grid.
 // =================================================================================================
@@ -472,7 +369,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_sub_u32 s62, s69, 1\n\t"
                 "s_lshl_b32 s70, 1, %[tshift]\n\t"
                 "s_sub_u32 s70, s70, 1\n\t"           // pixels per task - 1
-                "s_sub_u32 s64, %[gw], 10\n\t"
+                "s_sub_u32 s64, %[gw], 10\n\t"        // W - kWfSlope: x0 of a step that starts a row (StepWalk::next)
                 "s_mov_b32 s65, 0\n\t"               // 1: the batch is decoded part by part (see 27:)
                 "s_cmp_eq_u32 s69, 16\n\t"
                 "s_cselect_b32 s61, 1, 0\n\t"
@@ -895,7 +792,8 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 // ---- the step is finished.  The next one (x + 10 y = c + 1) starts one pixel to the right in the same row, or - past
                 // the right edge - at x = W - 10 one row down; its first batch sits in the slot just requested.  Everything the
                 // compiled code derives per step (StepIter, lane positions) is advanced here: ~25 instructions instead of ~90
-                // and two region crossings per step (there are W + 10 (H - 1) steps per grid).
+                // and two region crossings per step (there are W + 10 (H - 1) steps per grid).  Restates StepWalk::next of
+                // ccd_wavefront.hpp in assembly, with its multiply-shift for x0 / 10.
                 "30:\n\t"
                 "s_add_u32 %[pix0], %[pix0], %[n]\n\t"
                 "s_sub_u32 %[cleft], %[cleft], 1\n\t"
@@ -906,7 +804,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_cselect_b32 %[x0], s64, %[x0]\n\t"
                 "s_cselect_b32 s60, 1, 0\n\t"
                 "s_sub_u32 %[hy], %[hy], s60\n\t"     // rows left below the step's first
-                "s_mul_i32 s60, %[x0], 0xcccd\n\t"    // x0 / 10 (exact below 43699)
+                "s_mul_i32 s60, %[x0], 0xcccd\n\t"    // x0 / 10 (wf_div10)
                 "s_lshr_b32 s60, s60, 19\n\t"
                 "s_add_u32 s60, s60, 1\n\t"
                 "s_min_u32 %[n], s60, %[hy]\n\t"
@@ -1175,7 +1073,7 @@ __device__ __forceinline__ void mf_exact_task(const PipeCtx& C, int32_t* tile, i
         int32_t v = 0;
         if (k < n_sp) {
             const int yy = y - P.ctx_dy[k], xx = x + P.ctx_dx[k];
-            if (yy >= 0 && xx >= 0 && xx < W) v = C.s_ring[(yy & ring_mask) * 64 + ((xx + 10 * yy) & 63)];
+            if (yy >= 0 && xx >= 0 && xx < W) v = C.s_ring[ring_cell(yy, xx, ring_mask)];
         } else if (fin > 0) {
             v = reinterpret_cast<const int16_t*>(P.ifce_feat)[((y >> 1) * fw + (x >> 1)) * C.fstride + (k - n_sp)];
         }
@@ -1248,7 +1146,7 @@ __device__ __forceinline__ ExactOut exact_pixel(const ExactArgs& A, int y, int x
         int64_t v = 0;
         if (lane < n_sp) {
             const int yy = y - P.ctx_dy[lane], xx = x + P.ctx_dx[lane];
-            if (yy >= 0 && xx >= 0 && xx < A.W) v = s_ring[(yy & A.ring_mask) * 64 + ((xx + 10 * yy) & 63)];
+            if (yy >= 0 && xx >= 0 && xx < A.W) v = s_ring[ring_cell(yy, xx, A.ring_mask)];
         } else if (A.fin > 0) {
             const int pos = (y >> 1) * A.fw + (x >> 1);
             v = reinterpret_cast<const int16_t*>(P.ifce_feat)[pos * A.fstride + (lane - n_sp)];
@@ -1369,7 +1267,7 @@ struct TaskClock {
 // ---- two pieces of the vector-ALU task body that compile to the same code as functions --------------------------------------
 // Where the decoder puts the pixel's symbol (RowMeta::cell / goff), written right behind the early wait (`row`: kRows = dummy)
 __device__ __forceinline__ void store_row_position(RowMeta& meta, int row, int y, int x, int W, int ring_mask) {
-    meta.cell[row] = static_cast<uint32_t>(((y & ring_mask) << 6) | ((x + 10 * y) & 63));
+    meta.cell[row] = static_cast<uint32_t>(ring_cell(y, x, ring_mask));
     meta.goff[row] = static_cast<uint32_t>(y * W + x);
 }
 // The task's ready bit, behind its table stores: LDS requests of one wave are performed in order, so a relaxed or is enough (a
@@ -1480,16 +1378,16 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
     // Task t of a step (pixels t kTaskPix ..) has the global index seq0 kHalves + t and belongs to producer index % kProducers:
     // a producer visits only its own tasks (first owned one of the step, then every kProducers-th).
     uint32_t phase = static_cast<uint32_t>((static_cast<unsigned long long>(seq_base) * kHalves) % kProducers);  // (seq0 kHalves) mod kProducers
-    const bool split = k_left >= 0 && W > 9 && n_layers >= 2;  // (not in raster order)
-    const uint32_t n_steps_total = it.W <= 9u ? it.H * it.W : it.W + 10u * (it.H - 1u);
+    const bool split = k_left >= 0 && W > 9 && n_layers >= 2;  // !wf_raster(W): the call changed all 23 instantiations
+    const uint32_t n_steps_total = wf_n_steps(it.H, it.W);
     const uint32_t seg_end = seg_first + seg_steps;  // one past the segment's last step
     // leaves step `it` for the next one INSIDE a streamed body (wavefront order, not the last step: straight-line code, no test of
     // the grid's kind or end), with the bookkeeping of the dependencies: where the previous two steps begin in the stream
     const auto walk_on = [&]() {
         prev2_pix0 = prev_pix0; prev_pix0 = pix0; pix0 += it.n; prev_moved = it.moved;
         const uint32_t nx = it.x0 + 1u, mv = nx == it.W ? 1u : 0u;
-        it.x0 = mv ? it.W - 10u : nx; it.y0 += mv; it.moved = mv; --it.left;
-        it.n = min(it.H - it.y0, ((it.x0 * 0xcccdu) >> 19) + 1u);
+        it.x0 = mv ? it.W - kWfSlope : nx; it.y0 += mv; it.moved = mv; --it.left;
+        it.n = min(it.H - it.y0, wf_div10(it.x0) + 1u);
     };
     while (n_steps_total - it.left < seg_end && it.next()) {
         // one step of the segment - or, in a streamed body (StreamBody: its steps cut into tasks without regard to step ends), the
@@ -1516,10 +1414,10 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 const uint32_t ia = seg_pix0 + static_cast<uint32_t>(i0) - pix0;
                 const uint32_t n_a = min(static_cast<uint32_t>(cnt), it.n - ia);
                 const uint32_t bx1 = it.x0 + 1u, b_moved = bx1 == static_cast<uint32_t>(W) ? 1u : 0u;
-                const uint32_t bx0 = b_moved ? static_cast<uint32_t>(W) - 10u : bx1, by0 = it.y0 + b_moved;
+                const uint32_t bx0 = b_moved ? static_cast<uint32_t>(W) - kWfSlope : bx1, by0 = it.y0 + b_moved;
                 const bool in_b = static_cast<uint32_t>(px) >= n_a;  // (also the lanes behind the task's last pixel: unused)
                 const int ii = in_b ? px - static_cast<int>(n_a) : static_cast<int>(ia) + px;
-                const int y = static_cast<int>(in_b ? by0 : it.y0) + ii, x = static_cast<int>(in_b ? bx0 : it.x0) - 10 * ii;
+                const int y = static_cast<int>(in_b ? by0 : it.y0) + ii, x = static_cast<int>(in_b ? bx0 : it.x0) - kWfSlope * ii;
                 const uint32_t dy1 = it.moved, dy2 = it.moved + prev_moved;
                 const uint32_t prev_n = pix0 - prev_pix0, prev2_n = prev_pix0 - prev2_pix0;
                 // ---- vector-ALU body, feature request.  IFCE features do not depend on this grid: REQUEST them before waiting on the
@@ -1601,7 +1499,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     const unsigned long long t_g = PROF_T();
                     {   // where the decoder puts the pixel's symbol (RowMeta::cell / goff)
                         const int mi = (g == 0 && live) ? slot * kBpx + half * kTaskPix + n : kRows;
-                        meta.cell[mi] = static_cast<uint32_t>(((y & ring_mask) << 6) | ((x + 10 * y) & 63));
+                        meta.cell[mi] = static_cast<uint32_t>(ring_cell(y, x, ring_mask));
                         meta.goff[mi] = static_cast<uint32_t>(y * W + x);
                     }
                     // ---- B operand of the first layer: context k = g + 4 t at byte t, the two features at bytes 8..11
@@ -1613,7 +1511,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                             // unconditional read of a clamped cell + select: no exec-mask branches on the task's path
                             const int yy = y - (mf_dxy[t] >> 16), xx = x + static_cast<int16_t>(mf_dxy[t] & 0xffff);
                             const bool take = live && k < n_sp && yy >= 0 && xx >= 0 && xx < W && !(split && k == k_left);
-                            const int cell = take ? (yy & ring_mask) * 64 + ((xx + 10 * yy) & 63) : 0;
+                            const int cell = take ? ring_cell(yy, xx, ring_mask) : 0;
                             int32_t v = C.s_ring[cell];
                             v = take ? v : 0;
                             if (t < 4) w0 |= static_cast<uint32_t>(v & 0xff) << (8 * t);
@@ -1675,7 +1573,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         PROF_ADD(prof[0], t0);
                         PROF_SUB(prof[2], t0);  // the MLP's stamps bracket this wait: take it out of them
                         PROF_ADD(prof[5], t0);  // late wait
-                        if (live && x >= 1) xleft = static_cast<int32_t>(C.s_ring[(y & ring_mask) * 64 + ((x - 1 + 10 * y) & 63)]) << 16;
+                        if (live && x >= 1) xleft = static_cast<int32_t>(C.s_ring[ring_cell(y, x - 1, ring_mask)]) << 16;
                     }
                     clk.d = LPROF_T(pw == 0);
                     const unsigned long long t_h = PROF_T();
@@ -1790,7 +1688,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
 #pragma unroll
                     for (int t = 0; t < NOUT; ++t) {
                         const int yy = y - ctx_dy_l[t], xx = x + ctx_dx_l[t];
-                        rr[t] = C.s_ring[(yy & ring_mask) * 64 + ((xx + 10 * yy) & 63)];
+                        rr[t] = C.s_ring[ring_cell(yy, xx, ring_mask)];
                     }
                     // (a use the compiler cannot sink the reads behind: they stay unconditional - and ALL of them are on their way
                     // before the first one is waited for; one statement per read made it wait for each in turn)
@@ -1950,7 +1848,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 if (split) {
                     clk.begin(TaskClock::kWait);
                     const uint32_t want = uni(need_px);
-                    const uint32_t cell = static_cast<uint32_t>((y & ring_mask) * 64 + ((x - 1 + 10 * y) & 63));
+                    const uint32_t cell = static_cast<uint32_t>(ring_cell(y, x - 1, ring_mask));
                     uint32_t seen_v;
                     int32_t r;
                     asm volatile("ds_read_b32 %0, %2 offset:4\n\tds_read_i8 %1, %3\n\ts_waitcnt lgkmcnt(0)"
@@ -2331,7 +2229,7 @@ __global__ __launch_bounds__(kPipeThreads) void entropy_pipe_kernel(const Entrop
         C.fh = (g == P.n_grids - 1) ? C.H : P.grid_h[g + 1];
         C.fw = (g == P.n_grids - 1) ? C.W : P.grid_w[g + 1];
         {   // widest wavefront step of the grid decides the task shape
-            const int n_max = C.W <= 9 ? 1 : min(C.H, (C.W - 1) / 10 + 1);
+            const int n_max = wf_longest_step(C.H, C.W);
             // wide steps: 8-pixel tasks (throughput); short steps: the fewer pixels a task holds, the sooner its batch is ready
             C.task_pix = n_max >= CCD_T8 ? 8 : (n_max >= CCD_T4 ? 4 : 2);  // at most ~7 tasks per step: one round of the producers
         }
@@ -2538,7 +2436,7 @@ __global__ __launch_bounds__(kPipeThreads) void entropy_pipe_kernel(const Entrop
             int n_streamed = 0;
             for (int g2 = 0; g2 < P.n_grids; ++g2) {
                 const int gh = P.grid_h[g2], gw = P.grid_w[g2];
-                const int n_max = gw <= 9 ? 1 : min(gh, (gw - 1) / 10 + 1);
+                const int n_max = wf_longest_step(gh, gw);
                 StreamBody sb;
                 sb.init(static_cast<uint32_t>(gh), static_cast<uint32_t>(gw), n_max >= CCD_T8 ? 8 : (n_max >= CCD_T4 ? 4 : 2));
                 n_streamed += sb.on ? 1 : 0;
@@ -2586,7 +2484,7 @@ size_t entropy_pipe_lds_bytes(int dim, int n_layers, int ring_rows, int mfma) {
 
 // rows of the decoded-symbol ring for a stream whose widest grid is max_grid_w (0: too wide for the kernel)
 int entropy_pipe_ring_rows(int max_grid_w) {
-    const int need = max_grid_w / 10 + 6;
+    const int need = ring_rows_needed(max_grid_w);
     if (need > kRingRows) return 0;
     int r = 64;
     while (r < need) r *= 2;
@@ -2668,6 +2566,53 @@ hipError_t launch_entropy_pipe(const EntropyParams* d_slots, int n_slots, int nv
 }
 
 }  // namespace ccd
+
+// Host only (tests): the walks of ccd_wavefront.hpp as this translation unit compiles them (include/ccd.h).
+extern "C" int64_t ccd_debug_grid_walk(int h, int w, int task_pix, int which, int32_t* steps, int64_t cap, int32_t* segs, int32_t* n_segs) {
+    using namespace ccd;
+    if (h < 1 || w < 1 || h > kWfMaxSide || w > kWfMaxSide || (task_pix != 2 && task_pix != 4 && task_pix != 8) || which < 0 || which > 4 ||
+        cap < 0 || (segs && !n_segs))
+        return CCD_ERR_ARG;
+    if (segs) {
+        GridSeg gs[3];
+        *n_segs = grid_segments(static_cast<uint32_t>(h), static_cast<uint32_t>(w), task_pix, gs);
+        for (int i = 0; i < *n_segs; ++i) {
+            const int32_t row[6] = {static_cast<int32_t>(gs[i].first), static_cast<int32_t>(gs[i].steps), static_cast<int32_t>(gs[i].pix_before),
+                                    static_cast<int32_t>(gs[i].n_pix), gs[i].task_pix, gs[i].body ? 1 : 0};
+            for (int k = 0; k < 6; ++k) segs[i * 6 + k] = row[k];
+        }
+    }
+    int64_t c = 0;
+    const auto put = [&](uint32_t y0, uint32_t x0, uint32_t n, uint32_t moved, uint32_t left) {
+        if (steps && c < cap) {
+            const uint32_t row[5] = {y0, x0, n, moved, left};
+            for (int k = 0; k < 5; ++k) steps[c * 5 + k] = static_cast<int32_t>(row[k]);
+        }
+        ++c;
+    };
+    if (which == 1) {
+        StepIter it;
+        it.init(h, w);
+        while (it.next()) put(it.y0, it.x0, it.n, 0u, 0u);
+    } else if (which == 3) {
+        const int n_steps = wf_n_steps(h, w);
+        for (int s = 0; s < n_steps; ++s) {
+            int y0, x0;
+            const int n = wf_step(h, w, s, y0, x0);
+            put(y0, x0, n, wf_moved(w, s) ? 1u : 0u, static_cast<uint32_t>(n_steps - 1 - s));
+        }
+    } else {
+        StepWalk it;
+        it.init(static_cast<uint32_t>(h), static_cast<uint32_t>(w));
+        while (it.next()) {
+            if (which == 4 && !it.raster) it.seek_before(static_cast<uint32_t>(c) + 1u);  // this step's state again, all from the closed forms
+            put(it.y0, it.x0, it.n, it.moved, it.left);
+            if (which == 2 && !it.raster && it.left > 0) it.seek_before(static_cast<uint32_t>(c));  // a fresh state for step c
+        }
+    }
+    return c;
+}
+extern "C" int ccd_debug_stream_min_step(void) { return static_cast<int>(ccd::kStreamMinStep); }
 
 #if defined(CCD_PIPE_TRACE)
 // trace builds only (tools/trace_tasks.py): which grid / first task to record, and the records back

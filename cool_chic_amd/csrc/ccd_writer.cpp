@@ -15,6 +15,7 @@
 
 #include "ccd_device.hpp"
 #include "ccd_format.hpp"
+#include "ccd_wavefront.hpp"
 
 namespace ccd {
 namespace {
@@ -345,19 +346,13 @@ int64_t ccd_encode_coolchic(const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
                         feat[(static_cast<size_t>(k) * fh + y) * fw + x] = static_cast<int32_t>(static_cast<int64_t>(static_cast<float>(o[k])));
                 }
         }
-        const bool raster = W <= 9;
-        const long n_steps = raster ? static_cast<long>(H) * W : W + 10L * (H - 1);
+        const int n_steps = wf_n_steps(H, W);  // coding order: ccd_wavefront.hpp
         int64_t ctx[128], ms[2];
-        for (long c = 0; c < n_steps; ++c) {
-            int y0, x0, cnt;
-            if (raster) { y0 = static_cast<int>(c / W); x0 = static_cast<int>(c % W); cnt = 1; }
-            else {
-                if (c < W) { y0 = 0; x0 = static_cast<int>(c); }
-                else { y0 = static_cast<int>((c - W) / 10) + 1; x0 = W - 10 + static_cast<int>((c - W) % 10); }
-                cnt = std::min(H - y0, x0 / 10 + 1);
-            }
+        for (int c = 0; c < n_steps; ++c) {
+            int y0, x0;
+            const int cnt = wf_step(H, W, c, y0, x0);
             for (int i = 0; i < cnt; ++i) {
-                const int y = y0 + i, x = x0 - 10 * i;
+                const int y = y0 + i, x = x0 - kWfSlope * i;
                 for (int k = 0; k < n_sp; ++k) {
                     const int yy = y - dy[k], xx = x + dx[k];
                     ctx[k] = (yy >= 0 && xx >= 0 && xx < W) ? grids[g][static_cast<size_t>(yy) * W + xx] : 0;

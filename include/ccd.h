@@ -190,6 +190,15 @@ int ccd_batch_slot_stats(const ccd_batch* b, int slot, int32_t* out64);
  * instantiations inst[] (0 .. k - 1; -1 = generic kernel) on a device with n_conc concurrent streams and n_cu CUs: cg[i] in 0 .. 2;
  * returns the number of groups in use.  See ccd_batch_run. */
 int ccd_debug_chain_groups(const double* est, const int32_t* inst, int n, int n_conc, int n_cu, int32_t* cg);
+/* Host only (tests): the entropy stage's walk over one grid of h x w latents, computed by the code the kernels and both
+ * writers compile (ccd_wavefront.hpp).  which = 0: StepWalk::next from init; 1: StepIter::next; 2: for every step c >= 1 of
+ * a wavefront grid, StepWalk::seek_before(c) followed by next() (step 0 from init); 3: the free functions, step by step;
+ * 4: for every step c of a wavefront grid, the state of step c as seek_before(c + 1) leaves it (n: len_of, moved: moved_at).
+ * steps (may be NULL): [cap][5] = y0, x0, n, moved, left after the step (moved / left: 0 where `which` has none).
+ * segs (may be NULL): [3][6] = first, steps, pix_before, n_pix, task_pix, body of grid_segments(h, w, task_pix); *n_segs.
+ * Returns the number of steps (also with steps == NULL), CCD_ERR_ARG for h, w < 1 or > 16383 or task_pix not 2 / 4 / 8. */
+int64_t ccd_debug_grid_walk(int h, int w, int task_pix, int which, int32_t* steps, int64_t cap, int32_t* segs, int32_t* n_segs);
+int ccd_debug_stream_min_step(void);   /* kStreamMinStep of this build */
 /* How many of the library's side streams on `device` were MEASURED to run kernels concurrently (1 .. 4; once per process, ~10 ms
  * at the first call or the first ccd_batch_create): HIP multiplexes streams onto a few hardware queues, and launches on streams
  * that share one run one after the other.  The entropy launches of a batch that should overlap are put on these streams only,

@@ -243,6 +243,46 @@ def test_host_writer_is_the_yardstick(gpu, oracle):
     assert writer.encode_stream(hdr, nn, lat, device=0) == bs
 
 
+@pytest.mark.gpu
+def test_grids_on_the_edges_of_the_coding_order(gpu, oracle, monkeypatch):
+    """Pictures whose grids sit where the coding order (ccd_wavefront.hpp) changes its rule: widths 9 / 10 / 11 (raster against
+    wavefront) and 18 .. 21, 36 .. 42 (a step's first column moving into the next ten).  kodim14's networks, seeded random
+    latents: the device writer's bytes are the host writer's, and both entropy kernels read the same latents back."""
+    from cool_chic_amd import DecodeBatch, writer
+
+    bs, z, _ = load_golden("kodim14")
+    hdr, nn, _ = _cool_chics(oracle, bs)[0]
+    donor = writer.parse_cc_header(hdr)
+    rng = np.random.default_rng(20241019)
+    jobs = []
+    for size, widths in [((12, 40), (40, 20, 10, 5)), ((11, 42), (42, 21, 11, 6)), ((7, 36), (36, 18, 9)), ((3, 19), (19, 10, 5))]:
+        arch = writer.derive_arch(donor, img_size=size)
+        assert tuple(arch.grid_w[:len(widths)]) == widths
+        nn_i = nn
+        if writer.network_layout(arch) != writer.network_layout(donor):  # (3 rows: a grid's level comes from the height ratio)
+            nn_i = writer.encode_network(arch, writer.adapt_network(donor, z["cc0.nn_ints"], arch))
+        lat = [np.clip(np.rint(rng.laplace(0.0, 1.5, size=(arch.grid_h[g], arch.grid_w[g]))), -30, 30).astype(np.int8)
+               for g in range(arch.n_grids)]
+        jobs.append((arch, nn_i, lat))
+    got = _encode_all(gpu, jobs)
+    for (arch, nn_i, lat), cc in zip(jobs, got):
+        assert cc == writer.encode_coolchic(arch, nn_i, lat), tuple(arch.img_size)
+    for generic in (0, 1):
+        monkeypatch.setenv("CCD_FORCE_GENERIC", str(generic))  # read when a batch is created
+        dec = DecodeBatch(0)
+        try:
+            for cc in got:
+                dec.add(*_split_cc(cc), 8, 0)
+            dec.run()
+            dec.wait()
+            for i, (arch, _, lat) in enumerate(jobs):
+                assert dec.slot_status(i) == 0 and (dec.slot_kernels(i) & 1) == 1 - generic, (i, generic)
+                for g, a in enumerate(lat):
+                    assert np.array_equal(dec.latent(i, g), a), (tuple(arch.img_size), g, generic)
+        finally:
+            dec.close()
+
+
 def _round_trip(gpu, oracle, streams):
     """Decode every cool-chic of `streams` in one DecodeBatch, hand all slots to one EncodeBatch without leaving the device,
     compare with the bytes that were decoded; then decode the device-written payloads again: same latents."""
