@@ -213,8 +213,12 @@ SIGNATURES = {
     "ccd_rdoq_set_maps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "ccd_rdoq_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
                                 C.c_void_p]),
+    "ccd_rdoq_max_rounds": (C.c_int, []),
+    "ccd_rdoq_step_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_uint64), C.c_int, C.c_void_p]),
     "ccd_rdoq_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_rdoq_slot_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RdoqResult)]),
+    "ccd_rdoq_slot_open": (C.c_int64, [C.c_void_p, C.c_int]),
     "ccd_rdoq_slot_moves": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,

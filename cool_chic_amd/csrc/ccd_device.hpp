@@ -179,6 +179,8 @@ constexpr int kDsensBandSamples = 4096;  // luma samples of a band, about
 constexpr int kRdoqCell = 8;             // luma samples per side of a claim-raster cell (even: a 4:2:0 chroma sample lies in one cell)
 constexpr uint32_t kRdoqLaneCells = 32;  // a box of up to this many cells is walked by its latent's lane, a larger one by a wave
 constexpr uint32_t kRdoqChunk = 1024;    // latents one workgroup of the reduce launch sums
+constexpr int kRdoqMaxRounds = 64;       // rounds of one step at most (ccd_rdoq_max_rounds)
+constexpr uint8_t kRdoqSelected = 4, kRdoqBlocked = 8;  // bits of a pick byte beside the candidate's 1 / 2
 // The influence box of a latent in cells of the claim raster, inclusive (ccd_rdoq_influence_box).
 struct RdoqBox { uint16_t top, left, bottom, right; };
 // One grid of one slot.  The latents of a slot are numbered uid = first + y * w + x over its grids.
@@ -187,22 +189,25 @@ struct RdoqGrid {
     const int64_t* dd;       // [2][h][w], nullptr: zeros
     const float* db;         // [2][h][w]
     int8_t* moves;           // [h][w]: -1, 0, +1
-    uint8_t* pick;           // [h][w]: 0 no candidate, 1 candidate for -1, 2 candidate for +1 (claim -> select, reduce)
+    uint8_t* pick;           // [h][w]: 0 no candidate, 1 candidate for -1, 2 candidate for +1 (claim -> select, reduce), with
+                             // kRdoqSelected / kRdoqBlocked once a round has settled the candidate; neither: open
     const RdoqBox* box;      // [h][w]
     const uint32_t* big;     // indices y * w + x of the latents whose box has more than kRdoqLaneCells cells, ascending
     uint32_t n, first;       // h * w; uid of (0, 0)
     int32_t slot, grid;
 };
 struct RdoqSlot {
-    unsigned long long* raster;  // [cells_h][cells_w] claim words, all ones between two steps
+    unsigned long long* raster;  // [cells_h][cells_w] claim words, all ones between two rounds and between two steps
+    uint8_t* taken;              // [cells_h][cells_w]: 1 for a cell of a box selected in an earlier round of this step, 0 between steps
     int32_t cells_h, cells_w;
     double kD, kR, min_gain;
     uint64_t grid_mask;          // bit g admits the candidates of grid g
     int32_t first_grid, n_grids; // its entries of the grid table
     uint32_t raster_units;       // 16-byte units of the raster block
+    uint32_t taken_units;        // ... and of the taken block
 };
 // What one workgroup of the reduce launch leaves for a chunk of kRdoqChunk latents of one grid.
-struct RdoqPartial { int64_t n_candidates, n_moves, d_sse; double d_bits; };
+struct RdoqPartial { int64_t n_candidates, n_moves, d_sse; double d_bits; int64_t n_open; };
 
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.

@@ -82,8 +82,9 @@ hipError_t launch_latent_ingest(const IngestSeg* d_segs, const uint32_t* d_prefi
 hipError_t launch_dsens_apply(const DsensSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, hipStream_t stream);
 hipError_t launch_dsens_sse(const DsensPass* d_passes, const uint32_t* d_unit_prefix, const uint32_t* d_probe_prefix, int n_passes,
                             uint32_t n_units, uint32_t n_probes, int64_t* d_slab, hipStream_t stream);
-// ccd_rdoq.hip: claim, select, and the two phases of the reduce launch of one step
+// ccd_rdoq.hip: `rounds` times claim, select (and settle between two rounds), then the two phases of the reduce launch of one step
 hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
-                            const uint32_t* d_chunk_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks, uint32_t n_big,
-                            uint32_t n_chunks, RdoqPartial* d_partial, ccd_rdoq_result* d_results, hipStream_t stream);
+                            const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
+                            uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
+                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream);
 }  // namespace ccd

@@ -1,24 +1,36 @@
 // ccd_rdoq.hip - one RDOQ step: choose and apply +-1 moves of latents that provably do not interact (gfx950, wave64;
 // DESIGN.md 4.14, include/ccd.h ccd_rdoq_*).
 //
+// A step is R rounds (ccd_rdoq_step_rounds; R = 1: ccd_rdoq_step).  A candidate is open, selected or blocked; a round lets the open
+// ones compete, selects the winners and takes the cells of their boxes, and a candidate whose box holds a taken cell is blocked
+// for good.  With fixed keys the rounds end at the set a walk over the candidates in key order would take.
+//
 // Inputs are the two delta maps of every grid (distortion: int64, rate: float32) and, per latent, its influence box in cells
 // of the slot's claim raster (built on the host by the code behind ccd_rdoq_influence_box).  Two latents whose boxes share no
 // cell neither share a symbol of the rate model nor a sample of the planes, so their deltas add.
-//   rdoq_claim_kernel   the cost of both moves of a latent, its better move, whether that is a candidate, its 64-bit key
-//                       (cost as an ordered float, then the latent's number); a candidate does atomicMin of the key into every
-//                       cell of its box.  The smallest key wins a cell whatever the order of the atomics.
-//   rdoq_select_kernel  a candidate that finds its own key in every cell of its box is selected: the latent is stored as v + s
-//                       (a byte store into the caller's grid), the move map gets s, every other latent's entry 0.
-//   rdoq_reduce_kernel  phase 0: a workgroup sums candidates, moves, dD and dBits of one chunk of one grid; phase 1: a wave
-//                       per slot adds the chunks grid by grid, writes the result and stores all ones into the claim raster.
+//   rdoq_claim_kernel   round 0: the cost of both moves of a latent, its better move, whether that is a candidate, its 64-bit key
+//                       (cost as an ordered float, then the latent's number); later rounds: the open candidates, the same key.
+//                       An open candidate with a taken cell in its box becomes blocked and claims nothing (round 0 has nothing to
+//                       test: no cell is taken yet); every other one does atomicMin of the key into every cell of its box.  The smallest key wins a cell whatever the order
+//                       of the atomics.
+//   rdoq_select_kernel  an open candidate that finds its own key in every cell of its box is selected: the latent is stored as
+//                       v + s (a byte store into the caller's grid), the move map gets s; round 0 gives every other latent's
+//                       entry 0.
+//   rdoq_settle_kernel  between two rounds, a lane per cell: a cell whose key belongs to a candidate selected in this round
+//                       becomes taken, and the claim word goes back to all ones.
+//   rdoq_reduce_kernel  phase 0: a workgroup sums candidates, moves, open candidates, dD and dBits of one chunk of one grid;
+//                       phase 1: a wave per slot adds the chunks grid by grid, writes the result, stores all ones into the
+//                       claim raster and zeros into the taken raster.
 // Work is dealt out by cells: a workgroup is one wave, and it is either 64 latents of one grid, a lane each, for boxes of
 // up to kRdoqLaneCells cells, or ONE latent with a larger box (the grid's `big` list), the lanes over its cells.  A workgroup
 // finds its grid by bisection of a prefix table, as the dsens kernels do.
 //
-// The raster.  claim needs all ones.  select is the raster's last reader of a step; phase 1 of the reduce launch follows it on
-// the stream and stores all ones with plain vector stores; the next step's claim follows that launch on the stream.  Each word
-// is written by one kind of access per launch (atomics in claim, plain stores in reduce), and launches are ordered by their
-// stream: no access of one launch meets one of another.  The first step finds the ones ccd_rdoq_add left.
+// The rasters.  claim needs all ones in the claim raster and the cells taken so far in the taken raster.  Inside one launch a
+// word of either sees one kind of access: claim does plain loads of taken and atomics on the claim words; select does plain
+// loads of the claim words; settle loads a claim word and the pick byte of its owner and stores the cell's two words, one lane
+// per cell; phase 1 of the reduce launch, which follows the last round's select in place of a settle, stores every word of both
+// rasters with plain vector stores.  Launches are ordered by their stream: no access of one launch meets one of another.  The
+// first step finds what ccd_rdoq_add left: all ones and zeros.
 //
 // Sums: integers in any order; dBits in float64 in an order that is a function of the geometry alone (a lane adds its latents
 // in ascending order, a fixed shuffle tree adds the lanes, chunks and grids are added in ascending order).  No float atomics.
@@ -37,6 +49,9 @@ __device__ __forceinline__ uint32_t ordered(float c) {
 }
 
 struct Move { int pick; int s; unsigned long long key; };  // pick: 0 no candidate, 1 / 2 candidate for -1 / +1
+
+// A candidate no round has selected or blocked.
+__device__ __forceinline__ bool is_open(uint32_t pick) { return pick != 0 && !(pick & (kRdoqSelected | kRdoqBlocked)); }
 
 // Rule steps 1-3 for latent i of grid G.  Separate roundings of the two products and of the sum: what numpy float64 does.
 __device__ __forceinline__ Move best_move(const RdoqGrid& G, const RdoqSlot& S, uint32_t i) {
@@ -74,8 +89,9 @@ __device__ __forceinline__ Cells cells_of(const RdoqBox b, const RdoqSlot& S) {
     return c;
 }
 
-// kSelect == false: claim.  kSelect == true: select and apply.
-template <bool kSelect>
+// kSelect == false: claim.  kSelect == true: select and apply.  Round 0 (kFirst) finds the candidates; a later round reads their
+// state from the pick bytes and forms an open candidate's key again: its latent and the maps are what they were.
+template <bool kSelect, bool kFirst>
 __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                           const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix, int n_grids,
                                           uint32_t n_lane_blocks) {
@@ -89,14 +105,29 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
         const Cells c = cells_of(G.box[i], S);
         if (c.n > kRdoqLaneCells) return;  // a wave's
         if (!kSelect) {
-            const Move m = best_move(G, S, i);
-            G.pick[i] = static_cast<uint8_t>(m.pick);
-            if (m.pick)
+            Move m;
+            uint32_t pick;
+            if (kFirst) {
+                m = best_move(G, S, i);
+                pick = static_cast<uint32_t>(m.pick);
+            } else {
+                pick = G.pick[i];
+                if (!is_open(pick)) return;
+                m = best_move(G, S, i);
+            }
+            bool blocked = false;
+            if (!kFirst)  // (no cell is taken before the first round)
+                for (uint32_t r = 0; r < c.bh; ++r)
+                    for (uint32_t q = 0; q < c.bw; ++q) blocked = blocked || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
+            if (blocked) pick |= kRdoqBlocked;
+            if (kFirst || blocked) G.pick[i] = static_cast<uint8_t>(pick);
+            if (pick && !blocked)
                 for (uint32_t r = 0; r < c.bh; ++r)
                     for (uint32_t q = 0; q < c.bw; ++q) atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
         } else {
             int s = 0;
-            if (G.pick[i]) {
+            const uint32_t pick = G.pick[i];
+            if (is_open(pick)) {
                 const Move m = best_move(G, S, i);
                 bool mine = true;
                 for (uint32_t r = 0; r < c.bh; ++r)
@@ -104,9 +135,10 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
                 if (mine) {
                     s = m.s;
                     G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
+                    G.pick[i] = static_cast<uint8_t>(pick | kRdoqSelected);
                 }
             }
-            G.moves[i] = static_cast<int8_t>(s);
+            if (kFirst || s) G.moves[i] = static_cast<int8_t>(s);
         }
         return;
     }
@@ -118,17 +150,36 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
     const uint32_t i = G.big[u - big_prefix[e]];
     if (i >= G.n) return;
     const Cells c = cells_of(G.box[i], S);
+    // every lane reads the pick byte and the latent (best_move) before lane 0 stores either: one wave, program order
     if (!kSelect) {
-        const Move m = best_move(G, S, i);
-        if (lane == 0) G.pick[i] = static_cast<uint8_t>(m.pick);
-        if (m.pick)
+        Move m;
+        uint32_t pick;
+        if (kFirst) {
+            m = best_move(G, S, i);
+            pick = static_cast<uint32_t>(m.pick);
+        } else {
+            pick = G.pick[i];
+            if (!is_open(pick)) return;  // (the same in every lane)
+            m = best_move(G, S, i);
+        }
+        bool hit = false;
+        if (!kFirst)  // (no cell is taken before the first round)
+            for (uint32_t t = lane; t < c.n; t += 64) {
+                const uint32_t r = t / c.bw, q = t - r * c.bw;
+                hit = hit || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
+            }
+        const bool blocked = __any(hit);
+        if (blocked) pick |= kRdoqBlocked;
+        if (lane == 0 && (kFirst || blocked)) G.pick[i] = static_cast<uint8_t>(pick);
+        if (pick && !blocked)
             for (uint32_t t = lane; t < c.n; t += 64) {
                 const uint32_t r = t / c.bw, q = t - r * c.bw;
                 atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
             }
     } else {
         int s = 0;
-        if (G.pick[i]) {  // (the same in every lane)
+        const uint32_t pick = G.pick[i];
+        if (is_open(pick)) {  // (the same in every lane)
             const Move m = best_move(G, S, i);
             bool mine = true;
             for (uint32_t t = lane; t < c.n; t += 64) {
@@ -136,23 +187,47 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
                 mine = mine && S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] == m.key;
             }
             if (__all(mine)) s = m.s;
-            // every lane has read the latent (best_move) before lane 0 stores it: one wave, program order
-            if (lane == 0 && s) G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
+            if (lane == 0 && s) {
+                G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
+                G.pick[i] = static_cast<uint8_t>(pick | kRdoqSelected);
+            }
         }
-        if (lane == 0) G.moves[i] = static_cast<int8_t>(s);
+        if (lane == 0 && (kFirst || s)) G.moves[i] = static_cast<int8_t>(s);
     }
 }
 
+// kFirst: the kernels of round 0, all that a step of one round runs before the sums.
+template <bool kFirst>
 __global__ __launch_bounds__(64) void rdoq_claim_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                         const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
                                                         int n_grids, uint32_t n_lane_blocks) {
-    step_body<false>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
+    step_body<false, kFirst>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
 }
 
+template <bool kFirst>
 __global__ __launch_bounds__(64) void rdoq_select_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                          const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
                                                          int n_grids, uint32_t n_lane_blocks) {
-    step_body<true>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
+    step_body<true, kFirst>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
+}
+
+// Between two rounds: 64 cells of one slot, a lane each.  The low half of a claimed word is its owner's uid; the owner claimed
+// in this round, so a selected owner was selected in this round and owns every cell of its box.
+__global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                         const uint32_t* __restrict__ cell_prefix, int n_slots) {
+    const int k = entry_of(cell_prefix, n_slots, blockIdx.x);
+    const RdoqSlot& S = slots[k];
+    const size_t cell = static_cast<size_t>(blockIdx.x - cell_prefix[k]) * 64u + threadIdx.x;
+    if (cell >= static_cast<size_t>(S.cells_h) * S.cells_w) return;
+    const unsigned long long key = S.raster[cell];
+    if (key == ~0ull) return;  // nobody claimed the cell
+    const uint32_t uid = static_cast<uint32_t>(key);
+    int g = 0;  // the grid of the uid: first[] ascends over the slot's few grids
+    while (g + 1 < S.n_grids && grids[S.first_grid + g + 1].first <= uid) ++g;
+    const RdoqGrid& G = grids[S.first_grid + g];
+    const uint32_t i = uid - G.first;
+    if (i < G.n && (G.pick[i] & kRdoqSelected)) S.taken[cell] = 1;
+    S.raster[cell] = ~0ull;
 }
 
 __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
@@ -168,16 +243,19 @@ __device__ __forceinline__ double wave_sum_f64(double v) {  // a fixed tree: lan
 
 __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                          const uint32_t* __restrict__ chunk_prefix, int n_grids,
-                                                         RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results, int phase) {
+                                                         RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
+                                                         int64_t* __restrict__ open, int phase) {
     const uint32_t lane = threadIdx.x;
-    RdoqPartial acc = {0, 0, 0, 0.0};
+    RdoqPartial acc = {0, 0, 0, 0.0, 0};
     if (phase == 0) {
         const int e = entry_of(chunk_prefix, n_grids, blockIdx.x);
         const RdoqGrid& G = grids[e];
         const uint32_t i0 = (blockIdx.x - chunk_prefix[e]) * kRdoqChunk;
         const uint32_t i1 = min(i0 + kRdoqChunk, G.n);
         for (uint32_t i = i0 + lane; i < i1; i += 64) {
-            acc.n_candidates += G.pick[i] != 0;
+            const uint32_t pick = G.pick[i];
+            acc.n_candidates += pick != 0;
+            acc.n_open += is_open(pick);  // it took part in the last round and lost a cell
             const int s = G.moves[i];
             if (s == 0) continue;
             const size_t at = (s > 0 ? static_cast<size_t>(G.n) : 0) + i;
@@ -188,26 +266,29 @@ __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restr
     } else {
         const RdoqSlot& S = slots[blockIdx.x];
         ccd_rdoq_result& R = results[blockIdx.x];
-        RdoqPartial total = {0, 0, 0, 0.0};
+        RdoqPartial total = {0, 0, 0, 0.0, 0};
         for (int g = 0; g < S.n_grids; ++g) {
             const int e = S.first_grid + g;
-            acc = {0, 0, 0, 0.0};
+            acc = {0, 0, 0, 0.0, 0};
             for (uint32_t c = chunk_prefix[e] + lane; c < chunk_prefix[e + 1]; c += 64) {
                 const RdoqPartial P = partial[c];
                 acc.n_candidates += P.n_candidates;
                 acc.n_moves += P.n_moves;
                 acc.d_sse += P.d_sse;
                 acc.d_bits = __dadd_rn(acc.d_bits, P.d_bits);
+                acc.n_open += P.n_open;
             }
             acc.n_candidates = wave_sum_i64(acc.n_candidates);
             acc.n_moves = wave_sum_i64(acc.n_moves);
             acc.d_sse = wave_sum_i64(acc.d_sse);
             acc.d_bits = wave_sum_f64(acc.d_bits);
+            acc.n_open = wave_sum_i64(acc.n_open);
             if (lane == 0) R.n_moves_grid[g] = acc.n_moves;
             total.n_candidates += acc.n_candidates;
             total.n_moves += acc.n_moves;
             total.d_sse += acc.d_sse;
             total.d_bits = __dadd_rn(total.d_bits, acc.d_bits);
+            total.n_open += acc.n_open;
         }
         for (int g = S.n_grids + static_cast<int>(lane); g < CCD_MAX_GRIDS; g += 64) R.n_moves_grid[g] = 0;  // the block is the pool's
         if (lane == 0) {
@@ -218,29 +299,40 @@ __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restr
             R.d_sse = total.d_sse;
             R.d_bits = total.d_bits;
             R.d_cost = 0.0;  // the host's
+            open[blockIdx.x] = total.n_open;
         }
-        // all ones for the next step's claim (the ordering argument is at the head of this file)
+        // all ones and no taken cell for the next step's claim (the ordering argument is at the head of this file)
         uint4* words = reinterpret_cast<uint4*>(S.raster);
         for (uint32_t t = lane; t < S.raster_units; t += 64) words[t] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        uint4* marks = reinterpret_cast<uint4*>(S.taken);
+        for (uint32_t t = lane; t < S.taken_units; t += 64) marks[t] = make_uint4(0u, 0u, 0u, 0u);
         return;
     }
     acc.n_candidates = wave_sum_i64(acc.n_candidates);
     acc.n_moves = wave_sum_i64(acc.n_moves);
     acc.d_sse = wave_sum_i64(acc.d_sse);
     acc.d_bits = wave_sum_f64(acc.d_bits);
+    acc.n_open = wave_sum_i64(acc.n_open);
     if (lane == 0) partial[blockIdx.x] = acc;
 }
 }  // namespace
 
 hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
-                            const uint32_t* d_chunk_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks, uint32_t n_big,
-                            uint32_t n_chunks, RdoqPartial* d_partial, ccd_rdoq_result* d_results, hipStream_t stream) {
-    if (n_grids <= 0 || n_slots <= 0 || n_lane_blocks == 0 || n_chunks == 0) return hipSuccess;
+                            const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
+                            uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
+                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream) {
+    if (n_grids <= 0 || n_slots <= 0 || n_lane_blocks == 0 || n_chunks == 0 || n_cell_blocks == 0 || rounds < 1) return hipSuccess;
     const dim3 units(n_lane_blocks + n_big);
-    hipLaunchKernelGGL(rdoq_claim_kernel, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks);
-    hipLaunchKernelGGL(rdoq_select_kernel, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks);
-    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_chunks), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, 0);
-    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_slots), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, 1);
+    for (int k = 0; k < rounds; ++k) {
+        hipLaunchKernelGGL(k == 0 ? rdoq_claim_kernel<true> : rdoq_claim_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix,
+                           d_big_prefix, n_grids, n_lane_blocks);
+        hipLaunchKernelGGL(k == 0 ? rdoq_select_kernel<true> : rdoq_select_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix,
+                           d_big_prefix, n_grids, n_lane_blocks);
+        // after the last round phase 1 of the reduce launch writes both rasters
+        if (k + 1 < rounds) hipLaunchKernelGGL(rdoq_settle_kernel, dim3(n_cell_blocks), dim3(64), 0, stream, d_grids, d_slots, d_cell_prefix, n_slots);
+    }
+    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_chunks), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, d_open, 0);
+    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_slots), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, d_open, 1);
     return hipGetLastError();
 }
 }  // namespace ccd

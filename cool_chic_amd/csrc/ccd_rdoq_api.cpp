@@ -116,13 +116,14 @@ struct RSlot {
     const int64_t* dd[CCD_MAX_GRIDS] = {};
     const float* db[CCD_MAX_GRIDS] = {};
     bool have_maps = false;
-    Block mem;                               // boxes, big lists, move maps, pick bytes, raster
+    Block mem;                               // boxes, big lists, move maps, pick bytes, claim raster, taken raster
     size_t box_off[CCD_MAX_GRIDS] = {}, big_off[CCD_MAX_GRIDS] = {}, moves_off[CCD_MAX_GRIDS] = {}, pick_off[CCD_MAX_GRIDS] = {};
-    size_t raster_off = 0;
+    size_t raster_off = 0, taken_off = 0;
     uint32_t n[CCD_MAX_GRIDS] = {}, n_big[CCD_MAX_GRIDS] = {}, first[CCD_MAX_GRIDS] = {};
-    uint32_t raster_units = 0;
+    uint32_t raster_units = 0, taken_units = 0;
     double kD = 0, kR = 0;
     ccd_rdoq_result result;
+    int64_t n_open = 0;                      // candidates of the last round that lost a cell
     bool covered = false;                    // by a finished step
 };
 }  // namespace
@@ -141,6 +142,8 @@ struct ccd_rdoq {
 extern "C" {
 
 int ccd_rdoq_cell(void) { return kRdoqCell; }
+
+int ccd_rdoq_max_rounds(void) { return kRdoqMaxRounds; }
 
 int ccd_rdoq_influence_box(const ccd_cc_header* arch, int frame_data_type, int grid, int y, int x, int32_t cells[4]) {
     if (!arch || !cells || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
@@ -220,11 +223,16 @@ int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, in
     const size_t raster_bytes = align256(static_cast<size_t>(s.geo.cells_h) * s.geo.cells_w * sizeof(unsigned long long));
     s.raster_units = static_cast<uint32_t>(raster_bytes / 16);
     bytes += raster_bytes;
+    s.taken_off = bytes;
+    const size_t taken_bytes = align256(static_cast<size_t>(s.geo.cells_h) * s.geo.cells_w);
+    s.taken_units = static_cast<uint32_t>(taken_bytes / 16);
+    bytes += taken_bytes;
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(r->device));
     if (!s.mem.get(r->device, BlockPool::kDevice, bytes)) return CCD_ERR_NOMEM;
     if (hipMemcpy(s.mem.p, host.data(), upload, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(s.mem.as<char>() + s.raster_off, 0xff, raster_bytes) != hipSuccess ||  // what the first step's claim needs
+        hipMemset(s.mem.as<char>() + s.raster_off, 0xff, raster_bytes) != hipSuccess ||  // what the first step's claim needs:
+        hipMemset(s.mem.as<char>() + s.taken_off, 0, taken_bytes) != hipSuccess ||      // all ones, and no cell taken
         hipDeviceSynchronize() != hipSuccess) {
         s.mem.drop();
         return CCD_ERR_HIP;
@@ -245,7 +253,12 @@ int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const flo
 }
 
 int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream) {
-    if (!r || !kD || !kR || !min_gain || !grid_mask) return CCD_ERR_ARG;
+    return ccd_rdoq_step_rounds(r, kD, kR, min_gain, grid_mask, 1, stream);
+}
+
+int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, int max_rounds,
+                         void* stream) {
+    if (!r || !kD || !kR || !min_gain || !grid_mask || max_rounds < 1 || max_rounds > kRdoqMaxRounds) return CCD_ERR_ARG;
     if (r->pending) return CCD_ERR_ARG;
     const int n_slots = static_cast<int>(r->slots.size());
     int n_grids = 0;
@@ -256,22 +269,26 @@ int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double*
         n_grids += r->slots[k]->n_grids;
     }
     if (n_slots == 0) return CCD_OK;
-    // the tables of this step: grids, slots and the three prefix tables, one block, one copy
+    // the tables of this step: grids, slots and the four prefix tables, one block, one copy
     std::vector<RdoqGrid> grids;
     std::vector<RdoqSlot> slots(n_slots);
-    std::vector<uint32_t> lane_prefix(n_grids + 1, 0), big_prefix(n_grids + 1, 0), chunk_prefix(n_grids + 1, 0);
-    uint64_t lanes = 0, bigs = 0, chunks = 0;
+    std::vector<uint32_t> lane_prefix(n_grids + 1, 0), big_prefix(n_grids + 1, 0), chunk_prefix(n_grids + 1, 0), cell_prefix(n_slots + 1, 0);
+    uint64_t lanes = 0, bigs = 0, chunks = 0, cell_blocks = 0;
     for (int k = 0; k < n_slots; ++k) {
         RSlot& s = *r->slots[k];
         char* base = s.mem.as<char>();
         RdoqSlot& S = slots[k];
         std::memset(&S, 0, sizeof(S));
         S.raster = reinterpret_cast<unsigned long long*>(base + s.raster_off);
+        S.taken = reinterpret_cast<uint8_t*>(base + s.taken_off);
         S.cells_h = s.geo.cells_h; S.cells_w = s.geo.cells_w;
         S.kD = s.kD = kD[k]; S.kR = s.kR = kR[k]; S.min_gain = min_gain[k];
         S.grid_mask = grid_mask[k];
         S.first_grid = static_cast<int32_t>(grids.size()); S.n_grids = s.n_grids;
-        S.raster_units = s.raster_units;
+        S.raster_units = s.raster_units; S.taken_units = s.taken_units;
+        cell_blocks += (static_cast<uint64_t>(s.geo.cells_h) * s.geo.cells_w + 63) / 64;  // settle: a lane per cell
+        if (cell_blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+        cell_prefix[k + 1] = static_cast<uint32_t>(cell_blocks);
         for (int g = 0; g < s.n_grids; ++g) {
             RdoqGrid G;
             std::memset(&G, 0, sizeof(G));
@@ -291,13 +308,15 @@ int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double*
     }
     TableImage img;
     const size_t o_grids = img.put(grids), o_slots = img.put(slots);
-    const size_t o_lane = img.put(lane_prefix), o_big = img.put(big_prefix), o_chunk = img.put(chunk_prefix);
+    const size_t o_lane = img.put(lane_prefix), o_big = img.put(big_prefix), o_chunk = img.put(chunk_prefix), o_cell = img.put(cell_prefix);
     const std::vector<char>& buf = img.bytes;
     HIP_TRY(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     r->streams.note(st);
     // nothing of an earlier step is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
-    const size_t res_bytes = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
+    // the results, then one int64 per slot: its open candidates
+    const size_t open_off = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
+    const size_t res_bytes = open_off + static_cast<size_t>(n_slots) * sizeof(int64_t);
     if (!r->tables.ensure(r->device, buf.size()) || !r->partial.ensure(r->device, BlockPool::kDevice, chunks * sizeof(RdoqPartial)) ||
         !r->results.ensure(r->device, res_bytes))
         return CCD_ERR_NOMEM;
@@ -307,9 +326,11 @@ int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double*
         r->tables.upload(buf.size(), st) == hipSuccess &&
         launch_rdoq_step(reinterpret_cast<const RdoqGrid*>(base + o_grids), reinterpret_cast<const RdoqSlot*>(base + o_slots),
                          reinterpret_cast<const uint32_t*>(base + o_lane), reinterpret_cast<const uint32_t*>(base + o_big),
-                         reinterpret_cast<const uint32_t*>(base + o_chunk), n_grids, n_slots, static_cast<uint32_t>(lanes),
-                         static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks), r->partial.as<RdoqPartial>(),
-                         r->results.dev.as<ccd_rdoq_result>(), st) == hipSuccess &&
+                         reinterpret_cast<const uint32_t*>(base + o_chunk), reinterpret_cast<const uint32_t*>(base + o_cell), n_grids,
+                         n_slots, static_cast<uint32_t>(lanes), static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks),
+                         static_cast<uint32_t>(cell_blocks), max_rounds, r->partial.as<RdoqPartial>(),
+                         r->results.dev.as<ccd_rdoq_result>(), reinterpret_cast<int64_t*>(r->results.dev.as<char>() + open_off),
+                         st) == hipSuccess &&
         r->results.download(res_bytes, st) == hipSuccess;
     if (!ok) {  // part of the step may have been enqueued: drain it; no slot has a result, no step is in flight
         (void)hipStreamSynchronize(st);
@@ -331,9 +352,11 @@ int ccd_rdoq_wait(ccd_rdoq* r, void* stream) {
     if (r->step_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(r->step_stream));
     r->pending = 0;
     const ccd_rdoq_result* res = r->results.host.as<ccd_rdoq_result>();
+    const int64_t* open = reinterpret_cast<const int64_t*>(res + r->n_stepped);
     for (int k = 0; k < r->n_stepped; ++k) {
         RSlot& s = *r->slots[k];
         s.result = res[k];
+        s.n_open = open[k];
         s.result.d_cost = s.kD * static_cast<double>(s.result.d_sse) + s.kR * s.result.d_bits;
         s.covered = true;
     }
@@ -345,6 +368,12 @@ int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out) {
     if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
     *out = r->slots[slot]->result;
     return CCD_OK;
+}
+
+int64_t ccd_rdoq_slot_open(const ccd_rdoq* r, int slot) {
+    if (!r || slot < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
+    return r->slots[slot]->n_open;
 }
 
 int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {

@@ -190,13 +190,18 @@ class RdEvaluator:
         db = torch.as_tensor(self.rate_delta_map(slot, grid), device=dev).to(torch.float64)
         return move_cost_map(dd, db, n_samples, f.bitdepth, f.n_pixels, lmbda)
 
-    def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids: Optional[Sequence[int]] = None) -> List[List[StepReport]]:
+    def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids: Optional[Sequence[int]] = None,
+                rounds: int = 1) -> List[List[StepReport]]:
         """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True), then
         one RdoqStep over the evaluator's own device maps that moves latents of the candidates IN PLACE by +-1 where that lowers
         the cost by more than `min_gain` and the moves do not interact.  `grids`: the grids that may move (all by default).
         With every grid admitted a step of a real picture is usually ONE move: a candidate of the coarsest grids reaches the
         whole picture, is worth thousands of squared-error units and so beats and blocks everything else.  Pass the fine grids
         (for instance grids=(0, 1, 2)) for steps of hundreds of moves, and admit the coarse ones in a later call.
+        `rounds`: rounds of selection per step (RdoqStep.step; 1 .. 64, 8 is a sensible value): the maps of one evaluate() then
+        yield every move that a walk over the candidates in key order would take, not only the winners of the first contest,
+        a few times as many.  The advice about the coarse grids still holds: a coarse candidate with the BEST key still owns the
+        whole raster.  What changes is that a coarse candidate that LOSES no longer blocks the rest.
         Stops when no candidate moved or after `max_steps` steps; returns one list of StepReport per step (one per candidate:
         the candidate before the step, and what the step did).  After a step the cost of candidate s is before.cost + step.d_cost
         (its distortion part exactly, its rate part within the rate deltas' bound).
@@ -231,7 +236,7 @@ class RdEvaluator:
                 n_grids = int(self._jobs[s][0].n_grids)
                 self._rdoq.set_maps(s, [self._dd.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
                                     [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-            self._rdoq.step(kD, kR, [float(min_gain)] * n, masks, st)
+            self._rdoq.step(kD, kR, [float(min_gain)] * n, masks, st, rounds=rounds)
             self._rdoq.wait(st)
             results = [self._rdoq.result(s) for s in range(n)]
             reports.append([StepReport(b, r) for b, r in zip(before, results)])

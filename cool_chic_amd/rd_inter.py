@@ -237,13 +237,16 @@ class InterRdEvaluator:
         return move_cost_map(dd, db, n_samples, f.source.bitdepth, f.source.n_pixels, lmbda)
 
     def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids=None,
-                roles: Sequence[Union[str, int]] = ROLES) -> List[List[InterStepReport]]:
+                roles: Sequence[Union[str, int]] = ROLES, rounds: int = 1) -> List[List[InterStepReport]]:
         """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True) for the moving role, then
         one RdoqStep that moves latents of THAT role's cool-chic of every frame in place by +-1 where the cost falls by more than
         `min_gain` and the moves do not interact; the other role's grid mask is 0.  The moving role alternates over `roles`; the
         descent stops after `max_steps` steps or when a full cycle over `roles` moved nothing.  `grids`: the grids that may move
         (all by default), or a dict of them per role.  Returns one list of InterStepReport (one per frame) per step.  After a step
-        the frame's squared error is before + step.d_sse exactly; its bits within the rate deltas' bound of step.d_bits."""
+        the frame's squared error is before + step.d_sse exactly; its bits within the rate deltas' bound of step.d_bits.
+        `rounds`: rounds of selection per step (RdoqStep.step; 1 .. 64, 8 is a sensible value), as in RdEvaluator.descend: more
+        moves from the maps of one evaluate().  A coarse candidate with the best key still owns the whole raster, so the advice
+        to start with the fine grids holds; a coarse candidate that loses no longer blocks the rest."""
         n = len(self._frames)
         order = [_role(r) for r in roles]
         if not order:
@@ -285,7 +288,7 @@ class InterRdEvaluator:
                 masks.append(sum(1 << g for g in (range(n_grids) if g_ok is None else g_ok) if 0 <= g < n_grids))
                 self._rdoq.set_maps(s, [self._dd[role].delta_map(s // 2, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
                                     [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-            self._rdoq.step(kD, kR, [float(min_gain)] * (2 * n), masks, st)
+            self._rdoq.step(kD, kR, [float(min_gain)] * (2 * n), masks, st, rounds=rounds)
             self._rdoq.wait(st)
             results = [self._rdoq.result(2 * k + role) for k in range(n)]
             reports.append([InterStepReport(b, ROLES[role], r) for b, r in zip(before, results)])

@@ -2,7 +2,11 @@
 that provably do not interact and apply them to the device latents in place (wraps the ccd_rdoq_* C ABI).
 
 After a step the frame's squared error has changed by exactly `d_sse` and the model bits by `d_bits` (within the rate deltas'
-own bound): the sums of the chosen entries of the two maps."""
+own bound): the sums of the chosen entries of the two maps.
+
+A step may run several rounds (`rounds`): a candidate that lost a cell of its box to a candidate that itself lost elsewhere
+competes again once the winners' neighbourhoods are out of the way.  The selected set stays pairwise independent and grows
+towards the set a walk over the candidates in key order would take; `StepResult.n_open == 0` says it has got there."""
 import ctypes as C
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -17,11 +21,17 @@ class StepResult(NamedTuple):
     d_sse: int      # exact: the sum of the chosen dD
     d_bits: float   # the sum of the chosen dBits
     d_cost: float   # kD * d_sse + kR * d_bits
+    n_open: int = 0  # candidates of the last round that were not selected; 0: the selected set is maximal
 
 
 def cell() -> int:
     """Luma samples per side of a cell of the claim raster (ccd_rdoq_cell)."""
     return int(lib().ccd_rdoq_cell())
+
+
+def max_rounds() -> int:
+    """The most rounds a step may run (ccd_rdoq_max_rounds)."""
+    return int(lib().ccd_rdoq_max_rounds())
 
 
 def influence_box(arch: CCHeader, frame_data_type: int, grid: int, y: int, x: int) -> Tuple[int, int, int, int]:
@@ -60,15 +70,17 @@ class RdoqStep(_Handle):
         check(lib().ccd_rdoq_set_maps(self._h, int(slot), ptr_array(dd_ptrs), ptr_array(dbits_ptrs)), "ccd_rdoq_set_maps")
         self._keep(owner)
 
-    def step(self, kD: Sequence[float], kR: Sequence[float], min_gain: Sequence[float], grid_mask: Sequence[int], stream: int = 0):
+    def step(self, kD: Sequence[float], kR: Sequence[float], min_gain: Sequence[float], grid_mask: Sequence[int], stream: int = 0,
+             rounds: int = 1):
         """Per-slot factors of the cost dD * kD + dBits * kR, the least gain of a candidate and the grids that may move (bit g).
-        Only enqueues."""
+        `rounds` (1 .. max_rounds()): after each round the winners' boxes are taken, the candidates that meet them are dropped and
+        the rest compete again (include/ccd.h: ccd_rdoq_step_rounds); 1 is the single selection.  Only enqueues."""
         n = len(self)
         if not (len(kD) == len(kR) == len(min_gain) == len(grid_mask) == n):
             raise ValueError(f"the handle holds {n} slots")
-        check(lib().ccd_rdoq_step(self._h, (C.c_double * n)(*[float(v) for v in kD]), (C.c_double * n)(*[float(v) for v in kR]),
-                                  (C.c_double * n)(*[float(v) for v in min_gain]), (C.c_uint64 * n)(*[int(v) for v in grid_mask]),
-                                  C.c_void_p(stream or None)), "ccd_rdoq_step")
+        check(lib().ccd_rdoq_step_rounds(self._h, (C.c_double * n)(*[float(v) for v in kD]), (C.c_double * n)(*[float(v) for v in kR]),
+                                         (C.c_double * n)(*[float(v) for v in min_gain]), (C.c_uint64 * n)(*[int(v) for v in grid_mask]),
+                                         int(rounds), C.c_void_p(stream or None)), "ccd_rdoq_step_rounds")
 
     def wait(self, stream: int = 0):
         check(lib().ccd_rdoq_wait(self._h, C.c_void_p(stream or None)), "ccd_rdoq_wait")
@@ -76,8 +88,9 @@ class RdoqStep(_Handle):
     def result(self, slot: int) -> StepResult:
         r = RdoqResult()
         check(lib().ccd_rdoq_slot_result(self._h, int(slot), C.byref(r)), "ccd_rdoq_slot_result")
+        n_open = check(lib().ccd_rdoq_slot_open(self._h, int(slot)), "ccd_rdoq_slot_open")
         return StepResult(int(r.n_candidates), int(r.n_moves), tuple(int(r.n_moves_grid[g]) for g in range(r.n_grids)), int(r.d_sse),
-                          float(r.d_bits), float(r.d_cost))
+                          float(r.d_bits), float(r.d_cost), int(n_open))
 
     def moves(self, slot: int, grid: int) -> _DevArray:
         """After step() + wait(): int8 [h][w] on the device, the move (-1, 0, +1) the step applied at every latent of the grid.

@@ -618,6 +618,17 @@ int ccd_dsens_passes(const ccd_dsens* d, int slot);
  * candidates whose boxes share a cell with its own, and the candidate with the slot's smallest key always is.  Selected latents
  * are stored as v + s.  Negative or non-finite kD, kR, min_gain, NULL arrays, a slot without maps and a step in flight are
  * CCD_ERR_ARG.  The call only enqueues; ccd_rdoq_wait synchronises.  One step may be in flight per handle.
+ * ccd_rdoq_step_rounds: the same step in max_rounds rounds (1 .. ccd_rdoq_max_rounds() = 64, else CCD_ERR_ARG before the handle or
+ * the device is looked at); ccd_rdoq_step is max_rounds = 1.  Every candidate starts OPEN and no cell is TAKEN.  In a round (a) an
+ * open candidate whose box holds a taken cell becomes BLOCKED for good and claims nothing, (b) the other open candidates compete
+ * as above, (c) the winners are SELECTED and applied, (d) the cells of their boxes become taken.  A candidate that lost a cell to
+ * a candidate that then lost elsewhere competes again in the next round, so the selected set grows from round to round towards
+ * the set a walk over the candidates in ascending key order would take (each candidate taken unless its box shares a cell with an
+ * earlier taken one), and equals it once a round selects nothing.  Whatever max_rounds, the selected set is pairwise independent,
+ * a function of the maps and max_rounds alone, and the result and the move map cover all rounds.
+ * ccd_rdoq_slot_open: the candidates that took part in the LAST round of the last finished step and were not selected.  0: the
+ * selected set is maximal - every candidate is selected or shares a cell with a selected one; > 0: another round might select
+ * more.  CCD_ERR_ARG as ccd_rdoq_slot_result.
  * ccd_rdoq_slot_result: what the last finished step did; d_bits is a float64 sum in an order that depends on the geometry only
  * (the same words on a second call), d_cost = kD * d_sse + kR * d_bits.  ccd_rdoq_slot_moves: device int8 [h][w], the step's
  * move (-1, 0, +1) at every latent, and h * w as the return value; valid until the next step / destroy.  Both CCD_ERR_ARG for a
@@ -632,14 +643,18 @@ typedef struct {
     double d_cost;
 } ccd_rdoq_result;
 int ccd_rdoq_cell(void);
+int ccd_rdoq_max_rounds(void);
 int ccd_rdoq_influence_box(const ccd_cc_header* arch, int frame_data_type, int grid, int y, int x, int32_t cells[4]);
 int ccd_rdoq_create(int device, ccd_rdoq** out);
 void ccd_rdoq_destroy(ccd_rdoq* r);
 int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, int8_t* const* latents);
 int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const float* const* dbits);
 int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream);
+int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, int max_rounds,
+                         void* stream);
 int ccd_rdoq_wait(ccd_rdoq* r, void* stream);
 int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out);
+int64_t ccd_rdoq_slot_open(const ccd_rdoq* r, int slot);
 int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr);
 
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):

@@ -10,7 +10,8 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
 
   --rdoq            instead of the above: one requantisation step (RdoqStep) next to the
                     evaluate(rate_deltas, distortion_deltas) that feeds it, candidates and moves per step for three grid
-                    masks, and for kodim14 the cost after 1, 2, 4, 8 steps of RdEvaluator.descend
+                    masks; the same step in 1, 2, 4, 8 and 64 rounds (candidates, moves, open candidates, time); and for kodim14
+                    the cost after 1, 2, 4, 8 steps of RdEvaluator.descend with rounds=1 and with rounds=8
 
   --inter           instead of the above: the distortion deltas of P / B frames (DistortionDeltas.add_inter, DESIGN.md section
                     4.15) - one P and one B frame of the `vid5` fixture and a 1080p B frame of synth.gop1080p, both roles: passes,
@@ -162,7 +163,8 @@ def measure_ddeltas(streams, runs, n_probe_slots):
 def measure_rdoq(streams, runs, lmbda, trajectory):
     """The streams' own latents with a seeded tenth of the positions moved by +-1, scored against the frames the own latents
     decode to: the time of evaluate(rate_deltas, distortion_deltas), of one step over its maps (latents restored before every
-    step, outside the timed region), candidates and moves for three masks, and the cost along a descent."""
+    step, outside the timed region), candidates and moves for three masks, the step in 1 .. 64 rounds, and the cost along a
+    descent with one round and with eight."""
     import numpy as np
 
     from cool_chic_amd import RdoqStep
@@ -211,31 +213,43 @@ def measure_rdoq(streams, runs, lmbda, trajectory):
                       [ev.rate_delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids[s])], owner=ev)
         kD.append(1.0 / (3.0 * sources[s].n_pixels * 255.0 * 255.0))
         kR.append(lmbda / sources[s].n_pixels)
-    for label, mask_of in (("all_grids", lambda k: (1 << k) - 1), ("grids_0_2", lambda k: 7), ("grid_0", lambda k: 1)):
-        masks = [mask_of(k) for k in n_grids]
+
+    def timed_step(masks, rounds):
         times = []
         for it in range(3 + runs):
             restore()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            step.step(kD, kR, [0.0] * n, masks, st)
+            step.step(kD, kR, [0.0] * n, masks, st, rounds=rounds)
             e1.record()
             step.wait(st)
             if it >= 3:
                 times.append(e0.elapsed_time(e1))
         results = [step.result(s) for s in range(n)]
-        res[label] = {"step_ms": round(statistics.median(times), 4), "candidates": sum(r.n_candidates for r in results),
-                      "moves": sum(r.n_moves for r in results), "d_cost_slot0": results[0].d_cost}
+        return {"step_ms": round(statistics.median(times), 4), "step_ms_min_max": [round(min(times), 4), round(max(times), 4)],
+                "candidates": sum(r.n_candidates for r in results), "moves": sum(r.n_moves for r in results),
+                "open": sum(r.n_open for r in results), "d_cost_slot0": results[0].d_cost}
+
+    all_masks = {"all_grids": [(1 << k) - 1 for k in n_grids], "grids_0_2": [7] * n, "grid_0": [1] * n}
+    for label, masks in all_masks.items():
+        res[label] = timed_step(masks, 1)
+    for label in ("all_grids", "grids_0_2"):
+        res[label + "_rounds"] = {str(r): timed_step(all_masks[label], r) for r in (1, 2, 4, 8, 64)}
     step.close()
     if trajectory:
-        restore()
-        torch.cuda.synchronize()
-        reports = ev.descend(lmbda, max_steps=8, grids=(0, 1, 2))  # coarse candidates own the raster: one move per step
-        costs = [rep[0].before.cost for rep in reports] + [ev.evaluate(lmbda)[0].cost]
-        res["descent_grids_0_2"] = {"cost_after_steps": {str(k): costs[k] for k in (0, 1, 2, 4, 8) if k < len(costs)},
-                          "moves_per_step": [rep[0].step.n_moves for rep in reports],
-                          "candidates_per_step": [rep[0].step.n_candidates for rep in reports],
-                          "bits": [reports[0][0].before.bits, ev.evaluate(lmbda)[0].bits]}
+        for rounds in (1, 8):
+            restore()
+            torch.cuda.synchronize()
+            # coarse candidates own the raster: with every grid admitted a step is usually one move
+            reports = ev.descend(lmbda, max_steps=8, grids=(0, 1, 2), rounds=rounds)
+            last = ev.evaluate(lmbda)[0]
+            costs = [rep[0].before.cost for rep in reports] + [last.cost]
+            res["descent_grids_0_2" + ("" if rounds == 1 else f"_rounds{rounds}")] = {
+                "cost_after_steps": {str(k): costs[k] for k in (0, 1, 2, 4, 8) if k < len(costs)},
+                "moves_per_step": [rep[0].step.n_moves for rep in reports],
+                "candidates_per_step": [rep[0].step.n_candidates for rep in reports],
+                "open_per_step": [rep[0].step.n_open for rep in reports],
+                "bits": [reports[0][0].before.bits, last.bits]}
     ev.close()
     dec.close()
     return res

@@ -2,11 +2,12 @@
 DESIGN.md section 4.14): every step moves latents by +-1 where the exact change of the cost is negative and the moves do not
 interact.  The networks stay as they are; the new latents are range-coded by the device writer.
 
-    python tools/requantise.py in.cool source.png out.cool --lmbda 1e-3 [--max-steps 16] [--grids 0,1,2] [--min-gain 0]
+    python tools/requantise.py in.cool source.png out.cool --lmbda 1e-3 [--max-steps 16] [--grids 0,1,2] [--min-gain 0] [--rounds 8]
 
 Prints bits, PSNR and cost before and after, and the moves of every step.  A candidate of the coarsest grids reaches the
 whole picture and blocks every weaker one, so with all grids admitted (the default) a step is usually a single move: run with
---grids 0,1,2 first, then once more on the result without it."""
+--grids 0,1,2 first, then once more on the result without it.  --rounds 8 lets the candidates that lost a contest compete again
+within the step (a few times the moves per evaluation); a coarse candidate with the best key still owns the raster."""
 import argparse
 import sys
 
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--min-gain", type=float, default=0.0)
     ap.add_argument("--grids", default="", help="comma-separated grids that may move (default: all; with the coarsest grids admitted a step is usually one "
                     "move, because their candidates reach the whole picture and block the rest: start with 0,1,2)")
+    ap.add_argument("--rounds", type=int, default=1, help="rounds of selection per step (1 .. 64; 8 is a sensible value): losers of a round whose "
+                    "winners they do not meet compete again, for more moves from the maps of one evaluation")
     a = ap.parse_args()
     with open(a.stream, "rb") as f:
         bs = f.read()
@@ -58,13 +61,13 @@ def main():
     ev = RdEvaluator(0)
     ev.add(arch, nn, ptrs, source, owner=latents)
     grids = [int(g) for g in a.grids.split(",") if g != ""] or None
-    reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids)
+    reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
     after = ev.evaluate(a.lmbda)[0]
     before = reports[0][0].before if reports else after
     for k, rep in enumerate(reports):
         st = rep[0].step
         print(f"step {k}: {st.n_candidates} candidates, {st.n_moves} moves {list(st.n_moves_grid)}, d_sse {st.d_sse}, d_bits {st.d_bits:.3f}, "
-              f"d_cost {st.d_cost:.6g}")
+              f"d_cost {st.d_cost:.6g}" + (f", {st.n_open} still open" if a.rounds > 1 else ""))
     for label, c in (("before", before), ("after", after)):
         print(f"{label}: {c.bits:.1f} bits, PSNR {c.quality.psnr_db:.4f} dB, cost {c.cost:.9g}")
 

@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--max-steps", type=int, default=16, help="per frame")
     ap.add_argument("--min-gain", type=float, default=0.0)
     ap.add_argument("--grids", default="", help="comma-separated grids that may move, in every cool-chic (default: all; see tools/requantise.py)")
+    ap.add_argument("--rounds", type=int, default=1, help="rounds of selection per step (1 .. 64; 8 is a sensible value; see tools/requantise.py)")
     a = ap.parse_args()
     grids = [int(g) for g in a.grids.split(",") if g != ""] or None
     with open(a.stream, "rb") as f:
@@ -68,7 +69,7 @@ def main():
             ev = RdEvaluator(0)
             arch, nn, lat = cool_chics[k][0]
             ev.add(arch, nn, ptrs[0], sources[k], owner=lat)
-            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids)
+            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
             after = ev.evaluate(a.lmbda)[0]
             done[k] = [torch.as_tensor(ev._dec.plane_device(0, p), device="cuda").clone() for p in range(3)]
             moves = [(r[0].step.n_moves, "") for r in reports]
@@ -78,7 +79,7 @@ def main():
             (ra, rn, rl), (ma, mn, ml) = cool_chics[k]
             ev.add(frame_type, (ra, rn, ptrs[0]), (ma, mn, ptrs[1]), [done[r] for r in refs], fh.get_value("global_flow"),
                    fh.get_value("warp_filter_size"), sources[k], owner=(rl, ml))
-            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids)
+            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
             after = ev.evaluate(a.lmbda)[0]
             done[k] = [p.clone() for p in ev.planes(0)]
             moves = [(r[0].step.n_moves, " " + r[0].role) for r in reports]
