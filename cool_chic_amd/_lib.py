@@ -211,6 +211,7 @@ SIGNATURES = {
     "ccd_rdoq_destroy": (None, [C.c_void_p]),
     "ccd_rdoq_add": (C.c_int, [C.c_void_p, C.POINTER(CCHeader), C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_rdoq_set_maps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_link": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ccd_rdoq_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
                                 C.c_void_p]),
     "ccd_rdoq_max_rounds": (C.c_int, []),

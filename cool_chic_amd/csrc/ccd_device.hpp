@@ -183,7 +183,8 @@ constexpr int kRdoqMaxRounds = 64;       // rounds of one step at most (ccd_rdoq
 constexpr uint8_t kRdoqSelected = 4, kRdoqBlocked = 8;  // bits of a pick byte beside the candidate's 1 / 2
 // The influence box of a latent in cells of the claim raster, inclusive (ccd_rdoq_influence_box).
 struct RdoqBox { uint16_t top, left, bottom, right; };
-// One grid of one slot.  The latents of a slot are numbered uid = first + y * w + x over its grids.
+// One grid of one slot.  The latents of a slot are numbered uid = first + y * w + x over its grids; those of a linked pair
+// (ccd_rdoq_link) over the leader's grids, then the follower's.
 struct RdoqGrid {
     int8_t* lat;             // the caller's grid [h][w]: the only memory of the caller's a step writes
     const int64_t* dd;       // [2][h][w], nullptr: zeros
@@ -205,6 +206,8 @@ struct RdoqSlot {
     int32_t first_grid, n_grids; // its entries of the grid table
     uint32_t raster_units;       // 16-byte units of the raster block
     uint32_t taken_units;        // ... and of the taken block
+    int32_t partner;             // the other slot of its pair (ccd_rdoq_link), -1: none
+    int32_t owns_raster;         // 0 for a follower: raster and taken are its leader's, which settles and resets them
 };
 // What one workgroup of the reduce launch leaves for a chunk of kRdoqChunk latents of one grid.
 struct RdoqPartial { int64_t n_candidates, n_moves, d_sse; double d_bits; int64_t n_open; };

@@ -13,10 +13,15 @@
 #include "ccd_device.hpp"
 #include "ccd_format.hpp"
 
+// A failed call is reported by the return code alone: the thread's last HIP error is read once more, which resets it, so that
+// the caller's own runtime (PyTorch checks hipGetLastError after its launches) does not meet an error that was this library's.
 #define HIP_TRY(expr)                           \
     do {                                        \
         hipError_t e__ = (expr);                \
-        if (e__ != hipSuccess) return CCD_ERR_HIP; \
+        if (e__ != hipSuccess) {                \
+            (void)hipGetLastError();            \
+            return CCD_ERR_HIP;                 \
+        }                                       \
     } while (0)
 
 namespace ccd {

@@ -32,6 +32,16 @@
 // rasters with plain vector stores.  Launches are ordered by their stream: no access of one launch meets one of another.  The
 // first step finds what ccd_rdoq_add left: all ones and zeros.
 //
+// Groups.  The two slots of a linked pair (ccd_rdoq_link) share the leader's rasters: the follower's RdoqSlot carries the leader's
+// raster / taken pointers and its grids the pair-wide uid (the leader's latents first), so claim and select are the code above
+// with more candidates per word.  The smallest key still wins a cell whatever the order of the atomics: that never needed the
+// claimants to be of one slot.  The accesses per word per launch stay of one kind too: claim and select reach a shared word
+// from both slots, but with the same kind of access (atomics on claim words and loads of taken in claim, loads in select);
+// settle runs over the cells of the rasters' owners only, one lane per cell, and finds the owner of a claimed word in the
+// leader's grids or, from the follower's first uid on, in the follower's; in phase 1 of the reduce launch only the owner's
+// wave stores the rasters (RdoqSlot::owns_raster), so no word is written by two workgroups.  The follower's own raster block
+// stays as ccd_rdoq_add left it and is never read.
+//
 // Sums: integers in any order; dBits in float64 in an order that is a function of the geometry alone (a lane adds its latents
 // in ascending order, a fixed shuffle tree adds the lanes, chunks and grids are added in ascending order).  No float atomics.
 #include <hip/hip_runtime.h>
@@ -211,8 +221,10 @@ __global__ __launch_bounds__(64) void rdoq_select_kernel(const RdoqGrid* __restr
     step_body<true, kFirst>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
 }
 
-// Between two rounds: 64 cells of one slot, a lane each.  The low half of a claimed word is its owner's uid; the owner claimed
-// in this round, so a selected owner was selected in this round and owns every cell of its box.
+// Between two rounds: 64 cells of one raster, a lane each (a follower has no cell blocks: its leader's lanes settle the pair's
+// raster).  The low half of a claimed word is its owner's uid; the owner claimed in this round, so a selected owner was selected
+// in this round and owns every cell of its box.  In a pair the owner is a latent of either slot: the follower's uids begin where
+// the leader's end.
 __global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                          const uint32_t* __restrict__ cell_prefix, int n_slots) {
     const int k = entry_of(cell_prefix, n_slots, blockIdx.x);
@@ -222,9 +234,11 @@ __global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restr
     const unsigned long long key = S.raster[cell];
     if (key == ~0ull) return;  // nobody claimed the cell
     const uint32_t uid = static_cast<uint32_t>(key);
+    const RdoqSlot* T = &S;  // the slot of the uid
+    if (S.partner >= 0 && grids[slots[S.partner].first_grid].first <= uid) T = &slots[S.partner];
     int g = 0;  // the grid of the uid: first[] ascends over the slot's few grids
-    while (g + 1 < S.n_grids && grids[S.first_grid + g + 1].first <= uid) ++g;
-    const RdoqGrid& G = grids[S.first_grid + g];
+    while (g + 1 < T->n_grids && grids[T->first_grid + g + 1].first <= uid) ++g;
+    const RdoqGrid& G = grids[T->first_grid + g];
     const uint32_t i = uid - G.first;
     if (i < G.n && (G.pick[i] & kRdoqSelected)) S.taken[cell] = 1;
     S.raster[cell] = ~0ull;
@@ -301,7 +315,9 @@ __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restr
             R.d_cost = 0.0;  // the host's
             open[blockIdx.x] = total.n_open;
         }
-        // all ones and no taken cell for the next step's claim (the ordering argument is at the head of this file)
+        // all ones and no taken cell for the next step's claim (the ordering argument is at the head of this file); a pair's
+        // rasters are the leader's to store
+        if (!S.owns_raster) return;
         uint4* words = reinterpret_cast<uint4*>(S.raster);
         for (uint32_t t = lane; t < S.raster_units; t += 64) words[t] = make_uint4(~0u, ~0u, ~0u, ~0u);
         uint4* marks = reinterpret_cast<uint4*>(S.taken);

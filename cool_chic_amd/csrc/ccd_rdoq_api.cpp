@@ -125,6 +125,9 @@ struct RSlot {
     ccd_rdoq_result result;
     int64_t n_open = 0;                      // candidates of the last round that lost a cell
     bool covered = false;                    // by a finished step
+    int frame_data_type = 0;
+    uint32_t total = 0;                      // latents of all grids
+    int leader = -1, follower = -1;          // ccd_rdoq_link: the slot whose rasters this one claims in / the slot that claims in this one's
 };
 }  // namespace
 
@@ -186,6 +189,7 @@ int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, in
     if (rc < 0) return rc;
     const ccd_cc_header& h = s.geo.h;
     s.n_grids = h.n_grids;
+    s.frame_data_type = frame_data_type;
     uint64_t total = 0;
     for (int g = 0; g < h.n_grids; ++g) {
         if (!latents[g]) return CCD_ERR_ARG;
@@ -195,6 +199,7 @@ int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, in
         if (total > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
         s.n[g] = static_cast<uint32_t>(h.grid_h[g]) * static_cast<uint32_t>(h.grid_w[g]);
     }
+    s.total = static_cast<uint32_t>(total);
     // the boxes of every latent and the lists of those a wave walks, laid out as they go to the device
     std::vector<std::vector<RdoqBox>> boxes(h.n_grids);
     std::vector<std::vector<uint32_t>> big(h.n_grids);
@@ -252,6 +257,21 @@ int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const flo
     return CCD_OK;
 }
 
+int ccd_rdoq_link(ccd_rdoq* r, int slot, int leader) {
+    if (!r || slot < 0 || leader < 0 || slot == leader) return CCD_ERR_ARG;
+    const int n_slots = static_cast<int>(r->slots.size());
+    if (slot >= n_slots || leader >= n_slots || r->pending) return CCD_ERR_ARG;
+    RSlot& f = *r->slots[slot];
+    RSlot& l = *r->slots[leader];
+    if (f.leader >= 0 || f.follower >= 0 || l.leader >= 0 || l.follower >= 0) return CCD_ERR_ARG;  // pairs only
+    // congruent rasters: the same picture in the same cells, and boxes widened for the same planes
+    if (f.frame_data_type != l.frame_data_type || f.geo.h.img_size[0] != l.geo.h.img_size[0] || f.geo.h.img_size[1] != l.geo.h.img_size[1])
+        return CCD_ERR_VALUE;
+    f.leader = leader;
+    l.follower = slot;
+    return CCD_OK;
+}
+
 int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream) {
     return ccd_rdoq_step_rounds(r, kD, kR, min_gain, grid_mask, 1, stream);
 }
@@ -279,14 +299,19 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
         char* base = s.mem.as<char>();
         RdoqSlot& S = slots[k];
         std::memset(&S, 0, sizeof(S));
-        S.raster = reinterpret_cast<unsigned long long*>(base + s.raster_off);
-        S.taken = reinterpret_cast<uint8_t*>(base + s.taken_off);
+        // a follower claims in its leader's rasters, its uids after the leader's (both at most 2^31 - 1: 32 bits hold the pair)
+        const RSlot& owner = s.leader >= 0 ? *r->slots[s.leader] : s;
+        const uint32_t uid0 = s.leader >= 0 ? owner.total : 0;
+        S.raster = reinterpret_cast<unsigned long long*>(owner.mem.as<char>() + owner.raster_off);
+        S.taken = reinterpret_cast<uint8_t*>(owner.mem.as<char>() + owner.taken_off);
+        S.partner = s.leader >= 0 ? s.leader : s.follower;
+        S.owns_raster = s.leader < 0;
         S.cells_h = s.geo.cells_h; S.cells_w = s.geo.cells_w;
         S.kD = s.kD = kD[k]; S.kR = s.kR = kR[k]; S.min_gain = min_gain[k];
         S.grid_mask = grid_mask[k];
         S.first_grid = static_cast<int32_t>(grids.size()); S.n_grids = s.n_grids;
         S.raster_units = s.raster_units; S.taken_units = s.taken_units;
-        cell_blocks += (static_cast<uint64_t>(s.geo.cells_h) * s.geo.cells_w + 63) / 64;  // settle: a lane per cell
+        if (S.owns_raster) cell_blocks += (static_cast<uint64_t>(s.geo.cells_h) * s.geo.cells_w + 63) / 64;  // settle: a lane per cell
         if (cell_blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
         cell_prefix[k + 1] = static_cast<uint32_t>(cell_blocks);
         for (int g = 0; g < s.n_grids; ++g) {
@@ -297,7 +322,7 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
             G.pick = reinterpret_cast<uint8_t*>(base + s.pick_off[g]);
             G.box = reinterpret_cast<const RdoqBox*>(base + s.box_off[g]);
             G.big = reinterpret_cast<const uint32_t*>(base + s.big_off[g]);
-            G.n = s.n[g]; G.first = s.first[g]; G.slot = k; G.grid = g;
+            G.n = s.n[g]; G.first = uid0 + s.first[g]; G.slot = k; G.grid = g;
             lanes += (G.n + 63) / 64; bigs += s.n_big[g]; chunks += (G.n + kRdoqChunk - 1) / kRdoqChunk;
             if (lanes + bigs > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
             const size_t e = grids.size();

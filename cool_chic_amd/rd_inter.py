@@ -9,8 +9,14 @@ header bytes of BOTH cool-chics summed.
 
 The distortion deltas of a cool-chic are taken with the other one's output held fixed (DistortionDeltas.add_inter): the
 reconstruction is pointwise, so the footprints, lattice passes and influence boxes of an intra cool-chic hold for either.  A
-descent step therefore moves ONE role; inside one cool-chic the influence boxes make the chosen moves independent, and after the
-step the frame's squared error has changed by exactly the sum of the chosen entries."""
+descent step of one role moves that cool-chic alone; inside one cool-chic the influence boxes make the chosen moves independent,
+and after the step the frame's squared error has changed by exactly the sum of the chosen entries.
+
+A JOINT step (descend(joint=True)) moves both.  A sample of the frame reads both cool-chics' outputs at its own position only, and
+both have the frame's size and format, so their influence boxes lie in one raster of cells: a residue latent and a motion latent
+whose boxes share no cell change disjoint sets of samples, each map was taken with the partner as it is outside its own box, and
+the frame's squared error changes by the sum of the two entries.  The two rate models read nothing of each other, so the bits add.
+RdoqStep.link lets the two slots of a frame compete for the cells of one raster."""
 import ctypes as C
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -52,6 +58,13 @@ class InterStepReport(NamedTuple):
     step: StepResult
 
 
+class InterJointStepReport(NamedTuple):
+    """One frame in one JOINT step of InterRdEvaluator.descend(joint=True): the frame before the step and what the step did in
+    each cool-chic, (residue, motion)."""
+    before: InterCandidate
+    steps: Tuple[StepResult, StepResult]
+
+
 class _Frame(NamedTuple):
     frame_type: int                    # 1 P, 2 B
     archs: Tuple[CCHeader, CCHeader]
@@ -78,6 +91,7 @@ class InterRdEvaluator:
         self._dd: Dict[int, DistortionDeltas] = {}   # per role: a step reads the moving role's maps only
         self._dd_frames: Dict[int, int] = {0: 0, 1: 0}
         self._rdoq: Optional[RdoqStep] = None
+        self._n_linked = 0                           # frames whose motion slot is linked to the residue slot (descend(joint=True))
         self._frames: List[_Frame] = []
         self._owners = []
 
@@ -85,6 +99,7 @@ class InterRdEvaluator:
         if self._rdoq is not None:
             self._rdoq.close()
             self._rdoq = None
+            self._n_linked = 0
         for d in self._dd.values():
             d.close()
         self._dd = {}
@@ -237,7 +252,8 @@ class InterRdEvaluator:
         return move_cost_map(dd, db, n_samples, f.source.bitdepth, f.source.n_pixels, lmbda)
 
     def descend(self, lmbda: float, max_steps: int, min_gain: float = 0.0, grids=None,
-                roles: Sequence[Union[str, int]] = ROLES, rounds: int = 1) -> List[List[InterStepReport]]:
+                roles: Sequence[Union[str, int]] = ROLES, rounds: int = 1,
+                joint: bool = False) -> List[List[Union[InterStepReport, InterJointStepReport]]]:
         """Requantisation by descent.  Per step: evaluate(lmbda, rate_deltas=True, distortion_deltas=True) for the moving role, then
         one RdoqStep that moves latents of THAT role's cool-chic of every frame in place by +-1 where the cost falls by more than
         `min_gain` and the moves do not interact; the other role's grid mask is 0.  The moving role alternates over `roles`; the
@@ -246,11 +262,20 @@ class InterRdEvaluator:
         the frame's squared error is before + step.d_sse exactly; its bits within the rate deltas' bound of step.d_bits.
         `rounds`: rounds of selection per step (RdoqStep.step; 1 .. 64, 8 is a sensible value), as in RdEvaluator.descend: more
         moves from the maps of one evaluate().  A coarse candidate with the best key still owns the whole raster, so the advice
-        to start with the fine grids holds; a coarse candidate that loses no longer blocks the rest."""
+        to start with the fine grids holds; a coarse candidate that loses no longer blocks the rest.
+        `joint`: every step moves BOTH roles.  The motion slot of every frame is linked to its residue slot (RdoqStep.link, once),
+        a step is evaluate(lmbda, rate_deltas=True, distortion_deltas=True) for both roles and one RdoqStep whose selection is
+        pairwise independent across the two cool-chics of a frame, and the descent stops after `max_steps` steps or after a step
+        that moved nothing.  Returns one list of InterJointStepReport per step; the frame's squared error after a step is before +
+        steps[0].d_sse + steps[1].d_sse exactly.  `roles` must name both roles.  The evaluator keeps one RdoqStep, and the links
+        stay: a later alternating descent on this evaluator works as before, because the frozen role's mask is 0 and a slot that
+        offers no candidate leaves its partner's step what it would be unlinked."""
         n = len(self._frames)
         order = [_role(r) for r in roles]
         if not order:
             raise ValueError("no role may move")
+        if joint and set(order) != {0, 1}:
+            raise ValueError("a joint descent moves both roles")
         if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
             raise ValueError("lmbda and min_gain must be finite and not negative")
         if n == 0:
@@ -272,6 +297,8 @@ class InterRdEvaluator:
             d, r = move_scales(sum(int(t.numel()) for t in f.src), f.source.bitdepth, f.source.n_pixels, lmbda)
             kD.append(d)
             kR.append(r)
+        if joint:
+            return self._descend_joint(lmbda, int(max_steps), float(min_gain), grids_of, kD, kR, rounds, st)
         reports: List[List[InterStepReport]] = []
         idle = 0
         for step in range(int(max_steps)):
@@ -294,6 +321,29 @@ class InterRdEvaluator:
             reports.append([InterStepReport(b, ROLES[role], r) for b, r in zip(before, results)])
             idle = 0 if any(r.n_moves for r in results) else idle + 1
             if idle >= len(order):
+                break
+        return reports
+
+    def _descend_joint(self, lmbda, max_steps, min_gain, grids_of, kD, kR, rounds, st) -> List[List[InterJointStepReport]]:
+        n = len(self._frames)
+        for k in range(self._n_linked, n):
+            self._rdoq.link(2 * k + 1, 2 * k)
+        self._n_linked = n
+        reports: List[List[InterJointStepReport]] = []
+        for _ in range(max_steps):
+            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=ROLES)
+            masks = []
+            for s in range(2 * n):
+                n_grids = int(self._frames[s // 2].archs[s % 2].n_grids)
+                g_ok = grids_of(s % 2)
+                masks.append(sum(1 << g for g in (range(n_grids) if g_ok is None else g_ok) if 0 <= g < n_grids))
+                self._rdoq.set_maps(s, [self._dd[s % 2].delta_map(s // 2, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
+                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
+            self._rdoq.step(kD, kR, [min_gain] * (2 * n), masks, st, rounds=rounds)
+            self._rdoq.wait(st)
+            results = [(self._rdoq.result(2 * k), self._rdoq.result(2 * k + 1)) for k in range(n)]
+            reports.append([InterJointStepReport(b, r) for b, r in zip(before, results)])
+            if not any(r.n_moves for pair in results for r in pair):
                 break
         return reports
 

@@ -70,6 +70,13 @@ class RdoqStep(_Handle):
         check(lib().ccd_rdoq_set_maps(self._h, int(slot), ptr_array(dd_ptrs), ptr_array(dbits_ptrs)), "ccd_rdoq_set_maps")
         self._keep(owner)
 
+    def link(self, slot: int, leader: int):
+        """`slot` joins the claim raster of `leader`: from the next step on the candidates of both compete as one population, so
+        the moves a step selects are pairwise independent across both slots (include/ccd.h: ccd_rdoq_link).  For two cool-chics
+        that decode into one frame of the same size and sample format.  On a tie of the costs the leader's candidate wins.  Results,
+        move maps and masks stay per slot; a slot whose mask is 0 leaves its partner stepping as if unlinked.  There is no unlink."""
+        check(lib().ccd_rdoq_link(self._h, int(slot), int(leader)), "ccd_rdoq_link")
+
     def step(self, kD: Sequence[float], kR: Sequence[float], min_gain: Sequence[float], grid_mask: Sequence[int], stream: int = 0,
              rounds: int = 1):
         """Per-slot factors of the cost dD * kD + dBits * kR, the least gain of a candidate and the grids that may move (bit g).

@@ -629,6 +629,21 @@ int ccd_dsens_passes(const ccd_dsens* d, int slot);
  * ccd_rdoq_slot_open: the candidates that took part in the LAST round of the last finished step and were not selected.  0: the
  * selected set is maximal - every candidate is selected or shares a cell with a selected one; > 0: another round might select
  * more.  CCD_ERR_ARG as ccd_rdoq_slot_result.
+ * ccd_rdoq_link: `slot` joins the claim raster of `leader`; from then on the two slots are a GROUP and every later step lets
+ * their candidates compete as one population (two cool-chics that decode into one frame: the residue and the motion cool-chic of
+ * a P / B frame, whose reconstruction is pointwise).  The key of a group is (cost as float32, group-wide index): the leader's
+ * latents keep first[g] + y w + x, the follower's get total(leader) + first[g] + y w + x, so the leader's candidate wins a tie of
+ * the costs (a slot holds at most 2^31 - 1 latents: 32 bits hold both).  The rule of ccd_rdoq_step / ccd_rdoq_step_rounds holds
+ * with "slot" read as "group": a candidate is selected when it has the smallest key of all candidates of the group whose boxes
+ * share a cell with its own, the candidate with the group's smallest key always is, the cells taken in a round block the open
+ * candidates of either slot in the later rounds, and the fixed point is the walk over the group's candidates in ascending key
+ * order.  Costs, admission (kD, kR, min_gain, grid_mask), results, move maps and ccd_rdoq_slot_open stay per slot; a slot whose
+ * grid_mask is 0 offers nothing, and its partner then steps as if it were not linked.  CCD_ERR_ARG before the handle is looked
+ * at: a NULL r, a negative index, slot == leader; CCD_ERR_ARG also for an index past the slots, a step in flight, a slot or
+ * leader that already belongs to a group (pairs only; a follower cannot lead); CCD_ERR_VALUE when the two slots differ in
+ * frame_data_type or img_size (their rasters would not be congruent).  A refused link leaves the handle as it was.  Allowed
+ * before the first step and between steps; there is no unlink.  Linked pairs and plain slots may share a handle, and a slot
+ * nobody linked steps exactly as without this call.
  * ccd_rdoq_slot_result: what the last finished step did; d_bits is a float64 sum in an order that depends on the geometry only
  * (the same words on a second call), d_cost = kD * d_sse + kR * d_bits.  ccd_rdoq_slot_moves: device int8 [h][w], the step's
  * move (-1, 0, +1) at every latent, and h * w as the return value; valid until the next step / destroy.  Both CCD_ERR_ARG for a
@@ -649,6 +664,7 @@ int ccd_rdoq_create(int device, ccd_rdoq** out);
 void ccd_rdoq_destroy(ccd_rdoq* r);
 int ccd_rdoq_add(ccd_rdoq* r, const ccd_cc_header* arch, int frame_data_type, int8_t* const* latents);
 int ccd_rdoq_set_maps(ccd_rdoq* r, int slot, const int64_t* const* dd, const float* const* dbits);
+int ccd_rdoq_link(ccd_rdoq* r, int slot, int leader);
 int ccd_rdoq_step(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, void* stream);
 int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const double* min_gain, const uint64_t* grid_mask, int max_rounds,
                          void* stream);

@@ -18,6 +18,11 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     run + wait, the time per round split into float path, probe reconstruction and squared-error split (each
                     stage run alone through the library's measurement hook), next to K plain ccd_inter_reconstruct calls on the same frame
 
+  --inter --joint   instead of the above: the requantisation descent of the same P / B frames (InterRdEvaluator.descend, DESIGN.md
+                    section 4.15) run to its fixed point both ways, alternating the roles and with joint steps, from the same
+                    latents (the stream's own with a seeded tenth moved by +-1, scored against the frame the own latents decode
+                    to): evaluate() calls, distortion-delta runs, steps, moves, final D + lambda R and wall time of each way
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -337,6 +342,76 @@ def measure_inter(stream_bytes, coding_index, runs, n_probe_slots):
     return res
 
 
+def measure_inter_descent(stream_bytes, coding_index, runs, lmbda, rounds, grids, max_steps):
+    """InterRdEvaluator.descend on one P / B frame, alternating and joint, each from the same perturbed latents on a fresh
+    evaluator: one unmeasured descent, then `runs` timed ones (host wall time around descend(), the device idle before and
+    after)."""
+    import os
+    import tempfile
+    import time
+
+    import numpy as np
+
+    from cool_chic_amd import InterRdEvaluator
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    for k in range(coding_index + 1):
+        fh, ccs, rest = _split_frame(rest)
+    frame_type = fh.get_value("frame_type")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    refs = [frames[str(int(r))] for r in structure[coding_index]["index_references"]][:"IPB".index(frame_type)]
+    source = frames[str(int(structure[coding_index]["display_order"]))]
+    dec = DecodeBatch(0)
+    for ch, nn, lat in ccs:
+        dec.add(ch.raw, nn, lat, 0, 0)
+    dec.run(); dec.wait()
+    rng = np.random.default_rng(14)
+    start = []
+    for s in range(2):
+        row = []
+        for g in range(dec.header(s).n_grids):
+            a = dec.latent(s, g).astype(np.int64)
+            a = a + np.where(rng.random(a.shape) < 0.1, rng.choice([-1, 1], size=a.shape), 0)
+            row.append(torch.from_numpy(np.clip(a, -64, 63).astype(np.int8)).cuda())
+        start.append(row)
+    res = {"frame": frame_type, "size": [int(v) for v in source.img_size], "lmbda": lmbda, "rounds": rounds, "grids": grids, "max_steps": max_steps}
+    for joint in (False, True):
+        walls, r = [], {}
+        for it in range(1 + runs):
+            work = [[t.clone() for t in row] for row in start]
+            ev = InterRdEvaluator(0)
+            ev.add(frame_type, *[(dec.header(s), dec.network_bytes(s), [t.data_ptr() for t in work[s]]) for s in range(2)], refs,
+                   fh.get_value("global_flow"), fh.get_value("warp_filter_size"), source, owner=work)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            reports = ev.descend(lmbda, max_steps, grids=grids, rounds=rounds, joint=joint)
+            torch.cuda.synchronize()
+            if it > 0:
+                walls.append((time.perf_counter() - t0) * 1e3)
+            last = ev.evaluate(lmbda)[0]
+            per_step = [sum(s.n_moves for s in rep[0].steps) if joint else rep[0].step.n_moves for rep in reports]
+            idle = 1 if joint else 2
+            now = {"evaluate_calls": len(reports), "dsens_runs": len(reports) * (2 if joint else 1), "steps": len(reports),
+                   "moves": sum(per_step), "cost_before": reports[0][0].before.cost, "cost_after": last.cost,
+                   "at_fixed_point": len(per_step) >= idle and not any(per_step[-idle:])}
+            assert not r or now == r, "a descent is a function of its inputs"
+            r = now
+            ev.close()
+        r["wall_ms"] = round(statistics.median(walls), 2)
+        r["wall_ms_min_max"] = [round(min(walls), 2), round(max(walls), 2)]
+        res["joint" if joint else "alternating"] = r
+    dec.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
@@ -348,7 +423,22 @@ def main():
     ap.add_argument("--sets", default="kodim14,kodak24", help="with --rdoq: which of the two sets to measure")
     ap.add_argument("--inter", action="store_true", help="time the distortion deltas of P / B frames instead")
     ap.add_argument("--inter-sets", default="vid5,1080p", help="with --inter: which of the two sets to measure")
+    ap.add_argument("--joint", action="store_true", help="with --inter: the descent of the frames, alternating and joint, instead")
+    ap.add_argument("--rounds", type=int, default=8, help="with --inter --joint: rounds of selection per step")
+    ap.add_argument("--grids", default="0,1,2", help="with --inter --joint: the grids that may move, in both cool-chics")
+    ap.add_argument("--max-steps", type=int, default=400, help="with --inter --joint: steps of a descent at most")
     a = ap.parse_args()
+    if a.inter and a.joint:
+        line = {"tool": "rd_bench --inter --joint", "runs": a.runs}
+        args = (a.runs, a.lmbda, a.rounds, [int(g) for g in a.grids.split(",") if g != ""], a.max_steps)
+        if "vid5" in a.inter_sets.split(","):
+            vid5 = synth._golden("vid5")[0]
+            line["vid5_P"] = measure_inter_descent(vid5, 1, *args)
+            line["vid5_B"] = measure_inter_descent(vid5, 3, *args)
+        if "1080p" in a.inter_sets.split(","):
+            line["gop1080p_B"] = measure_inter_descent(synth.gop1080p(2)[0], 2, *args)
+        print(json.dumps(line))
+        return
     if a.inter:
         line = {"tool": "rd_bench --inter", "runs": a.runs}
         if "vid5" in a.inter_sets.split(","):

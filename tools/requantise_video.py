@@ -3,7 +3,7 @@
 frames through InterRdEvaluator.descend with the planes of the already REQUANTISED frames as their references.  The networks and
 every header stay as they are; the new latents of each cool-chic are range-coded by the device writer.
 
-    python tools/requantise_video.py in.cool source.yuv out.cool --lmbda 1e-3 [--max-steps 16] [--grids 0,1,2] [--min-gain 0]
+    python tools/requantise_video.py in.cool source.yuv out.cool --lmbda 1e-3 [--max-steps 16] [--grids 0,1,2] [--min-gain 0] [--joint]
 
 Prints bits, PSNR and cost of every frame before and after ("before": the stream's latents against the references as they are now,
 requantised), writes the stream, decodes it back with decode_video and asserts that every frame's planes are those the last
@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--min-gain", type=float, default=0.0)
     ap.add_argument("--grids", default="", help="comma-separated grids that may move, in every cool-chic (default: all; see tools/requantise.py)")
     ap.add_argument("--rounds", type=int, default=1, help="rounds of selection per step (1 .. 64; 8 is a sensible value; see tools/requantise.py)")
+    ap.add_argument("--joint", action="store_true", help="P / B frames: every step moves both cool-chics (InterRdEvaluator.descend(joint=True))")
     a = ap.parse_args()
     grids = [int(g) for g in a.grids.split(",") if g != ""] or None
     with open(a.stream, "rb") as f:
@@ -79,10 +80,13 @@ def main():
             (ra, rn, rl), (ma, mn, ml) = cool_chics[k]
             ev.add(frame_type, (ra, rn, ptrs[0]), (ma, mn, ptrs[1]), [done[r] for r in refs], fh.get_value("global_flow"),
                    fh.get_value("warp_filter_size"), sources[k], owner=(rl, ml))
-            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
+            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds, joint=a.joint)
             after = ev.evaluate(a.lmbda)[0]
             done[k] = [p.clone() for p in ev.planes(0)]
-            moves = [(r[0].step.n_moves, " " + r[0].role) for r in reports]
+            if a.joint:
+                moves = [(f"{r[0].steps[0].n_moves} + {r[0].steps[1].n_moves}", " residue + motion") for r in reports]
+            else:
+                moves = [(r[0].step.n_moves, " " + r[0].role) for r in reports]
         before = reports[0][0].before if reports else after
         print(f"frame {display[k]} ({frame_type}): steps " + ", ".join(f"{n}{role}" for n, role in moves))
         for label, c in (("before", before), ("after", after)):
