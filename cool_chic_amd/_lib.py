@@ -94,6 +94,11 @@ class DsensInter(C.Structure):
                 ("global_flow", C.c_int32 * 4), ("warp_filter_size", C.c_int32)]
 
 
+class DsensDependent(C.Structure):
+    _fields_ = [("frame_type", C.c_int32), ("which", C.c_int32), ("residue", C.c_void_p), ("motion", C.c_void_p),
+                ("other_ref", C.c_void_p * 3), ("src", C.c_void_p * 3), ("global_flow", C.c_int32 * 4), ("warp_filter_size", C.c_int32)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -205,6 +210,13 @@ SIGNATURES = {
     "ccd_dsens_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_dsens_slot_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_dsens_passes": (C.c_int, [C.c_void_p, C.c_int]),
+    "ccd_dsens_add_dependent": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DsensDependent)]),
+    "ccd_dsens_slot_dep_map": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_dsens_slot_dep_conflicts": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "ccd_latent_probe_stride_margin": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.c_int, C.c_int]),
+    "ccd_debug_lattice_stride": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    "ccd_debug_lattice_hit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ccd_rdoq_cell": (C.c_int, []),
     "ccd_rdoq_influence_box": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "ccd_rdoq_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/ccd.h"
+#include "ccd_lattice.hpp"
 
 namespace ccd {
 
@@ -171,6 +172,31 @@ struct DsensInterJob {
     int32_t wide;            // samples are u16
     int32_t tiles_x;         // workgroups per row of workgroups
     float maxv;              // 2^bitdepth - 1
+};
+// One (candidate, dependent, probe slot) of a round as dsens_dep_kernel sees it (ccd_inter.hip).  `recon` is the
+// DEPENDENT frame as dsens_inter_kernel would reconstruct it (mode 2) with the candidate's probe planes, as f32, in place of
+// reference `which`; recon.plane are the dependent's BASE planes, which are only read here.  A unit whose windows into the
+// reference touch the region of exactly one member of the pass's lattice adds its squared-error change to that entry of `acc`;
+// one that touches several sets their bytes of `flag`.
+struct DsensDepJob {
+    DsensInterJob recon;
+    const void* src[3];        // the dependent's source planes
+    unsigned long long* acc;   // [2][h][w] of the grid: the dependent map while it is summed (two's complement)
+    uint8_t* flag;             // [2][h][w]: 1 = a unit saw this entry together with another
+    int32_t which;             // the reference of the dependent that is the candidate's frame
+    int32_t h, w;              // of the grid
+    int32_t move;              // -1 / +1
+    int32_t stride, py, px;    // the pass's lattice
+    LatticeAxis ay, ax;        // rows, columns
+};
+// One grid of a candidate with dependents as dsens_dep_final_kernel sees it (ccd_dsens.hip): entry e of [2][h][w] becomes INT64_MIN
+// where the move leaves the alphabet or the entry is flagged, and the flagged legal entries are counted.
+struct DsensDepGrid {
+    const int8_t* lat;
+    int64_t* map;
+    const uint8_t* flag;
+    unsigned long long* conflicts;
+    uint32_t n;                // h * w
 };
 constexpr uint32_t kDsensChunk = 4096;   // bytes one 64-lane workgroup of dsens_apply_kernel writes
 constexpr int kDsensBandSamples = 4096;  // luma samples of a band, about

@@ -1,4 +1,4 @@
-// ccd_dsens.hip - the two integer kernels of the distortion deltas (gfx950; DESIGN.md 4.13, include/ccd.h ccd_dsens_*).
+// ccd_dsens.hip - the integer kernels of the distortion deltas (gfx950; DESIGN.md 4.13, include/ccd.h ccd_dsens_*).
 //
 // The planes of a moved latent come from the float path that exists (given-latent slots of a decode batch); what runs here
 // is what stands around a round of up to K such passes:
@@ -15,7 +15,9 @@
 //                       that covers the picture a hundred.
 //                       phase 1: a lane per probe adds its bands in band order and stores the entry, or INT64_MIN where the
 //                       move leaves the alphabet.
-// Every sum is an integer sum: any order gives the same bits.  No atomics, no waits; plain vector stores.
+//   dsens_dep_final_kernel  the dependent maps of a run: sentinels over the sums dsens_dep_kernel (ccd_inter.hip) left,
+//                       and the count of flagged entries per grid - the one integer atomic add of this file.
+// Every sum is an integer sum: any order gives the same bits.  No waits; plain vector stores.
 #include <hip/hip_runtime.h>
 
 #include "ccd_kernels.hpp"
@@ -134,7 +136,32 @@ __global__ __launch_bounds__(64) void dsens_sse_kernel(const DsensPass* __restri
     acc = wave_sum_i64(acc);
     if (lane == 0) slab[u] = acc;
 }
+
+// The dependent maps of a run, behind its last round: entry e of a grid's [2][h][w] is, in this order, INT64_MIN
+// where the move leaves the alphabet, INT64_MIN where dsens_dep_kernel flagged a conflict, else the sum it accumulated.  A
+// workgroup is 256 entries of one grid; the flagged legal entries are counted per grid (an integer sum: one atomic per wave).
+__global__ __launch_bounds__(256) void dsens_dep_final_kernel(const DsensDepGrid* __restrict__ grids, const uint32_t* __restrict__ prefix, int n_grids) {
+    const uint32_t blk = blockIdx.x;
+    const int g = entry_of(prefix, n_grids, blk);
+    const DsensDepGrid G = grids[g];
+    const uint32_t e = (blk - prefix[g]) * 256u + threadIdx.x;
+    bool counted = false;
+    if (e < 2u * G.n) {
+        const int v = G.lat[e < G.n ? e : e - G.n], move = e < G.n ? -1 : 1;
+        const bool legal = in_alphabet(v + move), flagged = G.flag[e] != 0;
+        if (!legal || flagged) G.map[e] = INT64_MIN;
+        counted = legal && flagged;
+    }
+    const unsigned long long mask = __ballot(counted);
+    if ((threadIdx.x & 63) == 0 && mask) atomicAdd(G.conflicts, static_cast<unsigned long long>(__popcll(mask)));
+}
 }  // namespace
+
+hipError_t launch_dsens_dep_final(const DsensDepGrid* d_grids, const uint32_t* d_prefix, int n_grids, uint32_t n_blocks, hipStream_t stream) {
+    if (n_grids <= 0 || n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(dsens_dep_final_kernel, dim3(n_blocks), dim3(256), 0, stream, d_grids, d_prefix, n_grids);
+    return hipGetLastError();
+}
 
 hipError_t launch_dsens_apply(const DsensSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, hipStream_t stream) {
     if (n_segs <= 0 || n_blocks == 0) return hipSuccess;

@@ -1,5 +1,5 @@
 // ccd_dsens_api.cpp - ccd_dsens_* and ccd_latent_footprint of include/ccd.h: the host side of the distortion deltas
-// (DESIGN.md sections 4.13, and 4.15 for the cool-chics of P / B frames).  Built on the public ccd_batch_* calls: the float path is
+// (DESIGN.md sections 4.13, 4.15 for the cool-chics of P / B frames, 4.16 for the frames that predict from a candidate's).  Built on the public ccd_batch_* calls: the float path is
 // the decode batch's, untouched.
 #include <array>
 #include <cstring>
@@ -67,24 +67,21 @@ int footprint(const ccd_cc_header& h, int grid, Footprint& f) {
 }  // namespace ccd
 
 namespace {
-// Smallest stride at which the intervals of two latents `stride` apart are disjoint along one axis of n latents and N samples
-// (and, chroma_shift = 1, their halves rounded outwards).
-int axis_stride(const Footprint& f, int a, int n, int N, int chroma_shift) {
-    for (int S = 1; S < n; ++S) {
-        bool ok = true;
-        for (int i = 0; ok && i + S < n; ++i) {
-            const int64_t s0 = static_cast<int64_t>(i) * f.num[a] / f.den[a], s1 = static_cast<int64_t>(i + S) * f.num[a] / f.den[a];
-            const int64_t end0 = std::min<int64_t>(s0 + f.hi[a], N - 1), begin1 = std::max<int64_t>(s1 + f.lo[a], 0);
-            ok = (begin1 >> chroma_shift) > (end0 >> chroma_shift);
-        }
-        if (ok) return S;
-    }
-    return std::max(n, 1);
+// Axis a (0 rows, 1 columns) of `grid` as ccd_lattice.hpp describes it.  4:2:0: the chroma planes take the footprint halved,
+// rounded outwards - as samples of the full picture that is the interval widened to even alignment.
+LatticeAxis lattice_axis(const ccd_cc_header& h, const Footprint& f, int grid, int a, int frame_data_type) {
+    LatticeAxis A;
+    A.n = a ? h.grid_w[grid] : h.grid_h[grid]; A.N = h.img_size[a];
+    A.lo = f.lo[a]; A.hi = f.hi[a]; A.num = f.num[a]; A.den = f.den[a];
+    A.even = frame_data_type == 1 ? 1 : 0;
+    return A;
 }
 
-int probe_stride(const ccd_cc_header& h, const Footprint& f, int grid, int frame_data_type) {
-    const int sh = frame_data_type == 1 ? 1 : 0;
-    return std::max(axis_stride(f, 0, h.grid_h[grid], h.img_size[0], sh), axis_stride(f, 1, h.grid_w[grid], h.img_size[1], sh));
+// The stride of the grid's lattices: the regions of two latents S apart in either direction keep `margin` samples between them
+// (0: they are disjoint, all the own maps need; DESIGN.md 4.16 for a candidate with dependents).
+int probe_stride(const ccd_cc_header& h, const Footprint& f, int grid, int frame_data_type, int margin) {
+    return std::max(lattice_stride(lattice_axis(h, f, grid, 0, frame_data_type), margin),
+                    lattice_stride(lattice_axis(h, f, grid, 1, frame_data_type), margin));
 }
 
 struct PassPlan { int grid, py, px, move; };
@@ -112,6 +109,28 @@ struct Candidate {
     float* ref_f32[2] = {};
     float* warped[2] = {};
     std::vector<std::array<void*, 3>> inter_planes;  // [0] base, [1 + k] probe slot k
+    // the frames that predict from this one: the passes keep `margin` samples between two regions, dsens_dep_kernel
+    // sums what every probe does to the dependents into `dep_maps`
+    struct Dependent {
+        ccd_dsens_dependent in;
+        Block buf;                 // [the other reference as f32, B frames][base planes]
+        float* other_f32 = nullptr;
+        void* base[3] = {};
+    };
+    std::vector<Dependent> deps;
+    int margin = 0;
+    Block dep_maps, dep_f32;                 // [maps][flags][conflict counters]; the frame's base and K probe planes as f32 4:4:4
+    size_t dep_zero_bytes = 0, flag_off[CCD_MAX_GRIDS] = {}, count_off = 0;
+    int64_t conflicts[CCD_MAX_GRIDS] = {};   // of the last finished run
+    bool dep_covered = false;
+    int64_t* dep_map(int g) const { return reinterpret_cast<int64_t*>(dep_maps.as<char>() + map_off[g]); }
+    uint8_t* dep_flag(int g) const { return dep_maps.as<uint8_t>() + flag_off[g]; }
+    unsigned long long* dep_count(int g) const { return reinterpret_cast<unsigned long long*>(dep_maps.as<char>() + count_off) + g; }
+    float* frame_f32(int k) const {  // k = -1: the base planes, else probe slot k
+        return dep_f32.as<float>() + static_cast<size_t>(k + 1) * 3 * hdr.img_size[0] * hdr.img_size[1];
+    }
+    const void* frame_plane(const ccd_dsens* d, int k, int p) const;
+    void drop() { priv.drop(); maps.drop(); inter_buf.drop(); dep_maps.drop(); dep_f32.drop(); for (auto& q : deps) q.buf.drop(); }
     int8_t* copy(int k, int g) const { return priv.as<int8_t>() + static_cast<size_t>(k) * copy_bytes + grid_off[g]; }
     int64_t* map(int g) const { return reinterpret_cast<int64_t*>(maps.as<char>() + map_off[g]); }
 };
@@ -126,6 +145,7 @@ struct Round {  // offsets into the tables block
     int n_segs = 0, n_passes = 0;
     uint32_t n_blocks = 0, n_units = 0, n_probes = 0;
     InterLaunch probes[2];  // by kernel instantiation: [0] run-time taps, [1] sinc-8
+    InterLaunch deps[2];    // dsens_dep_kernel, by the DEPENDENT's filter
 };
 }  // namespace
 
@@ -137,12 +157,21 @@ struct ccd_dsens {
     Mirror tables;
     Block slab;
     InterLaunch inter_base[2];  // the base slots of the inter candidates, behind the first round's float path
+    InterLaunch dep_base[2];    // the base planes of the dependents, behind those
+    InterLaunch dep_final;      // dsens_dep_final_kernel over the grids of the candidates with dependents
     bool planned = false;   // the tables describe every candidate
     int pending = 0;        // a run is in flight
     int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
-    int stages = 7;         // ccd_dsens_debug_stages
+    int stages = 31;        // ccd_dsens_debug_stages
     StreamSet streams;
 };
+
+// plane p of the candidate's frame as slot k decodes it (-1: the base slot)
+const void* Candidate::frame_plane(const ccd_dsens* d, int k, int p) const {
+    int ph = 0, pw = 0;
+    if (is_inter) return inter_planes[k + 1][p];
+    return ccd_batch_plane(d->batch, k < 0 ? base_slot : first_probe + k, p, &ph, &pw);
+}
 
 namespace {
 DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPlan& pp, bool empty) {
@@ -164,9 +193,8 @@ DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPla
     }
     const Footprint& f = c.fp[g];
     for (int p = 0; p < 3; ++p) {
-        int ph = 0, pw = 0;
-        P.base[p] = c.is_inter ? c.inter_planes[0][p] : ccd_batch_plane(d->batch, c.base_slot, p, &ph, &pw);
-        P.probe[p] = c.is_inter ? c.inter_planes[1 + k][p] : ccd_batch_plane(d->batch, c.first_probe + k, p, &ph, &pw);
+        P.base[p] = c.frame_plane(d, -1, p);
+        P.probe[p] = c.frame_plane(d, k, p);
         P.src[p] = c.src[p];
     }
     P.stride = c.stride[g]; P.py = pp.py; P.px = pp.px;
@@ -204,11 +232,54 @@ DsensInterJob make_inter_job(const ccd_dsens* d, const Candidate& c, int which) 
     return J;
 }
 
-int put_inter_launch(TableImage& img, const std::vector<DsensInterJob>& jobs, InterLaunch& L) {
+// dependent q of the candidate reconstructed with `ref` (the candidate's frame as f32 4:4:4) as its reference `which`: into its
+// base planes (base = true: a job of dsens_inter_kernel), or as dsens_dep_kernel reconstructs a unit
+DsensInterJob make_dep_recon(const Candidate& c, const Candidate::Dependent& q, const float* ref, bool base) {
+    DsensInterJob J;
+    std::memset(&J, 0, sizeof(J));
+    const bool two = q.in.frame_type == 2;
+    J.residue = q.in.residue; J.motion = q.in.motion;
+    J.ref0 = (two && q.in.which == 1) ? q.other_f32 : ref;
+    J.ref1 = (two && q.in.which == 0) ? q.other_f32 : ref;
+    for (int p = 0; p < 3; ++p) J.plane[p] = q.base[p];
+    J.mode = base ? 0 : 2;
+    J.frame_type = q.in.frame_type;
+    J.H = c.hdr.img_size[0]; J.W = c.hdr.img_size[1];
+    J.n_taps = q.in.warp_filter_size;
+    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? q.in.global_flow[i] : 0;
+    J.chroma_shift = c.frame_data_type == 1 ? 1 : 0;
+    J.wide = c.bitdepth > 8;
+    J.tiles_x = ((J.W >> J.chroma_shift) + 63) / 64;
+    J.maxv = static_cast<float>((1 << c.bitdepth) - 1);
+    return J;
+}
+
+DsensDepJob make_dep_job(const Candidate& c, const Candidate::Dependent& q, int k, const PassPlan& pp) {
+    DsensDepJob D;
+    std::memset(&D, 0, sizeof(D));
+    D.recon = make_dep_recon(c, q, c.frame_f32(k), false);
+    for (int p = 0; p < 3; ++p) D.src[p] = q.in.src[p];
+    const int g = pp.grid;
+    D.acc = reinterpret_cast<unsigned long long*>(c.dep_map(g));
+    D.flag = c.dep_flag(g);
+    D.which = q.in.which;
+    D.h = c.hdr.grid_h[g]; D.w = c.hdr.grid_w[g];
+    D.move = pp.move; D.stride = c.stride[g]; D.py = pp.py; D.px = pp.px;
+    D.ay = lattice_axis(c.hdr, c.fp[g], g, 0, c.frame_data_type);
+    D.ax = lattice_axis(c.hdr, c.fp[g], g, 1, c.frame_data_type);
+    return D;
+}
+
+inline const DsensInterJob& recon_of(const DsensInterJob& J) { return J; }
+inline const DsensInterJob& recon_of(const DsensDepJob& D) { return D.recon; }
+
+template <typename Job>
+int put_inter_launch(TableImage& img, const std::vector<Job>& jobs, InterLaunch& L) {
     std::vector<uint32_t> prefix(jobs.size() + 1, 0);
     uint64_t blocks = 0;
     for (size_t i = 0; i < jobs.size(); ++i) {
-        blocks += static_cast<uint64_t>(jobs[i].tiles_x) * (((jobs[i].H >> jobs[i].chroma_shift) + 3) / 4);
+        const DsensInterJob& J = recon_of(jobs[i]);
+        blocks += static_cast<uint64_t>(J.tiles_x) * (((J.H >> J.chroma_shift) + 3) / 4);
         if (blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
         prefix[i + 1] = static_cast<uint32_t>(blocks);
     }
@@ -233,11 +304,32 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
             const int rc = put_inter_launch(img, base[i], d->inter_base[i]);
             if (rc < 0) return rc;
         }
+        std::vector<DsensInterJob> dep_base[2];
+        std::vector<DsensDepGrid> grids;
+        std::vector<uint32_t> grid_prefix(1, 0);
+        for (const auto& cp : d->cands) {
+            for (const auto& q : cp->deps) dep_base[q.in.warp_filter_size == 8].push_back(make_dep_recon(*cp, q, cp->frame_f32(-1), true));
+            for (int g = 0; !cp->deps.empty() && g < cp->hdr.n_grids; ++g) {
+                DsensDepGrid G;
+                std::memset(&G, 0, sizeof(G));
+                G.lat = cp->lat[g]; G.map = cp->dep_map(g); G.flag = cp->dep_flag(g); G.conflicts = cp->dep_count(g);
+                G.n = static_cast<uint32_t>(cp->hdr.grid_h[g]) * static_cast<uint32_t>(cp->hdr.grid_w[g]);
+                grids.push_back(G);
+                grid_prefix.push_back(grid_prefix.back() + (2 * G.n + 255) / 256);
+            }
+        }
+        for (int i = 0; i < 2; ++i) {
+            const int rc = put_inter_launch(img, dep_base[i], d->dep_base[i]);
+            if (rc < 0) return rc;
+        }
+        d->dep_final.n_jobs = static_cast<int>(grids.size()); d->dep_final.n_blocks = grid_prefix.back();
+        d->dep_final.jobs = img.put(grids); d->dep_final.prefix = img.put(grid_prefix);
     }
     for (size_t r = 0; r < n_rounds; ++r) {
         std::vector<DsensSeg> segs;
         std::vector<DsensPass> passes;
         std::vector<DsensInterJob> jobs[2];
+        std::vector<DsensDepJob> dep_jobs[2];
         for (const auto& cp : d->cands) {
             const Candidate& c = *cp;
             const ccd_cc_header& h = c.hdr;
@@ -264,6 +356,8 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
                 }
                 if (cur) passes.push_back(make_pass(d, c, k, *cur, false));
                 if (cur && c.is_inter) jobs[c.inter.warp_filter_size == 8].push_back(make_inter_job(d, c, k));
+                for (size_t q = 0; cur && q < c.deps.size(); ++q)
+                    dep_jobs[c.deps[q].in.warp_filter_size == 8].push_back(make_dep_job(c, c.deps[q], k, *cur));
             }
             if (r == 0)
                 for (int g = 0; g < h.n_grids; ++g)
@@ -272,7 +366,8 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
         }
         Round& R = d->rounds[r];
         for (int i = 0; i < 2; ++i) {
-            const int rc = put_inter_launch(img, jobs[i], R.probes[i]);
+            int rc = put_inter_launch(img, jobs[i], R.probes[i]);
+            if (rc >= 0) rc = put_inter_launch(img, dep_jobs[i], R.deps[i]);
             if (rc < 0) return rc;
         }
         std::vector<uint32_t> seg_prefix(segs.size() + 1, 0), unit_prefix(passes.size() + 1, 0), probe_prefix(passes.size() + 1, 0);
@@ -317,14 +412,37 @@ int ccd_latent_footprint(const ccd_cc_header* arch, int grid, int32_t box[4]) {
     return CCD_OK;
 }
 
-int ccd_latent_probe_stride(const ccd_cc_header* arch, int grid, int frame_data_type) {
-    if (!arch || frame_data_type < 0 || frame_data_type > 2) return CCD_ERR_ARG;
+int ccd_latent_probe_stride_margin(const ccd_cc_header* arch, int grid, int frame_data_type, int margin) {
+    if (!arch || frame_data_type < 0 || frame_data_type > 2 || margin < 0) return CCD_ERR_ARG;
     ccd_cc_header h;
     if (rederive_cc_header(*arch, static_cast<size_t>(std::max(arch->nn_n_bytes, 0)), &h) < 0) return CCD_ERR_VALUE;
     Footprint f;
     const int rc = footprint(h, grid, f);
     if (rc < 0) return rc;
-    return rc == 1 ? 0 : probe_stride(h, f, grid, frame_data_type);
+    return rc == 1 ? 0 : probe_stride(h, f, grid, frame_data_type, margin);
+}
+
+int ccd_latent_probe_stride(const ccd_cc_header* arch, int grid, int frame_data_type) {
+    return ccd_latent_probe_stride_margin(arch, grid, frame_data_type, 0);
+}
+
+// Host only (tests): ccd_lattice.hpp on one axis given by its numbers - n latents over N samples, the footprint interval
+// [lo, hi] around floor(i num / den), `even` the 4:2:0 widening.  Not a function of any handle.
+int ccd_debug_lattice_stride(int n, int N, int lo, int hi, uint32_t num, uint32_t den, int even, int margin) {
+    if (n < 1 || N < 1 || den == 0 || lo > 0 || hi < 0 || margin < 0) return CCD_ERR_ARG;
+    return lattice_stride(LatticeAxis{n, N, lo, hi, num, den, even ? 1 : 0}, margin);
+}
+
+// ... -1: no member of the lattice (stride S, phase) has its region under [a, b]; its index: exactly one has; -2: more than one.
+// *first, *count (may be NULL): the first member hit and how many.
+int ccd_debug_lattice_hit(int n, int N, int lo, int hi, uint32_t num, uint32_t den, int even, int S, int phase, int a, int b, int32_t* first,
+                          int32_t* count) {
+    if (n < 1 || N < 1 || den == 0 || lo > 0 || hi < 0 || S < 1 || phase < 0) return CCD_ERR_ARG;
+    int f = -1;
+    const int c = lattice_hit(LatticeAxis{n, N, lo, hi, num, den, even ? 1 : 0}, S, phase, a, b, &f);
+    if (first) *first = f;
+    if (count) *count = c;
+    return c == 0 ? -1 : (c == 1 ? f : -2);
 }
 
 int ccd_dsens_create(int device, int n_probe_slots, ccd_dsens** out) {
@@ -348,9 +466,22 @@ void ccd_dsens_destroy(ccd_dsens* d) {
     (void)hipSetDevice(d->device);
     (void)d->streams.drain();
     ccd_batch_destroy(d->batch);  // drains the streams it was run on
-    for (auto& c : d->cands) { c->priv.drop(); c->maps.drop(); c->inter_buf.drop(); }
+    for (auto& c : d->cands) c->drop();
     d->tables.drop(); d->slab.drop();
     delete d;
+}
+
+// The passes of a candidate, grid by grid: every lattice of the stride that keeps c.margin samples between two regions.
+static void plan_passes(Candidate& c) {
+    const ccd_cc_header& h = c.hdr;
+    c.passes.clear();
+    for (int g = 0; g < h.n_grids; ++g) {
+        if (h.is_hyperlatent[g]) continue;
+        const int S = c.stride[g] = probe_stride(h, c.fp[g], g, c.frame_data_type, c.margin);
+        for (int move = -1; move <= 1; move += 2)
+            for (int py = 0; py < std::min(S, h.grid_h[g]); ++py)
+                for (int px = 0; px < std::min(S, h.grid_w[g]); ++px) c.passes.push_back(PassPlan{g, py, px, move});
+    }
 }
 
 // ccd_dsens_add and ccd_dsens_add_inter behind their pointer checks (inter: null for an intra candidate)
@@ -384,15 +515,12 @@ static int add_candidate(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t*
         const int rc = footprint(h, g, c.fp[g]);
         if (rc < 0) return rc;
         if (rc == 1) continue;
-        const int S = c.stride[g] = probe_stride(h, c.fp[g], g, frame_data_type);
-        for (int move = -1; move <= 1; move += 2)
-            for (int py = 0; py < std::min(S, h.grid_h[g]); ++py)
-                for (int px = 0; px < std::min(S, h.grid_w[g]); ++px) c.passes.push_back(PassPlan{g, py, px, move});
     }
+    plan_passes(c);
     for (int p = 0; p < 3; ++p) c.src[p] = src[p];
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(d->device));
-    auto drop = [&c] { c.priv.drop(); c.maps.drop(); c.inter_buf.drop(); };
+    auto drop = [&c] { c.drop(); };
     if (!c.priv.get(d->device, BlockPool::kDevice, std::max<size_t>(256, c.copy_bytes * d->K)) ||
         !c.maps.get(d->device, BlockPool::kDevice, std::max<size_t>(256, map_bytes))) {
         drop();
@@ -445,6 +573,55 @@ int ccd_dsens_add_inter(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t* 
     return add_candidate(d, arch, bytes_nn, n_nn, latents, src, bitdepth, frame_data_type, inter);
 }
 
+int ccd_dsens_add_dependent(ccd_dsens* d, int slot, const ccd_dsens_dependent* dep) {
+    if (!d || !dep || !dep->residue || !dep->motion || !dep->src[0] || !dep->src[1] || !dep->src[2]) return CCD_ERR_ARG;
+    if (dep->frame_type < 1 || dep->frame_type > 2 || dep->which < 0 || dep->which > 1 || (dep->frame_type == 1 && dep->which != 0)) return CCD_ERR_ARG;
+    for (int p = 0; p < 3; ++p)
+        if (dep->frame_type == 2 && !dep->other_ref[p]) return CCD_ERR_ARG;
+    if (d->pending) return CCD_ERR_ARG;
+    if (!warp_filter_ok(dep->warp_filter_size)) return CCD_ERR_VALUE;
+    if (slot < 0 || slot >= static_cast<int>(d->cands.size())) return CCD_ERR_ARG;
+    if (d->dead < 0) return d->dead;
+    Candidate& c = *d->cands[slot];
+    const ccd_cc_header& h = c.hdr;
+    if (!yuv420_sides_ok(c.frame_data_type, h.img_size[0], h.img_size[1])) return CCD_ERR_VALUE;
+    // ---- the device from here on ----
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t hw = static_cast<size_t>(h.img_size[0]) * h.img_size[1], sample = c.bitdepth > 8 ? 2 : 1;
+    const size_t chw = c.frame_data_type == 1 ? static_cast<size_t>(h.img_size[0] / 2) * (h.img_size[1] / 2) : hw;
+    const size_t f32_3 = align256(3 * hw * sizeof(float)), luma = align256(hw * sample), chroma = align256(chw * sample);
+    if (c.deps.empty()) {  // the first one: [maps as the own ones][flags][counters], and the frame as f32 for the base and K probe slots
+        size_t at = align256(c.map_off[h.n_grids - 1] + 2 * sizeof(int64_t) * h.grid_h[h.n_grids - 1] * h.grid_w[h.n_grids - 1]);
+        for (int g = 0; g < h.n_grids; ++g) { c.flag_off[g] = at; at += align256(2 * static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]); }
+        c.count_off = at;
+        at += align256(CCD_MAX_GRIDS * sizeof(unsigned long long));
+        if (!c.dep_maps.get(d->device, BlockPool::kDevice, at) ||
+            !c.dep_f32.get(d->device, BlockPool::kDevice, static_cast<size_t>(d->K + 1) * 3 * hw * sizeof(float))) {
+            c.dep_maps.drop(); c.dep_f32.drop();
+            return CCD_ERR_NOMEM;
+        }
+        c.dep_zero_bytes = at;
+    }
+    Candidate::Dependent q;
+    q.in = *dep;
+    const bool two = dep->frame_type == 2;
+    if (!q.buf.get(d->device, BlockPool::kDevice, (two ? f32_3 : 0) + luma + 2 * chroma)) {
+        if (c.deps.empty()) { c.dep_maps.drop(); c.dep_f32.drop(); }
+        return CCD_ERR_NOMEM;
+    }
+    char* at = q.buf.as<char>();
+    if (two) { q.other_f32 = reinterpret_cast<float*>(at); at += f32_3; }
+    q.base[0] = at; q.base[1] = at + luma; q.base[2] = at + luma + chroma;
+    c.deps.push_back(q);
+    int W = 0;  // the widest window of the dependents' warps: 2 bilinear, 4 bicubic, the filter size for sinc
+    for (const auto& e : c.deps) W = std::max(W, e.in.warp_filter_size);
+    c.margin = c.frame_data_type == 1 ? W + 2 : W - 1;
+    plan_passes(c);
+    c.covered = c.dep_covered = false;
+    d->planned = false;
+    return CCD_OK;
+}
+
 int ccd_dsens_run(ccd_dsens* d, void* stream) {
     if (!d || d->pending) return CCD_ERR_ARG;
     if (d->dead < 0) return d->dead;
@@ -471,7 +648,29 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
             HIP_TRY(launch_planes_to_444(pl[0], pl[1], pl[2], c.ref_f32[r], c.hdr.img_size[0], c.hdr.img_size[1], c.bitdepth, c.frame_data_type, st));
         }
     }
+    auto dep_launches = [&](const InterLaunch (&L)[2]) -> int {
+        for (int i = 0; i < 2; ++i)
+            if (launch_dsens_dep(reinterpret_cast<const DsensDepJob*>(base + L[i].jobs), reinterpret_cast<const uint32_t*>(base + L[i].prefix),
+                                 L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess) return CCD_ERR_HIP;
+        return CCD_OK;
+    };
+    // slot k (-1: the base slot) of a candidate with dependents as the dependents' warps read it
+    auto to_f32 = [&](const Candidate& c, int k) {
+        return launch_planes_to_444(c.frame_plane(d, k, 0), c.frame_plane(d, k, 1), c.frame_plane(d, k, 2), c.frame_f32(k), c.hdr.img_size[0],
+                                    c.hdr.img_size[1], c.bitdepth, c.frame_data_type, st);
+    };
+    const bool dep_convert = (d->stages & 8) != 0, dep_sum = (d->stages & 16) != 0;
+    for (const auto& cp : d->cands) {  // the sums and flags of the dependents start from zero; their other references as f32
+        const Candidate& c = *cp;
+        if (c.deps.empty()) continue;
+        HIP_TRY(hipMemsetAsync(c.dep_maps.p, 0, c.dep_zero_bytes, st));
+        for (const auto& q : c.deps)
+            if (q.other_f32 && dep_convert)
+                HIP_TRY(launch_planes_to_444(q.in.other_ref[0], q.in.other_ref[1], q.in.other_ref[2], q.other_f32, c.hdr.img_size[0], c.hdr.img_size[1],
+                                             c.bitdepth, c.frame_data_type, st));
+    }
     bool first = true;
+    size_t round = 0;
     for (const Round& R : d->rounds) {
         int rc = CCD_OK;
         if (d->stages & 1) {
@@ -480,23 +679,37 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
             if ((rc = ccd_batch_run(d->batch, stream)) < 0) return rc;
         }
         if (first && (d->stages & 2) && (rc = reconstruct(d->inter_base)) < 0) return rc;  // the base planes, and the warped references they leave
+        if (first && dep_convert) {  // the dependents' base planes from the candidates' base planes
+            for (const auto& cp : d->cands)
+                if (!cp->deps.empty()) HIP_TRY(to_f32(*cp, -1));
+            if ((rc = reconstruct(d->dep_base)) < 0) return rc;
+        }
         first = false;
         if ((d->stages & 2) && (rc = reconstruct(R.probes)) < 0) return rc;
+        if (dep_convert)
+            for (const auto& cp : d->cands)
+                for (int k = 0; !cp->deps.empty() && k < d->K && round * d->K + k < cp->passes.size(); ++k) HIP_TRY(to_f32(*cp, k));
+        if (dep_sum && (rc = dep_launches(R.deps)) < 0) return rc;
+        ++round;
         if (d->stages & 4) {
             HIP_TRY(launch_dsens_sse(reinterpret_cast<const DsensPass*>(base + R.passes), reinterpret_cast<const uint32_t*>(base + R.unit_prefix),
                                      reinterpret_cast<const uint32_t*>(base + R.probe_prefix), R.n_passes, R.n_units, R.n_probes,
                                      d->slab.as<int64_t>(), st));
         }
     }
+    if (dep_sum)
+        HIP_TRY(launch_dsens_dep_final(reinterpret_cast<const DsensDepGrid*>(base + d->dep_final.jobs), reinterpret_cast<const uint32_t*>(base + d->dep_final.prefix),
+                                       d->dep_final.n_jobs, d->dep_final.n_blocks, st));
     return CCD_OK;
 }
 
 // Not part of include/ccd.h: the measurement hook of tools/rd_bench.py --inter, which looks the symbol up by name.  Which stages of
 // every round the following runs enqueue - bit 0 the float path (apply + ccd_batch_run), bit 1 the reconstruction launches of inter
-// candidates, bit 2 the squared-error split; 7 by default.  A run with another mask covers no slot: ccd_dsens_slot_map refuses
+// candidates, bit 2 the squared-error split, bit 3 the conversions of candidates with dependents (their planes to f32, the
+// dependents' base planes), bit 4 dsens_dep_kernel and its finalising pass; 31 by default.  A run with another mask covers no slot: ccd_dsens_slot_map refuses
 // (CCD_ERR_ARG) until a full run has finished.
 int ccd_dsens_debug_stages(ccd_dsens* d, int mask) {
-    if (!d || d->pending || mask < 0 || mask > 7) return CCD_ERR_ARG;
+    if (!d || d->pending || mask < 0 || mask > 31) return CCD_ERR_ARG;
     d->stages = mask;
     return CCD_OK;
 }
@@ -519,7 +732,13 @@ int ccd_dsens_wait(ccd_dsens* d, void* stream) {
         Candidate& c = *cp;
         c.status = ccd_batch_slot_status(d->batch, c.base_slot);
         for (int k = 0; c.status == CCD_OK && k < d->K; ++k) c.status = ccd_batch_slot_status(d->batch, c.first_probe + k);
-        c.covered = d->stages == 7;
+        c.covered = (d->stages & 7) == 7;
+        c.dep_covered = c.covered && !c.deps.empty() && (d->stages & 24) == 24;
+        if (c.dep_covered && c.status == CCD_OK) {  // (the stream is idle: ccd_batch_wait synchronised)
+            unsigned long long n[CCD_MAX_GRIDS];
+            HIP_TRY(hipMemcpy(n, c.dep_count(0), sizeof(n), hipMemcpyDeviceToHost));
+            for (int g = 0; g < CCD_MAX_GRIDS; ++g) c.conflicts[g] = static_cast<int64_t>(n[g]);
+        }
         if (first == CCD_OK && c.status != CCD_OK) first = c.status;
     }
     return first;
@@ -532,6 +751,23 @@ int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_pt
     if (c.status != CCD_OK) return c.status;
     *dev_ptr = c.map(grid);
     return static_cast<int64_t>(c.hdr.grid_h[grid]) * c.hdr.grid_w[grid];
+}
+
+int64_t ccd_dsens_slot_dep_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr) {
+    if (!d || !dev_ptr || slot < 0 || slot >= static_cast<int>(d->cands.size())) return CCD_ERR_ARG;
+    const Candidate& c = *d->cands[slot];
+    if (grid < 0 || grid >= c.hdr.n_grids || c.deps.empty() || !c.dep_covered || d->pending) return CCD_ERR_ARG;
+    if (c.status != CCD_OK) return c.status;
+    *dev_ptr = c.dep_map(grid);
+    return static_cast<int64_t>(c.hdr.grid_h[grid]) * c.hdr.grid_w[grid];
+}
+
+int64_t ccd_dsens_slot_dep_conflicts(const ccd_dsens* d, int slot, int grid) {
+    if (!d || slot < 0 || slot >= static_cast<int>(d->cands.size())) return CCD_ERR_ARG;
+    const Candidate& c = *d->cands[slot];
+    if (grid < 0 || grid >= c.hdr.n_grids || c.deps.empty() || !c.dep_covered || d->pending) return CCD_ERR_ARG;
+    if (c.status != CCD_OK) return c.status;
+    return c.conflicts[grid];
 }
 
 int ccd_dsens_passes(const ccd_dsens* d, int slot) {

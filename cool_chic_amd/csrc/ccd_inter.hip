@@ -70,6 +70,12 @@ hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, 
 __device__ __forceinline__ int ic_tap_offset(float f, int size) {
     return static_cast<int>(fminf(fmaxf(f, -static_cast<float>(size + 16)), static_cast<float>(size + 16)));
 }
+// ---- WHERE a window reads, stated once for the warps and for dsens_dep_kernel (ic_window_axis).  Along an axis of n samples a
+// window is nt taps at consecutive integer positions from a first one; the tap at position t reads the reference at ic_tap_index:
+// border clamp, integer global shift, border clamp - monotone in t, so a window reads inside [index(first), index(first + nt - 1)].
+__device__ __forceinline__ int ic_tap_index(int t, int n, int g) { return ic_clamp(ic_clamp(t, 0, n - 1) + g, 0, n - 1); }
+// position of tap j of the sinc window around sample i with the tap offset r of its flow
+__device__ __forceinline__ int ic_sinc_tap(int i, int nt, int j, int r) { return i + (-(nt / 2) + 1) + j + r; }
 
 // ---- the sinc-windowed warp, templated on the tap count.  NT > 0: known at compile time, arrays of NT, every loop fully unrolled;
 // NT == 0: n_taps at run time, arrays of kMaxTaps, loops rolled.  r06: the run-time version keeps cx / cy / xs in scratch memory
@@ -105,15 +111,14 @@ __device__ __forceinline__ void ic_taps(const float* __restrict__ ref, int H, in
                                         const float (&cx)[kTapCap<NT>], const float (&cy)[kTapCap<NT>], int y, int x, float out[3]) {
     constexpr int kUnroll = kTapUnroll<NT>;
     const int nt = NT > 0 ? NT : n_taps;
-    const int lo = -(nt / 2) + 1;
     const size_t plane = static_cast<size_t>(H) * W;
     int xs[kTapCap<NT>];
 #pragma unroll kUnroll
-    for (int j = 0; j < nt; ++j) xs[j] = ic_clamp(ic_clamp(x + lo + j + rx, 0, W - 1) + gx, 0, W - 1);
+    for (int j = 0; j < nt; ++j) xs[j] = ic_tap_index(ic_sinc_tap(x, nt, j, rx), W, gx);
     float acc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll kUnroll
     for (int i = 0; i < nt; ++i) {
-        const int yy = ic_clamp(ic_clamp(y + lo + i + ry, 0, H - 1) + gy, 0, H - 1);
+        const int yy = ic_tap_index(ic_sinc_tap(y, nt, i, ry), H, gy);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* row = ref + c * plane + static_cast<size_t>(yy) * W;
@@ -150,21 +155,32 @@ __device__ __forceinline__ float ic_cubic_outer(float x) {
     t = __fmul_rn(t, x);
     return __fsub_rn(t, 4.0f * A);
 }
+// the position, in samples, that sample i of an axis of n reads under the flow f (normalised and back, as grid_sample does)
+__device__ __forceinline__ float ic_native_coord(float f, int i, int n) {
+    const float s = static_cast<float>((n - 1.0) / 2.0);
+    const float g = __fadd_rn(ic_lin_coord(i, n), __fdiv_rn(f, s));
+    return __fmul_rn(__fadd_rn(g, 1.0f), s);
+}
+// bilinear: the position is clamped to the picture (in place); the floor of the position
+__device__ __forceinline__ float ic_native_floor(int n_taps, float& c, int n) {
+    if (n_taps == 2) c = fminf(static_cast<float>(n - 1), fmaxf(c, 0.0f));
+    return floorf(c);
+}
+// ... and from it the position of tap j of the window (2 taps from the floor, 4 from one before it; the floor saturated)
+__device__ __forceinline__ int ic_native_tap(int n_taps, float c0f, int n, int j) {
+    if (n_taps == 2) return static_cast<int>(c0f) + j;
+    return static_cast<int>(fminf(fmaxf(c0f, -4.0f), static_cast<float>(n) + 4.0f)) - 1 + j;
+}
 __device__ __forceinline__ void ic_warp_pixel_native(const float* __restrict__ ref, int H, int W, int gx, int gy, int n_taps, float fx,
                                                      float fy, int y, int x, float out[3]) {
-    const float sx = static_cast<float>((W - 1.0) / 2.0), sy = static_cast<float>((H - 1.0) / 2.0);
-    const float gxn = __fadd_rn(ic_lin_coord(x, W), __fdiv_rn(fx, sx)), gyn = __fadd_rn(ic_lin_coord(y, H), __fdiv_rn(fy, sy));
-    float ix = __fmul_rn(__fadd_rn(gxn, 1.0f), sx), iy = __fmul_rn(__fadd_rn(gyn, 1.0f), sy);
+    float ix = ic_native_coord(fx, x, W), iy = ic_native_coord(fy, y, H);
     const size_t plane = static_cast<size_t>(H) * W;
     if (n_taps == 2) {
-        ix = fminf(static_cast<float>(W - 1), fmaxf(ix, 0.0f));
-        iy = fminf(static_cast<float>(H - 1), fmaxf(iy, 0.0f));
-        const float x0f = floorf(ix), y0f = floorf(iy);
+        const float x0f = ic_native_floor(2, ix, W), y0f = ic_native_floor(2, iy, H);
         const float w = __fsub_rn(ix, x0f), e = __fsub_rn(1.0f, w), n = __fsub_rn(iy, y0f), s = __fsub_rn(1.0f, n);
         const float w_nw = __fmul_rn(s, e), w_ne = __fmul_rn(s, w), w_sw = __fmul_rn(n, e), w_se = __fmul_rn(n, w);
-        const int x0 = static_cast<int>(x0f), y0 = static_cast<int>(y0f);
-        const int xa = ic_clamp(ic_clamp(x0, 0, W - 1) + gx, 0, W - 1), xb = ic_clamp(ic_clamp(x0 + 1, 0, W - 1) + gx, 0, W - 1);
-        const int ya = ic_clamp(ic_clamp(y0, 0, H - 1) + gy, 0, H - 1), yb = ic_clamp(ic_clamp(y0 + 1, 0, H - 1) + gy, 0, H - 1);
+        const int xa = ic_tap_index(ic_native_tap(2, x0f, W, 0), W, gx), xb = ic_tap_index(ic_native_tap(2, x0f, W, 1), W, gx);
+        const int ya = ic_tap_index(ic_native_tap(2, y0f, H, 0), H, gy), yb = ic_tap_index(ic_native_tap(2, y0f, H, 1), H, gy);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* r = ref + c * plane;
@@ -176,21 +192,19 @@ __device__ __forceinline__ void ic_warp_pixel_native(const float* __restrict__ r
         }
         return;
     }
-    const float x0f = floorf(ix), y0f = floorf(iy);
+    const float x0f = ic_native_floor(4, ix, W), y0f = ic_native_floor(4, iy, H);
     const float tx = __fsub_rn(ix, x0f), ty = __fsub_rn(iy, y0f);
     const float cx[4] = {ic_cubic_outer(__fadd_rn(tx, 1.0f)), ic_cubic_inner(tx), ic_cubic_inner(__fsub_rn(1.0f, tx)), ic_cubic_outer(__fsub_rn(2.0f, tx))};
     const float cy[4] = {ic_cubic_outer(__fadd_rn(ty, 1.0f)), ic_cubic_inner(ty), ic_cubic_inner(__fsub_rn(1.0f, ty)), ic_cubic_outer(__fsub_rn(2.0f, ty))};
-    const int x0 = static_cast<int>(fminf(fmaxf(x0f, -4.0f), static_cast<float>(W) + 4.0f));
-    const int y0 = static_cast<int>(fminf(fmaxf(y0f, -4.0f), static_cast<float>(H) + 4.0f));
     int xs[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) xs[j] = ic_clamp(ic_clamp(x0 - 1 + j, 0, W - 1) + gx, 0, W - 1);
+    for (int j = 0; j < 4; ++j) xs[j] = ic_tap_index(ic_native_tap(4, x0f, W, j), W, gx);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float row[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int yy = ic_clamp(ic_clamp(y0 - 1 + i, 0, H - 1) + gy, 0, H - 1);
+            const int yy = ic_tap_index(ic_native_tap(4, y0f, H, i), H, gy);
             const float* r = ref + c * plane + static_cast<size_t>(yy) * W;
             float acc = __fmaf_rn(r[xs[0]], cx[0], __fmul_rn(r[xs[1]], cx[1]));
             acc = __fadd_rn(acc, __fmul_rn(r[xs[2]], cx[2]));
@@ -216,6 +230,23 @@ __device__ __forceinline__ void ic_warp(const float* __restrict__ ref, int H, in
     ic_coeffs<NT>(sx, n_taps, cx);
     ic_coeffs<NT>(sy, n_taps, cy);
     ic_taps<NT>(ref, H, W, gx, gy, n_taps, ic_tap_offset(rxf, W), ic_tap_offset(ryf, H), cx, cy, y, x, out);
+}
+
+// the interval [a, b] of reference indices that ic_warp<NT> reads along one axis (n samples, global shift g) for sample i with
+// the flow f: the first tap from the pieces the warps use, then ic_tap_index of the two ends
+template <int NT>
+__device__ __forceinline__ void ic_window_axis(int n_taps, float f, int i, int n, int g, int& a, int& b) {
+    const int nt = NT > 0 ? NT : n_taps;
+    int first;
+    if (NT == 0 && n_taps < 6) {
+        float c = ic_native_coord(f, i, n);
+        const float c0f = ic_native_floor(n_taps, c, n);
+        first = ic_native_tap(n_taps, c0f, n, 0);
+    } else {
+        first = ic_sinc_tap(i, nt, 0, ic_tap_offset(floorf(f), n));
+    }
+    a = ic_tap_index(first, n, g);
+    b = ic_tap_index(first + nt - 1, n, g);
 }
 
 // ---- the blend (decode.py:170-189): weight = clamp(alpha | beta + 0.5, 0, 1), prediction = beta w0 + (1 - beta) w1 (B frames),
@@ -421,6 +452,107 @@ hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_pre
     if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
     if (sinc8) hipLaunchKernelGGL(dsens_inter_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
     else hipLaunchKernelGGL(dsens_inter_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
+    return hipGetLastError();
+}
+
+// ---- distortion deltas through the frames that predict from a moved one (ccd_dsens_add_dependent).  A job is one
+// (candidate, dependent, probe slot) of a round: the dependent frame F reconstructed with the candidate's PROBE planes as its
+// reference `which`.  The warp is not pointwise in the reference: a sample of F reads an N x N window at a flow-displaced place,
+// so the change of one latent of the reference scatters into F wherever F's flows point.  Per unit (one luma sample, or one 4:2:0
+// quad and its chroma sample; the tiles of dsens_inter_kernel):
+//   (a) the interval of reference indices every sample's window reads, per axis (ic_window_axis: the warps' own index pieces);
+//   (b) lattice_hit (ccd_lattice.hpp) on both axes: which members of the pass's lattice have their reference-change region under
+//       a window.  None: the unit reads unchanged reference samples only and is F's base, bit for bit - done.  Exactly one: the
+//       unit is reconstructed with the functions of dsens_inter_kernel and quantised, and the sum over its samples of
+//       (F' - src)^2 - (F - src)^2 goes to that entry's accumulator with one 64-bit integer atomic add (any order, same bits);
+//   (c) more than one: a conflict - the unit's change cannot be split between the entries, so each entry hit gets the byte 1 in
+//       `flag` (plain stores; every writer stores the same value) and dsens_dep_final_kernel turns it into the sentinel.
+// Only DIRECT dependents: frames that predict from F are not followed.  No LDS, no waits, no spinning.
+__device__ __forceinline__ int di_load(const void* plane, size_t at, int wide) {
+    return wide ? static_cast<int>(static_cast<const uint16_t*>(plane)[at]) : static_cast<int>(static_cast<const uint8_t*>(plane)[at]);
+}
+__device__ __forceinline__ long long di_gain(int q, int base, int src) {
+    const long long dq = q - src, db = base - src;
+    return dq * dq - db * db;
+}
+// what the windows of sample (y, x) hit: counts per axis (0 on either: nothing) and the first member of each
+template <int NT>
+__device__ __forceinline__ bool dd_sample_hits(const DsensDepJob& D, int y, int x, int& fy, int& cy, int& fx, int& cx) {
+    const DsensInterJob& J = D.recon;
+    const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
+    const int r = D.which;
+    int a, b;
+    ic_window_axis<NT>(J.n_taps, J.motion[(2 * r + 1) * plane + i], y, J.H, r ? J.gflow[3] : J.gflow[1], a, b);
+    cy = lattice_hit(D.ay, D.stride, D.py, a, b, &fy);
+    cx = 0;
+    if (cy == 0) return false;
+    ic_window_axis<NT>(J.n_taps, J.motion[(2 * r) * plane + i], x, J.W, r ? J.gflow[2] : J.gflow[0], a, b);
+    cx = lattice_hit(D.ax, D.stride, D.px, a, b, &fx);
+    return cx != 0;
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void dsens_dep_kernel(const DsensDepJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+    const uint32_t blk = blockIdx.x;
+    const int j = entry_of(prefix, n_jobs, blk);
+    const DsensDepJob& D = jobs[j];  // (uniform: scalar loads)
+    const DsensInterJob& J = D.recon;
+    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
+    int ux, uy;
+    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
+    const int cs = J.chroma_shift;
+    if (ux >= (J.W >> cs) || uy >= (J.H >> cs)) return;
+    const int n = cs ? 4 : 1;
+    const size_t map_plane = D.move > 0 ? static_cast<size_t>(D.h) * D.w : 0;
+    int state = 0, ey = 0, ex = 0;  // 0: nothing hit, 1: the entry (ey, ex) alone, 2: a conflict
+#pragma unroll 1
+    for (int q = 0; q < n; ++q) {
+        int fy, cy, fx, cx;
+        if (!dd_sample_hits<NT>(D, (uy << cs) + (q >> 1), (ux << cs) + (q & 1), fy, cy, fx, cx)) continue;
+        if (cy > 1 || cx > 1 || (state == 1 && (fy != ey || fx != ex))) state = 2;
+        else if (state == 0) { state = 1; ey = fy; ex = fx; }
+    }
+    if (state == 0) return;
+    if (state == 2) {
+#pragma unroll 1
+        for (int q = 0; q < n; ++q) {
+            int fy, cy, fx, cx;
+            if (!dd_sample_hits<NT>(D, (uy << cs) + (q >> 1), (ux << cs) + (q & 1), fy, cy, fx, cx)) continue;
+            for (int iy = 0; iy < cy; ++iy)
+                for (int ix = 0; ix < cx; ++ix)
+                    D.flag[map_plane + static_cast<size_t>(fy + iy * D.stride) * D.w + (fx + ix * D.stride)] = 1;
+        }
+        return;
+    }
+    const float maxv = J.maxv;
+    float v[3], sum1 = 0.0f, sum2 = 0.0f;
+    long long gain = 0;
+#pragma unroll 1
+    for (int q = 0; q < n; ++q) {
+        const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
+        di_pixel<NT>(J, y, x, v);
+        const size_t i = static_cast<size_t>(y) * J.W + x;
+        gain += di_gain(static_cast<int>(quantise_sample(v[0], maxv)), di_load(J.plane[0], i, J.wide), di_load(D.src[0], i, J.wide));
+        if (!cs) {
+            gain += di_gain(static_cast<int>(quantise_sample(v[1], maxv)), di_load(J.plane[1], i, J.wide), di_load(D.src[1], i, J.wide));
+            gain += di_gain(static_cast<int>(quantise_sample(v[2], maxv)), di_load(J.plane[2], i, J.wide), di_load(D.src[2], i, J.wide));
+        } else {
+            sum1 += round_to_grid(v[1], maxv);
+            sum2 += round_to_grid(v[2], maxv);
+        }
+    }
+    if (cs) {
+        const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
+        gain += di_gain(static_cast<int>(quantise_chroma420(sum1, maxv)), di_load(J.plane[1], ci, J.wide), di_load(D.src[1], ci, J.wide));
+        gain += di_gain(static_cast<int>(quantise_chroma420(sum2, maxv)), di_load(J.plane[2], ci, J.wide), di_load(D.src[2], ci, J.wide));
+    }
+    if (gain != 0) atomicAdd(D.acc + map_plane + static_cast<size_t>(ey) * D.w + ex, static_cast<unsigned long long>(gain));
+}
+
+hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    if (sinc8) hipLaunchKernelGGL(dsens_dep_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
+    else hipLaunchKernelGGL(dsens_dep_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
     return hipGetLastError();
 }
 

@@ -66,6 +66,7 @@ hipError_t launch_inter_coef8(int frame_type, int h, int w, const float* motion,
 hipError_t launch_inter_apply8(int frame_type, int h, int w, const int* gflow, const float* residue, const float* motion, const float* ref0,
                                const float* ref1, const void* coef, float* out, hipStream_t stream);
 hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
+hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
 hipError_t launch_spin(unsigned long long ticks, hipStream_t stream);
 // ccd_encode.hip
 size_t encode_contexts_lds_bytes(int dim);
@@ -82,6 +83,7 @@ hipError_t launch_latent_ingest(const IngestSeg* d_segs, const uint32_t* d_prefi
 hipError_t launch_dsens_apply(const DsensSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, hipStream_t stream);
 hipError_t launch_dsens_sse(const DsensPass* d_passes, const uint32_t* d_unit_prefix, const uint32_t* d_probe_prefix, int n_passes,
                             uint32_t n_units, uint32_t n_probes, int64_t* d_slab, hipStream_t stream);
+hipError_t launch_dsens_dep_final(const DsensDepGrid* d_grids, const uint32_t* d_prefix, int n_grids, uint32_t n_blocks, hipStream_t stream);
 // ccd_rdoq.hip: `rounds` times claim, select (and settle between two rounds), then the two phases of the reduce launch of one step
 hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
                             const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,

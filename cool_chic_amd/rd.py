@@ -80,6 +80,7 @@ class RdEvaluator:
         self._n_probe_slots = int(n_probe_slots)
         self._dd = None             # DistortionDeltas over the candidates, made when first asked for
         self._jobs: List[tuple] = []  # (arch, bytes_nn) per candidate, for it
+        self._dependents: List[List[dict]] = []  # per candidate: the add_dependent() calls, for it
         self._rdoq = None           # RdoqStep over the candidates, made by the first descend()
         self._caller_ptrs: List[Optional[List[int]]] = []  # the caller's device latents per candidate; None: host arrays
         self._dec = DecodeBatch(self.device)
@@ -127,8 +128,24 @@ class RdEvaluator:
         self._sources.append(_frame_planes(source, torch.device(f"cuda:{self.device}")))
         self._frames.append(source)
         self._jobs.append((arch, bytes_nn))
+        self._dependents.append([])
         self._caller_ptrs.append([int(p) for p in latents_or_ptrs] if on_device else None)
         return slot
+
+    def add_dependent(self, slot: int, frame_type: int, which: int, residue_ptr: int, motion_ptr: int, source_ptrs: Sequence[int],
+                      other_ref_ptrs: Optional[Sequence[int]] = None, global_flow: Sequence[int] = (0, 0, 0, 0),
+                      warp_filter_size: int = 8, owner=None) -> None:
+        """A P / B frame that predicts from candidate `slot` as its reference `which` (DistortionDeltas.add_dependent, DESIGN.md
+        4.16): recorded, and handed to the DistortionDeltas handle when evaluate(distortion_deltas=True) makes or extends it.
+        Changes nothing that evaluate() returns; dependent_delta_map() and cost_delta_map(dependents=True) read what it adds."""
+        if not 0 <= int(slot) < len(self._frames):
+            raise IndexError(f"no candidate {slot}")
+        dep = dict(frame_type=frame_type, which=which, residue_ptr=residue_ptr, motion_ptr=motion_ptr, source_ptrs=list(source_ptrs),
+                   other_ref_ptrs=None if other_ref_ptrs is None else list(other_ref_ptrs), global_flow=list(global_flow),
+                   warp_filter_size=warp_filter_size, owner=owner)
+        self._dependents[int(slot)].append(dep)
+        if self._dd is not None and int(slot) < len(self._dd):
+            self._dd.add_dependent(int(slot), **dep)
 
     def evaluate(self, lmbda: float, ms_ssim: bool = False, rate_deltas: bool = False, distortion_deltas: bool = False) -> List[Candidate]:
         """rate_deltas: the rate comes from EncodeBatch.measure_deltas, which leaves the same numbers and, for
@@ -156,6 +173,8 @@ class RdEvaluator:
                 f = self._frames[s]
                 self._dd.add(arch, bytes_nn, self._dec.latent_ptrs(s), [t.data_ptr() for t in self._sources[s]], f.bitdepth,
                              FRAME_DATA_TYPES.index(f.frame_data_type), owner=self._dec)
+                for dep in self._dependents[s]:
+                    self._dd.add_dependent(s, **dep)
             self._dd.run(st)
             self._dd.wait(st)
         out = []
@@ -176,17 +195,28 @@ class RdEvaluator:
             raise RuntimeError("no evaluate(distortion_deltas=True) has run")
         return self._dd.delta_map(slot, grid)
 
-    def cost_delta_map(self, slot: int, grid: int, lmbda: float) -> torch.Tensor:
+    def dependent_delta_map(self, slot: int, grid: int):
+        """After evaluate(distortion_deltas=True) of a candidate with add_dependent() frames: DistortionDeltas.dep_delta_map
+        (device, int64 [2][h][w]): what the move does to the squared error of the frames that predict from the candidate."""
+        if self._dd is None:
+            raise RuntimeError("no evaluate(distortion_deltas=True) has run")
+        return self._dd.dep_delta_map(slot, grid)
+
+    def cost_delta_map(self, slot: int, grid: int, lmbda: float, dependents: bool = False) -> torch.Tensor:
         """After evaluate(rate_deltas=True, distortion_deltas=True): what moving the latent (y, x) of `grid` by -1 (plane 0) or
         +1 (plane 1) does to the candidate's cost, the module's definition applied to the move - float64 [2][h][w] on the device,
 
             dD / (n_samples * (2^bitdepth - 1)^2) + lmbda * dBits / n_pixels
 
-        and +inf where the move leaves [-64, 63]."""
+        and +inf where the move leaves [-64, 63].  dependents=True: dD is the own delta plus dependent_delta_map's - the frames
+        of one video have one size, so one unit of squared error weighs the same in each - and +inf also at its conflicts."""
         dev = f"cuda:{self.device}"
         f = self._frames[slot]
         n_samples = sum(int(t.numel()) for t in self._sources[slot])
         dd = torch.as_tensor(self.distortion_delta_map(slot, grid), device=dev)
+        if dependents:
+            dep = torch.as_tensor(self.dependent_delta_map(slot, grid), device=dev)
+            dd = torch.where((dd == SENTINEL) | (dep == SENTINEL), torch.full_like(dd, SENTINEL), dd + dep)
         db = torch.as_tensor(self.rate_delta_map(slot, grid), device=dev).to(torch.float64)
         return move_cost_map(dd, db, n_samples, f.bitdepth, f.n_pixels, lmbda)
 

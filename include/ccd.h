@@ -592,6 +592,56 @@ int ccd_dsens_run(ccd_dsens* d, void* stream);
 int ccd_dsens_wait(ccd_dsens* d, void* stream);
 int64_t ccd_dsens_slot_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr);
 int ccd_dsens_passes(const ccd_dsens* d, int slot);
+/* Distortion deltas through the frames that predict from a moved one.  The planes of an I or P frame
+ * are references of other frames: a DEPENDENT F of slot `slot` is a P / B frame whose reference number `which` is the frame R
+ * that the slot decodes (intra, or one cool-chic of a P / B frame).  For every grid, position and sign
+ *
+ *     dDdep[s][g][y][x] = sum over the slot's dependents F of
+ *         SSE_F(reconstruct(F's residue, F's motion, references with R := planes decoded with latent[g][y][x] + s))
+ *       - SSE_F(reconstruct(F's residue, F's motion, references with R := planes as decoded))
+ *
+ * with reconstruct exactly ccd_inter_reconstruct and SSE_F the squared error of F's three integer planes against F's source.
+ * F's two float outputs, its other reference (B frames), its source and its global flow are given and held fixed: read at every
+ * run and never written, like `partner` (a caller that rewrote them between runs is followed).  F's size, bit depth and
+ * frame_data_type are the candidate's.  Only DIRECT dependents count: frames that predict from F are not followed.
+ * Layout int64 [2][h][w] per grid, INT64_MIN where v + s leaves [-64, 63], hyperlatent grids zeros with those sentinels: as the
+ * own map, which ccd_dsens_slot_map keeps handing out unchanged in meaning and in value (the slot's own frame only).
+ * The warp is not pointwise in the reference, so the change of one latent scatters into F where F's flows point.  A slot with
+ * dependents plans its passes with a wider stride, ccd_latent_probe_stride_margin(arch, grid, frame_data_type, margin) with
+ * margin = W - 1 (rgb, yuv444) or W + 2 (yuv420), W the widest window of its dependents' warps (2 bilinear, 4 bicubic, the filter
+ * size for sinc), on every grid; ccd_dsens_passes reports the new count.  With that margin one window never reads the regions of
+ * two latents of a pass, and a 4:2:0 quad does not either while the integer tap offsets of its four flows differ by at most 2
+ * per axis.  Where a unit (a luma sample, or a 4:2:0 quad with its chroma sample) still reads two regions its change cannot be
+ * split: the entries involved are CONFLICTS, INT64_MIN in the map like an illegal move, and ccd_dsens_slot_dep_conflicts counts
+ * the legal ones per grid.  A slot without dependents keeps its strides, passes and maps to the bit.
+ * ccd_dsens_add_dependent: CCD_ERR_ARG - before the device is touched - for a NULL argument (residue, motion, src[p] and, B frames,
+ * other_ref[p] included), a bad slot, a frame_type outside 1..2, `which` outside 0..1 or 1 for a P frame, a run in flight;
+ * CCD_ERR_VALUE for a filter size ccd_inter_reconstruct refuses, or a yuv420 candidate with an odd side.
+ * ccd_dsens_slot_dep_map / ccd_dsens_slot_dep_conflicts: as ccd_dsens_slot_map; CCD_ERR_ARG also for a slot without dependents.
+ * ccd_latent_probe_stride_margin (host only): ccd_latent_probe_stride with `margin` samples kept strictly between the regions
+ * of two latents a stride apart (margin 0: ccd_latent_probe_stride); CCD_ERR_ARG also for a negative margin. */
+typedef struct {
+    int32_t frame_type;        /* 1 P, 2 B: the DEPENDENT's */
+    int32_t which;             /* the candidate's frame is the dependent's reference 0 or 1 (P: 0) */
+    const float* residue;      /* DEVICE f32 [4|5][h][w] */
+    const float* motion;       /* DEVICE f32 [2|4][h][w] */
+    const void* other_ref[3];  /* B frames: DEVICE planes of the reference that is not the candidate */
+    const void* src[3];        /* DEVICE planes of the dependent's source */
+    int32_t global_flow[4];
+    int32_t warp_filter_size;
+} ccd_dsens_dependent;
+int ccd_dsens_add_dependent(ccd_dsens* d, int slot, const ccd_dsens_dependent* dep);
+int64_t ccd_dsens_slot_dep_map(const ccd_dsens* d, int slot, int grid, void** dev_ptr);
+int64_t ccd_dsens_slot_dep_conflicts(const ccd_dsens* d, int slot, int grid);
+int ccd_latent_probe_stride_margin(const ccd_cc_header* arch, int grid, int frame_data_type, int margin);
+/* Host only (tests): the lattice geometry of csrc/ccd_lattice.hpp on one axis given by its numbers: n latents over N samples,
+ * the footprint interval [lo, hi] around floor(i num / den), `even` the 4:2:0 widening of the regions.  ccd_debug_lattice_stride:
+ * the smallest stride that keeps `margin` samples between two regions (n when none does).  ccd_debug_lattice_hit: which member
+ * of the lattice (S, phase) has its region under the samples [a, b]: -1 none, its index for exactly one, -2 for more than one;
+ * *first and *count (may be NULL) the first member hit and how many.  CCD_ERR_ARG for numbers that describe no axis. */
+int ccd_debug_lattice_stride(int n, int N, int lo, int hi, uint32_t num, uint32_t den, int even, int margin);
+int ccd_debug_lattice_hit(int n, int N, int lo, int hi, uint32_t num, uint32_t den, int even, int S, int phase, int a, int b, int32_t* first,
+                          int32_t* count);
 
 /* ---- One RDOQ step: choose and apply +-1 moves that do not interact (ccd_rdoq.hip, ccd_rdoq_api.cpp) ----
  * From the two delta maps of every grid - the distortion deltas of ccd_dsens_slot_map and the rate deltas of

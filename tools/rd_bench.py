@@ -23,6 +23,11 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     latents (the stream's own with a seeded tenth moved by +-1, scored against the frame the own latents decode
                     to): evaluate() calls, distortion-delta runs, steps, moves, final D + lambda R and wall time of each way
 
+  --dependents      instead of the above: the distortion deltas THROUGH the frames that predict from a moved one (DESIGN.md section
+                    4.16) - the I frame of `vid5` and of synth.gop1080p(2) with their direct dependents: strides and passes with and
+                    without the margin, run + wait beside the same candidate without dependents (median of 5, min, max), the
+                    round's time split into float path, conversion, dep kernel and squared-error split, conflicts per grid
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -342,6 +347,116 @@ def measure_inter(stream_bytes, coding_index, runs, n_probe_slots):
     return res
 
 
+def measure_dependents(stream_bytes, runs, n_probe_slots):
+    """The I frame of a video stream as a candidate, alone and with the frames that predict from it directly as its dependents
+    (DESIGN.md 4.16), scored against the frames the stream decodes to: passes with and without the margin per grid, run + wait of
+    both handles (median, min, max), the round's time by stage, conflicts per grid."""
+    import ctypes as C
+    import os
+    import tempfile
+
+    from cool_chic_amd import DistortionDeltas
+    from cool_chic_amd._lib import check, lib
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+    from cool_chic_amd.bitstream.intercoding import _integer_planes
+    from cool_chic_amd.dsens import dependent_margin, probe_stride
+
+    st = torch.cuda.current_stream().cuda_stream
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    split = []
+    for k in range(len(structure)):
+        fh, ccs, rest = _split_frame(rest)
+        split.append((fh, ccs))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    dev = torch.device("cuda:0")
+    planes = {int(d): _integer_planes(fd, dev) for d, fd in frames.items()}
+    fh0, ccs0 = split[0]
+    assert fh0.get_value("frame_type") == "I"
+    display = int(structure[0]["display_order"])
+    bitdepth, fdt = fh0.get_value("bitdepth"), ["rgb", "yuv420", "yuv444"].index(fh0.get_value("frame_data_type"))
+    dec = DecodeBatch(0)
+    dec.add(ccs0[0][0].raw, ccs0[0][1], ccs0[0][2], 0, 0)
+    deps = []
+    for k in range(1, len(structure)):
+        refs = [int(r) for r in structure[k]["index_references"]]
+        fh, ccs = split[k]
+        n_refs = "IPB".index(fh.get_value("frame_type"))
+        if display not in refs[:n_refs]:
+            continue
+        first = len(dec)
+        for ch, nn, lat in ccs:
+            dec.add(ch.raw, nn, lat, 0, 0)
+        deps.append({"coding_index": k, "frame_type": n_refs, "which": refs[:n_refs].index(display), "slots": (first, first + 1),
+                     "other": planes[refs[1 - refs[:n_refs].index(display)]] if n_refs == 2 else None,
+                     "src": planes[int(structure[k]["display_order"])], "gflow": (list(fh.get_value("global_flow")) + [0] * 4)[:4],
+                     "taps": int(fh.get_value("warp_filter_size"))})
+    dec.run(st); dec.wait(st)
+    arch, nn = dec.header(0), dec.network_bytes(0)
+    src = planes[display]
+    stages = lib().ccd_dsens_debug_stages  # exported, not part of include/ccd.h
+    stages.restype, stages.argtypes = C.c_int, [C.c_void_p, C.c_int]
+
+    def timed(dd):
+        def step():
+            dd.run(st)
+            dd.wait(st)
+
+        step(); step()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step()
+            e1.record()
+            e1.synchronize()
+            out.append(e0.elapsed_time(e1))
+        return step, {"median": round(statistics.median(out), 3), "min": round(min(out), 3), "max": round(max(out), 3)}
+
+    m = dependent_margin(fdt, [d["taps"] for d in deps])
+    res = {"size": [int(v) for v in src[0].shape], "probe_slots": n_probe_slots, "dependents": [d["coding_index"] for d in deps], "margin": m,
+           "strides": {g: [probe_stride(arch, g, fdt), probe_stride(arch, g, fdt, margin=m)] for g in range(arch.n_grids)
+                       if not arch.is_hyperlatent[g]}}
+    alone = DistortionDeltas(0, n_probe_slots)
+    alone.add(arch, nn, dec.latent_ptrs(0), [t.data_ptr() for t in src], bitdepth, fdt, owner=(dec, src))
+    _, res["alone_run_wait_ms"] = timed(alone)
+    res["alone_passes"] = alone.passes(0)
+    own = [torch.as_tensor(alone.delta_map(0, g), device="cuda").clone() for g in range(arch.n_grids)]
+    alone.close()
+    dd = DistortionDeltas(0, n_probe_slots)
+    dd.add(arch, nn, dec.latent_ptrs(0), [t.data_ptr() for t in src], bitdepth, fdt, owner=(dec, src))
+    outs = []
+    for d in deps:
+        o = [torch.as_tensor(dec.output_device(s), device="cuda") for s in d["slots"]]
+        outs.append(o)
+        dd.add_dependent(0, d["frame_type"], d["which"], o[0].data_ptr(), o[1].data_ptr(), [t.data_ptr() for t in d["src"]],
+                         None if d["other"] is None else [t.data_ptr() for t in d["other"]], d["gflow"], d["taps"], owner=(o, planes))
+    step, res["run_wait_ms"] = timed(dd)
+    res["passes"] = dd.passes(0)
+    rounds = -(-res["passes"] // n_probe_slots)
+    res["rounds"] = rounds
+    res["conflicts"] = [dd.dep_conflicts(0, g) for g in range(arch.n_grids)]
+    assert all(torch.equal(torch.as_tensor(dd.delta_map(0, g), device="cuda"), own[g]) for g in range(arch.n_grids))
+    # every frame is its own source and the base planes are the decoded ones: no move lowers a dependent's squared error
+    dm = torch.as_tensor(dd.dep_delta_map(0, 0), device="cuda")
+    assert int((dm[dm != -2 ** 63] < 0).sum()) == 0
+    for label, mask in (("float_path", 1), ("conversion", 8), ("dep_kernel", 16), ("sse", 4)):
+        check(stages(dd._h, mask), "ccd_dsens_debug_stages")
+        res[label + "_ms_per_round"] = round(event_ms(step, runs) / rounds, 5)
+    check(stages(dd._h, 31), "ccd_dsens_debug_stages")
+    res["ms_per_round"] = round(res["run_wait_ms"]["median"] / rounds, 5)
+    dd.close()
+    dec.close()
+    return res
+
+
 def measure_inter_descent(stream_bytes, coding_index, runs, lmbda, rounds, grids, max_steps):
     """InterRdEvaluator.descend on one P / B frame, alternating and joint, each from the same perturbed latents on a fresh
     evaluator: one unmeasured descent, then `runs` timed ones (host wall time around descend(), the device idle before and
@@ -427,7 +542,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=8, help="with --inter --joint: rounds of selection per step")
     ap.add_argument("--grids", default="0,1,2", help="with --inter --joint: the grids that may move, in both cool-chics")
     ap.add_argument("--max-steps", type=int, default=400, help="with --inter --joint: steps of a descent at most")
+    ap.add_argument("--dependents", action="store_true", help="time the distortion deltas through the direct dependents of an I frame instead")
     a = ap.parse_args()
+    if a.dependents:
+        runs = min(a.runs, 5)
+        line = {"tool": "rd_bench --dependents", "runs": runs}
+        if "vid5" in a.inter_sets.split(","):
+            line["vid5_I"] = measure_dependents(synth._golden("vid5")[0], runs, a.probe_slots)
+        if "1080p" in a.inter_sets.split(","):
+            line["gop1080p_I"] = measure_dependents(synth.gop1080p(2)[0], runs, a.probe_slots)
+        print(json.dumps(line))
+        return
     if a.inter and a.joint:
         line = {"tool": "rd_bench --inter --joint", "runs": a.runs}
         args = (a.runs, a.lmbda, a.rounds, [int(g) for g in a.grids.split(",") if g != ""], a.max_steps)
