@@ -22,6 +22,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    rdoq.RdoqStep, RdEvaluator.descend
     (the same for the two cool-chics of a P / B frame, scored through the reconstruction against its references)
                                                    DistortionDeltas.add_inter, rd_inter.InterRdEvaluator
+    (intra frames and the residues of the frames that predict from them in one step, claims following the flows)
+                                                   RdoqStep.follow, rd_gop.GopDescent
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -37,6 +39,10 @@ def __getattr__(name):
         from .rd_inter import InterRdEvaluator
 
         return InterRdEvaluator
+    if name == "GopDescent":
+        from .rd_gop import GopDescent
+
+        return GopDescent
     if name == "DistortionDeltas":
         from .dsens import DistortionDeltas
 

@@ -99,6 +99,11 @@ class DsensDependent(C.Structure):
                 ("other_ref", C.c_void_p * 3), ("src", C.c_void_p * 3), ("global_flow", C.c_int32 * 4), ("warp_filter_size", C.c_int32)]
 
 
+class RdoqFollow(C.Structure):
+    _fields_ = [("frame_type", C.c_int32), ("which", C.c_int32), ("motion", C.c_void_p), ("global_flow", C.c_int32 * 4),
+                ("warp_filter_size", C.c_int32), ("target", C.c_int32), ("frozen", C.c_int32)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -233,6 +238,13 @@ SIGNATURES = {
     "ccd_rdoq_slot_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RdoqResult)]),
     "ccd_rdoq_slot_open": (C.c_int64, [C.c_void_p, C.c_int]),
     "ccd_rdoq_slot_moves": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_max_follows": (C.c_int, []),
+    "ccd_rdoq_lane_cells": (C.c_int, []),
+    "ccd_rdoq_follow": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RdoqFollow)]),
+    "ccd_rdoq_set_dep_maps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_slot_dep_sse": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "ccd_rdoq_slot_reach": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_rdoq_slot_flow_boxes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

@@ -238,6 +238,37 @@ struct RdoqSlot {
 // What one workgroup of the reduce launch leaves for a chunk of kRdoqChunk latents of one grid.
 struct RdoqPartial { int64_t n_candidates, n_moves, d_sse; double d_bits; int64_t n_open; };
 
+// ---- claims that follow the flows into the dependent frames (ccd_rdoq_follow).  Everything a following step
+// needs beyond RdoqGrid / RdoqSlot sits in tables of its own, entry for entry beside those, so that the kernels of a handle
+// without follows read what they always read.
+constexpr int kRdoqMaxFollows = 4;       // follows of one slot at most (ccd_rdoq_max_follows)
+// A reach table: per cell c of the followed slot's raster four words, all of them minima over the cells C = (Y, X) of the
+// dependent whose samples can read c: {min Y, min X, ~max Y, ~max X}.  All ones: nobody reads c.  One memset resets it.
+constexpr int kRdoqReachWords = 4;
+// One follow as rdoq_reach_kernel (ccd_inter.hip) sees it: the dependent F's flows into its reference `which`.
+struct RdoqReachJob {
+    const float* motion;     // F's motion output [2 | 4][H][W], read at every step
+    uint32_t* reach;         // [cells_h][cells_w][kRdoqReachWords]
+    int32_t which, H, W, n_taps;
+    int32_t gx, gy;          // F's global flow for reference `which`
+    int32_t cells_h, cells_w;
+};
+struct RdoqFollowRef {
+    const uint32_t* reach;       // the follow's reach table
+    unsigned long long* raster;  // the rasters of the follow's target (its group's)
+    uint8_t* taken;
+};
+struct RdoqSlotX {
+    int32_t n_follows;
+    int32_t comp_first, comp_n;  // the slot's component: its entries of the tables of first uids / slots, uids ascending
+    int32_t pad;
+    RdoqFollowRef follow[kRdoqMaxFollows];
+};
+struct RdoqGridX {
+    const int64_t* dd_dep;              // [2][h][w] the dependent map (ccd_rdoq_set_dep_maps), nullptr: none
+    RdoqBox* fbox[kRdoqMaxFollows];     // [h][w] per follow: the flow box of every latent; top > bottom: empty
+};
+
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.
 struct UpsampleLevel {

@@ -556,6 +556,58 @@ hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix,
     return hipGetLastError();
 }
 
+// ---- where the samples of a dependent frame read its reference, in cells of the RDOQ claim raster (ccd_rdoq_follow; DESIGN.md
+// 4.17).  A job is one follow: the dependent F's flows into its reference `which`.  A workgroup is one wave and one cell C of F,
+// a lane per luma sample of the cell: (a) the interval of reference indices the sample's window reads per axis (ic_window_axis,
+// as dsens_dep_kernel), (b) a wave reduction to the bounding rectangle of the cell's windows - inside the picture already, the
+// indices are clamped - (c) the lanes over the reference cells c the rectangle meets: reach[c] grows to hold C, four 32-bit
+// vector atomicMin per cell (the two upper bounds are kept complemented, so that all four are minima and all ones is "nobody").
+// Any order of the atomics leaves the same words.  No LDS, no waits, no spinning.
+template <int NT>
+__global__ __launch_bounds__(64) void rdoq_reach_kernel(const RdoqReachJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+    const int j = entry_of(prefix, n_jobs, blockIdx.x);
+    const RdoqReachJob& J = jobs[j];  // (uniform: scalar loads)
+    const uint32_t local = blockIdx.x - prefix[j], cw = static_cast<uint32_t>(J.cells_w);
+    const uint32_t Cy = local / cw, Cx = local - Cy * cw;
+    if (Cy >= static_cast<uint32_t>(J.cells_h)) return;
+    const uint32_t lane = threadIdx.x;
+    const int y = static_cast<int>(Cy) * kRdoqCell + static_cast<int>(lane) / kRdoqCell;
+    const int x = static_cast<int>(Cx) * kRdoqCell + static_cast<int>(lane) % kRdoqCell;
+    int ya = INT32_MAX, yb = -1, xa = INT32_MAX, xb = -1;
+    if (y < J.H && x < J.W) {  // (the sample (0, 0) of a cell always is: no cell is empty)
+        const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
+        ic_window_axis<NT>(J.n_taps, J.motion[(2 * J.which + 1) * plane + i], y, J.H, J.gy, ya, yb);
+        ic_window_axis<NT>(J.n_taps, J.motion[(2 * J.which) * plane + i], x, J.W, J.gx, xa, xb);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ya = min(ya, __shfl_xor(ya, off, 64)); xa = min(xa, __shfl_xor(xa, off, 64));
+        yb = max(yb, __shfl_xor(yb, off, 64)); xb = max(xb, __shfl_xor(xb, off, 64));
+    }
+    if (yb < ya || xb < xa) return;
+    // the indices are ic_tap_index's, inside [0, n - 1]; the bounds of the table are this kernel's to keep all the same
+    const uint32_t top = min(static_cast<uint32_t>(max(ya, 0) / kRdoqCell), static_cast<uint32_t>(J.cells_h - 1));
+    const uint32_t left = min(static_cast<uint32_t>(max(xa, 0) / kRdoqCell), cw - 1);
+    const uint32_t bottom = min(static_cast<uint32_t>(yb / kRdoqCell), static_cast<uint32_t>(J.cells_h - 1));
+    const uint32_t right = min(static_cast<uint32_t>(xb / kRdoqCell), cw - 1);
+    const uint32_t bw = right - left + 1, n = (bottom - top + 1) * bw;
+    for (uint32_t t = lane; t < n; t += 64) {
+        const uint32_t r = t / bw, q = t - r * bw;
+        uint32_t* w = J.reach + (static_cast<size_t>(top + r) * cw + left + q) * kRdoqReachWords;
+        atomicMin(w, Cy);
+        atomicMin(w + 1, Cx);
+        atomicMin(w + 2, ~Cy);
+        atomicMin(w + 3, ~Cx);
+    }
+}
+
+hipError_t launch_rdoq_reach(const RdoqReachJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    if (sinc8) hipLaunchKernelGGL(rdoq_reach_kernel<8>, dim3(n_blocks), dim3(64), 0, stream, d_jobs, d_prefix, n_jobs);
+    else hipLaunchKernelGGL(rdoq_reach_kernel<0>, dim3(n_blocks), dim3(64), 0, stream, d_jobs, d_prefix, n_jobs);
+    return hipGetLastError();
+}
+
 // ---- a kernel that only takes time: ccd_runtime.cpp measures with it which of the library's side streams run concurrently
 __global__ void spin_kernel(unsigned long long ticks) {
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();

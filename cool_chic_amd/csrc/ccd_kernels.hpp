@@ -84,9 +84,28 @@ hipError_t launch_dsens_apply(const DsensSeg* d_segs, const uint32_t* d_prefix, 
 hipError_t launch_dsens_sse(const DsensPass* d_passes, const uint32_t* d_unit_prefix, const uint32_t* d_probe_prefix, int n_passes,
                             uint32_t n_units, uint32_t n_probes, int64_t* d_slab, hipStream_t stream);
 hipError_t launch_dsens_dep_final(const DsensDepGrid* d_grids, const uint32_t* d_prefix, int n_grids, uint32_t n_blocks, hipStream_t stream);
-// ccd_rdoq.hip: `rounds` times claim, select (and settle between two rounds), then the two phases of the reduce launch of one step
+// ccd_inter.hip: the reach tables of the follows of one tap-count class
+hipError_t launch_rdoq_reach(const RdoqReachJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
+// What a step of a handle with follows or dependent maps launches beyond the tables of launch_rdoq_step (all device pointers).
+struct RdoqFollowLaunch {
+    const RdoqGridX* gx;            // beside the grid table
+    const RdoqSlotX* sx;            // beside the slot table
+    const uint32_t* comp_uid;       // first uids of the slots, component by component, ascending inside one
+    const int32_t* comp_slot;       // ... and their slots
+    const RdoqReachJob* reach_jobs[2];  // [0] run-time taps, [1] sinc-8
+    const uint32_t* reach_prefix[2];
+    int n_reach[2];
+    uint32_t reach_blocks[2];
+    void* reach_mem;                // every reach table of the handle, one block
+    size_t reach_bytes;
+    int64_t* partial_dep;           // [n_chunks]
+    int64_t* dep_out;               // [n_slots]
+    int stages;                     // ccd_rdoq_debug_stages: 1 memset + reach, 2 flow boxes, 4 rounds + sums (tools/rd_bench.py)
+};
+// ccd_rdoq.hip: `rounds` times claim, select (and settle between two rounds), then the two phases of the reduce launch of one step.
+// follow != nullptr: the reach tables and the flow boxes first, then the following variants of the same launches.
 hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
                             const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
                             uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
-                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream);
+                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream, const RdoqFollowLaunch* follow = nullptr);
 }  // namespace ccd

@@ -42,6 +42,17 @@
 // wave stores the rasters (RdoqSlot::owns_raster), so no word is written by two workgroups.  The follower's own raster block
 // stays as ccd_rdoq_add left it and is never read.
 //
+// Components (ccd_rdoq_follow).  A candidate of a following slot claims its CLAIM SET: its own box in its group's
+// rasters and, per follow, its flow box in the rasters of the follow's target (RdoqSlotX / RdoqGridX, tables beside RdoqSlot /
+// RdoqGrid that only the *_follow kernels read).  The slots that links or follows connect share one numbering of their latents,
+// so a key still names one candidate wherever it stands.  The rasters of a group are now reached from every slot of its
+// component, and a word still sees one kind of access per launch: in claim, atomicMin on claim words and plain loads of taken,
+// from any slot of the component; in select, plain loads of claim words; in settle, one lane per cell of the rasters' OWNER,
+// which loads the claim word, looks its owner up by uid over the component's slots (a bisection of the component's first uids;
+// the pick bytes it reads were last written by select, an earlier launch) and stores the cell's two words; in phase 1 of the
+// reduce launch the owner's wave alone stores the rasters.  The reach tables see atomics in the reach launch and loads in the
+// flow-box launch; a flow-box entry has one writer there and only readers afterwards.  Launches are ordered by their stream.
+//
 // Sums: integers in any order; dBits in float64 in an order that is a function of the geometry alone (a lane adds its latents
 // in ascending order, a fixed shuffle tree adds the lanes, chunks and grids are added in ascending order).  No float atomics.
 #include <hip/hip_runtime.h>
@@ -64,15 +75,25 @@ struct Move { int pick; int s; unsigned long long key; };  // pick: 0 no candida
 __device__ __forceinline__ bool is_open(uint32_t pick) { return pick != 0 && !(pick & (kRdoqSelected | kRdoqBlocked)); }
 
 // Rule steps 1-3 for latent i of grid G.  Separate roundings of the two products and of the sum: what numpy float64 does.
-__device__ __forceinline__ Move best_move(const RdoqGrid& G, const RdoqSlot& S, uint32_t i) {
+// kFollow: the distortion is the own delta plus the dependent map's (X->dd_dep, where given), and a move exists in neither where
+// either map holds the sentinel.
+template <bool kFollow>
+__device__ __forceinline__ Move best_move(const RdoqGrid& G, const RdoqSlot& S, const RdoqGridX* X, uint32_t i) {
     const int v = G.lat[i];
     double c64[2];
     bool exists[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int64_t dd = G.dd ? G.dd[static_cast<size_t>(k) * G.n + i] : 0;
+        int64_t dd = G.dd ? G.dd[static_cast<size_t>(k) * G.n + i] : 0;
         const float db = G.db[static_cast<size_t>(k) * G.n + i];
         exists[k] = in_alphabet(v) && in_alphabet(v + 2 * k - 1) && dd != INT64_MIN && isfinite(db);
+        if constexpr (kFollow) {
+            if (X->dd_dep) {
+                const int64_t dep = X->dd_dep[static_cast<size_t>(k) * G.n + i];
+                exists[k] = exists[k] && dep != INT64_MIN;
+                dd = static_cast<int64_t>(static_cast<uint64_t>(dd) + static_cast<uint64_t>(dep));
+            }
+        }
         c64[k] = __dadd_rn(__dmul_rn(static_cast<double>(dd), S.kD), __dmul_rn(static_cast<double>(db), S.kR));
     }
     const float c32[2] = {static_cast<float>(c64[0]), static_cast<float>(c64[1])};
@@ -99,17 +120,67 @@ __device__ __forceinline__ Cells cells_of(const RdoqBox b, const RdoqSlot& S) {
     return c;
 }
 
+// A flow box in cells of the target's raster (congruent with the slot's own: ccd_rdoq_follow checked); empty: no cell.
+__device__ __forceinline__ Cells flow_cells(const RdoqBox b, const RdoqSlot& S) {
+    if (b.top > b.bottom || b.left > b.right) return Cells{0, 0, 0, 0, 0};
+    return cells_of(b, S);
+}
+// The cells of a rectangle: all of them in this lane (kWave == false) or dealt out over the lanes of the wave.
+template <bool kWave, typename Fn>
+__device__ __forceinline__ void walk_cells(const Cells& c, uint32_t cells_w, uint32_t lane, Fn&& fn) {
+    if (kWave) {
+        for (uint32_t t = lane; t < c.n; t += 64) {
+            const uint32_t r = t / c.bw, q = t - r * c.bw;
+            fn(static_cast<size_t>(c.top + r) * cells_w + c.left + q);
+        }
+    } else {
+        for (uint32_t r = 0; r < c.bh; ++r)
+            for (uint32_t q = 0; q < c.bw; ++q) fn(static_cast<size_t>(c.top + r) * cells_w + c.left + q);
+    }
+}
+// The part of latent i's claim set that lies in the rasters of its follows' targets: is a cell of it taken,
+// claim every cell, does the key stand in every cell.  In a wave the answer is this lane's share.
+template <bool kWave>
+__device__ __forceinline__ bool flow_taken(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane) {
+    bool hit = false;
+    for (int k = 0; k < SX.n_follows; ++k) {
+        const uint8_t* taken = SX.follow[k].taken;
+        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { hit = hit || taken[at] != 0; });
+    }
+    return hit;
+}
+template <bool kWave>
+__device__ __forceinline__ void flow_claim(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane, unsigned long long key) {
+    for (int k = 0; k < SX.n_follows; ++k) {
+        unsigned long long* raster = SX.follow[k].raster;
+        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { atomicMin(&raster[at], key); });
+    }
+}
+template <bool kWave>
+__device__ __forceinline__ bool flow_mine(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane, unsigned long long key) {
+    bool mine = true;
+    for (int k = 0; k < SX.n_follows; ++k) {
+        const unsigned long long* raster = SX.follow[k].raster;
+        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { mine = mine && raster[at] == key; });
+    }
+    return mine;
+}
+
 // kSelect == false: claim.  kSelect == true: select and apply.  Round 0 (kFirst) finds the candidates; a later round reads their
 // state from the pick bytes and forms an open candidate's key again: its latent and the maps are what they were.
-template <bool kSelect, bool kFirst>
+// kFollow: "the box" is the claim set - the own box and, in the rasters of the follows' targets, the flow boxes (gx, sx: the
+// tables beside grids and slots; null and never read otherwise).
+template <bool kSelect, bool kFirst, bool kFollow>
 __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                           const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix, int n_grids,
-                                          uint32_t n_lane_blocks) {
+                                          uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx, const RdoqSlotX* __restrict__ sx) {
     const uint32_t lane = threadIdx.x;
     if (blockIdx.x < n_lane_blocks) {  // a lane per latent
         const int e = entry_of(lane_prefix, n_grids, blockIdx.x);
         const RdoqGrid& G = grids[e];
         const RdoqSlot& S = slots[G.slot];
+        const RdoqGridX* X = kFollow ? gx + e : nullptr;
+        const RdoqSlotX* SX = kFollow ? sx + G.slot : nullptr;
         const uint32_t i = (blockIdx.x - lane_prefix[e]) * 64u + lane;
         if (i >= G.n) return;
         const Cells c = cells_of(G.box[i], S);
@@ -118,30 +189,34 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
             Move m;
             uint32_t pick;
             if (kFirst) {
-                m = best_move(G, S, i);
+                m = best_move<kFollow>(G, S, X, i);
                 pick = static_cast<uint32_t>(m.pick);
             } else {
                 pick = G.pick[i];
                 if (!is_open(pick)) return;
-                m = best_move(G, S, i);
+                m = best_move<kFollow>(G, S, X, i);
             }
             bool blocked = false;
             if (!kFirst)  // (no cell is taken before the first round)
                 for (uint32_t r = 0; r < c.bh; ++r)
                     for (uint32_t q = 0; q < c.bw; ++q) blocked = blocked || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
+            if constexpr (kFollow && !kFirst) blocked = blocked || flow_taken<false>(*X, *SX, S, i, lane);
             if (blocked) pick |= kRdoqBlocked;
             if (kFirst || blocked) G.pick[i] = static_cast<uint8_t>(pick);
             if (pick && !blocked)
                 for (uint32_t r = 0; r < c.bh; ++r)
                     for (uint32_t q = 0; q < c.bw; ++q) atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
+            if constexpr (kFollow)
+                if (pick && !blocked) flow_claim<false>(*X, *SX, S, i, lane, m.key);
         } else {
             int s = 0;
             const uint32_t pick = G.pick[i];
             if (is_open(pick)) {
-                const Move m = best_move(G, S, i);
+                const Move m = best_move<kFollow>(G, S, X, i);
                 bool mine = true;
                 for (uint32_t r = 0; r < c.bh; ++r)
                     for (uint32_t q = 0; q < c.bw; ++q) mine = mine && S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] == m.key;
+                if constexpr (kFollow) mine = mine && flow_mine<false>(*X, *SX, S, i, lane, m.key);
                 if (mine) {
                     s = m.s;
                     G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
@@ -157,6 +232,8 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
     const int e = entry_of(big_prefix, n_grids, u);
     const RdoqGrid& G = grids[e];
     const RdoqSlot& S = slots[G.slot];
+    const RdoqGridX* X = kFollow ? gx + e : nullptr;
+    const RdoqSlotX* SX = kFollow ? sx + G.slot : nullptr;
     const uint32_t i = G.big[u - big_prefix[e]];
     if (i >= G.n) return;
     const Cells c = cells_of(G.box[i], S);
@@ -165,12 +242,12 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
         Move m;
         uint32_t pick;
         if (kFirst) {
-            m = best_move(G, S, i);
+            m = best_move<kFollow>(G, S, X, i);
             pick = static_cast<uint32_t>(m.pick);
         } else {
             pick = G.pick[i];
             if (!is_open(pick)) return;  // (the same in every lane)
-            m = best_move(G, S, i);
+            m = best_move<kFollow>(G, S, X, i);
         }
         bool hit = false;
         if (!kFirst)  // (no cell is taken before the first round)
@@ -178,6 +255,7 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
                 const uint32_t r = t / c.bw, q = t - r * c.bw;
                 hit = hit || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
             }
+        if constexpr (kFollow && !kFirst) hit = hit || flow_taken<true>(*X, *SX, S, i, lane);
         const bool blocked = __any(hit);
         if (blocked) pick |= kRdoqBlocked;
         if (lane == 0 && (kFirst || blocked)) G.pick[i] = static_cast<uint8_t>(pick);
@@ -186,16 +264,19 @@ __device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, co
                 const uint32_t r = t / c.bw, q = t - r * c.bw;
                 atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
             }
+        if constexpr (kFollow)
+            if (pick && !blocked) flow_claim<true>(*X, *SX, S, i, lane, m.key);
     } else {
         int s = 0;
         const uint32_t pick = G.pick[i];
         if (is_open(pick)) {  // (the same in every lane)
-            const Move m = best_move(G, S, i);
+            const Move m = best_move<kFollow>(G, S, X, i);
             bool mine = true;
             for (uint32_t t = lane; t < c.n; t += 64) {
                 const uint32_t r = t / c.bw, q = t - r * c.bw;
                 mine = mine && S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] == m.key;
             }
+            if constexpr (kFollow) mine = mine && flow_mine<true>(*X, *SX, S, i, lane, m.key);
             if (__all(mine)) s = m.s;
             if (lane == 0 && s) {
                 G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
@@ -211,22 +292,92 @@ template <bool kFirst>
 __global__ __launch_bounds__(64) void rdoq_claim_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                         const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
                                                         int n_grids, uint32_t n_lane_blocks) {
-    step_body<false, kFirst>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
+    step_body<false, kFirst, false>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, nullptr, nullptr);
 }
 
 template <bool kFirst>
 __global__ __launch_bounds__(64) void rdoq_select_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
                                                          const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
                                                          int n_grids, uint32_t n_lane_blocks) {
-    step_body<true, kFirst>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks);
+    step_body<true, kFirst, false>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, nullptr, nullptr);
+}
+
+// The following variants: the same bodies over claim sets.
+template <bool kFirst>
+__global__ __launch_bounds__(64) void rdoq_claim_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                               const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
+                                                               int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
+                                                               const RdoqSlotX* __restrict__ sx) {
+    step_body<false, kFirst, true>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
+}
+template <bool kFirst>
+__global__ __launch_bounds__(64) void rdoq_select_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                                const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
+                                                                int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
+                                                                const RdoqSlotX* __restrict__ sx) {
+    step_body<true, kFirst, true>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
+}
+
+// The flow box of every latent of a following slot, per follow: the bounding rectangle of reach[c] over the cells c of the
+// latent's own box, from the reach tables the launch before this one built.  The split of the step's kernels: a
+// lane per latent with a box of up to kRdoqLaneCells cells, a wave per latent of the `big` lists.  Every entry has one writer.
+__device__ __forceinline__ void reach_min(uint4& m, const uint32_t* __restrict__ reach, size_t at) {
+    const uint4 w = reinterpret_cast<const uint4*>(reach)[at];
+    m.x = min(m.x, w.x); m.y = min(m.y, w.y); m.z = min(m.z, w.z); m.w = min(m.w, w.w);
+}
+__device__ __forceinline__ RdoqBox flow_box_of(const uint4 m) {
+    RdoqBox b = {0xffff, 0xffff, 0, 0};  // empty
+    if (m.x != ~0u) {
+        b.top = static_cast<uint16_t>(m.x); b.left = static_cast<uint16_t>(m.y);
+        b.bottom = static_cast<uint16_t>(~m.z); b.right = static_cast<uint16_t>(~m.w);
+    }
+    return b;
+}
+__global__ __launch_bounds__(64) void rdoq_flowbox_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                          const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
+                                                          int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
+                                                          const RdoqSlotX* __restrict__ sx) {
+    const uint32_t lane = threadIdx.x;
+    const bool wave = blockIdx.x >= n_lane_blocks;
+    const uint32_t u = blockIdx.x - n_lane_blocks;
+    const int e = wave ? entry_of(big_prefix, n_grids, u) : entry_of(lane_prefix, n_grids, blockIdx.x);
+    const RdoqGrid& G = grids[e];
+    const RdoqSlot& S = slots[G.slot];
+    const RdoqSlotX& SX = sx[G.slot];
+    const RdoqGridX& X = gx[e];
+    if (SX.n_follows == 0) return;
+    const uint32_t i = wave ? G.big[u - big_prefix[e]] : (blockIdx.x - lane_prefix[e]) * 64u + lane;
+    if (i >= G.n) return;
+    const Cells c = cells_of(G.box[i], S);
+    if (!wave && c.n > kRdoqLaneCells) return;  // a wave's
+    for (int k = 0; k < SX.n_follows; ++k) {
+        uint4 m = make_uint4(~0u, ~0u, ~0u, ~0u);
+        const uint32_t* reach = SX.follow[k].reach;
+        if (wave) {
+            walk_cells<true>(c, S.cells_w, lane, [&](size_t at) { reach_min(m, reach, at); });
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                m.x = min(m.x, __shfl_xor(m.x, off, 64)); m.y = min(m.y, __shfl_xor(m.y, off, 64));
+                m.z = min(m.z, __shfl_xor(m.z, off, 64)); m.w = min(m.w, __shfl_xor(m.w, off, 64));
+            }
+            if (lane == 0) X.fbox[k][i] = flow_box_of(m);
+        } else {
+            walk_cells<false>(c, S.cells_w, lane, [&](size_t at) { reach_min(m, reach, at); });
+            X.fbox[k][i] = flow_box_of(m);
+        }
+    }
 }
 
 // Between two rounds: 64 cells of one raster, a lane each (a follower has no cell blocks: its leader's lanes settle the pair's
 // raster).  The low half of a claimed word is its owner's uid; the owner claimed in this round, so a selected owner was selected
 // in this round and owns every cell of its box.  In a pair the owner is a latent of either slot: the follower's uids begin where
 // the leader's end.
-__global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                         const uint32_t* __restrict__ cell_prefix, int n_slots) {
+// kFollow: the owner is a latent of any slot of the raster owner's component; its slot is the last entry of the component's
+// table of first uids that is not above the uid (a bisection; the partner test is its two-slot case).
+template <bool kFollow>
+__device__ __forceinline__ void settle_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                            const uint32_t* __restrict__ cell_prefix, int n_slots, const RdoqSlotX* __restrict__ sx,
+                                            const uint32_t* __restrict__ comp_uid, const int32_t* __restrict__ comp_slot) {
     const int k = entry_of(cell_prefix, n_slots, blockIdx.x);
     const RdoqSlot& S = slots[k];
     const size_t cell = static_cast<size_t>(blockIdx.x - cell_prefix[k]) * 64u + threadIdx.x;
@@ -235,13 +386,30 @@ __global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restr
     if (key == ~0ull) return;  // nobody claimed the cell
     const uint32_t uid = static_cast<uint32_t>(key);
     const RdoqSlot* T = &S;  // the slot of the uid
-    if (S.partner >= 0 && grids[slots[S.partner].first_grid].first <= uid) T = &slots[S.partner];
+    if constexpr (kFollow) {
+        int lo = sx[k].comp_first, hi = lo + sx[k].comp_n - 1;  // comp_uid[lo] == 0 <= uid
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (comp_uid[mid] <= uid) lo = mid; else hi = mid - 1;
+        }
+        T = &slots[comp_slot[lo]];
+    } else if (S.partner >= 0 && grids[slots[S.partner].first_grid].first <= uid) T = &slots[S.partner];
     int g = 0;  // the grid of the uid: first[] ascends over the slot's few grids
     while (g + 1 < T->n_grids && grids[T->first_grid + g + 1].first <= uid) ++g;
     const RdoqGrid& G = grids[T->first_grid + g];
     const uint32_t i = uid - G.first;
     if (i < G.n && (G.pick[i] & kRdoqSelected)) S.taken[cell] = 1;
     S.raster[cell] = ~0ull;
+}
+__global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                         const uint32_t* __restrict__ cell_prefix, int n_slots) {
+    settle_body<false>(grids, slots, cell_prefix, n_slots, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void rdoq_settle_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                                const uint32_t* __restrict__ cell_prefix, int n_slots,
+                                                                const RdoqSlotX* __restrict__ sx, const uint32_t* __restrict__ comp_uid,
+                                                                const int32_t* __restrict__ comp_slot) {
+    settle_body<true>(grids, slots, cell_prefix, n_slots, sx, comp_uid, comp_slot);
 }
 
 __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
@@ -255,12 +423,16 @@ __device__ __forceinline__ double wave_sum_f64(double v) {  // a fixed tree: lan
     return v;
 }
 
-__global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                         const uint32_t* __restrict__ chunk_prefix, int n_grids,
-                                                         RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
-                                                         int64_t* __restrict__ open, int phase) {
+// kFollow: the chosen entries of the dependent maps are summed beside d_sse (integers, any order): partial_dep per chunk, then
+// dep_out per slot.
+template <bool kFollow>
+__device__ __forceinline__ void reduce_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                            const uint32_t* __restrict__ chunk_prefix, int n_grids, RdoqPartial* __restrict__ partial,
+                                            ccd_rdoq_result* __restrict__ results, int64_t* __restrict__ open, int phase,
+                                            const RdoqGridX* __restrict__ gx, int64_t* __restrict__ partial_dep, int64_t* __restrict__ dep_out) {
     const uint32_t lane = threadIdx.x;
     RdoqPartial acc = {0, 0, 0, 0.0, 0};
+    int64_t dep = 0;
     if (phase == 0) {
         const int e = entry_of(chunk_prefix, n_grids, blockIdx.x);
         const RdoqGrid& G = grids[e];
@@ -276,11 +448,18 @@ __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restr
             acc.n_moves += 1;
             acc.d_sse += G.dd ? G.dd[at] : 0;
             acc.d_bits = __dadd_rn(acc.d_bits, static_cast<double>(G.db[at]));
+            if constexpr (kFollow)
+                if (gx[e].dd_dep) dep += gx[e].dd_dep[at];
         }
     } else {
         const RdoqSlot& S = slots[blockIdx.x];
         ccd_rdoq_result& R = results[blockIdx.x];
         RdoqPartial total = {0, 0, 0, 0.0, 0};
+        if constexpr (kFollow) {
+            for (uint32_t c = chunk_prefix[S.first_grid] + lane; c < chunk_prefix[S.first_grid + S.n_grids]; c += 64) dep += partial_dep[c];
+            dep = wave_sum_i64(dep);
+            if (lane == 0) dep_out[blockIdx.x] = dep;
+        }
         for (int g = 0; g < S.n_grids; ++g) {
             const int e = S.first_grid + g;
             acc = {0, 0, 0, 0.0, 0};
@@ -330,15 +509,59 @@ __global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restr
     acc.d_bits = wave_sum_f64(acc.d_bits);
     acc.n_open = wave_sum_i64(acc.n_open);
     if (lane == 0) partial[blockIdx.x] = acc;
+    if constexpr (kFollow) {
+        dep = wave_sum_i64(dep);
+        if (lane == 0) partial_dep[blockIdx.x] = dep;
+    }
+}
+__global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                         const uint32_t* __restrict__ chunk_prefix, int n_grids,
+                                                         RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
+                                                         int64_t* __restrict__ open, int phase) {
+    reduce_body<false>(grids, slots, chunk_prefix, n_grids, partial, results, open, phase, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void rdoq_reduce_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                                const uint32_t* __restrict__ chunk_prefix, int n_grids,
+                                                                RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
+                                                                int64_t* __restrict__ open, int phase, const RdoqGridX* __restrict__ gx,
+                                                                int64_t* __restrict__ partial_dep, int64_t* __restrict__ dep_out) {
+    reduce_body<true>(grids, slots, chunk_prefix, n_grids, partial, results, open, phase, gx, partial_dep, dep_out);
 }
 }  // namespace
 
 hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
                             const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
                             uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
-                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream) {
+                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream, const RdoqFollowLaunch* F) {
     if (n_grids <= 0 || n_slots <= 0 || n_lane_blocks == 0 || n_chunks == 0 || n_cell_blocks == 0 || rounds < 1) return hipSuccess;
     const dim3 units(n_lane_blocks + n_big);
+    if (F) {  // the variants over claim sets: one memset, the reach launch(es), the flow boxes, then 3 R + 1 launches as below
+        if (F->n_reach[0] + F->n_reach[1] > 0) {
+            if (F->stages & 1) {
+                hipError_t e = hipMemsetAsync(F->reach_mem, 0xff, F->reach_bytes, stream);
+                for (int c = 0; c < 2 && e == hipSuccess; ++c) e = launch_rdoq_reach(F->reach_jobs[c], F->reach_prefix[c], F->n_reach[c], F->reach_blocks[c], c, stream);
+                if (e != hipSuccess) return e;
+            }
+            if (F->stages & 2)
+                hipLaunchKernelGGL(rdoq_flowbox_kernel, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks,
+                                   F->gx, F->sx);
+        }
+        if (!(F->stages & 4)) return hipGetLastError();  // (a timing run of the tables alone: no result is written)
+        for (int k = 0; k < rounds; ++k) {
+            hipLaunchKernelGGL(k == 0 ? rdoq_claim_follow_kernel<true> : rdoq_claim_follow_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots,
+                               d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks, F->gx, F->sx);
+            hipLaunchKernelGGL(k == 0 ? rdoq_select_follow_kernel<true> : rdoq_select_follow_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots,
+                               d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks, F->gx, F->sx);
+            if (k + 1 < rounds)
+                hipLaunchKernelGGL(rdoq_settle_follow_kernel, dim3(n_cell_blocks), dim3(64), 0, stream, d_grids, d_slots, d_cell_prefix, n_slots, F->sx,
+                                   F->comp_uid, F->comp_slot);
+        }
+        hipLaunchKernelGGL(rdoq_reduce_follow_kernel, dim3(n_chunks), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results,
+                           d_open, 0, F->gx, F->partial_dep, F->dep_out);
+        hipLaunchKernelGGL(rdoq_reduce_follow_kernel, dim3(n_slots), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results,
+                           d_open, 1, F->gx, F->partial_dep, F->dep_out);
+        return hipGetLastError();
+    }
     for (int k = 0; k < rounds; ++k) {
         hipLaunchKernelGGL(k == 0 ? rdoq_claim_kernel<true> : rdoq_claim_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix,
                            d_big_prefix, n_grids, n_lane_blocks);

@@ -128,6 +128,17 @@ struct RSlot {
     int frame_data_type = 0;
     uint32_t total = 0;                      // latents of all grids
     int leader = -1, follower = -1;          // ccd_rdoq_link: the slot whose rasters this one claims in / the slot that claims in this one's
+    // ccd_rdoq_follow, ccd_rdoq_set_dep_maps
+    struct Follow {
+        ccd_rdoq_follow_desc d;
+        bool stepped = false;                // a finished or pending step built its tables
+        size_t reach_off = 0;                // in ccd_rdoq::follow_mem, of the last step
+        size_t fbox_off[CCD_MAX_GRIDS] = {};
+    };
+    std::vector<Follow> follows;
+    const int64_t* dd_dep[CCD_MAX_GRIDS] = {};
+    bool have_dep = false;
+    int64_t dep_sse = 0;                     // the chosen entries of the dependent maps, last step
 };
 }  // namespace
 
@@ -138,9 +149,43 @@ struct ccd_rdoq {
     Block partial;
     int pending = 0;       // a step is in flight
     int n_stepped = 0;     // slots the step in flight covers
+    bool following = false;  // ... and it ran the following variants: a dependent sum per slot came back
+    bool partial_step = false;  // ... without its rounds (ccd_rdoq_debug_stages): no result was written
     hipStream_t step_stream = nullptr;  // ... and the stream it was enqueued on
     StreamSet streams;
+    int debug_stages = 7;  // ccd_rdoq_debug_stages
+    Block follow_mem;      // the reach tables (first, one memset) and the flow-box tables of the last step with follows
 };
+
+namespace {
+// The component-wide first uid of every slot: slots connected by links or follows (slot <-> target) form a
+// component; its groups come in ascending order of their leader's slot, the leader's latents first, then the follower's.  A slot
+// in no follow relation gets what it always had.  CCD_ERR_VALUE: a component with 2^32 latents or more.
+int component_uids(const ccd_rdoq& r, std::vector<uint32_t>& uid0, std::vector<int>& comp) {
+    const int n = static_cast<int>(r.slots.size());
+    comp.resize(n);
+    uid0.assign(n, 0);
+    for (int k = 0; k < n; ++k) comp[k] = k;
+    auto find = [&](int k) { while (comp[k] != k) k = comp[k] = comp[comp[k]]; return k; };
+    auto join = [&](int a, int b) { a = find(a); b = find(b); if (a != b) comp[std::max(a, b)] = std::min(a, b); };
+    for (int k = 0; k < n; ++k) {
+        if (r.slots[k]->leader >= 0) join(k, r.slots[k]->leader);
+        for (const auto& f : r.slots[k]->follows) join(k, f.d.target);
+    }
+    std::vector<uint64_t> next(n, 0);  // per component root: the latents numbered so far
+    for (int k = 0; k < n; ++k) comp[k] = find(k);
+    for (int k = 0; k < n; ++k) {      // leaders in ascending order; a follower right behind its leader
+        const RSlot& s = *r.slots[k];
+        if (s.leader >= 0) continue;
+        uint64_t& at = next[comp[k]];
+        uid0[k] = static_cast<uint32_t>(at);
+        at += s.total;
+        if (s.follower >= 0) { uid0[s.follower] = static_cast<uint32_t>(at); at += r.slots[s.follower]->total; }
+        if (at > 0xffffffffull) return CCD_ERR_VALUE;
+    }
+    return CCD_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -175,6 +220,7 @@ void ccd_rdoq_destroy(ccd_rdoq* r) {
     (void)hipSetDevice(r->device);
     (void)r->streams.drain();
     for (auto& s : r->slots) s->mem.drop();
+    r->follow_mem.drop();
     r->tables.drop(); r->partial.drop(); r->results.drop();
     delete r;
 }
@@ -269,6 +315,72 @@ int ccd_rdoq_link(ccd_rdoq* r, int slot, int leader) {
         return CCD_ERR_VALUE;
     f.leader = leader;
     l.follower = slot;
+    std::vector<uint32_t> uid0;
+    std::vector<int> comp;
+    if (component_uids(*r, uid0, comp) < 0) {  // (only with follows: a pair alone holds 2^32 - 2 at most)
+        f.leader = l.follower = -1;
+        return CCD_ERR_VALUE;
+    }
+    return CCD_OK;
+}
+
+int ccd_rdoq_max_follows(void) { return kRdoqMaxFollows; }
+
+int ccd_rdoq_lane_cells(void) { return static_cast<int>(kRdoqLaneCells); }
+
+// Not part of include/ccd.h (tests/test_rdoq_follow.py): the pick bytes of the last finished step, device uint8 [h][w] - 0 no
+// candidate, 1 / 2 a candidate for -1 / +1, with 4 once selected and 8 once blocked; neither: open after the last round.
+int64_t ccd_rdoq_debug_picks(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {
+    if (!r || !dev_ptr || slot < 0 || grid < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    const RSlot& s = *r->slots[slot];
+    if (grid >= s.n_grids || !s.covered) return CCD_ERR_ARG;
+    *dev_ptr = s.mem.as<char>() + s.pick_off[grid];
+    return static_cast<int64_t>(s.n[grid]);
+}
+
+// Not part of include/ccd.h (tools/rd_bench.py --follow, as ccd_dsens_debug_stages): which stages of a step with follows are
+// enqueued - 1 the memset and the reach launch(es), 2 the flow boxes, 4 the rounds and the sums; 7 is a step.  Without bit 4 the
+// tables of the last full step stay in use and no result is written: after such a step no slot is covered, so the result
+// getters refuse until a full step has run.  For timing only.
+int ccd_rdoq_debug_stages(ccd_rdoq* r, int mask) {
+    if (!r || mask < 1 || mask > 7 || r->pending) return CCD_ERR_ARG;
+    r->debug_stages = mask;
+    return CCD_OK;
+}
+
+int ccd_rdoq_follow(ccd_rdoq* r, int slot, const ccd_rdoq_follow_desc* f) {
+    if (!r || !f || slot < 0 || !f->motion || f->target < 0 || f->frozen < -1) return CCD_ERR_ARG;
+    if (f->frame_type < 1 || f->frame_type > 2 || f->which < 0 || f->which >= f->frame_type) return CCD_ERR_ARG;
+    const int n_slots = static_cast<int>(r->slots.size());
+    if (slot >= n_slots || f->target >= n_slots || f->frozen >= n_slots || r->pending) return CCD_ERR_ARG;
+    RSlot& s = *r->slots[slot];
+    if (static_cast<int>(s.follows.size()) >= kRdoqMaxFollows) return CCD_ERR_ARG;
+    if (f->target == slot || !warp_filter_ok(f->warp_filter_size)) return CCD_ERR_VALUE;
+    const RSlot& t = *r->slots[f->target];  // congruent rasters, as ccd_rdoq_link asks
+    if (t.frame_data_type != s.frame_data_type || t.geo.h.img_size[0] != s.geo.h.img_size[0] || t.geo.h.img_size[1] != s.geo.h.img_size[1])
+        return CCD_ERR_VALUE;
+    RSlot::Follow fo;
+    fo.d = *f;
+    s.follows.push_back(fo);
+    std::vector<uint32_t> uid0;
+    std::vector<int> comp;
+    if (component_uids(*r, uid0, comp) < 0) {
+        s.follows.pop_back();
+        return CCD_ERR_VALUE;
+    }
+    return static_cast<int>(s.follows.size()) - 1;
+}
+
+int ccd_rdoq_set_dep_maps(ccd_rdoq* r, int slot, const int64_t* const* dd_dep) {
+    if (!r || slot < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    RSlot& s = *r->slots[slot];
+    s.have_dep = false;
+    for (int g = 0; g < s.n_grids; ++g) {
+        s.dd_dep[g] = dd_dep ? dd_dep[g] : nullptr;
+        s.have_dep = s.have_dep || s.dd_dep[g];
+    }
     return CCD_OK;
 }
 
@@ -289,6 +401,20 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
         n_grids += r->slots[k]->n_grids;
     }
     if (n_slots == 0) return CCD_OK;
+    // the flows are followed as they are: no move of a followed frame's motion cool-chic in the same step
+    bool following = false;
+    for (int k = 0; k < n_slots; ++k) {
+        const RSlot& s = *r->slots[k];
+        following = following || s.have_dep || !s.follows.empty();
+        for (const auto& f : s.follows)
+            if (f.d.frozen >= 0 && grid_mask[f.d.frozen] != 0) return CCD_ERR_VALUE;
+    }
+    std::vector<uint32_t> uid0;
+    std::vector<int> comp;
+    {
+        const int rc = component_uids(*r, uid0, comp);
+        if (rc < 0) return rc;
+    }
     // the tables of this step: grids, slots and the four prefix tables, one block, one copy
     std::vector<RdoqGrid> grids;
     std::vector<RdoqSlot> slots(n_slots);
@@ -299,9 +425,9 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
         char* base = s.mem.as<char>();
         RdoqSlot& S = slots[k];
         std::memset(&S, 0, sizeof(S));
-        // a follower claims in its leader's rasters, its uids after the leader's (both at most 2^31 - 1: 32 bits hold the pair)
+        // a follower claims in its leader's rasters, its uids after the leader's (both at most 2^31 - 1: 32 bits hold the pair);
+        // in a component with follows the uids run on over its groups (component_uids)
         const RSlot& owner = s.leader >= 0 ? *r->slots[s.leader] : s;
-        const uint32_t uid0 = s.leader >= 0 ? owner.total : 0;
         S.raster = reinterpret_cast<unsigned long long*>(owner.mem.as<char>() + owner.raster_off);
         S.taken = reinterpret_cast<uint8_t*>(owner.mem.as<char>() + owner.taken_off);
         S.partner = s.leader >= 0 ? s.leader : s.follower;
@@ -322,7 +448,7 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
             G.pick = reinterpret_cast<uint8_t*>(base + s.pick_off[g]);
             G.box = reinterpret_cast<const RdoqBox*>(base + s.box_off[g]);
             G.big = reinterpret_cast<const uint32_t*>(base + s.big_off[g]);
-            G.n = s.n[g]; G.first = uid0 + s.first[g]; G.slot = k; G.grid = g;
+            G.n = s.n[g]; G.first = uid0[k] + s.first[g]; G.slot = k; G.grid = g;
             lanes += (G.n + 63) / 64; bigs += s.n_big[g]; chunks += (G.n + kRdoqChunk - 1) / kRdoqChunk;
             if (lanes + bigs > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
             const size_t e = grids.size();
@@ -331,9 +457,84 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
             grids.push_back(G);
         }
     }
+    // with follows or dependent maps: the tables beside grids and slots, the components, the reach jobs; the reach tables come
+    // first in follow_mem (one memset), the flow boxes behind them
+    std::vector<RdoqGridX> gridsx;
+    std::vector<RdoqSlotX> slotsx;
+    std::vector<uint32_t> comp_uid, reach_prefix[2];
+    std::vector<int32_t> comp_slot;
+    std::vector<RdoqReachJob> reach_jobs[2];
+    size_t reach_bytes = 0, follow_bytes = 0;
+    if (following) {
+        gridsx.resize(n_grids);
+        slotsx.resize(n_slots);
+        std::memset(gridsx.data(), 0, gridsx.size() * sizeof(RdoqGridX));
+        std::memset(slotsx.data(), 0, slotsx.size() * sizeof(RdoqSlotX));
+        for (int k = 0; k < n_slots; ++k)
+            for (auto& f : r->slots[k]->follows) {
+                f.reach_off = follow_bytes;
+                follow_bytes += align256(static_cast<size_t>(r->slots[k]->geo.cells_h) * r->slots[k]->geo.cells_w * kRdoqReachWords * sizeof(uint32_t));
+            }
+        reach_bytes = follow_bytes;
+        for (int k = 0; k < n_slots; ++k)
+            for (auto& f : r->slots[k]->follows)
+                for (int g = 0; g < r->slots[k]->n_grids; ++g) {
+                    f.fbox_off[g] = follow_bytes;
+                    follow_bytes += align256(static_cast<size_t>(r->slots[k]->n[g]) * sizeof(RdoqBox));
+                }
+        // nothing of an earlier step is in flight: the block may be exchanged, and what ccd_rdoq_slot_reach handed out ends here
+        for (auto& s : r->slots)
+            for (auto& f : s->follows) f.stepped = false;
+        HIP_TRY(hipSetDevice(r->device));
+        if (!r->follow_mem.ensure(r->device, BlockPool::kDevice, std::max<size_t>(follow_bytes, 256))) return CCD_ERR_NOMEM;
+        char* fm = r->follow_mem.as<char>();
+        for (int root = 0; root < n_slots; ++root) {  // a component's slots in the order of their uids: leaders ascending, follower behind
+            if (comp[root] != root) continue;
+            const int32_t first = static_cast<int32_t>(comp_uid.size());
+            for (int k = 0; k < n_slots; ++k) {
+                if (comp[k] != root || r->slots[k]->leader >= 0) continue;
+                comp_uid.push_back(uid0[k]); comp_slot.push_back(k);
+                const int fo = r->slots[k]->follower;
+                if (fo >= 0) { comp_uid.push_back(uid0[fo]); comp_slot.push_back(fo); }
+            }
+            for (int k = 0; k < n_slots; ++k)
+                if (comp[k] == root) { slotsx[k].comp_first = first; slotsx[k].comp_n = static_cast<int32_t>(comp_uid.size()) - first; }
+        }
+        uint64_t blocks[2] = {0, 0};
+        reach_prefix[0].push_back(0); reach_prefix[1].push_back(0);
+        for (int k = 0; k < n_slots; ++k) {
+            RSlot& s = *r->slots[k];
+            RdoqSlotX& SX = slotsx[k];
+            SX.n_follows = static_cast<int32_t>(s.follows.size());
+            for (size_t q = 0; q < s.follows.size(); ++q) {
+                RSlot::Follow& f = s.follows[q];
+                const RdoqSlot& T = slots[f.d.target];  // (raster / taken: its group's)
+                SX.follow[q].reach = reinterpret_cast<const uint32_t*>(fm + f.reach_off);
+                SX.follow[q].raster = T.raster;
+                SX.follow[q].taken = T.taken;
+                RdoqReachJob J;
+                J.motion = f.d.motion; J.reach = reinterpret_cast<uint32_t*>(fm + f.reach_off);
+                J.which = f.d.which; J.H = s.geo.h.img_size[0]; J.W = s.geo.h.img_size[1]; J.n_taps = f.d.warp_filter_size;
+                J.gx = f.d.global_flow[2 * f.d.which]; J.gy = f.d.global_flow[2 * f.d.which + 1];
+                J.cells_h = s.geo.cells_h; J.cells_w = s.geo.cells_w;
+                const int c = f.d.warp_filter_size == 8;
+                blocks[c] += static_cast<uint64_t>(J.cells_h) * J.cells_w;
+                if (blocks[c] > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+                reach_jobs[c].push_back(J);
+                reach_prefix[c].push_back(static_cast<uint32_t>(blocks[c]));
+            }
+            for (int g = 0; g < s.n_grids; ++g) {
+                RdoqGridX& X = gridsx[slots[k].first_grid + g];
+                X.dd_dep = s.dd_dep[g];
+                for (size_t q = 0; q < s.follows.size(); ++q) X.fbox[q] = reinterpret_cast<RdoqBox*>(fm + s.follows[q].fbox_off[g]);
+            }
+        }
+    }
     TableImage img;
     const size_t o_grids = img.put(grids), o_slots = img.put(slots);
     const size_t o_lane = img.put(lane_prefix), o_big = img.put(big_prefix), o_chunk = img.put(chunk_prefix), o_cell = img.put(cell_prefix);
+    const size_t o_gx = img.put(gridsx), o_sx = img.put(slotsx), o_cuid = img.put(comp_uid), o_cslot = img.put(comp_slot);
+    const size_t o_rj[2] = {img.put(reach_jobs[0]), img.put(reach_jobs[1])}, o_rp[2] = {img.put(reach_prefix[0]), img.put(reach_prefix[1])};
     const std::vector<char>& buf = img.bytes;
     HIP_TRY(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -341,12 +542,30 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
     // nothing of an earlier step is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
     // the results, then one int64 per slot: its open candidates
     const size_t open_off = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
-    const size_t res_bytes = open_off + static_cast<size_t>(n_slots) * sizeof(int64_t);
-    if (!r->tables.ensure(r->device, buf.size()) || !r->partial.ensure(r->device, BlockPool::kDevice, chunks * sizeof(RdoqPartial)) ||
+    const size_t dep_off = open_off + static_cast<size_t>(n_slots) * sizeof(int64_t);  // (following) and one more: its dependent sum
+    const size_t res_bytes = dep_off + (following ? static_cast<size_t>(n_slots) * sizeof(int64_t) : 0);
+    const size_t partial_dep_off = align256(chunks * sizeof(RdoqPartial));
+    if (!r->tables.ensure(r->device, buf.size()) ||
+        !r->partial.ensure(r->device, BlockPool::kDevice, partial_dep_off + (following ? chunks * sizeof(int64_t) : 0)) ||
         !r->results.ensure(r->device, res_bytes))
         return CCD_ERR_NOMEM;
     std::memcpy(r->tables.host.p, buf.data(), buf.size());
     const char* base = r->tables.dev.as<char>();
+    RdoqFollowLaunch F;
+    if (following) {
+        F.gx = reinterpret_cast<const RdoqGridX*>(base + o_gx); F.sx = reinterpret_cast<const RdoqSlotX*>(base + o_sx);
+        F.comp_uid = reinterpret_cast<const uint32_t*>(base + o_cuid); F.comp_slot = reinterpret_cast<const int32_t*>(base + o_cslot);
+        for (int c = 0; c < 2; ++c) {
+            F.reach_jobs[c] = reinterpret_cast<const RdoqReachJob*>(base + o_rj[c]);
+            F.reach_prefix[c] = reinterpret_cast<const uint32_t*>(base + o_rp[c]);
+            F.n_reach[c] = static_cast<int>(reach_jobs[c].size());
+            F.reach_blocks[c] = reach_prefix[c].back();
+        }
+        F.reach_mem = r->follow_mem.p; F.reach_bytes = reach_bytes;
+        F.partial_dep = reinterpret_cast<int64_t*>(r->partial.as<char>() + partial_dep_off);
+        F.dep_out = reinterpret_cast<int64_t*>(r->results.dev.as<char>() + dep_off);
+        F.stages = r->debug_stages;
+    }
     const bool ok =
         r->tables.upload(buf.size(), st) == hipSuccess &&
         launch_rdoq_step(reinterpret_cast<const RdoqGrid*>(base + o_grids), reinterpret_cast<const RdoqSlot*>(base + o_slots),
@@ -355,13 +574,20 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
                          n_slots, static_cast<uint32_t>(lanes), static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks),
                          static_cast<uint32_t>(cell_blocks), max_rounds, r->partial.as<RdoqPartial>(),
                          r->results.dev.as<ccd_rdoq_result>(), reinterpret_cast<int64_t*>(r->results.dev.as<char>() + open_off),
-                         st) == hipSuccess &&
+                         st, following ? &F : nullptr) == hipSuccess &&
         r->results.download(res_bytes, st) == hipSuccess;
     if (!ok) {  // part of the step may have been enqueued: drain it; no slot has a result, no step is in flight
         (void)hipStreamSynchronize(st);
-        for (auto& s : r->slots) s->covered = false;
+        for (auto& s : r->slots) {
+            s->covered = false;
+            for (auto& f : s->follows) f.stepped = false;
+        }
         return CCD_ERR_HIP;
     }
+    for (auto& s : r->slots)
+        for (auto& f : s->follows) f.stepped = true;
+    r->following = following;
+    r->partial_step = following && !(r->debug_stages & 4);
     r->pending = 1;  // everything is enqueued
     r->n_stepped = n_slots;
     r->step_stream = st;
@@ -376,13 +602,19 @@ int ccd_rdoq_wait(ccd_rdoq* r, void* stream) {
     // the results are behind the step on the stream the step was given, whichever stream this call names
     if (r->step_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(r->step_stream));
     r->pending = 0;
+    if (r->partial_step) {  // a timing run of the tables alone: no slot has a result
+        for (auto& s : r->slots) s->covered = false;
+        return CCD_OK;
+    }
     const ccd_rdoq_result* res = r->results.host.as<ccd_rdoq_result>();
     const int64_t* open = reinterpret_cast<const int64_t*>(res + r->n_stepped);
     for (int k = 0; k < r->n_stepped; ++k) {
         RSlot& s = *r->slots[k];
         s.result = res[k];
         s.n_open = open[k];
-        s.result.d_cost = s.kD * static_cast<double>(s.result.d_sse) + s.kR * s.result.d_bits;
+        s.dep_sse = r->following ? open[r->n_stepped + k] : 0;
+        // (d_sse + dep_sse: 0 without dependent maps, and the sum is then d_sse to the bit)
+        s.result.d_cost = s.kD * static_cast<double>(s.result.d_sse + s.dep_sse) + s.kR * s.result.d_bits;
         s.covered = true;
     }
     return CCD_OK;
@@ -399,6 +631,31 @@ int64_t ccd_rdoq_slot_open(const ccd_rdoq* r, int slot) {
     if (!r || slot < 0) return CCD_ERR_ARG;
     if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
     return r->slots[slot]->n_open;
+}
+
+int ccd_rdoq_slot_dep_sse(const ccd_rdoq* r, int slot, int64_t* out) {
+    if (!r || !out || slot < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
+    *out = r->slots[slot]->dep_sse;
+    return CCD_OK;
+}
+
+int64_t ccd_rdoq_slot_reach(const ccd_rdoq* r, int slot, int follow, void** dev_ptr) {
+    if (!r || !dev_ptr || slot < 0 || follow < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    const RSlot& s = *r->slots[slot];
+    if (follow >= static_cast<int>(s.follows.size()) || !s.covered || !s.follows[follow].stepped) return CCD_ERR_ARG;
+    *dev_ptr = r->follow_mem.as<char>() + s.follows[follow].reach_off;
+    return static_cast<int64_t>(s.geo.cells_h) * s.geo.cells_w;
+}
+
+int64_t ccd_rdoq_slot_flow_boxes(const ccd_rdoq* r, int slot, int follow, int grid, void** dev_ptr) {
+    if (!r || !dev_ptr || slot < 0 || follow < 0 || grid < 0) return CCD_ERR_ARG;
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
+    const RSlot& s = *r->slots[slot];
+    if (follow >= static_cast<int>(s.follows.size()) || grid >= s.n_grids || !s.covered || !s.follows[follow].stepped) return CCD_ERR_ARG;
+    *dev_ptr = r->follow_mem.as<char>() + s.follows[follow].fbox_off[grid];
+    return static_cast<int64_t>(s.n[grid]);
 }
 
 int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {

@@ -132,6 +132,26 @@ class RdEvaluator:
         self._caller_ptrs.append([int(p) for p in latents_or_ptrs] if on_device else None)
         return slot
 
+    # -- what a caller that steps the candidates itself needs of one (rd_gop.GopDescent)
+    def planes(self, slot: int) -> List[torch.Tensor]:
+        """The integer device planes the candidate decodes to: library memory at a fixed address, rewritten by every evaluate()."""
+        return [torch.as_tensor(self._dec.plane_device(int(slot), p), device=f"cuda:{self.device}") for p in range(3)]
+
+    def architecture(self, slot: int) -> CCHeader:
+        return self._jobs[int(slot)][0]
+
+    def source(self, slot: int) -> FrameData:
+        return self._frames[int(slot)]
+
+    def caller_latent_ptrs(self, slot: int) -> Optional[List[int]]:
+        """The caller's device latents the candidate was added with; None: it was added from host arrays."""
+        return self._caller_ptrs[int(slot)]
+
+    def move_scales(self, slot: int, lmbda: float):
+        """move_scales() of the candidate's frame: (kD, kR) of an RdoqStep over its maps."""
+        f = self._frames[int(slot)]
+        return move_scales(sum(int(t.numel()) for t in self._sources[int(slot)]), f.bitdepth, f.n_pixels, lmbda)
+
     def add_dependent(self, slot: int, frame_type: int, which: int, residue_ptr: int, motion_ptr: int, source_ptrs: Sequence[int],
                       other_ref_ptrs: Optional[Sequence[int]] = None, global_flow: Sequence[int] = (0, 0, 0, 0),
                       warp_filter_size: int = 8, owner=None) -> None:
@@ -165,18 +185,8 @@ class RdEvaluator:
         results = self._meter.finish()
         self._dec.wait(st)          # a refused device latent raises here (CCD_ERR_VALUE)
         self._enc.wait(st)
-        if distortion_deltas:       # reads the grids in the decode batch's arenas and the sources the meter read
-            if self._dd is None:
-                self._dd = DistortionDeltas(self.device, self._n_probe_slots)
-            for s in range(len(self._dd), n):
-                arch, bytes_nn = self._jobs[s]
-                f = self._frames[s]
-                self._dd.add(arch, bytes_nn, self._dec.latent_ptrs(s), [t.data_ptr() for t in self._sources[s]], f.bitdepth,
-                             FRAME_DATA_TYPES.index(f.frame_data_type), owner=self._dec)
-                for dep in self._dependents[s]:
-                    self._dd.add_dependent(s, **dep)
-            self._dd.run(st)
-            self._dd.wait(st)
+        if distortion_deltas:
+            self.run_distortion_deltas()
         out = []
         for s, (r, f) in enumerate(zip(results, self._frames)):
             rate = self._enc.rate(s)
@@ -184,6 +194,26 @@ class RdEvaluator:
             mse, bits, cost = rd_cost(q.sse, q.n, f.bitdepth, rate.total_bits, rate.n_bytes_nn, rate.n_bytes_header, f.n_pixels, lmbda)
             out.append(Candidate(rate, q, mse, bits, cost))
         return out
+
+    def run_distortion_deltas(self) -> None:
+        """The DistortionDeltas run of evaluate(distortion_deltas=True) on its own, over the grids as the last evaluate() ingested
+        them: own maps and, for candidates with add_dependent() frames, dependent maps - which read the dependents' float outputs
+        as they are NOW, so a caller that evaluates the dependents between the two (rd_gop.GopDescent) gets maps of the current
+        state of both."""
+        n = len(self._frames)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        # reads the grids in the decode batch's arenas and the sources the meter read
+        if self._dd is None:
+            self._dd = DistortionDeltas(self.device, self._n_probe_slots)
+        for s in range(len(self._dd), n):
+            arch, bytes_nn = self._jobs[s]
+            f = self._frames[s]
+            self._dd.add(arch, bytes_nn, self._dec.latent_ptrs(s), [t.data_ptr() for t in self._sources[s]], f.bitdepth,
+                         FRAME_DATA_TYPES.index(f.frame_data_type), owner=self._dec)
+            for dep in self._dependents[s]:
+                self._dd.add_dependent(s, **dep)
+        self._dd.run(st)
+        self._dd.wait(st)
 
     def rate_delta_map(self, slot: int, grid: int):
         """After evaluate(rate_deltas=True): EncodeBatch.delta_map of the candidate (device, float32 [2][h][w])."""

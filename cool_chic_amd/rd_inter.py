@@ -163,6 +163,25 @@ class InterRdEvaluator:
         """The integer device planes of the frame as the last evaluate() reconstructed them."""
         return self._frames[frame].planes
 
+    # -- what a caller that steps the frames itself needs of one (rd_gop.GopDescent)
+    def frame(self, frame: int) -> _Frame:
+        """What add() recorded of the frame: type, architectures, the caller's latents, references, global flow, filter size,
+        source planes."""
+        return self._frames[int(frame)]
+
+    def output_ptr(self, frame: int, role) -> int:
+        """The device address of the float output of the role's cool-chic: library memory at a fixed address, rewritten by every
+        evaluate()."""
+        return int(self._dec.output_device(2 * int(frame) + _role(role)).__cuda_array_interface__["data"][0])
+
+    def frame_data_type_index(self, frame: int) -> int:
+        return self._fdt(self._frames[int(frame)])
+
+    def move_scales(self, frame: int, lmbda: float):
+        """rd.move_scales of the frame: (kD, kR) of an RdoqStep over the maps of either cool-chic."""
+        f = self._frames[int(frame)]
+        return move_scales(sum(int(t.numel()) for t in f.src), f.source.bitdepth, f.source.n_pixels, lmbda)
+
     def _fdt(self, f: _Frame) -> int:
         return FRAME_DATA_TYPES.index(f.source.frame_data_type)
 

@@ -11,7 +11,7 @@ import ctypes as C
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 from ._handle import _DevArray, _Handle, ptr_array
-from ._lib import CCHeader, RdoqResult, check, lib
+from ._lib import CCHeader, RdoqFollow, RdoqResult, check, lib
 
 
 class StepResult(NamedTuple):
@@ -32,6 +32,16 @@ def cell() -> int:
 def max_rounds() -> int:
     """The most rounds a step may run (ccd_rdoq_max_rounds)."""
     return int(lib().ccd_rdoq_max_rounds())
+
+
+def max_follows() -> int:
+    """The most follows one slot takes (ccd_rdoq_max_follows)."""
+    return int(lib().ccd_rdoq_max_follows())
+
+
+def lane_cells() -> int:
+    """Cells of a box up to which one lane walks it in a step's kernels (ccd_rdoq_lane_cells): a cost figure."""
+    return int(lib().ccd_rdoq_lane_cells())
 
 
 def influence_box(arch: CCHeader, frame_data_type: int, grid: int, y: int, x: int) -> Tuple[int, int, int, int]:
@@ -55,10 +65,15 @@ class RdoqStep(_Handle):
     def __len__(self):
         return len(self._grid_shapes)
 
+    def _open(self, create, device, *args):
+        super()._open(create, device, *args)
+        self._cells: list = []  # per slot: the (cells_h, cells_w) of its claim raster
+
     def add(self, arch: CCHeader, frame_data_type: int, latent_ptrs: Sequence[int], owner=None) -> int:
         """Device latents (int8 [h][w] per grid), read AND WRITTEN by every step.  Returns the slot."""
         slot = check(lib().ccd_rdoq_add(self._h, C.byref(arch), int(frame_data_type), ptr_array(latent_ptrs)), "ccd_rdoq_add")
         self._note_grids(arch, len(latent_ptrs))
+        self._cells.append((-(-int(arch.img_size[0]) // cell()), -(-int(arch.img_size[1]) // cell())))
         self._keep(owner)  # (the device latents the slot uses at step())
         return slot
 
@@ -76,6 +91,52 @@ class RdoqStep(_Handle):
         that decode into one frame of the same size and sample format.  On a tie of the costs the leader's candidate wins.  Results,
         move maps and masks stay per slot; a slot whose mask is 0 leaves its partner stepping as if unlinked.  There is no unlink."""
         check(lib().ccd_rdoq_link(self._h, int(slot), int(leader)), "ccd_rdoq_link")
+
+    def follow(self, slot: int, frame_type: int, which: int, motion_ptr: int, target: int, frozen: int = -1,
+               global_flow: Sequence[int] = (0, 0, 0, 0), warp_filter_size: int = 8, owner=None) -> int:
+        """The frame `slot` decodes is reference `which` of a P (1) / B (2) frame F whose device motion output (float32
+        [2 | 4][h][w]) is at `motion_ptr`: from the next step on a candidate of `slot` also claims, in the raster of `target` (F's
+        residue slot or the leader of F's pair; mask 0 if F is held fixed), the cells whose samples can read what it changes,
+        along the flows as they are at that step (include/ccd.h: ccd_rdoq_follow).  `frozen`: the slot of F's
+        motion cool-chic, which a step then refuses to move.  Returns the follow's index.  There is no unfollow."""
+        d = RdoqFollow(int(frame_type), int(which), int(motion_ptr) or None, (C.c_int32 * 4)(*[int(v) for v in global_flow]),
+                       int(warp_filter_size), int(target), int(frozen))
+        k = check(lib().ccd_rdoq_follow(self._h, int(slot), C.byref(d)), "ccd_rdoq_follow")
+        self._keep(owner)
+        return k
+
+    def set_dep_maps(self, slot: int, dep_ptrs: Optional[Sequence[Optional[int]]], owner=None):
+        """Per grid the device int64 [2][h][w] dependent map (DistortionDeltas.dep_delta_map), None / 0: none.  The cost of a move
+        becomes (dD + dDdep) * kD + dBits * kR, and a move exists in neither map's sentinel.  None: no dependent maps."""
+        if dep_ptrs is not None and len(dep_ptrs) != len(self._grid_shapes[int(slot)]):
+            raise ValueError(f"slot {slot} has {len(self._grid_shapes[int(slot)])} grids")
+        check(lib().ccd_rdoq_set_dep_maps(self._h, int(slot), None if dep_ptrs is None else ptr_array(dep_ptrs)), "ccd_rdoq_set_dep_maps")
+        self._keep(owner)
+
+    def dep_sse(self, slot: int) -> int:
+        """After step() + wait(): the exact sum of the chosen entries of the slot's dependent maps - what the step did to the
+        squared error of the frames that predict from the slot's frame.  StepResult.d_sse stays the slot's own frame's."""
+        v = C.c_int64()
+        check(lib().ccd_rdoq_slot_dep_sse(self._h, int(slot), C.byref(v)), "ccd_rdoq_slot_dep_sse")
+        return int(v.value)
+
+    def reach(self, slot: int, follow: int) -> _DevArray:
+        """After step() + wait(): the follow's reach table of that step, uint32 [cells_h][cells_w][4] on the device:
+        {top, left, ~bottom, ~right} in cells of the dependent, all ones where no sample of it reads the cell."""
+        ptr = C.c_void_p()
+        n = check(lib().ccd_rdoq_slot_reach(self._h, int(slot), int(follow), C.byref(ptr)), "ccd_rdoq_slot_reach")
+        ch, cw = self._cells[int(slot)]
+        assert ch * cw == n
+        return _DevArray(ptr.value or 0, (ch, cw, 4), "<u4", self)
+
+    def flow_boxes(self, slot: int, follow: int, grid: int) -> _DevArray:
+        """After step() + wait(): uint16 [h][w][4] on the device, {top, left, bottom, right} of every latent's flow box for the
+        follow; top > bottom: empty."""
+        ptr = C.c_void_p()
+        n = check(lib().ccd_rdoq_slot_flow_boxes(self._h, int(slot), int(follow), int(grid), C.byref(ptr)), "ccd_rdoq_slot_flow_boxes")
+        h, w = self._grid_shapes[int(slot)][int(grid)]
+        assert h * w == n
+        return _DevArray(ptr.value or 0, (h, w, 4), "<u2", self)
 
     def step(self, kD: Sequence[float], kR: Sequence[float], min_gain: Sequence[float], grid_mask: Sequence[int], stream: int = 0,
              rounds: int = 1):

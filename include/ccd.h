@@ -723,6 +723,55 @@ int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out);
 int64_t ccd_rdoq_slot_open(const ccd_rdoq* r, int slot);
 int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr);
 
+/* ---- Claims that follow the flows into the dependent frames ----
+ * Slot `slot` decodes a frame R (intra, or either cool-chic of a P / B frame).  A FOLLOW names a dependent F, a P / B frame with R
+ * as its reference `which`: F's device motion output (f32 [2 | 4][h][w], read at every step, never written), its global flow and
+ * warp filter size, `target` - the slot of this handle in whose claim raster F's samples are claimed: F's residue slot, or the
+ * leader of F's linked pair; a caller that holds F fixed still adds that slot and gives it grid_mask 0 - and `frozen`, the slot of
+ * F's motion cool-chic in this handle, or -1.  R and F have one img_size and frame_data_type.
+ * From the next step on a candidate of `slot` claims, beside its influence box, its FLOW BOX in the raster of every follow's
+ * target: per step a REACH TABLE is built from the flows as they then are - for every cell C (ccd_rdoq_cell() luma samples a side)
+ * of F the bounding rectangle of the reference indices the windows of its samples read (the index pieces of the warp), and for
+ * every cell c of R that rectangle meets reach[c] = bbox(reach[c], C) - and the flow box of a latent is the bounding rectangle of
+ * reach[c] over the cells c of its influence box, empty if all are.  A candidate is blocked when a cell of this CLAIM SET is taken,
+ * claims in every cell of it and is selected when its key stands in all of them; the rule of ccd_rdoq_step_rounds holds with
+ * "box" read as "claim set".  Slots connected by links or follows form a COMPONENT whose latents share one numbering (the groups
+ * in ascending order of their leader's slot, the leader's latents before the follower's); a slot in no follow relation keeps its
+ * numbering and steps exactly as without these calls.  Two selected moves change disjoint sets of samples of R and of every
+ * followed F, so own and dependent deltas add.  Only DIRECT dependents: what predicts from F is not followed.
+ * ccd_rdoq_follow returns the follow's index (0 .. ccd_rdoq_max_follows() - 1 = 3).  CCD_ERR_ARG before the handle is looked at: a
+ * NULL r / f / motion, a negative slot or target, frozen < -1, frame_type outside 1 .. 2, which outside 0 .. frame_type - 1;
+ * CCD_ERR_ARG also for an index past the slots, a step in flight, a fifth follow; CCD_ERR_VALUE for target == slot, a
+ * warp_filter_size ccd_inter_reconstruct refuses, a target of another img_size or frame_data_type, and a component that would
+ * hold 2^32 latents or more (ccd_rdoq_link refuses that too).  A refused call leaves the handle as it was.  There is no unfollow.
+ * ccd_rdoq_set_dep_maps: dd_dep[g] = device int64 [2][h][w], the dependent map of ccd_dsens_slot_dep_map, or NULL; the cost
+ * becomes (dD + dDdep) * kD + dBits * kR and a move exists in neither map's INT64_MIN.  dd_dep == NULL, or all entries NULL:
+ * the rule of ccd_rdoq_step to the bit.  ccd_rdoq_result.d_sse stays the change of the slot's OWN frame;
+ * ccd_rdoq_slot_dep_sse gives the exact sum of the chosen dependent entries, and d_cost = kD * (d_sse + dep_sse) + kR * d_bits.
+ * ccd_rdoq_step / ccd_rdoq_step_rounds return CCD_ERR_VALUE, before anything is enqueued, when the `frozen` slot of any follow
+ * has a non-zero grid_mask: the flows are followed as given, and no map prices a flow that moves in the same step.
+ * ccd_rdoq_slot_reach: the reach table of the last finished step, device uint32 [cells_h][cells_w][4] =
+ * {top, left, ~bottom, ~right} in cells of F (all ones: no sample of F reads the cell); returns cells_h * cells_w.
+ * ccd_rdoq_slot_flow_boxes: device uint16 [h][w][4] = {top, left, bottom, right} of every latent of `grid`, top > bottom: empty;
+ * returns h * w.  Both valid until the next step / destroy; CCD_ERR_ARG as ccd_rdoq_slot_moves, and for a follow no finished
+ * step covered. */
+typedef struct {
+    int32_t frame_type;        /* of F: 1 P, 2 B */
+    int32_t which;             /* F's reference that `slot` decodes */
+    const float* motion;       /* DEVICE f32 [2 | 4][h][w]: F's motion output */
+    int32_t global_flow[4];    /* F's, as ccd_inter_reconstruct takes it */
+    int32_t warp_filter_size;
+    int32_t target;            /* the slot whose raster F's samples are claimed in */
+    int32_t frozen;            /* the slot of F's motion cool-chic, or -1 */
+} ccd_rdoq_follow_desc;
+int ccd_rdoq_max_follows(void);
+int ccd_rdoq_lane_cells(void);  /* a box or flow box of more cells than this is walked by a wave, not a lane (a cost figure, not a limit) */
+int ccd_rdoq_follow(ccd_rdoq* r, int slot, const ccd_rdoq_follow_desc* f);
+int ccd_rdoq_set_dep_maps(ccd_rdoq* r, int slot, const int64_t* const* dd_dep);
+int ccd_rdoq_slot_dep_sse(const ccd_rdoq* r, int slot, int64_t* out);
+int64_t ccd_rdoq_slot_reach(const ccd_rdoq* r, int slot, int follow, void** dev_ptr);
+int64_t ccd_rdoq_slot_flow_boxes(const ccd_rdoq* r, int slot, int follow, int grid, void** dev_ptr);
+
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):
  * left[i], right[i] as the entropy kernel sees them (exhaustive parity tests of the f64 CDF). */
 int ccd_debug_laplace_bounds(int device, const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* s,

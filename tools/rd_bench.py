@@ -527,6 +527,158 @@ def measure_inter_descent(stream_bytes, coding_index, runs, lmbda, rounds, grids
     return res
 
 
+def measure_follow(stream_bytes, runs, lmbda, rounds, grids, n_probe_slots):
+    """The I frame of a video stream (a seeded tenth of its latents moved by +-1) with the frames that predict from it directly:
+    one RDOQ step priced by own + dependent deltas, without follows and with claims that follow the flows -
+    step time, moves and n_open of both, the reach launch, the flow-box launch and the round kernels timed apart, the evaluate
+    that feeds the step, and the share of latents whose flow box exceeds the cells a lane walks, on the stream's flows and on
+    random ones.  The dependents are held fixed (mask 0)."""
+    import ctypes as C
+    import os
+    import tempfile
+
+    import numpy as np
+
+    from cool_chic_amd import RdoqStep, rdoq
+    from cool_chic_amd._lib import check, lib
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+    from cool_chic_amd.bitstream.intercoding import _integer_planes
+
+    lane_cells = rdoq.lane_cells()
+    st = torch.cuda.current_stream().cuda_stream
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    split = []
+    for k in range(len(structure)):
+        fh, ccs, rest = _split_frame(rest)
+        split.append((fh, ccs))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    dev = torch.device("cuda:0")
+    planes = {int(d): _integer_planes(fd, dev) for d, fd in frames.items()}
+    fh0, ccs0 = split[0]
+    display = int(structure[0]["display_order"])
+    fdt = ["rgb", "yuv420", "yuv444"].index(fh0.get_value("frame_data_type"))
+    dec = DecodeBatch(0)
+    dec.add(ccs0[0][0].raw, ccs0[0][1], ccs0[0][2], 0, 0)
+    deps = []
+    for k in range(1, len(structure)):
+        refs = [int(r) for r in structure[k]["index_references"]]
+        fh, ccs = split[k]
+        n_refs = "IPB".index(fh.get_value("frame_type"))
+        if display not in refs[:n_refs]:
+            continue
+        first = len(dec)
+        for ch, nn, lat in ccs:
+            dec.add(ch.raw, nn, lat, 0, 0)
+        deps.append({"frame_type": n_refs, "which": refs[:n_refs].index(display), "slots": (first, first + 1),
+                     "other": planes[refs[1 - refs[:n_refs].index(display)]] if n_refs == 2 else None,
+                     "src": planes[int(structure[k]["display_order"])], "gflow": (list(fh.get_value("global_flow")) + [0] * 4)[:4],
+                     "taps": int(fh.get_value("warp_filter_size"))})
+    dec.run(st); dec.wait(st)
+    arch, nn = dec.header(0), dec.network_bytes(0)
+    rng = np.random.default_rng(14)
+    start = []
+    for g in range(arch.n_grids):
+        a = dec.latent(0, g).astype(np.int64)
+        a = a + np.where(rng.random(a.shape) < 0.1, rng.choice([-1, 1], size=a.shape), 0)
+        start.append(torch.from_numpy(np.clip(a, -64, 63).astype(np.int8)).cuda())
+    work = [t.clone() for t in start]
+    source = frames[str(display)]
+    ev = RdEvaluator(0, n_probe_slots)
+    ev.add(arch, nn, [t.data_ptr() for t in work], source, owner=work)
+    outs = []
+    for d in deps:
+        o = [torch.as_tensor(dec.output_device(s), device="cuda") for s in d["slots"]]
+        outs.append(o)
+        ev.add_dependent(0, d["frame_type"], d["which"], o[0].data_ptr(), o[1].data_ptr(), [t.data_ptr() for t in d["src"]],
+                         None if d["other"] is None else [t.data_ptr() for t in d["other"]], d["gflow"], d["taps"], owner=(o, planes))
+
+    def evaluate_step():
+        ev.evaluate(lmbda, rate_deltas=True, distortion_deltas=True)
+
+    res = {"size": [int(v) for v in source.img_size], "dependents": len(deps), "lmbda": lmbda, "rounds": rounds, "grids": grids, "lane_cells": lane_cells}
+    res["evaluate_deltas_ms"] = round(event_ms(evaluate_step, min(runs, 3), warmup=1), 3)
+    n_samples = sum(int(t.numel()) for t in planes[display])
+    kD, kR = 1.0 / (n_samples * float(2 ** source.bitdepth - 1) ** 2), lmbda / source.n_pixels
+    mask = sum(1 << g for g in grids if g < arch.n_grids)
+    stages = lib().ccd_rdoq_debug_stages  # exported, not part of include/ccd.h
+    stages.restype, stages.argtypes = C.c_int, [C.c_void_p, C.c_int]
+
+    def ptr(a):
+        return a.__cuda_array_interface__["data"][0]
+
+    def handle(follow, motions=None):
+        step = RdoqStep(0)
+        step.add(arch, fdt, [t.data_ptr() for t in work], owner=work)
+        step.set_maps(0, [ptr(ev.distortion_delta_map(0, g)) for g in range(arch.n_grids)], [ptr(ev.rate_delta_map(0, g)) for g in range(arch.n_grids)], owner=ev)
+        step.set_dep_maps(0, [ptr(ev.dependent_delta_map(0, g)) for g in range(arch.n_grids)])
+        zeros = []
+        for k, d in enumerate(deps):  # the residue cool-chic of every dependent, held fixed: the raster the follow claims in
+            h = dec.header(d["slots"][0])
+            z = [torch.zeros((2, int(h.grid_h[g]), int(h.grid_w[g])), dtype=torch.float32, device="cuda") for g in range(h.n_grids)]
+            zeros.append(z)
+            slot = step.add(h, fdt, dec.latent_ptrs(d["slots"][0]), owner=dec)
+            step.set_maps(slot, [None] * h.n_grids, [t.data_ptr() for t in z], owner=z)
+            if follow:
+                m = outs[k][1] if motions is None else motions[k]
+                step.follow(0, d["frame_type"], d["which"], m.data_ptr(), target=slot, global_flow=d["gflow"], warp_filter_size=d["taps"], owner=m)
+        n = 1 + len(deps)
+        return step, ([kD] * n, [kR] * n, [0.0] * n, [mask] + [0] * len(deps))
+
+    def timed(step, args, stage=7):
+        check(stages(step._h, stage), "ccd_rdoq_debug_stages")
+        times = []
+        for it in range(3 + runs):
+            for t, u in zip(work, start):
+                t.copy_(u)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step.step(*args, st, rounds=rounds)
+            e1.record()
+            step.wait(st)
+            if it >= 3:
+                times.append(e0.elapsed_time(e1))
+        check(stages(step._h, 7), "ccd_rdoq_debug_stages")
+        return {"ms": round(statistics.median(times), 4), "min_max": [round(min(times), 4), round(max(times), 4)]}
+
+    def share_big(step):
+        big = total = 0
+        for k in range(len(deps)):
+            for g in range(arch.n_grids):
+                b = torch.as_tensor(step.flow_boxes(0, k, g), device="cuda").to(torch.int64)
+                cells = torch.clamp(b[..., 2] - b[..., 0] + 1, min=0) * torch.clamp(b[..., 3] - b[..., 1] + 1, min=0)
+                big += int((cells > lane_cells).sum()); total += int(cells.numel())
+        return round(big / max(total, 1), 4)
+
+    for label, follow in (("without_follows", False), ("with_follows", True)):
+        step, args = handle(follow)
+        r = {"step": timed(step, args)}
+        out = step.result(0)
+        r.update(candidates=out.n_candidates, moves=out.n_moves, open=out.n_open, d_sse=out.d_sse, dep_sse=step.dep_sse(0))
+        if follow:
+            r["flow_box_over_lane_cells"] = share_big(step)
+            r["reach"], r["flow_boxes"], r["rounds_and_sums"] = timed(step, args, 1), timed(step, args, 2), timed(step, args, 4)
+        step.close()
+        res[label] = r
+    g = torch.Generator(device="cuda").manual_seed(14)
+    motions = [(torch.rand(o[1].shape, generator=g, device="cuda") * 40.0 - 20.0).contiguous() for o in outs]
+    step, args = handle(True, motions)
+    r = {"step": timed(step, args)}
+    out = step.result(0)
+    r.update(moves=out.n_moves, open=out.n_open, flow_box_over_lane_cells=share_big(step))
+    res["random_flows_20"] = r
+    step.close()
+    ev.close()
+    dec.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
@@ -543,7 +695,17 @@ def main():
     ap.add_argument("--grids", default="0,1,2", help="with --inter --joint: the grids that may move, in both cool-chics")
     ap.add_argument("--max-steps", type=int, default=400, help="with --inter --joint: steps of a descent at most")
     ap.add_argument("--dependents", action="store_true", help="time the distortion deltas through the direct dependents of an I frame instead")
+    ap.add_argument("--follow", action="store_true", help="time an RDOQ step of an I frame whose claims follow the flows into its dependents instead")
     a = ap.parse_args()
+    if a.follow:
+        line = {"tool": "rd_bench --follow", "runs": a.runs}
+        args = (a.runs, a.lmbda, a.rounds, [int(g) for g in a.grids.split(",") if g != ""], a.probe_slots)
+        if "vid5" in a.inter_sets.split(","):
+            line["vid5_I"] = measure_follow(synth._golden("vid5")[0], *args)
+        if "1080p" in a.inter_sets.split(","):
+            line["gop1080p_I"] = measure_follow(synth.gop1080p(2)[0], *args)
+        print(json.dumps(line))
+        return
     if a.dependents:
         runs = min(a.runs, 5)
         line = {"tool": "rd_bench --dependents", "runs": runs}

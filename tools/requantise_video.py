@@ -2,8 +2,12 @@
 4.14 and 4.15).  The frames are walked in coding order: I frames go through RdEvaluator.descend as in tools/requantise.py, P / B
 frames through InterRdEvaluator.descend with the planes of the already REQUANTISED frames as their references.  The networks and
 every header stay as they are; the new latents of each cool-chic are range-coded by the device writer.
+With --follow an I frame does not finish before its dependents start: it descends TOGETHER with the residues of the
+P / B frames that predict from it directly and whose other reference, if any, is already requantised (GopDescent: the steps are
+priced by own + dependent deltas and their claims follow the flows).  Those frames then go through their own descent as usual.
 
     python tools/requantise_video.py in.cool source.yuv out.cool --lmbda 1e-3 [--max-steps 16] [--grids 0,1,2] [--min-gain 0] [--joint]
+                                     [--follow]
 
 Prints bits, PSNR and cost of every frame before and after ("before": the stream's latents against the references as they are now,
 requantised), writes the stream, decodes it back with decode_video and asserts that every frame's planes are those the last
@@ -15,7 +19,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, ".")
-from cool_chic_amd import DecodeBatch, EncodeBatch, InterRdEvaluator, RdEvaluator  # noqa: E402
+from cool_chic_amd import DecodeBatch, EncodeBatch, GopDescent, InterRdEvaluator, RdEvaluator  # noqa: E402
 from cool_chic_amd.bitstream.decode import _split_frame, decode_video  # noqa: E402
 from cool_chic_amd.bitstream.header import VideoHeader  # noqa: E402
 from cool_chic_amd.quality import read_source  # noqa: E402
@@ -32,6 +36,8 @@ def main():
     ap.add_argument("--grids", default="", help="comma-separated grids that may move, in every cool-chic (default: all; see tools/requantise.py)")
     ap.add_argument("--rounds", type=int, default=1, help="rounds of selection per step (1 .. 64; 8 is a sensible value; see tools/requantise.py)")
     ap.add_argument("--joint", action="store_true", help="P / B frames: every step moves both cool-chics (InterRdEvaluator.descend(joint=True))")
+    ap.add_argument("--follow", action="store_true",
+                    help="an I frame and the residues of its direct dependents move in one descent whose claims follow the flows (GopDescent)")
     a = ap.parse_args()
     grids = [int(g) for g in a.grids.split(",") if g != ""] or None
     with open(a.stream, "rb") as f:
@@ -62,6 +68,10 @@ def main():
         cool_chics.append(row)
     dec.close()
 
+    def references(k):
+        n_refs = "IPB".index(parsed[k][0].get_value("frame_type"))
+        return [coding_of[int(r)] for r in structure[k]["index_references"]][:n_refs]
+
     done = {}  # coding index -> the device planes of the requantised frame, as its last evaluation scored them
     for k, (fh, _) in enumerate(parsed):
         frame_type = fh.get_value("frame_type")
@@ -70,12 +80,35 @@ def main():
             ev = RdEvaluator(0)
             arch, nn, lat = cool_chics[k][0]
             ev.add(arch, nn, ptrs[0], sources[k], owner=lat)
-            reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
-            after = ev.evaluate(a.lmbda)[0]
-            done[k] = [torch.as_tensor(ev._dec.plane_device(0, p), device="cuda").clone() for p in range(3)]
-            moves = [(r[0].step.n_moves, "") for r in reports]
+            # --follow: the frames that predict from this one directly and have no other reference still to come
+            group = [j for j in range(k + 1, n_frames) if a.follow and k in references(j) and all(r == k or r in done for r in references(j))]
+            if group:
+                inter = InterRdEvaluator(0)
+                gop = GopDescent(ev, inter)
+                for j in group:
+                    (ra, rn, rl), (ma, mn, ml) = cool_chics[j]
+                    fj = parsed[j][0]
+                    inter.add(fj.get_value("frame_type"), (ra, rn, [t.data_ptr() for t in rl]), (ma, mn, [t.data_ptr() for t in ml]),
+                              [gop.reference_planes(0) if r == k else done[r] for r in references(j)], fj.get_value("global_flow"),
+                              fj.get_value("warp_filter_size"), sources[j], owner=(rl, ml))
+                for f, j in enumerate(group):
+                    for which, r in enumerate(references(j)):
+                        if r == k:
+                            gop.follow(0, f, which)
+                steps = gop.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
+                after = ev.evaluate(a.lmbda)[0]
+                gop.close(); inter.close()
+                moves = [(f"{r.slots[0].step.n_moves} + {sum(s.step.n_moves for s in r.slots[1:])}",
+                          f" intra + residues of {', '.join(str(display[j]) for j in group)}") for r in steps]
+                before = steps[0].intra[0] if steps else after
+            else:
+                reports = ev.descend(a.lmbda, a.max_steps, a.min_gain, grids, rounds=a.rounds)
+                after = ev.evaluate(a.lmbda)[0]
+                moves = [(r[0].step.n_moves, "") for r in reports]
+                before = reports[0][0].before if reports else after
+            done[k] = [p.clone() for p in ev.planes(0)]
         else:
-            refs = [coding_of[int(r)] for r in structure[k]["index_references"]][:2 if frame_type == "B" else 1]
+            refs = references(k)
             ev = InterRdEvaluator(0)
             (ra, rn, rl), (ma, mn, ml) = cool_chics[k]
             ev.add(frame_type, (ra, rn, ptrs[0]), (ma, mn, ptrs[1]), [done[r] for r in refs], fh.get_value("global_flow"),
@@ -87,7 +120,7 @@ def main():
                 moves = [(f"{r[0].steps[0].n_moves} + {r[0].steps[1].n_moves}", " residue + motion") for r in reports]
             else:
                 moves = [(r[0].step.n_moves, " " + r[0].role) for r in reports]
-        before = reports[0][0].before if reports else after
+            before = reports[0][0].before if reports else after
         print(f"frame {display[k]} ({frame_type}): steps " + ", ".join(f"{n}{role}" for n, role in moves))
         for label, c in (("before", before), ("after", after)):
             print(f"  {label}: {c.bits:.1f} bits, PSNR {c.quality.psnr_db:.4f} dB, cost {c.cost:.9g}")
