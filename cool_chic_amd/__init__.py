@@ -24,6 +24,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    DistortionDeltas.add_inter, rd_inter.InterRdEvaluator
     (intra frames and the residues of the frames that predict from them in one step, claims following the flows)
                                                    RdoqStep.follow, rd_gop.GopDescent
+    nnquant.quantizemodel.quantize_model (the search over the networks' quantisation steps, one test pass per candidate)
+                                                   nnquant.NetworkQuantiser (every candidate of a module in one batch)
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -51,6 +53,10 @@ def __getattr__(name):
         from .rdoq import RdoqStep
 
         return RdoqStep
+    if name in ("NetworkQuantiser", "QuantisedNetwork"):
+        from . import nnquant
+
+        return getattr(nnquant, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -120,6 +120,12 @@ int derive_geometry(ccd_cc_header* h) {
 }
 }  // namespace
 
+int q_step_table(int group, int* log2_first) {
+    if (group < 0 || group >= 8) return 0;
+    *log2_first = kQStep[group].log2_first;
+    return kQStep[group].n;
+}
+
 int read_cc_header(const uint8_t* p, size_t n, ccd_cc_header* h) {
     std::memset(h, 0, sizeof(*h));
     BitReader br(p, n);

@@ -43,6 +43,9 @@ struct CodedFrame {
 int coding_structure(const ccd_video_header& h, std::vector<CodedFrame>& out);
 int read_frame_header(const uint8_t* p, size_t n, ccd_frame_header* h);
 int read_cc_header(const uint8_t* p, size_t n, ccd_cc_header* h);  // also fills the derived geometry
+// The header's table of quantisation steps for group 0 .. 7 (nnquant/quantstep.py:26-43): returns its length, the steps are
+// 2^(*log2_first) .. 2^(*log2_first + length - 1).
+int q_step_table(int group, int* log2_first);
 // The header a cool-chic with the transmitted fields of `tmpl`, an NN payload of n_nn bytes and no latent payload would carry,
 // parsed into `out` (a serialise / parse round trip: the derived geometry follows from the transmitted fields alone) and, with
 // `bytes`, as serialised.  CCD_ERR_VALUE for n_layer_synthesis outside 1 .. CCD_MAX_SYN_LAYERS, before anything indexes

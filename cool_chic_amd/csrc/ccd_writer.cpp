@@ -282,6 +282,90 @@ int64_t ccd_encode_network(const ccd_cc_header* arch, const int32_t* values, int
     return static_cast<int64_t>(bytes.size());
 }
 
+// ---- network quantisation -------------------------------------------------------------------
+int64_t ccd_network_values(const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, int32_t* values, int64_t cap) {
+    if (!arch || !bytes_nn || !values) return CCD_ERR_ARG;
+    ccd_cc_header h;
+    int rc = rederive_cc_header(*arch, n_nn, &h);
+    if (rc < 0) return rc;
+    size_t n_kind[8];
+    rc = network_layout(h, n_kind);
+    if (rc < 0) return rc;
+    std::vector<int> count;
+    for (int k = 0; k < 8; ++k) count.insert(count.end(), n_kind[k], h.nn_expgol_cnt[k]);
+    if (cap < static_cast<int64_t>(count.size())) return CCD_ERR_ARG;
+    std::vector<int64_t> ints;
+    rc = decode_exp_golomb(bytes_nn, n_nn, h.nn_n_bit_pad, count, ints);
+    if (rc < 0) return rc;
+    if (ints.size() != count.size()) return CCD_ERR_INVALID_DATA;
+    for (int64_t v : ints) if (v < INT32_MIN || v > INT32_MAX) return CCD_ERR_VALUE;
+    for (size_t i = 0; i < ints.size(); ++i) values[i] = static_cast<int32_t>(ints[i]);
+    return static_cast<int64_t>(ints.size());
+}
+
+int ccd_q_step_table(int group, int32_t* log2_first) {
+    if (!log2_first || group < 0 || group >= 8) return CCD_ERR_ARG;
+    int first = 0;
+    const int n = q_step_table(group, &first);
+    *log2_first = first;
+    return n;
+}
+
+int ccd_quantise_network(const ccd_cc_header* arch, const float* x, int64_t n_values, const int32_t q_step_log2[8],
+                         int32_t* values) {
+    if (!arch || !x || !q_step_log2 || !values) return CCD_ERR_ARG;
+    int64_t n_kind[8];
+    const int rc = ccd_network_layout(arch, n_kind);
+    if (rc < 0) return rc;
+    int64_t total = 0;
+    for (int k = 0; k < 8; ++k) {
+        int first = 0;
+        const int n = q_step_table(k, &first);
+        if (q_step_log2[k] < first || q_step_log2[k] >= first + n) return CCD_ERR_VALUE;
+        total += n_kind[k];
+    }
+    if (total != n_values) return CCD_ERR_ARG;
+    for (int k = 0; k < 8; ++k)
+        for (int64_t i = 0; i < n_kind[k]; ++i, ++x, ++values) {
+            if (!std::isfinite(*x)) return CCD_ERR_VALUE;
+            // x / 2^q in float32 (exact, or rounded once where the quotient is subnormal), then to the nearest integer, ties to even
+            const float r = std::nearbyintf(std::ldexp(*x, -q_step_log2[k]));
+            if (!(r >= -2147483648.0f && r < 2147483648.0f)) return CCD_ERR_VALUE;
+            *values = static_cast<int32_t>(r);
+        }
+    return CCD_OK;
+}
+
+int ccd_network_best_expgol(const ccd_cc_header* arch, const int32_t* values, int64_t n_values, int32_t order[8],
+                            int64_t n_bits[8]) {
+    if (!arch || !values || !order || !n_bits) return CCD_ERR_ARG;
+    int64_t n_kind[8];
+    const int rc = ccd_network_layout(arch, n_kind);
+    if (rc < 0) return rc;
+    int64_t total = 0;
+    for (int k = 0; k < 8; ++k) total += n_kind[k];
+    if (total != n_values) return CCD_ERR_ARG;
+    constexpr int kMaxOrder = 12;  // what read_cc_header accepts
+    const int32_t* v = values;
+    for (int k = 0; k < 8; ++k) {
+        int64_t bits[kMaxOrder + 1] = {};
+        for (int64_t i = 0; i < n_kind[k]; ++i, ++v) {
+            // the code ccd_encode_network writes: len - count zeros, then the len + 1 bits of y
+            const uint64_t u = *v <= 0 ? static_cast<uint64_t>(-2 * static_cast<int64_t>(*v)) : static_cast<uint64_t>(2 * static_cast<int64_t>(*v) - 1);
+            for (int count = 0; count <= kMaxOrder; ++count) {
+                const uint64_t y = u + (uint64_t{1} << count);
+                int len = 0;
+                while ((y >> len) > 1) ++len;
+                bits[count] += 2 * len - count + 1;
+            }
+        }
+        order[k] = 0;
+        for (int count = 1; count <= kMaxOrder; ++count) if (bits[count] < bits[order[k]]) order[k] = count;
+        n_bits[k] = bits[order[k]];
+    }
+    return CCD_OK;
+}
+
 int ccd_write_cc_header(const ccd_cc_header* h, uint8_t* out, size_t cap) {
     if (!h || !out || h->n_layer_synthesis < 1 || h->n_layer_synthesis > CCD_MAX_SYN_LAYERS) return CCD_ERR_ARG;
     const std::vector<uint8_t> b = cc_header_bytes(*h, h->n_bytes_latent);

@@ -70,6 +70,54 @@ def encode_network(arch: CCHeader, values: np.ndarray) -> bytes:
     return payload
 
 
+MAX_NN_BYTES = (1 << 14) - 1  # the header's nn_n_bytes field
+
+
+def q_step_range(group: int) -> range:
+    """log2 of every quantisation step the header can name for this group, finest first."""
+    first = C.c_int32()
+    n = check(lib().ccd_q_step_table(int(group), C.byref(first)), "ccd_q_step_table")
+    return range(first.value, first.value + n)
+
+
+def network_values(arch: CCHeader, bytes_nn: bytes) -> np.ndarray:
+    """The transmitted integers of an NN payload in stream order (int32): what encode_network takes."""
+    out = np.empty(sum(network_layout(arch)), np.int32)
+    n = check(lib().ccd_network_values(C.byref(arch), bytes_nn, len(bytes_nn), out.ctypes.data, out.size), "ccd_network_values")
+    return out[:n]
+
+
+def quantise_network(arch: CCHeader, values: np.ndarray, q_step_log2: Sequence[int]) -> np.ndarray:
+    """rint(x / 2^q) per group in float32, ties to even: float parameters in stream order -> int32 (ccd.h)."""
+    x = np.ascontiguousarray(values, dtype=np.float32)
+    q = np.ascontiguousarray(q_step_log2, dtype=np.int32)
+    if q.shape != (8,):
+        raise ValueError("one step per group: 8 values")
+    out = np.empty(x.size, np.int32)
+    check(lib().ccd_quantise_network(C.byref(arch), x.ctypes.data, x.size, q.ctypes.data, out.ctypes.data), "ccd_quantise_network")
+    return out
+
+
+def dequantise_network(arch: CCHeader, values: np.ndarray, q_step_log2: Sequence[int] = None) -> np.ndarray:
+    """int x 2^q per group in float32, the value a decoder multiplies out (steps of `arch` unless given): quantise_network's
+    inverse wherever the product is exact in float32."""
+    q = list(arch.nn_q_step_log2) if q_step_log2 is None else [int(v) for v in q_step_log2]
+    ints = np.asarray(values)
+    layout = network_layout(arch)
+    if ints.size != sum(layout):
+        raise ValueError("%d values, the layout wants %d" % (ints.size, sum(layout)))
+    step = np.repeat(np.ldexp(np.float32(1), np.asarray(q, np.int32)).astype(np.float32), layout)
+    return ints.astype(np.float32) * step
+
+
+def best_expgol(arch: CCHeader, values: np.ndarray):
+    """([order per group], [bits per group]): the Exp-Golomb orders 0 .. 12 that code `values` shortest (ccd.h)."""
+    v = np.ascontiguousarray(values, dtype=np.int32)
+    order, bits = (C.c_int32 * 8)(), (C.c_int64 * 8)()
+    check(lib().ccd_network_best_expgol(C.byref(arch), v.ctypes.data, v.size, order, bits), "ccd_network_best_expgol")
+    return list(order), list(bits)
+
+
 def encode_coolchic(arch: CCHeader, bytes_nn: bytes, latents: Sequence[np.ndarray], device=None) -> bytes:
     """Cool-chic header + NN payload + range-coded latents of one cool-chic (bitstream/encode.py:83-92).
     device=None: the host writer; an integer: the device writer on that GPU (encoder.EncodeBatch, same bytes)."""

@@ -346,6 +346,24 @@ int ccd_network_layout(const ccd_cc_header* arch, int64_t n_values[8]);
  * byte count (malloc'ed *out, free with ccd_free); *n_bit_pad = prefix padding bits for the header. */
 int64_t ccd_encode_network(const ccd_cc_header* arch, const int32_t* values, int64_t n_values, int32_t* n_bit_pad,
                            uint8_t** out);
+/* ---- network quantisation (host only; cool_chic_amd/nnquant.py) --------------------------------
+ * The transmitted integers of an NN payload in stream order (the groups of ccd_network_layout, Exp-Golomb orders and padding
+ * from `arch`): what ccd_encode_network takes.  Returns their number; CCD_ERR_ARG when `cap` is smaller, CCD_ERR_VALUE for an
+ * integer outside int32, else what the payload parser refuses. */
+int64_t ccd_network_values(const ccd_cc_header* arch, const uint8_t* bytes_nn, size_t n_nn, int32_t* values, int64_t cap);
+/* The header's table of quantisation steps of group 0 .. 7 (nnquant/quantstep.py:26-43): returns its length n and sets
+ * *log2_first; the steps are 2^(*log2_first) .. 2^(*log2_first + n - 1).  CCD_ERR_ARG for another group or a null pointer. */
+int ccd_q_step_table(int group, int32_t* log2_first);
+/* values[i] = rint(x[i] / 2^q_step_log2[group of i]) in float32, ties to even (torch.round(x / q); the division by a power of
+ * two is exact): float parameters in stream order -> the integers a decoder multiplies by the same steps.  CCD_ERR_VALUE for
+ * a step outside the header's table of its group (counts 9 17 9 17 13 1 13 25 from log2 -8 -16 -8 -16 -12 0 -12 -24), for a
+ * non-finite x and for a result outside int32; CCD_ERR_ARG when n_values is not the layout's total. */
+int ccd_quantise_network(const ccd_cc_header* arch, const float* x, int64_t n_values, const int32_t q_step_log2[8],
+                         int32_t* values);
+/* Per group the Exp-Golomb order 0 .. 12 whose code of the group's values is shortest (counted, ties to the smaller order,
+ * 0 for an empty group) and that length in bits: an encode with these orders has ceil(sum of n_bits / 8) bytes. */
+int ccd_network_best_expgol(const ccd_cc_header* arch, const int32_t* values, int64_t n_values, int32_t order[8],
+                            int64_t n_bits[8]);
 /* Header writers, AbstractHeader.to_bytes (header.py:90-105); n_bytes_header is computed. Return bytes written. */
 int ccd_write_cc_header(const ccd_cc_header* h, uint8_t* out, size_t cap); /* transmitted fields only */
 int ccd_write_frame_header(const ccd_frame_header* f, uint8_t* out, size_t cap);

@@ -28,6 +28,13 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     without the margin, run + wait beside the same candidate without dependents (median of 5, min, max), the
                     round's time split into float path, conversion, dep kernel and squared-error split, conflicts per grid
 
+  --networks        instead of the above: the search over the networks' quantisation steps (NetworkQuantiser, DESIGN.md section
+                    4.18) on a Kodak-size intra frame and on the 1080p I frame of gop1080p33, the stream's own networks dequantised,
+                    the source the decoded frame plus seeded noise of +-3 LSB: wall time of one sweep per module (median of 5, min,
+                    max), candidates per launch, device memory taken, the share of that spent building the candidates on the host, the same candidates (built outside the
+                    timer) priced one at a time through RdEvaluator (one evaluator per candidate: add, evaluate, close) and the ratio; for the Kodak-size frame at three lambdas
+                    the cost, network bytes and PSNR of the searched network beside the stream's own, and after descend(8)
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -679,6 +686,87 @@ def measure_follow(stream_bytes, runs, lmbda, rounds, grids, n_probe_slots):
     return res
 
 
+def measure_networks(hdr, nn, payload, bitdepth, fdt, runs, lmbdas, descend_steps):
+    """NetworkQuantiser.search on one intra cool-chic: the tables' wall times over `runs` searches at lmbdas[0], the yardstick
+    (every feasible candidate of those tables through an RdEvaluator of its own) and, per lambda, what the search reached."""
+    import time
+
+    import numpy as np
+
+    import cool_chic_amd
+    from cool_chic_amd import NetworkQuantiser
+    from cool_chic_amd.batch import FRAME_DATA_TYPES
+    from cool_chic_amd.nnquant import MODULES, build_network
+
+    dec = DecodeBatch(0)
+    dec.add(hdr, nn, payload, bitdepth, fdt)
+    dec.run(); dec.wait()
+    arch = dec.header(0)
+    rng = np.random.default_rng(18)
+    maxv = 2 ** bitdepth - 1
+    planes = [np.clip(p.astype(np.int64) + rng.integers(-3, 4, p.shape), 0, maxv).astype(p.dtype) for p in dec.planes(0)]
+    source = _planes_to_frame_data(planes, bitdepth, FRAME_DATA_TYPES[fdt])
+    latents = [torch.from_numpy(dec.latent(0, g)).cuda() for g in range(arch.n_grids)]
+    ptrs = [t.data_ptr() for t in latents]
+    dec.close()
+    floats = writer.dequantise_network(arch, writer.network_values(arch, nn))
+    res = {"size": [int(v) for v in arch.img_size], "symbols": int(arch.n_symbols), "parameters": int(floats.size), "runs": runs}
+    cool_chic_amd.pool_trim(0)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    nq = NetworkQuantiser(0)
+    searches = []
+    for it in range(1 + runs):
+        out = nq.search(arch, floats, ptrs, source, lmbdas[0], owner=latents)
+        if it > 0:
+            searches.append(out)
+    torch.cuda.synchronize()
+    res["device_mib_taken"] = round((free0 - torch.cuda.mem_get_info(0)[0]) / 2 ** 20, 1)  # the library's block cache after the searches
+    one = searches[0]
+    steps = [writer.q_step_range(g)[0] for g in range(8)]
+    res["modules"] = {}
+    for k, t in enumerate(one.tables):
+        secs = [s.pricing[k].seconds for s in searches]
+        build = [s.pricing[k].build_seconds for s in searches]
+        _, gw, gb = next(m for m in MODULES if m[0] == t.module)
+        nets = []
+        for c in t.cells:
+            if c.feasible:
+                s = list(steps)
+                s[gw], s[gb] = c.q_w, c.q_b
+                nets.append(build_network(arch, floats, s))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for net in nets:  # the yardstick: one candidate at a time through the calls the parent commit has
+            with RdEvaluator(0) as ev:
+                ev.add(net.header, net.bytes_nn, ptrs, source, owner=latents)
+                ev.evaluate(lmbdas[0])
+        alone = time.perf_counter() - t0
+        res["modules"][t.module] = {"candidates": len(t.cells), "feasible": len(nets), "per_launch": one.pricing[k].chunk,
+                                    "sweep_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4), "max": round(max(secs), 4)},
+                                    "of_which_building_candidates_s": round(statistics.median(build), 4),
+                                    "one_at_a_time_s": round(alone, 4), "ratio": round(alone / statistics.median(secs), 2)}
+        if t.chosen is not None:  # (a module without a feasible cell kept its steps)
+            steps[gw], steps[gb] = t.cells[t.chosen].q_w, t.cells[t.chosen].q_b
+    res["reached"] = {}
+    for lmbda in lmbdas:
+        out = nq.search(arch, floats, ptrs, source, lmbda, owner=latents)
+        row = {}
+        for label, a, b in (("stream", arch, nn), ("searched", out.header, out.bytes_nn)):
+            work = [t.clone() for t in latents]
+            with RdEvaluator(0) as ev:
+                ev.add(a, b, [t.data_ptr() for t in work], source, owner=work)
+                c = ev.evaluate(lmbda)[0]
+                row[label] = {"cost": c.cost, "bytes_nn": len(b), "psnr_db": round(c.quality.psnr_db, 4), "bits": round(c.bits, 1)}
+                if descend_steps > 0:
+                    ev.descend(lmbda, descend_steps, grids=(0, 1, 2), rounds=8)
+                    c = ev.evaluate(lmbda)[0]
+                    row[label + f"_descend{descend_steps}"] = {"cost": c.cost, "psnr_db": round(c.quality.psnr_db, 4), "bits": round(c.bits, 1)}
+        row["steps"] = list(out.header.nn_q_step_log2)
+        res["reached"][repr(lmbda)] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
@@ -696,7 +784,25 @@ def main():
     ap.add_argument("--max-steps", type=int, default=400, help="with --inter --joint: steps of a descent at most")
     ap.add_argument("--dependents", action="store_true", help="time the distortion deltas through the direct dependents of an I frame instead")
     ap.add_argument("--follow", action="store_true", help="time an RDOQ step of an I frame whose claims follow the flows into its dependents instead")
+    ap.add_argument("--networks", action="store_true", help="time the search over the networks' quantisation steps instead")
+    ap.add_argument("--network-sets", default="kodak,1080p", help="with --networks: which of the two frames to measure")
     a = ap.parse_args()
+    if a.networks:
+        from cool_chic_amd.bitstream.decode import _split_frame
+        from cool_chic_amd.bitstream.header import VideoHeader
+
+        runs = min(a.runs, 5)
+        line = {"tool": "rd_bench --networks", "runs": runs}
+        if "kodak" in a.network_sets.split(","):
+            line["kodak_512x768"] = measure_networks(*synth.split_image_stream(synth.workload("kodak24")["streams"][0]), 8, 0, runs, [1e-3, 1e-4, 1e-2], 8)
+        if "1080p" in a.network_sets.split(","):
+            rest = VideoHeader().read_header(synth.gop1080p(2)[0])
+            fh, ccs, rest = _split_frame(rest)
+            assert fh.get_value("frame_type") == "I"
+            fdt = ["rgb", "yuv420", "yuv444"].index(fh.get_value("frame_data_type"))
+            line["gop1080p_I"] = measure_networks(ccs[0][0].raw, ccs[0][1], ccs[0][2], fh.get_value("bitdepth"), fdt, runs, [1e-3], 0)
+        print(json.dumps(line))
+        return
     if a.follow:
         line = {"tool": "rd_bench --follow", "runs": a.runs}
         args = (a.runs, a.lmbda, a.rounds, [int(g) for g in a.grids.split(",") if g != ""], a.probe_slots)
