@@ -9,7 +9,8 @@
 // (16 B per symbol algorithmic; bench.py leg `rate_model` reports the achieved GB/s against the 8 TB/s roof).
 // Parity: the REFERENCE's compute_rate on 2^16 symbols (tests/golden/rate.npz, tests/golden/gen/dump_rate.py), within 2e-6
 // relative + 2e-6 bits + 3e-7 / p bits per symbol (the last term is the formula's own conditioning: p is a difference of
-// two CDF values; tests/test_gpu_parity.py).
+// two CDF values; tests/test_gpu_parity.py), and the same tolerance against the formula in float64 over the whole scale table,
+// around the expm1 switch and beyond the table, every launch path bit for bit (tests/test_rate_model.py).  NaN in, NaN out.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,8 +54,10 @@ __device__ __forceinline__ float symbol_rate(float xi, float m, float s) {
     float r = __builtin_amdgcn_rcpf(s);
     r = __builtin_fmaf(__builtin_fmaf(-s, r, 1.0f), r, r);
     float p = laplace_cdf(xi + 0.5f, m, r) - laplace_cdf(xi - 0.5f, m, r);
-    p = fmaxf(p, 1.52587890625e-05f);  // 2^-16: no symbol costs more than 16 bits
-    return -__builtin_amdgcn_logf(p);  // v_log_f32 = log2; p is a normal number in [2^-16, 1]
+    // 2^-16: no symbol costs more than 16 bits.  A compare and select, NOT fmaxf: fmaxf(NaN, c) is c, which would price a NaN in
+    // x, mu or scale at exactly 16 bits; the reference's clamp_min hands the NaN on, and so does this (NaN < c is false)
+    p = p < 1.52587890625e-05f ? 1.52587890625e-05f : p;
+    return -__builtin_amdgcn_logf(p);  // v_log_f32 = log2; p is a normal number in [2^-16, 1], or NaN
 }
 
 // 16 B/symbol of HBM traffic and ~45 VALU instructions: HBM-bound.  Every lane moves 16 bytes per array and iteration

@@ -476,7 +476,14 @@ size_t ccd_enc_payload_bound(int64_t n_symbols);
 
 /* ---- rate model (reference: coolchic/component/core/arm.py:448-485 compute_rate / _laplace_cdf, float32) ------
  * rate[i] = -log2(max(cdf(x+0.5) - cdf(x-0.5), 2^-16)) with the continuous Laplace(mu, scale) of the reference.
- * x, mu, scale, rate (optional), total_bits (optional, one double) are DEVICE pointers; asynchronous on `stream`. */
+ * x, mu, scale, rate (optional), total_bits (optional, one double) are DEVICE pointers; asynchronous on `stream`.
+ * x, mu, scale and rate are arrays of n floats each, at any 4-byte alignment (all four 16-byte aligned: the vector kernel);
+ * exactly n floats of rate are written.  total_bits is overwritten (its value before the call does not matter) with the sum
+ * of the n rates in float64; with n == 0 it becomes 0.0 and rate is not touched.  Both outputs may be asked for in one call.
+ * NaN in, NaN out: a NaN in x[i], mu[i] or scale[i] gives rate[i] = NaN (never the 16 bits of the clamp) and a NaN total.
+ * scale[i] is a positive normal float; for any other scale (zero, negative, subnormal, infinite), or an infinite x or mu, the
+ * values are unspecified, but no memory access depends on the values.  CCD_ERR_ARG for a NULL x, mu or scale, n < 0, or both
+ * outputs NULL (checked before the device is touched). */
 int ccd_compute_rate(int device, void* stream, const float* x, const float* mu, const float* scale, int64_t n,
                      float* rate, double* total_bits);
 
