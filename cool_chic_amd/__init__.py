@@ -26,6 +26,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    RdoqStep.follow, rd_gop.GopDescent
     nnquant.quantizemodel.quantize_model (the search over the networks' quantisation steps, one test pass per candidate)
                                                    nnquant.NetworkQuantiser (every candidate of a module in one batch)
+    (the same search for the two cool-chics of a P / B frame: candidates reconstructed and scored on the device, many per launch)
+                                                   iscore.InterScore, nnquant_inter.InterNetworkQuantiser
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -57,6 +59,14 @@ def __getattr__(name):
         from . import nnquant
 
         return getattr(nnquant, name)
+    if name == "InterScore":
+        from .iscore import InterScore
+
+        return InterScore
+    if name in ("InterNetworkQuantiser", "QuantisedInterNetworks"):
+        from . import nnquant_inter
+
+        return getattr(nnquant_inter, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -104,6 +104,12 @@ class RdoqFollow(C.Structure):
                 ("warp_filter_size", C.c_int32), ("target", C.c_int32), ("frozen", C.c_int32)]
 
 
+class IScoreFrame(C.Structure):
+    _fields_ = [("frame_type", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("bitdepth", C.c_int32), ("frame_data_type", C.c_int32),
+                ("residue", C.c_void_p), ("motion", C.c_void_p), ("ref0", C.c_void_p * 3), ("ref1", C.c_void_p * 3), ("src", C.c_void_p * 3),
+                ("global_flow", C.c_int32 * 4), ("warp_filter_size", C.c_int32)]
+
+
 class Video(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("frames", C.POINTER(Frame))]
 
@@ -249,6 +255,15 @@ SIGNATURES = {
     "ccd_rdoq_slot_dep_sse": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     "ccd_rdoq_slot_reach": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ccd_rdoq_slot_flow_boxes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_iscore_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "ccd_iscore_destroy": (None, [C.c_void_p]),
+    "ccd_iscore_add_frame": (C.c_int, [C.c_void_p, C.POINTER(IScoreFrame)]),
+    "ccd_iscore_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ccd_iscore_clear_items": (C.c_int, [C.c_void_p]),
+    "ccd_iscore_run": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_iscore_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ccd_iscore_frame_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ccd_iscore_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ccd_debug_laplace_sweep": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccd_debug_laplace_bounds": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),

@@ -189,6 +189,18 @@ struct DsensDepJob {
     int32_t stride, py, px;    // the pass's lattice
     LatticeAxis ay, ax;        // rows, columns
 };
+// One candidate of one P / B frame as inter_score_kernel sees it (ccd_inter.hip).  `recon` is the frame as
+// dsens_inter_kernel would reconstruct it (mode 0: the frame's base pair, which keeps the warps; 1: another residue output, which
+// reads them; 2: another motion output) - its planes are never stored, recon.plane stays null: the squared error of every sample
+// against `src` is summed instead, per plane, one partial per workgroup.
+struct InterScoreJob {
+    DsensInterJob recon;
+    const void* src[3];        // the frame's source planes
+    uint32_t part_first;       // workgroup k of the job owns the partials [3 (part_first + k), 3 (part_first + k) + 3)
+    uint32_t pad;
+};
+// The partials of one job as inter_score_final_kernel sums them: workgroups [first, first + count) of the partial array.
+struct InterScoreRange { uint32_t first, count; };
 // One grid of a candidate with dependents as dsens_dep_final_kernel sees it (ccd_dsens.hip): entry e of [2][h][w] becomes INT64_MIN
 // where the move leaves the alphabet or the entry is flagged, and the flagged legal entries are counted.
 struct DsensDepGrid {

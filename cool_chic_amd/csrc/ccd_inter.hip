@@ -556,6 +556,95 @@ hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix,
     return hipGetLastError();
 }
 
+// ---- the squared error of many candidates of P / B frames in one launch (ccd_iscore).  A job is one candidate of
+// one frame: the frame's two float outputs with one of them replaced.  Tiles, units and modes are dsens_inter_kernel's, and so are
+// the operations per unit (di_pixel, then the sample helpers in planes_kernel's quad order); where that kernel stores a sample this
+// one takes (sample - source)^2, as integers, so the sums are those of ccd_inter_reconstruct followed by the quality meter.  No
+// plane is stored.  Reduction as quality_sse_kernel: u64 per lane and plane, wave shuffle, the four wave partials through LDS, one
+// thread stores the workgroup's three partials; inter_score_final_kernel adds a job's partials in a fixed order.  Plain vector
+// stores; no atomics, no waits on other workgroups.
+__device__ __forceinline__ uint64_t is_wave_sum(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(static_cast<unsigned long long>(v), off, 64);
+    return v;
+}
+__device__ __forceinline__ uint64_t is_sq(unsigned q, int src) {
+    const int64_t d = static_cast<int64_t>(q) - src;
+    return static_cast<uint64_t>(d * d);
+}
+
+template <int NT>  // as dsens_inter_kernel
+__global__ __launch_bounds__(256) void inter_score_kernel(const InterScoreJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs,
+                                                          uint64_t* __restrict__ part) {
+    __shared__ uint64_t wave_part[3][4];
+    const uint32_t blk = blockIdx.x;
+    const int j = entry_of(prefix, n_jobs, blk);
+    const InterScoreJob& S = jobs[j];  // (uniform: scalar loads)
+    const DsensInterJob& J = S.recon;
+    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
+    int ux, uy;
+    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
+    const int cs = J.chroma_shift;
+    uint64_t e0 = 0, e1 = 0, e2 = 0;
+    if (ux < (J.W >> cs) && uy < (J.H >> cs)) {  // (every thread reaches the barrier below)
+        const float maxv = J.maxv;
+        float v[3], sum1 = 0.0f, sum2 = 0.0f;  // planes_kernel's order over the quad: dy outer, dx inner
+        const int n = cs ? 4 : 1;              // one loop body for both shapes: the warp is instantiated once
+#pragma unroll 1
+        for (int q = 0; q < n; ++q) {
+            const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
+            di_pixel<NT>(J, y, x, v);
+            const size_t i = static_cast<size_t>(y) * J.W + x;
+            e0 += is_sq(quantise_sample(v[0], maxv), di_load(S.src[0], i, J.wide));
+            if (!cs) {
+                e1 = is_sq(quantise_sample(v[1], maxv), di_load(S.src[1], i, J.wide));
+                e2 = is_sq(quantise_sample(v[2], maxv), di_load(S.src[2], i, J.wide));
+            } else {
+                sum1 += round_to_grid(v[1], maxv);
+                sum2 += round_to_grid(v[2], maxv);
+            }
+        }
+        if (cs) {
+            const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
+            e1 = is_sq(quantise_chroma420(sum1, maxv), di_load(S.src[1], ci, J.wide));
+            e2 = is_sq(quantise_chroma420(sum2, maxv), di_load(S.src[2], ci, J.wide));
+        }
+    }
+    e0 = is_wave_sum(e0); e1 = is_wave_sum(e1); e2 = is_wave_sum(e2);
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) { wave_part[0][tid >> 6] = e0; wave_part[1][tid >> 6] = e1; wave_part[2][tid >> 6] = e2; }
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t* out = part + (static_cast<size_t>(S.part_first) + local) * 3;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) out[p] = wave_part[p][0] + wave_part[p][1] + wave_part[p][2] + wave_part[p][3];
+    }
+}
+
+// One wave per (job, plane): adds the job's workgroup partials of the plane, lane-strided, then the shuffle tree.
+__global__ __launch_bounds__(64) void inter_score_final_kernel(const InterScoreRange* __restrict__ ranges, const uint64_t* __restrict__ part,
+                                                               uint64_t* __restrict__ sse) {
+    const uint32_t r = blockIdx.x / 3, p = blockIdx.x % 3;
+    const InterScoreRange R = ranges[r];
+    uint64_t acc = 0;
+    for (uint32_t i = threadIdx.x; i < R.count; i += 64) acc += part[(static_cast<size_t>(R.first) + i) * 3 + p];
+    acc = is_wave_sum(acc);
+    if (threadIdx.x == 0) sse[static_cast<size_t>(r) * 3 + p] = acc;
+}
+
+hipError_t launch_inter_score(const InterScoreJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, uint64_t* d_part,
+                              hipStream_t stream) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    if (sinc8) hipLaunchKernelGGL(inter_score_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs, d_part);
+    else hipLaunchKernelGGL(inter_score_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs, d_part);
+    return hipGetLastError();
+}
+hipError_t launch_inter_score_final(const InterScoreRange* d_ranges, int n_ranges, const uint64_t* d_part, uint64_t* d_sse, hipStream_t stream) {
+    if (n_ranges <= 0) return hipSuccess;
+    hipLaunchKernelGGL(inter_score_final_kernel, dim3(static_cast<uint32_t>(n_ranges) * 3), dim3(64), 0, stream, d_ranges, d_part, d_sse);
+    return hipGetLastError();
+}
+
 // ---- where the samples of a dependent frame read its reference, in cells of the RDOQ claim raster (ccd_rdoq_follow; DESIGN.md
 // 4.17).  A job is one follow: the dependent F's flows into its reference `which`.  A workgroup is one wave and one cell C of F,
 // a lane per luma sample of the cell: (a) the interval of reference indices the sample's window reads per axis (ic_window_axis,

@@ -1,0 +1,216 @@
+// ccd_iscore_api.cpp - ccd_iscore_* of include/ccd.h: the squared error of many candidates of P / B frames per launch (DESIGN.md
+// section 4.19).  A candidate is a frame with the float output of one of its two cool-chics replaced; inter_score_kernel
+// (ccd_inter.hip) reconstructs, quantises and scores it without storing a plane.
+#include <cstring>
+#include <new>
+
+#include "ccd_host.hpp"
+#include "ccd_iscore_plan.hpp"
+#include "ccd_kernels.hpp"
+
+using namespace ccd;
+
+namespace {
+struct Frame {
+    ccd_iscore_frame in;
+    Block buf;                 // [references as 4:4:4 f32][the base pair's warped references]
+    float* ref_f32[2] = {};
+    float* warped[2] = {};
+};
+struct Item { int frame, role; const float* output; };
+struct Launch { size_t jobs = 0, prefix = 0; int n_jobs = 0; uint32_t n_blocks = 0; };  // offsets into the tables block
+
+// the frame with `output` in place of the output of cool-chic `role` (-1: the frame's own pair, which keeps the warps)
+InterScoreJob make_job(const Frame& f, int role, const float* output, uint32_t part_first) {
+    InterScoreJob S;
+    std::memset(&S, 0, sizeof(S));
+    DsensInterJob& J = S.recon;
+    const ccd_iscore_frame& in = f.in;
+    const bool two = in.frame_type == 2;
+    J.residue = role == 0 ? output : in.residue;
+    J.motion = role == 1 ? output : in.motion;
+    J.ref0 = f.ref_f32[0]; J.ref1 = two ? f.ref_f32[1] : f.ref_f32[0];
+    J.w0 = f.warped[0]; J.w1 = f.warped[1];
+    J.mode = role < 0 ? 0 : (role == 0 ? 1 : 2);
+    J.frame_type = in.frame_type;
+    J.H = in.h; J.W = in.w;
+    J.n_taps = in.warp_filter_size;
+    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? in.global_flow[i] : 0;
+    J.chroma_shift = in.frame_data_type == 1 ? 1 : 0;
+    J.wide = in.bitdepth > 8;
+    J.tiles_x = iscore_tiles_x(in.w, J.chroma_shift);
+    J.maxv = static_cast<float>((1 << in.bitdepth) - 1);
+    for (int p = 0; p < 3; ++p) S.src[p] = in.src[p];
+    S.part_first = part_first;
+    return S;
+}
+}  // namespace
+
+struct ccd_iscore {
+    int device = 0;
+    std::vector<std::unique_ptr<Frame>> frames;
+    std::vector<Item> items;
+    Mirror tables, out;        // job tables (up); uint64 sse[results][3] (down)
+    Block part;                // uint64 [workgroups][3]
+    std::vector<IScoreSlot> plan;  // of the run in flight / last finished: frames first, then items
+    int pending = 0;
+    int done_frames = 0, done_items = 0;  // what the last finished run covered
+    StreamSet streams;
+};
+
+extern "C" {
+
+int ccd_iscore_create(int device, ccd_iscore** out) {
+    if (!out) return CCD_ERR_ARG;
+    *out = nullptr;
+    ccd_iscore* s = new (std::nothrow) ccd_iscore();
+    if (!s) return CCD_ERR_NOMEM;
+    s->device = device;
+    *out = s;
+    return CCD_OK;
+}
+
+void ccd_iscore_destroy(ccd_iscore* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)s->streams.drain();
+    for (auto& f : s->frames) f->buf.drop();
+    s->tables.drop(); s->out.drop(); s->part.drop();
+    delete s;
+}
+
+int ccd_iscore_add_frame(ccd_iscore* s, const ccd_iscore_frame* frame) {
+    if (!s || !frame || !frame->residue || !frame->motion) return CCD_ERR_ARG;
+    if (frame->frame_type < 1 || frame->frame_type > 2 || frame->bitdepth < 8 || frame->bitdepth > 16 || frame->frame_data_type < 0 ||
+        frame->frame_data_type > 2)
+        return CCD_ERR_ARG;
+    for (int p = 0; p < 3; ++p)
+        if (!frame->ref0[p] || !frame->src[p] || (frame->frame_type == 2 && !frame->ref1[p])) return CCD_ERR_ARG;
+    if (s->pending) return CCD_ERR_ARG;
+    if (!warp_filter_ok(frame->warp_filter_size)) return CCD_ERR_VALUE;
+    if (frame->h < 1 || frame->w < 1 || frame->h > kIScoreMaxSide || frame->w > kIScoreMaxSide) return CCD_ERR_VALUE;
+    if (!yuv420_sides_ok(frame->frame_data_type, frame->h, frame->w)) return CCD_ERR_VALUE;
+    std::unique_ptr<Frame> fp(new (std::nothrow) Frame());
+    if (!fp) return CCD_ERR_NOMEM;
+    fp->in = *frame;
+    // ---- the device from here on ----
+    HIP_TRY(hipSetDevice(s->device));
+    const int n_refs = frame->frame_type == 2 ? 2 : 1;
+    const size_t f32_3 = align256(static_cast<size_t>(3) * frame->h * frame->w * sizeof(float));
+    if (!fp->buf.get(s->device, BlockPool::kDevice, 2 * n_refs * f32_3)) return CCD_ERR_NOMEM;
+    char* at = fp->buf.as<char>();
+    for (int r = 0; r < n_refs; ++r, at += f32_3) fp->ref_f32[r] = reinterpret_cast<float*>(at);
+    for (int r = 0; r < n_refs; ++r, at += f32_3) fp->warped[r] = reinterpret_cast<float*>(at);
+    s->frames.push_back(std::move(fp));
+    return static_cast<int>(s->frames.size()) - 1;
+}
+
+int ccd_iscore_add(ccd_iscore* s, int frame, int role, const float* output) {
+    if (!s || !output || role < 0 || role > 1 || frame < 0) return CCD_ERR_ARG;
+    if (frame >= static_cast<int>(s->frames.size()) || s->pending) return CCD_ERR_ARG;
+    if (s->items.size() >= static_cast<size_t>(kIScoreMaxItems)) return CCD_ERR_UNSUPPORTED;
+    s->items.push_back(Item{frame, role, output});
+    return static_cast<int>(s->items.size()) - 1;
+}
+
+int ccd_iscore_clear_items(ccd_iscore* s) {
+    if (!s || s->pending) return CCD_ERR_ARG;
+    s->items.clear();
+    s->done_items = 0;
+    return CCD_OK;
+}
+
+int ccd_iscore_run(ccd_iscore* s, void* stream) {
+    if (!s || s->pending) return CCD_ERR_ARG;
+    if (s->frames.empty()) return CCD_OK;
+    const size_t n_frames = s->frames.size(), n_items = s->items.size(), n_results = n_frames + n_items;
+    std::vector<IScoreGeo> geo(n_frames);
+    for (size_t f = 0; f < n_frames; ++f) {
+        const ccd_iscore_frame& in = s->frames[f]->in;
+        geo[f] = IScoreGeo{in.h, in.w, in.frame_data_type == 1 ? 1 : 0, in.warp_filter_size == 8 ? 1 : 0};
+    }
+    std::vector<int> item_frame(n_items);
+    for (size_t i = 0; i < n_items; ++i) item_frame[i] = s->items[i].frame;
+    uint32_t class_blocks[kIScoreClasses], total_blocks = 0;
+    const int rc = iscore_plan(geo, item_frame, s->plan, class_blocks, &total_blocks);
+    if (rc < 0) return rc;
+    std::vector<InterScoreJob> jobs[kIScoreClasses];
+    std::vector<uint32_t> prefix[kIScoreClasses];
+    for (auto& p : prefix) p.push_back(0);
+    std::vector<InterScoreRange> ranges(n_results);
+    for (size_t r = 0; r < n_results; ++r) {
+        const IScoreSlot& P = s->plan[r];
+        const Item* it = r < n_frames ? nullptr : &s->items[r - n_frames];
+        const Frame& f = *s->frames[it ? it->frame : r];
+        jobs[P.cls].push_back(make_job(f, it ? it->role : -1, it ? it->output : nullptr, P.part_first));
+        prefix[P.cls].push_back(prefix[P.cls].back() + P.n_blocks);
+        ranges[r] = InterScoreRange{P.part_first, P.n_blocks};
+    }
+    TableImage img;
+    Launch L[kIScoreClasses];
+    for (int c = 0; c < kIScoreClasses; ++c) {
+        L[c].n_jobs = static_cast<int>(jobs[c].size()); L[c].n_blocks = class_blocks[c];
+        L[c].jobs = img.put(jobs[c]); L[c].prefix = img.put(prefix[c]);
+    }
+    const size_t off_ranges = img.put(ranges);
+    // ---- the device from here on ----
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // nothing of an earlier run is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
+    if (!s->tables.ensure(s->device, img.bytes.size()) || !s->out.ensure(s->device, n_results * 3 * sizeof(uint64_t)) ||
+        !s->part.ensure(s->device, BlockPool::kDevice, std::max<size_t>(256, static_cast<size_t>(total_blocks) * 3 * sizeof(uint64_t))))
+        return CCD_ERR_NOMEM;
+    std::memcpy(s->tables.host.p, img.bytes.data(), img.bytes.size());
+    s->streams.note(st);
+    HIP_TRY(s->tables.upload(img.bytes.size(), st));
+    for (const auto& fp : s->frames) {  // the references as the warp reads them
+        const ccd_iscore_frame& in = fp->in;
+        for (int r = 0; r < (in.frame_type == 2 ? 2 : 1); ++r) {
+            const void* const* pl = r ? in.ref1 : in.ref0;
+            HIP_TRY(launch_planes_to_444(pl[0], pl[1], pl[2], fp->ref_f32[r], in.h, in.w, in.bitdepth, in.frame_data_type, st));
+        }
+    }
+    const char* base = s->tables.dev.as<char>();
+    for (int c = 0; c < kIScoreClasses; ++c)  // the base pairs first: the residue candidates read the warps they keep
+        HIP_TRY(launch_inter_score(reinterpret_cast<const InterScoreJob*>(base + L[c].jobs), reinterpret_cast<const uint32_t*>(base + L[c].prefix),
+                                   L[c].n_jobs, L[c].n_blocks, c & 1, s->part.as<uint64_t>(), st));
+    HIP_TRY(launch_inter_score_final(reinterpret_cast<const InterScoreRange*>(base + off_ranges), static_cast<int>(n_results), s->part.as<uint64_t>(),
+                                     s->out.dev.as<uint64_t>(), st));
+    HIP_TRY(s->out.download(n_results * 3 * sizeof(uint64_t), st));
+    s->pending = 1;
+    return CCD_OK;
+}
+
+int ccd_iscore_wait(ccd_iscore* s, void* stream) {
+    if (!s) return CCD_ERR_ARG;
+    if (!s->pending) return CCD_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    s->pending = 0;
+    s->done_frames = static_cast<int>(s->frames.size());
+    s->done_items = static_cast<int>(s->items.size());
+    return CCD_OK;
+}
+
+static int iscore_result(const ccd_iscore* s, const ccd_iscore_frame& in, size_t r, uint64_t* sse, uint64_t* n) {
+    const uint64_t* out = s->out.host.as<uint64_t>() + r * 3;
+    const uint64_t luma = static_cast<uint64_t>(in.h) * in.w;
+    const uint64_t chroma = in.frame_data_type == 1 ? static_cast<uint64_t>(in.h / 2) * (in.w / 2) : luma;
+    for (int p = 0; p < 3; ++p) { sse[p] = out[p]; n[p] = p ? chroma : luma; }
+    return CCD_OK;
+}
+
+int ccd_iscore_frame_result(const ccd_iscore* s, int frame, uint64_t* sse, uint64_t* n) {
+    if (!s || !sse || !n || frame < 0) return CCD_ERR_ARG;
+    if (s->pending || frame >= s->done_frames) return CCD_ERR_ARG;
+    return iscore_result(s, s->frames[frame]->in, frame, sse, n);
+}
+
+int ccd_iscore_result(const ccd_iscore* s, int item, uint64_t* sse, uint64_t* n) {
+    if (!s || !sse || !n || item < 0) return CCD_ERR_ARG;
+    if (s->pending || item >= s->done_items) return CCD_ERR_ARG;
+    // (frames added after the run sit behind the items of the finished run in no table: the run's own frame count places the item)
+    return iscore_result(s, s->frames[s->items[item].frame]->in, static_cast<size_t>(s->done_frames) + item, sse, n);
+}
+
+}  // extern "C"

@@ -67,6 +67,9 @@ hipError_t launch_inter_apply8(int frame_type, int h, int w, const int* gflow, c
                                const float* ref1, const void* coef, float* out, hipStream_t stream);
 hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
 hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
+hipError_t launch_inter_score(const InterScoreJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, uint64_t* d_part,
+                              hipStream_t stream);
+hipError_t launch_inter_score_final(const InterScoreRange* d_ranges, int n_ranges, const uint64_t* d_part, uint64_t* d_sse, hipStream_t stream);
 hipError_t launch_spin(unsigned long long ticks, hipStream_t stream);
 // ccd_encode.hip
 size_t encode_contexts_lds_bytes(int dim);

@@ -1,6 +1,6 @@
 // ccd_planes.hpp - the sample step of the integer planes (decode.py:191-206 + png.py:57-58 / yuv.py:152-160), shared by the kernels
-// that must agree bit for bit: planes_kernel (ccd_float.hip), syn_fused_kernel (ccd_synth_fused.hip), dsens_inter_kernel and
-// dsens_dep_kernel (ccd_inter.hip).
+// that must agree bit for bit: planes_kernel (ccd_float.hip), syn_fused_kernel (ccd_synth_fused.hip), dsens_inter_kernel,
+// dsens_dep_kernel and inter_score_kernel (ccd_inter.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,7 +14,7 @@ orders (counted exactly, ties to the smaller order) and its own payload size; ti
 the coarser weight step, then the coarser bias step.
 
 The selection (order of the modules, tie-breaks, sweeps, infeasible cells) is `search_steps`, a pure function over a pricing
-callable, so it is testable without a device.  Intra frames only."""
+callable, so it is testable without a device.  Intra frames only; the two cool-chics of a P / B frame: nnquant_inter.py."""
 import itertools
 import time
 from typing import TYPE_CHECKING, Callable, List, NamedTuple, Optional, Sequence

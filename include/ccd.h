@@ -797,6 +797,54 @@ int ccd_rdoq_slot_dep_sse(const ccd_rdoq* r, int slot, int64_t* out);
 int64_t ccd_rdoq_slot_reach(const ccd_rdoq* r, int slot, int follow, void** dev_ptr);
 int64_t ccd_rdoq_slot_flow_boxes(const ccd_rdoq* r, int slot, int follow, int grid, void** dev_ptr);
 
+/* ---- the squared error of many candidates of P / B frames per launch ----
+ * A FRAME is a P / B frame as ccd_inter_reconstruct takes it - the f32 outputs of its residue and motion cool-chics (its base
+ * pair), the integer planes of its references, global flow, filter size - and the planes of its source.  An ITEM is that frame
+ * with the output of ONE of the two cool-chics replaced: role 0 another residue output [4 | 5][h][w], role 1 another motion
+ * output [2 | 4][h][w].  For the base pair of every frame and for every item a run gives, per plane,
+ *
+ *     sse[p] = sum over the plane of (ccd_inter_reconstruct(residue, motion, references)[p] - src[p])^2
+ *
+ * as exact integers - what ccd_inter_reconstruct followed by ccd_quality_score_batch reports, from the same device functions -
+ * and n[p], the plane's sample count.  No plane is stored.  All pointers are DEVICE pointers, read at every run and never written;
+ * they must stay valid while the handle may run (a caller that rewrote a buffer between runs is followed, as with `partner` of
+ * ccd_dsens_add_inter).  frame_data_type 0 rgb, 1 yuv420, 2 yuv444; planes u8 at 8 bits, else u16.
+ * Per run: the references of every frame are converted once, the base pairs of all frames are scored by one launch (which keeps
+ * their warped references: a residue item only reads those), all items by one more (each of the two becomes two launches when
+ * both the sinc-8 and another filter size are present), and one small launch adds up the workgroup partials.  A result does
+ * not depend on what else the handle holds.  ccd_iscore_run only enqueues on `stream`; ccd_iscore_wait synchronises.  One run
+ * may be in flight per handle.  ccd_iscore_clear_items drops the items and keeps the frames (a long list is priced in chunks);
+ * ccd_iscore_destroy drains the streams the handle was given.  Scratch comes from the block cache: ccd_iscore_add_frame takes
+ * the frame's (references and warped references as 4:4:4 f32), ccd_iscore_run the tables and partials; CCD_ERR_NOMEM from either.
+ * ccd_iscore_add_frame / ccd_iscore_add return the frame / item index.  ccd_iscore_frame_result / ccd_iscore_result: sse[3] and
+ * n[3] of a base pair / an item the last finished run covered.
+ * CCD_ERR_ARG - before the device is touched - for a NULL argument (residue, motion, ref0[p], src[p] and, B frames, ref1[p]
+ * included), a frame_type outside 1..2, a role outside 0..1, a bit depth outside 8..16, a frame_data_type outside 0..2, a frame or
+ * item index out of range (or not covered by a finished run), a run in flight; CCD_ERR_VALUE - also before the device is touched -
+ * for a filter size ccd_inter_reconstruct refuses, yuv420 with an odd side, a side outside 1..16383.  A refused call leaves the
+ * handle as it was. */
+typedef struct ccd_iscore ccd_iscore;
+typedef struct {
+    int32_t frame_type;        /* 1 P, 2 B */
+    int32_t h, w, bitdepth, frame_data_type;
+    const float* residue;      /* DEVICE f32 [4 | 5][h][w]: the base pair */
+    const float* motion;       /* DEVICE f32 [2 | 4][h][w] */
+    const void* ref0[3];       /* DEVICE integer planes of the references, layout of ccd_inter_reconstruct */
+    const void* ref1[3];       /* B frames */
+    const void* src[3];        /* DEVICE planes of the frame's source */
+    int32_t global_flow[4];
+    int32_t warp_filter_size;  /* 2, 4, 6..16 even */
+} ccd_iscore_frame;
+int ccd_iscore_create(int device, ccd_iscore** out);
+void ccd_iscore_destroy(ccd_iscore* s);
+int ccd_iscore_add_frame(ccd_iscore* s, const ccd_iscore_frame* frame);
+int ccd_iscore_add(ccd_iscore* s, int frame, int role, const float* output);
+int ccd_iscore_clear_items(ccd_iscore* s);
+int ccd_iscore_run(ccd_iscore* s, void* stream);
+int ccd_iscore_wait(ccd_iscore* s, void* stream);
+int ccd_iscore_frame_result(const ccd_iscore* s, int frame, uint64_t* sse, uint64_t* n);
+int ccd_iscore_result(const ccd_iscore* s, int item, uint64_t* sse, uint64_t* n);
+
 /* Leaky-quantised-Laplace boundaries computed ON THE GPU for a list of (mu_idx, scale_idx, s):
  * left[i], right[i] as the entropy kernel sees them (exhaustive parity tests of the f64 CDF). */
 int ccd_debug_laplace_bounds(int device, const int32_t* mu_idx, const int32_t* scale_idx, const int32_t* s,

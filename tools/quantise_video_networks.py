@@ -1,0 +1,135 @@
+"""Searches the quantisation steps of the networks of every frame of a `.cool` video against its source (DESIGN.md sections 4.18
+and 4.19).  The frames are walked in coding order: I frames go through NetworkQuantiser, P / B frames through
+InterNetworkQuantiser with the planes of the frames as they decode with the networks ALREADY CHOSEN as their references.  The
+float parameters are the stream's own integers dequantised; latents and every frame header stay as they are.
+
+    python tools/quantise_video_networks.py in.cool source.yuv out.cool --lmbda 1e-3 [--sweeps N] [--fast-path-only]
+
+Prints bytes of networks, PSNR and cost of every frame before and after ("before": the stream's networks against the references
+as they are now), writes the stream, decodes it back with decode_video and asserts that every frame's planes are those the last
+evaluation scored."""
+import argparse
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+from cool_chic_amd import DecodeBatch, EncodeBatch, InterRdEvaluator, RdEvaluator, writer  # noqa: E402
+from cool_chic_amd.bitstream.decode import _split_frame, decode_video  # noqa: E402
+from cool_chic_amd.bitstream.header import VideoHeader  # noqa: E402
+from cool_chic_amd.nnquant import NetworkQuantiser  # noqa: E402
+from cool_chic_amd.nnquant_inter import InterNetworkQuantiser  # noqa: E402
+from cool_chic_amd.quality import read_source  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("stream")
+    ap.add_argument("source", help="planar .yuv (or .png / .ppm for one frame) of the stream's size and format; frame d = display index d")
+    ap.add_argument("out")
+    ap.add_argument("--lmbda", type=float, required=True)
+    ap.add_argument("--sweeps", type=int, default=1)
+    ap.add_argument("--fast-path-only", action="store_true", help="only networks whose ARM fits the pipelined entropy kernel")
+    a = ap.parse_args()
+    with open(a.stream, "rb") as f:
+        bs = f.read()
+    vh = VideoHeader()
+    rest = vh.read_header(bs)
+    n_frames = vh.get_value("n_frames")
+    structure = vh.get_coding_structure()
+    parsed = []
+    for _ in range(n_frames):
+        fh, ccs, rest = _split_frame(rest)
+        parsed.append((fh, ccs))
+    display = [int(structure[k]["display_order"]) for k in range(n_frames)]
+    coding_of = {d: k for k, d in enumerate(display)}
+    original = decode_video(a.stream)  # {display index: FrameData}: sizes and formats of the sources
+    sources = [read_source(a.source, original[str(display[k])], frame_index=display[k]) for k in range(n_frames)]
+
+    # the latents of every cool-chic, entropy-decoded once; they stay on the device
+    dec = DecodeBatch(0)
+    slots = [[dec.add(ch.raw, nn, lat, 0, 0) for ch, nn, lat in ccs] for _, ccs in parsed]
+    dec.run(); dec.wait()
+    cool_chics = []  # per frame: [[arch, nn, [device tensors]]]; arch and nn are replaced by the chosen ones
+    for k, (_, ccs) in enumerate(parsed):
+        row = []
+        for s, (_, nn, _) in zip(slots[k], ccs):
+            arch = dec.header(s)
+            row.append([arch, nn, [torch.from_numpy(np.ascontiguousarray(dec.latent(s, g))).cuda() for g in range(arch.n_grids)]])
+        cool_chics.append(row)
+    dec.close()
+
+    def floats(arch, nn):
+        return writer.dequantise_network(arch, writer.network_values(arch, nn))
+
+    done = {}  # coding index -> the device planes of the frame under its chosen networks
+    for k, (fh, _) in enumerate(parsed):
+        frame_type = fh.get_value("frame_type")
+        row = cool_chics[k]
+        ptrs = [[t.data_ptr() for t in lat] for _, _, lat in row]
+        owner = [lat for _, _, lat in row]
+        if frame_type == "I":
+            arch, nn, _ = row[0]
+            with RdEvaluator(0) as ev:
+                ev.add(arch, nn, ptrs[0], sources[k], owner=owner)
+                before = ev.evaluate(a.lmbda)[0]
+            res = NetworkQuantiser(0).search(arch, floats(arch, nn), ptrs[0], sources[k], a.lmbda, sweeps=a.sweeps,
+                                             fast_path_only=a.fast_path_only, owner=owner)
+            row[0][0], row[0][1] = res.header, res.bytes_nn
+            with RdEvaluator(0) as ev:
+                ev.add(res.header, res.bytes_nn, ptrs[0], sources[k], owner=owner)
+                after = ev.evaluate(a.lmbda)[0]
+                done[k] = [p.clone() for p in ev.planes(0)]
+            n_before, n_after = len(nn), len(res.bytes_nn)
+        else:
+            n_refs = "IPB".index(frame_type)
+            refs = [done[coding_of[int(r)]] for r in structure[k]["index_references"]][:n_refs]
+            gf, taps = fh.get_value("global_flow"), fh.get_value("warp_filter_size")
+            with InterRdEvaluator(0) as ev:
+                ev.add(frame_type, (row[0][0], row[0][1], ptrs[0]), (row[1][0], row[1][1], ptrs[1]), refs, gf, taps, sources[k], owner=owner)
+                before = ev.evaluate(a.lmbda)[0]
+            n_before = len(row[0][1]) + len(row[1][1])
+            res = InterNetworkQuantiser(0).search(frame_type, (row[0][0], floats(row[0][0], row[0][1]), ptrs[0]),
+                                                  (row[1][0], floats(row[1][0], row[1][1]), ptrs[1]), refs, gf, taps, sources[k], a.lmbda,
+                                                  sweeps=a.sweeps, fast_path_only=a.fast_path_only, owner=owner)
+            for role, net in enumerate(res.roles):
+                row[role][0], row[role][1] = net.header, net.bytes_nn
+            with InterRdEvaluator(0) as ev:
+                ev.add(frame_type, (row[0][0], row[0][1], ptrs[0]), (row[1][0], row[1][1], ptrs[1]), refs, gf, taps, sources[k], owner=owner)
+                after = ev.evaluate(a.lmbda)[0]
+                done[k] = [p.clone() for p in ev.planes(0)]
+            assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)
+            n_after = len(row[0][1]) + len(row[1][1])
+        print(f"frame {display[k]} ({frame_type}):")
+        for label, c, n in (("before", before, n_before), ("after", after, n_after)):
+            print(f"  {label}: {n} bytes of networks, {c.bits:.1f} bits, PSNR {c.quality.psnr_db:.4f} dB, cost {c.cost:.9g}")
+
+    # every cool-chic through the device writer, the video and frame headers of the stream kept
+    enc = EncodeBatch(0)
+    for row in cool_chics:
+        for arch, nn, lat in row:
+            enc.add_device(arch, nn, [t.data_ptr() for t in lat], owner=lat)
+    enc.run(); enc.wait()
+    out, s = [vh.raw], 0
+    for (fh, _), row in zip(parsed, cool_chics):
+        out.append(fh.raw)
+        for _ in row:
+            out.append(enc.bytes(s))
+            s += 1
+    enc.close()
+    data = b"".join(out)
+    with open(a.out, "wb") as f:
+        f.write(data)
+    # what was written decodes to the planes the last evaluations scored
+    back = decode_video(a.out)
+    for k in range(n_frames):
+        fd = back[str(display[k])]
+        want = [p.cpu().numpy() for p in done[k]]
+        assert all(np.array_equal(x, y) for x, y in zip(fd.integer_planes(), want)), \
+            f"frame {display[k]} of the written stream does not decode to the evaluated planes"
+    print(f"{a.out}: {len(data)} bytes (was {len(bs)})")
+
+
+if __name__ == "__main__":
+    main()

@@ -35,6 +35,11 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     timer) priced one at a time through RdEvaluator (one evaluator per candidate: add, evaluate, close) and the ratio; for the Kodak-size frame at three lambdas
                     the cost, network bytes and PSNR of the searched network beside the stream's own, and after descend(8)
 
+  --networks --inter  instead of the above: the same search for the two cool-chics of a P / B frame (InterNetworkQuantiser, DESIGN.md
+                    section 4.19) - the P frame of `vid5`, a 1080p P frame grown from it and a B frame of synth.gop1080p (--inter-sets): wall time of one sweep
+                    per module and role (median of 5, min, max), candidates per launch, the host share spent building candidates, and
+                    the same candidates (built outside the timer) one at a time through InterRdEvaluator (add, evaluate, close)
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -767,6 +772,131 @@ def measure_networks(hdr, nn, payload, bitdepth, fdt, runs, lmbdas, descend_step
     return res
 
 
+def ip_1080p():
+    """A 1920x1080 I P stream in the geometry of gop1080p33, whose own structure (two I frames, hierarchical B between them) has
+    no P frame: the I and P frames of `vid5` grown the way synth.gop1080p grows its donors."""
+    from cool_chic_amd.bitstream.decode import _split_frame
+    from cool_chic_amd.bitstream.header import VideoHeader
+
+    H, W = 1080, 1920
+    bs, z = synth._golden("vid5")
+    rest = VideoHeader().read_header(bs)
+    out, cc_idx = [writer.video_header_bytes(2, [0], [1])], 0
+    for k in range(2):
+        fh, ccs, rest = _split_frame(rest)
+        assert fh.get_value("frame_type") == "IP"[k]
+        refs = [0] * k
+        out.append(writer.frame_header_bytes(k, "IP"[k], fh.c.frame_data_type, fh.c.bitdepth, refs, [0] * (2 * len(refs)), fh.c.warp_filter_size))
+        for ch, nn, _ in ccs:
+            donor = writer.parse_cc_header(ch.raw)
+            lat = [z[f"cc{cc_idx}.latent{g}"] for g in range(donor.n_grids)]
+            if donor.latent_resolution[0] == 0:  # residue / intra: "auto" levels for this picture size
+                v = synth.auto_resolution(H * W)
+                arch = writer.derive_arch(donor, img_size=(H, W), latent_resolution=(0, v),
+                                          hyperlatent_resolution=(4, v) if donor.flag_hyperlatent else tuple(donor.hyperlatent_resolution),
+                                          n_latent_grids=(v + 1) + ((v - 3) if donor.flag_hyperlatent else 0))
+                nn = writer.encode_network(arch, writer.adapt_network(donor, z[f"cc{cc_idx}.nn_ints"], arch))
+            else:                                # motion: latent 2-6 whatever the size
+                arch = writer.derive_arch(donor, img_size=(H, W))
+            out.append(writer.encode_coolchic(arch, nn, writer.tile_latents(lat, donor, arch)))
+            cc_idx += 1
+    return b"".join(out)
+
+
+def measure_inter_networks(stream_bytes, coding_index, runs, lmbda):
+    """InterNetworkQuantiser.search on one P / B frame of a video stream (the stream's own networks dequantised, the source the
+    decoded frame plus seeded noise of +-3 LSB, the references as decode_video gives them): the tables' wall times over `runs`
+    searches and the yardstick - every feasible candidate of those tables, built outside the timer, through an InterRdEvaluator
+    of its own (add, evaluate, close)."""
+    import os
+    import tempfile
+    import time
+
+    import numpy as np
+
+    from cool_chic_amd import InterRdEvaluator
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+    from cool_chic_amd.bitstream.intercoding import _integer_planes
+    from cool_chic_amd.nnquant import MODULES, build_network
+    from cool_chic_amd.nnquant_inter import ROLES, InterNetworkQuantiser
+
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    for k in range(coding_index + 1):
+        fh, ccs, rest = _split_frame(rest)
+    frame_type = fh.get_value("frame_type")
+    n_refs = "IPB".index(frame_type)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    dev = torch.device("cuda:0")
+    refs = [_integer_planes(frames[str(int(r))], dev) for r in structure[coding_index]["index_references"]][:n_refs]
+    own = frames[str(int(structure[coding_index]["display_order"]))]
+    rng = np.random.default_rng(18)
+    maxv = 2 ** own.bitdepth - 1
+    planes = [np.clip(p.astype(np.int64) + rng.integers(-3, 4, p.shape), 0, maxv).astype(p.dtype) for p in own.integer_planes()]
+    source = _planes_to_frame_data(planes, own.bitdepth, own.frame_data_type)
+    gflow, taps = fh.get_value("global_flow"), fh.get_value("warp_filter_size")
+    dec = DecodeBatch(0)
+    for ch, nn, lat in ccs:
+        dec.add(ch.raw, nn, lat, 0, 0)
+    dec.run(); dec.wait()
+    archs = [dec.header(r) for r in range(2)]
+    latents = [[torch.from_numpy(dec.latent(r, g)).cuda() for g in range(archs[r].n_grids)] for r in range(2)]
+    ptrs = [[t.data_ptr() for t in row] for row in latents]
+    dec.close()
+    floats = [writer.dequantise_network(archs[r], writer.network_values(archs[r], ccs[r][1])) for r in range(2)]
+    res = {"frame": frame_type, "size": [int(v) for v in archs[0].img_size], "warp_filter_size": int(taps),
+           "parameters": [int(x.size) for x in floats], "runs": runs}
+    nq = InterNetworkQuantiser(0)
+
+    def search():
+        return nq.search(frame_type, (archs[0], floats[0], ptrs[0]), (archs[1], floats[1], ptrs[1]), refs, gflow, taps, source, lmbda, owner=latents)
+
+    searches = [search() for _ in range(1 + runs)][1:]
+    one = searches[0]
+    steps = [[writer.q_step_range(g)[0] for g in range(8)] for _ in range(2)]
+    res["modules"] = {}
+    for k, t in enumerate(one.tables):
+        secs = [s.pricing[k].seconds for s in searches]
+        build = [s.pricing[k].build_seconds for s in searches]
+        _, gw, gb = next(m for m in MODULES if m[0] == t.module)
+        partner = build_network(archs[1 - t.role], floats[1 - t.role], steps[1 - t.role])
+        pairs = []
+        for c in t.cells:
+            if c.feasible:
+                s = list(steps[t.role])
+                s[gw], s[gb] = c.q_w, c.q_b
+                net = build_network(archs[t.role], floats[t.role], s)
+                pairs.append((net, partner) if t.role == 0 else (partner, net))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for a, b in pairs:  # the yardstick: one candidate at a time through the calls the parent commit has
+            with InterRdEvaluator(0) as ev:
+                ev.add(frame_type, (a.header, a.bytes_nn, ptrs[0]), (b.header, b.bytes_nn, ptrs[1]), refs, gflow, taps, source, owner=latents)
+                ev.evaluate(lmbda)
+        alone = time.perf_counter() - t0
+        res["modules"][f"{ROLES[t.role]} {t.module}"] = {
+            "candidates": len(t.cells), "feasible": len(pairs), "per_launch": one.pricing[k].chunk,
+            "sweep_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4), "max": round(max(secs), 4)},
+            "of_which_building_candidates_s": round(statistics.median(build), 4),
+            "one_at_a_time_s": round(alone, 4), "ratio": round(alone / statistics.median(secs), 2)}
+        if t.chosen is not None:
+            steps[t.role][gw], steps[t.role][gb] = t.cells[t.chosen].q_w, t.cells[t.chosen].q_b
+    with InterRdEvaluator(0) as ev:
+        ev.add(frame_type, (archs[0], ccs[0][1], ptrs[0]), (archs[1], ccs[1][1], ptrs[1]), refs, gflow, taps, source, owner=latents)
+        c = ev.evaluate(lmbda)[0]
+    res["reached"] = {"stream": {"cost": c.cost, "bytes_nn": len(ccs[0][1]) + len(ccs[1][1]), "psnr_db": round(c.quality.psnr_db, 4), "bits": round(c.bits, 1)},
+                      "searched": {"cost": one.candidate.cost, "bytes_nn": sum(len(n.bytes_nn) for n in one.roles),
+                                   "psnr_db": round(one.candidate.quality.psnr_db, 4), "bits": round(one.candidate.bits, 1)},
+                      "steps": [list(n.header.nn_q_step_log2) for n in one.roles]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=9)
@@ -787,6 +917,16 @@ def main():
     ap.add_argument("--networks", action="store_true", help="time the search over the networks' quantisation steps instead")
     ap.add_argument("--network-sets", default="kodak,1080p", help="with --networks: which of the two frames to measure")
     a = ap.parse_args()
+    if a.networks and a.inter:
+        runs = min(a.runs, 5)
+        line = {"tool": "rd_bench --networks --inter", "runs": runs}
+        if "vid5" in a.inter_sets.split(","):
+            line["vid5_P"] = measure_inter_networks(synth._golden("vid5")[0], 1, runs, a.lmbda)
+        if "1080p" in a.inter_sets.split(","):
+            line["1080p_P"] = measure_inter_networks(ip_1080p(), 1, runs, a.lmbda)
+            line["gop1080p_B"] = measure_inter_networks(synth.gop1080p(2)[0], 2, runs, a.lmbda)
+        print(json.dumps(line))
+        return
     if a.networks:
         from cool_chic_amd.bitstream.decode import _split_frame
         from cool_chic_amd.bitstream.header import VideoHeader
