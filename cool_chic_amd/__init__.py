@@ -28,10 +28,12 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    nnquant.NetworkQuantiser (every candidate of a module in one batch)
     (the same search for the two cool-chics of a P / B frame: candidates reconstructed and scored on the device, many per launch)
                                                    iscore.InterScore, nnquant_inter.InterNetworkQuantiser
+    (no counterpart: a +-1 descent over the ARM's transmitted integers, every candidate's rate change from one table)
+                                                   EncodeBatch.measure_param_deltas, nnrefine.ArmRefiner
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
-from .encoder import EncodeBatch  # noqa: F401
+from .encoder import EncodeBatch, ParamDeltas  # noqa: F401
 
 
 def __getattr__(name):
@@ -67,6 +69,10 @@ def __getattr__(name):
         from . import nnquant_inter
 
         return getattr(nnquant_inter, name)
+    if name in ("ArmRefiner", "RefinedNetwork", "expgol_bit_deltas", "pick_moves"):
+        from . import nnrefine
+
+        return getattr(nnrefine, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

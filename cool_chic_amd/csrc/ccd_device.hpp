@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/ccd.h"
+#include "ccd_armdelta_plan.hpp"
 #include "ccd_lattice.hpp"
 
 namespace ccd {
@@ -105,6 +106,19 @@ struct DeltaParams {
     uint32_t tile_first[CCD_MAX_GRIDS];   // first workgroup of the IFCE stage that belongs to grid g (grows with g)
     uint32_t n_tiles;
     float* map[CCD_MAX_GRIDS];            // per grid [2][h][w]: plane 0 the change for v - 1, plane 1 for v + 1
+};
+
+// ARM parameter deltas (encode_param_delta_kernel / encode_param_delta_final_kernel): what a slot of a
+// measure_param_deltas writes.  Candidate c = 2 (k - first) + (sign > 0).  A wave walks chunk j of the slot's workgroups -
+// [j kArmDeltaChunkBlocks, (j + 1) kArmDeltaChunkBlocks) of the rate kernel's numbering - for a tile of kArmDeltaTile candidates and
+// leaves one cell per candidate; the final kernel adds a candidate's cells in chunk order.
+struct ParamDeltaCell { double bits; int64_t sum_width, moved; };
+struct ParamDeltaParams {
+    const ArmDeltaMove* cand;   // [n_cand]
+    ParamDeltaCell* partial;    // [n_chunks][n_cand]
+    ParamDeltaCell* out;        // [n_cand]: +inf, 0, 0 for a candidate that is not legal
+    uint32_t n_cand, n_chunks;
+    int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental: which instantiation prices the slot
 };
 
 // One copy of the ingest launch (ccd_ingest.hip): latent grid `src` of a slot whose latents were GIVEN as device pointers

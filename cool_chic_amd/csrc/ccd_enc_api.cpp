@@ -2,6 +2,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 
 #include "ccd_host.hpp"
 #include "ccd_kernels.hpp"
@@ -28,6 +29,11 @@ struct EncSlot {
     ccd_enc_rate rate{};
     size_t map_off = 0;            // floats before this slot's planes in the handle's map block
     size_t delta_off = 0;          // floats before this slot's delta maps in the handle's delta map block
+    // ARM parameter deltas (ccd_enc_measure_param_deltas)
+    ArmDeltaShape arm_shape{};
+    std::vector<int64_t> arm_ints; // the ARM's transmitted integers, stream order
+    int param_first = 0, param_count = 0;  // the range the last table covers, clipped to this slot
+    size_t param_off = 0;          // candidates before this slot's in the handle's tables
 };
 enum { kIdle = 0, kRun = 1, kMeasure = 2 };  // what ccd_enc::in_flight holds
 }  // namespace
@@ -55,6 +61,11 @@ struct ccd_enc {
     size_t delta_slots = 0;        // slots the three above describe
     bool delta_pending = false;    // the measure in flight is a measure_deltas
     bool delta_valid = false;      // the last finished measure was one
+    // ARM parameter deltas (ccd_enc_measure_param_deltas): a measure whose two extra launches write here
+    Mirror param_table, param_out; // ParamDeltaParams[n] and every slot's candidates; one ParamDeltaCell per candidate
+    Block param_slab;              // the chunks' cells
+    bool param_pending = false;    // the measure in flight is a measure_param_deltas
+    bool param_valid = false;      // the last finished measure was one
     StreamSet streams;             // every stream a run was enqueued on
 };
 
@@ -89,6 +100,7 @@ void ccd_enc_destroy(ccd_enc* e) {
     e->table.drop(); e->status.drop();
     e->rate_table.drop(); e->rate_slab.drop(); e->rate_out.drop(); e->rate_map.drop();
     e->delta_table.drop(); e->delta_slab.drop(); e->delta_map.drop();
+    e->param_table.drop(); e->param_out.drop(); e->param_slab.drop();
     delete e;
 }
 
@@ -194,6 +206,8 @@ int ccd_enc_add(ccd_enc* e, const ccd_cc_header* tmpl, const uint8_t* bytes_nn, 
     Q.pairs = s.pairs.as<EncodePair>();
     Q.out = s.out.as<uint32_t>();
     s.nn.assign(bytes_nn, bytes_nn + n_nn);
+    s.arm_shape = armdelta_shape(h);
+    s.arm_ints.assign(net.ints.begin(), net.ints.begin() + std::min<int64_t>(armdelta_count(s.arm_shape), static_cast<int64_t>(net.ints.size())));
     e->slots.push_back(std::move(sp));
     return static_cast<int>(e->slots.size()) - 1;
 }
@@ -233,6 +247,8 @@ void harvest(ccd_enc* e) {
         e->map_valid = e->rate_has_map;
         e->delta_valid = e->delta_pending;
         e->delta_pending = false;
+        e->param_valid = e->param_pending;
+        e->param_pending = false;
     }
     e->last_kind = e->in_flight;
     e->in_flight = kIdle;
@@ -302,6 +318,7 @@ int enqueue_measure(ccd_enc* e, hipStream_t st, bool map, unsigned* max_blocks_o
     *lds_out = lds;
     e->map_valid = false;  // the planes of the last measure are about to be overwritten or given back
     e->delta_valid = false;
+    e->param_valid = false;
     if (e->rate_slots != n || e->rate_has_map != map) {
         e->rate_slots = 0;
         size_t n_blocks = 0, out_bytes = 0, n_map = 0;
@@ -425,6 +442,114 @@ int ccd_enc_measure_deltas(ccd_enc* e, void* stream) {
     HIP_TRY(e->delta_table.upload(n * sizeof(DeltaParams), st));
     HIP_TRY(launch_encode_deltas(e->table.dev.as<EncodeParams>(), e->delta_table.dev.as<DeltaParams>(), static_cast<int>(n), max_blocks, max_tiles, lds, st));
     e->delta_pending = true;
+    return CCD_OK;
+}
+
+int ccd_enc_measure_param_deltas(ccd_enc* e, void* stream, int first, int count, int mode) {
+    if (!e || first < 0 || mode < kArmDeltaAuto || mode > kArmDeltaIncremental) return CCD_ERR_ARG;
+    const size_t n = e->slots.size();
+    if (n == 0) return CCD_OK;
+    // ---- everything the host can refuse, before the device is touched: the path of every slot, the launch's dimensions ----
+    if (n > 65535) return CCD_ERR_UNSUPPORTED;
+    std::vector<std::pair<int, int>> range(n);  // first, count per slot: the range asked for, clipped
+    size_t n_cand = 0, n_cells = 0;
+    unsigned max_cand = 0, max_chunks = 0;
+    std::vector<int> path(n);
+    size_t lds_generic = 0, lds_incremental = 0;  // 0: no slot takes that path
+    for (size_t i = 0; i < n; ++i) {
+        const EncSlot& s = *e->slots[i];
+        const int rc = armdelta_path(s.arm_shape, mode);
+        if (rc < 0) return rc;
+        path[i] = rc;
+        if (rc == kArmDeltaIncremental) lds_incremental = std::max(lds_incremental, static_cast<size_t>(armdelta_incremental_lds(s.arm_shape)));
+        else lds_generic = std::max(lds_generic, encode_contexts_lds_bytes(s.ep.ep.dim));
+        const int64_t n_arm = static_cast<int64_t>(s.arm_ints.size());
+        const int64_t lo = std::min<int64_t>(first, n_arm), hi = count < 0 ? n_arm : std::min<int64_t>(static_cast<int64_t>(first) + count, n_arm);
+        range[i] = {static_cast<int>(lo), static_cast<int>(hi - lo)};
+        const size_t cand = 2 * static_cast<size_t>(hi - lo);
+        const size_t chunks = (s.ep.n_blocks + kArmDeltaChunkBlocks - 1) / kArmDeltaChunkBlocks;
+        if ((cand + kArmDeltaTile - 1) / kArmDeltaTile > 65535) return CCD_ERR_UNSUPPORTED;
+        n_cand += cand;
+        n_cells += cand * chunks;
+        max_cand = std::max<unsigned>(max_cand, static_cast<unsigned>(cand));
+        max_chunks = std::max<unsigned>(max_chunks, static_cast<unsigned>(chunks));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->in_flight != kIdle) {  // the tables below are rebuilt: nothing of this handle may still read them
+        HIP_TRY(hipStreamSynchronize(e->last_stream));
+        harvest(e);
+    }
+    e->param_valid = false;  // the table of the last call is about to be overwritten: a failure from here on leaves no table
+    const size_t cand_at = align256(n * sizeof(ParamDeltaParams));
+    const size_t table_bytes = cand_at + std::max<size_t>(n_cand, 1) * sizeof(ArmDeltaMove);
+    const size_t out_bytes = std::max<size_t>(n_cand, 1) * sizeof(ParamDeltaCell);
+    if (!e->param_table.ensure(e->device, table_bytes) || !e->param_out.ensure(e->device, out_bytes) ||
+        !e->param_slab.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_cells * sizeof(ParamDeltaCell), 256)))
+        return CCD_ERR_NOMEM;
+    {
+        ParamDeltaParams* tab = e->param_table.host.as<ParamDeltaParams>();
+        ArmDeltaMove* cands = reinterpret_cast<ArmDeltaMove*>(e->param_table.host.as<char>() + cand_at);
+        const ArmDeltaMove* d_cands = reinterpret_cast<const ArmDeltaMove*>(e->param_table.dev.as<char>() + cand_at);
+        size_t at = 0, cell = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const EncSlot& s = *e->slots[i];
+            const int p_first = range[i].first;
+            const uint32_t cand = 2 * static_cast<uint32_t>(range[i].second);
+            const uint32_t chunks = (s.ep.n_blocks + kArmDeltaChunkBlocks - 1) / kArmDeltaChunkBlocks;
+            for (uint32_t c = 0; c < cand; ++c) {
+                const int64_t k = p_first + (c >> 1);
+                int64_t index = 0;
+                const int rc = armdelta_move(s.arm_shape, k, (c & 1) ? 1 : -1, s.arm_ints[static_cast<size_t>(k)], &cands[at + c], &index);
+                if (rc < 0) return rc;  // (cannot happen: decode_network took these shifts)
+            }
+            tab[i] = ParamDeltaParams{d_cands + at, e->param_slab.as<ParamDeltaCell>() + cell, e->param_out.dev.as<ParamDeltaCell>() + at, cand, chunks, path[i], 0};
+            at += cand;
+            cell += static_cast<size_t>(cand) * chunks;
+        }
+    }
+    unsigned max_blocks = 0;
+    size_t lds = 0;
+    const int rc = enqueue_measure(e, st, false, &max_blocks, &lds);  // the meter's two launches first: its results are its own
+    if (rc < 0) return rc;
+    launched(e, st, kMeasure);
+    {   // the slots learn their rows only now that the measure is under way
+        size_t at = 0;
+        for (size_t i = 0; i < n; ++i) {
+            EncSlot& s = *e->slots[i];
+            s.param_first = range[i].first;
+            s.param_count = range[i].second;
+            s.param_off = at;
+            at += 2 * static_cast<size_t>(s.param_count);
+        }
+    }
+    HIP_TRY(e->param_table.upload(table_bytes, st));
+    HIP_TRY(launch_encode_param_deltas(e->table.dev.as<EncodeParams>(), e->param_table.dev.as<ParamDeltaParams>(), static_cast<int>(n), max_chunks,
+                                       max_cand, lds_generic, lds_incremental, st));
+    HIP_TRY(e->param_out.download(out_bytes, st));
+    e->param_pending = true;
+    return CCD_OK;
+}
+
+int ccd_enc_slot_param_count(const ccd_enc* e, int slot) {
+    if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size())) return CCD_ERR_ARG;
+    return static_cast<int>(e->slots[slot]->arm_ints.size());
+}
+
+int ccd_enc_slot_param_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved) {
+    if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size()) || e->in_flight == kMeasure || !e->param_valid ||
+        static_cast<size_t>(slot) >= e->n_measured || !e->slots[slot]->measured)
+        return CCD_ERR_ARG;
+    const EncSlot& s = *e->slots[slot];
+    if (s.rate.status < 0) return s.rate.status;
+    if (first) *first = s.param_first;
+    if (count) *count = s.param_count;
+    const ParamDeltaCell* cell = e->param_out.host.as<ParamDeltaCell>() + s.param_off;
+    for (int c = 0; c < 2 * s.param_count; ++c) {
+        if (bits) bits[c] = cell[c].bits;
+        if (sum_width) sum_width[c] = cell[c].sum_width;
+        if (moved) moved[c] = cell[c].moved;
+    }
     return CCD_OK;
 }
 

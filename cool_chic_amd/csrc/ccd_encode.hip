@@ -36,10 +36,24 @@ constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever rea
 // kOverride: the one latent `ov` names is taken as ov.val wherever the pixel reads it (a spatial tap when ov.grid == g, an
 // IFCE source when ov.grid > g), memory stays as it is - the delta kernels' "what if".  Without it `ov` is not looked at and
 // the function is what it was before it had the parameter.
+// kParam: one entry of the fixed-point ARM is taken as entry + pm.inc (the parameter table's "what if").  The
+// sums are wrapping 64-bit, a ring, so the unit's accumulator with that entry is the accumulator as it is plus pm.inc times the
+// unit's input pm.in (times one for a bias), bit for bit; pm is wave-uniform and the weights stay scalar loads.
+// kInputsOnly: the ARM's inputs (contexts and IFCE features) are left in the first dim columns and nothing else is done - the
+// incremental path of the parameter table keeps them there.
 struct LatentOverride { int grid, y, x, val; };
-template <bool kOverride>
+// table indices (latent.py:156-165, rangecoder.py:90-91) of the ARM's two sums, as the Laplace parameters
+__device__ __forceinline__ void arm_sums_to_model(const EntropyParams& P, uint64_t st0, uint64_t st1, double& mu, double& rcp) {
+    const int64_t mi = (static_cast<int64_t>(st0) >> 24) + kMuOffset, si = (static_cast<int64_t>(st1) >> 24) + kScaleOffset;
+    const int mu_idx = static_cast<int>(mi < 0 ? 0 : (mi > kNumMu - 1 ? kNumMu - 1 : mi));
+    const int sc_idx = static_cast<int>(si < 0 ? 0 : (si > kNumScale - 1 ? kNumScale - 1 : si));
+
+    mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
+    rcp = P.rcp_table[sc_idx];
+}
+template <bool kOverride, bool kParam = false, bool kInputsOnly = false>
 __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g, int y, int x, int lane, unsigned char* smem_raw,
-                                                   const LatentOverride& ov, double& mu, double& rcp) {
+                                                   const LatentOverride& ov, double& mu, double& rcp, const ArmDeltaMove& pm = ArmDeltaMove{}) {
     const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
     int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
     int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
@@ -82,6 +96,7 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
     } else {
         for (int o = 0; o < n_if; ++o) xa[(n_sp + o) * kEncThreads] = 0;
     }
+    if (kInputsOnly) return;
 
     // ---- ARM (armint.py:180-203): stabiliser branch, hidden layers, output layer; weights are wave-uniform reads ----
     const int64_t* ws = P.arm + (P.arm_len - 2 - 2 * dim);
@@ -91,6 +106,10 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
         const uint64_t v = static_cast<uint64_t>(xa[k * kEncThreads]);
         st0 += v * static_cast<uint64_t>(ws[k * 2]);
         st1 += v * static_cast<uint64_t>(ws[k * 2 + 1]);
+    }
+    if (kParam && pm.layer == P.n_layers) {
+        const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xa[pm.in * kEncThreads]));
+        if (pm.out == 0) st0 += c; else st1 += c;
     }
     int64_t* xin = xa;
     int64_t* xout = xb;
@@ -105,6 +124,11 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
                 const uint64_t v = static_cast<uint64_t>(xin[k * kEncThreads]);
                 a0 += v * static_cast<uint64_t>(lw[k * dim + o]);
                 a1 += v * static_cast<uint64_t>(lw[k * dim + o1]);
+            }
+            if (kParam && pm.layer == l && (pm.out == o || pm.out == o1)) {
+                const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[pm.in * kEncThreads]));
+                if (pm.out == o) a0 += c;
+                if (pm.out == o1) a1 += c;
             }
             const int64_t v0 = static_cast<int64_t>(a0), v1 = static_cast<int64_t>(a1);
             xout[o * kEncThreads] = (v0 < 0 ? 0 : v0) >> 16;
@@ -121,15 +145,13 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
             a0 += v * static_cast<uint64_t>(lw[k * 2]);
             a1 += v * static_cast<uint64_t>(lw[k * 2 + 1]);
         }
+        if (kParam && pm.layer == P.n_layers - 1) {
+            const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[pm.in * kEncThreads]));
+            if (pm.out == 0) a0 += c; else a1 += c;
+        }
         st0 += a0; st1 += a1;
     }
-    // table indices (latent.py:156-165, rangecoder.py:90-91)
-    const int64_t mi = (static_cast<int64_t>(st0) >> 24) + kMuOffset, si = (static_cast<int64_t>(st1) >> 24) + kScaleOffset;
-    const int mu_idx = static_cast<int>(mi < 0 ? 0 : (mi > kNumMu - 1 ? kNumMu - 1 : mi));
-    const int sc_idx = static_cast<int>(si < 0 ? 0 : (si > kNumScale - 1 ? kNumScale - 1 : si));
-
-    mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
-    rcp = P.rcp_table[sc_idx];
+    arm_sums_to_model(P, st0, st1, mu, rcp);
 }
 
 // The interval [left, right) of symbol `sym` (already checked to be in the alphabet) at (y, x) of grid g under the leaky
@@ -469,6 +491,215 @@ __global__ __launch_bounds__(kEncThreads) void encode_delta_kernel(const EncodeP
     out[n + p] = has_p ? static_cast<float>(ap) : inf;
 }
 
+// ---- ARM parameter deltas: what the slot's model bits would change by if ONE transmitted ARM integer were v - 1 or v + 1 ------
+// DESIGN.md 4.20.  Two launches behind the meter's, no atomics.
+//   1. encode_param_delta_kernel: blockIdx = (chunk, tile of 64 candidates, slot).  The wave walks the chunk's 64-pixel
+//      workgroups in order; per workgroup one evaluation as it is, then one per candidate with the candidate's entry moved
+//      (generic path: encode_pixel_model<.., true>; incremental path: arm_candidate on the kept state), the width compared, and the lanes' log2(width) - log2(width'), width' - width and "moved"
+//      summed by wave_sum's fixed tree.  Lane c mod 64 keeps candidate c's running sums over the chunk's workgroups and stores
+//      the cell.  A workgroup in which no lane's width moved adds nothing (its wave sums would be +0.0, 0, 0).
+//   2. encode_param_delta_final_kernel: one wave per candidate adds its cells lane-strided in chunk order and through the tree.
+// The order of the additions of a candidate follows from the slot's geometry alone: not from the range of parameters asked for
+// (which only decides the tile a candidate shares), the batch or the device.  Tail lanes and lanes whose symbol is outside the
+// alphabet hold 0 and stay for the shuffles (the meter's launch set such a slot's status).
+// ---- the incremental path: the base evaluation's state stays in the LDS, a candidate is a rank-1 update of it ----
+// Per-lane columns, [k][lane] like xa / xb: the inputs [dim], then every hidden layer's accumulators BEFORE the ReLU
+// [n_hidden][dim], then - only for three hidden layers or more - two scratch columns [dim] each (armdelta_incremental_lds).
+// The stabiliser's two sums and the output layer's two accumulators of the base are kept in registers (ArmBase).
+struct ArmBase { uint64_t st0, st1, a0, a1; };
+__device__ __forceinline__ int64_t relu16(int64_t v) { return (v < 0 ? 0 : v) >> 16; }
+// input k of layer l (l == n_hidden: of the output layer) as the base evaluation has it
+__device__ __forceinline__ int64_t arm_input(const int64_t* x0, int dim, int l, int k) {
+    return l == 0 ? x0[k * kEncThreads] : relu16(x0[(l * dim + k) * kEncThreads]);  // layer l - 1's accumulators sit at column l * dim
+}
+// The base evaluation from the inputs in the first dim columns: armint.py:180-203, every accumulator stored.
+__device__ __forceinline__ ArmBase arm_base_store(const EntropyParams& P, int64_t* x0) {
+    const int dim = P.dim, n_hidden = P.n_layers - 1;
+    const int64_t* ws = P.arm + (P.arm_len - 2 - 2 * dim);
+    const int64_t* bs = ws + 2 * dim;
+    ArmBase B{static_cast<uint64_t>(bs[0]), static_cast<uint64_t>(bs[1]), 0, 0};
+    for (int k = 0; k < dim; ++k) {
+        const uint64_t v = static_cast<uint64_t>(x0[k * kEncThreads]);
+        B.st0 += v * static_cast<uint64_t>(ws[k * 2]);
+        B.st1 += v * static_cast<uint64_t>(ws[k * 2 + 1]);
+    }
+    const int64_t* lw = P.arm;
+    for (int l = 0; l < n_hidden; ++l) {
+        const int64_t* lb = lw + dim * dim;
+        int64_t* acc = x0 + (l + 1) * dim * kEncThreads;
+        for (int o = 0; o < dim; o += 2) {
+            const int o1 = min(o + 1, dim - 1);
+            uint64_t a0 = static_cast<uint64_t>(lb[o]), a1 = static_cast<uint64_t>(lb[o1]);
+            for (int k = 0; k < dim; ++k) {
+                const uint64_t v = static_cast<uint64_t>(arm_input(x0, dim, l, k));
+                a0 += v * static_cast<uint64_t>(lw[k * dim + o]);
+                a1 += v * static_cast<uint64_t>(lw[k * dim + o1]);
+            }
+            acc[o * kEncThreads] = static_cast<int64_t>(a0);
+            acc[o1 * kEncThreads] = static_cast<int64_t>(a1);
+        }
+        lw = lb + dim;
+    }
+    const int64_t* lb = lw + dim * 2;
+    B.a0 = static_cast<uint64_t>(lb[0]); B.a1 = static_cast<uint64_t>(lb[1]);
+    for (int k = 0; k < dim; ++k) {
+        const uint64_t v = static_cast<uint64_t>(arm_input(x0, dim, n_hidden, k));
+        B.a0 += v * static_cast<uint64_t>(lw[k * 2]);
+        B.a1 += v * static_cast<uint64_t>(lw[k * 2 + 1]);
+    }
+    return B;
+}
+// The ARM's two sums with the candidate's entry moved.  Every step is the full evaluation's arithmetic modulo 2^64: the moved
+// unit's accumulator changes by inc * input, its activation by delta, the next layer's accumulators by delta * weight (re-rounded
+// by their own ReLU), the layers behind that are recomputed in full.  delta == 0: the base's sums.
+__device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x0, const ArmBase& B, const ArmDeltaMove& pm, uint64_t& st0, uint64_t& st1) {
+    const int dim = P.dim, n_hidden = P.n_layers - 1;
+    const int64_t hidden_len = static_cast<int64_t>(dim) * dim + dim;
+    const int64_t* wo = P.arm + n_hidden * hidden_len;  // the output layer: w[dim][2], b[2]
+    uint64_t a0 = B.a0, a1 = B.a1;
+    st0 = B.st0; st1 = B.st1;
+    if (pm.layer >= n_hidden) {  // output layer or stabiliser: one accumulator moves
+        const bool stab = pm.layer > n_hidden;
+        const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(arm_input(x0, dim, stab ? 0 : n_hidden, pm.in)));
+        if (pm.out == 0) a0 += c; else a1 += c;
+    } else {
+        const int l = pm.layer;
+        const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(arm_input(x0, dim, l, pm.in)));
+        const int64_t a = x0[((l + 1) * dim + pm.out) * kEncThreads];
+        const int64_t delta = relu16(static_cast<int64_t>(static_cast<uint64_t>(a) + c)) - relu16(a);
+        if (delta != 0) {
+            const uint64_t d = static_cast<uint64_t>(delta);
+            if (l + 1 == n_hidden) {  // the output layer is next
+                a0 += d * static_cast<uint64_t>(wo[pm.out * 2]);
+                a1 += d * static_cast<uint64_t>(wo[pm.out * 2 + 1]);
+            } else {
+                const int64_t* lw = P.arm + (l + 1) * hidden_len;  // layer l + 1: its accumulators move by delta * w[out][.]
+                const int64_t* acc = x0 + (l + 2) * dim * kEncThreads;
+                int64_t* sa = x0 + (n_hidden + 1) * dim * kEncThreads;  // scratch, touched only when a layer lies behind l + 1
+                int64_t* sb = sa + dim * kEncThreads;
+                const bool last = l + 2 == n_hidden;
+                if (last) { a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]); }
+                for (int o = 0; o < dim; ++o) {
+                    const int64_t v = relu16(static_cast<int64_t>(static_cast<uint64_t>(acc[o * kEncThreads]) + d * static_cast<uint64_t>(lw[pm.out * dim + o])));
+                    if (last) {
+                        a0 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2]);
+                        a1 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2 + 1]);
+                    } else sa[o * kEncThreads] = v;
+                }
+                if (!last) {
+                    for (int m = l + 2; m < n_hidden; ++m) {  // in full, as encode_pixel_model does
+                        const int64_t* mw = P.arm + m * hidden_len;
+                        const int64_t* mb = mw + dim * dim;
+                        for (int o = 0; o < dim; ++o) {
+                            uint64_t t = static_cast<uint64_t>(mb[o]);
+                            for (int k = 0; k < dim; ++k) t += static_cast<uint64_t>(sa[k * kEncThreads]) * static_cast<uint64_t>(mw[k * dim + o]);
+                            sb[o * kEncThreads] = relu16(static_cast<int64_t>(t));
+                        }
+                        int64_t* t = sa; sa = sb; sb = t;
+                    }
+                    a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]);
+                    for (int k = 0; k < dim; ++k) {
+                        const uint64_t v = static_cast<uint64_t>(sa[k * kEncThreads]);
+                        a0 += v * static_cast<uint64_t>(wo[k * 2]);
+                        a1 += v * static_cast<uint64_t>(wo[k * 2 + 1]);
+                    }
+                }
+            }
+        }
+    }
+    st0 += a0; st1 += a1;
+}
+
+// kIncremental: the slots whose path is the incremental one (ParamDeltaParams::path); the other instantiation takes the rest.
+// Both give the same 64-bit words: the integer model is the same modulo 2^64, the floats and the order they are added in are
+// this one function's.
+template <bool kIncremental>
+__global__ __launch_bounds__(kEncThreads) void encode_param_delta_kernel(const EncodeParams* slots, const ParamDeltaParams* param) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.z];
+    const EntropyParams& P = Q.ep;
+    const ParamDeltaParams& D = param[blockIdx.z];
+    const uint32_t chunk = blockIdx.x, c0 = blockIdx.y * kArmDeltaTile;
+    if ((D.path == kArmDeltaIncremental) != kIncremental || chunk >= D.n_chunks || c0 >= D.n_cand) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    const uint32_t nc = min(static_cast<uint32_t>(kArmDeltaTile), D.n_cand - c0);
+    const uint32_t b_end = min((chunk + 1) * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.n_blocks);
+    int64_t* x0 = reinterpret_cast<int64_t*>(smem_raw) + lane;
+    ParamDeltaCell acc{0.0, 0, 0};  // of candidate c0 + lane
+    int g = 0;
+#pragma unroll 1
+    for (uint32_t b = chunk * kArmDeltaChunkBlocks; b < b_end; ++b) {
+        while (g + 1 < n_grids && b >= Q.block_first[g + 1]) ++g;
+        const int H = P.grid_h[g], W = P.grid_w[g];
+        const int p = static_cast<int>(b - Q.block_first[g]) * kEncThreads + lane;
+        const int sym = p < H * W ? P.latent[g][p] : 0;
+        const bool ok = p < H * W && in_alphabet(sym);
+        const int y = ok ? p / W : 0, x = ok ? p - y * W : 0;
+        double mu, rcp, base = 0.0;
+        uint32_t width = 0;
+        ArmBase B{0, 0, 0, 0};
+        if (ok) {
+            if (kIncremental) {
+                encode_pixel_model<false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+                B = arm_base_store(P, x0);
+                arm_sums_to_model(P, B.st0 + B.a0, B.st1 + B.a1, mu, rcp);
+            } else encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+            width = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
+            base = log2(static_cast<double>(width));
+        }
+#pragma unroll 1
+        for (uint32_t ci = 0; ci < nc; ++ci) {
+            const ArmDeltaMove pm = D.cand[c0 + ci];  // wave-uniform
+            if (!pm.legal) continue;
+            double d_bits = 0.0;
+            int64_t d_width = 0;
+            if (ok) {
+                if (kIncremental) {
+                    uint64_t st0, st1;
+                    arm_candidate(P, x0, B, pm, st0, st1);
+                    arm_sums_to_model(P, st0, st1, mu, rcp);
+                } else encode_pixel_model<false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp, pm);
+                const uint32_t w = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
+                if (w != width) {
+                    d_bits = base - log2(static_cast<double>(w));
+                    d_width = static_cast<int64_t>(w) - static_cast<int64_t>(width);
+                }
+            }
+            const bool moved = d_width != 0;
+            if (__ballot(moved) == 0) continue;
+            const double s_bits = wave_sum(d_bits);
+            const uint64_t s_width = wave_sum(static_cast<uint64_t>(d_width)), s_moved = wave_sum(static_cast<uint64_t>(moved ? 1 : 0));
+            if (static_cast<uint32_t>(lane) == ci) {
+                acc.bits += s_bits;
+                acc.sum_width += static_cast<int64_t>(s_width);
+                acc.moved += static_cast<int64_t>(s_moved);
+            }
+        }
+    }
+    if (static_cast<uint32_t>(lane) < nc) D.partial[static_cast<size_t>(chunk) * D.n_cand + c0 + lane] = acc;
+}
+
+// blockIdx.x = candidate, blockIdx.y = slot.
+__global__ __launch_bounds__(kEncThreads) void encode_param_delta_final_kernel(const ParamDeltaParams* param) {
+    const ParamDeltaParams& D = param[blockIdx.y];
+    const uint32_t c = blockIdx.x;
+    if (c >= D.n_cand) return;
+    const int lane = threadIdx.x;
+    double bits = 0.0;
+    uint64_t width = 0, moved = 0;
+    for (uint32_t j = lane; j < D.n_chunks; j += kEncThreads) {
+        const ParamDeltaCell cell = D.partial[static_cast<size_t>(j) * D.n_cand + c];
+        bits += cell.bits;
+        width += static_cast<uint64_t>(cell.sum_width);
+        moved += static_cast<uint64_t>(cell.moved);
+    }
+    bits = wave_sum(bits); width = wave_sum(width); moved = wave_sum(moved);
+    if (lane != 0) return;
+    if (D.cand[c].legal) D.out[c] = ParamDeltaCell{bits, static_cast<int64_t>(width), static_cast<int64_t>(moved)};
+    else D.out[c] = ParamDeltaCell{static_cast<double>(__builtin_inff()), 0, 0};
+}
+
 size_t encode_contexts_lds_bytes(int dim) { return static_cast<size_t>(2) * dim * kEncThreads * sizeof(int64_t); }
 int encode_block_threads() { return kEncThreads; }
 
@@ -523,6 +754,37 @@ hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(encode_delta_kernel, dim3(max_blocks, n_slots), dim3(kEncThreads), lds_bytes, stream, d_slots, d_delta);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_param_deltas(const EncodeParams* d_slots, const ParamDeltaParams* d_param, int n_slots, unsigned max_chunks,
+                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
+    if (n_slots <= 0 || max_cand == 0) return hipSuccess;
+    if (max_chunks > 0) {
+        const dim3 grid(max_chunks, (max_cand + kArmDeltaTile - 1) / kArmDeltaTile, n_slots);
+        // one launch per path that has slots (lds == 0: none); each workgroup of the other path's slots returns at once
+        if (lds_generic > 0) {
+            if (lds_generic > 64 * 1024) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_param_delta_kernel<false>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_generic));
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(encode_param_delta_kernel<false>, grid, dim3(kEncThreads), lds_generic, stream, d_slots, d_param);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        if (lds_incremental > 0) {
+            if (lds_incremental > 64 * 1024) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_param_delta_kernel<true>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_incremental));
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(encode_param_delta_kernel<true>, grid, dim3(kEncThreads), lds_incremental, stream, d_slots, d_param);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    hipLaunchKernelGGL(encode_param_delta_final_kernel, dim3(max_cand, n_slots), dim3(kEncThreads), 0, stream, d_param);
     return hipGetLastError();
 }
 

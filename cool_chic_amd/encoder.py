@@ -24,6 +24,14 @@ class SlotRate(NamedTuple):
     n_bytes_header: int
 
 
+class ParamDeltas(NamedTuple):
+    """What measure_param_deltas() found for one slot: rows are the ARM integers first .. first + len - 1, columns -1 and +1."""
+    first: int
+    bits: np.ndarray        # float64 [count][2]: change of total_bits; +inf: the move cannot be transmitted
+    sum_width: np.ndarray   # int64 [count][2]: exact change of the sum of interval widths
+    moved: np.ndarray       # int64 [count][2]: symbols whose width changed
+
+
 class EncodeBatch(_Handle):
     """One slot per cool-chic; run() encodes all of them in the same two launches, measure() prices them without the chain."""
 
@@ -90,6 +98,29 @@ class EncodeBatch(_Handle):
         (y, x) alone were v - 1 (plane 0) or v + 1 (plane 1); +inf where that leaves [-64, 63].  Valid until the next measure /
         measure_deltas / close."""
         return self._grid_map("ccd_enc_slot_delta_map", slot, grid, "<f4", (2,))
+
+    def measure_param_deltas(self, stream: int = 0, first: int = 0, count: int = -1, mode: int = 0):
+        """measure() followed by the ARM parameter table's launches: rate() as after measure(), and
+        param_deltas() of every slot for the ARM integers [first, first + count) in stream order (count < 0: all; clipped to
+        each slot's param_count()).  mode 0 automatic, 1 generic, 2 incremental (refused where a slot cannot take it)."""
+        check(lib().ccd_enc_measure_param_deltas(self._h, C.c_void_p(stream or None), int(first), int(count), int(mode)),
+              "ccd_enc_measure_param_deltas")
+
+    def param_count(self, slot: int) -> int:
+        """Transmitted integers of the slot's ARM: groups 0 and 1 of writer.network_layout."""
+        return check(lib().ccd_enc_slot_param_count(self._h, int(slot)), "ccd_enc_slot_param_count")
+
+    def param_deltas(self, slot: int) -> ParamDeltas:
+        """After measure_param_deltas() + wait(): per parameter and sign ([count][2], -1 first) the exact change of the slot's
+        total model bits (float64, +inf where the integer would leave int32), of its sum of interval widths and the number of
+        symbols whose width changed.  A slot with a latent outside the alphabet raises its status."""
+        first, count = C.c_int(0), C.c_int(0)
+        check(lib().ccd_enc_slot_param_deltas(self._h, int(slot), C.byref(first), C.byref(count), None, None, None), "ccd_enc_slot_param_deltas")
+        bits = np.empty((count.value, 2), np.float64)
+        sum_width, moved = np.empty((count.value, 2), np.int64), np.empty((count.value, 2), np.int64)
+        check(lib().ccd_enc_slot_param_deltas(self._h, int(slot), None, None, bits.ctypes.data, sum_width.ctypes.data, moved.ctypes.data),
+              "ccd_enc_slot_param_deltas")
+        return ParamDeltas(first.value, bits, sum_width, moved)
 
     def slot_status(self, slot: int) -> Tuple[int, np.ndarray]:
         """(status, counters) after wait(): counters[1] payload words, [2] inverted runs begun by the coder, [3] resolved

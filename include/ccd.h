@@ -470,6 +470,32 @@ int64_t ccd_enc_slot_rate_map(const ccd_enc* e, int slot, int grid, const float*
  * a NULL argument, a bad slot or grid, or when the last finished measure was not a measure_deltas that covered the slot. */
 int ccd_enc_measure_deltas(ccd_enc* e, void* stream);
 int ccd_enc_slot_delta_map(const ccd_enc* e, int slot, int grid, void** dev_ptr);
+/* ---- ARM parameter deltas: the exact change of a slot's model bits if ONE transmitted integer of its ARM were v - 1 or v + 1
+ * (DESIGN.md section 4.20).  Parameter k, 0 <= k < ccd_enc_slot_param_count, counts the ARM's integers in stream order
+ * (ccd_network_values: groups 0 and 1 of ccd_network_layout): the weights of every layer [out][in], the stabiliser's [2][dim],
+ * then the biases of every layer and the stabiliser's two.  The candidate network is the slot's with values[k] + s taken
+ * through the fixed-point conversion ccd_enc_add applies; per (k, s), s = -1 first:
+ *   bits       float64  total_bits with the candidate - total_bits as it is: the sum over the symbols whose interval width
+ *                       changed of log2(width) - log2(width'); exactly 0.0 when none did
+ *   sum_width  int64    the exact change of the meter's sum_width (over all grids)
+ *   moved      int64    the number of symbols whose width changed
+ * A candidate whose integer leaves int32 cannot be transmitted: +inf, 0, 0.
+ * ccd_enc_measure_param_deltas is a ccd_enc_measure(e, stream, 0) - same ccd_enc_slot_rate results, word for word, same rule of
+ * one operation in flight, ended by ccd_enc_wait - followed by the table's two launches for the parameters [first, first + count)
+ * of every slot (count < 0: all from first; the range is clipped to each slot's parameter count).  A slot's words do not depend
+ * on the range, the other slots, the device or the mode.  mode: 0 automatic (the incremental path where a slot's state fits the
+ * LDS, else the generic one), 1 the generic path (one full evaluation of the model per candidate and symbol), 2 the incremental
+ * path (the base evaluation's accumulators kept per lane, a candidate as a rank-1 update of the layer behind it): if a slot's
+ * state does not fit, the call returns CCD_ERR_UNSUPPORTED.  CCD_ERR_ARG (NULL handle, first < 0, another mode) and
+ * CCD_ERR_UNSUPPORTED (mode 2 as above; more than 65 535 slots or 2 x 2^21 candidates of one slot in a call) are found before
+ * the device is touched and leave the handle and the last table as they were; CCD_ERR_NOMEM / CCD_ERR_HIP leave no table.
+ * ccd_enc_slot_param_deltas: the slot's range into *first / *count and the three arrays [count][2] (any of the five may be
+ * NULL); returns the slot's status like ccd_enc_slot_delta_map (CCD_ERR_VALUE for a device latent outside the alphabet, nothing
+ * is written then).  CCD_ERR_ARG for a NULL handle, a bad slot, or when the last finished measure was not a
+ * measure_param_deltas that covered the slot: the next measure of any kind invalidates the table, a run does not touch it. */
+int ccd_enc_measure_param_deltas(ccd_enc* e, void* stream, int first, int count, int mode);
+int ccd_enc_slot_param_count(const ccd_enc* e, int slot);
+int ccd_enc_slot_param_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved);
 /* Size of a slot's payload buffer: every symbol has a width of at least 1 / 2^24, so n symbols give at most
  * 4 * (ceil(24 n / 32) + 2) bytes.  0 for n < 0. */
 size_t ccd_enc_payload_bound(int64_t n_symbols);

@@ -3,7 +3,10 @@ and 4.19).  The frames are walked in coding order: I frames go through NetworkQu
 InterNetworkQuantiser with the planes of the frames as they decode with the networks ALREADY CHOSEN as their references.  The
 float parameters are the stream's own integers dequantised; latents and every frame header stay as they are.
 
-    python tools/quantise_video_networks.py in.cool source.yuv out.cool --lmbda 1e-3 [--sweeps N] [--fast-path-only]
+    python tools/quantise_video_networks.py in.cool source.yuv out.cool --lmbda 1e-3 [--sweeps N] [--fast-path-only] [--refine-arm N]
+
+--refine-arm runs at most N steps of the +-1 descent over the ARM's integers (nnrefine.ArmRefiner) on
+every cool-chic after its steps are chosen: the rate alone moves, so the planes the later frames predict from stay.
 
 Prints bytes of networks, PSNR and cost of every frame before and after ("before": the stream's networks against the references
 as they are now), writes the stream, decodes it back with decode_video and asserts that every frame's planes are those the last
@@ -20,6 +23,7 @@ from cool_chic_amd.bitstream.decode import _split_frame, decode_video  # noqa: E
 from cool_chic_amd.bitstream.header import VideoHeader  # noqa: E402
 from cool_chic_amd.nnquant import NetworkQuantiser  # noqa: E402
 from cool_chic_amd.nnquant_inter import InterNetworkQuantiser  # noqa: E402
+from cool_chic_amd.nnrefine import ArmRefiner  # noqa: E402
 from cool_chic_amd.quality import read_source  # noqa: E402
 
 
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--lmbda", type=float, required=True)
     ap.add_argument("--sweeps", type=int, default=1)
     ap.add_argument("--fast-path-only", action="store_true", help="only networks whose ARM fits the pipelined entropy kernel")
+    ap.add_argument("--refine-arm", type=int, default=0, metavar="N", help="ArmRefiner.refine on every searched cool-chic, at most N steps")
     a = ap.parse_args()
     with open(a.stream, "rb") as f:
         bs = f.read()
@@ -63,6 +68,15 @@ def main():
     def floats(arch, nn):
         return writer.dequantise_network(arch, writer.network_values(arch, nn))
 
+    def refine(what, net, p, owner):
+        """(header, bytes_nn) of a searched network after --refine-arm."""
+        if a.refine_arm <= 0:
+            return net.header, net.bytes_nn
+        fine = ArmRefiner(0).refine(net.header, net.values, p, a.refine_arm, owner=owner)
+        print(f"  {what}: {len(fine.log)} refinement steps ({fine.stopped}), objective {fine.start_objective:.3f} -> "
+              f"{fine.log[-1].objective if fine.log else fine.start_objective:.3f} bits, {len(net.bytes_nn)} -> {len(fine.bytes_nn)} bytes")
+        return fine.header, fine.bytes_nn
+
     done = {}  # coding index -> the device planes of the frame under its chosen networks
     for k, (fh, _) in enumerate(parsed):
         frame_type = fh.get_value("frame_type")
@@ -76,12 +90,16 @@ def main():
                 before = ev.evaluate(a.lmbda)[0]
             res = NetworkQuantiser(0).search(arch, floats(arch, nn), ptrs[0], sources[k], a.lmbda, sweeps=a.sweeps,
                                              fast_path_only=a.fast_path_only, owner=owner)
-            row[0][0], row[0][1] = res.header, res.bytes_nn
+            row[0][0], row[0][1] = refine(f"frame {display[k]}", res, ptrs[0], owner)
             with RdEvaluator(0) as ev:
-                ev.add(res.header, res.bytes_nn, ptrs[0], sources[k], owner=owner)
+                ev.add(row[0][0], row[0][1], ptrs[0], sources[k], owner=owner)
                 after = ev.evaluate(a.lmbda)[0]
                 done[k] = [p.clone() for p in ev.planes(0)]
-            n_before, n_after = len(nn), len(res.bytes_nn)
+            if a.refine_arm > 0:
+                assert after.mse == res.candidate.mse and after.cost <= res.candidate.cost
+            else:
+                assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)
+            n_before, n_after = len(nn), len(row[0][1])
         else:
             n_refs = "IPB".index(frame_type)
             refs = [done[coding_of[int(r)]] for r in structure[k]["index_references"]][:n_refs]
@@ -94,12 +112,15 @@ def main():
                                                   (row[1][0], floats(row[1][0], row[1][1]), ptrs[1]), refs, gf, taps, sources[k], a.lmbda,
                                                   sweeps=a.sweeps, fast_path_only=a.fast_path_only, owner=owner)
             for role, net in enumerate(res.roles):
-                row[role][0], row[role][1] = net.header, net.bytes_nn
+                row[role][0], row[role][1] = refine(f"frame {display[k]} {('residue', 'motion')[role]}", net, ptrs[role], owner)
             with InterRdEvaluator(0) as ev:
                 ev.add(frame_type, (row[0][0], row[0][1], ptrs[0]), (row[1][0], row[1][1], ptrs[1]), refs, gf, taps, sources[k], owner=owner)
                 after = ev.evaluate(a.lmbda)[0]
                 done[k] = [p.clone() for p in ev.planes(0)]
-            assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)
+            if a.refine_arm > 0:  # the ARMs' integers move the rate alone
+                assert after.mse == res.candidate.mse and after.cost <= res.candidate.cost
+            else:
+                assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)
             n_after = len(row[0][1]) + len(row[1][1])
         print(f"frame {display[k]} ({frame_type}):")
         for label, c, n in (("before", before, n_before), ("after", after, n_after)):

@@ -40,6 +40,14 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     per module and role (median of 5, min, max), candidates per launch, the host share spent building candidates, and
                     the same candidates (built outside the timer) one at a time through InterRdEvaluator (add, evaluate, close)
 
+  --arm-refine      instead of the above: the ARM parameter table (EncodeBatch.measure_param_deltas) of
+                    kodim14, of the 24 streams of `kodak24` in one handle and of the 1080p I frame of gop1080p33 (--refine-sets):
+                    measure_param_deltas + wait for the whole table, event-timed and as wall time (3 warm-ups and the median of
+                    --runs), in modes 0 (automatic: the incremental path) and 1 (generic); the
+                    same candidates (built outside the timer) priced by the calls the parent commit has - one add_device slot
+                    per candidate over the shared latents, measure, chunked by max_in_flight_bytes as NetworkQuantiser does -
+                    and the ratio of the wall times; and one descent of 25 steps on kodim14 (ArmRefiner.refine)
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -772,6 +780,93 @@ def measure_networks(hdr, nn, payload, bitdepth, fdt, runs, lmbdas, descend_step
     return res
 
 
+def measure_arm_table(ccs, runs, warmup, descent_steps):
+    """The ARM parameter table of the cool-chics `ccs` [(header bytes, NN payload, latent payload)] in one handle."""
+    import time
+
+    import numpy as np
+
+    from cool_chic_amd._lib import CCHeader
+    from cool_chic_amd.nnquant import NetworkQuantiser
+    from cool_chic_amd.nnrefine import ArmRefiner
+
+    st = torch.cuda.current_stream().cuda_stream
+    dec = DecodeBatch(0)
+    for hdr, nn, payload in ccs:
+        dec.add(hdr, nn, payload, 0, 0)
+    dec.run(st); dec.wait(st)
+    n = len(ccs)
+    archs = [dec.header(s) for s in range(n)]
+    nns = [dec.network_bytes(s) for s in range(n)]
+    ptrs = [dec.latent_ptrs(s) for s in range(n)]
+    n_arm = [sum(writer.network_layout(a)[:2]) for a in archs]
+    res = {"streams": n, "symbols": int(sum(a.n_symbols for a in archs)), "candidates": 2 * sum(n_arm), "runs": runs, "warmup": warmup}
+    enc = EncodeBatch(0)
+    for s in range(n):
+        enc.add_device(archs[s], nns[s], ptrs[s], owner=dec)
+    for mode in (0, 1):  # automatic (the incremental path where the state fits the LDS) and generic
+        def table():
+            enc.measure_param_deltas(st, mode=mode)
+            enc.wait(st)
+        for _ in range(warmup):
+            table()
+        torch.cuda.synchronize()
+        ev_ms, wall = [], []
+        for _ in range(runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            table()
+            e1.record()
+            e1.synchronize()
+            wall.append(time.perf_counter() - t0)
+            ev_ms.append(e0.elapsed_time(e1))
+        res[f"table_mode{mode}"] = {"event_ms": {"median": round(statistics.median(ev_ms), 2), "min": round(min(ev_ms), 2), "max": round(max(ev_ms), 2)},
+                                    "wall_s": round(statistics.median(wall), 4)}
+    tables = [enc.param_deltas(s) for s in range(n)]
+    base = [enc.rate(s).total_bits for s in range(n)]
+    enc.close()
+    # the yardstick: every candidate a slot of its own over the shared latents; the candidates are built OUTSIDE the timer
+    nq = NetworkQuantiser(0)
+    yard, worst = 0.0, 0.0
+    for s in range(n):
+        values = writer.network_values(archs[s], nns[s])
+        cands = []
+        for k in range(n_arm[s]):
+            for sign in (-1, 1):
+                v = values.copy()
+                v[k] += sign
+                h = CCHeader.from_buffer_copy(bytes(archs[s]))
+                cands.append((h, writer.encode_network(h, v)))
+        chunk = nq.chunk_size(archs[s], 0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bits = []
+        for at in range(0, len(cands), chunk):
+            with EncodeBatch(0) as one:
+                for h, b in cands[at:at + chunk]:
+                    one.add_device(h, b, ptrs[s], owner=dec)
+                one.measure(st)
+                one.wait(st)
+                bits += [one.rate(i).total_bits for i in range(len(cands[at:at + chunk]))]
+        yard += time.perf_counter() - t0
+        got = np.asarray(bits).reshape(-1, 2) - base[s]  # two rounded totals apart: a plausibility check, not the accuracy test
+        worst = max(worst, float(np.abs(got - tables[s].bits).max()))
+        res.setdefault("yardstick_per_launch", chunk)
+    res["yardstick_wall_s"] = round(yard, 4)
+    res["ratio_yardstick_over_table_mode0"] = round(yard / res["table_mode0"]["wall_s"], 2)
+    res["largest_difference_from_the_yardstick_bits"] = worst
+    if descent_steps > 0:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fine = ArmRefiner(0).refine(archs[0], writer.network_values(archs[0], nns[0]), ptrs[0], descent_steps, owner=dec)
+        res["descent"] = {"steps": len(fine.log), "stopped": fine.stopped, "wall_s": round(time.perf_counter() - t0, 3),
+                          "objective_before": fine.start_objective, "objective_after": fine.log[-1].objective if fine.log else fine.start_objective,
+                          "bytes_nn_before": len(nns[0]), "bytes_nn_after": len(fine.bytes_nn)}
+    dec.close()
+    return res
+
+
 def ip_1080p():
     """A 1920x1080 I P stream in the geometry of gop1080p33, whose own structure (two I frames, hierarchical B between them) has
     no P frame: the I and P frames of `vid5` grown the way synth.gop1080p grows its donors."""
@@ -916,7 +1011,25 @@ def main():
     ap.add_argument("--follow", action="store_true", help="time an RDOQ step of an I frame whose claims follow the flows into its dependents instead")
     ap.add_argument("--networks", action="store_true", help="time the search over the networks' quantisation steps instead")
     ap.add_argument("--network-sets", default="kodak,1080p", help="with --networks: which of the two frames to measure")
+    ap.add_argument("--arm-refine", action="store_true", help="time the ARM parameter table and one descent instead")
+    ap.add_argument("--refine-sets", default="kodim14,kodak24,1080p", help="with --arm-refine: which of the three inputs to measure")
     a = ap.parse_args()
+    if a.arm_refine:
+        from cool_chic_amd.bitstream.decode import _split_frame
+        from cool_chic_amd.bitstream.header import VideoHeader
+
+        line = {"tool": "rd_bench --arm-refine"}
+        k24 = synth.workload("kodak24")["streams"]
+        if "kodim14" in a.refine_sets.split(","):
+            line["kodim14"] = measure_arm_table([synth.split_image_stream(k24[0])], a.runs, 3, 25)
+        if "kodak24" in a.refine_sets.split(","):
+            line["kodak24"] = measure_arm_table([synth.split_image_stream(bs) for bs in k24], a.runs, 3, 0)
+        if "1080p" in a.refine_sets.split(","):
+            fh, ccs, _ = _split_frame(VideoHeader().read_header(synth.gop1080p(2)[0]))
+            assert fh.get_value("frame_type") == "I"
+            line["gop1080p_I"] = measure_arm_table([(ccs[0][0].raw, ccs[0][1], ccs[0][2])], a.runs, 3, 0)
+        print(json.dumps(line))
+        return
     if a.networks and a.inter:
         runs = min(a.runs, 5)
         line = {"tool": "rd_bench --networks --inter", "runs": runs}
