@@ -30,6 +30,8 @@ package is the thin host-side mirror of the reference's decode surface:
                                                    iscore.InterScore, nnquant_inter.InterNetworkQuantiser
     (no counterpart: a +-1 descent over the ARM's transmitted integers, every candidate's rate change from one table)
                                                    EncodeBatch.measure_param_deltas, nnrefine.ArmRefiner
+    (the same over the IFCE's integers, and over both rate networks in one descent)
+                                                   EncodeBatch.measure_ifce_deltas, nnrefine.RateRefiner
 """
 from ._lib import CcdError, lib  # noqa: F401
 from .batch import DecodeBatch  # noqa: F401
@@ -69,7 +71,7 @@ def __getattr__(name):
         from . import nnquant_inter
 
         return getattr(nnquant_inter, name)
-    if name in ("ArmRefiner", "RefinedNetwork", "expgol_bit_deltas", "pick_moves"):
+    if name in ("ArmRefiner", "RateRefiner", "RefinedNetwork", "expgol_bit_deltas", "pick_moves"):
         from . import nnrefine
 
         return getattr(nnrefine, name)

@@ -216,6 +216,9 @@ SIGNATURES = {
     "ccd_enc_measure_param_deltas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "ccd_enc_slot_param_count": (C.c_int, [C.c_void_p, C.c_int]),
     "ccd_enc_slot_param_deltas": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccd_enc_measure_ifce_deltas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "ccd_enc_slot_ifce_count": (C.c_int, [C.c_void_p, C.c_int]),
+    "ccd_enc_slot_ifce_deltas": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccd_latent_footprint": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.POINTER(C.c_int32)]),
     "ccd_latent_probe_stride": (C.c_int, [C.POINTER(CCHeader), C.c_int, C.c_int]),
     "ccd_dsens_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -6,6 +6,7 @@
 
 #include "../../include/ccd.h"
 #include "ccd_armdelta_plan.hpp"
+#include "ccd_ifcedelta_plan.hpp"
 #include "ccd_lattice.hpp"
 
 namespace ccd {
@@ -119,6 +120,19 @@ struct ParamDeltaParams {
     ParamDeltaCell* out;        // [n_cand]: +inf, 0, 0 for a candidate that is not legal
     uint32_t n_cand, n_chunks;
     int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental: which instantiation prices the slot
+};
+
+// IFCE parameter deltas (encode_ifce_delta_kernel / encode_ifce_delta_final_kernel): what a slot of a
+// measure_ifce_deltas writes.  The chunks and the cells are the ARM table's.  The candidates are sorted by their grid (stably:
+// a grid's weights, then its biases, each in stream order), so that a tile of kArmDeltaTile candidates walks the blocks of as
+// few grids as the count allows; row[j] is the row of the table (2 (k - first) + (sign > 0)) sorted candidate j answers.
+struct IfceDeltaParams {
+    const IfceDeltaMove* cand;  // [n_cand], sorted by grid
+    const uint32_t* row;        // [n_cand]
+    ParamDeltaCell* partial;    // [n_chunks][n_cand], indexed like cand
+    ParamDeltaCell* out;        // [n_cand], indexed by row: +inf, 0, 0 for a candidate that is not legal
+    uint32_t n_cand, n_chunks;
+    int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental
 };
 
 // One copy of the ingest launch (ccd_ingest.hip): latent grid `src` of a slot whose latents were GIVEN as device pointers

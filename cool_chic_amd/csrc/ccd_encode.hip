@@ -41,6 +41,7 @@ constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever rea
 // unit's input pm.in (times one for a bias), bit for bit; pm is wave-uniform and the weights stay scalar loads.
 // kInputsOnly: the ARM's inputs (contexts and IFCE features) are left in the first dim columns and nothing else is done - the
 // incremental path of the parameter table keeps them there.
+// kIfce: one entry of the fixed-point IFCE of grid im.grid is taken as entry + im.inc (ifce_feature).
 struct LatentOverride { int grid, y, x, val; };
 // table indices (latent.py:156-165, rangecoder.py:90-91) of the ARM's two sums, as the Laplace parameters
 __device__ __forceinline__ void arm_sums_to_model(const EntropyParams& P, uint64_t st0, uint64_t st1, double& mu, double& rcp) {
@@ -51,9 +52,35 @@ __device__ __forceinline__ void arm_sums_to_model(const EntropyParams& P, uint64
     mu = -64.0 + static_cast<double>(mu_idx) * (1.0 / 256.0);
     rcp = P.rcp_table[sc_idx];
 }
-template <bool kOverride, bool kParam = false, bool kInputsOnly = false>
+// Feature o of the position (fy, fx) of grid g (coolchic.py:94-146): the accumulate over the fin source channels, the >> 24 and
+// the .to(torch.float) / back to int64 round trip around F.interpolate (coolchic.py:142-144).  fw_ / fb_: the grid's w[fin][n_if]
+// and b[n_if]; first: the stack is a single all-zero channel (coolchic.py:95-96).  kCand: the entry im names is taken as
+// entry + im.inc (the IFCE table's "what if"): the accumulator is a ring, so it is the accumulator as it is plus
+// im.inc times the source (times one for a bias); the caller has checked im.grid == g and im.out == o.  The base and the
+// candidate of either path of the table go through this one function.
+template <bool kOverride, bool kCand>
+__device__ __forceinline__ int64_t ifce_feature(const EntropyParams& P, int g, int fy, int fx, int o, int n_if, int fin, bool first,
+                                                int base_level, const int64_t* fw_, const int64_t* fb_, const LatentOverride& ov,
+                                                const IfceDeltaMove& im) {
+    uint64_t acc = static_cast<uint64_t>(fb_[o]);
+    if (kCand && im.in < 0) acc += static_cast<uint64_t>(im.inc);
+    if (!first) {
+        for (int c = 0; c < fin; ++c) {
+            const int m = g + 1 + c;
+            const int sh = P.level[m] - base_level;
+            int64_t v = P.latent[m][(fy >> sh) * P.grid_w[m] + (fx >> sh)];
+            if (kOverride && m == ov.grid && (fy >> sh) == ov.y && (fx >> sh) == ov.x) v = ov.val;
+            acc += static_cast<uint64_t>(v << 16) * static_cast<uint64_t>(fw_[c * n_if + o]);
+            if (kCand && c == im.in) acc += static_cast<uint64_t>(v << 16) * static_cast<uint64_t>(im.inc);
+        }
+    }
+    const int64_t q8 = static_cast<int64_t>(acc) >> 24;
+    return static_cast<int32_t>(static_cast<int64_t>(static_cast<float>(q8)));
+}
+template <bool kOverride, bool kParam = false, bool kInputsOnly = false, bool kIfce = false>
 __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g, int y, int x, int lane, unsigned char* smem_raw,
-                                                   const LatentOverride& ov, double& mu, double& rcp, const ArmDeltaMove& pm = ArmDeltaMove{}) {
+                                                   const LatentOverride& ov, double& mu, double& rcp, const ArmDeltaMove& pm = ArmDeltaMove{},
+                                                   const IfceDeltaMove& im = IfceDeltaMove{}) {
     const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
     int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
     int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
@@ -78,19 +105,9 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
         const bool first = g == n_grids - 1;          // the stack is a single all-zero channel (coolchic.py:95-96)
         const int base_level = first ? 0 : P.level[g + 1];
         for (int o = 0; o < n_if; ++o) {
-            uint64_t acc = static_cast<uint64_t>(fb_[o]);
-            if (!first) {
-                for (int c = 0; c < fin; ++c) {
-                    const int m = g + 1 + c;
-                    const int sh = P.level[m] - base_level;
-                    int64_t v = P.latent[m][(fy >> sh) * P.grid_w[m] + (fx >> sh)];
-                    if (kOverride && m == ov.grid && (fy >> sh) == ov.y && (fx >> sh) == ov.x) v = ov.val;
-                    acc += static_cast<uint64_t>(v << 16) * static_cast<uint64_t>(fw_[c * n_if + o]);
-                }
-            }
-            const int64_t q8 = static_cast<int64_t>(acc) >> 24;
-            // .to(torch.float) / back to int64 round trip around F.interpolate (coolchic.py:142-144)
-            const int64_t f = static_cast<int32_t>(static_cast<int64_t>(static_cast<float>(q8)));
+            int64_t f;
+            if (kIfce && im.grid == g && im.out == o) f = ifce_feature<kOverride, true>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, im);
+            else f = ifce_feature<kOverride, false>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, im);
             xa[(n_sp + o) * kEncThreads] = static_cast<int64_t>(static_cast<uint64_t>(f) << 16);
         }
     } else {
@@ -549,13 +566,54 @@ __device__ __forceinline__ ArmBase arm_base_store(const EntropyParams& P, int64_
     }
     return B;
 }
+// Input `in` of layer l1 (l1 == n_hidden: of the output layer) moved by d: the layer's accumulators move by d * w[in][.] (re-rounded
+// by their own ReLU), the layers behind it are recomputed in full through the two scratch columns sa and sa + dim columns; the last
+// hidden layer's units go straight into the output layer's sums.  a0, a1: the output layer's two accumulators, the base's on
+// entry.  sa is touched only when a hidden layer lies behind l1, the second column only when two do.
+__device__ __forceinline__ void arm_input_moved(const EntropyParams& P, int64_t* x0, int l1, int in, uint64_t d, uint64_t& a0, uint64_t& a1, int64_t* sa) {
+    const int dim = P.dim, n_hidden = P.n_layers - 1;
+    const int64_t hidden_len = static_cast<int64_t>(dim) * dim + dim;
+    const int64_t* wo = P.arm + n_hidden * hidden_len;  // the output layer: w[dim][2], b[2]
+    if (l1 == n_hidden) {
+        a0 += d * static_cast<uint64_t>(wo[in * 2]);
+        a1 += d * static_cast<uint64_t>(wo[in * 2 + 1]);
+        return;
+    }
+    const int64_t* lw = P.arm + l1 * hidden_len;
+    const int64_t* acc = x0 + (l1 + 1) * dim * kEncThreads;
+    int64_t* sb = sa + dim * kEncThreads;
+    const bool last = l1 + 1 == n_hidden;
+    if (last) { a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]); }
+    for (int o = 0; o < dim; ++o) {
+        const int64_t v = relu16(static_cast<int64_t>(static_cast<uint64_t>(acc[o * kEncThreads]) + d * static_cast<uint64_t>(lw[in * dim + o])));
+        if (last) {
+            a0 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2]);
+            a1 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2 + 1]);
+        } else sa[o * kEncThreads] = v;
+    }
+    if (last) return;
+    a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]);
+    for (int m = l1 + 1; m < n_hidden; ++m) {  // in full, as encode_pixel_model does
+        const int64_t* mw = P.arm + m * hidden_len;
+        const int64_t* mb = mw + dim * dim;
+        const bool fold = m + 1 == n_hidden;  // (the sums are a ring: the order the units are added in does not matter)
+        for (int o = 0; o < dim; ++o) {
+            uint64_t t = static_cast<uint64_t>(mb[o]);
+            for (int k = 0; k < dim; ++k) t += static_cast<uint64_t>(sa[k * kEncThreads]) * static_cast<uint64_t>(mw[k * dim + o]);
+            const int64_t v = relu16(static_cast<int64_t>(t));
+            if (fold) {
+                a0 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2]);
+                a1 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2 + 1]);
+            } else sb[o * kEncThreads] = v;
+        }
+        int64_t* t = sa; sa = sb; sb = t;
+    }
+}
 // The ARM's two sums with the candidate's entry moved.  Every step is the full evaluation's arithmetic modulo 2^64: the moved
 // unit's accumulator changes by inc * input, its activation by delta, the next layer's accumulators by delta * weight (re-rounded
 // by their own ReLU), the layers behind that are recomputed in full.  delta == 0: the base's sums.
 __device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x0, const ArmBase& B, const ArmDeltaMove& pm, uint64_t& st0, uint64_t& st1) {
     const int dim = P.dim, n_hidden = P.n_layers - 1;
-    const int64_t hidden_len = static_cast<int64_t>(dim) * dim + dim;
-    const int64_t* wo = P.arm + n_hidden * hidden_len;  // the output layer: w[dim][2], b[2]
     uint64_t a0 = B.a0, a1 = B.a1;
     st0 = B.st0; st1 = B.st1;
     if (pm.layer >= n_hidden) {  // output layer or stabiliser: one accumulator moves
@@ -567,47 +625,49 @@ __device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x
         const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(arm_input(x0, dim, l, pm.in)));
         const int64_t a = x0[((l + 1) * dim + pm.out) * kEncThreads];
         const int64_t delta = relu16(static_cast<int64_t>(static_cast<uint64_t>(a) + c)) - relu16(a);
-        if (delta != 0) {
-            const uint64_t d = static_cast<uint64_t>(delta);
-            if (l + 1 == n_hidden) {  // the output layer is next
-                a0 += d * static_cast<uint64_t>(wo[pm.out * 2]);
-                a1 += d * static_cast<uint64_t>(wo[pm.out * 2 + 1]);
-            } else {
-                const int64_t* lw = P.arm + (l + 1) * hidden_len;  // layer l + 1: its accumulators move by delta * w[out][.]
-                const int64_t* acc = x0 + (l + 2) * dim * kEncThreads;
-                int64_t* sa = x0 + (n_hidden + 1) * dim * kEncThreads;  // scratch, touched only when a layer lies behind l + 1
-                int64_t* sb = sa + dim * kEncThreads;
-                const bool last = l + 2 == n_hidden;
-                if (last) { a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]); }
-                for (int o = 0; o < dim; ++o) {
-                    const int64_t v = relu16(static_cast<int64_t>(static_cast<uint64_t>(acc[o * kEncThreads]) + d * static_cast<uint64_t>(lw[pm.out * dim + o])));
-                    if (last) {
-                        a0 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2]);
-                        a1 += static_cast<uint64_t>(v) * static_cast<uint64_t>(wo[o * 2 + 1]);
-                    } else sa[o * kEncThreads] = v;
-                }
-                if (!last) {
-                    for (int m = l + 2; m < n_hidden; ++m) {  // in full, as encode_pixel_model does
-                        const int64_t* mw = P.arm + m * hidden_len;
-                        const int64_t* mb = mw + dim * dim;
-                        for (int o = 0; o < dim; ++o) {
-                            uint64_t t = static_cast<uint64_t>(mb[o]);
-                            for (int k = 0; k < dim; ++k) t += static_cast<uint64_t>(sa[k * kEncThreads]) * static_cast<uint64_t>(mw[k * dim + o]);
-                            sb[o * kEncThreads] = relu16(static_cast<int64_t>(t));
-                        }
-                        int64_t* t = sa; sa = sb; sb = t;
-                    }
-                    a0 = static_cast<uint64_t>(wo[2 * dim]); a1 = static_cast<uint64_t>(wo[2 * dim + 1]);
-                    for (int k = 0; k < dim; ++k) {
-                        const uint64_t v = static_cast<uint64_t>(sa[k * kEncThreads]);
-                        a0 += v * static_cast<uint64_t>(wo[k * 2]);
-                        a1 += v * static_cast<uint64_t>(wo[k * 2 + 1]);
-                    }
-                }
-            }
-        }
+        if (delta != 0) arm_input_moved(P, x0, l + 1, pm.out, static_cast<uint64_t>(delta), a0, a1, x0 + (n_hidden + 1) * dim * kEncThreads);
     }
     st0 += a0; st1 += a1;
+}
+
+// The IFCE table's candidate on the same kept state: feature im.out of the pixel's grid is evaluated again with
+// the candidate's entry moved (ifce_feature, fin multiply-adds).  Its change d in the << 16 input form moves the stabiliser's
+// two sums by d * ws[n_sp + out][.] and ALL of layer 0's accumulators by d * w0[n_sp + out][.] - both exact in the ring - and
+// every layer behind layer 0 is recomputed in full.  Of the kept state a candidate reads the inputs and layer 0's accumulators
+// only, so the columns of the later layers' accumulators serve as the scratch.  d == 0: the base's sums.
+__device__ __forceinline__ void ifce_candidate(const EntropyParams& P, int g, int y, int x, int64_t* x0, const ArmBase& B, const IfceDeltaMove& im,
+                                               uint64_t& st0, uint64_t& st1) {
+    const int dim = P.dim, n_if = P.n_ifce_out, fin = P.ifce_in[g], row = P.n_spatial + im.out;
+    const int64_t* fw_ = P.ifce + P.ifce_off[g];
+    const bool first = g == P.n_grids - 1;
+    const int64_t f = ifce_feature<false, true>(P, g, y >> 1, x >> 1, im.out, n_if, fin, first, first ? 0 : P.level[g + 1], fw_, fw_ + fin * n_if,
+                                                LatentOverride{}, im);
+    const uint64_t d = (static_cast<uint64_t>(f) << 16) - static_cast<uint64_t>(x0[row * kEncThreads]);
+    uint64_t a0 = B.a0, a1 = B.a1;
+    st0 = B.st0; st1 = B.st1;
+    if (d != 0) {
+        const int64_t* ws = P.arm + (P.arm_len - 2 - 2 * dim);
+        st0 += d * static_cast<uint64_t>(ws[row * 2]);
+        st1 += d * static_cast<uint64_t>(ws[row * 2 + 1]);
+        // the scratch: the columns of layer 1's and layer 2's accumulators, which no IFCE candidate reads (ifcedelta_incremental_lds)
+        arm_input_moved(P, x0, 0, row, d, a0, a1, x0 + 2 * dim * kEncThreads);
+    }
+    st0 += a0; st1 += a1;
+}
+
+// What one 64-pixel block adds to a candidate's running sums: the lanes' log2(width) - log2(width'), width' - width and "moved"
+// through wave_sum's fixed tree, kept by the lane `mine` names.  A block in which no lane's width moved adds nothing (its wave sums
+// would be +0.0, 0, 0).  Every lane of the wave calls it.
+__device__ __forceinline__ void delta_block_sums(double d_bits, int64_t d_width, bool mine, ParamDeltaCell& acc) {
+    const bool moved = d_width != 0;
+    if (__ballot(moved) == 0) return;
+    const double s_bits = wave_sum(d_bits);
+    const uint64_t s_width = wave_sum(static_cast<uint64_t>(d_width)), s_moved = wave_sum(static_cast<uint64_t>(moved ? 1 : 0));
+    if (mine) {
+        acc.bits += s_bits;
+        acc.sum_width += static_cast<int64_t>(s_width);
+        acc.moved += static_cast<int64_t>(s_moved);
+    }
 }
 
 // kIncremental: the slots whose path is the incremental one (ParamDeltaParams::path); the other instantiation takes the rest.
@@ -666,18 +726,98 @@ __global__ __launch_bounds__(kEncThreads) void encode_param_delta_kernel(const E
                     d_width = static_cast<int64_t>(w) - static_cast<int64_t>(width);
                 }
             }
-            const bool moved = d_width != 0;
-            if (__ballot(moved) == 0) continue;
-            const double s_bits = wave_sum(d_bits);
-            const uint64_t s_width = wave_sum(static_cast<uint64_t>(d_width)), s_moved = wave_sum(static_cast<uint64_t>(moved ? 1 : 0));
-            if (static_cast<uint32_t>(lane) == ci) {
-                acc.bits += s_bits;
-                acc.sum_width += static_cast<int64_t>(s_width);
-                acc.moved += static_cast<int64_t>(s_moved);
-            }
+            delta_block_sums(d_bits, d_width, static_cast<uint32_t>(lane) == ci, acc);
         }
     }
     if (static_cast<uint32_t>(lane) < nc) D.partial[static_cast<size_t>(chunk) * D.n_cand + c0 + lane] = acc;
+}
+
+// ---- IFCE parameter deltas: the same table for the transmitted IFCE integers -----------------------------------
+// The launches, the chunks, the cells and the order of a candidate's additions are the ARM table's.  What differs: a candidate
+// of grid g can only move symbols of grid g, and a block's grid is uniform, so the wave walks only the blocks of the grids its
+// tile's candidates name (the candidates are sorted by grid: the first and the last give the range) and a candidate adds nothing
+// for a block of another grid - which is what it would add there, a workgroup in which no width moved.  Generic path: feature
+// im.out of grid im.grid through ifce_feature<.., true> inside a full encode_pixel_model; incremental path: ifce_candidate.
+template <bool kIncremental>
+__global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_kernel(const EncodeParams* slots, const IfceDeltaParams* param) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const EncodeParams& Q = slots[blockIdx.z];
+    const EntropyParams& P = Q.ep;
+    const IfceDeltaParams& D = param[blockIdx.z];
+    const uint32_t chunk = blockIdx.x, c0 = blockIdx.y * kArmDeltaTile;
+    if ((D.path == kArmDeltaIncremental) != kIncremental || chunk >= D.n_chunks || c0 >= D.n_cand) return;
+    const int lane = threadIdx.x;
+    const int n_grids = P.n_grids;
+    const uint32_t nc = min(static_cast<uint32_t>(kArmDeltaTile), D.n_cand - c0);
+    const int g_lo = D.cand[c0].grid, g_hi = D.cand[c0 + nc - 1].grid;  // 0 <= g_lo <= g_hi < n_grids (ifcedelta_place)
+    const uint32_t b_first = max(chunk * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.block_first[g_lo]);
+    const uint32_t b_end = min(min((chunk + 1) * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.n_blocks),
+                               g_hi + 1 < n_grids ? Q.block_first[g_hi + 1] : Q.n_blocks);
+    int64_t* x0 = reinterpret_cast<int64_t*>(smem_raw) + lane;
+    ParamDeltaCell acc{0.0, 0, 0};  // of sorted candidate c0 + lane
+    int g = g_lo;
+#pragma unroll 1
+    for (uint32_t b = b_first; b < b_end; ++b) {
+        while (g + 1 < n_grids && b >= Q.block_first[g + 1]) ++g;
+        const int H = P.grid_h[g], W = P.grid_w[g];
+        const int p = static_cast<int>(b - Q.block_first[g]) * kEncThreads + lane;
+        const int sym = p < H * W ? P.latent[g][p] : 0;
+        const bool ok = p < H * W && in_alphabet(sym);
+        const int y = ok ? p / W : 0, x = ok ? p - y * W : 0;
+        double mu, rcp, base = 0.0;
+        uint32_t width = 0;
+        ArmBase B{0, 0, 0, 0};
+        if (ok) {
+            if (kIncremental) {
+                encode_pixel_model<false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+                B = arm_base_store(P, x0);
+                arm_sums_to_model(P, B.st0 + B.a0, B.st1 + B.a1, mu, rcp);
+            } else encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+            width = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
+            base = log2(static_cast<double>(width));
+        }
+#pragma unroll 1
+        for (uint32_t ci = 0; ci < nc; ++ci) {
+            const IfceDeltaMove im = D.cand[c0 + ci];  // wave-uniform
+            if (!im.legal || im.grid != g) continue;
+            double d_bits = 0.0;
+            int64_t d_width = 0;
+            if (ok) {
+                if (kIncremental) {
+                    uint64_t st0, st1;
+                    ifce_candidate(P, g, y, x, x0, B, im, st0, st1);
+                    arm_sums_to_model(P, st0, st1, mu, rcp);
+                } else encode_pixel_model<false, false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp, ArmDeltaMove{}, im);
+                const uint32_t w = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
+                if (w != width) {
+                    d_bits = base - log2(static_cast<double>(w));
+                    d_width = static_cast<int64_t>(w) - static_cast<int64_t>(width);
+                }
+            }
+            delta_block_sums(d_bits, d_width, static_cast<uint32_t>(lane) == ci, acc);
+        }
+    }
+    if (static_cast<uint32_t>(lane) < nc) D.partial[static_cast<size_t>(chunk) * D.n_cand + c0 + lane] = acc;
+}
+
+// blockIdx.x = sorted candidate, blockIdx.y = slot: encode_param_delta_final_kernel's additions, stored at the candidate's row.
+__global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_final_kernel(const IfceDeltaParams* param) {
+    const IfceDeltaParams& D = param[blockIdx.y];
+    const uint32_t c = blockIdx.x;
+    if (c >= D.n_cand) return;
+    const int lane = threadIdx.x;
+    double bits = 0.0;
+    uint64_t width = 0, moved = 0;
+    for (uint32_t j = lane; j < D.n_chunks; j += kEncThreads) {
+        const ParamDeltaCell cell = D.partial[static_cast<size_t>(j) * D.n_cand + c];
+        bits += cell.bits;
+        width += static_cast<uint64_t>(cell.sum_width);
+        moved += static_cast<uint64_t>(cell.moved);
+    }
+    bits = wave_sum(bits); width = wave_sum(width); moved = wave_sum(moved);
+    if (lane != 0) return;
+    if (D.cand[c].legal) D.out[D.row[c]] = ParamDeltaCell{bits, static_cast<int64_t>(width), static_cast<int64_t>(moved)};
+    else D.out[D.row[c]] = ParamDeltaCell{static_cast<double>(__builtin_inff()), 0, 0};
 }
 
 // blockIdx.x = candidate, blockIdx.y = slot.
@@ -757,35 +897,50 @@ hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* 
     return hipGetLastError();
 }
 
-hipError_t launch_encode_param_deltas(const EncodeParams* d_slots, const ParamDeltaParams* d_param, int n_slots, unsigned max_chunks,
-                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
+// What the ARM's and the IFCE's table share: one launch of the table kernel per path that has slots (lds == 0: none; each
+// workgroup of the other path's slots returns at once), then the final kernel.
+template <class Params>
+static hipError_t launch_delta_table(void (*generic)(const EncodeParams*, const Params*), void (*incremental)(const EncodeParams*, const Params*),
+                                     void (*final)(const Params*), const EncodeParams* d_slots, const Params* d_param, int n_slots,
+                                     unsigned max_chunks, unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
     if (n_slots <= 0 || max_cand == 0) return hipSuccess;
     if (max_chunks > 0) {
         const dim3 grid(max_chunks, (max_cand + kArmDeltaTile - 1) / kArmDeltaTile, n_slots);
-        // one launch per path that has slots (lds == 0: none); each workgroup of the other path's slots returns at once
         if (lds_generic > 0) {
             if (lds_generic > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_param_delta_kernel<false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_generic));
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(generic), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   static_cast<int>(lds_generic));
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(encode_param_delta_kernel<false>, grid, dim3(kEncThreads), lds_generic, stream, d_slots, d_param);
+            hipLaunchKernelGGL(generic, grid, dim3(kEncThreads), lds_generic, stream, d_slots, d_param);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
         if (lds_incremental > 0) {
             if (lds_incremental > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(encode_param_delta_kernel<true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_incremental));
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(incremental), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   static_cast<int>(lds_incremental));
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(encode_param_delta_kernel<true>, grid, dim3(kEncThreads), lds_incremental, stream, d_slots, d_param);
+            hipLaunchKernelGGL(incremental, grid, dim3(kEncThreads), lds_incremental, stream, d_slots, d_param);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
     }
-    hipLaunchKernelGGL(encode_param_delta_final_kernel, dim3(max_cand, n_slots), dim3(kEncThreads), 0, stream, d_param);
+    hipLaunchKernelGGL(final, dim3(max_cand, n_slots), dim3(kEncThreads), 0, stream, d_param);
     return hipGetLastError();
+}
+
+hipError_t launch_encode_param_deltas(const EncodeParams* d_slots, const ParamDeltaParams* d_param, int n_slots, unsigned max_chunks,
+                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
+    return launch_delta_table(encode_param_delta_kernel<false>, encode_param_delta_kernel<true>, encode_param_delta_final_kernel, d_slots,
+                              d_param, n_slots, max_chunks, max_cand, lds_generic, lds_incremental, stream);
+}
+
+hipError_t launch_encode_ifce_deltas(const EncodeParams* d_slots, const IfceDeltaParams* d_param, int n_slots, unsigned max_chunks,
+                                     unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
+    return launch_delta_table(encode_ifce_delta_kernel<false>, encode_ifce_delta_kernel<true>, encode_ifce_delta_final_kernel, d_slots,
+                              d_param, n_slots, max_chunks, max_cand, lds_generic, lds_incremental, stream);
 }
 
 }  // namespace ccd

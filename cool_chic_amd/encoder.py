@@ -114,13 +114,32 @@ class EncodeBatch(_Handle):
         """After measure_param_deltas() + wait(): per parameter and sign ([count][2], -1 first) the exact change of the slot's
         total model bits (float64, +inf where the integer would leave int32), of its sum of interval widths and the number of
         symbols whose width changed.  A slot with a latent outside the alphabet raises its status."""
+        return self._table("ccd_enc_slot_param_deltas", slot)
+
+    def _table(self, getter: str, slot: int) -> ParamDeltas:
+        fn = getattr(lib(), getter)
         first, count = C.c_int(0), C.c_int(0)
-        check(lib().ccd_enc_slot_param_deltas(self._h, int(slot), C.byref(first), C.byref(count), None, None, None), "ccd_enc_slot_param_deltas")
+        check(fn(self._h, int(slot), C.byref(first), C.byref(count), None, None, None), getter)
         bits = np.empty((count.value, 2), np.float64)
         sum_width, moved = np.empty((count.value, 2), np.int64), np.empty((count.value, 2), np.int64)
-        check(lib().ccd_enc_slot_param_deltas(self._h, int(slot), None, None, bits.ctypes.data, sum_width.ctypes.data, moved.ctypes.data),
-              "ccd_enc_slot_param_deltas")
+        check(fn(self._h, int(slot), None, None, bits.ctypes.data, sum_width.ctypes.data, moved.ctypes.data), getter)
         return ParamDeltas(first.value, bits, sum_width, moved)
+
+    def measure_ifce_deltas(self, stream: int = 0, first: int = 0, count: int = -1, mode: int = 0):
+        """measure() followed by the IFCE parameter table's launches: rate() as after measure(), and
+        ifce_deltas() of every slot for the IFCE integers [first, first + count) in stream order (count < 0: all; clipped to each
+        slot's ifce_count()).  Modes as measure_param_deltas.  A handle holds one table: param_deltas() refuses after this."""
+        check(lib().ccd_enc_measure_ifce_deltas(self._h, C.c_void_p(stream or None), int(first), int(count), int(mode)),
+              "ccd_enc_measure_ifce_deltas")
+
+    def ifce_count(self, slot: int) -> int:
+        """Transmitted integers of the slot's IFCE: groups 2 and 3 of writer.network_layout; 0 for a slot without IFCE."""
+        return check(lib().ccd_enc_slot_ifce_count(self._h, int(slot)), "ccd_enc_slot_ifce_count")
+
+    def ifce_deltas(self, slot: int) -> ParamDeltas:
+        """After measure_ifce_deltas() + wait(): param_deltas()' three arrays for the IFCE integers; rows count from the first
+        IFCE integer, so row r is values[param_count(slot) + first + r] of writer.network_values."""
+        return self._table("ccd_enc_slot_ifce_deltas", slot)
 
     def slot_status(self, slot: int) -> Tuple[int, np.ndarray]:
         """(status, counters) after wait(): counters[1] payload words, [2] inverted runs begun by the coder, [3] resolved

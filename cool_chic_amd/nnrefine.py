@@ -6,7 +6,11 @@ reconstruction is needed - the same code serves an intra frame and both cool-chi
 for the exact change of the latents' model bits for -1 and +1 at every ARM integer (EncodeBatch.measure_param_deltas), adds the
 exact change of the payload's size, picks moves, and accepts them only if the existing meter says that the objective fell.
 
-`expgol_bit_deltas` and `pick_moves` are pure functions, testable without a device."""
+RateRefiner is the same descent over both rate networks, the ARM and the IFCE: the IFCE's integers change the
+features the ARM reads and nothing else, so the objective holds for them too.
+
+`expgol_bit_deltas`, `payload_byte_deltas`, their `rate_` forms over groups 0 .. 3 and `pick_moves` are pure functions, testable
+without a device."""
 from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
@@ -63,12 +67,10 @@ def _arm_groups(arch: CCHeader, values: np.ndarray):
     return layout, v.astype(np.int64)
 
 
-def expgol_bit_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
-    """float64 [n_arm][2] (-1 first): the exact change of the NN payload's bit count before padding if ARM integer k alone were
-    values[k] - 1 / + 1, under the orders in arch.nn_expgol_cnt.  +inf where the integer would leave int32."""
+def _expgol_bit_deltas(arch: CCHeader, values: np.ndarray, n_groups: int) -> np.ndarray:
     layout, v = _arm_groups(arch, values)
-    n_w, n_arm = layout[0], layout[0] + layout[1]
-    count = np.repeat(np.array([arch.nn_expgol_cnt[0], arch.nn_expgol_cnt[1]], np.int64), [n_w, n_arm - n_w])
+    n_arm = sum(layout[:n_groups])  # the groups are contiguous in stream order
+    count = np.repeat(np.array([arch.nn_expgol_cnt[g] for g in range(n_groups)], np.int64), layout[:n_groups])
     a = v[:n_arm]
     base = _code_len(a, count)
     out = np.empty((n_arm, 2), np.float64)
@@ -78,18 +80,28 @@ def expgol_bit_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
     return out
 
 
-def payload_byte_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
-    """float64 [n_arm][2]: the exact change of 8 * len(bytes_nn) for the same single moves when every group's order is chosen
-    again (writer.best_expgol, then writer.encode_network: what ArmRefiner builds), relative to `values` with ITS best orders.
-    A group's bits at every order change by the one code that moved, so the new minimum needs no second pass over the group."""
+def expgol_bit_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
+    """float64 [n_arm][2] (-1 first): the exact change of the NN payload's bit count before padding if ARM integer k alone were
+    values[k] - 1 / + 1, under the orders in arch.nn_expgol_cnt.  +inf where the integer would leave int32."""
+    return _expgol_bit_deltas(arch, values, 2)
+
+
+def rate_expgol_bit_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
+    """expgol_bit_deltas for both rate networks: float64 [n_arm + n_ifce][2], groups 0 .. 3 of writer.network_layout (the ARM's
+    weights and biases, then the IFCE's), which follow each other in the stream: row k is values[k]."""
+    return _expgol_bit_deltas(arch, values, 4)
+
+
+def _payload_byte_deltas(arch: CCHeader, values: np.ndarray, n_groups: int) -> np.ndarray:
     layout, v = _arm_groups(arch, values)
-    n_w, n_arm = layout[0], layout[0] + layout[1]
+    n_arm = sum(layout[:n_groups])
     orders = np.arange(MAX_ORDER + 1, dtype=np.int64)
     at = np.cumsum([0] + layout)
     best = [int(_code_len(v[at[g]:at[g + 1], None], orders[None, :]).sum(axis=0).min()) if layout[g] else 0 for g in range(8)]
     total = sum(best)
     out = np.empty((n_arm, 2), np.float64)
-    for g, (lo, hi) in enumerate(((0, n_w), (n_w, n_arm))):
+    for g in range(n_groups):
+        lo, hi = int(at[g]), int(at[g + 1])
         a = v[lo:hi]
         per_order = _code_len(a[:, None], orders[None, :])            # [n][13]
         group = per_order.sum(axis=0)                                  # [13]
@@ -99,6 +111,18 @@ def payload_byte_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
             out[lo:hi, j] = 8.0 * (-(-bits // 8) - -(-total // 8))
             out[lo:hi, j][(a + s < INT32_MIN) | (a + s > INT32_MAX)] = np.inf
     return out
+
+
+def payload_byte_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
+    """float64 [n_arm][2]: the exact change of 8 * len(bytes_nn) for the same single moves when every group's order is chosen
+    again (writer.best_expgol, then writer.encode_network: what ArmRefiner builds), relative to `values` with ITS best orders.
+    A group's bits at every order change by the one code that moved, so the new minimum needs no second pass over the group."""
+    return _payload_byte_deltas(arch, values, 2)
+
+
+def rate_payload_byte_deltas(arch: CCHeader, values: np.ndarray) -> np.ndarray:
+    """payload_byte_deltas for both rate networks: float64 [n_arm + n_ifce][2], groups 0 .. 3."""
+    return _payload_byte_deltas(arch, values, 4)
 
 
 def pick_moves(d_latent: np.ndarray, d_nn: np.ndarray, max_moves: int) -> List[Move]:
@@ -148,6 +172,16 @@ class ArmRefiner:
             enc.wait(stream)
             return enc.rate(slot).total_bits, enc.param_deltas(slot)
 
+    _covers = "the ARM"
+
+    def _n_params(self, h: CCHeader) -> int:
+        """Rows the table of _table() has: the integers refine() may move are values[:this]."""
+        return sum(writer.network_layout(h)[:2])
+
+    def _nn_deltas(self, h: CCHeader, values: np.ndarray) -> np.ndarray:
+        """The exact change of 8 * len(bytes_nn) for every row and sign of the table."""
+        return payload_byte_deltas(h, values)
+
     def _price(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
         """total_bits of a candidate by the existing meter; None where the library refuses the network."""
         from .encoder import EncodeBatch
@@ -187,10 +221,9 @@ class ArmRefiner:
             objective = base_bits + 8.0 * len(nn)
             if start is None:
                 start = objective
-            n_arm = table.bits.shape[0]
-            if table.first != 0 or n_arm != sum(writer.network_layout(h)[:2]):
-                raise ValueError("the table does not cover the ARM")
-            moves = pick_moves(table.bits, payload_byte_deltas(h, values), int(batch))
+            if table.first != 0 or table.bits.shape[0] != self._n_params(h):
+                raise ValueError("the table does not cover " + self._covers)
+            moves = pick_moves(table.bits, self._nn_deltas(h, values), int(batch))
             if not moves:
                 stopped = "no move promises a gain"
                 break
@@ -222,3 +255,57 @@ class ArmRefiner:
             bits = self._price(h, nn, ptrs, owner, stream)
             start = float("inf") if bits is None else bits + 8.0 * len(nn)
         return RefinedNetwork(h, nn, values, start, log, stopped)
+
+
+class RateRefiner(ArmRefiner):
+    """refine(): ArmRefiner's descent over BOTH rate networks of one cool-chic, the ARM and the IFCE.  The
+    IFCE's integers change the features the ARM reads and nothing else, so the objective, the acceptance rule and the meter are
+    ArmRefiner's; every step takes both tables (EncodeBatch.measure_param_deltas, measure_ifce_deltas), makes ONE pick_moves over
+    their rows and builds the candidate with all orders chosen again.  Groups 0 .. 3 are contiguous in the stream, so a
+    Move.index is an index into `values` for both modules.  modules=("ifce",) refines the IFCE alone, ("arm",) is ArmRefiner."""
+
+    _covers = "the ARM and the IFCE"
+
+    def __init__(self, device: int = 0, modules: Sequence[str] = ("arm", "ifce")):
+        super().__init__(device)
+        self.modules = tuple(modules)
+        if not self.modules or any(m not in ("arm", "ifce") for m in self.modules) or len(set(self.modules)) != len(self.modules):
+            raise ValueError('modules: "arm", "ifce" or both')
+
+    def _n_params(self, h: CCHeader) -> int:
+        return sum(writer.network_layout(h)[:4])
+
+    def _nn_deltas(self, h: CCHeader, values: np.ndarray) -> np.ndarray:
+        """rate_payload_byte_deltas, +inf in the rows of a module that is not refined: whatever the table holds there, pick_moves
+        never takes such a row."""
+        out = rate_payload_byte_deltas(h, values)
+        n_arm = sum(writer.network_layout(h)[:2])
+        if "arm" not in self.modules:
+            out[:n_arm] = np.inf
+        if "ifce" not in self.modules:
+            out[n_arm:] = np.inf
+        return out
+
+    def _table(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
+        """(total_bits, ParamDeltas over [n_arm + n_ifce] rows): one measure per module refined on one handle; the rows of the
+        other module hold +inf, 0, 0."""
+        from .encoder import EncodeBatch, ParamDeltas
+
+        n_arm, n = sum(writer.network_layout(h)[:2]), self._n_params(h)
+        bits = np.full((n, 2), np.inf, np.float64)
+        sum_width, moved = np.zeros((n, 2), np.int64), np.zeros((n, 2), np.int64)
+        with EncodeBatch(self.device) as enc:
+            slot = enc.add_device(h, nn, ptrs, owner=owner)
+            for module in self.modules:
+                if module == "arm":
+                    enc.measure_param_deltas(stream)
+                    enc.wait(stream)
+                    t, rows = enc.param_deltas(slot), slice(0, n_arm)
+                else:
+                    enc.measure_ifce_deltas(stream)
+                    enc.wait(stream)
+                    t, rows = enc.ifce_deltas(slot), slice(n_arm, n)
+                if t.first != 0 or t.bits.shape[0] != rows.stop - rows.start:
+                    raise ValueError("the table does not cover " + self._covers)
+                bits[rows], sum_width[rows], moved[rows] = t.bits, t.sum_width, t.moved
+            return enc.rate(slot).total_bits, ParamDeltas(0, bits, sum_width, moved)

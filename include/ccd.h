@@ -496,6 +496,18 @@ int ccd_enc_slot_delta_map(const ccd_enc* e, int slot, int grid, void** dev_ptr)
 int ccd_enc_measure_param_deltas(ccd_enc* e, void* stream, int first, int count, int mode);
 int ccd_enc_slot_param_count(const ccd_enc* e, int slot);
 int ccd_enc_slot_param_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved);
+/* ---- IFCE parameter deltas: the same table for the transmitted IFCE integers.  Parameter k,
+ * 0 <= k < ccd_enc_slot_ifce_count, counts groups 2 and 3 of ccd_network_layout in stream order: the weights [n_ifce_out][fin_g]
+ * of every grid with input_features_ifce[g] > 0 in grid order, then the biases [n_ifce_out] of those grids.  The fields, the
+ * +inf, 0, 0 of a move that leaves int32, the range, the modes, the refusals and the rule that the next measure of any kind
+ * invalidates the table are those of the three functions above; ccd_enc_measure_ifce_deltas is a ccd_enc_measure(e, stream, 0)
+ * followed by the table.  A weight of the coarsest grid reads an all-zero channel: its rows are exactly 0.0, 0, 0.  A slot
+ * without IFCE has ccd_enc_slot_ifce_count == 0 and an empty table (*count == 0), it refuses no mode.  A handle holds ONE table:
+ * after a measure_ifce_deltas ccd_enc_slot_param_deltas returns CCD_ERR_ARG, and ccd_enc_slot_ifce_deltas after a
+ * measure_param_deltas. */
+int ccd_enc_measure_ifce_deltas(ccd_enc* e, void* stream, int first, int count, int mode);
+int ccd_enc_slot_ifce_count(const ccd_enc* e, int slot);
+int ccd_enc_slot_ifce_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved);
 /* Size of a slot's payload buffer: every symbol has a width of at least 1 / 2^24, so n symbols give at most
  * 4 * (ceil(24 n / 32) + 2) bytes.  0 for n < 0. */
 size_t ccd_enc_payload_bound(int64_t n_symbols);

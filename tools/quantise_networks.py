@@ -2,12 +2,13 @@
 section 4.18): float parameters + the stream's latents + a source in, a `.cool` file out.
 
     python tools/quantise_networks.py in.cool source.png out.cool --lmbda 1e-3 [--params floats.npz] [--sweeps N]
-                                      [--fast-path-only] [--refine-arm N] [--descend STEPS]
+                                      [--fast-path-only] [--refine-arm N | --refine-rate N] [--descend STEPS]
 
 The architecture and the latents are the input stream's.  --params: an .npz whose array `values` holds the float32 parameters
 in stream order (writer.network_layout); without it the stream's own networks are dequantised and searched again.
 --refine-arm runs at most N steps of the +-1 descent over the ARM's integers on the searched network (nnrefine.ArmRefiner,
-DESIGN.md section 4.20: rate only, the planes stay).  --descend
+DESIGN.md section 4.20: rate only, the planes stay); --refine-rate the same descent over both rate networks, the ARM's and the
+IFCE's integers (nnrefine.RateRefiner, section 4.21).  --descend
 runs RdEvaluator.descend (8 rounds per step) on the result for at most STEPS steps.  Prints the chosen steps, payload bytes,
 bits, PSNR and cost beside the input stream's own, writes the stream and checks that it decodes to the planes that were scored."""
 import argparse
@@ -21,7 +22,7 @@ from cool_chic_amd import DecodeBatch, EncodeBatch, RdEvaluator, writer  # noqa:
 from cool_chic_amd.batch import FRAME_DATA_TYPES  # noqa: E402
 from cool_chic_amd.bitstream.header import CoolChicHeader, FrameHeader, VideoHeader  # noqa: E402
 from cool_chic_amd.nnquant import NetworkQuantiser  # noqa: E402
-from cool_chic_amd.nnrefine import ArmRefiner  # noqa: E402
+from cool_chic_amd.nnrefine import ArmRefiner, RateRefiner  # noqa: E402
 from cool_chic_amd.quality import _planes_to_frame_data, read_source  # noqa: E402
 
 
@@ -35,9 +36,13 @@ def main():
     ap.add_argument("--sweeps", type=int, default=1)
     ap.add_argument("--fast-path-only", action="store_true", help="only networks whose ARM fits the pipelined entropy kernel")
     ap.add_argument("--refine-arm", type=int, default=0, metavar="N", help="ArmRefiner.refine on the searched network, at most N steps")
-    ap.add_argument("--refine-batch", type=int, default=1, help="moves tried together per step of --refine-arm")
+    ap.add_argument("--refine-rate", type=int, default=0, metavar="N", help="RateRefiner.refine (ARM and IFCE) on the searched network, at most N steps")
+    ap.add_argument("--refine-batch", type=int, default=1, help="moves tried together per step of --refine-arm / --refine-rate")
     ap.add_argument("--descend", type=int, default=0, metavar="STEPS", help="RdEvaluator.descend on the result, at most STEPS steps")
     a = ap.parse_args()
+    if a.refine_arm > 0 and a.refine_rate > 0:
+        raise SystemExit("--refine-arm or --refine-rate, not both")
+    n_refine = max(a.refine_arm, a.refine_rate)
     with open(a.stream, "rb") as f:
         bs = f.read()
     vh, fh, ch = VideoHeader(), FrameHeader(), CoolChicHeader()
@@ -76,8 +81,9 @@ def main():
               + ("" if t.chosen is None else f", chose (2^{t.cells[t.chosen].q_w}, 2^{t.cells[t.chosen].q_b}) cost {t.cells[t.chosen].cost:.9g}"))
     rows = [("stream", own, len(nn), list(arch.nn_q_step_log2)), ("searched", res.candidate, len(res.bytes_nn), list(res.header.nn_q_step_log2))]
     searched = res.candidate
-    if a.refine_arm > 0:
-        fine = ArmRefiner(0).refine(res.header, res.values, ptrs, a.refine_arm, batch=a.refine_batch, owner=latents)
+    if n_refine > 0:
+        refiner = RateRefiner(0) if a.refine_rate > 0 else ArmRefiner(0)
+        fine = refiner.refine(res.header, res.values, ptrs, n_refine, batch=a.refine_batch, owner=latents)
         for k, step in enumerate(fine.log):
             print(f"refine {k}: {[(m.index, m.sign) for m in step.moves]}, objective {step.objective:.3f} (predicted {step.predicted:.3f}), "
                   f"{step.n_bytes_nn} bytes of networks, {len(step.rejected)} larger batches rejected")
@@ -87,7 +93,7 @@ def main():
     with RdEvaluator(0) as ev, EncodeBatch(0) as enc, DecodeBatch(0) as back:
         ev.add(res.header, res.bytes_nn, ptrs, source, owner=latents)
         after = ev.evaluate(a.lmbda)[0]
-        if a.refine_arm > 0:  # the ARM's integers move the rate alone
+        if n_refine > 0:  # the ARM's and the IFCE's integers move the rate alone
             assert after.mse == searched.mse and after.cost <= searched.cost
             rows.append(("refined", after, len(res.bytes_nn), list(res.header.nn_q_step_log2)))
         else:

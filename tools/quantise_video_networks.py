@@ -3,7 +3,7 @@ and 4.19).  The frames are walked in coding order: I frames go through NetworkQu
 InterNetworkQuantiser with the planes of the frames as they decode with the networks ALREADY CHOSEN as their references.  The
 float parameters are the stream's own integers dequantised; latents and every frame header stay as they are.
 
-    python tools/quantise_video_networks.py in.cool source.yuv out.cool --lmbda 1e-3 [--sweeps N] [--fast-path-only] [--refine-arm N]
+    python tools/quantise_video_networks.py in.cool source.yuv out.cool --lmbda 1e-3 [--sweeps N] [--fast-path-only] [--refine-arm N | --refine-rate N]
 
 --refine-arm runs at most N steps of the +-1 descent over the ARM's integers (nnrefine.ArmRefiner) on
 every cool-chic after its steps are chosen: the rate alone moves, so the planes the later frames predict from stay.
@@ -23,7 +23,7 @@ from cool_chic_amd.bitstream.decode import _split_frame, decode_video  # noqa: E
 from cool_chic_amd.bitstream.header import VideoHeader  # noqa: E402
 from cool_chic_amd.nnquant import NetworkQuantiser  # noqa: E402
 from cool_chic_amd.nnquant_inter import InterNetworkQuantiser  # noqa: E402
-from cool_chic_amd.nnrefine import ArmRefiner  # noqa: E402
+from cool_chic_amd.nnrefine import ArmRefiner, RateRefiner  # noqa: E402
 from cool_chic_amd.quality import read_source  # noqa: E402
 
 
@@ -36,7 +36,12 @@ def main():
     ap.add_argument("--sweeps", type=int, default=1)
     ap.add_argument("--fast-path-only", action="store_true", help="only networks whose ARM fits the pipelined entropy kernel")
     ap.add_argument("--refine-arm", type=int, default=0, metavar="N", help="ArmRefiner.refine on every searched cool-chic, at most N steps")
+    ap.add_argument("--refine-rate", type=int, default=0, metavar="N",
+                    help="RateRefiner.refine (the ARM's and the IFCE's integers, DESIGN.md section 4.21) on every searched cool-chic, at most N steps")
     a = ap.parse_args()
+    if a.refine_arm > 0 and a.refine_rate > 0:
+        raise SystemExit("--refine-arm or --refine-rate, not both")
+    n_refine = max(a.refine_arm, a.refine_rate)
     with open(a.stream, "rb") as f:
         bs = f.read()
     vh = VideoHeader()
@@ -69,10 +74,10 @@ def main():
         return writer.dequantise_network(arch, writer.network_values(arch, nn))
 
     def refine(what, net, p, owner):
-        """(header, bytes_nn) of a searched network after --refine-arm."""
-        if a.refine_arm <= 0:
+        """(header, bytes_nn) of a searched network after --refine-arm / --refine-rate."""
+        if n_refine <= 0:
             return net.header, net.bytes_nn
-        fine = ArmRefiner(0).refine(net.header, net.values, p, a.refine_arm, owner=owner)
+        fine = (RateRefiner(0) if a.refine_rate > 0 else ArmRefiner(0)).refine(net.header, net.values, p, n_refine, owner=owner)
         print(f"  {what}: {len(fine.log)} refinement steps ({fine.stopped}), objective {fine.start_objective:.3f} -> "
               f"{fine.log[-1].objective if fine.log else fine.start_objective:.3f} bits, {len(net.bytes_nn)} -> {len(fine.bytes_nn)} bytes")
         return fine.header, fine.bytes_nn
@@ -95,7 +100,7 @@ def main():
                 ev.add(row[0][0], row[0][1], ptrs[0], sources[k], owner=owner)
                 after = ev.evaluate(a.lmbda)[0]
                 done[k] = [p.clone() for p in ev.planes(0)]
-            if a.refine_arm > 0:
+            if n_refine > 0:
                 assert after.mse == res.candidate.mse and after.cost <= res.candidate.cost
             else:
                 assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)
@@ -117,7 +122,7 @@ def main():
                 ev.add(frame_type, (row[0][0], row[0][1], ptrs[0]), (row[1][0], row[1][1], ptrs[1]), refs, gf, taps, sources[k], owner=owner)
                 after = ev.evaluate(a.lmbda)[0]
                 done[k] = [p.clone() for p in ev.planes(0)]
-            if a.refine_arm > 0:  # the ARMs' integers move the rate alone
+            if n_refine > 0:  # the ARMs' and the IFCEs' integers move the rate alone
                 assert after.mse == res.candidate.mse and after.cost <= res.candidate.cost
             else:
                 assert (after.mse, after.bits, after.cost) == (res.candidate.mse, res.candidate.bits, res.candidate.cost)

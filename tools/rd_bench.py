@@ -48,6 +48,10 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     per candidate over the shared latents, measure, chunked by max_in_flight_bytes as NetworkQuantiser does -
                     and the ratio of the wall times; and one descent of 25 steps on kodim14 (ArmRefiner.refine)
 
+  --ifce-refine     the same three inputs and figures for the IFCE parameter table (EncodeBatch.measure_ifce_deltas, DESIGN.md
+                    section 4.21), and on kodim14 one RateRefiner descent of 25 steps (ARM + IFCE) beside ArmRefiner's 25 steps:
+                    bits, bytes and wall time of both
+
 Device times are event-timed on the stream the work runs on, after 3 warm-up runs, median of --runs.  Prints one JSON line.
 The ingest kernel's own time comes from a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/rd_bench.py --runs 3 --no-replaced"""
@@ -780,15 +784,16 @@ def measure_networks(hdr, nn, payload, bitdepth, fdt, runs, lmbdas, descend_step
     return res
 
 
-def measure_arm_table(ccs, runs, warmup, descent_steps):
-    """The ARM parameter table of the cool-chics `ccs` [(header bytes, NN payload, latent payload)] in one handle."""
+def measure_arm_table(ccs, runs, warmup, descent_steps, ifce=False):
+    """The ARM parameter table (ifce: the IFCE parameter table) of the cool-chics `ccs` [(header bytes, NN payload, latent payload)] in one
+    handle."""
     import time
 
     import numpy as np
 
     from cool_chic_amd._lib import CCHeader
     from cool_chic_amd.nnquant import NetworkQuantiser
-    from cool_chic_amd.nnrefine import ArmRefiner
+    from cool_chic_amd.nnrefine import ArmRefiner, RateRefiner
 
     st = torch.cuda.current_stream().cuda_stream
     dec = DecodeBatch(0)
@@ -799,14 +804,15 @@ def measure_arm_table(ccs, runs, warmup, descent_steps):
     archs = [dec.header(s) for s in range(n)]
     nns = [dec.network_bytes(s) for s in range(n)]
     ptrs = [dec.latent_ptrs(s) for s in range(n)]
-    n_arm = [sum(writer.network_layout(a)[:2]) for a in archs]
+    first = [sum(writer.network_layout(a)[:2]) if ifce else 0 for a in archs]          # the table's row 0 in writer.network_values
+    n_arm = [sum(writer.network_layout(a)[2:4] if ifce else writer.network_layout(a)[:2]) for a in archs]  # rows of the table
     res = {"streams": n, "symbols": int(sum(a.n_symbols for a in archs)), "candidates": 2 * sum(n_arm), "runs": runs, "warmup": warmup}
     enc = EncodeBatch(0)
     for s in range(n):
         enc.add_device(archs[s], nns[s], ptrs[s], owner=dec)
     for mode in (0, 1):  # automatic (the incremental path where the state fits the LDS) and generic
         def table():
-            enc.measure_param_deltas(st, mode=mode)
+            (enc.measure_ifce_deltas if ifce else enc.measure_param_deltas)(st, mode=mode)
             enc.wait(st)
         for _ in range(warmup):
             table()
@@ -823,7 +829,7 @@ def measure_arm_table(ccs, runs, warmup, descent_steps):
             ev_ms.append(e0.elapsed_time(e1))
         res[f"table_mode{mode}"] = {"event_ms": {"median": round(statistics.median(ev_ms), 2), "min": round(min(ev_ms), 2), "max": round(max(ev_ms), 2)},
                                     "wall_s": round(statistics.median(wall), 4)}
-    tables = [enc.param_deltas(s) for s in range(n)]
+    tables = [(enc.ifce_deltas if ifce else enc.param_deltas)(s) for s in range(n)]
     base = [enc.rate(s).total_bits for s in range(n)]
     enc.close()
     # the yardstick: every candidate a slot of its own over the shared latents; the candidates are built OUTSIDE the timer
@@ -835,7 +841,7 @@ def measure_arm_table(ccs, runs, warmup, descent_steps):
         for k in range(n_arm[s]):
             for sign in (-1, 1):
                 v = values.copy()
-                v[k] += sign
+                v[first[s] + k] += sign
                 h = CCHeader.from_buffer_copy(bytes(archs[s]))
                 cands.append((h, writer.encode_network(h, v)))
         chunk = nq.chunk_size(archs[s], 0)
@@ -851,18 +857,23 @@ def measure_arm_table(ccs, runs, warmup, descent_steps):
                 bits += [one.rate(i).total_bits for i in range(len(cands[at:at + chunk]))]
         yard += time.perf_counter() - t0
         got = np.asarray(bits).reshape(-1, 2) - base[s]  # two rounded totals apart: a plausibility check, not the accuracy test
-        worst = max(worst, float(np.abs(got - tables[s].bits).max()))
+        worst = max(worst, float(np.abs(got - tables[s].bits).max(initial=0.0)))
         res.setdefault("yardstick_per_launch", chunk)
     res["yardstick_wall_s"] = round(yard, 4)
     res["ratio_yardstick_over_table_mode0"] = round(yard / res["table_mode0"]["wall_s"], 2)
+    res["ratio_table_mode1_over_mode0"] = round(res["table_mode1"]["wall_s"] / res["table_mode0"]["wall_s"], 2)
     res["largest_difference_from_the_yardstick_bits"] = worst
     if descent_steps > 0:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fine = ArmRefiner(0).refine(archs[0], writer.network_values(archs[0], nns[0]), ptrs[0], descent_steps, owner=dec)
-        res["descent"] = {"steps": len(fine.log), "stopped": fine.stopped, "wall_s": round(time.perf_counter() - t0, 3),
-                          "objective_before": fine.start_objective, "objective_after": fine.log[-1].objective if fine.log else fine.start_objective,
-                          "bytes_nn_before": len(nns[0]), "bytes_nn_after": len(fine.bytes_nn)}
+        for key, refiner in (("descent", ArmRefiner(0)),) + ((("descent_arm_ifce", RateRefiner(0)),) if ifce else ()):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fine = refiner.refine(archs[0], writer.network_values(archs[0], nns[0]), ptrs[0], descent_steps, owner=dec)
+            n_first = sum(writer.network_layout(archs[0])[:2])
+            res[key] = {"steps": len(fine.log), "stopped": fine.stopped, "wall_s": round(time.perf_counter() - t0, 3),
+                        "objective_before": fine.start_objective, "objective_after": fine.log[-1].objective if fine.log else fine.start_objective,
+                        "total_bits_after": fine.log[-1].total_bits if fine.log else None,
+                        "bytes_nn_before": len(nns[0]), "bytes_nn_after": len(fine.bytes_nn),
+                        "ifce_moves": sum(m.index >= n_first for step in fine.log for m in step.moves)}
     dec.close()
     return res
 
@@ -1012,22 +1023,23 @@ def main():
     ap.add_argument("--networks", action="store_true", help="time the search over the networks' quantisation steps instead")
     ap.add_argument("--network-sets", default="kodak,1080p", help="with --networks: which of the two frames to measure")
     ap.add_argument("--arm-refine", action="store_true", help="time the ARM parameter table and one descent instead")
-    ap.add_argument("--refine-sets", default="kodim14,kodak24,1080p", help="with --arm-refine: which of the three inputs to measure")
+    ap.add_argument("--ifce-refine", action="store_true", help="time the IFCE parameter table and the ARM + IFCE descent instead")
+    ap.add_argument("--refine-sets", default="kodim14,kodak24,1080p", help="with --arm-refine / --ifce-refine: which of the three inputs to measure")
     a = ap.parse_args()
-    if a.arm_refine:
+    if a.arm_refine or a.ifce_refine:
         from cool_chic_amd.bitstream.decode import _split_frame
         from cool_chic_amd.bitstream.header import VideoHeader
 
-        line = {"tool": "rd_bench --arm-refine"}
+        line = {"tool": "rd_bench --ifce-refine" if a.ifce_refine else "rd_bench --arm-refine"}
         k24 = synth.workload("kodak24")["streams"]
         if "kodim14" in a.refine_sets.split(","):
-            line["kodim14"] = measure_arm_table([synth.split_image_stream(k24[0])], a.runs, 3, 25)
+            line["kodim14"] = measure_arm_table([synth.split_image_stream(k24[0])], a.runs, 3, 25, ifce=a.ifce_refine)
         if "kodak24" in a.refine_sets.split(","):
-            line["kodak24"] = measure_arm_table([synth.split_image_stream(bs) for bs in k24], a.runs, 3, 0)
+            line["kodak24"] = measure_arm_table([synth.split_image_stream(bs) for bs in k24], a.runs, 3, 0, ifce=a.ifce_refine)
         if "1080p" in a.refine_sets.split(","):
             fh, ccs, _ = _split_frame(VideoHeader().read_header(synth.gop1080p(2)[0]))
             assert fh.get_value("frame_type") == "I"
-            line["gop1080p_I"] = measure_arm_table([(ccs[0][0].raw, ccs[0][1], ccs[0][2])], a.runs, 3, 0)
+            line["gop1080p_I"] = measure_arm_table([(ccs[0][0].raw, ccs[0][1], ccs[0][2])], a.runs, 3, 0, ifce=a.ifce_refine)
         print(json.dumps(line))
         return
     if a.networks and a.inter:
