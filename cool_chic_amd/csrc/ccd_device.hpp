@@ -5,9 +5,8 @@
 #include <cstdint>
 
 #include "../../include/ccd.h"
-#include "ccd_armdelta_plan.hpp"
-#include "ccd_ifcedelta_plan.hpp"
 #include "ccd_lattice.hpp"
+#include "ccd_ratedelta_plan.hpp"
 
 namespace ccd {
 
@@ -109,31 +108,25 @@ struct DeltaParams {
     float* map[CCD_MAX_GRIDS];            // per grid [2][h][w]: plane 0 the change for v - 1, plane 1 for v + 1
 };
 
-// ARM parameter deltas (encode_param_delta_kernel / encode_param_delta_final_kernel): what a slot of a
-// measure_param_deltas writes.  Candidate c = 2 (k - first) + (sign > 0).  A wave walks chunk j of the slot's workgroups -
+// Rate-network parameter deltas (encode_rate_delta_kernel / encode_rate_delta_final_kernel): what a slot of a
+// measure_param_deltas (the ARM's integers) or a measure_ifce_deltas (the IFCE's, 4.21) writes.  Row
+// r = 2 (k - first) + (sign > 0) of the slot's table.  A wave walks chunk j of the slot's workgroups -
 // [j kArmDeltaChunkBlocks, (j + 1) kArmDeltaChunkBlocks) of the rate kernel's numbering - for a tile of kArmDeltaTile candidates and
 // leaves one cell per candidate; the final kernel adds a candidate's cells in chunk order.
+// ARM: candidate c is row c, row == nullptr.  IFCE: the candidates are sorted by their grid (stably: a grid's weights, then its
+// biases, each in stream order), so that a tile walks the blocks of as few grids as the count allows; row[c] is the row sorted
+// candidate c answers.
 struct ParamDeltaCell { double bits; int64_t sum_width, moved; };
-struct ParamDeltaParams {
-    const ArmDeltaMove* cand;   // [n_cand]
-    ParamDeltaCell* partial;    // [n_chunks][n_cand]
-    ParamDeltaCell* out;        // [n_cand]: +inf, 0, 0 for a candidate that is not legal
-    uint32_t n_cand, n_chunks;
-    int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental: which instantiation prices the slot
-};
-
-// IFCE parameter deltas (encode_ifce_delta_kernel / encode_ifce_delta_final_kernel): what a slot of a
-// measure_ifce_deltas writes.  The chunks and the cells are the ARM table's.  The candidates are sorted by their grid (stably:
-// a grid's weights, then its biases, each in stream order), so that a tile of kArmDeltaTile candidates walks the blocks of as
-// few grids as the count allows; row[j] is the row of the table (2 (k - first) + (sign > 0)) sorted candidate j answers.
-struct IfceDeltaParams {
-    const IfceDeltaMove* cand;  // [n_cand], sorted by grid
-    const uint32_t* row;        // [n_cand]
+struct RateDeltaParams {
+    const RateDeltaMove* cand;  // [n_cand]
+    const uint32_t* row;        // [n_cand], or nullptr: candidate c answers row c
     ParamDeltaCell* partial;    // [n_chunks][n_cand], indexed like cand
     ParamDeltaCell* out;        // [n_cand], indexed by row: +inf, 0, 0 for a candidate that is not legal
     uint32_t n_cand, n_chunks;
-    int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental
+    int32_t path, pad;          // kArmDeltaGeneric / kArmDeltaIncremental: which instantiation prices the slot
 };
+// whose integers a table prices (the kernel's kKind) and whose entry a RateDeltaMove moves (encode_pixel_model's kMove: or none's)
+enum { kRateDeltaNone = -1, kRateDeltaArm = 0, kRateDeltaIfce = 1 };
 
 // One copy of the ingest launch (ccd_ingest.hip): latent grid `src` of a slot whose latents were GIVEN as device pointers
 // (ccd_batch_add_latents) goes to `dst`, where the entropy kernel would have left it.  The segments of one slot are adjacent.

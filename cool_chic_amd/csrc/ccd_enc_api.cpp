@@ -39,7 +39,6 @@ struct EncSlot {
     std::vector<int64_t> ifce_ints;  // the IFCE's transmitted integers, stream order (empty: no grid has IFCE)
 };
 enum { kIdle = 0, kRun = 1, kMeasure = 2 };  // what ccd_enc::in_flight holds
-enum { kTableArm = 0, kTableIfce = 1 };      // whose integers a parameter table prices
 }  // namespace
 
 struct ccd_enc {
@@ -66,11 +65,11 @@ struct ccd_enc {
     bool delta_pending = false;    // the measure in flight is a measure_deltas
     bool delta_valid = false;      // the last finished measure was one
     // ARM parameter deltas (ccd_enc_measure_param_deltas): a measure whose two extra launches write here
-    Mirror param_table, param_out; // ParamDeltaParams[n] and every slot's candidates; one ParamDeltaCell per candidate
+    Mirror param_table, param_out; // RateDeltaParams[n], every slot's candidates and the IFCE table's rows; one ParamDeltaCell per candidate
     Block param_slab;              // the chunks' cells
     bool param_pending = false;    // the measure in flight is a measure_param_deltas
     bool param_valid = false;      // the last finished measure was one
-    int param_pending_kind = kTableArm, param_kind = kTableArm;  // kTableArm / kTableIfce: of the table in flight / of the valid one
+    int param_pending_kind = kRateDeltaArm, param_kind = kRateDeltaArm;  // kRateDeltaArm / kRateDeltaIfce: of the table in flight / of the valid one
     StreamSet streams;             // every stream a run was enqueued on
 };
 
@@ -457,11 +456,12 @@ int ccd_enc_measure_deltas(ccd_enc* e, void* stream) {
 }
 
 namespace {
-// ccd_enc_measure_param_deltas (kind == kTableArm) and ccd_enc_measure_ifce_deltas (kTableIfce): the range, the refusals, the
-// cells and the meter's launches in front are the same; the candidates, the path's LDS and the kernels are the kind's.
+// ccd_enc_measure_param_deltas (kind == kRateDeltaArm) and ccd_enc_measure_ifce_deltas (kRateDeltaIfce): the range, the refusals, the
+// cells, the candidates and the meter's launches in front are the same; the integers, their places, the incremental path's LDS,
+// the order of the candidates (the IFCE's are sorted by grid) and the kernel's instantiation are the kind's.
 int measure_table(ccd_enc* e, void* stream, int first, int count, int mode, int kind) {
     if (!e || first < 0 || mode < kArmDeltaAuto || mode > kArmDeltaIncremental) return CCD_ERR_ARG;
-    const bool ifce = kind == kTableIfce;
+    const bool ifce = kind == kRateDeltaIfce;
     const size_t n = e->slots.size();
     if (n == 0) return CCD_OK;
     // ---- everything the host can refuse, before the device is touched: the path of every slot, the launch's dimensions ----
@@ -473,17 +473,17 @@ int measure_table(ccd_enc* e, void* stream, int first, int count, int mode, int 
     size_t lds_generic = 0, lds_incremental = 0;  // 0: no slot takes that path
     for (size_t i = 0; i < n; ++i) {
         const EncSlot& s = *e->slots[i];
-        const int64_t n_arm = static_cast<int64_t>(ifce ? s.ifce_ints.size() : s.arm_ints.size());  // the integers of the kind
+        const int64_t n_arm = static_cast<int64_t>((ifce ? s.ifce_ints : s.arm_ints).size());  // the integers of the kind
         if (ifce && n_arm == 0) {  // nothing to price by either path: the slot refuses no mode and asks for no LDS
             range[i] = {0, 0};
             path[i] = kArmDeltaGeneric;
             continue;
         }
-        const int rc = ifce ? ifcedelta_path(s.ifce_shape, mode) : armdelta_path(s.arm_shape, mode);
+        const int64_t lds_inc = ifce ? ifcedelta_incremental_lds(s.ifce_shape) : armdelta_incremental_lds(s.arm_shape);
+        const int rc = ratedelta_path(lds_inc, mode);
         if (rc < 0) return rc;
         path[i] = rc;
-        const size_t lds_inc = static_cast<size_t>(ifce ? ifcedelta_incremental_lds(s.ifce_shape) : armdelta_incremental_lds(s.arm_shape));
-        if (rc == kArmDeltaIncremental) lds_incremental = std::max(lds_incremental, lds_inc);
+        if (rc == kArmDeltaIncremental) lds_incremental = std::max(lds_incremental, static_cast<size_t>(lds_inc));
         else lds_generic = std::max(lds_generic, encode_contexts_lds_bytes(s.ep.ep.dim));
         const int64_t lo = std::min<int64_t>(first, n_arm), hi = count < 0 ? n_arm : std::min<int64_t>(static_cast<int64_t>(first) + count, n_arm);
         range[i] = {static_cast<int>(lo), static_cast<int>(hi - lo)};
@@ -502,67 +502,51 @@ int measure_table(ccd_enc* e, void* stream, int first, int count, int mode, int 
         harvest(e);
     }
     e->param_valid = false;  // the table of the last call is about to be overwritten: a failure from here on leaves no table
-    static_assert(sizeof(ArmDeltaMove) == sizeof(IfceDeltaMove), "one candidate array serves both tables");
-    const size_t cand_at = align256(n * (ifce ? sizeof(IfceDeltaParams) : sizeof(ParamDeltaParams)));
-    const size_t row_at = cand_at + align256(std::max<size_t>(n_cand, 1) * sizeof(ArmDeltaMove));  // the IFCE table's rows
-    const size_t table_bytes = ifce ? row_at + std::max<size_t>(n_cand, 1) * sizeof(uint32_t) : cand_at + std::max<size_t>(n_cand, 1) * sizeof(ArmDeltaMove);
-    const size_t out_bytes = std::max<size_t>(n_cand, 1) * sizeof(ParamDeltaCell);
+    const size_t n_cand1 = std::max<size_t>(n_cand, 1);
+    const size_t cand_at = align256(n * sizeof(RateDeltaParams));
+    const size_t row_at = cand_at + align256(n_cand1 * sizeof(RateDeltaMove));  // the IFCE table's rows
+    const size_t table_bytes = row_at + (ifce ? n_cand1 * sizeof(uint32_t) : 0);
+    const size_t out_bytes = n_cand1 * sizeof(ParamDeltaCell);
     if (!e->param_table.ensure(e->device, table_bytes) || !e->param_out.ensure(e->device, out_bytes) ||
         !e->param_slab.ensure(e->device, BlockPool::kDevice, std::max<size_t>(n_cells * sizeof(ParamDeltaCell), 256)))
         return CCD_ERR_NOMEM;
-    if (ifce) {
-        IfceDeltaParams* tab = e->param_table.host.as<IfceDeltaParams>();
-        IfceDeltaMove* cands = reinterpret_cast<IfceDeltaMove*>(e->param_table.host.as<char>() + cand_at);
-        uint32_t* rows = reinterpret_cast<uint32_t*>(e->param_table.host.as<char>() + row_at);
-        const IfceDeltaMove* d_cands = reinterpret_cast<const IfceDeltaMove*>(e->param_table.dev.as<char>() + cand_at);
-        const uint32_t* d_rows = reinterpret_cast<const uint32_t*>(e->param_table.dev.as<char>() + row_at);
-        size_t at = 0, cell = 0;
-        std::vector<IfceDeltaMove> moves;
-        for (size_t i = 0; i < n; ++i) {
-            const EncSlot& s = *e->slots[i];
-            const int p_first = range[i].first;
-            const uint32_t cand = 2 * static_cast<uint32_t>(range[i].second);
-            const uint32_t chunks = (s.ep.n_blocks + kArmDeltaChunkBlocks - 1) / kArmDeltaChunkBlocks;
-            moves.resize(cand);
-            for (uint32_t c = 0; c < cand; ++c) {
-                const int64_t k = p_first + (c >> 1);
-                int64_t index = 0;
-                const int rc = ifcedelta_move(s.ifce_shape, k, (c & 1) ? 1 : -1, s.ifce_ints[static_cast<size_t>(k)], &moves[c], &index);
-                if (rc < 0) return rc;  // (cannot happen: decode_network took these shifts)
-            }
-            // sorted by grid, rows in order inside a grid: a counting sort over the grids
+    RateDeltaParams* tab = e->param_table.host.as<RateDeltaParams>();
+    RateDeltaMove* cands = reinterpret_cast<RateDeltaMove*>(e->param_table.host.as<char>() + cand_at);
+    uint32_t* rows = reinterpret_cast<uint32_t*>(e->param_table.host.as<char>() + row_at);
+    const RateDeltaMove* d_cands = reinterpret_cast<const RateDeltaMove*>(e->param_table.dev.as<char>() + cand_at);
+    const uint32_t* d_rows = reinterpret_cast<const uint32_t*>(e->param_table.dev.as<char>() + row_at);
+    size_t at = 0, cell = 0;
+    std::vector<RateDeltaMove> unsorted;
+    for (size_t i = 0; i < n; ++i) {
+        const EncSlot& s = *e->slots[i];
+        const std::vector<int64_t>& ints = ifce ? s.ifce_ints : s.arm_ints;
+        const int p_first = range[i].first;
+        const uint32_t cand = 2 * static_cast<uint32_t>(range[i].second);
+        const uint32_t chunks = (s.ep.n_blocks + kArmDeltaChunkBlocks - 1) / kArmDeltaChunkBlocks;
+        unsorted.resize(ifce ? cand : 0);
+        RateDeltaMove* moves = ifce ? unsorted.data() : cands + at;  // the ARM's candidate c is row c: made in place
+        for (uint32_t c = 0; c < cand; ++c) {
+            const int64_t k = p_first + (c >> 1);
+            int64_t index = 0;
+            int shift = 0;
+            int rc = ifce ? ifcedelta_place(s.ifce_shape, k, &moves[c], &index, &shift) : armdelta_place(s.arm_shape, k, &moves[c], &index, &shift);
+            if (rc == CCD_OK) rc = ratedelta_move((c & 1) ? 1 : -1, ints[static_cast<size_t>(k)], shift, &moves[c]);
+            if (rc < 0) return rc;  // (cannot happen: decode_network took these shifts)
+        }
+        if (ifce) {  // sorted by grid, rows in order inside a grid: a counting sort over the grids
             uint32_t next[CCD_MAX_GRIDS + 1] = {0};
-            for (uint32_t c = 0; c < cand; ++c) ++next[moves[c].grid + 1];
+            for (uint32_t c = 0; c < cand; ++c) ++next[moves[c].at + 1];
             for (int g = 0; g < CCD_MAX_GRIDS; ++g) next[g + 1] += next[g];
             for (uint32_t c = 0; c < cand; ++c) {
-                const uint32_t j = next[moves[c].grid]++;
+                const uint32_t j = next[moves[c].at]++;
                 cands[at + j] = moves[c];
                 rows[at + j] = c;
             }
-            tab[i] = IfceDeltaParams{d_cands + at, d_rows + at, e->param_slab.as<ParamDeltaCell>() + cell, e->param_out.dev.as<ParamDeltaCell>() + at, cand, chunks, path[i], 0};
-            at += cand;
-            cell += static_cast<size_t>(cand) * chunks;
         }
-    } else {
-        ParamDeltaParams* tab = e->param_table.host.as<ParamDeltaParams>();
-        ArmDeltaMove* cands = reinterpret_cast<ArmDeltaMove*>(e->param_table.host.as<char>() + cand_at);
-        const ArmDeltaMove* d_cands = reinterpret_cast<const ArmDeltaMove*>(e->param_table.dev.as<char>() + cand_at);
-        size_t at = 0, cell = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const EncSlot& s = *e->slots[i];
-            const int p_first = range[i].first;
-            const uint32_t cand = 2 * static_cast<uint32_t>(range[i].second);
-            const uint32_t chunks = (s.ep.n_blocks + kArmDeltaChunkBlocks - 1) / kArmDeltaChunkBlocks;
-            for (uint32_t c = 0; c < cand; ++c) {
-                const int64_t k = p_first + (c >> 1);
-                int64_t index = 0;
-                const int rc = armdelta_move(s.arm_shape, k, (c & 1) ? 1 : -1, s.arm_ints[static_cast<size_t>(k)], &cands[at + c], &index);
-                if (rc < 0) return rc;  // (cannot happen: decode_network took these shifts)
-            }
-            tab[i] = ParamDeltaParams{d_cands + at, e->param_slab.as<ParamDeltaCell>() + cell, e->param_out.dev.as<ParamDeltaCell>() + at, cand, chunks, path[i], 0};
-            at += cand;
-            cell += static_cast<size_t>(cand) * chunks;
-        }
+        tab[i] = RateDeltaParams{d_cands + at, ifce ? d_rows + at : nullptr, e->param_slab.as<ParamDeltaCell>() + cell,
+                                 e->param_out.dev.as<ParamDeltaCell>() + at, cand, chunks, path[i], 0};
+        at += cand;
+        cell += static_cast<size_t>(cand) * chunks;
     }
     unsigned max_blocks = 0;
     size_t lds = 0;
@@ -580,12 +564,8 @@ int measure_table(ccd_enc* e, void* stream, int first, int count, int mode, int 
         }
     }
     HIP_TRY(e->param_table.upload(table_bytes, st));
-    if (ifce)
-        HIP_TRY(launch_encode_ifce_deltas(e->table.dev.as<EncodeParams>(), e->param_table.dev.as<IfceDeltaParams>(), static_cast<int>(n), max_chunks,
-                                          max_cand, lds_generic, lds_incremental, st));
-    else
-        HIP_TRY(launch_encode_param_deltas(e->table.dev.as<EncodeParams>(), e->param_table.dev.as<ParamDeltaParams>(), static_cast<int>(n), max_chunks,
-                                           max_cand, lds_generic, lds_incremental, st));
+    HIP_TRY(launch_encode_rate_deltas(kind, e->table.dev.as<EncodeParams>(), e->param_table.dev.as<RateDeltaParams>(), static_cast<int>(n), max_chunks,
+                                      max_cand, lds_generic, lds_incremental, st));
     HIP_TRY(e->param_out.download(out_bytes, st));
     e->param_pending = true;
     e->param_pending_kind = kind;
@@ -611,8 +591,8 @@ int slot_table(const ccd_enc* e, int slot, int kind, int* first, int* count, dou
 }
 }  // namespace
 
-int ccd_enc_measure_param_deltas(ccd_enc* e, void* stream, int first, int count, int mode) { return measure_table(e, stream, first, count, mode, kTableArm); }
-int ccd_enc_measure_ifce_deltas(ccd_enc* e, void* stream, int first, int count, int mode) { return measure_table(e, stream, first, count, mode, kTableIfce); }
+int ccd_enc_measure_param_deltas(ccd_enc* e, void* stream, int first, int count, int mode) { return measure_table(e, stream, first, count, mode, kRateDeltaArm); }
+int ccd_enc_measure_ifce_deltas(ccd_enc* e, void* stream, int first, int count, int mode) { return measure_table(e, stream, first, count, mode, kRateDeltaIfce); }
 
 int ccd_enc_slot_param_count(const ccd_enc* e, int slot) {
     if (!e || slot < 0 || slot >= static_cast<int>(e->slots.size())) return CCD_ERR_ARG;
@@ -624,10 +604,10 @@ int ccd_enc_slot_ifce_count(const ccd_enc* e, int slot) {
 }
 
 int ccd_enc_slot_param_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved) {
-    return slot_table(e, slot, kTableArm, first, count, bits, sum_width, moved);
+    return slot_table(e, slot, kRateDeltaArm, first, count, bits, sum_width, moved);
 }
 int ccd_enc_slot_ifce_deltas(const ccd_enc* e, int slot, int* first, int* count, double* bits, int64_t* sum_width, int64_t* moved) {
-    return slot_table(e, slot, kTableIfce, first, count, bits, sum_width, moved);
+    return slot_table(e, slot, kRateDeltaIfce, first, count, bits, sum_width, moved);
 }
 
 int ccd_enc_wait(ccd_enc* e, void* stream) {

@@ -36,12 +36,13 @@ constexpr int kEncThreads = 64;  // one wave per workgroup: a lane only ever rea
 // kOverride: the one latent `ov` names is taken as ov.val wherever the pixel reads it (a spatial tap when ov.grid == g, an
 // IFCE source when ov.grid > g), memory stays as it is - the delta kernels' "what if".  Without it `ov` is not looked at and
 // the function is what it was before it had the parameter.
-// kParam: one entry of the fixed-point ARM is taken as entry + pm.inc (the parameter table's "what if").  The
-// sums are wrapping 64-bit, a ring, so the unit's accumulator with that entry is the accumulator as it is plus pm.inc times the
-// unit's input pm.in (times one for a bias), bit for bit; pm is wave-uniform and the weights stay scalar loads.
+// kMove: whose entry `mv` moves - the parameter tables' "what if"; kRateDeltaNone: `mv` is not looked at.
+//   kRateDeltaArm: one entry of the fixed-point ARM is taken as entry + mv.inc.  The sums are wrapping 64-bit, a
+//   ring, so the unit's accumulator with that entry is the accumulator as it is plus mv.inc times the unit's input mv.in (times
+//   one for a bias), bit for bit; mv is wave-uniform and the weights stay scalar loads.
+//   kRateDeltaIfce: one entry of the fixed-point IFCE of grid mv.at is taken as entry + mv.inc (ifce_feature).
 // kInputsOnly: the ARM's inputs (contexts and IFCE features) are left in the first dim columns and nothing else is done - the
-// incremental path of the parameter table keeps them there.
-// kIfce: one entry of the fixed-point IFCE of grid im.grid is taken as entry + im.inc (ifce_feature).
+// incremental path of the parameter tables keeps them there.
 struct LatentOverride { int grid, y, x, val; };
 // table indices (latent.py:156-165, rangecoder.py:90-91) of the ARM's two sums, as the Laplace parameters
 __device__ __forceinline__ void arm_sums_to_model(const EntropyParams& P, uint64_t st0, uint64_t st1, double& mu, double& rcp) {
@@ -56,12 +57,12 @@ __device__ __forceinline__ void arm_sums_to_model(const EntropyParams& P, uint64
 // the .to(torch.float) / back to int64 round trip around F.interpolate (coolchic.py:142-144).  fw_ / fb_: the grid's w[fin][n_if]
 // and b[n_if]; first: the stack is a single all-zero channel (coolchic.py:95-96).  kCand: the entry im names is taken as
 // entry + im.inc (the IFCE table's "what if"): the accumulator is a ring, so it is the accumulator as it is plus
-// im.inc times the source (times one for a bias); the caller has checked im.grid == g and im.out == o.  The base and the
+// im.inc times the source (times one for a bias); the caller has checked im.at == g and im.out == o.  The base and the
 // candidate of either path of the table go through this one function.
 template <bool kOverride, bool kCand>
 __device__ __forceinline__ int64_t ifce_feature(const EntropyParams& P, int g, int fy, int fx, int o, int n_if, int fin, bool first,
                                                 int base_level, const int64_t* fw_, const int64_t* fb_, const LatentOverride& ov,
-                                                const IfceDeltaMove& im) {
+                                                const RateDeltaMove& im) {
     uint64_t acc = static_cast<uint64_t>(fb_[o]);
     if (kCand && im.in < 0) acc += static_cast<uint64_t>(im.inc);
     if (!first) {
@@ -77,10 +78,9 @@ __device__ __forceinline__ int64_t ifce_feature(const EntropyParams& P, int g, i
     const int64_t q8 = static_cast<int64_t>(acc) >> 24;
     return static_cast<int32_t>(static_cast<int64_t>(static_cast<float>(q8)));
 }
-template <bool kOverride, bool kParam = false, bool kInputsOnly = false, bool kIfce = false>
+template <bool kOverride, int kMove = kRateDeltaNone, bool kInputsOnly = false>
 __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g, int y, int x, int lane, unsigned char* smem_raw,
-                                                   const LatentOverride& ov, double& mu, double& rcp, const ArmDeltaMove& pm = ArmDeltaMove{},
-                                                   const IfceDeltaMove& im = IfceDeltaMove{}) {
+                                                   const LatentOverride& ov, double& mu, double& rcp, const RateDeltaMove& mv = RateDeltaMove{}) {
     const int dim = P.dim, n_sp = P.n_spatial, n_if = P.has_ifce ? P.n_ifce_out : 0;
     int64_t* xa = reinterpret_cast<int64_t*>(smem_raw) + lane;  // [dim][64], this lane's column
     int64_t* xb = xa + dim * kEncThreads;                       // [dim][64]
@@ -106,8 +106,8 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
         const int base_level = first ? 0 : P.level[g + 1];
         for (int o = 0; o < n_if; ++o) {
             int64_t f;
-            if (kIfce && im.grid == g && im.out == o) f = ifce_feature<kOverride, true>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, im);
-            else f = ifce_feature<kOverride, false>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, im);
+            if (kMove == kRateDeltaIfce && mv.at == g && mv.out == o) f = ifce_feature<kOverride, true>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, mv);
+            else f = ifce_feature<kOverride, false>(P, g, fy, fx, o, n_if, fin, first, base_level, fw_, fb_, ov, mv);
             xa[(n_sp + o) * kEncThreads] = static_cast<int64_t>(static_cast<uint64_t>(f) << 16);
         }
     } else {
@@ -124,9 +124,9 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
         st0 += v * static_cast<uint64_t>(ws[k * 2]);
         st1 += v * static_cast<uint64_t>(ws[k * 2 + 1]);
     }
-    if (kParam && pm.layer == P.n_layers) {
-        const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xa[pm.in * kEncThreads]));
-        if (pm.out == 0) st0 += c; else st1 += c;
+    if (kMove == kRateDeltaArm && mv.at == P.n_layers) {
+        const uint64_t c = static_cast<uint64_t>(mv.inc) * (mv.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xa[mv.in * kEncThreads]));
+        if (mv.out == 0) st0 += c; else st1 += c;
     }
     int64_t* xin = xa;
     int64_t* xout = xb;
@@ -142,10 +142,10 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
                 a0 += v * static_cast<uint64_t>(lw[k * dim + o]);
                 a1 += v * static_cast<uint64_t>(lw[k * dim + o1]);
             }
-            if (kParam && pm.layer == l && (pm.out == o || pm.out == o1)) {
-                const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[pm.in * kEncThreads]));
-                if (pm.out == o) a0 += c;
-                if (pm.out == o1) a1 += c;
+            if (kMove == kRateDeltaArm && mv.at == l && (mv.out == o || mv.out == o1)) {
+                const uint64_t c = static_cast<uint64_t>(mv.inc) * (mv.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[mv.in * kEncThreads]));
+                if (mv.out == o) a0 += c;
+                if (mv.out == o1) a1 += c;
             }
             const int64_t v0 = static_cast<int64_t>(a0), v1 = static_cast<int64_t>(a1);
             xout[o * kEncThreads] = (v0 < 0 ? 0 : v0) >> 16;
@@ -162,9 +162,9 @@ __device__ __forceinline__ void encode_pixel_model(const EntropyParams& P, int g
             a0 += v * static_cast<uint64_t>(lw[k * 2]);
             a1 += v * static_cast<uint64_t>(lw[k * 2 + 1]);
         }
-        if (kParam && pm.layer == P.n_layers - 1) {
-            const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[pm.in * kEncThreads]));
-            if (pm.out == 0) a0 += c; else a1 += c;
+        if (kMove == kRateDeltaArm && mv.at == P.n_layers - 1) {
+            const uint64_t c = static_cast<uint64_t>(mv.inc) * (mv.in < 0 ? uint64_t{1} : static_cast<uint64_t>(xin[mv.in * kEncThreads]));
+            if (mv.out == 0) a0 += c; else a1 += c;
         }
         st0 += a0; st1 += a1;
     }
@@ -508,17 +508,24 @@ __global__ __launch_bounds__(kEncThreads) void encode_delta_kernel(const EncodeP
     out[n + p] = has_p ? static_cast<float>(ap) : inf;
 }
 
-// ---- ARM parameter deltas: what the slot's model bits would change by if ONE transmitted ARM integer were v - 1 or v + 1 ------
-// DESIGN.md 4.20.  Two launches behind the meter's, no atomics.
-//   1. encode_param_delta_kernel: blockIdx = (chunk, tile of 64 candidates, slot).  The wave walks the chunk's 64-pixel
-//      workgroups in order; per workgroup one evaluation as it is, then one per candidate with the candidate's entry moved
-//      (generic path: encode_pixel_model<.., true>; incremental path: arm_candidate on the kept state), the width compared, and the lanes' log2(width) - log2(width'), width' - width and "moved"
-//      summed by wave_sum's fixed tree.  Lane c mod 64 keeps candidate c's running sums over the chunk's workgroups and stores
-//      the cell.  A workgroup in which no lane's width moved adds nothing (its wave sums would be +0.0, 0, 0).
-//   2. encode_param_delta_final_kernel: one wave per candidate adds its cells lane-strided in chunk order and through the tree.
+// ---- rate-network parameter deltas: what the slot's model bits would change by if ONE transmitted integer of the ARM (DESIGN.md
+// 4.20) or of the IFCE (4.21) were v - 1 or v + 1.  Two launches behind the meter's, no atomics.
+//   1. encode_rate_delta_kernel: blockIdx = (chunk, tile of 64 candidates, slot).  The wave walks the chunk's 64-pixel
+//      workgroups in order; per workgroup one evaluation as it is, then one per candidate with the candidate's entry moved, the
+//      width compared, and the lanes' log2(width) - log2(width'), width' - width and "moved" summed by wave_sum's fixed tree.
+//      Lane c mod 64 keeps candidate c's running sums over the chunk's workgroups and stores the cell.  A workgroup in which no
+//      lane's width moved adds nothing (its wave sums would be +0.0, 0, 0).
+//   2. encode_rate_delta_final_kernel: one wave per candidate adds its cells lane-strided in chunk order and through the tree.
 // The order of the additions of a candidate follows from the slot's geometry alone: not from the range of parameters asked for
 // (which only decides the tile a candidate shares), the batch or the device.  Tail lanes and lanes whose symbol is outside the
 // alphabet hold 0 and stay for the shuffles (the meter's launch set such a slot's status).
+// What differs between the two networks (kKind), and nothing else:
+//   a. the blocks walked: an IFCE candidate of grid g can only move symbols of grid g, and a block's grid is uniform, so the wave
+//      walks only the blocks of the grids its tile's candidates name (they are sorted by grid: the first and the last give the range);
+//   b. an IFCE candidate adds nothing for a block of another grid - which is what it would add there, no width moved;
+//   c. what prices a lane: the generic path is a full encode_pixel_model<.., kKind> with the entry moved, the incremental path
+//      arm_candidate or ifce_candidate on the kept state;
+//   d. the row of the table a candidate answers: its own, or RateDeltaParams::row's for the sorted IFCE candidates.
 // ---- the incremental path: the base evaluation's state stays in the LDS, a candidate is a rank-1 update of it ----
 // Per-lane columns, [k][lane] like xa / xb: the inputs [dim], then every hidden layer's accumulators BEFORE the ReLU
 // [n_hidden][dim], then - only for three hidden layers or more - two scratch columns [dim] each (armdelta_incremental_lds).
@@ -612,16 +619,16 @@ __device__ __forceinline__ void arm_input_moved(const EntropyParams& P, int64_t*
 // The ARM's two sums with the candidate's entry moved.  Every step is the full evaluation's arithmetic modulo 2^64: the moved
 // unit's accumulator changes by inc * input, its activation by delta, the next layer's accumulators by delta * weight (re-rounded
 // by their own ReLU), the layers behind that are recomputed in full.  delta == 0: the base's sums.
-__device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x0, const ArmBase& B, const ArmDeltaMove& pm, uint64_t& st0, uint64_t& st1) {
+__device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x0, const ArmBase& B, const RateDeltaMove& pm, uint64_t& st0, uint64_t& st1) {
     const int dim = P.dim, n_hidden = P.n_layers - 1;
     uint64_t a0 = B.a0, a1 = B.a1;
     st0 = B.st0; st1 = B.st1;
-    if (pm.layer >= n_hidden) {  // output layer or stabiliser: one accumulator moves
-        const bool stab = pm.layer > n_hidden;
+    if (pm.at >= n_hidden) {  // output layer or stabiliser: one accumulator moves
+        const bool stab = pm.at > n_hidden;
         const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(arm_input(x0, dim, stab ? 0 : n_hidden, pm.in)));
         if (pm.out == 0) a0 += c; else a1 += c;
     } else {
-        const int l = pm.layer;
+        const int l = pm.at;
         const uint64_t c = static_cast<uint64_t>(pm.inc) * (pm.in < 0 ? uint64_t{1} : static_cast<uint64_t>(arm_input(x0, dim, l, pm.in)));
         const int64_t a = x0[((l + 1) * dim + pm.out) * kEncThreads];
         const int64_t delta = relu16(static_cast<int64_t>(static_cast<uint64_t>(a) + c)) - relu16(a);
@@ -635,7 +642,7 @@ __device__ __forceinline__ void arm_candidate(const EntropyParams& P, int64_t* x
 // two sums by d * ws[n_sp + out][.] and ALL of layer 0's accumulators by d * w0[n_sp + out][.] - both exact in the ring - and
 // every layer behind layer 0 is recomputed in full.  Of the kept state a candidate reads the inputs and layer 0's accumulators
 // only, so the columns of the later layers' accumulators serve as the scratch.  d == 0: the base's sums.
-__device__ __forceinline__ void ifce_candidate(const EntropyParams& P, int g, int y, int x, int64_t* x0, const ArmBase& B, const IfceDeltaMove& im,
+__device__ __forceinline__ void ifce_candidate(const EntropyParams& P, int g, int y, int x, int64_t* x0, const ArmBase& B, const RateDeltaMove& im,
                                                uint64_t& st0, uint64_t& st1) {
     const int dim = P.dim, n_if = P.n_ifce_out, fin = P.ifce_in[g], row = P.n_spatial + im.out;
     const int64_t* fw_ = P.ifce + P.ifce_off[g];
@@ -670,92 +677,29 @@ __device__ __forceinline__ void delta_block_sums(double d_bits, int64_t d_width,
     }
 }
 
-// kIncremental: the slots whose path is the incremental one (ParamDeltaParams::path); the other instantiation takes the rest.
-// Both give the same 64-bit words: the integer model is the same modulo 2^64, the floats and the order they are added in are
-// this one function's.
-template <bool kIncremental>
-__global__ __launch_bounds__(kEncThreads) void encode_param_delta_kernel(const EncodeParams* slots, const ParamDeltaParams* param) {
+// kKind: whose integers the table prices (kRateDeltaArm / kRateDeltaIfce; a. - c. above).  kIncremental: the slots whose path is the
+// incremental one (RateDeltaParams::path); the other instantiation takes the rest.  Both give the same 64-bit words: the integer
+// model is the same modulo 2^64, the floats and the order they are added in are this one function's.
+template <int kKind, bool kIncremental>
+__global__ __launch_bounds__(kEncThreads) void encode_rate_delta_kernel(const EncodeParams* slots, const RateDeltaParams* param) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const EncodeParams& Q = slots[blockIdx.z];
     const EntropyParams& P = Q.ep;
-    const ParamDeltaParams& D = param[blockIdx.z];
+    const RateDeltaParams& D = param[blockIdx.z];
     const uint32_t chunk = blockIdx.x, c0 = blockIdx.y * kArmDeltaTile;
     if ((D.path == kArmDeltaIncremental) != kIncremental || chunk >= D.n_chunks || c0 >= D.n_cand) return;
     const int lane = threadIdx.x;
     const int n_grids = P.n_grids;
     const uint32_t nc = min(static_cast<uint32_t>(kArmDeltaTile), D.n_cand - c0);
-    const uint32_t b_end = min((chunk + 1) * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.n_blocks);
-    int64_t* x0 = reinterpret_cast<int64_t*>(smem_raw) + lane;
-    ParamDeltaCell acc{0.0, 0, 0};  // of candidate c0 + lane
-    int g = 0;
-#pragma unroll 1
-    for (uint32_t b = chunk * kArmDeltaChunkBlocks; b < b_end; ++b) {
-        while (g + 1 < n_grids && b >= Q.block_first[g + 1]) ++g;
-        const int H = P.grid_h[g], W = P.grid_w[g];
-        const int p = static_cast<int>(b - Q.block_first[g]) * kEncThreads + lane;
-        const int sym = p < H * W ? P.latent[g][p] : 0;
-        const bool ok = p < H * W && in_alphabet(sym);
-        const int y = ok ? p / W : 0, x = ok ? p - y * W : 0;
-        double mu, rcp, base = 0.0;
-        uint32_t width = 0;
-        ArmBase B{0, 0, 0, 0};
-        if (ok) {
-            if (kIncremental) {
-                encode_pixel_model<false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
-                B = arm_base_store(P, x0);
-                arm_sums_to_model(P, B.st0 + B.a0, B.st1 + B.a1, mu, rcp);
-            } else encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
-            width = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
-            base = log2(static_cast<double>(width));
-        }
-#pragma unroll 1
-        for (uint32_t ci = 0; ci < nc; ++ci) {
-            const ArmDeltaMove pm = D.cand[c0 + ci];  // wave-uniform
-            if (!pm.legal) continue;
-            double d_bits = 0.0;
-            int64_t d_width = 0;
-            if (ok) {
-                if (kIncremental) {
-                    uint64_t st0, st1;
-                    arm_candidate(P, x0, B, pm, st0, st1);
-                    arm_sums_to_model(P, st0, st1, mu, rcp);
-                } else encode_pixel_model<false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp, pm);
-                const uint32_t w = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
-                if (w != width) {
-                    d_bits = base - log2(static_cast<double>(w));
-                    d_width = static_cast<int64_t>(w) - static_cast<int64_t>(width);
-                }
-            }
-            delta_block_sums(d_bits, d_width, static_cast<uint32_t>(lane) == ci, acc);
-        }
-    }
-    if (static_cast<uint32_t>(lane) < nc) D.partial[static_cast<size_t>(chunk) * D.n_cand + c0 + lane] = acc;
-}
-
-// ---- IFCE parameter deltas: the same table for the transmitted IFCE integers -----------------------------------
-// The launches, the chunks, the cells and the order of a candidate's additions are the ARM table's.  What differs: a candidate
-// of grid g can only move symbols of grid g, and a block's grid is uniform, so the wave walks only the blocks of the grids its
-// tile's candidates name (the candidates are sorted by grid: the first and the last give the range) and a candidate adds nothing
-// for a block of another grid - which is what it would add there, a workgroup in which no width moved.  Generic path: feature
-// im.out of grid im.grid through ifce_feature<.., true> inside a full encode_pixel_model; incremental path: ifce_candidate.
-template <bool kIncremental>
-__global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_kernel(const EncodeParams* slots, const IfceDeltaParams* param) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const EncodeParams& Q = slots[blockIdx.z];
-    const EntropyParams& P = Q.ep;
-    const IfceDeltaParams& D = param[blockIdx.z];
-    const uint32_t chunk = blockIdx.x, c0 = blockIdx.y * kArmDeltaTile;
-    if ((D.path == kArmDeltaIncremental) != kIncremental || chunk >= D.n_chunks || c0 >= D.n_cand) return;
-    const int lane = threadIdx.x;
-    const int n_grids = P.n_grids;
-    const uint32_t nc = min(static_cast<uint32_t>(kArmDeltaTile), D.n_cand - c0);
-    const int g_lo = D.cand[c0].grid, g_hi = D.cand[c0 + nc - 1].grid;  // 0 <= g_lo <= g_hi < n_grids (ifcedelta_place)
-    const uint32_t b_first = max(chunk * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.block_first[g_lo]);
+    // a. the grids whose blocks the wave walks: all of them, or those the tile's candidates name (0 <= g <= g_hi < n_grids, ifcedelta_place)
+    int g = 0, g_hi = n_grids - 1;
+    if constexpr (kKind == kRateDeltaIfce) { g = D.cand[c0].at; g_hi = D.cand[c0 + nc - 1].at; }
+    uint32_t b_first = chunk * kArmDeltaChunkBlocks;
+    if constexpr (kKind == kRateDeltaIfce) b_first = max(b_first, Q.block_first[g]);
     const uint32_t b_end = min(min((chunk + 1) * static_cast<uint32_t>(kArmDeltaChunkBlocks), Q.n_blocks),
                                g_hi + 1 < n_grids ? Q.block_first[g_hi + 1] : Q.n_blocks);
     int64_t* x0 = reinterpret_cast<int64_t*>(smem_raw) + lane;
-    ParamDeltaCell acc{0.0, 0, 0};  // of sorted candidate c0 + lane
-    int g = g_lo;
+    ParamDeltaCell acc{0.0, 0, 0};  // of candidate c0 + lane
 #pragma unroll 1
     for (uint32_t b = b_first; b < b_end; ++b) {
         while (g + 1 < n_grids && b >= Q.block_first[g + 1]) ++g;
@@ -769,7 +713,7 @@ __global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_kernel(const En
         ArmBase B{0, 0, 0, 0};
         if (ok) {
             if (kIncremental) {
-                encode_pixel_model<false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
+                encode_pixel_model<false, kRateDeltaNone, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
                 B = arm_base_store(P, x0);
                 arm_sums_to_model(P, B.st0 + B.a0, B.st1 + B.a1, mu, rcp);
             } else encode_pixel_model<false>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp);
@@ -778,16 +722,18 @@ __global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_kernel(const En
         }
 #pragma unroll 1
         for (uint32_t ci = 0; ci < nc; ++ci) {
-            const IfceDeltaMove im = D.cand[c0 + ci];  // wave-uniform
-            if (!im.legal || im.grid != g) continue;
+            const RateDeltaMove mv = D.cand[c0 + ci];  // wave-uniform
+            if (!mv.legal) continue;
+            if constexpr (kKind == kRateDeltaIfce) if (mv.at != g) continue;  // b.
             double d_bits = 0.0;
             int64_t d_width = 0;
             if (ok) {
-                if (kIncremental) {
+                if (kIncremental) {  // c.
                     uint64_t st0, st1;
-                    ifce_candidate(P, g, y, x, x0, B, im, st0, st1);
+                    if constexpr (kKind == kRateDeltaIfce) ifce_candidate(P, g, y, x, x0, B, mv, st0, st1);
+                    else arm_candidate(P, x0, B, mv, st0, st1);
                     arm_sums_to_model(P, st0, st1, mu, rcp);
-                } else encode_pixel_model<false, false, false, true>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp, ArmDeltaMove{}, im);
+                } else encode_pixel_model<false, kKind>(P, g, y, x, lane, smem_raw, LatentOverride{}, mu, rcp, mv);
                 const uint32_t w = window_left(mu, rcp, sym + 1, kExpTab) - window_left(mu, rcp, sym, kExpTab);
                 if (w != width) {
                     d_bits = base - log2(static_cast<double>(w));
@@ -800,9 +746,9 @@ __global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_kernel(const En
     if (static_cast<uint32_t>(lane) < nc) D.partial[static_cast<size_t>(chunk) * D.n_cand + c0 + lane] = acc;
 }
 
-// blockIdx.x = sorted candidate, blockIdx.y = slot: encode_param_delta_final_kernel's additions, stored at the candidate's row.
-__global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_final_kernel(const IfceDeltaParams* param) {
-    const IfceDeltaParams& D = param[blockIdx.y];
+// blockIdx.x = candidate, blockIdx.y = slot; the cell is stored at the candidate's row (d. above).
+__global__ __launch_bounds__(kEncThreads) void encode_rate_delta_final_kernel(const RateDeltaParams* param) {
+    const RateDeltaParams& D = param[blockIdx.y];
     const uint32_t c = blockIdx.x;
     if (c >= D.n_cand) return;
     const int lane = threadIdx.x;
@@ -816,28 +762,9 @@ __global__ __launch_bounds__(kEncThreads) void encode_ifce_delta_final_kernel(co
     }
     bits = wave_sum(bits); width = wave_sum(width); moved = wave_sum(moved);
     if (lane != 0) return;
-    if (D.cand[c].legal) D.out[D.row[c]] = ParamDeltaCell{bits, static_cast<int64_t>(width), static_cast<int64_t>(moved)};
-    else D.out[D.row[c]] = ParamDeltaCell{static_cast<double>(__builtin_inff()), 0, 0};
-}
-
-// blockIdx.x = candidate, blockIdx.y = slot.
-__global__ __launch_bounds__(kEncThreads) void encode_param_delta_final_kernel(const ParamDeltaParams* param) {
-    const ParamDeltaParams& D = param[blockIdx.y];
-    const uint32_t c = blockIdx.x;
-    if (c >= D.n_cand) return;
-    const int lane = threadIdx.x;
-    double bits = 0.0;
-    uint64_t width = 0, moved = 0;
-    for (uint32_t j = lane; j < D.n_chunks; j += kEncThreads) {
-        const ParamDeltaCell cell = D.partial[static_cast<size_t>(j) * D.n_cand + c];
-        bits += cell.bits;
-        width += static_cast<uint64_t>(cell.sum_width);
-        moved += static_cast<uint64_t>(cell.moved);
-    }
-    bits = wave_sum(bits); width = wave_sum(width); moved = wave_sum(moved);
-    if (lane != 0) return;
-    if (D.cand[c].legal) D.out[c] = ParamDeltaCell{bits, static_cast<int64_t>(width), static_cast<int64_t>(moved)};
-    else D.out[c] = ParamDeltaCell{static_cast<double>(__builtin_inff()), 0, 0};
+    const uint32_t r = D.row ? D.row[c] : c;  // wave-uniform
+    if (D.cand[c].legal) D.out[r] = ParamDeltaCell{bits, static_cast<int64_t>(width), static_cast<int64_t>(moved)};
+    else D.out[r] = ParamDeltaCell{static_cast<double>(__builtin_inff()), 0, 0};
 }
 
 size_t encode_contexts_lds_bytes(int dim) { return static_cast<size_t>(2) * dim * kEncThreads * sizeof(int64_t); }
@@ -897,50 +824,30 @@ hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* 
     return hipGetLastError();
 }
 
-// What the ARM's and the IFCE's table share: one launch of the table kernel per path that has slots (lds == 0: none; each
-// workgroup of the other path's slots returns at once), then the final kernel.
-template <class Params>
-static hipError_t launch_delta_table(void (*generic)(const EncodeParams*, const Params*), void (*incremental)(const EncodeParams*, const Params*),
-                                     void (*final)(const Params*), const EncodeParams* d_slots, const Params* d_param, int n_slots,
-                                     unsigned max_chunks, unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
-    if (n_slots <= 0 || max_cand == 0) return hipSuccess;
-    if (max_chunks > 0) {
-        const dim3 grid(max_chunks, (max_cand + kArmDeltaTile - 1) / kArmDeltaTile, n_slots);
-        if (lds_generic > 0) {
-            if (lds_generic > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(generic), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   static_cast<int>(lds_generic));
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(generic, grid, dim3(kEncThreads), lds_generic, stream, d_slots, d_param);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        if (lds_incremental > 0) {
-            if (lds_incremental > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(incremental), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   static_cast<int>(lds_incremental));
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(incremental, grid, dim3(kEncThreads), lds_incremental, stream, d_slots, d_param);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    hipLaunchKernelGGL(final, dim3(max_cand, n_slots), dim3(kEncThreads), 0, stream, d_param);
-    return hipGetLastError();
-}
-
-hipError_t launch_encode_param_deltas(const EncodeParams* d_slots, const ParamDeltaParams* d_param, int n_slots, unsigned max_chunks,
-                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
-    return launch_delta_table(encode_param_delta_kernel<false>, encode_param_delta_kernel<true>, encode_param_delta_final_kernel, d_slots,
-                              d_param, n_slots, max_chunks, max_cand, lds_generic, lds_incremental, stream);
-}
-
-hipError_t launch_encode_ifce_deltas(const EncodeParams* d_slots, const IfceDeltaParams* d_param, int n_slots, unsigned max_chunks,
+// One launch of the kind's table kernel per path that has slots (lds == 0: none; each workgroup of the other path's slots returns
+// at once), then the final kernel.
+hipError_t launch_encode_rate_deltas(int kind, const EncodeParams* d_slots, const RateDeltaParams* d_param, int n_slots, unsigned max_chunks,
                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream) {
-    return launch_delta_table(encode_ifce_delta_kernel<false>, encode_ifce_delta_kernel<true>, encode_ifce_delta_final_kernel, d_slots,
-                              d_param, n_slots, max_chunks, max_cand, lds_generic, lds_incremental, stream);
+    if (n_slots <= 0 || max_cand == 0) return hipSuccess;
+    using Kernel = void (*)(const EncodeParams*, const RateDeltaParams*);
+    static constexpr Kernel kernels[2][2] = {{encode_rate_delta_kernel<kRateDeltaArm, false>, encode_rate_delta_kernel<kRateDeltaArm, true>},
+                                             {encode_rate_delta_kernel<kRateDeltaIfce, false>, encode_rate_delta_kernel<kRateDeltaIfce, true>}};
+    const size_t lds[2] = {lds_generic, lds_incremental};
+    const dim3 grid(max_chunks, (max_cand + kArmDeltaTile - 1) / kArmDeltaTile, n_slots);
+    for (int path = 0; path < 2; ++path) {  // generic, incremental
+        if (max_chunks == 0 || lds[path] == 0) continue;
+        const Kernel kernel = kernels[kind == kRateDeltaIfce][path];
+        if (lds[path] > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               static_cast<int>(lds[path]));
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(kEncThreads), lds[path], stream, d_slots, d_param);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(encode_rate_delta_final_kernel, dim3(max_cand, n_slots), dim3(kEncThreads), 0, stream, d_param);
+    return hipGetLastError();
 }
 
 }  // namespace ccd

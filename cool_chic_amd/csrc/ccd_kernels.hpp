@@ -79,9 +79,7 @@ hipError_t launch_encode_rate(const EncodeParams* d_slots, const RateParams* d_r
                               size_t lds_bytes, hipStream_t stream);
 hipError_t launch_encode_deltas(const EncodeParams* d_slots, const DeltaParams* d_delta, int n_slots, unsigned max_blocks,
                                 unsigned max_tiles, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_encode_param_deltas(const EncodeParams* d_slots, const ParamDeltaParams* d_param, int n_slots, unsigned max_chunks,
-                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream);
-hipError_t launch_encode_ifce_deltas(const EncodeParams* d_slots, const IfceDeltaParams* d_param, int n_slots, unsigned max_chunks,
+hipError_t launch_encode_rate_deltas(int kind, const EncodeParams* d_slots, const RateDeltaParams* d_param, int n_slots, unsigned max_chunks,
                                      unsigned max_cand, size_t lds_generic, size_t lds_incremental, hipStream_t stream);
 // ccd_ingest.hip
 hipError_t launch_latent_ingest(const IngestSeg* d_segs, const uint32_t* d_prefix, int n_segs, uint32_t n_blocks, int32_t* d_status_all,

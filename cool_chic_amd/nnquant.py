@@ -17,7 +17,7 @@ The selection (order of the modules, tie-breaks, sweeps, infeasible cells) is `s
 callable, so it is testable without a device.  Intra frames only; the two cool-chics of a P / B frame: nnquant_inter.py."""
 import itertools
 import time
-from typing import TYPE_CHECKING, Callable, List, NamedTuple, Optional, Sequence
+from typing import TYPE_CHECKING, Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -132,6 +132,31 @@ def refused(call, *args, **kwargs):
         return None, True
 
 
+def network_rates(device: int, nets: Sequence[Tuple[CCHeader, bytes]], latent_ptrs: Sequence[int], owner=None, stream: int = 0,
+                  raise_status: bool = False) -> list:
+    """(total_bits, n_bytes_header) per (header, bytes_nn) over the device latents, None where the library refuses the network:
+    the rate meter alone, one EncodeBatch, one measure and one wait.  raise_status: a slot the meter leaves with a negative
+    status (a latent outside the alphabet) raises it."""
+    from .encoder import EncodeBatch
+
+    out = [None] * len(nets)
+    with EncodeBatch(device) as enc:
+        slots = []
+        for i, (header, bytes_nn) in enumerate(nets):
+            s, no = refused(enc.add_device, header, bytes_nn, latent_ptrs, owner=owner)
+            if not no:
+                slots.append((i, s))
+        if slots:
+            enc.measure(stream)
+            enc.wait(stream)
+            for i, s in slots:
+                r = enc.rate(s)
+                if raise_status and r.status < 0:
+                    raise CcdError(r.status, "ccd_enc_slot_rate")
+                out[i] = (r.total_bits, r.n_bytes_header)
+    return out
+
+
 def build_network(arch: CCHeader, float_values: np.ndarray, steps: Sequence[int], fast_path_only: bool = False) -> Optional[_Network]:
     """The integer network of `float_values` at `steps` with its best Exp-Golomb orders; None where the quantiser refuses a
     value or a step (CCD_ERR_VALUE).  Not `feasible`: a payload beyond the header's 14-bit nn_n_bytes (the header writer does
@@ -183,7 +208,6 @@ class NetworkQuantiser:
         import torch
 
         from .batch import FRAME_DATA_TYPES, DecodeBatch
-        from .encoder import EncodeBatch
         from .quality import QualityMeter, _frame_planes
         from .rd import RdEvaluator, rd_cost
 
@@ -220,21 +244,7 @@ class NetworkQuantiser:
         priced: dict = {}   # of the table being chosen from: cell index -> (total_bits, sse, n_bytes_header)
 
         def rates(nets: List[_Network]):
-            """(total_bits, n_bytes_header) per network, None where the library refuses it: the rate meter alone."""
-            out = [None] * len(nets)
-            with EncodeBatch(self.device) as enc:
-                slots = []
-                for i, net in enumerate(nets):
-                    s, no = refused(enc.add_device, net.header, net.bytes_nn, ptrs, owner=owner)
-                    if not no:
-                        slots.append((i, s))
-                if slots:
-                    enc.measure(st)
-                    enc.wait(st)
-                    for i, s in slots:
-                        r = enc.rate(s)
-                        out[i] = (r.total_bits, r.n_bytes_header)
-            return out
+            return network_rates(self.device, [(net.header, net.bytes_nn) for net in nets], ptrs, owner, st)
 
         def errors(nets: List[_Network]):
             """sse per plane per network, None where the library refuses it: the float path over the given latents and the

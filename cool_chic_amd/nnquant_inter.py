@@ -20,7 +20,7 @@ import numpy as np
 
 from . import writer
 from ._lib import CCHeader
-from .nnquant import MODULES, Cell, Pricing, _Network, build_network, choose, module_cells, refused
+from .nnquant import MODULES, Cell, Pricing, _Network, build_network, choose, module_cells, network_rates, refused
 
 ROLES = ("residue", "motion")
 
@@ -106,7 +106,6 @@ class InterNetworkQuantiser:
         import torch
 
         from .batch import FRAME_DATA_TYPES, DecodeBatch
-        from .encoder import EncodeBatch
         from .io import FrameData
         from .iscore import InterScore
         from .quality import _frame_planes
@@ -142,21 +141,7 @@ class InterNetworkQuantiser:
         bitdepth = int(source.bitdepth)
 
         def rates(role: int, nets: List[_Network]):
-            """(total_bits, n_bytes_header) per network, None where the library refuses it: the rate meter alone."""
-            out = [None] * len(nets)
-            with EncodeBatch(self.device) as enc:
-                slots = []
-                for i, net in enumerate(nets):
-                    s, no = refused(enc.add_device, net.header, net.bytes_nn, ptrs[role], owner=owner)
-                    if not no:
-                        slots.append((i, s))
-                if slots:
-                    enc.measure(st)
-                    enc.wait(st)
-                    for i, s in slots:
-                        r = enc.rate(s)
-                        out[i] = (r.total_bits, r.n_bytes_header)
-            return out
+            return network_rates(self.device, [(net.header, net.bytes_nn) for net in nets], ptrs[role], owner, st)
 
         def decode(role: int, nets: List[_Network], use):
             """The float outputs of the networks over the role's latents: use(dec, [(index into nets, device address)]) runs

@@ -1,13 +1,12 @@
-"""ArmRefiner: a +-1 descent over the transmitted integers of a cool-chic's ARM, after the steps are chosen.
+"""ArmRefiner, RateRefiner: a +-1 descent over the transmitted integers of a cool-chic's rate networks - the ARM,
+the IFCE (4.21) or both - after the steps are chosen.
 
-The ARM's integers change only the rate: the planes, the squared error and the header size stay what they were, so "better" is
-fewer bits, total_bits + 8 * len(bytes_nn) in rd.rd_cost's terms, for every lambda > 0, and neither a source picture nor a
-reconstruction is needed - the same code serves an intra frame and both cool-chics of a P / B frame.  Every step asks the device
-for the exact change of the latents' model bits for -1 and +1 at every ARM integer (EncodeBatch.measure_param_deltas), adds the
-exact change of the payload's size, picks moves, and accepts them only if the existing meter says that the objective fell.
-
-RateRefiner is the same descent over both rate networks, the ARM and the IFCE: the IFCE's integers change the
-features the ARM reads and nothing else, so the objective holds for them too.
+These integers change only the rate: the planes, the squared error and the header size stay what they were (the IFCE's change
+the features the ARM reads and nothing else), so "better" is fewer bits, total_bits + 8 * len(bytes_nn) in rd.rd_cost's terms,
+for every lambda > 0, and neither a source picture nor a reconstruction is needed - the same code serves an intra frame and both
+cool-chics of a P / B frame.  Every step asks the device for the exact change of the latents' model bits for -1 and +1 at every
+integer (EncodeBatch.measure_param_deltas, measure_ifce_deltas), adds the exact change of the payload's size, picks moves, and
+accepts them only if the existing meter says that the objective fell.
 
 `expgol_bit_deltas`, `payload_byte_deltas`, their `rate_` forms over groups 0 .. 3 and `pick_moves` are pure functions, testable
 without a device."""
@@ -17,7 +16,7 @@ import numpy as np
 
 from . import writer
 from ._lib import CCHeader
-from .nnquant import refused
+from .nnquant import network_rates
 
 MAX_ORDER = 12  # Exp-Golomb orders the header can name (ccd_network_best_expgol)
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
@@ -156,48 +155,62 @@ def build_candidate(arch: CCHeader, values: np.ndarray):
 
 
 class ArmRefiner:
-    """refine(): the +-1 descent of one cool-chic's ARM on one MI355X."""
+    """refine(): the +-1 descent over the transmitted integers of the rate networks in `modules` - "arm", "ifce" or both - of one
+    cool-chic on one MI355X.  ArmRefiner(device) refines the ARM alone; RateRefiner is this class with both
+    modules as the default (4.21).  Groups 0 .. 3 are contiguous in the stream, so a Move.index is an index into `values` for
+    both modules; every step takes the tables of the modules refined, makes ONE pick_moves over their rows and builds the
+    candidate with all orders chosen again."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, modules: Sequence[str] = ("arm",)):
         self.device = int(device)
-
-    def _table(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
-        """(total_bits, ParamDeltas) of the network as it stands: one measure_param_deltas.  refine() calls it through self,
-        so a test can put a made-up table in its place."""
-        from .encoder import EncodeBatch
-
-        with EncodeBatch(self.device) as enc:
-            slot = enc.add_device(h, nn, ptrs, owner=owner)
-            enc.measure_param_deltas(stream)
-            enc.wait(stream)
-            return enc.rate(slot).total_bits, enc.param_deltas(slot)
-
-    _covers = "the ARM"
+        self.modules = tuple(modules)
+        if not self.modules or any(m not in ("arm", "ifce") for m in self.modules) or len(set(self.modules)) != len(self.modules):
+            raise ValueError('modules: "arm", "ifce" or both')
 
     def _n_params(self, h: CCHeader) -> int:
-        """Rows the table of _table() has: the integers refine() may move are values[:this]."""
-        return sum(writer.network_layout(h)[:2])
+        """Rows the table of _table() has, the ARM's and then the IFCE's: the integers refine() may move are values[:this]."""
+        return sum(writer.network_layout(h)[:4])
 
     def _nn_deltas(self, h: CCHeader, values: np.ndarray) -> np.ndarray:
-        """The exact change of 8 * len(bytes_nn) for every row and sign of the table."""
-        return payload_byte_deltas(h, values)
+        """The exact change of 8 * len(bytes_nn) for every row and sign of the table (rate_payload_byte_deltas), +inf in the
+        rows of a module that is not refined: whatever the table holds there, pick_moves never takes such a row."""
+        out = rate_payload_byte_deltas(h, values)
+        n_arm = sum(writer.network_layout(h)[:2])
+        if "arm" not in self.modules:
+            out[:n_arm] = np.inf
+        if "ifce" not in self.modules:
+            out[n_arm:] = np.inf
+        return out
+
+    def _table(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
+        """(total_bits, ParamDeltas over [n_arm + n_ifce] rows) of the network as it stands: one measure per module refined
+        (EncodeBatch.measure_param_deltas, measure_ifce_deltas) on one handle; the rows of the other module hold +inf, 0, 0.
+        refine() calls it through self, so a test can put a made-up table in its place."""
+        from .encoder import EncodeBatch, ParamDeltas
+
+        n_arm, n = sum(writer.network_layout(h)[:2]), self._n_params(h)
+        bits = np.full((n, 2), np.inf, np.float64)
+        sum_width, moved = np.zeros((n, 2), np.int64), np.zeros((n, 2), np.int64)
+        with EncodeBatch(self.device) as enc:
+            slot = enc.add_device(h, nn, ptrs, owner=owner)
+            for module in self.modules:
+                if module == "arm":
+                    enc.measure_param_deltas(stream)
+                    enc.wait(stream)
+                    t, rows = enc.param_deltas(slot), slice(0, n_arm)
+                else:
+                    enc.measure_ifce_deltas(stream)
+                    enc.wait(stream)
+                    t, rows = enc.ifce_deltas(slot), slice(n_arm, n)
+                if t.first != 0 or t.bits.shape[0] != rows.stop - rows.start:
+                    raise ValueError("the %s table does not cover the module" % module)
+                bits[rows], sum_width[rows], moved[rows] = t.bits, t.sum_width, t.moved
+            return enc.rate(slot).total_bits, ParamDeltas(0, bits, sum_width, moved)
 
     def _price(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
         """total_bits of a candidate by the existing meter; None where the library refuses the network."""
-        from .encoder import EncodeBatch
-
-        with EncodeBatch(self.device) as enc:
-            slot, no = refused(enc.add_device, h, nn, ptrs, owner=owner)
-            if no:
-                return None
-            enc.measure(stream)
-            enc.wait(stream)
-            r = enc.rate(slot)
-            if r.status < 0:
-                from ._lib import CcdError
-
-                raise CcdError(r.status, "ccd_enc_slot_rate")
-            return r.total_bits
+        r, = network_rates(self.device, [(h, nn)], ptrs, owner, stream, raise_status=True)
+        return None if r is None else r[0]
 
     def refine(self, arch: CCHeader, values: np.ndarray, latent_ptrs: Sequence[int], max_steps: int, batch: int = 1, owner=None,
                stream: int = 0) -> RefinedNetwork:
@@ -222,7 +235,7 @@ class ArmRefiner:
             if start is None:
                 start = objective
             if table.first != 0 or table.bits.shape[0] != self._n_params(h):
-                raise ValueError("the table does not cover " + self._covers)
+                raise ValueError("the table does not cover the ARM and the IFCE")
             moves = pick_moves(table.bits, self._nn_deltas(h, values), int(batch))
             if not moves:
                 stopped = "no move promises a gain"
@@ -258,54 +271,9 @@ class ArmRefiner:
 
 
 class RateRefiner(ArmRefiner):
-    """refine(): ArmRefiner's descent over BOTH rate networks of one cool-chic, the ARM and the IFCE.  The
-    IFCE's integers change the features the ARM reads and nothing else, so the objective, the acceptance rule and the meter are
-    ArmRefiner's; every step takes both tables (EncodeBatch.measure_param_deltas, measure_ifce_deltas), makes ONE pick_moves over
-    their rows and builds the candidate with all orders chosen again.  Groups 0 .. 3 are contiguous in the stream, so a
-    Move.index is an index into `values` for both modules.  modules=("ifce",) refines the IFCE alone, ("arm",) is ArmRefiner."""
-
-    _covers = "the ARM and the IFCE"
+    """ArmRefiner over BOTH rate networks unless told otherwise: modules=("ifce",) refines the IFCE alone, ("arm",) is
+    ArmRefiner.  The IFCE's integers change the features the ARM reads and nothing else, so the objective, the acceptance rule
+    and the meter are the same."""
 
     def __init__(self, device: int = 0, modules: Sequence[str] = ("arm", "ifce")):
-        super().__init__(device)
-        self.modules = tuple(modules)
-        if not self.modules or any(m not in ("arm", "ifce") for m in self.modules) or len(set(self.modules)) != len(self.modules):
-            raise ValueError('modules: "arm", "ifce" or both')
-
-    def _n_params(self, h: CCHeader) -> int:
-        return sum(writer.network_layout(h)[:4])
-
-    def _nn_deltas(self, h: CCHeader, values: np.ndarray) -> np.ndarray:
-        """rate_payload_byte_deltas, +inf in the rows of a module that is not refined: whatever the table holds there, pick_moves
-        never takes such a row."""
-        out = rate_payload_byte_deltas(h, values)
-        n_arm = sum(writer.network_layout(h)[:2])
-        if "arm" not in self.modules:
-            out[:n_arm] = np.inf
-        if "ifce" not in self.modules:
-            out[n_arm:] = np.inf
-        return out
-
-    def _table(self, h: CCHeader, nn: bytes, ptrs, owner, stream):
-        """(total_bits, ParamDeltas over [n_arm + n_ifce] rows): one measure per module refined on one handle; the rows of the
-        other module hold +inf, 0, 0."""
-        from .encoder import EncodeBatch, ParamDeltas
-
-        n_arm, n = sum(writer.network_layout(h)[:2]), self._n_params(h)
-        bits = np.full((n, 2), np.inf, np.float64)
-        sum_width, moved = np.zeros((n, 2), np.int64), np.zeros((n, 2), np.int64)
-        with EncodeBatch(self.device) as enc:
-            slot = enc.add_device(h, nn, ptrs, owner=owner)
-            for module in self.modules:
-                if module == "arm":
-                    enc.measure_param_deltas(stream)
-                    enc.wait(stream)
-                    t, rows = enc.param_deltas(slot), slice(0, n_arm)
-                else:
-                    enc.measure_ifce_deltas(stream)
-                    enc.wait(stream)
-                    t, rows = enc.ifce_deltas(slot), slice(n_arm, n)
-                if t.first != 0 or t.bits.shape[0] != rows.stop - rows.start:
-                    raise ValueError("the table does not cover " + self._covers)
-                bits[rows], sum_width[rows], moved[rows] = t.bits, t.sum_width, t.moved
-            return enc.rate(slot).total_bits, ParamDeltas(0, bits, sum_width, moved)
+        super().__init__(device, modules)
