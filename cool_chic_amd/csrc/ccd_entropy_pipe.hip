@@ -407,9 +407,8 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "ds_read_b32 %[top], v53\n\t"
                 "ds_read_b32 %[ring], v53 offset:520\n\t"
                 "ds_read_b32 %[goff], v53 offset:1040\n\t"
-                "ds_read_b64 v[40:41], v50\n\t"
-                "ds_read_b64 v[42:43], v50 offset:512\n\t"
-                "s_waitcnt lgkmcnt(5)\n\t"
+                "ds_read2st64_b64 v[40:43], v50 offset1:1\n\t"
+                "s_waitcnt lgkmcnt(4)\n\t"
                 "v_readfirstlane_b32 s58, v52\n\t"
                 "s_cmp_eq_u32 s58, s57\n\t"
                 "s_cbranch_scc1 13f\n\t"
@@ -432,10 +431,9 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_cbranch_scc1 400f\n\t"
                 "s_cmp_eq_u32 s58, 4\n\t"          // a 4-symbol part (4-pixel tasks): ccd_dec_parts4.inc
                 "s_cbranch_scc1 440f\n\t"
-                "s_branch 1f\n\t"
+                "s_branch 31f\n\t"
                 "8:\n\t"
-                "ds_read_b64 v[40:41], v50\n\t"
-                "ds_read_b64 v[42:43], v50 offset:512\n\t"
+                "ds_read2st64_b64 v[40:43], v50 offset1:1\n\t"
                 "s_branch 19f\n\t"
                 "13:\n\t"
                 "s_add_u32 %[spins], %[spins], s68\n\t"
@@ -444,6 +442,10 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_sub_u32 s58, s54, %[i]\n\t"
                 "s_cmp_eq_u32 s58, 16\n\t"
                 "s_cbranch_scc1 80f\n\t"
+                // a look leaves rows 0 / 1 in flight as ONE read (both in v[40:43]); the loop's copies count single reads, so whoever
+                // enters the loop behind a look waits for that read here (the unrolled blocks count it themselves)
+                "31:\n\t"
+                "s_waitcnt lgkmcnt(0)\n\t"
                 ".p2align 6\n\t"
                 "1:\n\t"
                 // ---- copy 0: (L, P) of the current symbol in v[40:41], two rows ahead in flight (order: dloop_variants.hip)
@@ -581,9 +583,8 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "ds_read_b32 %[top], v53\n\t"
                 "ds_read_b32 %[ring], v53 offset:520\n\t"
                 "ds_read_b32 %[goff], v53 offset:1040\n\t"
-                "ds_read_b64 v[40:41], v50\n\t"
-                "ds_read_b64 v[42:43], v50 offset:512\n\t"
-                "s_waitcnt lgkmcnt(5)\n\t"
+                "ds_read2st64_b64 v[40:43], v50 offset1:1\n\t"
+                "s_waitcnt lgkmcnt(4)\n\t"
                 "v_readfirstlane_b32 s58, v52\n\t"
                 "s_bitcmp1_b32 s58, s59\n\t"
                 "s_cbranch_scc1 27f\n\t"
@@ -597,7 +598,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_cmp_eq_u32 s58, 8\n\t"
                 "s_cbranch_scc1 420f\n\t"
                 "s_cmp_eq_u32 s58, 4\n\t"          // a 4-symbol part at pixel 4, 8 or 12 of the batch
-                "s_cbranch_scc0 1b\n\t"
+                "s_cbranch_scc0 31b\n\t"
                 "s_and_b32 s58, %[i], s62\n\t"
                 "s_cmp_eq_u32 s58, 4\n\t"
                 "s_cbranch_scc1 450f\n\t"
@@ -605,7 +606,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_cbranch_scc1 460f\n\t"
                 "s_cmp_eq_u32 s58, 12\n\t"
                 "s_cbranch_scc1 470f\n\t"
-                "s_branch 1b\n\t"
+                "s_branch 31b\n\t"
                 // the batch is finished (its last part is published): slot handed back, batch counted
                 "29:\n\t"
                 "s_mov_b32 s65, 0\n\t"
@@ -754,15 +755,14 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "ds_read_b32 %[ring], v53 offset:520\n\t"
                 "ds_read_b32 %[goff], v53 offset:1040\n\t"
                 "v_lshl_add_u32 v50, s56, 9, %[tabl]\n\t"
-                "ds_read_b64 v[40:41], v50\n\t"
-                "ds_read_b64 v[42:43], v50 offset:512\n\t"
+                "ds_read2st64_b64 v[40:43], v50 offset1:1\n\t"
                 // a FULL batch of this step ahead (the common case on the wide grids): its end index needs no clamp, its ready word
                 // is compared with the constant "all parts", and nothing else is tested (s72 = n on grids with 16-symbol batches,
                 // 0 on the others: never full)
                 "s_add_u32 s54, %[i], s69\n\t"
                 "s_cmp_le_u32 s54, s72\n\t"
                 "s_cbranch_scc0 25f\n\t"
-                "s_waitcnt lgkmcnt(5)\n\t"          // the counter (the first of the six answers)
+                "s_waitcnt lgkmcnt(4)\n\t"          // the counter (the first of the five answers)
                 "v_readfirstlane_b32 s59, v54\n\t"
                 "s_cmp_eq_u32 s59, s73\n\t"
                 "s_cbranch_scc1 80b\n\t"
@@ -778,13 +778,13 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                 "s_add_u32 s57, s58, s70\n\t"
                 "s_lshr_b32 s57, s57, %[tshift]\n\t"
                 "s_bfm_b32 s57, s57, 0\n\t"
-                "s_waitcnt lgkmcnt(5)\n\t"          // the counter (the first of the six answers)
+                "s_waitcnt lgkmcnt(4)\n\t"          // the counter (the first of the five answers)
                 "v_readfirstlane_b32 s59, v54\n\t"
                 "s_cmp_eq_u32 s59, s57\n\t"
                 "s_cbranch_scc0 23f\n\t"
                 "s_cmp_eq_u32 s58, 16\n\t"
                 "s_cbranch_scc1 80b\n\t"
-                "s_branch 1b\n\t"
+                "s_branch 31b\n\t"
                 // not complete when asked: poll it like a batch entered from the top (v51 = its counter, v53 = its top symbols)
                 "23:\n\t"
                 "s_mov_b32 s68, 0\n\t"
@@ -840,7 +840,7 @@ __device__ __forceinline__ uint32_t decoder_grid(const PipeCtx& C, DecState& S) 
                   [wbuf] "v"(wbuf), [wbase] "s"(wbase), [tabl] "v"(tab_lane), [lane] "v"(static_cast<uint32_t>(lane)),
                   [l4] "v"(lane_top_off), [lat] "s"(lat_addr)
                 : "memory", "vcc", "scc", "m0", "s40", "s41", "s42", "s43", "s44", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55",
-                  "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60");
+                  "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61");
 #pragma clang diagnostic pop
             if (status == 0) break;  // every step of the segment is done
             if (status == 3) {  // the region renormalised with the last buffered payload word: refill, resume inside the batch

@@ -8,10 +8,37 @@ rotation without index arithmetic, bound test or branch; rows at immediate offse
 renormalisation / sentinel test per two symbols (block_paired).  A pair whose new range has a zero high word leaves through its
 trampoline, which renormalises in place or restores the conventions of the 3-copy loop (i, v50, range registers) and continues
 in that loop's handler.
-    python tools/gen_decoder_block.py"""
+
+Table rows: a block keeps its rows in two VGPR quads that alternate every two symbols (QUADS).  An even symbol j asks for rows
+j + 2 and j + 3 with ONE ds_read2st64_b64 (offsets in units of 64 x 8 B = one row of the table: no further base registers) into the
+other quad and waits once for rows j and j + 1; an odd symbol carries neither a read nor a wait.  The s_waitcnt counts are
+derived from the LDS operations the block itself has issued (class InFlight), not written down.
+    python tools/gen_decoder_block.py                      the four files of the kernel
+    python tools/gen_decoder_block.py --single-rows --out DIR
+                                                           the earlier form (one ds_read_b64 + one wait per symbol), for
+                                                           tools/ubench/dcycle.hip"""
+import sys
 from pathlib import Path
 
 PAIRS = [("v40", "v41", "v[46:47]"), ("v42", "v43", "v[40:41]"), ("v46", "v47", "v[42:43]")]  # (L, P) of the current row, where row j + 2 goes
+
+
+QUADS = [("v40", "v41", "v42", "v43"), ("v58", "v59", "v60", "v61")]   # (L, P) of an even symbol and of the odd one behind it
+LOOP_ROWS = ["v[40:41]", "v[42:43]", "v[46:47]"]                        # the current row of copy 0 / 1 / 2 of the 3-copy loop
+ROWS2 = True     # False: one ds_read_b64 and one wait per symbol (PAIRS)
+
+
+class InFlight:
+    """The LDS operations a block has issued, oldest first (LDS answers a wave in order): wait(tag) is the s_waitcnt that
+    guarantees the operation `tag` and lets everything issued behind it stay in flight."""
+    def __init__(self):
+        self.ops = ["rows0"]   # the look in front of the block asked for rows 0 / 1 last
+
+    def issue(self, tag):
+        self.ops.append(tag)
+
+    def wait(self, tag):
+        return "s_waitcnt lgkmcnt(%d)" % (len(self.ops) - 1 - self.ops.index(tag))
 
 
 def q(s):
@@ -38,13 +65,16 @@ def block_paired(n, tramp0, label0=300, lane0=0, part=False, cont=False, chain=N
     part's first row); it ends in the loop's part-end handler (2:) like a part that ran through the 3-copy loop.
     chain (r06, 4-symbol parts): label of the NEXT part's block.  The part asks for the slot's ready word two symbols before its end;
     behind its last symbol it publishes itself and, if the next part's bit is set, goes straight on in that part's block (rows
-    4 / 5 of this block are that part's first two: moved to where its block expects them) - ~28 instructions between two parts
+    4 / 5 of this block are that part's first two: with paired reads they arrive in the quad its block starts with) - ~28 instructions between two parts
     instead of the part-end handler + a look at the ready word + the dispatch (~45 instructions, an LDS round trip, four taken
     branches: ~480 ticks per part measured with 4-pixel tasks on a half-size grid, profiles/r06/prof_grids_t8_40.txt)."""
     assert n % 2 == 0
     out = []
+    fl = InFlight()
     for j in range(n):
         cur_l, cur_p, nxt = PAIRS[j % 3]
+        if ROWS2:
+            cur_l, cur_p = QUADS[j // 2 % 2][2 * (j % 2):2 * (j % 2) + 2]
         rcur, rnew = RP[j % 3], RP[(j + 1) % 3]
         dcur, dnew = DP[j % 2], DP[(j + 1) % 2]
         lp_lo, lp_hi, lane = HS[j % 2]
@@ -52,13 +82,21 @@ def block_paired(n, tramp0, label0=300, lane0=0, part=False, cont=False, chain=N
         if part and (cont or chain) and j == n - 2:
             # first part of a batch: ask for the slot's ready word now - behind the block it says whether the second part is there
             out.append(q("ds_read_b32 v54, v51"))
+            fl.issue("rdy")
         wait = "s_waitcnt lgkmcnt(2)"
         if part and (cont or chain) and j >= n - 2:
             wait = "s_waitcnt lgkmcnt(3)"
-        out += [q("s_lshr_b64 s[40:41], %s, 24" % pair(rcur)),
-                q("ds_read_b64 %s, v50 offset:%d" % (nxt, 512 * (j + 2))),
-                q(wait),
-                q("v_mad_u64_u32 v[44:45], s[42:43], s40, %s, 0" % cur_l),
+        out.append(q("s_lshr_b64 s[40:41], %s, 24" % pair(rcur)))
+        if not ROWS2:
+            out += [q("ds_read_b64 %s, v50 offset:%d" % (nxt, 512 * (j + 2))), q(wait)]
+        elif j % 2 == 0:
+            # rows n / n + 1 are wanted only where the block goes straight on in another one (cont, chain)
+            if j + 2 < n or (part and (cont or chain)):
+                to = QUADS[(j // 2 + 1) % 2]
+                out.append(q("ds_read2st64_b64 v[%s:%s], v50 offset0:%d offset1:%d" % (to[0][1:], to[3][1:], j + 2, j + 3)))
+                fl.issue("rows%d" % (j + 2))
+            out.append(q(fl.wait("rows%d" % j)))
+        out += [q("v_mad_u64_u32 v[44:45], s[42:43], s40, %s, 0" % cur_l),
                 q("v_mad_u32_u24 v45, %s, s41, v45" % cur_l),
                 q("v_cmpx_ge_u64 vcc, %s, v[44:45]" % pair(dcur)),
                 q("v_mad_u64_u32 v[48:49], s[42:43], s40, %s, 0" % cur_p),
@@ -84,11 +122,13 @@ def block_paired(n, tramp0, label0=300, lane0=0, part=False, cont=False, chain=N
         # points at the batch's first symbol, as that block expects) and leave through the full batch's epilogue: a batch taken in
         # two parts then costs ~15 instructions more than one taken whole, not a polling round trip and two part hand-overs.
         assert n == 8 and RP[n % 3] == RP[8 % 3] and DP[n % 2] == DP[0]
+        fl.issue("ring"), fl.issue("pixels")
+        rdy_wait = fl.wait("rdy") if ROWS2 else "s_waitcnt lgkmcnt(4)"
         out += [q("s_mov_b64 exec, 0xff"), q("v_sub_u32 v52, %[top], %[raw]"), q("v_add_u32 v52, 1, v52"), q("ds_write_b8 %[ring], v52"),
                 q("global_store_byte %[goff], v52, %[lat]"), q("s_mov_b64 exec, -1"),
                 q("s_add_u32 s58, %[pix0], %[i]"), q("s_add_u32 s58, s58, 8"), q("v_mov_b32 v56, s58"), q("ds_write_b32 %[rdy], v56 offset:68"),
                 q("s_sub_u32 s59, s66, %[i]"),
-                q("s_waitcnt lgkmcnt(4)"),          # (the ready word: in front of rows 8 and 9 and the two stores)
+                q(rdy_wait),                        # (the ready word: in front of rows 8 and 9 and the two stores)
                 q("v_readfirstlane_b32 s58, v54"),
                 q("s_cmp_eq_u32 s59, 16"), q("s_cbranch_scc0 %df" % (label0 + n + 1)),
                 q("s_bitcmp1_b32 s58, 1"), q("s_cbranch_scc0 %df" % (label0 + n + 1)),
@@ -99,19 +139,25 @@ def block_paired(n, tramp0, label0=300, lane0=0, part=False, cont=False, chain=N
     if part and chain:
         assert n == 4 and DP[n % 2] == DP[0] and lane0 in (0, 4, 8)
         nxt_bit = lane0 // 4 + 1
+        fl.issue("ring"), fl.issue("pixels")
+        rdy_wait = fl.wait("rdy") if ROWS2 else "s_waitcnt lgkmcnt(4)"
+        # rows 4 / 5 are the next part's first two.  Paired reads: they are in the quad its block starts with (n = 4), and its
+        # first symbol waits for them; single reads: moved to where its block expects them
+        assert not ROWS2 or QUADS[n // 2 % 2] == QUADS[0]
+        hand_rows = [] if ROWS2 else [
+            q("s_waitcnt lgkmcnt(2)"),          # rows 4 and 5
+            q("v_mov_b32 v40, v42"), q("v_mov_b32 v41, v43"), q("v_mov_b32 v42, v46"), q("v_mov_b32 v43, v47")]
         out += [q("s_mov_b64 exec, 0x%x" % (0xf << lane0)), q("v_sub_u32 v52, %[top], %[raw]"), q("v_add_u32 v52, 1, v52"), q("ds_write_b8 %[ring], v52"),
                 q("global_store_byte %[goff], v52, %[lat]"), q("s_mov_b64 exec, -1"),
                 q("s_add_u32 s58, %[pix0], %[i]"), q("s_add_u32 s58, s58, 4"), q("v_mov_b32 v56, s58"), q("ds_write_b32 %[rdy], v56 offset:68"),
                 q("s_add_u32 s59, %[i], 8"),
-                q("s_waitcnt lgkmcnt(4)"),          # (the ready word: in front of rows 4 and 5 and the two stores)
+                q(rdy_wait),                        # (the ready word: in front of rows 4 and 5 and the two stores)
                 q("v_readfirstlane_b32 s58, v54"),
                 q("s_cmp_le_u32 s59, s66"), q("s_cbranch_scc0 %df" % (label0 + n + 1)),      # a FULL part of this batch behind this one?
                 q("s_bitcmp1_b32 s58, %d" % nxt_bit), q("s_cbranch_scc0 %df" % (label0 + n + 1)),
                 # go on in the next part's block: range in s[52:53], its rows 0 / 1 in v[40:41] / v[42:43], v50 = its first row, the
                 # part's top symbols / ring cells / grid offsets read again (its producer has stored them by now)
-                q("s_mov_b64 s[52:53], %s" % pair(RP[n % 3])),
-                q("s_waitcnt lgkmcnt(2)"),          # rows 4 and 5
-                q("v_mov_b32 v40, v42"), q("v_mov_b32 v41, v43"), q("v_mov_b32 v42, v46"), q("v_mov_b32 v43, v47"),
+                q("s_mov_b64 s[52:53], %s" % pair(RP[n % 3]))] + hand_rows + [
                 q("v_add_u32 v50, 0x800, v50"),
                 q("ds_read_b32 %[top], v53"), q("ds_read_b32 %[ring], v53 offset:520"), q("ds_read_b32 %[goff], v53 offset:1040"),
                 q("s_add_u32 %[i], %[i], 4"), q("s_mov_b32 s67, %[i]"), q("s_add_u32 s54, %[i], 4"),
@@ -146,6 +192,12 @@ def loop_conventions(e):
         out.append(q("s_add_u32 %%[i], %%[i], %d" % e))
     if e // 3:
         out.append(q("v_add_u32 v50, 0x%x, v50" % (0x600 * (e // 3))))
+    if ROWS2:
+        # the loop's copy behind the handler finds row e + 1 in its own registers and expects row e + 2 in flight to the next
+        # copy's: asked for again (whatever the block still has in flight arrives first)
+        c = e % 3
+        out += [q("ds_read_b64 %s, v50 offset:%d" % (LOOP_ROWS[(c + 1) % 3], 512 * (c + 1))),
+                q("ds_read_b64 %s, v50 offset:%d" % (LOOP_ROWS[(c + 2) % 3], 512 * (c + 2)))]
     out.append(q("s_branch %db" % (40 + e % 3)))
     return out
 
@@ -198,7 +250,12 @@ def trampolines_paired(n, tramp0, label0=300):
 
 
 def main():
+    global ROWS2
+    argv = sys.argv[1:]
+    ROWS2 = "--single-rows" not in argv
     root = Path(__file__).resolve().parents[1] / "cool_chic_amd" / "csrc"
+    if "--out" in argv:
+        root = Path(argv[argv.index("--out") + 1])
     head = "/* Generated by tools/gen_decoder_block.py - do not edit. */\n"
     (root / "ccd_dec_block16p.inc").write_text(head + "\n".join(block_paired(16, 201)) + "\n")
     # the two 8-symbol parts of a 16-pixel batch that is decoded part by part (each with its trampolines behind it)

@@ -5,12 +5,25 @@
 // waves that keep the LDS busy?
 //   V = 0: block + the least a loop needs (two row reads, compare, branch)      V = 1: + publication      V = 2: the production cycle
 //     hipcc --offload-arch=gfx950 -O3 -I../../cool_chic_amd/csrc [-DVARIANT=V, default 2] -o dcycle dcycle.hip && ./dcycle
+// The block of the kernel asks for its table rows two per LDS read.  The earlier form (one ds_read_b64 and one wait per
+// symbol) for comparison:
+//     python ../gen_decoder_block.py --single-rows --out old && hipcc ... -DSINGLE_ROWS -Iold -I../../cool_chic_amd/csrc ...
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 
 #ifndef VARIANT
 #define VARIANT 2
+#endif
+// rows 0 / 1 of the next batch, and the wait that guarantees the ready word read in front of the top symbols and of them
+#ifdef SINGLE_ROWS
+#define ROWS01 "ds_read_b64 v[40:41], v50\n\t" "ds_read_b64 v[42:43], v50 offset:512\n\t"
+#define LOOK_WAIT "s_waitcnt lgkmcnt(3)\n\t"
+#define FORM "single row reads"
+#else
+#define ROWS01 "ds_read2st64_b64 v[40:43], v50 offset1:1\n\t"
+#define LOOK_WAIT "s_waitcnt lgkmcnt(2)\n\t"
+#define FORM "paired row reads"
 #endif
 
 template <int V>
@@ -53,8 +66,7 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             "v_lshl_add_u32 v53, s56, 2, %[l4]\n\t"
             "ds_read_b32 %[top], v53\n\t"
             "v_lshl_add_u32 v50, s56, 9, %[tabl]\n\t"
-            "ds_read_b64 v[40:41], v50\n\t"
-            "ds_read_b64 v[42:43], v50 offset:512\n\t"
+            ROWS01
             ".p2align 6\n\t"
             "80:\n\t"
 #include "ccd_dec_block16p.inc"
@@ -84,15 +96,14 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             "v_lshl_add_u32 v53, s56, 2, %[l4]\n\t"
             "ds_read_b32 %[top], v53\n\t"
             "v_lshl_add_u32 v50, s56, 9, %[tabl]\n\t"
-            "ds_read_b64 v[40:41], v50\n\t"
-            "ds_read_b64 v[42:43], v50 offset:512\n\t"
+            ROWS01
             "s_add_u32 s54, %[i], s69\n\t"
             "s_cmp_le_u32 s54, s72\n\t"
             "s_cbranch_scc0 25f\n\t"
             "v_add_u32 %[ring], s71, %[ring]\n\t"
             "v_and_b32 %[ring], %[rmask], %[ring]\n\t"
             "v_add_u32 %[goff], %[gstride], %[goff]\n\t"
-            "s_waitcnt lgkmcnt(3)\n\t"
+            LOOK_WAIT
             "v_readfirstlane_b32 s59, v54\n\t"
             "s_cmp_eq_u32 s59, s73\n\t"
             "s_cbranch_scc1 80b\n\t"
@@ -101,8 +112,7 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             "s_and_b32 s55, %[seq], %[smask]\n\t"
             "s_lshl_b32 s56, s55, 4\n\t"
             "v_lshl_add_u32 v50, s56, 9, %[tabl]\n\t"
-            "ds_read_b64 v[40:41], v50\n\t"
-            "ds_read_b64 v[42:43], v50 offset:512\n\t"
+            ROWS01
             "s_cmp_lt_u32 %[i], %[n]\n\t"
             "s_cbranch_scc1 80b\n\t"
 #endif
@@ -123,7 +133,7 @@ __global__ __launch_bounds__(512) void dcycle(uint64_t* out, int n_batches, int 
             : [n] "s"(n), [smask] "s"(7u), [rdy] "v"(rdy), [zero] "v"(0u), [three] "v"(3u), [rmask] "s"(511u * 64u + 63u), [gstride] "s"(64u),
               [tabl] "v"(tabl), [l4] "v"(l4), [lat] "s"(lat_addr), [pix0] "s"(pix0), [wbase] "s"(2u), [wbuf] "v"(static_cast<uint32_t>(lane * 2654435761u))
             : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58",
-              "s59", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v56", "v57");
+              "s59", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v56", "v57", "v58", "v59", "v60", "v61");
         const uint64_t t1 = __builtin_amdgcn_s_memtime();
         if (lane == 0) { out[0] = t1 - t0; out[1] = rc_range; out[2] = status; out[3] = i; out[4] = rc_dist; }
         *reinterpret_cast<volatile int*>(&junk[0]) = 0x7fffffff;  // tell the busy waves to stop
@@ -155,7 +165,7 @@ int main() {
             hipDeviceSynchronize();
         }
         hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-        printf("variant %d%s, %s: %.1f ticks per 16-symbol batch = %.1f / symbol   (status %llu, symbols %llu, range %016llx, dist %016llx)\n",
+        printf(FORM ", variant %d%s, %s: %.1f ticks per 16-symbol batch = %.1f / symbol   (status %llu, symbols %llu, range %016llx, dist %016llx)\n",
                VARIANT,
 #ifdef NO_GLOBAL_STORE
                " (no global store)",
