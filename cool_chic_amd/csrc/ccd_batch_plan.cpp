@@ -104,13 +104,9 @@ int choose_entropy_kernel(const ccd_batch* b, Slot& s, SlotPlan& p) {
     int max_w = 0;
     for (int g = 0; g < h.n_grids; ++g) max_w = std::max(max_w, static_cast<int>(h.grid_w[g]));
     s.use_pipe = !b->force_generic && entropy_pipe_supports(h.total_context_arm, h.n_hidden_layers_arm + 1, (net.arm.w32 && net.feat_i32 && !net.arm.dyn_act) ? 1 : 0, max_w);
-    {
-        long long max_w_abs = 0;
-        for (const FixedLayer& L : net.arm.layers) for (int64_t w : L.w) max_w_abs = std::max<long long>(max_w_abs, w < 0 ? -w : w);
-        for (int64_t w : net.arm.ws) max_w_abs = std::max<long long>(max_w_abs, w < 0 ? -w : w);
-        s.use_mfma = s.use_pipe && b->opt_mfma_arm &&
-                     entropy_pipe_supports_mfma(h.total_context_arm, h.n_hidden_layers_arm + 1, h.output_feature_ifce, net.arm.narrow ? 1 : 0, max_w, max_w_abs);
-    }
+    s.use_mfma = s.use_pipe && b->opt_mfma_arm &&
+                 entropy_pipe_supports_mfma(h.total_context_arm, h.n_hidden_layers_arm + 1, h.output_feature_ifce, net.arm.narrow ? 1 : 0, max_w,
+                                            arm_max_abs_weight(net.arm), worst_feature_bound(net));
     s.use_dyn = s.use_pipe && !s.use_mfma && (net.arm.dyn_feat || b->opt_range_bits != 0);
     s.fixed_shape = (s.use_pipe && !s.use_mfma && b->opt_fixed_shape) ? entropy_pipe_fixed_shape(h.total_context_arm, h.n_hidden_layers_arm + 1, h.spatial_context_arm) : 0;
     s.ring_rows = s.use_mfma ? std::max(entropy_pipe_ring_rows(max_w), 64) : 512;  // the matrix-core variant needs the LDS for its operand tables

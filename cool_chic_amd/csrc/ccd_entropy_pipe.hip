@@ -973,11 +973,14 @@ __device__ __forceinline__ void mad64_seq(int64_t& acc, int32_t x, int32_t w) {
 // shift-adds, so the result is the int64 sum of armint.py:180-203 exactly.  Lane l = 16 g + n holds pixel n; the accumulator
 // of rows 4 g + r lands in lane group g, register r - which is where the next layer's B operand wants it when tile 1 puts
 // neurons 16..19 at rows 0, 4, 8, 12: no cross-lane movement between layers.  Envelope (host: ccd_batch_plan.cpp): `narrow`
-// (so |IFCE feature| < 2^15: two bytes), dim <= 20, <= 8 IFCE features, |weight| < 2^23 (three bytes).  Hidden activations
-// travel as three bytes; a task that meets one >= 2^23 (128.0 in Q16; never seen on real streams; EntropyParams::mfma holds
-// the exponent so that tests can lower it) is redone
+// and a worst-case IFCE feature <= 0x7F7F (two signed digits end there, not at 2^15 - 1), dim <= 20, <= 8 IFCE features,
+// |weight| <= 0x7F7F7F (three signed digits end there, not at 2^23 - 1).  Hidden activations travel as three digits; a task
+// that meets one above 0x7F7F7F (127.5 in Q16; no real stream has one - the crafted networks of tests/arm_envelope.py do,
+// test_matrix_core_cases; EntropyParams::mfma holds an exponent so that tests can lower the limit further) is redone
 // by mf_exact_task in plain int64.  tools/ubench/arm_mfma.hip is the stand-alone version of this scheme.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+constexpr long long kMfMaxDigits3 = 0x7F7F7F;  // largest value of three signed-digit bytes (the smallest is -0x808080)
+constexpr long long kMfMaxDigits2 = 0x7F7F;    // of two
 constexpr int kMfLayer1 = 8;    // A operands of the first layer: 2 tiles x 4 byte sums (tile 1 also holds the stabiliser rows 1, 2)
 constexpr int kMfHidden = 10;   // per further hidden layer: 2 tiles x 5 byte sums
 constexpr int kMfOut = 5;       // output layer: rows 0 (mu), 1 (log-scale)
@@ -1119,8 +1122,9 @@ __device__ __forceinline__ void mf_exact_task(const PipeCtx& C, int32_t* tile, i
 // network exceeds 2^15 (three of the six networks the reference encoder produced in the build container), its features
 // reach ~2^10: a feature with |f| >= 2^feat_bits is a sentinel in the int16 plane and its value sits in the int32 side
 // plane; a task learns of a sentinel when it loads its features, before it waits for anything, and a pixel that met one
-// is redone here in plain 64 x 64 -> 64 arithmetic.  Never taken on the streams seen so far; tests lower feat_bits to
-// drive ordinary streams through it (EntropyParams::feat_bits).
+// is redone here in plain 64 x 64 -> 64 arithmetic.  No stream of the reference encoder takes it; the crafted networks of
+// tests/arm_envelope.py do at the default limit (feat_dyn, feat_side_plane, ifce_w_*: test_every_case_on_the_production_path),
+// and tests lower feat_bits to drive ordinary streams through it (EntropyParams::feat_bits).
 constexpr int16_t kFeatSentinel = -32768;
 
 // One pixel's ARM in plain wrapping int64, the whole wave on it: lane k holds input / activation k (dim <= 32), lane o
@@ -1578,13 +1582,14 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                     clk.d = LPROF_T(pw == 0);
                     const unsigned long long t_h = PROF_T();
                     int32_t av[5];
-                    uint32_t big = 0;  // OR of every hidden activation of the lane (they are >= 0)
+                    uint32_t big = 0;   // OR of every hidden activation of the lane (they are >= 0)
+                    uint32_t over = 0;  // OR of (activation + 0x808080): bits from 24 up <=> an activation in 0x7F7F80 .. 2^23 - 1 (or beyond)
 #pragma unroll
                     for (int r = 0; r < 5; ++r) {
                         mad64(pre[r], xleft, mf_wl[r]);
                         const int64_t a = pre[r] < 0 ? 0 : pre[r];
                         av[r] = static_cast<int32_t>(a >> 16);
-                        big |= static_cast<uint32_t>(av[r]);
+                        big |= static_cast<uint32_t>(av[r]); over |= static_cast<uint32_t>(av[r]) + 0x00808080u;
                     }
                     mad64(st0, xleft, mf_wl[5]);
                     mad64(st1, xleft, mf_wl[6]);
@@ -1602,13 +1607,13 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         for (int r = 0; r < 4; ++r) {
                             const int64_t a = mf_comb5(c2, r, b_h[r]);
                             av[r] = static_cast<int32_t>((a < 0 ? 0 : a) >> 16);
-                            big |= static_cast<uint32_t>(av[r]);
+                            big |= static_cast<uint32_t>(av[r]); over |= static_cast<uint32_t>(av[r]) + 0x00808080u;
                         }
                         av[4] = 0;
                         if (dim > 16) {
                             const int64_t a = mf_comb5(c2b, 0, b_h[4]);
                             av[4] = static_cast<int32_t>((a < 0 ? 0 : a) >> 16);
-                            big |= static_cast<uint32_t>(av[4]);
+                            big |= static_cast<uint32_t>(av[4]); over |= static_cast<uint32_t>(av[4]) + 0x00808080u;
                         }
                         if (l + 1 < n_layers - 1) {  // deeper networks: operands of the next hidden layer
                             const i32x4* sl = sa + (kMfLayer1 + l * kMfHidden) * 64;
@@ -1634,9 +1639,11 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                         out_mu = mf_comb5(c3, 0, b_mu) + st0;
                         out_ls = mf_comb5(c3, 1, b_ls) + st1;
                     }
-                    // an activation outside the 3-byte range anywhere in the task: redo the task in plain int64
-                    if (__ballot((big >> mf_bits) != 0u) != 0ull) {
+                    // an activation outside the three signed digits (above 0x7F7F7F: `over` carries into bit 24), or outside the
+                    // lowered limit of a test, anywhere in the task: redo the task in plain int64
+                    if (__ballot(((big >> mf_bits) | (over >> 24)) != 0u) != 0ull) {
                         if (g == 0 && live) mf_exact_task<NV>(C, act, n, y, x, W, fin, fw, feat_plane, ring_mask, out_mu, out_ls);
+                        if (lane == 0) atomicAdd(reinterpret_cast<int*>(P.status) + 39, 1);  // status[39]: tasks redone (tests)
                     }
                     const int64_t m8 = (out_mu >> 24) + kMuOffset, s8 = (out_ls >> 24) + kScaleOffset;
                     const int32_t idx_mu = static_cast<int32_t>(m8 < 0 ? 0 : (m8 > kNumMu - 1 ? kNumMu - 1 : m8));
@@ -1954,7 +1961,7 @@ __device__ __forceinline__ uint32_t producer_grid(const PipeCtx& C_run, unsigned
                 idx_mu = table_index(out_m, kMuOffset, kNumMu - 1);
                 idx_sc = table_index(out_l, kScaleOffset, kNumScale - 1);
                 own_rcp = C.s_rcp[idx_sc];  // the one LDS trip between the output layer and the first f64 multiply
-                // ---- a feature of some pixel was not exact in 16 bits (never on the streams seen so far): that pixel again,
+                // ---- a feature of some pixel was not exact in 16 bits (tests/test_arm_envelope.py; no trained network): that pixel again,
                 // in plain int64; its table parameters replace what the lines above wrote from the sentinel
                 if (DYN && __builtin_expect(bad_lanes != 0ull, 0)) {
                     int n_redo = 0;
@@ -2499,11 +2506,15 @@ bool entropy_pipe_supports(int dim, int n_layers, int operands_ok, int max_grid_
 }
 
 // The matrix-core evaluation of the ARM (see the MF notes above producer_grid); max_abs_weight over every ARM layer
-// and the stabiliser.
-bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narrow, int max_grid_w, long long max_abs_weight) {
+// and the stabiliser, max_feature_bound = the worst case of an IFCE feature (ccd::worst_feature_bound: a feature lies in
+// [-bound, bound - 1]).  The limits are those of the signed digits, not of the bit width: three digits hold
+// -0x808080 .. 0x7F7F7F and two hold -0x8080 .. 0x7F7F = 32 639 (tests/test_arm_envelope.py sits on both).
+bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narrow, int max_grid_w, long long max_abs_weight,
+                                long long max_feature_bound) {
     const int ring = entropy_pipe_ring_rows(max_grid_w);
     return narrow && ring > 0 && dim <= 20 && n_layers >= 2 && n_layers <= 8 && n_ifce_out <= 8 &&
-           max_abs_weight < (1ll << 23) && entropy_pipe_lds_bytes(dim, n_layers, ring, 1) <= 160 * 1024;
+           max_abs_weight <= kMfMaxDigits3 && max_feature_bound <= kMfMaxDigits2 + 1 &&
+           entropy_pipe_lds_bytes(dim, n_layers, ring, 1) <= 160 * 1024;
 }
 
 // ---- debug: every left cumulative the producers can compute for a run of scale indices -------------------------------

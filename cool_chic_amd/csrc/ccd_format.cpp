@@ -521,6 +521,19 @@ int decode_network(const ccd_cc_header& h, const uint8_t* bytes_nn, size_t n_nn,
     return CCD_OK;
 }
 
+long long arm_max_abs_weight(const FixedArm& arm) {
+    u128 m = 0;
+    for (const FixedLayer& L : arm.layers) for (int64_t w : L.w) m = std::max(m, mag(w));
+    for (int64_t w : arm.ws) m = std::max(m, mag(w));
+    return static_cast<long long>(std::min(m, static_cast<u128>(INT64_MAX)));
+}
+
+long long worst_feature_bound(const Network& net) {
+    int64_t m = 0;
+    for (int64_t b : net.ifce_feat_bound) m = std::max(m, b);
+    return m;
+}
+
 bool float_path_stays_finite(const Network& net, int n_levels, int noise) {
     const double kLimit = std::ldexp(1.0, 120);  // FLT_MAX ~ 2^128: a partial sum of two bounded terms stays finite too
     auto abs_sum = [](const float* w, size_t n) { double s = 0; for (size_t i = 0; i < n; ++i) s += std::fabs(static_cast<double>(w[i])); return s; };

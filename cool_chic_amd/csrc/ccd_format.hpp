@@ -112,6 +112,11 @@ int decode_exp_golomb(const uint8_t* p, size_t n, int n_pad_bits, const std::vec
 // Number of transmitted integers per (module, weight|bias) group, stream order (types.py:18-19,98-101).
 int network_layout(const ccd_cc_header& h, size_t n_kind[8]);
 int decode_network(const ccd_cc_header& h, const uint8_t* bytes_nn, size_t n_nn, Network& net);
+// Largest magnitude of any ARM weight, stabiliser included (fixed point; saturates at INT64_MAX), and the largest of
+// Network::ifce_feat_bound: what the matrix-core decision of the entropy kernel is taken on (entropy_pipe_supports_mfma),
+// by the batch and by ccd_network_kernel_class alike.
+long long arm_max_abs_weight(const FixedArm& arm);
+long long worst_feature_bound(const Network& net);
 
 // Context template: (dy, dx) of the n highest-priority causal neighbours, component/core/arm.py:493-562.
 // The neighbour of (y, x) is (y - dy, x + dx) with dy in 0..4, dx in -4..4.

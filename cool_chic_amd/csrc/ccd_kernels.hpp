@@ -19,7 +19,8 @@ hipError_t launch_laplace_sweep_generic(const float* scale_table, int scale_firs
 // ccd_entropy_pipe.hip
 size_t entropy_pipe_lds_bytes(int dim, int n_layers, int ring_rows, int mfma);
 int entropy_pipe_ring_rows(int max_grid_w);
-bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narrow, int max_grid_w, long long max_abs_weight);
+bool entropy_pipe_supports_mfma(int dim, int n_layers, int n_ifce_out, int narrow, int max_grid_w, long long max_abs_weight,
+                                long long max_feature_bound);
 bool entropy_pipe_supports(int dim, int n_layers, int narrow, int max_grid_w);
 hipError_t launch_entropy_pipe(const EntropyParams* d_slots, int n_slots, int nv, int mfma, int dyn, int shape, size_t lds_bytes, hipStream_t stream);
 int entropy_pipe_fixed_shape(int dim, int n_layers, int n_spatial);

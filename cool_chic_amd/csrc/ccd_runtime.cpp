@@ -242,8 +242,11 @@ int ccd_network_kernel_class(const uint8_t* cc_header, size_t n_hdr, const uint8
     int n_levels = 0;
     for (int g = 0; g < h->n_grids; ++g) n_levels += h->is_hyperlatent[g] ? 0 : 1;
     const bool finite = float_path_stays_finite(net, n_levels, h->flag_common_randomness ? n_levels : 0);
+    const bool mfma = pipe && entropy_pipe_supports_mfma(h->total_context_arm, h->n_hidden_layers_arm + 1, h->output_feature_ifce, net.arm.narrow ? 1 : 0,
+                                                         max_w, arm_max_abs_weight(net.arm), worst_feature_bound(net));
     return (pipe ? 1 : 0) | (pipe && net.arm.dyn_feat ? 16 : 0) | (finite ? 0 : 128) | (((h->total_context_arm + 3) / 4 & 15) << 8) |
-           (((h->n_hidden_layers_arm + 1) & 15) << 12);
+           (((h->n_hidden_layers_arm + 1) & 15) << 12) | (net.arm.narrow ? 1 << 16 : 0) | (net.ifce_w32 ? 1 << 17 : 0) | (mfma ? 1 << 18 : 0) |
+           (net.arm.w32 ? 1 << 19 : 0) | (net.arm.dyn_act ? 1 << 20 : 0) | (net.feat_i32 ? 1 << 21 : 0) | (net.arm.dyn_feat ? 1 << 22 : 0);
 }
 
 int ccd_debug_fd_profile(uint64_t* out16, int reset) {

@@ -181,7 +181,7 @@ int ccd_batch_slot_status(const ccd_batch* b, int slot);
 /* Raw per-slot counters of the entropy kernel after ccd_batch_wait: [0] status, [1] payload words read,
  * [2..3] symbols decoded (lo, hi); [36] latent grids whose body the pipelined kernel decoded as one stream of pixels
  * (batches cut without regard to wavefront steps: DESIGN.md 4.1); [37] batches its decoder took part by part; [39] pixels it
- * redid in int64 (dynamic operand check); [62] symbols that left the decoder's common path (window misses, sentinels), [63] of
+ * redid in int64 (dynamic operand check; with CCD_OPT_MFMA_ARM: 8-pixel tasks redone for an activation beyond three digits); [62] symbols that left the decoder's common path (window misses, sentinels), [63] of
  * which took the full 128-way search (pipelined kernel); the other words [4..61] are profiling cycle counters when built with
  * -DCCD_PIPE_PROFILE (which also reuses [36] and [37]).
  * `out64` receives 64 words. */
@@ -236,11 +236,12 @@ int ccd_batch_slot_kernels(const ccd_batch* b, int slot);
  *   CCD_OPT_KEEP_FLOAT  1 (default): the f32 synthesis output is always written (ccd_batch_output);
  *                       0: slots that produce integer planes directly (rgb / yuv444 intra frames) write only those.
  *   CCD_OPT_MFMA_ARM    0 (default): the integer ARM on the vector ALU; 1: streams inside the envelope (<= 20 ARM inputs,
- *                       <= 8 IFCE features, |weight| < 2^23, widest grid <= 2 500) evaluate it with
- *                       v_mfma_i32_16x16x64_i8 (exact limb-split int8).  Results are identical bit for bit either way; on
- *                       MI355X the matrix-core variant is the slower one, it is kept as a measured
- *                       alternative.  Values 2..22 lower the activation width above which a task is redone in plain
- *                       int64 - normally 23 bits - so that tests reach that path.
+ *                       <= 8 IFCE features, |weight| <= 0x7F7F7F, worst-case IFCE feature <= 0x7F7F, widest grid <= 2 500)
+ *                       evaluate it with v_mfma_i32_16x16x64_i8 (exact: operands split into signed-digit bytes, three per
+ *                       weight and activation, two per feature - hence the limits).  Results are identical bit for bit
+ *                       either way; on MI355X the matrix-core variant is the slower one, it is kept as a
+ *                       measured alternative.  A task that meets a hidden activation above 0x7F7F7F is redone in plain
+ *                       int64; values 2..22 lower that limit to 2^value so that tests reach the redo with ordinary streams.
  *   CCD_OPT_RANGE_BITS  0 (default): production limit of the pipelined entropy kernel's dynamic operand check (an IFCE feature
  *                       with |f| >= 2^15 sends its pixel through the int64 redo).  Tests pass 8..14 to lower the limit and
  *                       drive ordinary streams through the redo; results are identical bit for bit.
@@ -897,15 +898,21 @@ int ccd_debug_laplace_sweep(int device, int which, int scale_first, int n_scales
 /* Host only: 1 when this cool-chic's ARM runs on the pipelined entropy kernel: every ARM / stabiliser weight fits int32, no
  * hidden activation can leave int32 even for worst-case inputs, the worst-case IFCE feature fits the kernel's int32 side
  * plane (< 2^30), <= 32 ARM inputs, <= 8 layers, picture not wider than the symbol ring (5 060).  What depends on the data -
- * IFCE features as 16-bit operands - is checked per task on the device and the pixel redone in plain int64 (never taken on
- * any stream seen so far).  0 when it needs the generic 64-bit kernel (~7x slower; no network the reference encoder produced
+ * IFCE features as 16-bit operands - is checked per task on the device and the pixel redone in plain int64 (no trained
+ * network takes it; tests/test_arm_envelope.py does).  0 when it needs the generic 64-bit kernel (~7x slower; no network the reference encoder produced
  * does), < 0 on a malformed header / payload. */
 int ccd_network_fits_fast_path(const uint8_t* cc_header, size_t n_hdr, const uint8_t* bytes_nn, size_t n_nn);
 /* Host only: WHICH entropy-kernel instantiation a batch with default options gives this cool-chic (tests and DESIGN.md's
  * instantiation table): bit 0 = pipelined kernel (else the generic one), bit 4 = its instantiation with the device check of the
  * IFCE features (worst-case feature >= 2^15), bit 7 = the network is outside the finite envelope of the float stages (vector-ALU
  * float kernels only), bits 8..11 = NV = ceil(ARM inputs / 4), bits 12..15 = ARM layers (hidden + output).
- * Same bits 0, 4 and 7 as ccd_batch_slot_kernels.  < 0 on a malformed header / payload. */
+ * Same bits 0, 4 and 7 as ccd_batch_slot_kernels.  Above them the decisions behind the choice, one bit each (the network's own
+ * flags, whatever bit 0 says): bit 16 = `narrow` (32-bit operands and accumulators below 2^62 guaranteed: the generic kernel's
+ * 32-bit form, and a condition of the matrix cores), bit 17 = every IFCE weight fits int32 (the register-resident feature
+ * pass), bit 18 = a batch with CCD_OPT_MFMA_ARM = 1 runs this ARM on the matrix cores (ccd_batch_slot_kernels bit 3), bit 19 =
+ * every ARM / stabiliser weight fits int32, bit 20 = a hidden activation could leave int32, bit 21 = the worst-case IFCE
+ * feature is below 2^30, bit 22 = it is 2^15 or more (bit 4 without the "pipelined" condition).
+ * < 0 on a malformed header / payload. */
 int ccd_network_kernel_class(const uint8_t* cc_header, size_t n_hdr, const uint8_t* bytes_nn, size_t n_nn);
 
 /* Profile builds only (-DCCD_FD_PROFILE): cycles per phase of the fused float kernel, summed over wave 0 of every

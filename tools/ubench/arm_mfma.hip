@@ -23,7 +23,7 @@ struct Net {  // fixed-point parameters as the decoder sees them (int32 operands
 };
 
 // ---- host reference: armint.py:180-203 in int64 ----
-static int64_t g_max_act = 0;  // the scheme carries activations as 3 signed-digit bytes: |act| < 2^23 (128.0 in Q16)
+static int64_t g_max_act = 0;  // the scheme carries activations as 3 signed-digit bytes: act <= 0x7F7F7F (127.5 in Q16)
 static void ref_arm(const Net& n, const int32_t* v /*[DIM] raw inputs*/, int64_t out[2]) {
     int64_t x[DIM], y[DIM], stab[2];
     for (int i = 0; i < DIM; ++i) x[i] = (int64_t)v[i] << 16;
@@ -35,7 +35,7 @@ static void ref_arm(const Net& n, const int32_t* v /*[DIM] raw inputs*/, int64_t
     for (int o = 0; o < 2; ++o) { int64_t a = n.b3[o]; for (int i = 0; i < DIM; ++i) a += x[i] * n.w3[i][o]; out[o] = (a + stab[o]) >> 24; }
 }
 
-static inline int limb(int32_t w, int j) {  // signed-digit byte j of w, |w| < 2^23
+static inline int limb(int32_t w, int j) {  // signed-digit byte j of w, -0x808080 <= w <= 0x7F7F7F
     if (j < 0 || j > 2) return 0;
     const uint32_t d = ((uint32_t)w + 0x00808080u) ^ 0x00808080u;
     return (int8_t)(d >> (8 * j));
