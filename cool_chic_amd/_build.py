@@ -5,7 +5,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["ccd_format.cpp", "ccd_writer.cpp", "ccd_runtime.cpp", "ccd_batch_plan.cpp", "ccd_batch.cpp", "ccd_video.cpp", "ccd_enc_api.cpp", "ccd_quality_api.cpp", "ccd_dsens_api.cpp", "ccd_rdoq_api.cpp", "ccd_iscore_api.cpp", "ccd_entropy.hip", "ccd_entropy_pipe.hip", "ccd_float.hip", "ccd_synth_fused.hip", "ccd_fused.hip", "ccd_fused_pre.hip", "ccd_fused_cr.hip", "ccd_inter.hip", "ccd_png.hip", "ccd_rate.hip", "ccd_encode.hip", "ccd_quality.hip", "ccd_ingest.hip", "ccd_dsens.hip", "ccd_rdoq.hip"]
-HEADERS = ["ccd_format.hpp", "ccd_device.hpp", "ccd_host.hpp", "ccd_kernels.hpp", "ccd_laplace.hpp", "ccd_quality.hpp", "ccd_planes.hpp", "ccd_trig.hpp", "ccd_wavefront.hpp", "ccd_lattice.hpp", "ccd_iscore_plan.hpp", "ccd_ratedelta_plan.hpp", "ccd_fused_kernel.inc", "ccd_exp_table.inc", "ccd_dec_block16p.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "../../include/ccd.h", "../../include/ccd_scale_table.inc"]
+HEADERS = ["ccd_format.hpp", "ccd_device.hpp", "ccd_host.hpp", "ccd_kernels.hpp", "ccd_laplace.hpp", "ccd_quality.hpp", "ccd_planes.hpp", "ccd_trig.hpp", "ccd_wavefront.hpp", "ccd_lattice.hpp", "ccd_iscore_plan.hpp", "ccd_inter_job.hpp", "ccd_ratedelta_plan.hpp", "ccd_fused_kernel.inc", "ccd_exp_table.inc", "ccd_dec_block16p.inc", "ccd_dec_tramp16p.inc", "ccd_dec_parts8.inc", "ccd_dec_parts4.inc", "../../include/ccd.h", "../../include/ccd_scale_table.inc"]
 LIB = os.path.join(_HERE, "libccd.so")
 
 

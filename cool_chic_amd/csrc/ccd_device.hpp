@@ -174,18 +174,20 @@ struct DsensPass {
     int32_t upp, rows;       // bands per probe, luma rows per band
     int32_t empty;
 };
-// One slot of an inter candidate as dsens_inter_kernel sees it (ccd_inter.hip): the float outputs of the frame's
-// two cool-chics - one of them a slot of the handle's batch, the other the caller's partner - go through the reconstruction of
-// inter_recon_kernel and the integer step of planes_kernel into planes the handle owns.  A workgroup is 64 x 4 units, a unit one
+// ---- P / B frames reconstructed by units (ccd_inter.hip: dsens_inter_kernel, dsens_dep_kernel, inter_score_kernel; DESIGN.md
+// 4.15, 4.16, 4.19; filled on the host by ccd_inter_job.hpp) ----
+// One frame as the unit walk (di_unit) reconstructs it: the float outputs of the frame's two cool-chics go through the
+// reconstruction of inter_recon_kernel and the integer step of planes_kernel.  A workgroup is a tile of 64 x 4 units, a unit one
 // luma sample or, 4:2:0, one 2 x 2 luma quad and its chroma sample; the jobs of a launch share a prefix table of workgroups.
-struct DsensInterJob {
+// What becomes of a quantised sample is the kernel's: dsens_inter_kernel stores it to `plane`, the other two compare it with a source.
+struct InterUnitJob {
     const float* residue;    // [4 | 5][H][W]
     const float* motion;     // [2 | 4][H][W]
     const float* ref0;       // [3][H][W] f32, launch_planes_to_444 of the reference's planes
     const float* ref1;       // B frames
     float* w0;               // [3][H][W] the warped reference: written by mode 0 (null: not kept), read by mode 1
     float* w1;               // B frames
-    void* plane[3];          // u8 / u16 planes out
+    void* plane[3];          // u8 / u16 planes: written by dsens_inter_kernel, the base read by dsens_dep_kernel, else null
     int32_t mode;            // 0 base: warp and keep, 1 residue probe: the kept warps, 2 motion probe: warp
     int32_t frame_type, H, W, n_taps;
     int32_t gflow[4];
@@ -194,13 +196,14 @@ struct DsensInterJob {
     int32_t tiles_x;         // workgroups per row of workgroups
     float maxv;              // 2^bitdepth - 1
 };
-// One (candidate, dependent, probe slot) of a round as dsens_dep_kernel sees it (ccd_inter.hip).  `recon` is the
-// DEPENDENT frame as dsens_inter_kernel would reconstruct it (mode 2) with the candidate's probe planes, as f32, in place of
-// reference `which`; recon.plane are the dependent's BASE planes, which are only read here.  A unit whose windows into the
-// reference touch the region of exactly one member of the pass's lattice adds its squared-error change to that entry of `acc`;
-// one that touches several sets their bytes of `flag`.
+static_assert(sizeof(InterUnitJob) == 128, "InterUnitJob is a table entry: host and device agree on its layout");
+// One (candidate, dependent, probe slot) of a round as dsens_dep_kernel sees it.  `recon` is the DEPENDENT frame
+// (an InterUnitJob, mode 2) with the candidate's probe planes, as f32, in place of reference `which`; recon.plane are the
+// dependent's BASE planes, which are only read here.  A unit whose windows into the reference touch the region of exactly one
+// member of the pass's lattice adds its squared-error change to that entry of `acc`; one that touches several sets their bytes
+// of `flag`.
 struct DsensDepJob {
-    DsensInterJob recon;
+    InterUnitJob recon;
     const void* src[3];        // the dependent's source planes
     unsigned long long* acc;   // [2][h][w] of the grid: the dependent map while it is summed (two's complement)
     uint8_t* flag;             // [2][h][w]: 1 = a unit saw this entry together with another
@@ -210,18 +213,21 @@ struct DsensDepJob {
     int32_t stride, py, px;    // the pass's lattice
     LatticeAxis ay, ax;        // rows, columns
 };
-// One candidate of one P / B frame as inter_score_kernel sees it (ccd_inter.hip).  `recon` is the frame as
-// dsens_inter_kernel would reconstruct it (mode 0: the frame's base pair, which keeps the warps; 1: another residue output, which
-// reads them; 2: another motion output) - its planes are never stored, recon.plane stays null: the squared error of every sample
-// against `src` is summed instead, per plane, one partial per workgroup.
+// One candidate of one P / B frame as inter_score_kernel sees it.  `recon` is the frame (an InterUnitJob; mode 0:
+// the frame's base pair, 1: another residue output, 2: another motion output) - its planes are never stored, recon.plane stays
+// null: the squared error of every sample against `src` is summed instead, per plane, one partial per workgroup.
 struct InterScoreJob {
-    DsensInterJob recon;
+    InterUnitJob recon;
     const void* src[3];        // the frame's source planes
     uint32_t part_first;       // workgroup k of the job owns the partials [3 (part_first + k), 3 (part_first + k) + 3)
     uint32_t pad;
 };
 // The partials of one job as inter_score_final_kernel sums them: workgroups [first, first + count) of the partial array.
 struct InterScoreRange { uint32_t first, count; };
+// the frame of a job of any of the three kernels
+__host__ __device__ inline const InterUnitJob& unit_job(const InterUnitJob& J) { return J; }
+__host__ __device__ inline const InterUnitJob& unit_job(const DsensDepJob& D) { return D.recon; }
+__host__ __device__ inline const InterUnitJob& unit_job(const InterScoreJob& S) { return S.recon; }
 // One grid of a candidate with dependents as dsens_dep_final_kernel sees it (ccd_dsens.hip): entry e of [2][h][w] becomes INT64_MIN
 // where the move leaves the alphabet or the entry is flagged, and the flagged legal entries are counted.
 struct DsensDepGrid {

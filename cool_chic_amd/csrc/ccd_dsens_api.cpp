@@ -6,6 +6,7 @@
 #include <new>
 
 #include "ccd_host.hpp"
+#include "ccd_inter_job.hpp"
 #include "ccd_kernels.hpp"
 
 using namespace ccd;
@@ -130,22 +131,21 @@ struct Candidate {
         return dep_f32.as<float>() + static_cast<size_t>(k + 1) * 3 * hdr.img_size[0] * hdr.img_size[1];
     }
     const void* frame_plane(const ccd_dsens* d, int k, int p) const;
+    // the candidate's frame with the frame header of a P / B frame of its size: its own, or a dependent's
+    InterFrameDesc frame_desc(int frame_type, int warp_filter_size, const int32_t* global_flow) const {
+        return InterFrameDesc{hdr.img_size[0], hdr.img_size[1], bitdepth, frame_data_type, frame_type, warp_filter_size, global_flow};
+    }
     void drop() { priv.drop(); maps.drop(); inter_buf.drop(); dep_maps.drop(); dep_f32.drop(); for (auto& q : deps) q.buf.drop(); }
     int8_t* copy(int k, int g) const { return priv.as<int8_t>() + static_cast<size_t>(k) * copy_bytes + grid_off[g]; }
     int64_t* map(int g) const { return reinterpret_cast<int64_t*>(maps.as<char>() + map_off[g]); }
 };
 
-struct InterLaunch {  // one launch of dsens_inter_kernel: offsets into the tables block
-    size_t jobs = 0, prefix = 0;
-    int n_jobs = 0;
-    uint32_t n_blocks = 0;
-};
 struct Round {  // offsets into the tables block
     size_t segs = 0, seg_prefix = 0, passes = 0, unit_prefix = 0, probe_prefix = 0;
     int n_segs = 0, n_passes = 0;
     uint32_t n_blocks = 0, n_units = 0, n_probes = 0;
-    InterLaunch probes[2];  // by kernel instantiation: [0] run-time taps, [1] sinc-8
-    InterLaunch deps[2];    // dsens_dep_kernel, by the DEPENDENT's filter
+    JobLaunch probes[2];  // dsens_inter_kernel, by kernel instantiation: [0] run-time taps, [1] sinc-8
+    JobLaunch deps[2];    // dsens_dep_kernel, by the DEPENDENT's filter
 };
 }  // namespace
 
@@ -156,9 +156,9 @@ struct ccd_dsens {
     std::vector<Round> rounds;
     Mirror tables;
     Block slab;
-    InterLaunch inter_base[2];  // the base slots of the inter candidates, behind the first round's float path
-    InterLaunch dep_base[2];    // the base planes of the dependents, behind those
-    InterLaunch dep_final;      // dsens_dep_final_kernel over the grids of the candidates with dependents
+    JobLaunch inter_base[2];  // the base slots of the inter candidates, behind the first round's float path
+    JobLaunch dep_base[2];    // the base planes of the dependents, behind those
+    JobLaunch dep_final;      // dsens_dep_final_kernel over the grids of the candidates with dependents
     bool planned = false;   // the tables describe every candidate
     int pending = 0;        // a run is in flight
     int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
@@ -210,9 +210,10 @@ DsensPass make_pass(const ccd_dsens* d, const Candidate& c, int k, const PassPla
 }
 
 // slot `which` (-1: the base slot, else probe slot k) of an inter candidate as dsens_inter_kernel reconstructs it
-DsensInterJob make_inter_job(const ccd_dsens* d, const Candidate& c, int which) {
-    DsensInterJob J;
+InterUnitJob make_inter_job(const ccd_dsens* d, const Candidate& c, int which) {
+    InterUnitJob J;
     std::memset(&J, 0, sizeof(J));
+    fill_inter_geometry(J, c.frame_desc(c.inter.frame_type, c.inter.warp_filter_size, c.inter.global_flow));
     const float* own = ccd_batch_output(d->batch, which < 0 ? c.base_slot : c.first_probe + which);
     J.residue = c.inter.role == 0 ? own : c.inter.partner;
     J.motion = c.inter.role == 0 ? c.inter.partner : own;
@@ -221,36 +222,21 @@ DsensInterJob make_inter_job(const ccd_dsens* d, const Candidate& c, int which) 
     J.w0 = c.warped[0]; J.w1 = c.warped[1];
     for (int p = 0; p < 3; ++p) J.plane[p] = c.inter_planes[which + 1][p];
     J.mode = which < 0 ? 0 : (c.inter.role == 0 ? 1 : 2);
-    J.frame_type = c.inter.frame_type;
-    J.H = c.hdr.img_size[0]; J.W = c.hdr.img_size[1];
-    J.n_taps = c.inter.warp_filter_size;
-    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? c.inter.global_flow[i] : 0;
-    J.chroma_shift = c.frame_data_type == 1 ? 1 : 0;
-    J.wide = c.bitdepth > 8;
-    J.tiles_x = ((J.W >> J.chroma_shift) + 63) / 64;
-    J.maxv = static_cast<float>((1 << c.bitdepth) - 1);
     return J;
 }
 
 // dependent q of the candidate reconstructed with `ref` (the candidate's frame as f32 4:4:4) as its reference `which`: into its
 // base planes (base = true: a job of dsens_inter_kernel), or as dsens_dep_kernel reconstructs a unit
-DsensInterJob make_dep_recon(const Candidate& c, const Candidate::Dependent& q, const float* ref, bool base) {
-    DsensInterJob J;
+InterUnitJob make_dep_recon(const Candidate& c, const Candidate::Dependent& q, const float* ref, bool base) {
+    InterUnitJob J;
     std::memset(&J, 0, sizeof(J));
+    fill_inter_geometry(J, c.frame_desc(q.in.frame_type, q.in.warp_filter_size, q.in.global_flow));
     const bool two = q.in.frame_type == 2;
     J.residue = q.in.residue; J.motion = q.in.motion;
     J.ref0 = (two && q.in.which == 1) ? q.other_f32 : ref;
     J.ref1 = (two && q.in.which == 0) ? q.other_f32 : ref;
     for (int p = 0; p < 3; ++p) J.plane[p] = q.base[p];
     J.mode = base ? 0 : 2;
-    J.frame_type = q.in.frame_type;
-    J.H = c.hdr.img_size[0]; J.W = c.hdr.img_size[1];
-    J.n_taps = q.in.warp_filter_size;
-    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? q.in.global_flow[i] : 0;
-    J.chroma_shift = c.frame_data_type == 1 ? 1 : 0;
-    J.wide = c.bitdepth > 8;
-    J.tiles_x = ((J.W >> J.chroma_shift) + 63) / 64;
-    J.maxv = static_cast<float>((1 << c.bitdepth) - 1);
     return J;
 }
 
@@ -270,24 +256,6 @@ DsensDepJob make_dep_job(const Candidate& c, const Candidate::Dependent& q, int 
     return D;
 }
 
-inline const DsensInterJob& recon_of(const DsensInterJob& J) { return J; }
-inline const DsensInterJob& recon_of(const DsensDepJob& D) { return D.recon; }
-
-template <typename Job>
-int put_inter_launch(TableImage& img, const std::vector<Job>& jobs, InterLaunch& L) {
-    std::vector<uint32_t> prefix(jobs.size() + 1, 0);
-    uint64_t blocks = 0;
-    for (size_t i = 0; i < jobs.size(); ++i) {
-        const DsensInterJob& J = recon_of(jobs[i]);
-        blocks += static_cast<uint64_t>(J.tiles_x) * (((J.H >> J.chroma_shift) + 3) / 4);
-        if (blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
-        prefix[i + 1] = static_cast<uint32_t>(blocks);
-    }
-    L.n_jobs = static_cast<int>(jobs.size()); L.n_blocks = static_cast<uint32_t>(blocks);
-    L.jobs = img.put(jobs); L.prefix = img.put(prefix);
-    return CCD_OK;
-}
-
 // Every round's segments, passes and reconstruction jobs, one block, one copy.
 int build_tables(ccd_dsens* d, hipStream_t st) {
     const int K = d->K;
@@ -297,14 +265,14 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
     d->rounds.assign(n_rounds, Round{});
     uint32_t max_units = 1;
     {
-        std::vector<DsensInterJob> base[2];
+        std::vector<InterUnitJob> base[2];
         for (const auto& cp : d->cands)
             if (cp->is_inter) base[cp->inter.warp_filter_size == 8].push_back(make_inter_job(d, *cp, -1));
         for (int i = 0; i < 2; ++i) {
-            const int rc = put_inter_launch(img, base[i], d->inter_base[i]);
+            const int rc = put_job_launch(img, base[i], d->inter_base[i]);
             if (rc < 0) return rc;
         }
-        std::vector<DsensInterJob> dep_base[2];
+        std::vector<InterUnitJob> dep_base[2];
         std::vector<DsensDepGrid> grids;
         std::vector<uint32_t> grid_prefix(1, 0);
         for (const auto& cp : d->cands) {
@@ -319,7 +287,7 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
             }
         }
         for (int i = 0; i < 2; ++i) {
-            const int rc = put_inter_launch(img, dep_base[i], d->dep_base[i]);
+            const int rc = put_job_launch(img, dep_base[i], d->dep_base[i]);
             if (rc < 0) return rc;
         }
         d->dep_final.n_jobs = static_cast<int>(grids.size()); d->dep_final.n_blocks = grid_prefix.back();
@@ -328,7 +296,7 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
     for (size_t r = 0; r < n_rounds; ++r) {
         std::vector<DsensSeg> segs;
         std::vector<DsensPass> passes;
-        std::vector<DsensInterJob> jobs[2];
+        std::vector<InterUnitJob> jobs[2];
         std::vector<DsensDepJob> dep_jobs[2];
         for (const auto& cp : d->cands) {
             const Candidate& c = *cp;
@@ -366,8 +334,8 @@ int build_tables(ccd_dsens* d, hipStream_t st) {
         }
         Round& R = d->rounds[r];
         for (int i = 0; i < 2; ++i) {
-            int rc = put_inter_launch(img, jobs[i], R.probes[i]);
-            if (rc >= 0) rc = put_inter_launch(img, dep_jobs[i], R.deps[i]);
+            int rc = put_job_launch(img, jobs[i], R.probes[i]);
+            if (rc >= 0) rc = put_job_launch(img, dep_jobs[i], R.deps[i]);
             if (rc < 0) return rc;
         }
         std::vector<uint32_t> seg_prefix(segs.size() + 1, 0), unit_prefix(passes.size() + 1, 0), probe_prefix(passes.size() + 1, 0);
@@ -527,20 +495,15 @@ static int add_candidate(ccd_dsens* d, const ccd_cc_header* arch, const uint8_t*
         return CCD_ERR_NOMEM;
     }
     if (inter) {  // [references as f32][warped references, residue candidates][planes of the base and the K probe slots]
-        const size_t hw = static_cast<size_t>(h.img_size[0]) * h.img_size[1], sample = bitdepth > 8 ? 2 : 1;
-        const size_t chw = frame_data_type == 1 ? static_cast<size_t>(h.img_size[0] / 2) * (h.img_size[1] / 2) : hw;
-        const size_t f32_3 = align256(3 * hw * sizeof(float)), luma = align256(hw * sample), chroma = align256(chw * sample);
+        const PlaneLayout lay = plane_layout(h.img_size[0], h.img_size[1], bitdepth, frame_data_type);
         const int n_refs = inter->frame_type == 2 ? 2 : 1, n_warped = inter->role == 0 ? n_refs : 0;
-        const size_t total = (n_refs + n_warped) * f32_3 + static_cast<size_t>(d->K + 1) * (luma + 2 * chroma);
+        const size_t total = (n_refs + n_warped) * lay.f32_3 + static_cast<size_t>(d->K + 1) * lay.planes();
         if (!c.inter_buf.get(d->device, BlockPool::kDevice, total)) { drop(); return CCD_ERR_NOMEM; }
-        char* at = c.inter_buf.as<char>();
-        for (int r = 0; r < n_refs; ++r, at += f32_3) c.ref_f32[r] = reinterpret_cast<float*>(at);
-        for (int r = 0; r < n_warped; ++r, at += f32_3) c.warped[r] = reinterpret_cast<float*>(at);
+        BlockCursor cur(c.inter_buf);
+        for (int r = 0; r < n_refs; ++r) c.ref_f32[r] = cur.f32(lay);
+        for (int r = 0; r < n_warped; ++r) c.warped[r] = cur.f32(lay);
         c.inter_planes.resize(d->K + 1);
-        for (auto& pl : c.inter_planes) {
-            pl[0] = at; pl[1] = at + luma; pl[2] = at + luma + chroma;
-            at += luma + 2 * chroma;
-        }
+        for (auto& pl : c.inter_planes) cur.planes(lay, pl.data());
     }
     // the slots of an inter cool-chic produce its float output only (as the decoder adds them): the planes are the frame's
     const int slot_bitdepth = inter ? 0 : bitdepth;
@@ -587,9 +550,8 @@ int ccd_dsens_add_dependent(ccd_dsens* d, int slot, const ccd_dsens_dependent* d
     if (!yuv420_sides_ok(c.frame_data_type, h.img_size[0], h.img_size[1])) return CCD_ERR_VALUE;
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(d->device));
-    const size_t hw = static_cast<size_t>(h.img_size[0]) * h.img_size[1], sample = c.bitdepth > 8 ? 2 : 1;
-    const size_t chw = c.frame_data_type == 1 ? static_cast<size_t>(h.img_size[0] / 2) * (h.img_size[1] / 2) : hw;
-    const size_t f32_3 = align256(3 * hw * sizeof(float)), luma = align256(hw * sample), chroma = align256(chw * sample);
+    const size_t hw = static_cast<size_t>(h.img_size[0]) * h.img_size[1];
+    const PlaneLayout lay = plane_layout(h.img_size[0], h.img_size[1], c.bitdepth, c.frame_data_type);
     if (c.deps.empty()) {  // the first one: [maps as the own ones][flags][counters], and the frame as f32 for the base and K probe slots
         size_t at = align256(c.map_off[h.n_grids - 1] + 2 * sizeof(int64_t) * h.grid_h[h.n_grids - 1] * h.grid_w[h.n_grids - 1]);
         for (int g = 0; g < h.n_grids; ++g) { c.flag_off[g] = at; at += align256(2 * static_cast<size_t>(h.grid_h[g]) * h.grid_w[g]); }
@@ -605,13 +567,13 @@ int ccd_dsens_add_dependent(ccd_dsens* d, int slot, const ccd_dsens_dependent* d
     Candidate::Dependent q;
     q.in = *dep;
     const bool two = dep->frame_type == 2;
-    if (!q.buf.get(d->device, BlockPool::kDevice, (two ? f32_3 : 0) + luma + 2 * chroma)) {
+    if (!q.buf.get(d->device, BlockPool::kDevice, (two ? lay.f32_3 : 0) + lay.planes())) {
         if (c.deps.empty()) { c.dep_maps.drop(); c.dep_f32.drop(); }
         return CCD_ERR_NOMEM;
     }
-    char* at = q.buf.as<char>();
-    if (two) { q.other_f32 = reinterpret_cast<float*>(at); at += f32_3; }
-    q.base[0] = at; q.base[1] = at + luma; q.base[2] = at + luma + chroma;
+    BlockCursor cur(q.buf);
+    if (two) q.other_f32 = cur.f32(lay);
+    cur.planes(lay, q.base);
     c.deps.push_back(q);
     int W = 0;  // the widest window of the dependents' warps: 2 bilinear, 4 bicubic, the filter size for sinc
     for (const auto& e : c.deps) W = std::max(W, e.in.warp_filter_size);
@@ -633,12 +595,12 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
         const int rc = build_tables(d, st);
         if (rc < 0) return rc;
     }
-    const char* base = d->tables.dev.as<char>();
+    const Mirror& T = d->tables;
     d->pending = 1;
-    auto reconstruct = [&](const InterLaunch (&L)[2]) -> int {  // one launch per kernel instantiation in use
+    auto reconstruct = [&](const JobLaunch (&L)[2]) -> int {  // one launch per kernel instantiation in use
         for (int i = 0; i < 2; ++i)
-            if (launch_dsens_inter(reinterpret_cast<const DsensInterJob*>(base + L[i].jobs), reinterpret_cast<const uint32_t*>(base + L[i].prefix),
-                                   L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess) return CCD_ERR_HIP;
+            if (launch_dsens_inter(T.dev_at<InterUnitJob>(L[i].jobs), T.dev_at<uint32_t>(L[i].prefix), L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess)
+                return CCD_ERR_HIP;
         return CCD_OK;
     };
     for (const auto& cp : d->cands) {  // the references of the inter candidates as the warp reads them
@@ -648,10 +610,10 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
             HIP_TRY(launch_planes_to_444(pl[0], pl[1], pl[2], c.ref_f32[r], c.hdr.img_size[0], c.hdr.img_size[1], c.bitdepth, c.frame_data_type, st));
         }
     }
-    auto dep_launches = [&](const InterLaunch (&L)[2]) -> int {
+    auto dep_launches = [&](const JobLaunch (&L)[2]) -> int {
         for (int i = 0; i < 2; ++i)
-            if (launch_dsens_dep(reinterpret_cast<const DsensDepJob*>(base + L[i].jobs), reinterpret_cast<const uint32_t*>(base + L[i].prefix),
-                                 L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess) return CCD_ERR_HIP;
+            if (launch_dsens_dep(T.dev_at<DsensDepJob>(L[i].jobs), T.dev_at<uint32_t>(L[i].prefix), L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess)
+                return CCD_ERR_HIP;
         return CCD_OK;
     };
     // slot k (-1: the base slot) of a candidate with dependents as the dependents' warps read it
@@ -674,8 +636,7 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
     for (const Round& R : d->rounds) {
         int rc = CCD_OK;
         if (d->stages & 1) {
-            HIP_TRY(launch_dsens_apply(reinterpret_cast<const DsensSeg*>(base + R.segs), reinterpret_cast<const uint32_t*>(base + R.seg_prefix), R.n_segs,
-                                       R.n_blocks, st));
+            HIP_TRY(launch_dsens_apply(T.dev_at<DsensSeg>(R.segs), T.dev_at<uint32_t>(R.seg_prefix), R.n_segs, R.n_blocks, st));
             if ((rc = ccd_batch_run(d->batch, stream)) < 0) return rc;
         }
         if (first && (d->stages & 2) && (rc = reconstruct(d->inter_base)) < 0) return rc;  // the base planes, and the warped references they leave
@@ -692,14 +653,13 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
         if (dep_sum && (rc = dep_launches(R.deps)) < 0) return rc;
         ++round;
         if (d->stages & 4) {
-            HIP_TRY(launch_dsens_sse(reinterpret_cast<const DsensPass*>(base + R.passes), reinterpret_cast<const uint32_t*>(base + R.unit_prefix),
-                                     reinterpret_cast<const uint32_t*>(base + R.probe_prefix), R.n_passes, R.n_units, R.n_probes,
-                                     d->slab.as<int64_t>(), st));
+            HIP_TRY(launch_dsens_sse(T.dev_at<DsensPass>(R.passes), T.dev_at<uint32_t>(R.unit_prefix), T.dev_at<uint32_t>(R.probe_prefix), R.n_passes,
+                                     R.n_units, R.n_probes, d->slab.as<int64_t>(), st));
         }
     }
     if (dep_sum)
-        HIP_TRY(launch_dsens_dep_final(reinterpret_cast<const DsensDepGrid*>(base + d->dep_final.jobs), reinterpret_cast<const uint32_t*>(base + d->dep_final.prefix),
-                                       d->dep_final.n_jobs, d->dep_final.n_blocks, st));
+        HIP_TRY(launch_dsens_dep_final(T.dev_at<DsensDepGrid>(d->dep_final.jobs), T.dev_at<uint32_t>(d->dep_final.prefix), d->dep_final.n_jobs,
+                                       d->dep_final.n_blocks, st));
     return CCD_OK;
 }
 

@@ -69,6 +69,8 @@ struct Mirror {
     bool ensure(int device, size_t bytes) { return dev.ensure(device, BlockPool::kDevice, bytes) && host.ensure(device, BlockPool::kPinned, bytes); }
     hipError_t upload(size_t bytes, hipStream_t st) const { return hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, st); }
     hipError_t download(size_t bytes, hipStream_t st) const { return hipMemcpyAsync(host.p, dev.p, bytes, hipMemcpyDeviceToHost, st); }
+    // the table a TableImage placed at `off`, where the kernels read it
+    template <typename T> const T* dev_at(size_t off) const { return reinterpret_cast<const T*>(dev.as<char>() + off); }
     void drop() { dev.drop(); host.drop(); }
 };
 

@@ -255,6 +255,21 @@ __device__ __forceinline__ void ic_window_axis(int n_taps, float f, int i, int n
 __device__ __forceinline__ float ic_weight(float v) { const float a = v + 0.5f; return a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a); }
 __device__ __forceinline__ float ic_mix(float b, float w0, float w1) { const float t0 = b * w0, t1 = (1.0f - b) * w1; return t0 + t1; }
 __device__ __forceinline__ float ic_sample(float a, float pred, float residue) { const float m = a * pred; return m + residue; }
+// the tail of inter_recon_body for the unit walk (di_pixel): sample i from its warped references (w1: B frames) and a = ic_weight(alpha)
+__device__ __forceinline__ void ic_blend(bool two, const float* __restrict__ residue, size_t plane, size_t i, float a, const float w0[3],
+                                         const float w1[3], float out[3]) {
+    float pred[3];
+    if (two) {
+        const float b = ic_weight(residue[4 * plane + i]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pred[c] = ic_mix(b, w0[c], w1[c]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pred[c] = w0[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = ic_sample(a, pred[c], residue[c * plane + i]);
+}
 
 struct InterParams {
     const float* residue;  // [4 | 5][H][W]
@@ -316,7 +331,8 @@ __device__ __forceinline__ void inter_warp_ref(const InterParams& p, const float
     else ic_warp<NT>(ref, p.H, p.W, p.gflow[2 * r], p.gflow[2 * r + 1], p.n_taps, fx, fy, y, x, out);
 }
 // One pixel of a P / B frame.  The mix stays inside the B branch, behind the second warp: hoisted behind both warps, the 8-tap
-// kernels need 256 registers and run one wave per SIMD.
+// kernels need 256 registers and run one wave per SIMD - and through ic_blend, which sits behind both, inter_recon_kernel<8> needs
+// 206 and runs two, so the tail is written out here.
 template <int NT, bool AHEAD>
 __device__ __forceinline__ void inter_recon_body(const InterParams& p, const float4* __restrict__ coef) {
     int x, y;
@@ -362,15 +378,15 @@ hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const in
     return hipGetLastError();
 }
 
-// ---- distortion deltas of P / B frames (ccd_dsens_add_inter): reconstruction and integer planes of every probe
-// slot of a round in one launch.  A job is one slot; its workgroups find it in a prefix table (entry_of), as the other dsens kernels
-// find their entries.  Per sample the operations of inter_recon_kernel (same device functions: ic_warp and the blend
-// pieces) followed by those of planes_kernel (ccd_float.hip; the sample helpers are shared, ccd_planes.hpp: round to the bit-depth grid, clamp, round; 4:2:0 chroma = the
-// sequential f32 sum of the quad's rounded samples, then quantise_chroma420): the f32 that inter_recon_kernel stores and planes_kernel
-// loads is the register in between, so the planes are those of ccd_inter_reconstruct bit for bit.  What a residue probe cannot
-// change - the warped references - is computed by the base job of a run (mode 0), kept as f32 and only read by residue probes
-// (mode 1); a motion probe (mode 2) warps.  Every output word has one writer: a thread owns one luma sample or, 4:2:0, one 2 x 2
-// quad and its chroma sample.  Plain vector stores; no atomics, no waits, no LDS.
+// ---- P / B frames by units: the walk that dsens_inter_kernel, dsens_dep_kernel and inter_score_kernel share (DESIGN.md 4.15, 4.16,
+// 4.19; the job: InterUnitJob, ccd_device.hpp).  A job is one frame to reconstruct; its workgroups find it in a prefix table
+// (di_locate), a thread owns one unit: one luma sample or, 4:2:0, one 2 x 2 quad and its chroma sample.  Per sample (di_unit) the
+// operations of inter_recon_kernel (same device functions: ic_warp and ic_blend) followed by those of planes_kernel (ccd_float.hip;
+// the sample helpers are shared, ccd_planes.hpp: round to the bit-depth grid, clamp, round; 4:2:0 chroma = the sequential f32 sum
+// of the quad's rounded samples, then quantise_chroma420): the f32 that inter_recon_kernel stores and planes_kernel loads is the
+// register in between, so the quantised samples are the planes of ccd_inter_reconstruct bit for bit.  What a residue candidate
+// cannot change - the warped references - is computed by the base job (mode 0), kept as f32 and only read by residue jobs (mode 1);
+// a motion job (mode 2) warps.  What becomes of a quantised sample is the kernel's sink.
 __device__ __forceinline__ void di_store(void* plane, size_t at, unsigned v, int wide) {
     if (wide) static_cast<uint16_t*>(plane)[at] = static_cast<uint16_t>(v);
     else static_cast<uint8_t*>(plane)[at] = static_cast<uint8_t>(v);
@@ -378,11 +394,11 @@ __device__ __forceinline__ void di_store(void* plane, size_t at, unsigned v, int
 
 // the frame's float sample (y, x) of the three channels: what inter_recon_body stores, from the same pieces
 template <int NT>
-__device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, float out[3]) {
+__device__ __forceinline__ void di_pixel(const InterUnitJob& J, int y, int x, float out[3]) {
     const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
     const float a = ic_weight(J.residue[3 * plane + i]);
     const bool two = J.frame_type == 2;
-    float w0[3] = {0.0f, 0.0f, 0.0f}, w1[3] = {0.0f, 0.0f, 0.0f}, pred[3];
+    float w0[3] = {0.0f, 0.0f, 0.0f}, w1[3] = {0.0f, 0.0f, 0.0f};
     if (J.mode == 1) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { w0[c] = J.w0[c * plane + i]; if (two) w1[c] = J.w1[c * plane + i]; }
@@ -403,28 +419,28 @@ __device__ __forceinline__ void di_pixel(const DsensInterJob& J, int y, int x, f
             for (int c = 0; c < 3; ++c) { J.w0[c * plane + i] = w0[c]; if (two) J.w1[c * plane + i] = w1[c]; }
         }
     }
-    if (two) {
-        const float b = ic_weight(J.residue[4 * plane + i]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pred[c] = ic_mix(b, w0[c], w1[c]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pred[c] = w0[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = ic_sample(a, pred[c], J.residue[c * plane + i]);
+    ic_blend(two, J.residue, plane, i, a, w0, w1, out);
 }
 
-template <int NT>  // as inter_recon_kernel: 8 = the sinc-8 warp of every preset, 0 = a run-time tap count and the native paths
-__global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+// The job of this workgroup, its index `local` among the job's workgroups and the thread's unit; `inside`: the unit lies inside the
+// frame (a flag, not a return: inter_score_kernel's threads all meet at a barrier).
+struct DiUnit { uint32_t local; int ux, uy; bool inside; };
+template <class Job>
+__device__ __forceinline__ const Job& di_locate(const Job* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs, DiUnit& u) {
     const uint32_t blk = blockIdx.x;
     const int j = entry_of(prefix, n_jobs, blk);
-    const DsensInterJob J = jobs[j];  // (uniform: scalar registers)
-    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
-    int ux, uy;
-    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
+    const InterUnitJob& J = unit_job(jobs[j]);  // (uniform: scalar loads)
+    u.local = blk - prefix[j];
+    const uint32_t tiles_x = static_cast<uint32_t>(J.tiles_x);
+    tile_pixel(u.local % tiles_x, u.local / tiles_x, &u.ux, &u.uy);
+    u.inside = u.ux < (J.W >> J.chroma_shift) && u.uy < (J.H >> J.chroma_shift);  // (4:2:0 frames have even sides)
+    return jobs[j];
+}
+// Unit (ux, uy) of the frame: sink(plane, index, quantised sample) once per output sample - 4:4:4 the three planes at i; 4:2:0 the
+// four luma samples, then the two chroma samples at ci.
+template <int NT, class Sink>
+__device__ __forceinline__ void di_unit(const InterUnitJob& J, int ux, int uy, Sink&& sink) {
     const int cs = J.chroma_shift;
-    if (ux >= (J.W >> cs) || uy >= (J.H >> cs)) return;  // (4:2:0 frames have even sides)
     const float maxv = J.maxv;
     float v[3], sum1 = 0.0f, sum2 = 0.0f;  // planes_kernel's order over the quad: dy outer, dx inner
     const int n = cs ? 4 : 1;              // one loop body for both shapes: the warp is instantiated once
@@ -433,10 +449,10 @@ __global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* _
         const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
         di_pixel<NT>(J, y, x, v);
         const size_t i = static_cast<size_t>(y) * J.W + x;
-        di_store(J.plane[0], i, quantise_sample(v[0], maxv), J.wide);
+        sink(0, i, quantise_sample(v[0], maxv));
         if (!cs) {
-            di_store(J.plane[1], i, quantise_sample(v[1], maxv), J.wide);
-            di_store(J.plane[2], i, quantise_sample(v[2], maxv), J.wide);
+            sink(1, i, quantise_sample(v[1], maxv));
+            sink(2, i, quantise_sample(v[2], maxv));
         } else {
             sum1 += round_to_grid(v[1], maxv);
             sum2 += round_to_grid(v[2], maxv);
@@ -444,15 +460,29 @@ __global__ __launch_bounds__(256) void dsens_inter_kernel(const DsensInterJob* _
     }
     if (!cs) return;
     const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
-    di_store(J.plane[1], ci, quantise_chroma420(sum1, maxv), J.wide);
-    di_store(J.plane[2], ci, quantise_chroma420(sum2, maxv), J.wide);
+    sink(1, ci, quantise_chroma420(sum1, maxv));
+    sink(2, ci, quantise_chroma420(sum2, maxv));
+}
+// One launch over jobs and their prefix table of workgroups: the sinc-8 instantiation or the run-time one; nothing when empty.
+template <class Job, class... X>
+static hipError_t launch_jobs(void (*k8)(const Job*, const uint32_t*, int, X...), void (*k0)(const Job*, const uint32_t*, int, X...), unsigned threads,
+                              const Job* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream, X... extra) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(sinc8 ? k8 : k0, dim3(n_blocks), dim3(threads), 0, stream, d_jobs, d_prefix, n_jobs, extra...);
+    return hipGetLastError();
 }
 
-hipError_t launch_dsens_inter(const DsensInterJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
-    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
-    if (sinc8) hipLaunchKernelGGL(dsens_inter_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
-    else hipLaunchKernelGGL(dsens_inter_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
-    return hipGetLastError();
+// ---- distortion deltas of P / B frames (ccd_dsens_add_inter): the integer planes of every probe slot of a round in
+// one launch.  A job is one slot.  Every output word has one writer.  Plain vector stores; no atomics, no waits, no LDS.
+template <int NT>  // as inter_recon_kernel: 8 = the sinc-8 warp of every preset, 0 = a run-time tap count and the native paths
+__global__ __launch_bounds__(256) void dsens_inter_kernel(const InterUnitJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+    DiUnit u;
+    const InterUnitJob J = di_locate(jobs, prefix, n_jobs, u);  // (a copy: scalar registers)
+    if (!u.inside) return;
+    di_unit<NT>(J, u.ux, u.uy, [&](int p, size_t at, unsigned q) { di_store(J.plane[p], at, q, J.wide); });
+}
+hipError_t launch_dsens_inter(const InterUnitJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
+    return launch_jobs(dsens_inter_kernel<8>, dsens_inter_kernel<0>, 256, d_jobs, d_prefix, n_jobs, n_blocks, sinc8, stream);
 }
 
 // ---- distortion deltas through the frames that predict from a moved one (ccd_dsens_add_dependent).  A job is one
@@ -478,7 +508,7 @@ __device__ __forceinline__ long long di_gain(int q, int base, int src) {
 // what the windows of sample (y, x) hit: counts per axis (0 on either: nothing) and the first member of each
 template <int NT>
 __device__ __forceinline__ bool dd_sample_hits(const DsensDepJob& D, int y, int x, int& fy, int& cy, int& fx, int& cx) {
-    const DsensInterJob& J = D.recon;
+    const InterUnitJob& J = D.recon;
     const size_t plane = static_cast<size_t>(J.H) * J.W, i = static_cast<size_t>(y) * J.W + x;
     const int r = D.which;
     int a, b;
@@ -493,16 +523,12 @@ __device__ __forceinline__ bool dd_sample_hits(const DsensDepJob& D, int y, int 
 
 template <int NT>
 __global__ __launch_bounds__(256) void dsens_dep_kernel(const DsensDepJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
-    const uint32_t blk = blockIdx.x;
-    const int j = entry_of(prefix, n_jobs, blk);
-    const DsensDepJob& D = jobs[j];  // (uniform: scalar loads)
-    const DsensInterJob& J = D.recon;
-    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
-    int ux, uy;
-    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
-    const int cs = J.chroma_shift;
-    if (ux >= (J.W >> cs) || uy >= (J.H >> cs)) return;
-    const int n = cs ? 4 : 1;
+    DiUnit u;
+    const DsensDepJob& D = di_locate(jobs, prefix, n_jobs, u);
+    if (!u.inside) return;
+    const InterUnitJob& J = D.recon;
+    const int ux = u.ux, uy = u.uy;
+    const int cs = J.chroma_shift, n = cs ? 4 : 1;
     const size_t map_plane = D.move > 0 ? static_cast<size_t>(D.h) * D.w : 0;
     int state = 0, ey = 0, ex = 0;  // 0: nothing hit, 1: the entry (ey, ex) alone, 2: a conflict
 #pragma unroll 1
@@ -524,43 +550,20 @@ __global__ __launch_bounds__(256) void dsens_dep_kernel(const DsensDepJob* __res
         }
         return;
     }
-    const float maxv = J.maxv;
-    float v[3], sum1 = 0.0f, sum2 = 0.0f;
     long long gain = 0;
-#pragma unroll 1
-    for (int q = 0; q < n; ++q) {
-        const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
-        di_pixel<NT>(J, y, x, v);
-        const size_t i = static_cast<size_t>(y) * J.W + x;
-        gain += di_gain(static_cast<int>(quantise_sample(v[0], maxv)), di_load(J.plane[0], i, J.wide), di_load(D.src[0], i, J.wide));
-        if (!cs) {
-            gain += di_gain(static_cast<int>(quantise_sample(v[1], maxv)), di_load(J.plane[1], i, J.wide), di_load(D.src[1], i, J.wide));
-            gain += di_gain(static_cast<int>(quantise_sample(v[2], maxv)), di_load(J.plane[2], i, J.wide), di_load(D.src[2], i, J.wide));
-        } else {
-            sum1 += round_to_grid(v[1], maxv);
-            sum2 += round_to_grid(v[2], maxv);
-        }
-    }
-    if (cs) {
-        const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
-        gain += di_gain(static_cast<int>(quantise_chroma420(sum1, maxv)), di_load(J.plane[1], ci, J.wide), di_load(D.src[1], ci, J.wide));
-        gain += di_gain(static_cast<int>(quantise_chroma420(sum2, maxv)), di_load(J.plane[2], ci, J.wide), di_load(D.src[2], ci, J.wide));
-    }
+    di_unit<NT>(J, ux, uy, [&](int p, size_t at, unsigned q) {
+        gain += di_gain(static_cast<int>(q), di_load(J.plane[p], at, J.wide), di_load(D.src[p], at, J.wide));
+    });
     if (gain != 0) atomicAdd(D.acc + map_plane + static_cast<size_t>(ey) * D.w + ex, static_cast<unsigned long long>(gain));
 }
 
 hipError_t launch_dsens_dep(const DsensDepJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
-    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
-    if (sinc8) hipLaunchKernelGGL(dsens_dep_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
-    else hipLaunchKernelGGL(dsens_dep_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
-    return hipGetLastError();
+    return launch_jobs(dsens_dep_kernel<8>, dsens_dep_kernel<0>, 256, d_jobs, d_prefix, n_jobs, n_blocks, sinc8, stream);
 }
 
 // ---- the squared error of many candidates of P / B frames in one launch (ccd_iscore).  A job is one candidate of
-// one frame: the frame's two float outputs with one of them replaced.  Tiles, units and modes are dsens_inter_kernel's, and so are
-// the operations per unit (di_pixel, then the sample helpers in planes_kernel's quad order); where that kernel stores a sample this
-// one takes (sample - source)^2, as integers, so the sums are those of ccd_inter_reconstruct followed by the quality meter.  No
-// plane is stored.  Reduction as quality_sse_kernel: u64 per lane and plane, wave shuffle, the four wave partials through LDS, one
+// one frame: the frame's two float outputs with one of them replaced.  The unit walk with a sink that takes (sample - source)^2, as
+// integers, so the sums are those of ccd_inter_reconstruct followed by the quality meter.  No plane is stored.  Reduction as quality_sse_kernel: u64 per lane and plane, wave shuffle, the four wave partials through LDS, one
 // thread stores the workgroup's three partials; inter_score_final_kernel adds a job's partials in a fixed order.  Plain vector
 // stores; no atomics, no waits on other workgroups.
 __device__ __forceinline__ uint64_t is_wave_sum(uint64_t v) {
@@ -577,45 +580,22 @@ template <int NT>  // as dsens_inter_kernel
 __global__ __launch_bounds__(256) void inter_score_kernel(const InterScoreJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs,
                                                           uint64_t* __restrict__ part) {
     __shared__ uint64_t wave_part[3][4];
-    const uint32_t blk = blockIdx.x;
-    const int j = entry_of(prefix, n_jobs, blk);
-    const InterScoreJob& S = jobs[j];  // (uniform: scalar loads)
-    const DsensInterJob& J = S.recon;
-    const uint32_t local = blk - prefix[j], tiles_x = static_cast<uint32_t>(J.tiles_x);
-    int ux, uy;
-    tile_pixel(local % tiles_x, local / tiles_x, &ux, &uy);
-    const int cs = J.chroma_shift;
+    DiUnit u;
+    const InterScoreJob& S = di_locate(jobs, prefix, n_jobs, u);
+    const InterUnitJob& J = S.recon;
     uint64_t e0 = 0, e1 = 0, e2 = 0;
-    if (ux < (J.W >> cs) && uy < (J.H >> cs)) {  // (every thread reaches the barrier below)
-        const float maxv = J.maxv;
-        float v[3], sum1 = 0.0f, sum2 = 0.0f;  // planes_kernel's order over the quad: dy outer, dx inner
-        const int n = cs ? 4 : 1;              // one loop body for both shapes: the warp is instantiated once
-#pragma unroll 1
-        for (int q = 0; q < n; ++q) {
-            const int y = (uy << cs) + (q >> 1), x = (ux << cs) + (q & 1);
-            di_pixel<NT>(J, y, x, v);
-            const size_t i = static_cast<size_t>(y) * J.W + x;
-            e0 += is_sq(quantise_sample(v[0], maxv), di_load(S.src[0], i, J.wide));
-            if (!cs) {
-                e1 = is_sq(quantise_sample(v[1], maxv), di_load(S.src[1], i, J.wide));
-                e2 = is_sq(quantise_sample(v[2], maxv), di_load(S.src[2], i, J.wide));
-            } else {
-                sum1 += round_to_grid(v[1], maxv);
-                sum2 += round_to_grid(v[2], maxv);
-            }
-        }
-        if (cs) {
-            const size_t ci = static_cast<size_t>(uy) * (J.W / 2) + ux;
-            e1 = is_sq(quantise_chroma420(sum1, maxv), di_load(S.src[1], ci, J.wide));
-            e2 = is_sq(quantise_chroma420(sum2, maxv), di_load(S.src[2], ci, J.wide));
-        }
+    if (u.inside) {  // (every thread reaches the barrier below)
+        di_unit<NT>(J, u.ux, u.uy, [&](int p, size_t at, unsigned q) {
+            const uint64_t e = is_sq(q, di_load(S.src[p], at, J.wide));
+            if (p == 0) e0 += e; else if (p == 1) e1 += e; else e2 += e;
+        });
     }
     e0 = is_wave_sum(e0); e1 = is_wave_sum(e1); e2 = is_wave_sum(e2);
     const int tid = threadIdx.x;
     if ((tid & 63) == 0) { wave_part[0][tid >> 6] = e0; wave_part[1][tid >> 6] = e1; wave_part[2][tid >> 6] = e2; }
     __syncthreads();
     if (tid == 0) {
-        uint64_t* out = part + (static_cast<size_t>(S.part_first) + local) * 3;
+        uint64_t* out = part + (static_cast<size_t>(S.part_first) + u.local) * 3;
 #pragma unroll
         for (int p = 0; p < 3; ++p) out[p] = wave_part[p][0] + wave_part[p][1] + wave_part[p][2] + wave_part[p][3];
     }
@@ -634,10 +614,7 @@ __global__ __launch_bounds__(64) void inter_score_final_kernel(const InterScoreR
 
 hipError_t launch_inter_score(const InterScoreJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, uint64_t* d_part,
                               hipStream_t stream) {
-    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
-    if (sinc8) hipLaunchKernelGGL(inter_score_kernel<8>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs, d_part);
-    else hipLaunchKernelGGL(inter_score_kernel<0>, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs, d_part);
-    return hipGetLastError();
+    return launch_jobs(inter_score_kernel<8>, inter_score_kernel<0>, 256, d_jobs, d_prefix, n_jobs, n_blocks, sinc8, stream, d_part);
 }
 hipError_t launch_inter_score_final(const InterScoreRange* d_ranges, int n_ranges, const uint64_t* d_part, uint64_t* d_sse, hipStream_t stream) {
     if (n_ranges <= 0) return hipSuccess;
@@ -691,10 +668,7 @@ __global__ __launch_bounds__(64) void rdoq_reach_kernel(const RdoqReachJob* __re
 }
 
 hipError_t launch_rdoq_reach(const RdoqReachJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream) {
-    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
-    if (sinc8) hipLaunchKernelGGL(rdoq_reach_kernel<8>, dim3(n_blocks), dim3(64), 0, stream, d_jobs, d_prefix, n_jobs);
-    else hipLaunchKernelGGL(rdoq_reach_kernel<0>, dim3(n_blocks), dim3(64), 0, stream, d_jobs, d_prefix, n_jobs);
-    return hipGetLastError();
+    return launch_jobs(rdoq_reach_kernel<8>, rdoq_reach_kernel<0>, 64, d_jobs, d_prefix, n_jobs, n_blocks, sinc8, stream);
 }
 
 // ---- a kernel that only takes time: ccd_runtime.cpp measures with it which of the library's side streams run concurrently

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "ccd_host.hpp"
+#include "ccd_inter_job.hpp"
 #include "ccd_iscore_plan.hpp"
 #include "ccd_kernels.hpp"
 
@@ -18,28 +19,20 @@ struct Frame {
     float* warped[2] = {};
 };
 struct Item { int frame, role; const float* output; };
-struct Launch { size_t jobs = 0, prefix = 0; int n_jobs = 0; uint32_t n_blocks = 0; };  // offsets into the tables block
 
 // the frame with `output` in place of the output of cool-chic `role` (-1: the frame's own pair, which keeps the warps)
 InterScoreJob make_job(const Frame& f, int role, const float* output, uint32_t part_first) {
     InterScoreJob S;
     std::memset(&S, 0, sizeof(S));
-    DsensInterJob& J = S.recon;
+    InterUnitJob& J = S.recon;
     const ccd_iscore_frame& in = f.in;
     const bool two = in.frame_type == 2;
+    fill_inter_geometry(J, InterFrameDesc{in.h, in.w, in.bitdepth, in.frame_data_type, in.frame_type, in.warp_filter_size, in.global_flow});
     J.residue = role == 0 ? output : in.residue;
     J.motion = role == 1 ? output : in.motion;
     J.ref0 = f.ref_f32[0]; J.ref1 = two ? f.ref_f32[1] : f.ref_f32[0];
     J.w0 = f.warped[0]; J.w1 = f.warped[1];
     J.mode = role < 0 ? 0 : (role == 0 ? 1 : 2);
-    J.frame_type = in.frame_type;
-    J.H = in.h; J.W = in.w;
-    J.n_taps = in.warp_filter_size;
-    for (int i = 0; i < 4; ++i) J.gflow[i] = (i < 2 || two) ? in.global_flow[i] : 0;
-    J.chroma_shift = in.frame_data_type == 1 ? 1 : 0;
-    J.wide = in.bitdepth > 8;
-    J.tiles_x = iscore_tiles_x(in.w, J.chroma_shift);
-    J.maxv = static_cast<float>((1 << in.bitdepth) - 1);
     for (int p = 0; p < 3; ++p) S.src[p] = in.src[p];
     S.part_first = part_first;
     return S;
@@ -96,11 +89,11 @@ int ccd_iscore_add_frame(ccd_iscore* s, const ccd_iscore_frame* frame) {
     // ---- the device from here on ----
     HIP_TRY(hipSetDevice(s->device));
     const int n_refs = frame->frame_type == 2 ? 2 : 1;
-    const size_t f32_3 = align256(static_cast<size_t>(3) * frame->h * frame->w * sizeof(float));
-    if (!fp->buf.get(s->device, BlockPool::kDevice, 2 * n_refs * f32_3)) return CCD_ERR_NOMEM;
-    char* at = fp->buf.as<char>();
-    for (int r = 0; r < n_refs; ++r, at += f32_3) fp->ref_f32[r] = reinterpret_cast<float*>(at);
-    for (int r = 0; r < n_refs; ++r, at += f32_3) fp->warped[r] = reinterpret_cast<float*>(at);
+    const PlaneLayout lay = plane_layout(frame->h, frame->w, frame->bitdepth, frame->frame_data_type);
+    if (!fp->buf.get(s->device, BlockPool::kDevice, 2 * n_refs * lay.f32_3)) return CCD_ERR_NOMEM;
+    BlockCursor cur(fp->buf);
+    for (int r = 0; r < n_refs; ++r) fp->ref_f32[r] = cur.f32(lay);
+    for (int r = 0; r < n_refs; ++r) fp->warped[r] = cur.f32(lay);
     s->frames.push_back(std::move(fp));
     return static_cast<int>(s->frames.size()) - 1;
 }
@@ -135,22 +128,19 @@ int ccd_iscore_run(ccd_iscore* s, void* stream) {
     const int rc = iscore_plan(geo, item_frame, s->plan, class_blocks, &total_blocks);
     if (rc < 0) return rc;
     std::vector<InterScoreJob> jobs[kIScoreClasses];
-    std::vector<uint32_t> prefix[kIScoreClasses];
-    for (auto& p : prefix) p.push_back(0);
     std::vector<InterScoreRange> ranges(n_results);
     for (size_t r = 0; r < n_results; ++r) {
         const IScoreSlot& P = s->plan[r];
         const Item* it = r < n_frames ? nullptr : &s->items[r - n_frames];
         const Frame& f = *s->frames[it ? it->frame : r];
         jobs[P.cls].push_back(make_job(f, it ? it->role : -1, it ? it->output : nullptr, P.part_first));
-        prefix[P.cls].push_back(prefix[P.cls].back() + P.n_blocks);
         ranges[r] = InterScoreRange{P.part_first, P.n_blocks};
     }
     TableImage img;
-    Launch L[kIScoreClasses];
+    JobLaunch L[kIScoreClasses];
     for (int c = 0; c < kIScoreClasses; ++c) {
-        L[c].n_jobs = static_cast<int>(jobs[c].size()); L[c].n_blocks = class_blocks[c];
-        L[c].jobs = img.put(jobs[c]); L[c].prefix = img.put(prefix[c]);
+        const int rc_c = put_job_launch(img, jobs[c], L[c]);  // (its workgroups are the plan's class_blocks[c]: both are inter_blocks)
+        if (rc_c < 0) return rc_c;
     }
     const size_t off_ranges = img.put(ranges);
     // ---- the device from here on ----
@@ -170,11 +160,10 @@ int ccd_iscore_run(ccd_iscore* s, void* stream) {
             HIP_TRY(launch_planes_to_444(pl[0], pl[1], pl[2], fp->ref_f32[r], in.h, in.w, in.bitdepth, in.frame_data_type, st));
         }
     }
-    const char* base = s->tables.dev.as<char>();
     for (int c = 0; c < kIScoreClasses; ++c)  // the base pairs first: the residue candidates read the warps they keep
-        HIP_TRY(launch_inter_score(reinterpret_cast<const InterScoreJob*>(base + L[c].jobs), reinterpret_cast<const uint32_t*>(base + L[c].prefix),
-                                   L[c].n_jobs, L[c].n_blocks, c & 1, s->part.as<uint64_t>(), st));
-    HIP_TRY(launch_inter_score_final(reinterpret_cast<const InterScoreRange*>(base + off_ranges), static_cast<int>(n_results), s->part.as<uint64_t>(),
+        HIP_TRY(launch_inter_score(s->tables.dev_at<InterScoreJob>(L[c].jobs), s->tables.dev_at<uint32_t>(L[c].prefix), L[c].n_jobs, L[c].n_blocks, c & 1,
+                                   s->part.as<uint64_t>(), st));
+    HIP_TRY(launch_inter_score_final(s->tables.dev_at<InterScoreRange>(off_ranges), static_cast<int>(n_results), s->part.as<uint64_t>(),
                                      s->out.dev.as<uint64_t>(), st));
     HIP_TRY(s->out.download(n_results * 3 * sizeof(uint64_t), st));
     s->pending = 1;

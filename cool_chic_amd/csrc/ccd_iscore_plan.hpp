@@ -1,10 +1,11 @@
 // ccd_iscore_plan.hpp - which launch every job of a ccd_iscore run belongs to and where its workgroup partials sit (host only, no
-// HIP: tools/iscore_host_check.cpp runs it under the sanitizers).  Results are numbered frames first (the base pairs), then items.
+// HIP calls: tools/iscore_host_check.cpp runs it under the sanitizers).  Results are numbered frames first (the base pairs), then items.
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "../../include/ccd.h"
+#include "ccd_inter_job.hpp"
 
 namespace ccd {
 
@@ -15,12 +16,6 @@ constexpr int kIScoreClasses = 4;
 
 struct IScoreGeo { int32_t h, w, chroma_shift, sinc8; };
 struct IScoreSlot { int32_t cls; uint32_t n_blocks, part_first; };
-
-// workgroups of 64 x 4 units (a unit: one luma sample or, 4:2:0, one quad) that cover a frame
-inline int32_t iscore_tiles_x(int w, int chroma_shift) { return ((w >> chroma_shift) + 63) / 64; }
-inline uint32_t iscore_blocks(const IScoreGeo& g) {
-    return static_cast<uint32_t>(iscore_tiles_x(g.w, g.chroma_shift)) * static_cast<uint32_t>(((g.h >> g.chroma_shift) + 3) / 4);
-}
 
 // out[r] for every result, the workgroups of every launch and of the whole run.  CCD_ERR_ARG for an item of no frame,
 // CCD_ERR_UNSUPPORTED when a run would need 2^31 workgroups or more.
@@ -35,7 +30,7 @@ inline int iscore_plan(const std::vector<IScoreGeo>& frames, const std::vector<i
         const IScoreGeo& g = frames[item ? static_cast<size_t>(item_frame[r - n_frames]) : r];
         IScoreSlot& s = out[r];
         s.cls = (item ? 2 : 0) + (g.sinc8 ? 1 : 0);
-        s.n_blocks = iscore_blocks(g);
+        s.n_blocks = inter_blocks(g.h, g.w, g.chroma_shift);
         s.part_first = static_cast<uint32_t>(total);
         total += s.n_blocks;
         per_class[s.cls] += s.n_blocks;

@@ -550,14 +550,14 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
         !r->results.ensure(r->device, res_bytes))
         return CCD_ERR_NOMEM;
     std::memcpy(r->tables.host.p, buf.data(), buf.size());
-    const char* base = r->tables.dev.as<char>();
+    const Mirror& T = r->tables;
     RdoqFollowLaunch F;
     if (following) {
-        F.gx = reinterpret_cast<const RdoqGridX*>(base + o_gx); F.sx = reinterpret_cast<const RdoqSlotX*>(base + o_sx);
-        F.comp_uid = reinterpret_cast<const uint32_t*>(base + o_cuid); F.comp_slot = reinterpret_cast<const int32_t*>(base + o_cslot);
+        F.gx = T.dev_at<RdoqGridX>(o_gx); F.sx = T.dev_at<RdoqSlotX>(o_sx);
+        F.comp_uid = T.dev_at<uint32_t>(o_cuid); F.comp_slot = T.dev_at<int32_t>(o_cslot);
         for (int c = 0; c < 2; ++c) {
-            F.reach_jobs[c] = reinterpret_cast<const RdoqReachJob*>(base + o_rj[c]);
-            F.reach_prefix[c] = reinterpret_cast<const uint32_t*>(base + o_rp[c]);
+            F.reach_jobs[c] = T.dev_at<RdoqReachJob>(o_rj[c]);
+            F.reach_prefix[c] = T.dev_at<uint32_t>(o_rp[c]);
             F.n_reach[c] = static_cast<int>(reach_jobs[c].size());
             F.reach_blocks[c] = reach_prefix[c].back();
         }
@@ -568,9 +568,8 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
     }
     const bool ok =
         r->tables.upload(buf.size(), st) == hipSuccess &&
-        launch_rdoq_step(reinterpret_cast<const RdoqGrid*>(base + o_grids), reinterpret_cast<const RdoqSlot*>(base + o_slots),
-                         reinterpret_cast<const uint32_t*>(base + o_lane), reinterpret_cast<const uint32_t*>(base + o_big),
-                         reinterpret_cast<const uint32_t*>(base + o_chunk), reinterpret_cast<const uint32_t*>(base + o_cell), n_grids,
+        launch_rdoq_step(T.dev_at<RdoqGrid>(o_grids), T.dev_at<RdoqSlot>(o_slots), T.dev_at<uint32_t>(o_lane), T.dev_at<uint32_t>(o_big),
+                         T.dev_at<uint32_t>(o_chunk), T.dev_at<uint32_t>(o_cell), n_grids,
                          n_slots, static_cast<uint32_t>(lanes), static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks),
                          static_cast<uint32_t>(cell_blocks), max_rounds, r->partial.as<RdoqPartial>(),
                          r->results.dev.as<ccd_rdoq_result>(), reinterpret_cast<int64_t*>(r->results.dev.as<char>() + open_off),

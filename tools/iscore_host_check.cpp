@@ -1,6 +1,7 @@
 // iscore_host_check.cpp - the job and partial planning of a ccd_iscore run (cool_chic_amd/csrc/ccd_iscore_plan.hpp, DESIGN.md section
-// 4.19) as a stand-alone CPU program: meant to be built with -fsanitize=address,undefined, host code only (the header has no HIP
-// in it, no device code is compiled, no device is needed, and the sanitizers are never asked of an offload target):
+// 4.19) and the host side of the unit kernels of P / B frames (ccd_inter_job.hpp: job geometry, workgroup counts, launch tables,
+// block layout) as a stand-alone CPU program: meant to be built with -fsanitize=address,undefined, host code only (the headers
+// make no HIP call, no device code is compiled, no device is needed, and the sanitizers are never asked of an offload target):
 //
 //   hipcc --offload-host-only -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //       tools/iscore_host_check.cpp -o iscore_host_check
@@ -9,10 +10,16 @@
 // Seeded frames of every size class (one unit, one-pixel sides, ragged tiles, 1080p, the format's 16 383 limit) with random items:
 // every job's workgroups are those of its tiles, the partial ranges tile [0, total) without gap or overlap in result order, the
 // launches' workgroup counts add up, the classes follow (item, sinc-8), and the refusals (an item of no frame, 2^31 workgroups).
+// ccd_inter_job.hpp over the sides 1, 2, 63, 64, 65, 16 383, the three formats (4:2:0 with even sides), 8 / 10 / 16 bits, P and B:
+// fill_inter_geometry against the expressions it replaced, written out here; inter_blocks against a count of the tiles that hold a
+// unit; put_job_launch's prefix sums and its 2^31 refusal; BlockCursor's sub-blocks aligned to 256 bytes, disjoint, inside the block.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
+#include <utility>
 
+#include "../cool_chic_amd/csrc/ccd_inter_job.hpp"
 #include "../cool_chic_amd/csrc/ccd_iscore_plan.hpp"
 
 #define CHECK(cond)                                                                   \
@@ -22,7 +29,105 @@
 
 using namespace ccd;
 
+// workgroups of a frame by enumeration: the 64 x 4 tiles of the unit raster that hold at least one unit
+static uint32_t blocks_by_count(int h, int w, int cs) {
+    const int uh = h >> cs, uw = w >> cs;
+    uint32_t n = 0;
+    for (int ty = 0; ty * 4 < uh; ++ty)
+        for (int tx = 0; tx * 64 < uw; ++tx) ++n;
+    return n;
+}
+
+static long long check_inter_job() {
+    const int sides[] = {1, 2, 63, 64, 65, 16383}, depths[] = {8, 10, 16};
+    const int32_t flow[4] = {3, -5, -7, 11};
+    long long n = 0;
+    std::vector<InterUnitJob> jobs;
+    for (int h : sides) for (int w : sides) for (int fdt = 0; fdt < 3; ++fdt) for (int bd : depths) for (int ft = 1; ft <= 2; ++ft) {
+        if (fdt == 1 && ((h | w) & 1)) continue;  // 4:2:0: even sides only
+        const int taps = (n % 2) ? 8 : 4;
+        InterUnitJob J;
+        std::memset(&J, 0x5a, sizeof(J));
+        const InterUnitJob before = J;
+        fill_inter_geometry(J, InterFrameDesc{h, w, bd, fdt, ft, taps, flow});
+        // the expressions of make_inter_job / make_dep_recon / make_job before the filler
+        const bool two = ft == 2;
+        const int cs = fdt == 1 ? 1 : 0;
+        CHECK(J.frame_type == ft && J.H == h && J.W == w && J.n_taps == taps);
+        for (int i = 0; i < 4; ++i) CHECK(J.gflow[i] == ((i < 2 || two) ? flow[i] : 0));
+        CHECK(J.chroma_shift == cs && J.wide == (bd > 8) && J.tiles_x == ((w >> cs) + 63) / 64);
+        CHECK(J.maxv == static_cast<float>((1 << bd) - 1));
+        // pointers and mode are the caller's
+        CHECK(J.residue == before.residue && J.motion == before.motion && J.ref0 == before.ref0 && J.ref1 == before.ref1 && J.w0 == before.w0 &&
+              J.w1 == before.w1 && J.plane[0] == before.plane[0] && J.plane[1] == before.plane[1] && J.plane[2] == before.plane[2] && J.mode == before.mode);
+        CHECK(inter_tiles_x(w, cs) == J.tiles_x && inter_blocks(h, w, cs) == blocks_by_count(h, w, cs) && inter_blocks(h, w, cs) >= 1);
+        jobs.push_back(J);
+        // the layout: sizes that hold the planes, and the sub-blocks a candidate of K probe slots carves (ccd_dsens_add_inter)
+        const PlaneLayout lay = plane_layout(h, w, bd, fdt);
+        const size_t hw = static_cast<size_t>(h) * w, chw = cs ? static_cast<size_t>(h / 2) * (w / 2) : hw, sample = bd > 8 ? 2 : 1;
+        CHECK(lay.f32_3 % 256 == 0 && lay.luma % 256 == 0 && lay.chroma % 256 == 0);
+        CHECK(lay.f32_3 >= 12 * hw && lay.f32_3 < 12 * hw + 256 && lay.luma >= hw * sample && lay.luma < hw * sample + 256);
+        CHECK(lay.chroma >= chw * sample && lay.chroma < chw * sample + 256 && lay.planes() == lay.luma + 2 * lay.chroma);
+        if (hw <= 65 * 65) {  // (the cursor only adds: nothing of the block is touched, small blocks say it all)
+            const int K = 3, n_refs = two ? 2 : 1;
+            const size_t total = 2 * n_refs * lay.f32_3 + (K + 1) * lay.planes();
+            Block blk;  // (host memory behind a Block: no pool, no device)
+            blk.p = std::aligned_alloc(256, total);
+            CHECK(blk.p != nullptr);
+            BlockCursor cur(blk);
+            std::vector<std::pair<char*, size_t>> subs;
+            for (int r = 0; r < 2 * n_refs; ++r) subs.emplace_back(reinterpret_cast<char*>(cur.f32(lay)), 12 * hw);
+            for (int k = 0; k <= K; ++k) {
+                void* pl[3];
+                cur.planes(lay, pl);
+                for (int p = 0; p < 3; ++p) subs.emplace_back(static_cast<char*>(pl[p]), (p ? chw : hw) * sample);
+            }
+            char* end = static_cast<char*>(blk.p);
+            for (const auto& sb : subs) {  // in order, aligned, each behind the one before, all inside the block
+                CHECK(reinterpret_cast<uintptr_t>(sb.first) % 256 == 0 && sb.first >= end);
+                std::memset(sb.first, 0, sb.second);  // (under the address sanitizer: inside the allocation)
+                end = sb.first + sb.second;
+            }
+            CHECK(cur.at == static_cast<char*>(blk.p) + total && end <= cur.at);
+            std::free(blk.p);
+        }
+        ++n;
+    }
+    // launch tables: the prefix is the running sum of the jobs' workgroups, a job inside a larger struct counts by its frame
+    TableImage img;
+    JobLaunch L;
+    img.put("x", 1);  // (so that the tables do not start at 0)
+    CHECK(put_job_launch(img, jobs, L) == CCD_OK && L.n_jobs == static_cast<int>(jobs.size()));
+    CHECK(L.jobs % 256 == 0 && L.prefix % 256 == 0 && L.jobs >= 256 && L.prefix >= L.jobs + jobs.size() * sizeof(InterUnitJob));
+    CHECK(img.bytes.size() == L.prefix + (jobs.size() + 1) * sizeof(uint32_t));
+    uint64_t sum = 0;
+    for (size_t i = 0; i <= jobs.size(); ++i) {
+        uint32_t got;
+        std::memcpy(&got, img.bytes.data() + L.prefix + i * sizeof(uint32_t), sizeof(got));
+        CHECK(got == sum);
+        if (i < jobs.size()) {
+            CHECK(std::memcmp(img.bytes.data() + L.jobs + i * sizeof(InterUnitJob), &jobs[i], sizeof(InterUnitJob)) == 0);
+            sum += blocks_by_count(jobs[i].H, jobs[i].W, jobs[i].chroma_shift);
+        }
+    }
+    CHECK(L.n_blocks == sum);
+    std::vector<InterScoreJob> none;
+    CHECK(put_job_launch(img, none, L) == CCD_OK && L.n_jobs == 0 && L.n_blocks == 0);
+    // 2^31 workgroups: 2^20 per 16 383 x 16 383 frame, so 2 047 jobs fit and 2 048 do not
+    InterScoreJob big;
+    std::memset(&big, 0, sizeof(big));
+    fill_inter_geometry(big.recon, InterFrameDesc{16383, 16383, 8, 0, 1, 8, flow});
+    CHECK(put_job_launch(img, std::vector<InterScoreJob>(2047, big), L) == CCD_OK && L.n_blocks == 2047u << 20);
+    CHECK(put_job_launch(img, std::vector<InterScoreJob>(2048, big), L) == CCD_ERR_UNSUPPORTED);
+    DsensDepJob dep;
+    std::memset(&dep, 0, sizeof(dep));
+    dep.recon = big.recon;
+    CHECK(put_job_launch(img, std::vector<DsensDepJob>(2, dep), L) == CCD_OK && L.n_blocks == 2u << 20);
+    return n;
+}
+
 int main() {
+    const long long filled = check_inter_job();
     std::mt19937 rng(419);
     const int sides[] = {1, 2, 3, 4, 5, 63, 64, 65, 67, 70, 127, 128, 130, 131, 1080, 1920, 16383};
     const int n_sides = static_cast<int>(sizeof(sides) / sizeof(sides[0]));
@@ -67,9 +172,9 @@ int main() {
     std::vector<IScoreGeo> big(1, IScoreGeo{16383, 16383, 0, 1});
     std::vector<IScoreSlot> plan;
     uint32_t cls[kIScoreClasses], total = 0;
-    CHECK(iscore_blocks(big[0]) == (1u << 20));
+    CHECK(inter_blocks(big[0].h, big[0].w, big[0].chroma_shift) == (1u << 20));
     CHECK(iscore_plan(big, std::vector<int>(2046, 0), plan, cls, &total) == CCD_OK && total == 2047u << 20);
     CHECK(iscore_plan(big, std::vector<int>(2047, 0), plan, cls, &total) == CCD_ERR_UNSUPPORTED);
-    std::printf("iscore_host_check: %lld jobs planned, all checks passed\n", jobs);
+    std::printf("iscore_host_check: %lld jobs planned, %lld job geometries filled, all checks passed\n", jobs, filled);
     return 0;
 }
