@@ -15,6 +15,11 @@ class _DevArray:
         self._owner = owner  # keeps the batch (and its arena) alive
 
 
+def dev_ptr(array) -> int:
+    """The device address of a _DevArray, or of anything else with a __cuda_array_interface__."""
+    return int(array.__cuda_array_interface__["data"][0])
+
+
 def ptr_array(ptrs: Sequence) -> C.Array:
     """A c_void_p array of the addresses in `ptrs`, in order; None / 0 becomes NULL."""
     return (C.c_void_p * len(ptrs))(*[int(p) if p else None for p in ptrs])

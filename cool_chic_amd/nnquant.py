@@ -85,34 +85,43 @@ def choose(cells: Sequence[Cell]) -> Optional[int]:
     return None if best is None else best[1]
 
 
-def search_steps(price: Callable[[int, List[int]], Sequence[Cell]], has_ifce: bool, sweeps: int = 1,
-                 chosen: Optional[Callable[[int, int], None]] = None):
-    """The selection: every group starts at its finest step; a sweep visits ARM, IFCE (skipped without features), upsampling
-    and synthesis, and gives each the choose() of price(module, current steps) - all pairs of the module's table with the other
-    modules as they stand.  A module without a feasible cell keeps its steps.  Sweeps repeat, up to `sweeps`, until one changes
-    nothing.  `chosen(module, cell index)` is told every choice.  Returns (steps [8], [ModuleTable])."""
-    steps = [writer.q_step_range(g)[0] for g in range(8)]
-    tables: List[ModuleTable] = []
+def _sweep(price, has_ifce: Sequence[bool], sweeps: int, chosen, labels: Sequence[str]):
+    """The selection over len(has_ifce) networks: every group starts at its finest step; a sweep visits network 0's ARM, IFCE
+    (skipped where has_ifce[network] is false), upsampling and synthesis, then the next network's, and gives each the choose() of
+    price(network, module, steps [n][8]) - all pairs of its table, everything else as it stands.  A module without a feasible cell
+    keeps its steps.  Sweeps repeat, up to `sweeps`, until one changes nothing.  `chosen(network, module, cell index)` is told
+    every choice.  Returns (steps [n][8], [(sweep, network, module, cells, chosen)]); labels[network] is for the error's text."""
+    steps = [[writer.q_step_range(g)[0] for g in range(8)] for _ in has_ifce]
+    tables = []
     for sweep in range(max(int(sweeps), 1)):
         changed = False
-        for m, (name, gw, gb) in enumerate(MODULES):
-            if name == "ifce" and not has_ifce:
-                continue
-            cells = list(price(m, list(steps)))
-            if [(c.q_w, c.q_b) for c in cells] != module_cells(m):
-                raise ValueError(f"the {name} table is not the {len(module_cells(m))} pairs of its groups' steps")
-            k = choose(cells)
-            tables.append(ModuleTable(sweep, name, cells, k))
-            if k is None:
-                continue
-            if chosen is not None:
-                chosen(m, k)
-            if (cells[k].q_w, cells[k].q_b) != (steps[gw], steps[gb]):
-                steps[gw], steps[gb] = cells[k].q_w, cells[k].q_b
-                changed = True
+        for net, own in enumerate(steps):
+            for m, (name, gw, gb) in enumerate(MODULES):
+                if name == "ifce" and not has_ifce[net]:
+                    continue
+                cells = list(price(net, m, [list(s) for s in steps]))
+                if [(c.q_w, c.q_b) for c in cells] != module_cells(m):
+                    raise ValueError(f"the {labels[net]}{name} table is not the {len(module_cells(m))} pairs of its groups' steps")
+                k = choose(cells)
+                tables.append((sweep, net, name, cells, k))
+                if k is None:
+                    continue
+                if chosen is not None:
+                    chosen(net, m, k)
+                if (cells[k].q_w, cells[k].q_b) != (own[gw], own[gb]):
+                    own[gw], own[gb] = cells[k].q_w, cells[k].q_b
+                    changed = True
         if not changed:
             break
     return steps, tables
+
+
+def search_steps(price: Callable[[int, List[int]], Sequence[Cell]], has_ifce: bool, sweeps: int = 1,
+                 chosen: Optional[Callable[[int, int], None]] = None):
+    """The selection (_sweep) over one network: price(module, steps [8]), chosen(module, cell index) -> (steps [8], [ModuleTable])."""
+    steps, tables = _sweep(lambda _, m, steps: price(m, steps[0]), [has_ifce], sweeps,
+                           None if chosen is None else lambda _, m, k: chosen(m, k), [""])
+    return steps[0], [ModuleTable(sweep, name, cells, k) for sweep, _, name, cells, k in tables]
 
 
 class _Network(NamedTuple):
@@ -132,6 +141,16 @@ def refused(call, *args, **kwargs):
         return None, True
 
 
+def add_networks(add, nets: Sequence[tuple], *args, **kwargs) -> List[Tuple[int, int]]:
+    """add(header, bytes_nn, *args, **kwargs) of every network: [(index into nets, slot)] of those the library does not refuse."""
+    slots = []
+    for i, net in enumerate(nets):
+        s, no = refused(add, net[0], net[1], *args, **kwargs)
+        if not no:
+            slots.append((i, s))
+    return slots
+
+
 def network_rates(device: int, nets: Sequence[Tuple[CCHeader, bytes]], latent_ptrs: Sequence[int], owner=None, stream: int = 0,
                   raise_status: bool = False) -> list:
     """(total_bits, n_bytes_header) per (header, bytes_nn) over the device latents, None where the library refuses the network:
@@ -141,11 +160,7 @@ def network_rates(device: int, nets: Sequence[Tuple[CCHeader, bytes]], latent_pt
 
     out = [None] * len(nets)
     with EncodeBatch(device) as enc:
-        slots = []
-        for i, (header, bytes_nn) in enumerate(nets):
-            s, no = refused(enc.add_device, header, bytes_nn, latent_ptrs, owner=owner)
-            if not no:
-                slots.append((i, s))
+        slots = add_networks(enc.add_device, nets, latent_ptrs, owner=owner)
         if slots:
             enc.measure(stream)
             enc.wait(stream)
@@ -177,6 +192,53 @@ def build_network(arch: CCHeader, float_values: np.ndarray, steps: Sequence[int]
     return _Network(h, nn, values, feasible)
 
 
+def float_network(arch: CCHeader, float_values, source, name: str = ""):
+    """(float32 parameters in stream order, writer.network_layout(arch)) of a network to search, checked against both."""
+    if tuple(arch.img_size) != tuple(source.img_size):
+        raise ValueError(f"the {name + ' ' if name else ''}architecture is {arch.img_size[0]}x{arch.img_size[1]}, the source "
+                         f"{source.img_size[0]}x{source.img_size[1]}")
+    x = np.ascontiguousarray(float_values, dtype=np.float32).ravel()
+    layout = writer.network_layout(arch)
+    if x.size != sum(layout):
+        raise ValueError("%s%d parameters, the layout wants %d" % (name + ": " if name else "", x.size, sum(layout)))
+    return x, layout
+
+
+def module_candidates(arch: CCHeader, float_values: np.ndarray, steps: Sequence[int], module: int, fast_path_only: bool = False):
+    """(module_cells(module), the build_network of every cell): the module at each pair of its table, the others at `steps`."""
+    _, gw, gb = MODULES[module]
+    pairs = module_cells(module)
+    nets = []
+    for q_w, q_b in pairs:
+        s = list(steps)
+        s[gw], s[gb] = q_w, q_b
+        nets.append(build_network(arch, float_values, s, fast_path_only))
+    return pairs, nets
+
+
+def chunk_size(max_in_flight_bytes: int, arch: CCHeader, module: int) -> int:
+    """Candidates per launch: max_in_flight_bytes over the slot_bytes estimate, at least one."""
+    return max(1, int(max_in_flight_bytes) // NetworkQuantiser.slot_bytes(arch, module))
+
+
+def table_chunk(max_in_flight_bytes: int, arch: CCHeader, need_rate: bool, need_planes: bool) -> int:
+    """Candidates per launch of a table: the smaller chunk_size of the meters that run for it."""
+    return min(chunk_size(max_in_flight_bytes, arch, 0) if need_rate else 1 << 30,
+               chunk_size(max_in_flight_bytes, arch, 2) if need_planes else 1 << 30)
+
+
+def table_cells(pairs: Sequence[Tuple[int, int]], nets: Sequence[Optional[_Network]], priced: dict, cost) -> List[Cell]:
+    """The table's cells: cell i is feasible where `priced` has it, at (mse, bits, cost) = cost(payload bytes, priced[i])."""
+    cells = []
+    for i, (q_w, q_b) in enumerate(pairs):
+        n_nn = len(nets[i].bytes_nn) if nets[i] is not None else -1
+        if i in priced:
+            cells.append(Cell(q_w, q_b, True, n_nn, *cost(n_nn, priced[i])))
+        else:
+            cells.append(Cell(q_w, q_b, False, n_nn, float("nan"), float("nan"), float("nan")))
+    return cells
+
+
 class NetworkQuantiser:
     """search(): the q-step search of one intra frame's networks on one MI355X."""
 
@@ -198,7 +260,7 @@ class NetworkQuantiser:
 
     def chunk_size(self, arch: CCHeader, module: int) -> int:
         """Candidates per launch: max_in_flight_bytes over the slot_bytes estimate, at least one."""
-        return max(1, self.max_in_flight_bytes // self.slot_bytes(arch, module))
+        return chunk_size(self.max_in_flight_bytes, arch, module)
 
     def search(self, arch: CCHeader, float_values: np.ndarray, latent_ptrs: Sequence[int], source, lmbda: float, sweeps: int = 1,
                fast_path_only: bool = False, owner=None) -> QuantisedNetwork:
@@ -207,22 +269,15 @@ class NetworkQuantiser:
         kept alive by `owner`); source: the FrameData the planes are scored against."""
         import torch
 
-        from .batch import FRAME_DATA_TYPES, DecodeBatch
-        from .quality import QualityMeter, _frame_planes
+        from .batch import DecodeBatch
+        from .quality import QualityMeter, _frame_planes, scored_frame_type
         from .rd import RdEvaluator, rd_cost
+        from .rdoq import check_lambda
 
-        if not np.isfinite(float(lmbda)) or float(lmbda) < 0.0:
-            raise ValueError("lmbda must be finite and not negative")
-        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
-            raise ValueError(f"cannot score a {source.frame_data_type} frame")
-        if tuple(arch.img_size) != tuple(source.img_size):
-            raise ValueError(f"the architecture is {arch.img_size[0]}x{arch.img_size[1]}, the source {source.img_size[0]}x{source.img_size[1]}")
-        x = np.ascontiguousarray(float_values, dtype=np.float32).ravel()
-        layout = writer.network_layout(arch)
-        if x.size != sum(layout):
-            raise ValueError("%d parameters, the layout wants %d" % (x.size, sum(layout)))
+        check_lambda(lmbda)
+        fdt = scored_frame_type(source)
+        x, layout = float_network(arch, float_values, source)
         ptrs = [int(p) for p in latent_ptrs]
-        fdt = FRAME_DATA_TYPES.index(source.frame_data_type)
         dev = torch.device(f"cuda:{self.device}")
         st = torch.cuda.current_stream(self.device).cuda_stream
         src_planes = _frame_planes(source, dev)
@@ -251,11 +306,7 @@ class NetworkQuantiser:
             quality meter alone."""
             out = [None] * len(nets)
             with DecodeBatch(self.device) as dec, QualityMeter(self.device) as meter:
-                slots = []
-                for i, net in enumerate(nets):
-                    s, no = refused(dec.add_latents_device, net.header, net.bytes_nn, ptrs, source.bitdepth, fdt, owner=owner)
-                    if not no:
-                        slots.append((i, s))
+                slots = add_networks(dec.add_latents_device, nets, ptrs, source.bitdepth, fdt, owner=owner)
                 if slots:
                     dec.run(st)
                     decoded = [[torch.as_tensor(dec.plane_device(s, p), device=dev) for p in range(3)] for _, s in slots]
@@ -268,17 +319,11 @@ class NetworkQuantiser:
 
         def price(m: int, steps: List[int]) -> List[Cell]:
             t0 = time.perf_counter()
-            _, gw, gb = MODULES[m]
-            pairs = module_cells(m)
-            nets = []
-            for q_w, q_b in pairs:
-                s = list(steps)
-                s[gw], s[gb] = q_w, q_b
-                nets.append(build_network(arch, x, s, fast_path_only))
+            pairs, nets = module_candidates(arch, x, steps, m, fast_path_only)
             t_built = time.perf_counter()
             need_rate = m < 2 or state["total_bits"] is None
             need_planes = m >= 2 or state["sse"] is None
-            chunk = min(self.chunk_size(arch, 0) if need_rate else 1 << 30, self.chunk_size(arch, 2) if need_planes else 1 << 30)
+            chunk = table_chunk(self.max_in_flight_bytes, arch, need_rate, need_planes)
             live = [i for i, n in enumerate(nets) if n is not None and n.feasible]
             priced.clear()
             for at in range(0, len(live), chunk):
@@ -288,14 +333,12 @@ class NetworkQuantiser:
                 for i, ri, ei in zip(part, r, e):
                     if ri is not None and ei is not None:
                         priced[i] = (ri[0], ei, ri[1])
-            cells = []
-            for i, (q_w, q_b) in enumerate(pairs):
-                if i not in priced:
-                    cells.append(Cell(q_w, q_b, False, len(nets[i].bytes_nn) if nets[i] is not None else -1, float("nan"), float("nan"), float("nan")))
-                    continue
-                total_bits, sse, n_hdr = priced[i]
-                mse, bits, cost = rd_cost(sse, n_samples, source.bitdepth, total_bits, len(nets[i].bytes_nn), n_hdr, source.n_pixels, lmbda)
-                cells.append(Cell(q_w, q_b, True, len(nets[i].bytes_nn), mse, bits, cost))
+
+            def cost(n_nn: int, p):
+                total_bits, sse, n_hdr = p
+                return rd_cost(sse, n_samples, source.bitdepth, total_bits, n_nn, n_hdr, source.n_pixels, lmbda)
+
+            cells = table_cells(pairs, nets, priced, cost)
             pricing.append(Pricing(time.perf_counter() - t0, t_built - t0, chunk))
             return cells
 

@@ -19,8 +19,10 @@ from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import writer
+from ._handle import dev_ptr
 from ._lib import CCHeader
-from .nnquant import MODULES, Cell, Pricing, _Network, build_network, choose, module_cells, network_rates, refused
+from .nnquant import (Cell, Pricing, _Network, _sweep, add_networks, build_network, chunk_size, float_network, module_candidates,
+                      network_rates, table_cells, table_chunk)
 
 ROLES = ("residue", "motion")
 
@@ -53,34 +55,11 @@ class QuantisedInterNetworks(NamedTuple):
 
 def search_steps_pair(price: Callable[[int, int, List[List[int]]], Sequence[Cell]], has_ifce: Tuple[bool, bool] = (False, False),
                       sweeps: int = 1, chosen: Optional[Callable[[int, int, int], None]] = None):
-    """nnquant.search_steps over two networks: every group of both starts at its finest step; a sweep visits the residue
-    cool-chic's ARM, IFCE (skipped where has_ifce[role] is false), upsampling and synthesis, then the motion cool-chic's, and gives
-    each the choose() of price(role, module, current steps [2][8]) - all pairs of the module's table, everything else as it
-    stands.  A module without a feasible cell keeps its steps.  Sweeps repeat, up to `sweeps`, until one changes nothing.
-    `chosen(role, module, cell index)` is told every choice.  Returns (steps [2][8], [InterModuleTable])."""
-    steps = [[writer.q_step_range(g)[0] for g in range(8)] for _ in range(2)]
-    tables: List[InterModuleTable] = []
-    for sweep in range(max(int(sweeps), 1)):
-        changed = False
-        for role in range(2):
-            for m, (name, gw, gb) in enumerate(MODULES):
-                if name == "ifce" and not has_ifce[role]:
-                    continue
-                cells = list(price(role, m, [list(s) for s in steps]))
-                if [(c.q_w, c.q_b) for c in cells] != module_cells(m):
-                    raise ValueError(f"the {ROLES[role]} {name} table is not the {len(module_cells(m))} pairs of its groups' steps")
-                k = choose(cells)
-                tables.append(InterModuleTable(sweep, role, name, cells, k))
-                if k is None:
-                    continue
-                if chosen is not None:
-                    chosen(role, m, k)
-                if (cells[k].q_w, cells[k].q_b) != (steps[role][gw], steps[role][gb]):
-                    steps[role][gw], steps[role][gb] = cells[k].q_w, cells[k].q_b
-                    changed = True
-        if not changed:
-            break
-    return steps, tables
+    """nnquant.search_steps over two networks (nnquant._sweep): the residue cool-chic's modules, then the motion cool-chic's, each
+    given the choose() of price(role, module, current steps [2][8]); `chosen(role, module, cell index)` is told every choice.
+    Returns (steps [2][8], [InterModuleTable])."""
+    steps, tables = _sweep(price, has_ifce, sweeps, chosen, [r + " " for r in ROLES])
+    return steps, [InterModuleTable(*t) for t in tables]
 
 
 class InterNetworkQuantiser:
@@ -92,10 +71,8 @@ class InterNetworkQuantiser:
         self.max_in_flight_bytes = int(max_in_flight_bytes)
 
     def chunk_size(self, arch: CCHeader, module: int) -> int:
-        """Candidates per launch: max_in_flight_bytes over NetworkQuantiser.slot_bytes, at least one."""
-        from .nnquant import NetworkQuantiser
-
-        return max(1, self.max_in_flight_bytes // NetworkQuantiser.slot_bytes(arch, module))
+        """Candidates per launch (nnquant.chunk_size of max_in_flight_bytes)."""
+        return chunk_size(self.max_in_flight_bytes, arch, module)
 
     def search(self, frame_type, residue, motion, references: Sequence, global_flow: Sequence[int], warp_filter_size: int, source,
                lmbda: float, sweeps: int = 1, fast_path_only: bool = False, owner=None) -> QuantisedInterNetworks:
@@ -105,38 +82,25 @@ class InterNetworkQuantiser:
         takes them."""
         import torch
 
-        from .batch import FRAME_DATA_TYPES, DecodeBatch
-        from .io import FrameData
+        from .batch import DecodeBatch
         from .iscore import InterScore
-        from .quality import _frame_planes
+        from .quality import _frame_planes, scored_frame_type
         from .rd import rd_cost
-        from .rd_inter import InterRdEvaluator
+        from .rd_inter import InterRdEvaluator, inter_frame_type, padded_global_flow, reference_planes
+        from .rdoq import check_lambda
 
-        ft = {"P": 1, "B": 2}.get(frame_type, frame_type)
-        if ft not in (1, 2):
-            raise ValueError(f"frame_type must be 'P' / 'B' (1 / 2), not {frame_type!r}")
-        if not np.isfinite(float(lmbda)) or float(lmbda) < 0.0:
-            raise ValueError("lmbda must be finite and not negative")
-        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
-            raise ValueError(f"cannot score a {source.frame_data_type} frame")
-        if len(references) < ft:
-            raise ValueError(f"a {'PB'[ft - 1]} frame needs {ft} reference frame(s)")
+        ft = inter_frame_type(frame_type)
+        check_lambda(lmbda)
+        fdt = scored_frame_type(source)
+        dev = torch.device(f"cuda:{self.device}")
+        refs = reference_planes(ft, references, dev)
         archs, xs, ptrs, layouts = [], [], [], []
         for role, (arch, float_values, latent_ptrs) in enumerate((residue, motion)):
-            if tuple(arch.img_size) != tuple(source.img_size):
-                raise ValueError(f"the {ROLES[role]} architecture is {arch.img_size[0]}x{arch.img_size[1]}, the source "
-                                 f"{source.img_size[0]}x{source.img_size[1]}")
-            x = np.ascontiguousarray(float_values, dtype=np.float32).ravel()
-            layout = writer.network_layout(arch)
-            if x.size != sum(layout):
-                raise ValueError("%s: %d parameters, the layout wants %d" % (ROLES[role], x.size, sum(layout)))
+            x, layout = float_network(arch, float_values, source, ROLES[role])
             archs.append(arch); xs.append(x); layouts.append(layout); ptrs.append([int(p) for p in latent_ptrs])
-        fdt = FRAME_DATA_TYPES.index(source.frame_data_type)
-        dev = torch.device(f"cuda:{self.device}")
         st = torch.cuda.current_stream(self.device).cuda_stream
         src = _frame_planes(source, dev)
-        refs = [_frame_planes(r, dev) if isinstance(r, FrameData) else [p for p in r] for r in list(references)[:ft]]
-        gf = ([int(v) for v in global_flow] + [0, 0, 0, 0])[:4]
+        gf = padded_global_flow(global_flow)
         h, w = (int(v) for v in source.img_size)
         bitdepth = int(source.bitdepth)
 
@@ -147,15 +111,11 @@ class InterNetworkQuantiser:
             """The float outputs of the networks over the role's latents: use(dec, [(index into nets, device address)]) runs
             while they are valid; networks the library refuses are left out."""
             with DecodeBatch(self.device) as dec:
-                slots = []
-                for i, net in enumerate(nets):
-                    s, no = refused(dec.add_latents_device, net.header, net.bytes_nn, ptrs[role], 0, 0, owner=owner)
-                    if not no:
-                        slots.append((i, s))
+                slots = add_networks(dec.add_latents_device, nets, ptrs[role], 0, 0, owner=owner)
                 if not slots:
                     return None
                 dec.run(st)
-                out = use(dec, [(i, int(dec.output_device(s).__cuda_array_interface__["data"][0])) for i, s in slots])
+                out = use(dec, [(i, dev_ptr(dec.output_device(s))) for i, s in slots])
                 dec.wait(st)  # a refused device latent raises here (CCD_ERR_VALUE)
                 return out
 
@@ -215,18 +175,12 @@ class InterNetworkQuantiser:
 
         def price(role: int, m: int, steps: List[List[int]]) -> List[Cell]:
             t0 = time.perf_counter()
-            _, gw, gb = MODULES[m]
-            pairs = module_cells(m)
             arch, other = archs[role], 1 - role
-            nets = []
-            for q_w, q_b in pairs:
-                s = list(steps[role])
-                s[gw], s[gb] = q_w, q_b
-                nets.append(build_network(arch, xs[role], s, fast_path_only))
+            pairs, nets = module_candidates(arch, xs[role], steps[role], m, fast_path_only)
             t_built = time.perf_counter()
             need_rate = m < 2 or bits[role] is None
             need_planes = m >= 2 or state["sse"] is None
-            chunk = min(self.chunk_size(arch, 0) if need_rate else 1 << 30, self.chunk_size(arch, 2) if need_planes else 1 << 30)
+            chunk = table_chunk(self.max_in_flight_bytes, arch, need_rate, need_planes)
             # without a decodable partner no pair exists: every cell is infeasible
             live = [i for i, n in enumerate(nets) if n is not None and n.feasible] if cur[other] is not None else []
             priced.clear()
@@ -255,16 +209,13 @@ class InterNetworkQuantiser:
             finally:
                 if score is not None:
                     score.close()
-            cells = []
-            for i, (q_w, q_b) in enumerate(pairs):
-                if i not in priced:
-                    cells.append(Cell(q_w, q_b, False, len(nets[i].bytes_nn) if nets[i] is not None else -1, float("nan"), float("nan"), float("nan")))
-                    continue
-                (total_bits, n_hdr), sse, _ = priced[i]
-                n_nn = len(nets[i].bytes_nn)
-                mse, b, cost = rd_cost(sse, n_samples, bitdepth, total_bits + bits[other][0], n_nn + len(cur[other].bytes_nn),
-                                       n_hdr + bits[other][1], source.n_pixels, lmbda)
-                cells.append(Cell(q_w, q_b, True, n_nn, mse, b, cost))
+
+            def cost(n_nn: int, p):  # of the pair: the partner's bits and bytes as they stand
+                (total_bits, n_hdr), sse, _ = p
+                return rd_cost(sse, n_samples, bitdepth, total_bits + bits[other][0], n_nn + len(cur[other].bytes_nn),
+                               n_hdr + bits[other][1], source.n_pixels, lmbda)
+
+            cells = table_cells(pairs, nets, priced, cost)
             pricing.append(Pricing(time.perf_counter() - t0, t_built - t0, chunk))
             return cells
 

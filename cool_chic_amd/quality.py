@@ -20,6 +20,7 @@ import torch
 
 from ._handle import _Handle
 from ._lib import QualityItem, QualityResult, check, lib
+from .batch import FRAME_DATA_TYPES
 from .io import FrameData
 
 PSNR, MS_SSIM = 1, 2  # CCD_QUALITY_PSNR, CCD_QUALITY_MS_SSIM
@@ -91,6 +92,13 @@ def _frame_planes(fd: FrameData, device: torch.device) -> List[torch.Tensor]:
     from .bitstream.intercoding import _integer_planes
 
     return _integer_planes(fd, device)
+
+
+def scored_frame_type(fd: FrameData) -> int:
+    """The index of the frame's sample format in FRAME_DATA_TYPES; a format that has no planes to score raises."""
+    if fd.frame_data_type not in ("rgb", "yuv420", "yuv444"):
+        raise ValueError(f"cannot score a {fd.frame_data_type} frame")
+    return FRAME_DATA_TYPES.index(fd.frame_data_type)
 
 
 class QualityMeter(_Handle):

@@ -24,13 +24,14 @@ from typing import List, NamedTuple, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from ._handle import dev_ptr
 from ._lib import CCHeader
 from .batch import FRAME_DATA_TYPES, DecodeBatch
 from .dsens import SENTINEL, DistortionDeltas
 from .encoder import EncodeBatch, SlotRate
 from .io import FrameData
-from .quality import FrameQuality, QualityMeter, _frame_planes
-from .rdoq import RdoqStep, StepResult
+from .quality import FrameQuality, QualityMeter, _frame_planes, scored_frame_type
+from .rdoq import RdoqStep, SlotMaps, StepResult, check_lambda, grid_mask, run_step
 
 
 class Candidate(NamedTuple):
@@ -112,9 +113,7 @@ class RdEvaluator:
     def add(self, arch: CCHeader, bytes_nn: bytes, latents_or_ptrs: Sequence[Union[np.ndarray, int]], source: FrameData, owner=None) -> int:
         """A candidate: host latent arrays (uploaded once, here) or device addresses (int8 [h][w] per grid, read at every
         evaluate(); `owner` keeps them alive), and the frame it is scored against."""
-        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
-            raise ValueError(f"cannot score a {source.frame_data_type} frame")
-        fdt = FRAME_DATA_TYPES.index(source.frame_data_type)
+        fdt = scored_frame_type(source)
         on_device = all(isinstance(x, (int, np.integer)) for x in latents_or_ptrs)
         if on_device:
             slot = self._dec.add_latents_device(arch, bytes_nn, latents_or_ptrs, source.bitdepth, fdt, owner=owner)
@@ -272,8 +271,7 @@ class RdEvaluator:
         for s, ptrs in enumerate(self._caller_ptrs):
             if ptrs is None:
                 raise ValueError(f"candidate {s} was added from host arrays: descend() moves device latents the caller owns")
-        if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
-            raise ValueError("lmbda and min_gain must be finite and not negative")
+        check_lambda(lmbda, min_gain)
         if n == 0:
             return []
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -282,23 +280,14 @@ class RdEvaluator:
         for s in range(len(self._rdoq), n):
             f = self._frames[s]
             self._rdoq.add(self._jobs[s][0], FRAME_DATA_TYPES.index(f.frame_data_type), self._caller_ptrs[s])
-        kD, kR, masks = [], [], []
-        for s, f in enumerate(self._frames):
-            d, r = move_scales(sum(int(t.numel()) for t in self._sources[s]), f.bitdepth, f.n_pixels, lmbda)
-            kD.append(d)
-            kR.append(r)
-            n_grids = int(self._jobs[s][0].n_grids)
-            masks.append(sum(1 << g for g in (range(n_grids) if grids is None else grids) if 0 <= g < n_grids))
+        fixed = [(*self.move_scales(s, lmbda), grid_mask(int(arch.n_grids), grids), range(int(arch.n_grids)))
+                 for s, (arch, _) in enumerate(self._jobs)]
         reports: List[List[StepReport]] = []
         for _ in range(int(max_steps)):
-            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True)
-            for s in range(n):  # the maps' addresses are those of this evaluate()
-                n_grids = int(self._jobs[s][0].n_grids)
-                self._rdoq.set_maps(s, [self._dd.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
-                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-            self._rdoq.step(kD, kR, [float(min_gain)] * n, masks, st, rounds=rounds)
-            self._rdoq.wait(st)
-            results = [self._rdoq.result(s) for s in range(n)]
+            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True)  # (the maps' addresses are those of this run)
+            slots = [SlotMaps(kD, kR, mask, [dev_ptr(self._dd.delta_map(s, g)) for g in gs], [dev_ptr(self._enc.delta_map(s, g)) for g in gs])
+                     for s, (kD, kR, mask, gs) in enumerate(fixed)]
+            results = run_step(self._rdoq, st, slots, min_gain, rounds)
             reports.append([StepReport(b, r) for b, r in zip(before, results)])
             if not any(r.n_moves for r in results):
                 break

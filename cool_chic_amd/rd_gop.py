@@ -20,13 +20,13 @@ those; and references that are themselves P / B frames are not supported here (I
 layer and RdoqStep.follow take them."""
 from typing import List, NamedTuple, Optional, Sequence
 
-import numpy as np
 import torch
 
+from ._handle import dev_ptr
 from .batch import FRAME_DATA_TYPES
 from .rd import Candidate, RdEvaluator
 from .rd_inter import InterCandidate, InterRdEvaluator
-from .rdoq import RdoqStep, StepResult
+from .rdoq import RdoqStep, SlotMaps, StepResult, check_lambda, grid_mask, run_step
 
 
 class GopSlotReport(NamedTuple):
@@ -52,10 +52,6 @@ class GopStepReport(NamedTuple):
     def d_sse(self) -> int:
         """What the step did to the summed squared error of all frames, exactly."""
         return sum(s.d_sse + s.dep_sse for s in self.slots)
-
-
-def _ptr(dev_array) -> int:
-    return int(dev_array.__cuda_array_interface__["data"][0])
 
 
 class GopDescent:
@@ -129,8 +125,7 @@ class GopDescent:
     def step(self, lmbda: float, min_gain: float = 0.0, grids: Optional[Sequence[int]] = None, rounds: int = 8) -> GopStepReport:
         """One step as the module's docstring orders it.  `grids`: the grids that may move in the intra and the residue
         cool-chics (all by default; the advice of RdEvaluator.descend about the coarse grids holds)."""
-        if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
-            raise ValueError("lmbda and min_gain must be finite and not negative")
+        check_lambda(lmbda, min_gain)
         intra, inter = self.intra, self.inter
         n_i, n_f = len(intra), len(inter)
         rdoq = self._slots()
@@ -139,32 +134,24 @@ class GopDescent:
         before_f = inter.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=("residue",))  # 2.
         intra.run_distortion_deltas()                                                                   # 3.
         followed = {s for s, _, _ in self._follows}
-        kD, kR, masks = [], [], []
-
-        def mask(n_grids):
-            return sum(1 << g for g in (range(n_grids) if grids is None else grids) if 0 <= g < n_grids)
-
-        for s in range(n_i):
-            d, r = intra.move_scales(s, lmbda)
-            n_grids = int(intra.architecture(s).n_grids)
-            kD.append(d); kR.append(r); masks.append(mask(n_grids))
-            rdoq.set_maps(s, [_ptr(intra.distortion_delta_map(s, g)) for g in range(n_grids)], [_ptr(intra.rate_delta_map(s, g)) for g in range(n_grids)])
-            rdoq.set_dep_maps(s, [_ptr(intra.dependent_delta_map(s, g)) for g in range(n_grids)] if s in followed else None)
-        for s in range(2 * n_f):
-            f = inter.frame(s // 2)
-            d, r = inter.move_scales(s // 2, lmbda)
-            n_grids = int(f.archs[s % 2].n_grids)
-            kD.append(d); kR.append(r); masks.append(mask(n_grids) if s % 2 == 0 else 0)  # the flows are followed as they are
-            dd = [_ptr(inter.distortion_delta_map(s // 2, "residue", g)) for g in range(n_grids)] if s % 2 == 0 else [None] * n_grids
-            rdoq.set_maps(n_i + s, dd, [_ptr(inter.rate_delta_map(s // 2, s % 2, g)) for g in range(n_grids)])
-        rdoq.step(kD, kR, [float(min_gain)] * (n_i + 2 * n_f), masks, st, rounds=rounds)
-        rdoq.wait(st)
         slots = []
-        for s in range(n_i + 2 * n_f):
-            res = rdoq.result(s)
+        for s in range(n_i):
+            gs = range(int(intra.architecture(s).n_grids))
+            slots.append(SlotMaps(*intra.move_scales(s, lmbda), grid_mask(len(gs), grids),
+                                  [dev_ptr(intra.distortion_delta_map(s, g)) for g in gs], [dev_ptr(intra.rate_delta_map(s, g)) for g in gs],
+                                  [dev_ptr(intra.dependent_delta_map(s, g)) for g in gs] if s in followed else None))
+        for s in range(2 * n_f):  # the residues move; the flows are followed as they are
+            k, role = divmod(s, 2)
+            gs = range(int(inter.frame(k).archs[role].n_grids))
+            slots.append(SlotMaps(*inter.move_scales(k, lmbda), grid_mask(len(gs), grids) if role == 0 else 0,
+                                  [dev_ptr(inter.distortion_delta_map(k, "residue", g)) for g in gs] if role == 0 else None,
+                                  [dev_ptr(inter.rate_delta_map(k, role, g)) for g in gs]))
+        results = run_step(rdoq, st, slots, min_gain, rounds)
+        reports = []
+        for s, res in enumerate(results):
             frame, role = (s, "intra") if s < n_i else ((s - n_i) // 2, ("residue", "motion")[(s - n_i) % 2])
-            slots.append(GopSlotReport(frame, role, res.d_sse, rdoq.dep_sse(s), res.d_bits, res))
-        return GopStepReport(before_i, before_f, slots)
+            reports.append(GopSlotReport(frame, role, res.d_sse, rdoq.dep_sse(s), res.d_bits, res))
+        return GopStepReport(before_i, before_f, reports)
 
     def step_moves(self, frame: int, role: str, grid: int):
         """After step(): the move (-1, 0, +1) the last step applied at every latent of the grid (device, int8 [h][w]); `frame` and

@@ -23,14 +23,15 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from ._handle import dev_ptr
 from ._lib import CCHeader, check, lib
 from .batch import FRAME_DATA_TYPES, DecodeBatch
 from .dsens import DistortionDeltas
 from .encoder import EncodeBatch, SlotRate
 from .io import FrameData
-from .quality import FrameQuality, QualityMeter, _frame_planes
+from .quality import FrameQuality, QualityMeter, _frame_planes, scored_frame_type
 from .rd import move_cost_map, move_scales, rd_cost
-from .rdoq import RdoqStep, StepResult
+from .rdoq import RdoqStep, SlotMaps, StepResult, check_lambda, grid_mask, run_step
 
 ROLES = ("residue", "motion")
 
@@ -41,6 +42,25 @@ def _role(role: Union[str, int]) -> int:
     if role in (0, 1):
         return int(role)
     raise ValueError(f"role must be 'residue' / 'motion' (0 / 1), not {role!r}")
+
+
+def inter_frame_type(frame_type: Union[str, int]) -> int:
+    """1 for 'P' / 1, 2 for 'B' / 2: the number of reference frames."""
+    ft = {"P": 1, "B": 2}.get(frame_type, frame_type)
+    if ft not in (1, 2):
+        raise ValueError(f"frame_type must be 'P' / 'B' (1 / 2), not {frame_type!r}")
+    return ft
+
+
+def reference_planes(ft: int, references: Sequence, device: torch.device) -> List[List[torch.Tensor]]:
+    """The frame's `ft` references as device planes: a FrameData is uploaded, three planes are taken as they are."""
+    if len(references) < ft:
+        raise ValueError(f"a {'PB'[ft - 1]} frame needs {ft} reference frame(s)")
+    return [_frame_planes(r, device) if isinstance(r, FrameData) else [p for p in r] for r in list(references)[:ft]]
+
+
+def padded_global_flow(global_flow: Sequence[int]) -> List[int]:
+    return ([int(v) for v in global_flow] + [0, 0, 0, 0])[:4]
 
 
 class InterCandidate(NamedTuple):
@@ -122,22 +142,15 @@ class InterRdEvaluator:
         at every evaluate() and moved in place by descend(); `owner` keeps it alive.  references: one (P) or two (B) reference
         frames, each a FrameData or three integer device planes (torch tensors, kept and read at every evaluate()); source: the
         frame it is scored against, which also gives the bit depth and the sample format.  Returns the frame index."""
-        ft = {"P": 1, "B": 2}.get(frame_type, frame_type)
-        if ft not in (1, 2):
-            raise ValueError(f"frame_type must be 'P' / 'B' (1 / 2), not {frame_type!r}")
-        if source.frame_data_type not in ("rgb", "yuv420", "yuv444"):
-            raise ValueError(f"cannot score a {source.frame_data_type} frame")
-        if len(references) < ft:
-            raise ValueError(f"a {'PB'[ft - 1]} frame needs {ft} reference frame(s)")
+        ft = inter_frame_type(frame_type)
+        scored_frame_type(source)
         dev = torch.device(f"cuda:{self.device}")
+        refs = reference_planes(ft, references, dev)
         src = _frame_planes(source, dev)
-        refs = []
-        for r in list(references)[:ft]:
-            planes = _frame_planes(r, dev) if isinstance(r, FrameData) else [p for p in r]
+        for planes in refs:
             if [tuple(p.shape) for p in planes] != [tuple(p.shape) for p in src] or any(p.dtype != s.dtype or not p.is_cuda or
                                                                                        not p.is_contiguous() for p, s in zip(planes, src)):
                 raise ValueError("a reference must have the frame's plane sizes and sample type, on the device")
-            refs.append(planes)
         archs, nns, ptrs = [], [], []
         for role, (arch, nn, latent_ptrs) in enumerate((residue, motion)):
             if not all(isinstance(x, (int, np.integer)) for x in latent_ptrs):
@@ -154,8 +167,8 @@ class InterRdEvaluator:
             # the rate meter reads the grids where the decode batch keeps them
             self._enc.add_device(archs[role], nns[role], self._dec.latent_ptrs(slot), owner=self._dec)
         planes = [torch.empty_like(p) for p in src]
-        gf = ([int(v) for v in global_flow] + [0, 0, 0, 0])[:4]
-        self._frames.append(_Frame(ft, tuple(archs), tuple(nns), tuple(ptrs), refs, gf, int(warp_filter_size), source, src, planes))
+        self._frames.append(_Frame(ft, tuple(archs), tuple(nns), tuple(ptrs), refs, padded_global_flow(global_flow), int(warp_filter_size),
+                                   source, src, planes))
         self._owners.append(owner)
         return len(self._frames) - 1
 
@@ -172,7 +185,7 @@ class InterRdEvaluator:
     def output_ptr(self, frame: int, role) -> int:
         """The device address of the float output of the role's cool-chic: library memory at a fixed address, rewritten by every
         evaluate()."""
-        return int(self._dec.output_device(2 * int(frame) + _role(role)).__cuda_array_interface__["data"][0])
+        return dev_ptr(self._dec.output_device(2 * int(frame) + _role(role)))
 
     def frame_data_type_index(self, frame: int) -> int:
         return self._fdt(self._frames[int(frame)])
@@ -192,7 +205,7 @@ class InterRdEvaluator:
         def ptrs(planes):
             return (C.c_void_p * 3)(*[p.data_ptr() for p in planes])
 
-        out = [self._dec.output_device(2 * k + r).__cuda_array_interface__["data"][0] for r in range(2)]
+        out = [dev_ptr(self._dec.output_device(2 * k + r)) for r in range(2)]
         check(lib().ccd_inter_reconstruct(self.device, C.c_void_p(st or None), f.frame_type, h, w, f.source.bitdepth, self._fdt(f),
                                           C.c_void_p(out[0]), C.c_void_p(out[1]), ptrs(f.refs[0]), ptrs(f.refs[1]) if f.frame_type == 2 else None,
                                           (C.c_int32 * 4)(*f.global_flow), f.warp_filter_size, ptrs(f.planes)), "ccd_inter_reconstruct")
@@ -203,7 +216,7 @@ class InterRdEvaluator:
         d = self._dd[role]
         for k in range(self._dd_frames[role], len(self._frames)):
             f = self._frames[k]
-            partner = self._dec.output_device(2 * k + 1 - role).__cuda_array_interface__["data"][0]
+            partner = dev_ptr(self._dec.output_device(2 * k + 1 - role))
             d.add_inter(f.archs[role], f.nns[role], self._dec.latent_ptrs(2 * k + role), [t.data_ptr() for t in f.src], f.source.bitdepth,
                         self._fdt(f), f.frame_type, role, partner, [t.data_ptr() for t in f.refs[0]],
                         [t.data_ptr() for t in f.refs[1]] if f.frame_type == 2 else None, f.global_flow, f.warp_filter_size, owner=self._dec)
@@ -295,8 +308,7 @@ class InterRdEvaluator:
             raise ValueError("no role may move")
         if joint and set(order) != {0, 1}:
             raise ValueError("a joint descent moves both roles")
-        if float(min_gain) < 0.0 or not np.isfinite(float(min_gain)) or float(lmbda) < 0.0 or not np.isfinite(float(lmbda)):
-            raise ValueError("lmbda and min_gain must be finite and not negative")
+        check_lambda(lmbda, min_gain)
         if n == 0:
             return []
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -305,64 +317,33 @@ class InterRdEvaluator:
         for s in range(len(self._rdoq), 2 * n):
             f = self._frames[s // 2]
             self._rdoq.add(f.archs[s % 2], self._fdt(f), f.caller_ptrs[s % 2])
-
-        def grids_of(role):
-            g = grids.get(ROLES[role], grids.get(role)) if isinstance(grids, dict) else grids
-            return g
-
-        kD, kR = [], []
-        for s in range(2 * n):
-            f = self._frames[s // 2]
-            d, r = move_scales(sum(int(t.numel()) for t in f.src), f.source.bitdepth, f.source.n_pixels, lmbda)
-            kD.append(d)
-            kR.append(r)
         if joint:
-            return self._descend_joint(lmbda, int(max_steps), float(min_gain), grids_of, kD, kR, rounds, st)
-        reports: List[List[InterStepReport]] = []
-        idle = 0
+            for k in range(self._n_linked, n):
+                self._rdoq.link(2 * k + 1, 2 * k)
+            self._n_linked = n
+        cycle = [(0, 1)] if joint else [(r,) for r in order]  # the roles that move, step after step
+        fixed = []  # per slot: kD, kR, the mask of a step in which its role moves, its grids
+        for s in range(2 * n):
+            n_grids = int(self._frames[s // 2].archs[s % 2].n_grids)
+            g_ok = grids.get(ROLES[s % 2], grids.get(s % 2)) if isinstance(grids, dict) else grids
+            fixed.append((*self.move_scales(s // 2, lmbda), grid_mask(n_grids, g_ok), range(n_grids)))
+        reports, idle = [], 0
         for step in range(int(max_steps)):
-            role = order[step % len(order)]
-            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=(role,))
-            masks = []
-            for s in range(2 * n):
-                n_grids = int(self._frames[s // 2].archs[s % 2].n_grids)
-                if s % 2 != role:
-                    masks.append(0)
-                    self._rdoq.set_maps(s, [None] * n_grids, [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-                    continue
-                g_ok = grids_of(role)
-                masks.append(sum(1 << g for g in (range(n_grids) if g_ok is None else g_ok) if 0 <= g < n_grids))
-                self._rdoq.set_maps(s, [self._dd[role].delta_map(s // 2, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
-                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-            self._rdoq.step(kD, kR, [float(min_gain)] * (2 * n), masks, st, rounds=rounds)
-            self._rdoq.wait(st)
-            results = [self._rdoq.result(2 * k + role) for k in range(n)]
-            reports.append([InterStepReport(b, ROLES[role], r) for b, r in zip(before, results)])
-            idle = 0 if any(r.n_moves for r in results) else idle + 1
-            if idle >= len(order):
-                break
-        return reports
-
-    def _descend_joint(self, lmbda, max_steps, min_gain, grids_of, kD, kR, rounds, st) -> List[List[InterJointStepReport]]:
-        n = len(self._frames)
-        for k in range(self._n_linked, n):
-            self._rdoq.link(2 * k + 1, 2 * k)
-        self._n_linked = n
-        reports: List[List[InterJointStepReport]] = []
-        for _ in range(max_steps):
-            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=ROLES)
-            masks = []
-            for s in range(2 * n):
-                n_grids = int(self._frames[s // 2].archs[s % 2].n_grids)
-                g_ok = grids_of(s % 2)
-                masks.append(sum(1 << g for g in (range(n_grids) if g_ok is None else g_ok) if 0 <= g < n_grids))
-                self._rdoq.set_maps(s, [self._dd[s % 2].delta_map(s // 2, g).__cuda_array_interface__["data"][0] for g in range(n_grids)],
-                                    [self._enc.delta_map(s, g).__cuda_array_interface__["data"][0] for g in range(n_grids)])
-            self._rdoq.step(kD, kR, [min_gain] * (2 * n), masks, st, rounds=rounds)
-            self._rdoq.wait(st)
-            results = [(self._rdoq.result(2 * k), self._rdoq.result(2 * k + 1)) for k in range(n)]
-            reports.append([InterJointStepReport(b, r) for b, r in zip(before, results)])
-            if not any(r.n_moves for pair in results for r in pair):
+            moving = cycle[step % len(cycle)]
+            before = self.evaluate(lmbda, rate_deltas=True, distortion_deltas=True, roles=moving)
+            slots = []
+            for s, (kD, kR, mask, gs) in enumerate(fixed):  # a role that does not move: mask 0, no distortion maps
+                moves = s % 2 in moving
+                slots.append(SlotMaps(kD, kR, mask if moves else 0,
+                                      [dev_ptr(self._dd[s % 2].delta_map(s // 2, g)) for g in gs] if moves else None,
+                                      [dev_ptr(self._enc.delta_map(s, g)) for g in gs]))
+            results = run_step(self._rdoq, st, slots, min_gain, rounds)
+            if joint:
+                reports.append([InterJointStepReport(b, (results[2 * k], results[2 * k + 1])) for k, b in enumerate(before)])
+            else:
+                reports.append([InterStepReport(b, ROLES[moving[0]], results[2 * k + moving[0]]) for k, b in enumerate(before)])
+            idle = 0 if any(r.n_moves for s, r in enumerate(results) if s % 2 in moving) else idle + 1
+            if idle >= len(cycle):  # every role set of the cycle has had a step since the last move
                 break
         return reports
 

@@ -8,7 +8,7 @@ A step may run several rounds (`rounds`): a candidate that lost a cell of its bo
 competes again once the winners' neighbourhoods are out of the way.  The selected set stays pairwise independent and grows
 towards the set a walk over the candidates in key order would take; `StepResult.n_open == 0` says it has got there."""
 import ctypes as C
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from ._handle import _DevArray, _Handle, ptr_array
 from ._lib import CCHeader, RdoqFollow, RdoqResult, check, lib
@@ -22,6 +22,41 @@ class StepResult(NamedTuple):
     d_bits: float   # the sum of the chosen dBits
     d_cost: float   # kD * d_sse + kR * d_bits
     n_open: int = 0  # candidates of the last round that were not selected; 0: the selected set is maximal
+
+
+UNCHANGED = object()  # SlotMaps.dep_ptrs: the slot's dependent maps stay what they are
+
+
+class SlotMaps(NamedTuple):
+    """What run_step gives one slot for one step."""
+    kD: float
+    kR: float
+    mask: int                                   # the grids that may move (grid_mask)
+    dd_ptrs: Optional[Sequence[Optional[int]]]  # per grid the distortion map; None: none, the slot's moves cost their bits
+    dbits_ptrs: Sequence[int]                   # per grid the rate map
+    dep_ptrs: Optional[Sequence[Optional[int]]] = UNCHANGED  # per grid the dependent map, or None: the slot has none
+
+
+def grid_mask(n_grids: int, grids: Optional[Sequence[int]] = None) -> int:
+    """Bit g for every grid g of `grids` (None: all) that exists."""
+    return sum(1 << g for g in (range(n_grids) if grids is None else grids) if 0 <= g < n_grids)
+
+
+def check_lambda(lmbda: float, min_gain: Optional[float] = None) -> None:
+    """A descent's lmbda and min_gain, or a search's lmbda alone (min_gain None): finite and not negative."""
+    if not all(0.0 <= float(v) < float("inf") for v in (lmbda, min_gain or 0.0)):  # (nan fails every comparison)
+        raise ValueError(f"{'lmbda' if min_gain is None else 'lmbda and min_gain'} must be finite and not negative")
+
+
+def run_step(rdoq, stream: int, slots: Sequence[SlotMaps], min_gain: float, rounds: int = 1) -> List[StepResult]:
+    """One step of an RdoqStep whose slots are `slots`, in order: the maps of every slot, step, wait; the result of every slot."""
+    for s, m in enumerate(slots):
+        rdoq.set_maps(s, [None] * len(m.dbits_ptrs) if m.dd_ptrs is None else m.dd_ptrs, m.dbits_ptrs)
+        if m.dep_ptrs is not UNCHANGED:
+            rdoq.set_dep_maps(s, m.dep_ptrs)
+    rdoq.step([m.kD for m in slots], [m.kR for m in slots], [float(min_gain)] * len(slots), [m.mask for m in slots], stream, rounds=rounds)
+    rdoq.wait(stream)
+    return [rdoq.result(s) for s in range(len(slots))]
 
 
 def cell() -> int:
