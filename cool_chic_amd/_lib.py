@@ -265,6 +265,7 @@ SIGNATURES = {
     "ccd_iscore_destroy": (None, [C.c_void_p]),
     "ccd_iscore_add_frame": (C.c_int, [C.c_void_p, C.POINTER(IScoreFrame)]),
     "ccd_iscore_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ccd_iscore_add_refs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "ccd_iscore_clear_items": (C.c_int, [C.c_void_p]),
     "ccd_iscore_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ccd_iscore_wait": (C.c_int, [C.c_void_p, C.c_void_p]),

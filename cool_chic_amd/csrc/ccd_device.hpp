@@ -185,10 +185,11 @@ struct InterUnitJob {
     const float* motion;     // [2 | 4][H][W]
     const float* ref0;       // [3][H][W] f32, launch_planes_to_444 of the reference's planes
     const float* ref1;       // B frames
-    float* w0;               // [3][H][W] the warped reference: written by mode 0 (null: not kept), read by mode 1
-    float* w1;               // B frames
+    float* w0;               // [3][H][W] the warped reference: written by mode 0 (null: not kept), read by mode 1 (and 4)
+    float* w1;               // B frames (read by mode 1 and 3)
     void* plane[3];          // u8 / u16 planes: written by dsens_inter_kernel, the base read by dsens_dep_kernel, else null
-    int32_t mode;            // 0 base: warp and keep, 1 residue probe: the kept warps, 2 motion probe: warp
+    int32_t mode;            // 0 base: warp and keep, 1 residue probe: the kept warps, 2 motion probe: warp; B frames with one
+                             // reference replaced: 3 warp ref0 and read w1, 4 read w0 and warp ref1.  Only mode 0 writes w0 / w1.
     int32_t frame_type, H, W, n_taps;
     int32_t gflow[4];
     int32_t chroma_shift;    // 1 for yuv420
@@ -222,6 +223,16 @@ struct InterScoreJob {
     uint32_t part_first;       // workgroup k of the job owns the partials [3 (part_first + k), 3 (part_first + k) + 3)
     uint32_t pad;
 };
+// One frame's integer planes -> the [3][h][w] f32 tensor the warp reads, as a job of planes_to_444_jobs_kernel (a replaced
+// reference of a reference item): workgroups are 64 x 4 tiles of pixels, tiles_x per row.
+struct PlanesConvJob {
+    const void* p[3];          // u8 / u16 planes, chroma half-size where chroma_half
+    float* out;
+    int32_t h, w, chroma_half, wide;
+    int32_t tiles_x;
+    float maxv;                // 2^bitdepth - 1
+};
+static_assert(sizeof(PlanesConvJob) == 56, "PlanesConvJob is a table entry: host and device agree on its layout");
 // The partials of one job as inter_score_final_kernel sums them: workgroups [first, first + count) of the partial array.
 struct InterScoreRange { uint32_t first, count; };
 // the frame of a job of any of the three kernels

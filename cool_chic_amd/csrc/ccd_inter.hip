@@ -39,16 +39,41 @@ __device__ __forceinline__ void ic_sincos(float a, float* s_out, float* c_out) {
 // Integer planes of a decoded frame -> the [3][H][W] float tensor the warper reads (value = q / (2^bd - 1),
 // 4:2:0 chroma repeated 2x2).
 template <typename T>
-__global__ void planes_to_444_kernel(const T* p0, const T* p1, const T* p2, float* out, int h, int w, int chroma_half, float maxv) {
-    int x, y;
-    tile_pixel(blockIdx.x, blockIdx.y, &x, &y);
-    if (x >= w || y >= h) return;
+__device__ __forceinline__ void planes_to_444_pixel(const T* p0, const T* p1, const T* p2, float* out, int h, int w, int chroma_half, float maxv, int x, int y) {
     const size_t plane = static_cast<size_t>(h) * w, i = static_cast<size_t>(y) * w + x;
     out[i] = static_cast<float>(p0[i]) / maxv;
     const int cw = chroma_half ? w / 2 : w;
     const size_t ci = chroma_half ? static_cast<size_t>(y >> 1) * cw + (x >> 1) : i;
     out[plane + i] = static_cast<float>(p1[ci]) / maxv;
     out[2 * plane + i] = static_cast<float>(p2[ci]) / maxv;
+}
+template <typename T>
+__global__ void planes_to_444_kernel(const T* p0, const T* p1, const T* p2, float* out, int h, int w, int chroma_half, float maxv) {
+    int x, y;
+    tile_pixel(blockIdx.x, blockIdx.y, &x, &y);
+    if (x >= w || y >= h) return;
+    planes_to_444_pixel(p0, p1, p2, out, h, w, chroma_half, maxv, x, y);
+}
+// The same conversion of many frames in one launch (the reference items of a ccd_iscore run): a job is one frame,
+// its workgroups - the 64 x 4 pixel tiles of planes_to_444_kernel - find it in a prefix table.  Every output word has one writer.
+__global__ __launch_bounds__(256) void planes_to_444_jobs_kernel(const PlanesConvJob* __restrict__ jobs, const uint32_t* __restrict__ prefix, int n_jobs) {
+    const int j = entry_of(prefix, n_jobs, blockIdx.x);
+    const PlanesConvJob& C = jobs[j];  // (uniform: scalar loads)
+    const uint32_t local = blockIdx.x - prefix[j], tiles_x = static_cast<uint32_t>(C.tiles_x);
+    int x, y;
+    tile_pixel(local % tiles_x, local / tiles_x, &x, &y);
+    if (x >= C.w || y >= C.h) return;
+    if (C.wide)
+        planes_to_444_pixel(static_cast<const uint16_t*>(C.p[0]), static_cast<const uint16_t*>(C.p[1]), static_cast<const uint16_t*>(C.p[2]), C.out, C.h, C.w,
+                            C.chroma_half, C.maxv, x, y);
+    else
+        planes_to_444_pixel(static_cast<const uint8_t*>(C.p[0]), static_cast<const uint8_t*>(C.p[1]), static_cast<const uint8_t*>(C.p[2]), C.out, C.h, C.w,
+                            C.chroma_half, C.maxv, x, y);
+}
+hipError_t launch_planes_to_444_jobs(const PlanesConvJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, hipStream_t stream) {
+    if (n_jobs <= 0 || n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(planes_to_444_jobs_kernel, dim3(n_blocks), dim3(256), 0, stream, d_jobs, d_prefix, n_jobs);
+    return hipGetLastError();
 }
 
 hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, float* out, int h, int w, int bitdepth,
@@ -386,7 +411,9 @@ hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const in
 // of the quad's rounded samples, then quantise_chroma420): the f32 that inter_recon_kernel stores and planes_kernel loads is the
 // register in between, so the quantised samples are the planes of ccd_inter_reconstruct bit for bit.  What a residue candidate
 // cannot change - the warped references - is computed by the base job (mode 0), kept as f32 and only read by residue jobs (mode 1);
-// a motion job (mode 2) warps.  What becomes of a quantised sample is the kernel's sink.
+// a motion job (mode 2) warps.  A job whose ref0 / ref1 are OTHER planes than the frame's references (a reference item, DESIGN.md
+// 4.22) is a mode 2 job where all of the frame's references are replaced, and mode 3 / 4 where only reference 0 / 1 of a B frame
+// is: that one is warped, the other's kept warp is read.  What becomes of a quantised sample is the kernel's sink.
 __device__ __forceinline__ void di_store(void* plane, size_t at, unsigned v, int wide) {
     if (wide) static_cast<uint16_t*>(plane)[at] = static_cast<uint16_t>(v);
     else static_cast<uint8_t*>(plane)[at] = static_cast<uint8_t>(v);
@@ -406,11 +433,19 @@ __device__ __forceinline__ void di_pixel(const InterUnitJob& J, int y, int x, fl
         // one body for both references (the straight-line f64 evaluations of two inlined warps cost twice the registers); the
         // selects keep w0 / w1 out of indexed private memory
         const int n_refs = two ? 2 : 1;
+        // a reference item with one reference of a B frame replaced (mode 3 / 4) warps that one and reads the other's kept warp
+        const int kept = J.mode == 3 ? 1 : (J.mode == 4 ? 0 : -1);
 #pragma unroll 1
         for (int r = 0; r < n_refs; ++r) {
             float w[3];
-            ic_warp<NT>(r ? J.ref1 : J.ref0, J.H, J.W, r ? J.gflow[2] : J.gflow[0], r ? J.gflow[3] : J.gflow[1], J.n_taps,
-                        J.motion[(2 * r) * plane + i], J.motion[(2 * r + 1) * plane + i], y, x, w);
+            if (r == kept) {
+                const float* k = r ? J.w1 : J.w0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) w[c] = k[c * plane + i];
+            } else {
+                ic_warp<NT>(r ? J.ref1 : J.ref0, J.H, J.W, r ? J.gflow[2] : J.gflow[0], r ? J.gflow[3] : J.gflow[1], J.n_taps,
+                            J.motion[(2 * r) * plane + i], J.motion[(2 * r + 1) * plane + i], y, x, w);
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) { w0[c] = r == 0 ? w[c] : w0[c]; w1[c] = r == 1 ? w[c] : w1[c]; }
         }

@@ -60,6 +60,7 @@ int fused_dec_profile_pre(unsigned long long* out16, int reset);
 // ccd_inter.hip
 hipError_t launch_planes_to_444(const void* p0, const void* p1, const void* p2, float* out, int h, int w, int bitdepth,
                                 int frame_data_type, hipStream_t stream);
+hipError_t launch_planes_to_444_jobs(const PlanesConvJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, hipStream_t stream);
 hipError_t launch_inter_recon(int frame_type, int h, int w, int n_taps, const int* gflow, const float* residue, const float* motion,
                               const float* ref0, const float* ref1, float* out, hipStream_t stream);
 size_t inter_coef_bytes(int frame_type, int h, int w);

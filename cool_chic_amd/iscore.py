@@ -3,7 +3,10 @@ DESIGN.md section 4.19).
 
 A frame is a P / B frame as InterRdEvaluator reconstructs it - the float outputs of its two cool-chics, its references, its source;
 an item is that frame with ONE of the two outputs replaced.  The numbers are those of ccd_inter_reconstruct followed by
-QualityMeter.score_planes, as integers, without a plane being stored."""
+QualityMeter.score_planes, as integers, without a plane being stored.
+
+A reference item (add_refs; section 4.22) is the frame's own pair reconstructed against OTHER reference planes - what a candidate
+of the frame it predicts from decodes to - in the same index space and with the same kind of result."""
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
@@ -16,7 +19,7 @@ def _ptrs3(ptrs: Optional[Sequence[int]]):
 
 
 class InterScore(_Handle):
-    """add_frame() the frames, add() candidates, run() + wait(), then frame_sse() / sse(); clear_items() keeps the frames."""
+    """add_frame() the frames, add() / add_refs() candidates, run() + wait(), then frame_sse() / sse(); clear_items() keeps the frames."""
 
     _destroy = "ccd_iscore_destroy"
 
@@ -42,6 +45,17 @@ class InterScore(_Handle):
         """The frame with the output of its residue (role 0) or motion (role 1) cool-chic replaced by the device f32 tensor at
         `output_ptr` ([4 | 5][h][w] / [2 | 4][h][w]).  Returns the item."""
         item = check(lib().ccd_iscore_add(self._h, int(frame), int(role), C.c_void_p(int(output_ptr) or None)), "ccd_iscore_add")
+        if owner is not None:
+            self._item_owners.append(owner)
+        return item
+
+    def add_refs(self, frame: int, ref0_ptrs: Optional[Sequence[int]] = None, ref1_ptrs: Optional[Sequence[int]] = None, owner=None) -> int:
+        """The frame's base pair against the device integer planes `ref0_ptrs` in place of reference 0 and / or `ref1_ptrs` in
+        place of reference 1 (B frames); None: the frame's own reference.  Layout of add_frame's references; read at every run,
+        never written.  Returns the item, in the index space of add()."""
+        r0 = None if ref0_ptrs is None else _ptrs3(ref0_ptrs)
+        r1 = None if ref1_ptrs is None else _ptrs3(ref1_ptrs)
+        item = check(lib().ccd_iscore_add_refs(self._h, int(frame), r0, r1), "ccd_iscore_add_refs")
         if owner is not None:
             self._item_owners.append(owner)
         return item

@@ -14,7 +14,11 @@ orders (counted exactly, ties to the smaller order) and its own payload size; ti
 the coarser weight step, then the coarser bias step.
 
 The selection (order of the modules, tie-breaks, sweeps, infeasible cells) is `search_steps`, a pure function over a pricing
-callable, so it is testable without a device.  Intra frames only; the two cool-chics of a P / B frame: nnquant_inter.py."""
+callable, so it is testable without a device.  Intra frames only; the two cool-chics of a P / B frame: nnquant_inter.py.
+
+With `dependents` a candidate is also priced through the P / B frames that predict from the frame: the planes a
+plane-moving candidate (upsampling, synthesis) decodes to become reference items of ONE InterScore that holds every dependent, one
+run per chunk, and the cost of a cell is rd.cost_with_dependents.  Depth one: the dependents' own dependents are not followed."""
 import itertools
 import time
 from typing import TYPE_CHECKING, Callable, List, NamedTuple, Optional, Sequence, Tuple
@@ -65,6 +69,21 @@ class QuantisedNetwork(NamedTuple):
     candidate: "Candidate"  # of the result, from RdEvaluator.evaluate
     tables: List[ModuleTable]
     pricing: List[Pricing]  # one per table
+    dependents: tuple = ()  # search(dependents=...): (sse[3], n[3]) of every dependent against the result's planes, in their order
+
+
+class Dependent(NamedTuple):
+    """A P / B frame that predicts from the searched frame (NetworkQuantiser.search(dependents=...)): the frame as
+    InterScore.add_frame takes it, with the searched frame as its reference `which`."""
+    frame_type: int                 # 1 P, 2 B
+    which: int                      # 0 / 1: which of the dependent's references the searched frame is
+    residue_ptr: int                # device f32 [4 | 5][h][w]: the dependent's base residue output
+    motion_ptr: int                 # device f32 [2 | 4][h][w]: its base motion output
+    other_ref_ptrs: Optional[Sequence[int]]  # B frames: the device integer planes of the OTHER reference
+    global_flow: Sequence[int]
+    warp_filter_size: int
+    source: object                  # the dependent's FrameData
+    owner: object = None            # keeps the device memory behind the pointers alive
 
 
 def module_cells(module: int):
@@ -216,15 +235,15 @@ def module_candidates(arch: CCHeader, float_values: np.ndarray, steps: Sequence[
     return pairs, nets
 
 
-def chunk_size(max_in_flight_bytes: int, arch: CCHeader, module: int) -> int:
+def chunk_size(max_in_flight_bytes: int, arch: CCHeader, module: int, n_dependents: int = 0) -> int:
     """Candidates per launch: max_in_flight_bytes over the slot_bytes estimate, at least one."""
-    return max(1, int(max_in_flight_bytes) // NetworkQuantiser.slot_bytes(arch, module))
+    return max(1, int(max_in_flight_bytes) // NetworkQuantiser.slot_bytes(arch, module, n_dependents))
 
 
-def table_chunk(max_in_flight_bytes: int, arch: CCHeader, need_rate: bool, need_planes: bool) -> int:
+def table_chunk(max_in_flight_bytes: int, arch: CCHeader, need_rate: bool, need_planes: bool, n_dependents: int = 0) -> int:
     """Candidates per launch of a table: the smaller chunk_size of the meters that run for it."""
     return min(chunk_size(max_in_flight_bytes, arch, 0) if need_rate else 1 << 30,
-               chunk_size(max_in_flight_bytes, arch, 2) if need_planes else 1 << 30)
+               chunk_size(max_in_flight_bytes, arch, 2, n_dependents) if need_planes else 1 << 30)
 
 
 def table_cells(pairs: Sequence[Tuple[int, int]], nets: Sequence[Optional[_Network]], priced: dict, cost) -> List[Cell]:
@@ -239,6 +258,25 @@ def table_cells(pairs: Sequence[Tuple[int, int]], nets: Sequence[Optional[_Netwo
     return cells
 
 
+def check_dependents(source, dependents) -> list:
+    """The Dependent list of a search over `source`; ValueError for one of another size, format or bit depth, a frame type that is
+    not P / B, a reference index the frame type does not have, a B frame without its other reference."""
+    from .quality import scored_frame_type
+
+    deps = list(dependents or ())
+    own = (tuple(source.img_size), scored_frame_type(source), int(source.bitdepth))
+    for k, d in enumerate(deps):
+        if (tuple(d.source.img_size), scored_frame_type(d.source), int(d.source.bitdepth)) != own:
+            raise ValueError(f"dependent {k} is {d.source.img_size[0]}x{d.source.img_size[1]} {d.source.frame_data_type} at "
+                             f"{d.source.bitdepth} bits, the frame {source.img_size[0]}x{source.img_size[1]} {source.frame_data_type} "
+                             f"at {source.bitdepth} bits")
+        if int(d.frame_type) not in (1, 2) or int(d.which) not in (0, 1) or (int(d.frame_type) == 1 and int(d.which) != 0):
+            raise ValueError(f"dependent {k}: frame_type {d.frame_type} with the frame as its reference {d.which}")
+        if int(d.frame_type) == 2 and d.other_ref_ptrs is None:
+            raise ValueError(f"dependent {k} is a B frame without its other reference's planes")
+    return deps
+
+
 class NetworkQuantiser:
     """search(): the q-step search of one intra frame's networks on one MI355X."""
 
@@ -248,40 +286,71 @@ class NetworkQuantiser:
         self.max_in_flight_bytes = int(max_in_flight_bytes)
 
     @staticmethod
-    def slot_bytes(arch: CCHeader, module: int) -> int:
+    def slot_bytes(arch: CCHeader, module: int, n_dependents: int = 0) -> int:
         """Device bytes one candidate of this module is COUNTED with when chunks are sized - an estimate from the architecture,
         not what the handles allocate (their tables, partial sums and the block pool's rounding come on top; measured 17 %
         above the budget on a 1080p frame): a rate-meter slot (ARM, IFCE: the encoder's pair and payload
-        buffers) or a given-latents decode slot (latents, dense stack, float output, planes)."""
+        buffers) or a given-latents decode slot (latents, dense stack, float output, planes).  n_dependents: a plane-moving
+        candidate is also a reference item of every dependent, 12 bytes per pixel each (its planes as the warp reads them)."""
         n_sym, px = int(arch.n_symbols), int(arch.img_size[0]) * int(arch.img_size[1])
         if module < 2:
             return 16 * n_sym + (64 << 10)
-        return n_sym + px * (4 * int(arch.input_feature_synthesis) + 4 * int(arch.out_channels) + 6) + (64 << 10)
+        return n_sym + px * (4 * int(arch.input_feature_synthesis) + 4 * int(arch.out_channels) + 6 + 12 * int(n_dependents)) + (64 << 10)
 
-    def chunk_size(self, arch: CCHeader, module: int) -> int:
+    def chunk_size(self, arch: CCHeader, module: int, n_dependents: int = 0) -> int:
         """Candidates per launch: max_in_flight_bytes over the slot_bytes estimate, at least one."""
-        return chunk_size(self.max_in_flight_bytes, arch, module)
+        return chunk_size(self.max_in_flight_bytes, arch, module, n_dependents)
 
     def search(self, arch: CCHeader, float_values: np.ndarray, latent_ptrs: Sequence[int], source, lmbda: float, sweeps: int = 1,
-               fast_path_only: bool = False, owner=None) -> QuantisedNetwork:
+               fast_path_only: bool = False, owner=None, dependents: Optional[Sequence[Dependent]] = None) -> QuantisedNetwork:
         """arch: the architecture (the transmitted fields but the networks' are read); float_values: float32 parameters in
         stream order (writer.network_layout); latent_ptrs: device latents as RdEvaluator.add takes them (int8 [h][w] per grid,
-        kept alive by `owner`); source: the FrameData the planes are scored against."""
+        kept alive by `owner`); source: the FrameData the planes are scored against.  dependents: the P / B frames that predict
+        from this frame (Dependent; same size, format and bit depth, else ValueError): every cell's cost becomes
+        rd.cost_with_dependents - an upsampling / synthesis candidate's planes are scored as the dependents' reference, an ARM /
+        IFCE candidate keeps the current network's dependent term as it keeps its sse.  None: nothing changes."""
         import torch
 
-        from .batch import DecodeBatch
-        from .quality import QualityMeter, _frame_planes, scored_frame_type
-        from .rd import RdEvaluator, rd_cost
+        from .quality import _frame_planes, scored_frame_type
         from .rdoq import check_lambda
 
         check_lambda(lmbda)
         fdt = scored_frame_type(source)
+        deps = check_dependents(source, dependents)
         x, layout = float_network(arch, float_values, source)
         ptrs = [int(p) for p in latent_ptrs]
         dev = torch.device(f"cuda:{self.device}")
         st = torch.cuda.current_stream(self.device).cuda_stream
         src_planes = _frame_planes(source, dev)
         n_samples = [int(t.numel()) for t in src_planes]
+        score = None
+        if deps:
+            from .iscore import InterScore
+
+            # every dependent once; the reference the candidates replace is never read through the frame (the source planes
+            # stand in for it), a B frame's other reference is warped once per run by the base pair and kept
+            score = InterScore(self.device)
+            own = [t.data_ptr() for t in src_planes]
+            for d in deps:
+                d_src = _frame_planes(d.source, dev)
+                refs = [own, own]
+                if int(d.frame_type) == 2:
+                    refs[1 - int(d.which)] = [int(p) for p in d.other_ref_ptrs]
+                score.add_frame(int(d.frame_type), int(source.img_size[0]), int(source.img_size[1]), int(source.bitdepth), fdt, int(d.residue_ptr),
+                                int(d.motion_ptr), refs[0], refs[1] if int(d.frame_type) == 2 else None, [t.data_ptr() for t in d_src],
+                                d.global_flow, int(d.warp_filter_size), owner=(d.owner, d_src, src_planes))
+        try:
+            return self._search(arch, x, layout, ptrs, source, lmbda, sweeps, fast_path_only, owner, deps, score, src_planes, n_samples, fdt, dev, st)
+        finally:
+            if score is not None:
+                score.close()
+
+    def _search(self, arch, x, layout, ptrs, source, lmbda, sweeps, fast_path_only, owner, deps, score, src_planes, n_samples, fdt, dev, st):
+        import torch
+
+        from .batch import DecodeBatch
+        from .quality import QualityMeter
+        from .rd import RdEvaluator, cost_with_dependents, rd_cost
 
         def full(net: _Network):
             with RdEvaluator(self.device) as ev:
@@ -289,21 +358,16 @@ class NetworkQuantiser:
                 return ev.evaluate(lmbda)[0]
 
         # what the meter that a module does NOT run would say: the current network's; None until a network has been priced
-        state = {"total_bits": None, "sse": None, "n_bytes_header": None}
-        start = build_network(arch, x, [writer.q_step_range(g)[0] for g in range(8)], fast_path_only)
-        if start is not None and start.feasible:
-            c, no = refused(full, start)
-            if not no:
-                state.update(total_bits=c.rate.total_bits, sse=tuple(c.quality.sse), n_bytes_header=c.rate.n_bytes_header)
+        state = {"total_bits": None, "sse": None, "n_bytes_header": None, "dep": None}
         pricing: List[Pricing] = []
-        priced: dict = {}   # of the table being chosen from: cell index -> (total_bits, sse, n_bytes_header)
+        priced: dict = {}   # of the table being chosen from: cell index -> (total_bits, sse, n_bytes_header, dependents' (sse, n))
 
         def rates(nets: List[_Network]):
             return network_rates(self.device, [(net.header, net.bytes_nn) for net in nets], ptrs, owner, st)
 
         def errors(nets: List[_Network]):
-            """sse per plane per network, None where the library refuses it: the float path over the given latents and the
-            quality meter alone."""
+            """(sse per plane, the dependents' (sse, n) or None) per network, None where the library refuses it: the float path
+            over the given latents and the quality meter alone, and the networks' planes as reference items of every dependent."""
             out = [None] * len(nets)
             with DecodeBatch(self.device) as dec, QualityMeter(self.device) as meter:
                 slots = add_networks(dec.add_latents_device, nets, ptrs, source.bitdepth, fdt, owner=owner)
@@ -311,11 +375,30 @@ class NetworkQuantiser:
                     dec.run(st)
                     decoded = [[torch.as_tensor(dec.plane_device(s, p), device=dev) for p in range(3)] for _, s in slots]
                     meter.score_planes_async(decoded, [src_planes] * len(slots), [source.bitdepth] * len(slots), False, stream=st)
+                    items = []
+                    if score is not None:  # same stream: behind the float path that writes the planes
+                        for planes in decoded:
+                            pp = [t.data_ptr() for t in planes]
+                            items.append([score.add_refs(k, pp if int(d.which) == 0 else None, pp if int(d.which) == 1 else None)
+                                          for k, d in enumerate(deps)])
+                        score.run(st)
                     res = meter.finish()
                     dec.wait(st)
-                    for (i, _), r in zip(slots, res):
-                        out[i] = tuple(int(v) for v in r.sse)
+                    if score is not None:
+                        score.wait(st)
+                    for j, ((i, _), r) in enumerate(zip(slots, res)):
+                        out[i] = (tuple(int(v) for v in r.sse), tuple(score.sse(it) for it in items[j]) if score is not None else None)
+                    if score is not None:
+                        score.clear_items()
             return out
+
+        start = build_network(arch, x, [writer.q_step_range(g)[0] for g in range(8)], fast_path_only)
+        if start is not None and start.feasible:
+            c, no = refused(full, start)
+            if not no:
+                state.update(total_bits=c.rate.total_bits, sse=tuple(c.quality.sse), n_bytes_header=c.rate.n_bytes_header)
+                if score is not None:
+                    state.update(dep=errors([start])[0][1])
 
         def price(m: int, steps: List[int]) -> List[Cell]:
             t0 = time.perf_counter()
@@ -323,32 +406,36 @@ class NetworkQuantiser:
             t_built = time.perf_counter()
             need_rate = m < 2 or state["total_bits"] is None
             need_planes = m >= 2 or state["sse"] is None
-            chunk = table_chunk(self.max_in_flight_bytes, arch, need_rate, need_planes)
+            chunk = table_chunk(self.max_in_flight_bytes, arch, need_rate, need_planes, len(deps))
             live = [i for i, n in enumerate(nets) if n is not None and n.feasible]
             priced.clear()
             for at in range(0, len(live), chunk):
                 part = live[at:at + chunk]
                 r = rates([nets[i] for i in part]) if need_rate else [(state["total_bits"], state["n_bytes_header"])] * len(part)
-                e = errors([nets[i] for i in part]) if need_planes else [state["sse"]] * len(part)
+                e = errors([nets[i] for i in part]) if need_planes else [(state["sse"], state["dep"])] * len(part)
                 for i, ri, ei in zip(part, r, e):
                     if ri is not None and ei is not None:
-                        priced[i] = (ri[0], ei, ri[1])
+                        priced[i] = (ri[0], ei[0], ri[1], ei[1])
 
             def cost(n_nn: int, p):
-                total_bits, sse, n_hdr = p
-                return rd_cost(sse, n_samples, source.bitdepth, total_bits, n_nn, n_hdr, source.n_pixels, lmbda)
+                total_bits, sse, n_hdr, dep = p
+                own = rd_cost(sse, n_samples, source.bitdepth, total_bits, n_nn, n_hdr, source.n_pixels, lmbda)
+                if score is None:
+                    return own
+                return own[0], own[1], cost_with_dependents(own, [(d_sse, d_n, source.bitdepth) for d_sse, d_n in dep])
 
             cells = table_cells(pairs, nets, priced, cost)
             pricing.append(Pricing(time.perf_counter() - t0, t_built - t0, chunk))
             return cells
 
         def chosen(m: int, k: int) -> None:
-            total_bits, sse, n_hdr = priced[k]
-            state.update(total_bits=total_bits, sse=sse, n_bytes_header=n_hdr)
+            total_bits, sse, n_hdr, dep = priced[k]
+            state.update(total_bits=total_bits, sse=sse, n_bytes_header=n_hdr, dep=dep)
 
         steps, tables = search_steps(price, layout[2] > 0, sweeps, chosen)
         net = build_network(arch, x, steps, fast_path_only)
         if net is None or not net.feasible:
             raise ValueError("no feasible network was found: every candidate of the module that holds the start back is infeasible "
                              "(a payload beyond 16 383 bytes, a refused value or, with fast_path_only, an ARM outside the fast path)")
-        return QuantisedNetwork(net.header, net.bytes_nn, net.values, full(net), tables, pricing)
+        result = full(net)
+        return QuantisedNetwork(net.header, net.bytes_nn, net.values, result, tables, pricing, errors([net])[0][1] if score is not None else ())

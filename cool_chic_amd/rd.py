@@ -17,6 +17,13 @@ latents is the decoder's exact integer ARM priced as model bits, 24 - log2(inter
 estimate of training and not the coded bytes (the payload is 0 to 3 words above ceil(total_bits / 32)).  The
 cost is computed on the host in float64 from the device's exact integer squared error and its total_bits.
 
+A candidate of a frame that P / B frames predict from is also priced through them (cost_with_dependents):
+
+    cost_with_dependents = cost + sum over the dependents d of  sse_d / (n_samples_d * (2^bitdepth_d - 1)^2)
+
+the GOP's summed per-frame cost with the dependents' own bits left out - the candidate does not change them - where sse_d is the
+squared error of dependent d reconstructed against the candidate's planes (InterScore.add_refs).  float64, in list order.
+
 Intra frames only: one cool-chic per frame.  P / B frames (two cool-chics and a reconstruction) are not evaluated here;
 ccd_batch_add_latents itself takes any cool-chic."""
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -55,6 +62,17 @@ def rd_cost(sse: Sequence[int], n: Sequence[int], bitdepth: int, total_bits: flo
     mse = float(sum(int(v) for v in sse)) / (float(sum(int(v) for v in n)) * maxv * maxv)
     bits = float(total_bits) + 8.0 * float(int(n_bytes_nn) + int(n_bytes_header))
     return mse, bits, mse + float(lmbda) * bits / float(n_pixels)
+
+
+def cost_with_dependents(own, dependents) -> float:
+    """own: rd_cost's (mse, bits, cost) of the frame; dependents: [(sse[3], n[3], bitdepth)] of the frames that predict from it,
+    each reconstructed against the frame's planes, in registration order.  own.cost plus every dependent's mse (rd_cost's
+    definition), summed in float64 in list order: the definition in this module's docstring."""
+    cost = float(own[2])
+    for sse, n, bitdepth in dependents:
+        maxv = float(2 ** int(bitdepth) - 1)
+        cost += float(sum(int(v) for v in sse)) / (float(sum(int(v) for v in n)) * maxv * maxv)
+    return cost
 
 
 def move_scales(n_samples: int, bitdepth: int, n_pixels: int, lmbda: float):

@@ -861,7 +861,22 @@ int64_t ccd_rdoq_slot_flow_boxes(const ccd_rdoq* r, int slot, int follow, int gr
  * included), a frame_type outside 1..2, a role outside 0..1, a bit depth outside 8..16, a frame_data_type outside 0..2, a frame or
  * item index out of range (or not covered by a finished run), a run in flight; CCD_ERR_VALUE - also before the device is touched -
  * for a filter size ccd_inter_reconstruct refuses, yuv420 with an odd side, a side outside 1..16383.  A refused call leaves the
- * handle as it was. */
+ * handle as it was.
+ *
+ * REFERENCE ITEMS: ccd_iscore_add_refs adds the frame's BASE pair reconstructed against OTHER integer
+ * planes in place of reference 0 (ref0), reference 1 (ref1, B frames) or both - the planes a candidate of the REFERENCE frame
+ * decodes to - in the layout of ccd_inter_reconstruct (u8 at 8 bits, else u16; half-size chroma for yuv420).  A NULL array means
+ * "the frame's own reference".  It returns the item index in the SAME index space as ccd_iscore_add; the result comes from
+ * ccd_iscore_result, ccd_iscore_clear_items drops these items too.  The planes are read at every run and never written.
+ * Scratch: ccd_iscore_add_refs takes 3 h w f32 per replaced reference from the block cache (CCD_ERR_NOMEM otherwise),
+ * ccd_iscore_clear_items and ccd_iscore_destroy give it back.
+ * Launches of a run, in order: the references of the frames (one conversion per reference); the base pairs; the conversion of
+ * the replaced references of ALL reference items (one launch over a job table); the items, role and reference items together
+ * (two launches where sinc-8 and another filter size are both present, as for the base pairs); the final sum.  A reference item
+ * of a B frame with one reference replaced warps only that one and reads the other's warp as the base pair of the same run kept
+ * it; no item writes the kept warps.  A result does not depend on what else the handle holds.
+ * CCD_ERR_ARG - before the device is touched - for a NULL handle, a frame index out of range, both arrays NULL, an array with a
+ * NULL plane in it, ref1 given for a P frame, a run in flight.  A refused call leaves the handle as it was. */
 typedef struct ccd_iscore ccd_iscore;
 typedef struct {
     int32_t frame_type;        /* 1 P, 2 B */
@@ -878,6 +893,7 @@ int ccd_iscore_create(int device, ccd_iscore** out);
 void ccd_iscore_destroy(ccd_iscore* s);
 int ccd_iscore_add_frame(ccd_iscore* s, const ccd_iscore_frame* frame);
 int ccd_iscore_add(ccd_iscore* s, int frame, int role, const float* output);
+int ccd_iscore_add_refs(ccd_iscore* s, int frame, const void* const ref0[3], const void* const ref1[3]);
 int ccd_iscore_clear_items(ccd_iscore* s);
 int ccd_iscore_run(ccd_iscore* s, void* stream);
 int ccd_iscore_wait(ccd_iscore* s, void* stream);

@@ -13,6 +13,10 @@
 // ccd_inter_job.hpp over the sides 1, 2, 63, 64, 65, 16 383, the three formats (4:2:0 with even sides), 8 / 10 / 16 bits, P and B:
 // fill_inter_geometry against the expressions it replaced, written out here; inter_blocks against a count of the tiles that hold a
 // unit; put_job_launch's prefix sums and its 2^31 refusal; BlockCursor's sub-blocks aligned to 256 bytes, disjoint, inside the block.
+// Reference items: every item of a round also is, at random, a role item or a reference item with reference
+// 0, 1 or both replaced; iscore_plan_conv gives one conversion job per replaced reference, in item order, reference 0 first, whose
+// workgroups are the PIXEL tiles of the frame (whatever its format) and tile [0, total) without gap or overlap; iscore_ref_mode is
+// checked against the table of the unit walk's modes; the refusals: an item of no frame, a refs outside 0..3, 2^31 workgroups.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -131,7 +135,9 @@ int main() {
     std::mt19937 rng(419);
     const int sides[] = {1, 2, 3, 4, 5, 63, 64, 65, 67, 70, 127, 128, 130, 131, 1080, 1920, 16383};
     const int n_sides = static_cast<int>(sizeof(sides) / sizeof(sides[0]));
-    long long jobs = 0;
+    long long jobs = 0, conv_jobs = 0;
+    // the unit walk's mode of a reference item: P frames and "both" warp everything (2); a B frame's single replaced reference: 3 / 4
+    CHECK(iscore_ref_mode(1, 1) == 2 && iscore_ref_mode(2, 3) == 2 && iscore_ref_mode(2, 1) == 3 && iscore_ref_mode(2, 2) == 4);
     for (int round = 0; round < 400; ++round) {
         std::vector<IScoreGeo> frames(rng() % 6);
         for (auto& g : frames) {
@@ -160,6 +166,35 @@ int main() {
         }
         CHECK(total == at);
         for (int c = 0; c < kIScoreClasses; ++c) CHECK(cls[c] == per[c]);
+        // the same items as reference items
+        std::vector<IScoreItemGeo> items(item_frame.size());
+        for (size_t i = 0; i < items.size(); ++i) items[i] = IScoreItemGeo{item_frame[i], static_cast<int32_t>(rng() % 4)};
+        std::vector<IScoreConv> conv;
+        uint32_t conv_total = 7;
+        CHECK(iscore_plan_conv(frames, items, conv, &conv_total) == CCD_OK);
+        size_t k = 0;
+        uint64_t conv_at = 0;
+        for (size_t i = 0; i < items.size(); ++i) {
+            const IScoreGeo& g = frames[static_cast<size_t>(items[i].frame)];
+            for (int which = 0; which < 2; ++which) {
+                if (!(items[i].refs >> which & 1)) continue;
+                CHECK(k < conv.size() && conv[k].item == static_cast<int32_t>(i) && conv[k].which == which);
+                CHECK(conv[k].n_blocks == blocks_by_count(g.h, g.w, 0) && conv[k].n_blocks >= 1 && conv[k].block_first == conv_at);
+                conv_at += conv[k].n_blocks;
+                ++k;
+                ++conv_jobs;
+            }
+        }
+        CHECK(k == conv.size() && conv_total == conv_at);
+        if (!items.empty()) {
+            std::vector<IScoreItemGeo> bad = items;
+            bad.back().refs = 4;
+            CHECK(iscore_plan_conv(frames, bad, conv, &conv_total) == CCD_ERR_ARG);
+            bad.back() = IScoreItemGeo{static_cast<int32_t>(frames.size()), 1};
+            CHECK(iscore_plan_conv(frames, bad, conv, &conv_total) == CCD_ERR_ARG);
+            bad.back().frame = -1;
+            CHECK(iscore_plan_conv(frames, bad, conv, &conv_total) == CCD_ERR_ARG);
+        }
         if (!frames.empty()) {  // an item of no frame
             std::vector<int> bad = item_frame;
             bad.push_back(static_cast<int>(frames.size()));
@@ -175,6 +210,12 @@ int main() {
     CHECK(inter_blocks(big[0].h, big[0].w, big[0].chroma_shift) == (1u << 20));
     CHECK(iscore_plan(big, std::vector<int>(2046, 0), plan, cls, &total) == CCD_OK && total == 2047u << 20);
     CHECK(iscore_plan(big, std::vector<int>(2047, 0), plan, cls, &total) == CCD_ERR_UNSUPPORTED);
-    std::printf("iscore_host_check: %lld jobs planned, %lld job geometries filled, all checks passed\n", jobs, filled);
+    // conversion workgroups: 2^20 per 16 383 x 16 383 reference, two per item with both replaced
+    std::vector<IScoreConv> conv;
+    CHECK(iscore_plan_conv(big, std::vector<IScoreItemGeo>(1023, IScoreItemGeo{0, 3}), conv, &total) == CCD_OK && total == 2046u << 20 && conv.size() == 2046);
+    CHECK(iscore_plan_conv(big, std::vector<IScoreItemGeo>(1024, IScoreItemGeo{0, 3}), conv, &total) == CCD_ERR_UNSUPPORTED);
+    CHECK(iscore_plan_conv(big, std::vector<IScoreItemGeo>(5, IScoreItemGeo{0, 0}), conv, &total) == CCD_OK && total == 0 && conv.empty());
+    static_assert(sizeof(PlanesConvJob) == 56 && sizeof(InterUnitJob) == 128, "table entries");
+    std::printf("iscore_host_check: %lld jobs planned, %lld conversion jobs planned, %lld job geometries filled, all checks passed\n", jobs, conv_jobs, filled);
     return 0;
 }

@@ -35,6 +35,9 @@ against the route it replaces, in the same process: kodim14 alone and the 24 str
                     timer) priced one at a time through RdEvaluator (one evaluator per candidate: add, evaluate, close) and the ratio; for the Kodak-size frame at three lambdas
                     the cost, network bytes and PSNR of the searched network beside the stream's own, and after descend(8)
 
+  --networks --dependents  instead of the above: the search of an I frame's networks through the frames that predict from it
+                    (NetworkQuantiser.search(dependents=...)) on the I frame of vid5 and on the 1080p I frame
+                    of the 33-frame GOP, each with its direct dependents, against the same candidates priced one at a time.
   --networks --inter  instead of the above: the same search for the two cool-chics of a P / B frame (InterNetworkQuantiser, DESIGN.md
                     section 4.19) - the P frame of `vid5`, a 1080p P frame grown from it and a B frame of synth.gop1080p (--inter-sets): wall time of one sweep
                     per module and role (median of 5, min, max), candidates per launch, the host share spent building candidates, and
@@ -784,6 +787,198 @@ def measure_networks(hdr, nn, payload, bitdepth, fdt, runs, lmbdas, descend_step
     return res
 
 
+def measure_network_dependents(stream_bytes, runs, lmbdas):
+    """NetworkQuantiser.search(dependents=...) on the first I frame of a video stream with its direct dependents:
+    the tables' wall times over `runs` searches at lmbdas[0]; the yardstick - the same candidates one at a time through calls the
+    parent commit has, RdEvaluator for the frame, ccd_inter_reconstruct + QualityMeter per dependent, candidates built outside the
+    timer; the kernel time of one reference item next to one motion item of a P and of a B dependent; per lambda the summed
+    cost (the frame and its direct dependents) of the networks chosen without and with the dependents."""
+    import ctypes as C
+    import os
+    import tempfile
+    import time
+
+    import numpy as np
+
+    from cool_chic_amd import InterScore, NetworkQuantiser
+    from cool_chic_amd._lib import check, lib
+    from cool_chic_amd.batch import FRAME_DATA_TYPES
+    from cool_chic_amd.bitstream.decode import _split_frame, decode_video
+    from cool_chic_amd.bitstream.header import VideoHeader
+    from cool_chic_amd.bitstream.intercoding import _integer_planes
+    from cool_chic_amd.nnquant import MODULES, Dependent, build_network
+    from cool_chic_amd.quality import QualityMeter, _frame_planes
+    from cool_chic_amd.rd import cost_with_dependents
+
+    st = torch.cuda.current_stream().cuda_stream
+    dev = torch.device("cuda:0")
+    vh = VideoHeader()
+    rest = vh.read_header(stream_bytes)
+    structure = vh.get_coding_structure()
+    split = []
+    for _ in range(len(structure)):
+        fh, ccs, rest = _split_frame(rest)
+        split.append((fh, ccs))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.cool")
+        with open(path, "wb") as f:
+            f.write(stream_bytes)
+        frames = decode_video(path)
+    fh0, ccs0 = split[0]
+    assert fh0.get_value("frame_type") == "I"
+    display = int(structure[0]["display_order"])
+    bitdepth, fdt = fh0.get_value("bitdepth"), FRAME_DATA_TYPES.index(fh0.get_value("frame_data_type"))
+    maxv = 2 ** bitdepth - 1
+    rng = np.random.default_rng(22)
+
+    def noisy(fd):  # the decoded frame plus seeded noise of a few LSB, as measure_networks' source
+        return _planes_to_frame_data([np.clip(p.astype(np.int64) + rng.integers(-3, 4, p.shape), 0, maxv).astype(p.dtype) for p in fd.integer_planes()],
+                                     bitdepth, FRAME_DATA_TYPES[fdt])
+
+    dec = DecodeBatch(0)
+    dec.add(ccs0[0][0].raw, ccs0[0][1], ccs0[0][2], bitdepth, fdt)
+    found = []
+    for k in range(1, len(structure)):
+        refs = [int(r) for r in structure[k]["index_references"]]
+        fh, ccs = split[k]
+        n_refs = "IPB".index(fh.get_value("frame_type"))
+        if display not in refs[:n_refs]:
+            continue
+        first = len(dec)
+        for ch, nn, lat in ccs:
+            dec.add(ch.raw, nn, lat, 0, 0)
+        found.append((k, fh, n_refs, refs[:n_refs], first))
+    dec.run(st); dec.wait(st)
+    arch, nn = dec.header(0), dec.network_bytes(0)
+    latents = [torch.from_numpy(dec.latent(0, g)).cuda() for g in range(arch.n_grids)]
+    ptrs = [t.data_ptr() for t in latents]
+    source = noisy(frames[str(display)])
+    deps, keep = [], []
+    for k, fh, n_refs, refs, first in found:
+        which = refs.index(display)
+        outs = [torch.as_tensor(dec.output_device(first + j), device=dev)[0].clone() for j in range(2)]
+        other = _integer_planes(frames[str(refs[1 - which])], dev) if n_refs == 2 else None
+        d_source = noisy(frames[str(int(structure[k]["display_order"]))])
+        keep.append((outs, other, _frame_planes(d_source, dev)))
+        deps.append(Dependent(n_refs, which, outs[0].data_ptr(), outs[1].data_ptr(), None if other is None else [t.data_ptr() for t in other],
+                              (list(fh.get_value("global_flow")) + [0] * 4)[:4], int(fh.get_value("warp_filter_size")), d_source, owner=keep[-1]))
+    dec.close()
+    H, W = int(arch.img_size[0]), int(arch.img_size[1])
+    floats = writer.dequantise_network(arch, writer.network_values(arch, nn))
+    res = {"size": [H, W], "dependents": len(deps), "of_which_B": sum(d.frame_type == 2 for d in deps), "runs": runs}
+
+    def ptrs3(planes):
+        return (C.c_void_p * 3)(*[p.data_ptr() for p in planes])
+
+    def reconstruct(d, src_planes, planes, out):  # ccd_inter_reconstruct of a dependent against `planes`
+        refs = [planes, planes]
+        if d.frame_type == 2:
+            refs[1 - d.which] = None
+        r = [ptrs3(x) if x is not None else (C.c_void_p * 3)(*d.other_ref_ptrs) for x in refs]
+        check(lib().ccd_inter_reconstruct(0, C.c_void_p(st or None), d.frame_type, H, W, bitdepth, fdt, C.c_void_p(d.residue_ptr), C.c_void_p(d.motion_ptr),
+                                          r[0], r[1] if d.frame_type == 2 else None, (C.c_int32 * 4)(*d.global_flow), d.warp_filter_size, ptrs3(out)),
+              "ccd_inter_reconstruct")
+
+    nq = NetworkQuantiser(0)
+    searches = []
+    for it in range(1 + runs):
+        out = nq.search(arch, floats, ptrs, source, lmbdas[0], owner=latents, dependents=deps)
+        if it > 0:
+            searches.append(out)
+    one = searches[0]
+    steps = [writer.q_step_range(g)[0] for g in range(8)]
+    res["modules"] = {}
+    scratch = [torch.empty_like(p) for p in keep[0][2]]
+    for k, t in enumerate(one.tables):
+        secs = [s.pricing[k].seconds for s in searches]
+        _, gw, gb = next(m for m in MODULES if m[0] == t.module)
+        nets = []
+        for c in t.cells:
+            if c.feasible:
+                s = list(steps)
+                s[gw], s[gb] = c.q_w, c.q_b
+                nets.append(build_network(arch, floats, s))
+        moving = t.module in ("upsampling", "synthesis")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with QualityMeter(0) as meter:
+            for net in nets:  # the yardstick: one candidate at a time through the calls the parent commit has
+                with RdEvaluator(0) as ev:
+                    ev.add(net.header, net.bytes_nn, ptrs, source, owner=latents)
+                    ev.evaluate(lmbdas[0])
+                    if moving:  # (a candidate that moves no plane keeps the current dependent term on both routes)
+                        planes = ev.planes(0)
+                        for d, (_, _, d_src) in zip(deps, keep):
+                            reconstruct(d, d_src, planes, scratch)
+                            meter.score_planes([scratch], [d_src], [bitdepth], ms_ssim=False)
+        alone = time.perf_counter() - t0
+        res["modules"][t.module] = {"candidates": len(t.cells), "feasible": len(nets), "per_launch": one.pricing[k].chunk,
+                                    "sweep_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4), "max": round(max(secs), 4)},
+                                    "one_at_a_time_s": round(alone, 4), "ratio": round(alone / statistics.median(secs), 2)}
+        if t.chosen is not None:
+            steps[gw], steps[gb] = t.cells[t.chosen].q_w, t.cells[t.chosen].q_b
+
+    # one reference item next to one motion item (mode 2) of the same frame: a run with N items less a run with none, over N
+    own_planes = _frame_planes(source, dev)
+    res["item_ms"] = {}
+    n_items = 16
+    for label, ft in (("P", 1), ("B", 2)):
+        pick = [(d, kp) for d, kp in zip(deps, keep) if d.frame_type == ft]
+        if not pick:
+            continue
+        d, (_, _, d_src) = pick[0]
+        o = [t.data_ptr() for t in own_planes]
+        refs = [o, o]
+        if ft == 2:
+            refs[1 - d.which] = list(d.other_ref_ptrs)
+
+        def timed(kind):
+            with InterScore(0) as score:
+                score.add_frame(ft, H, W, bitdepth, fdt, d.residue_ptr, d.motion_ptr, refs[0], refs[1] if ft == 2 else None,
+                                [t.data_ptr() for t in d_src], d.global_flow, d.warp_filter_size)
+                for _ in range(n_items if kind else 0):
+                    if kind == "motion":
+                        score.add(0, 1, d.motion_ptr)
+                    elif kind == "residue":
+                        score.add(0, 0, d.residue_ptr)
+                    elif kind == "both":
+                        score.add_refs(0, o, o)
+                    else:
+                        score.add_refs(0, o if d.which == 0 else None, o if d.which == 1 else None)
+
+                def step():
+                    score.run(st)
+                    score.wait(st)
+                return event_ms(step, runs)
+        base = timed(None)
+        row = {"run_without_items_ms": round(base, 4)}
+        for kind in ("motion", "residue", "ref") + (("both",) if ft == 2 else ()):
+            row[kind + "_item_ms"] = round((timed(kind) - base) / n_items, 4)
+        res["item_ms"][label] = row
+
+    def summed(net):
+        """cost_with_dependents of a search result: its own candidate and the dependents against its planes."""
+        with RdEvaluator(0) as ev, QualityMeter(0) as meter:
+            ev.add(net.header, net.bytes_nn, ptrs, source, owner=latents)
+            c = ev.evaluate(lmbda)[0]
+            terms = []
+            for d, (_, _, d_src) in zip(deps, keep):
+                reconstruct(d, d_src, ev.planes(0), scratch)
+                r = meter.score_planes([scratch], [d_src], [bitdepth], ms_ssim=False)[0]
+                terms.append((tuple(int(v) for v in r.sse), tuple(int(v) for v in r.n), bitdepth))
+            return c.cost, cost_with_dependents((c.mse, c.bits, c.cost), terms)
+
+    res["reached"] = {}
+    for lmbda in lmbdas:
+        row = {}
+        for label, kw in (("without", {}), ("with", {"dependents": deps})):
+            out = nq.search(arch, floats, ptrs, source, lmbda, owner=latents, **kw)
+            own, total = summed(out)
+            row[label] = {"steps": list(out.header.nn_q_step_log2), "bytes_nn": len(out.bytes_nn), "own_cost": own, "summed_cost": total}
+        res["reached"][repr(lmbda)] = row
+    return res
+
+
 def measure_arm_table(ccs, runs, warmup, descent_steps, ifce=False):
     """The ARM parameter table (ifce: the IFCE parameter table) of the cool-chics `ccs` [(header bytes, NN payload, latent payload)] in one
     handle."""
@@ -1050,6 +1245,15 @@ def main():
         if "1080p" in a.inter_sets.split(","):
             line["1080p_P"] = measure_inter_networks(ip_1080p(), 1, runs, a.lmbda)
             line["gop1080p_B"] = measure_inter_networks(synth.gop1080p(2)[0], 2, runs, a.lmbda)
+        print(json.dumps(line))
+        return
+    if a.networks and a.dependents:
+        runs = min(a.runs, 5)
+        line = {"tool": "rd_bench --networks --dependents", "runs": runs}
+        if "vid5" in a.inter_sets.split(","):
+            line["vid5_I"] = measure_network_dependents(synth._golden("vid5")[0], runs, [1e-3, 1e-2])
+        if "1080p" in a.inter_sets.split(","):
+            line["gop1080p33_I"] = measure_network_dependents(synth.gop1080p(32)[0], runs, [1e-3, 1e-2])
         print(json.dumps(line))
         return
     if a.networks:
