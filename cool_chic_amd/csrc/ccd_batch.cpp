@@ -285,6 +285,8 @@ static int run_prologue(ccd_batch* b, hipStream_t st) {
     const int rc = build_launch_tables(b, st);
     if (rc < 0) return rc;
     if (b->params_up && b->params_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->params_up, 0));
+    b->run_stream = st;
+    b->has_run = true;
     return CCD_OK;
 }
 
@@ -345,6 +347,8 @@ int ccd_batch_wait(ccd_batch* b, void* stream) {
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     b->streams.note(st);
+    // the status words and the results are behind the run on the stream the run was given, whichever stream this call names
+    if (b->has_run && b->run_stream != st) HIP_TRY(hipStreamSynchronize(b->run_stream));
     // slots added after the last run have no status yet: the words of the slots that DID run are refreshed all the same (their
     // array and its pinned copy were sized for them)
     const size_t n = std::min(b->slots.size(), static_cast<size_t>(b->n_params_uploaded));

@@ -161,6 +161,7 @@ struct ccd_dsens {
     JobLaunch dep_final;      // dsens_dep_final_kernel over the grids of the candidates with dependents
     bool planned = false;   // the tables describe every candidate
     int pending = 0;        // a run is in flight
+    hipStream_t run_stream = nullptr;  // ... on this stream
     int dead = CCD_OK;      // an add failed half way: the batch holds slots no candidate owns
     int stages = 31;        // ccd_dsens_debug_stages
     StreamSet streams;
@@ -597,6 +598,7 @@ int ccd_dsens_run(ccd_dsens* d, void* stream) {
     }
     const Mirror& T = d->tables;
     d->pending = 1;
+    d->run_stream = st;
     auto reconstruct = [&](const JobLaunch (&L)[2]) -> int {  // one launch per kernel instantiation in use
         for (int i = 0; i < 2; ++i)
             if (launch_dsens_inter(T.dev_at<InterUnitJob>(L[i].jobs), T.dev_at<uint32_t>(L[i].prefix), L[i].n_jobs, L[i].n_blocks, i, st) != hipSuccess)
@@ -681,6 +683,11 @@ int ccd_dsens_wait(ccd_dsens* d, void* stream) {
         HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
         d->pending = 0;
         return CCD_OK;
+    }
+    // the maps are behind the run on the stream the run was given, whichever stream this call names
+    if (d->pending && d->run_stream != static_cast<hipStream_t>(stream)) {
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipStreamSynchronize(d->run_stream));
     }
     const int rc = ccd_batch_wait(d->batch, stream);  // synchronises; the first error of the batch's slots
     const bool ran = d->pending != 0;

@@ -237,6 +237,8 @@ struct ccd_batch {
     // every stream the caller handed to ccd_batch_run_stage / ccd_batch_wait / ccd_batch_copy_*: drained before a block of this
     // batch goes back to the pool (or its tables are replaced)
     ccd::StreamSet streams;
+    hipStream_t run_stream = nullptr;    // the stream of the last ccd_batch_run[_stage]: ccd_batch_wait waits for it too
+    bool has_run = false;
     int drain();                         // ... with this batch's launches on the shared side streams (ccd_batch.cpp)
     // fork / join of the entropy launches over the device's side streams: the EVENTS belong to the batch (two host threads
     // running two batches on one GPU share the side streams, which only serialises their launches, but never an event)

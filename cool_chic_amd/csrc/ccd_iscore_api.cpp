@@ -59,6 +59,7 @@ struct ccd_iscore {
     Block part;                // uint64 [workgroups][3]
     std::vector<IScoreSlot> plan;  // of the run in flight / last finished: frames first, then items
     int pending = 0;
+    hipStream_t run_stream = nullptr;     // the stream of the run in flight
     int done_frames = 0, done_items = 0;  // what the last finished run covered
     StreamSet streams;
 };
@@ -230,6 +231,7 @@ int ccd_iscore_run(ccd_iscore* s, void* stream) {
                                      s->out.dev.as<uint64_t>(), st));
     HIP_TRY(s->out.download(n_results * 3 * sizeof(uint64_t), st));
     s->pending = 1;
+    s->run_stream = st;
     return CCD_OK;
 }
 
@@ -238,6 +240,8 @@ int ccd_iscore_wait(ccd_iscore* s, void* stream) {
     if (!s->pending) return CCD_OK;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    // the results are behind the run on the stream the run was given, whichever stream this call names
+    if (s->run_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(s->run_stream));
     s->pending = 0;
     s->done_frames = static_cast<int>(s->frames.size());
     s->done_items = static_cast<int>(s->items.size());

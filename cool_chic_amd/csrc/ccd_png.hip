@@ -923,6 +923,7 @@ struct ccd_png {
     int flip = 0;
     uint32_t x2n[32];
     int pending = 0;                 // pictures of the pack in flight
+    hipStream_t pack_stream = nullptr;  // ... and the stream it was enqueued on
     int level = CCD_PNG_LITERAL;     // read when a pack is enqueued
     // level 1 workspace
     size_t prev_cap = 0, lz_cap = 0, lzc_cap = 0, flag_cap = 0;
@@ -1102,6 +1103,7 @@ int ccd_png_pack_batch(ccd_png* p, const ccd_png_item* items, int n, void* strea
     if (hipMemcpyAsync(p->h_meta, p->d_meta, static_cast<size_t>(n) * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
         return CCD_ERR_HIP;
     p->pending = n;
+    p->pack_stream = st;
     return CCD_OK;
 }
 
@@ -1109,6 +1111,8 @@ int ccd_png_finish_batch(ccd_png* p, void* stream, int64_t* sizes, int n) {
     if (!p || !sizes || p->pending <= 0 || n != p->pending) return CCD_ERR_ARG;
     if (hipSetDevice(p->device) != hipSuccess) return CCD_ERR_HIP;
     if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) return CCD_ERR_HIP;
+    // the sizes are behind the pack on the stream the pack was given, whichever stream this call names
+    if (p->pack_stream != static_cast<hipStream_t>(stream) && hipStreamSynchronize(p->pack_stream) != hipSuccess) return CCD_ERR_HIP;
     p->pending = 0;
     int rc = CCD_OK;
     for (int i = 0; i < n; ++i) {

@@ -93,6 +93,7 @@ struct ccd_quality {
     Block dev, head_host, out_host;    // scratch (device), its head (pinned), QualityOut[planes] (pinned)
     QualityPlan plan;                  // of the scoring in flight / last finished
     int pending = 0;                   // items of the scoring in flight
+    hipStream_t score_stream = nullptr;  // ... and the stream it was enqueued on
     double g[kQWin];
     StreamSet streams;                 // every stream a scoring was enqueued on
 };
@@ -164,6 +165,7 @@ int ccd_quality_score_batch(ccd_quality* q, const ccd_quality_item* items, int n
     HIP_TRY(launch_quality(B, P.sse_prefix[np], st));
     HIP_TRY(hipMemcpyAsync(q->out_host.p, B.out, np * sizeof(QualityOut), hipMemcpyDeviceToHost, st));
     q->pending = n;
+    q->score_stream = st;
     return CCD_OK;
 }
 
@@ -171,6 +173,8 @@ int ccd_quality_finish_batch(ccd_quality* q, void* stream, ccd_quality_result* r
     if (!q || !results || q->pending <= 0 || n != q->pending) return CCD_ERR_ARG;
     HIP_TRY(hipSetDevice(q->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    // the results are behind the scoring on the stream the scoring was given, whichever stream this call names
+    if (q->score_stream != static_cast<hipStream_t>(stream)) HIP_TRY(hipStreamSynchronize(q->score_stream));
     q->pending = 0;
     const QualityOut* out = q->out_host.as<QualityOut>();
     for (int i = 0; i < n; ++i) {

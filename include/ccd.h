@@ -175,7 +175,9 @@ int ccd_batch_prepare(ccd_batch* b, void* stream);
 int ccd_batch_run(ccd_batch* b, void* stream);
 /* Enqueue only one stage (profiling / tests): 0 entropy, 1 upsampling, 2 synthesis(+integer planes). */
 int ccd_batch_run_stage(ccd_batch* b, void* stream, int stage);
-/* Waits for `stream` and returns the first per-slot decode error (CCD_ERR_INVALID_DATA ...). */
+/* Waits for `stream` - and, where that is another one, for the stream of the last ccd_batch_run[_stage]: the results are behind
+ * the run - and returns the first per-slot decode error (CCD_ERR_INVALID_DATA ...).  The waits of the other handles
+ * (ccd_enc_wait, ccd_dsens_wait, ccd_rdoq_wait, ccd_iscore_wait, ccd_quality_finish_batch, ccd_png_finish[_batch]) do the same. */
 int ccd_batch_wait(ccd_batch* b, void* stream);
 int ccd_batch_slot_status(const ccd_batch* b, int slot);
 /* Raw per-slot counters of the entropy kernel after ccd_batch_wait: [0] status, [1] payload words read,
@@ -313,7 +315,9 @@ int ccd_decode_video(const uint8_t* bitstream, size_t n, int device, ccd_video* 
  * bitdepth == 8 else u16; half-size chroma for yuv420), global_flow = (x, y) integer translation per reference
  * (frame header), warp_filter_size = 2 (bilinear) / 4 (bicubic grid_sample) / 6..16 even (sinc) as in warp.py:49-56.  Writes the integer planes of the frame.
  * CCD_ERR_ARG for a missing buffer or a bit depth outside 8..16, CCD_ERR_VALUE for a filter size or frame_data_type (0..3) out of
- * range and for yuv420 with an odd h or w; all checked before the device is touched. */
+ * range and for yuv420 with an odd h or w; all checked before the device is touched.
+ * The launches go to `stream` and read the inputs in stream order; the call synchronises `stream` before it returns (its scratch
+ * goes back to the block cache), so the planes are written on return. */
 int ccd_inter_reconstruct(int device, void* stream, int frame_type, int h, int w, int bitdepth, int frame_data_type,
                           const float* residue, const float* motion, const void* const* ref0_planes,
                           const void* const* ref1_planes, const int32_t* global_flow, int warp_filter_size,
@@ -379,7 +383,9 @@ void ccd_free(void* p);
  * blocks: any PNG reader decodes exactly the input planes; the bytes differ from PIL's (PNG bytes are not normative).
  * Level CCD_PNG_LITERAL (0, the default of a new handle): literal-only blocks.  Level CCD_PNG_LZ77 (1): every block
  * also searches matches inside itself (LZ77 on the device) and keeps the level-0 coding where
- * that is not smaller, so a level-1 file is never larger than the level-0 file and ccd_png_bound still holds. */
+ * that is not smaller, so a level-1 file is never larger than the level-0 file and ccd_png_bound still holds.
+ * ccd_png_destroy frees the workspace with hipFree, which waits for the device: a pack still in flight on any stream has
+ * finished when it returns. */
 typedef struct ccd_png ccd_png;
 typedef struct {
     const uint8_t *r, *g, *b; /* device planes [h][w] */
@@ -731,7 +737,8 @@ int ccd_debug_lattice_hit(int n, int N, int lo, int hi, uint32_t num, uint32_t d
  * (cost as float32, then slot-wide index first[g] + y w + x); a candidate is selected when it has the smallest key of all
  * candidates whose boxes share a cell with its own, and the candidate with the slot's smallest key always is.  Selected latents
  * are stored as v + s.  Negative or non-finite kD, kR, min_gain, NULL arrays, a slot without maps and a step in flight are
- * CCD_ERR_ARG.  The call only enqueues; ccd_rdoq_wait synchronises.  One step may be in flight per handle.
+ * CCD_ERR_ARG.  The call only enqueues; ccd_rdoq_wait synchronises.  One step may be in flight per handle.  ccd_rdoq_destroy drains
+ * the streams the handle was given.
  * ccd_rdoq_step_rounds: the same step in max_rounds rounds (1 .. ccd_rdoq_max_rounds() = 64, else CCD_ERR_ARG before the handle or
  * the device is looked at); ccd_rdoq_step is max_rounds = 1.  Every candidate starts OPEN and no cell is TAKEN.  In a round (a) an
  * open candidate whose box holds a taken cell becomes BLOCKED for good and claims nothing, (b) the other open candidates compete

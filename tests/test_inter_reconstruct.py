@@ -8,6 +8,7 @@ and tests/inter_reference.py - a float64 restatement of what the reference does,
 two.  The CPU tests hold the oracle to the float64 reference; the GPU tests hold the kernel to the oracle (bit-exact, 16-bit
 planes included, where a one-ulp change of the blend shows) and a subset to the float64 reference."""
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import pytest
@@ -223,10 +224,16 @@ def test_oracle_rejects_invalid_arguments(oracle):
 # ---------------------------------------------------------------------------------------------------------------- GPU
 
 
-def _kernel(c, d):
-    import torch
+class _Inputs(NamedTuple):
+    """The device tensors of one call: the two float outputs, the planes of one or two references, the planes it writes."""
+    residue: object
+    motion: object
+    refs: list
+    out: list
 
-    from cool_chic_amd._lib import check, lib
+
+def _device_inputs(c, d):
+    import torch
 
     res, mot, r0, r1 = d
     dev = torch.device("cuda:0")
@@ -237,19 +244,31 @@ def _kernel(c, d):
 
     refs = [planes(r0)] + ([planes(r1)] if r1 is not None else [])
     out = [torch.zeros(p.shape, dtype=dt, device=dev) for p in r0]
-    res_t = torch.from_numpy(res).to(dev).contiguous()
-    mot_t = torch.from_numpy(mot).to(dev).contiguous()
+    return _Inputs(torch.from_numpy(res).to(dev).contiguous(), torch.from_numpy(mot).to(dev).contiguous(), refs, out)
+
+
+def _launch(c, t, stream):
+    """ccd_inter_reconstruct of the case over the tensors `t` on `stream` (a hipStream_t as an integer, 0: the default stream)."""
+    from cool_chic_amd._lib import check, lib
 
     def ptrs(ps):
         return (C.c_void_p * 3)(*[p.data_ptr() for p in ps])
 
-    torch.cuda.synchronize()
     gf = (C.c_int32 * 4)(*c["gflow"])
-    check(lib().ccd_inter_reconstruct(0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None), c["frame_type"], c["h"],
-                                      c["w"], c["bitdepth"], c["fdt"], C.c_void_p(res_t.data_ptr()), C.c_void_p(mot_t.data_ptr()),
-                                      ptrs(refs[0]), ptrs(refs[1]) if r1 is not None else None, gf, c["n_taps"], ptrs(out)),
+    check(lib().ccd_inter_reconstruct(0, C.c_void_p(stream or None), c["frame_type"], c["h"],
+                                      c["w"], c["bitdepth"], c["fdt"], C.c_void_p(t.residue.data_ptr()), C.c_void_p(t.motion.data_ptr()),
+                                      ptrs(t.refs[0]), ptrs(t.refs[1]) if len(t.refs) == 2 else None, gf, c["n_taps"], ptrs(t.out)),
           "ccd_inter_reconstruct")
-    return [p.to(torch.int32).cpu().numpy().astype(np.uint16) for p in out]
+
+
+def _kernel(c, d, stream=None):
+    """The planes the kernel writes for the case; `stream`: a hipStream_t as an integer, torch's current stream by default."""
+    import torch
+
+    t = _device_inputs(c, d)
+    torch.cuda.synchronize()
+    _launch(c, t, torch.cuda.current_stream(torch.device("cuda:0")).cuda_stream if stream is None else stream)
+    return [p.to(torch.int32).cpu().numpy().astype(np.uint16) for p in t.out]
 
 
 @pytest.mark.gpu
