@@ -318,6 +318,14 @@ struct RdoqGridX {
     const int64_t* dd_dep;              // [2][h][w] the dependent map (ccd_rdoq_set_dep_maps), nullptr: none
     RdoqBox* fbox[kRdoqMaxFollows];     // [h][w] per follow: the flow box of every latent; top > bottom: empty
 };
+// What the reduce launch writes (a kernel argument, by value: it is only stored through).
+struct RdoqSums {
+    RdoqPartial* partial;          // [n_chunks]
+    ccd_rdoq_result* results;      // [n_slots]
+    int64_t* open;                 // [n_slots] candidates still open after the last round
+    int64_t* partial_dep;          // [n_chunks], [n_slots]: the dependent maps' sums, with RdoqStepTables::gx only
+    int64_t* dep_out;
+};
 
 // Upsampling level: stack_in [c_in][h_in][w_in] f32 (or the coarsest int8 grid) ->
 // stack_out [c_in + 1][h_out][w_out]; channel 0 = pre-concat conv of the int8 grid `target`.

@@ -93,26 +93,38 @@ hipError_t launch_dsens_sse(const DsensPass* d_passes, const uint32_t* d_unit_pr
 hipError_t launch_dsens_dep_final(const DsensDepGrid* d_grids, const uint32_t* d_prefix, int n_grids, uint32_t n_blocks, hipStream_t stream);
 // ccd_inter.hip: the reach tables of the follows of one tap-count class
 hipError_t launch_rdoq_reach(const RdoqReachJob* d_jobs, const uint32_t* d_prefix, int n_jobs, uint32_t n_blocks, int sinc8, hipStream_t stream);
-// What a step of a handle with follows or dependent maps launches beyond the tables of launch_rdoq_step (all device pointers).
-struct RdoqFollowLaunch {
-    const RdoqGridX* gx;            // beside the grid table
-    const RdoqSlotX* sx;            // beside the slot table
-    const uint32_t* comp_uid;       // first uids of the slots, component by component, ascending inside one
-    const int32_t* comp_slot;       // ... and their slots
+// The tables of one step (all device pointers), as the host hands them to launch_rdoq_step.  The kernels take the pointers they
+// read as __restrict__ arguments of their own (ccd_rdoq.hip says why), not this struct.
+struct RdoqStepTables {
+    const RdoqGrid* grids;         // [n_grids], slot by slot
+    const RdoqSlot* slots;         // [n_slots]
+    const uint32_t* lane_prefix;   // [n_grids + 1] workgroups of 64 latents, a lane each
+    const uint32_t* big_prefix;    // [n_grids + 1] entries of the `big` lists, a workgroup each
+    const uint32_t* chunk_prefix;  // [n_grids + 1] chunks of kRdoqChunk latents (reduce, phase 0)
+    const uint32_t* cell_prefix;   // [n_slots + 1] workgroups of 64 cells of the rasters' owners (settle)
+    int32_t n_grids, n_slots;
+    uint32_t n_lane_blocks;        // lane_prefix[n_grids]: the workgroups behind them are the waves of the `big` lists
+    // with follows or dependent maps; null, and read by no kernel, without
+    const RdoqGridX* gx;           // beside the grid table
+    const RdoqSlotX* sx;           // beside the slot table
+    const uint32_t* comp_uid;      // first uids of the slots, component by component, ascending inside one
+    const int32_t* comp_slot;      // ... and their slots
+};
+// One step as ccd_rdoq.hip launches it: `rounds` times claim, select (and settle between two rounds), then the two phases of the
+// reduce launch.  t.gx != nullptr (a handle with follows or dependent maps): the reach tables and the flow boxes first, then the
+// following variants of the same launches; the members from reach_jobs on are read only then.
+struct RdoqStepLaunch {
+    RdoqStepTables t;
+    RdoqSums sums;
+    uint32_t n_big, n_chunks, n_cell_blocks;  // the ends of t.big_prefix, t.chunk_prefix, t.cell_prefix
+    int rounds;
     const RdoqReachJob* reach_jobs[2];  // [0] run-time taps, [1] sinc-8
     const uint32_t* reach_prefix[2];
     int n_reach[2];
     uint32_t reach_blocks[2];
     void* reach_mem;                // every reach table of the handle, one block
     size_t reach_bytes;
-    int64_t* partial_dep;           // [n_chunks]
-    int64_t* dep_out;               // [n_slots]
     int stages;                     // ccd_rdoq_debug_stages: 1 memset + reach, 2 flow boxes, 4 rounds + sums (tools/rd_bench.py)
 };
-// ccd_rdoq.hip: `rounds` times claim, select (and settle between two rounds), then the two phases of the reduce launch of one step.
-// follow != nullptr: the reach tables and the flow boxes first, then the following variants of the same launches.
-hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
-                            const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
-                            uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
-                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream, const RdoqFollowLaunch* follow = nullptr);
+hipError_t launch_rdoq_step(const RdoqStepLaunch& L, hipStream_t stream);
 }  // namespace ccd

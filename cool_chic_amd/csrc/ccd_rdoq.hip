@@ -8,22 +8,24 @@
 // Inputs are the two delta maps of every grid (distortion: int64, rate: float32) and, per latent, its influence box in cells
 // of the slot's claim raster (built on the host by the code behind ccd_rdoq_influence_box).  Two latents whose boxes share no
 // cell neither share a symbol of the rate model nor a sample of the planes, so their deltas add.
-//   rdoq_claim_kernel   round 0: the cost of both moves of a latent, its better move, whether that is a candidate, its 64-bit key
-//                       (cost as an ordered float, then the latent's number); later rounds: the open candidates, the same key.
-//                       An open candidate with a taken cell in its box becomes blocked and claims nothing (round 0 has nothing to
-//                       test: no cell is taken yet); every other one does atomicMin of the key into every cell of its box.  The smallest key wins a cell whatever the order
-//                       of the atomics.
-//   rdoq_select_kernel  an open candidate that finds its own key in every cell of its box is selected: the latent is stored as
-//                       v + s (a byte store into the caller's grid), the move map gets s; round 0 gives every other latent's
-//                       entry 0.
-//   rdoq_settle_kernel  between two rounds, a lane per cell: a cell whose key belongs to a candidate selected in this round
-//                       becomes taken, and the claim word goes back to all ones.
-//   rdoq_reduce_kernel  phase 0: a workgroup sums candidates, moves, open candidates, dD and dBits of one chunk of one grid;
-//                       phase 1: a wave per slot adds the chunks grid by grid, writes the result, stores all ones into the
-//                       claim raster and zeros into the taken raster.
+//   rdoq_step_kernel<kSelect, kFirst, kFollow>   claim and select, one body (step_latent):
+//     claim   round 0 (kFirst): the cost of both moves of a latent, its better move, whether that is a candidate, its 64-bit key
+//             (cost as an ordered float, then the latent's number); later rounds: the open candidates, the same key.  An open
+//             candidate with a taken cell in its box becomes blocked and claims nothing (round 0 has nothing to test: no cell is
+//             taken yet); every other one does atomicMin of the key into every cell of its box.  The smallest key wins a cell
+//             whatever the order of the atomics.
+//     select  an open candidate that finds its own key in every cell of its box is selected: the latent is stored as v + s (a
+//             byte store into the caller's grid), the move map gets s; round 0 gives every other latent's entry 0.
+//   rdoq_settle_kernel<kFollow>   between two rounds, a lane per cell: a cell whose key belongs to a candidate selected in this
+//             round becomes taken, and the claim word goes back to all ones.
+//   rdoq_reduce_kernel<kFollow>   phase 0: a workgroup sums candidates, moves, open candidates, dD and dBits of one chunk of one
+//             grid; phase 1: a wave per slot adds the chunks grid by grid, writes the result, stores all ones into the claim
+//             raster and zeros into the taken raster.
 // Work is dealt out by cells: a workgroup is one wave, and it is either 64 latents of one grid, a lane each, for boxes of
-// up to kRdoqLaneCells cells, or ONE latent with a larger box (the grid's `big` list), the lanes over its cells.  A workgroup
-// finds its grid by bisection of a prefix table, as the dsens kernels do.
+// up to kRdoqLaneCells cells, or ONE latent with a larger box (the grid's `big` list), the lanes over its cells.  Both are the
+// same body, step_latent<kWave>: the box is walked by the three helpers set_taken / set_claim / set_mine, which deal its cells
+// out with walk_cells<kWave>; the wave joins its lanes' answers with __any / __all and lets lane 0 store.  A workgroup finds its
+// grid by bisection of a prefix table, as the dsens kernels do.
 //
 // The rasters.  claim needs all ones in the claim raster and the cells taken so far in the taken raster.  Inside one launch a
 // word of either sees one kind of access: claim does plain loads of taken and atomics on the claim words; select does plain
@@ -44,7 +46,7 @@
 //
 // Components (ccd_rdoq_follow).  A candidate of a following slot claims its CLAIM SET: its own box in its group's
 // rasters and, per follow, its flow box in the rasters of the follow's target (RdoqSlotX / RdoqGridX, tables beside RdoqSlot /
-// RdoqGrid that only the *_follow kernels read).  The slots that links or follows connect share one numbering of their latents,
+// RdoqGrid that only the kFollow instantiations read).  The slots that links or follows connect share one numbering of their latents,
 // so a key still names one candidate wherever it stands.  The rasters of a group are now reached from every slot of its
 // component, and a word still sees one kind of access per launch: in claim, atomicMin on claim words and plain loads of taken,
 // from any slot of the component; in select, plain loads of claim words; in settle, one lane per cell of the rasters' OWNER,
@@ -138,184 +140,114 @@ __device__ __forceinline__ void walk_cells(const Cells& c, uint32_t cells_w, uin
             for (uint32_t q = 0; q < c.bw; ++q) fn(static_cast<size_t>(c.top + r) * cells_w + c.left + q);
     }
 }
-// The part of latent i's claim set that lies in the rasters of its follows' targets: is a cell of it taken,
-// claim every cell, does the key stand in every cell.  In a wave the answer is this lane's share.
-template <bool kWave>
-__device__ __forceinline__ bool flow_taken(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane) {
+// The rectangles of latent i's claim set with their rasters: its own box in its group's and, kFollow, its flow boxes in those of its
+// follows' targets (X, SX: the entries beside G and S, null and never read otherwise).  fn answers for the own
+// box whether the flow boxes are still to be walked: where the own box has decided, as for nearly every open candidate of a
+// select, their tables are not even loaded.
+template <bool kFollow, typename Fn>
+__device__ __forceinline__ void claim_set(const Cells& own, const RdoqSlot& S, const RdoqGridX* X, const RdoqSlotX* SX, uint32_t i, Fn&& fn) {
+    if (!fn(own, S.raster, S.taken)) return;
+    if constexpr (kFollow)
+        for (int k = 0; k < SX->n_follows; ++k) fn(flow_cells(X->fbox[k][i], S), SX->follow[k].raster, SX->follow[k].taken);
+}
+// Is a cell of the claim set taken, claim every cell, does the key stand in every cell.  In a wave the answer is this lane's share.
+template <bool kWave, bool kFollow>
+__device__ __forceinline__ bool set_taken(const Cells& own, const RdoqSlot& S, const RdoqGridX* X, const RdoqSlotX* SX, uint32_t i, uint32_t lane) {
     bool hit = false;
-    for (int k = 0; k < SX.n_follows; ++k) {
-        const uint8_t* taken = SX.follow[k].taken;
-        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { hit = hit || taken[at] != 0; });
-    }
+    claim_set<kFollow>(own, S, X, SX, i, [&](const Cells& c, const unsigned long long*, const uint8_t* taken) {
+        walk_cells<kWave>(c, S.cells_w, lane, [&](size_t at) { hit = hit || taken[at] != 0; });
+        return !hit;
+    });
     return hit;
 }
-template <bool kWave>
-__device__ __forceinline__ void flow_claim(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane, unsigned long long key) {
-    for (int k = 0; k < SX.n_follows; ++k) {
-        unsigned long long* raster = SX.follow[k].raster;
-        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { atomicMin(&raster[at], key); });
-    }
+template <bool kWave, bool kFollow>
+__device__ __forceinline__ void set_claim(const Cells& own, const RdoqSlot& S, const RdoqGridX* X, const RdoqSlotX* SX, uint32_t i, uint32_t lane,
+                                          unsigned long long key) {
+    claim_set<kFollow>(own, S, X, SX, i, [&](const Cells& c, unsigned long long* raster, const uint8_t*) {
+        walk_cells<kWave>(c, S.cells_w, lane, [&](size_t at) { atomicMin(&raster[at], key); });
+        return true;
+    });
 }
-template <bool kWave>
-__device__ __forceinline__ bool flow_mine(const RdoqGridX& X, const RdoqSlotX& SX, const RdoqSlot& S, uint32_t i, uint32_t lane, unsigned long long key) {
+template <bool kWave, bool kFollow>
+__device__ __forceinline__ bool set_mine(const Cells& own, const RdoqSlot& S, const RdoqGridX* X, const RdoqSlotX* SX, uint32_t i, uint32_t lane,
+                                         unsigned long long key) {
     bool mine = true;
-    for (int k = 0; k < SX.n_follows; ++k) {
-        const unsigned long long* raster = SX.follow[k].raster;
-        walk_cells<kWave>(flow_cells(X.fbox[k][i], S), S.cells_w, lane, [&](size_t at) { mine = mine && raster[at] == key; });
-    }
+    claim_set<kFollow>(own, S, X, SX, i, [&](const Cells& c, const unsigned long long* raster, const uint8_t*) {
+        walk_cells<kWave>(c, S.cells_w, lane, [&](size_t at) { mine = mine && raster[at] == key; });
+        return mine;
+    });
     return mine;
 }
 
+// One body for both work splits.  kWave == false: a lane per latent, 64 latents of one grid per workgroup; kWave == true: one
+// latent of a `big` list, the lanes over the cells of its claim set - every lane reads the pick byte and the latent (best_move)
+// before lane 0 stores either (one wave, program order), the lanes' answers meet in __any / __all, and lane 0 alone stores.
 // kSelect == false: claim.  kSelect == true: select and apply.  Round 0 (kFirst) finds the candidates; a later round reads their
 // state from the pick bytes and forms an open candidate's key again: its latent and the maps are what they were.
-// kFollow: "the box" is the claim set - the own box and, in the rasters of the follows' targets, the flow boxes (gx, sx: the
-// tables beside grids and slots; null and never read otherwise).
-template <bool kSelect, bool kFirst, bool kFollow>
-__device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                          const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix, int n_grids,
-                                          uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx, const RdoqSlotX* __restrict__ sx) {
+// kFollow: "the box" is the claim set (claim_set above).
+template <bool kWave, bool kSelect, bool kFirst, bool kFollow>
+__device__ __forceinline__ void step_latent(const RdoqGrid& G, const RdoqSlot& S, const RdoqGridX* __restrict__ X, const RdoqSlotX* __restrict__ SX,
+                                            uint32_t i) {
     const uint32_t lane = threadIdx.x;
-    if (blockIdx.x < n_lane_blocks) {  // a lane per latent
-        const int e = entry_of(lane_prefix, n_grids, blockIdx.x);
-        const RdoqGrid& G = grids[e];
-        const RdoqSlot& S = slots[G.slot];
-        const RdoqGridX* X = kFollow ? gx + e : nullptr;
-        const RdoqSlotX* SX = kFollow ? sx + G.slot : nullptr;
-        const uint32_t i = (blockIdx.x - lane_prefix[e]) * 64u + lane;
-        if (i >= G.n) return;
-        const Cells c = cells_of(G.box[i], S);
-        if (c.n > kRdoqLaneCells) return;  // a wave's
-        if (!kSelect) {
-            Move m;
-            uint32_t pick;
-            if (kFirst) {
-                m = best_move<kFollow>(G, S, X, i);
-                pick = static_cast<uint32_t>(m.pick);
-            } else {
-                pick = G.pick[i];
-                if (!is_open(pick)) return;
-                m = best_move<kFollow>(G, S, X, i);
-            }
-            bool blocked = false;
-            if (!kFirst)  // (no cell is taken before the first round)
-                for (uint32_t r = 0; r < c.bh; ++r)
-                    for (uint32_t q = 0; q < c.bw; ++q) blocked = blocked || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
-            if constexpr (kFollow && !kFirst) blocked = blocked || flow_taken<false>(*X, *SX, S, i, lane);
-            if (blocked) pick |= kRdoqBlocked;
-            if (kFirst || blocked) G.pick[i] = static_cast<uint8_t>(pick);
-            if (pick && !blocked)
-                for (uint32_t r = 0; r < c.bh; ++r)
-                    for (uint32_t q = 0; q < c.bw; ++q) atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
-            if constexpr (kFollow)
-                if (pick && !blocked) flow_claim<false>(*X, *SX, S, i, lane, m.key);
-        } else {
-            int s = 0;
-            const uint32_t pick = G.pick[i];
-            if (is_open(pick)) {
-                const Move m = best_move<kFollow>(G, S, X, i);
-                bool mine = true;
-                for (uint32_t r = 0; r < c.bh; ++r)
-                    for (uint32_t q = 0; q < c.bw; ++q) mine = mine && S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] == m.key;
-                if constexpr (kFollow) mine = mine && flow_mine<false>(*X, *SX, S, i, lane, m.key);
-                if (mine) {
-                    s = m.s;
-                    G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
-                    G.pick[i] = static_cast<uint8_t>(pick | kRdoqSelected);
-                }
-            }
-            if (kFirst || s) G.moves[i] = static_cast<int8_t>(s);
-        }
-        return;
-    }
-    // one latent, the lanes over its cells
-    const uint32_t u = blockIdx.x - n_lane_blocks;
-    const int e = entry_of(big_prefix, n_grids, u);
-    const RdoqGrid& G = grids[e];
-    const RdoqSlot& S = slots[G.slot];
-    const RdoqGridX* X = kFollow ? gx + e : nullptr;
-    const RdoqSlotX* SX = kFollow ? sx + G.slot : nullptr;
-    const uint32_t i = G.big[u - big_prefix[e]];
     if (i >= G.n) return;
     const Cells c = cells_of(G.box[i], S);
-    // every lane reads the pick byte and the latent (best_move) before lane 0 stores either: one wave, program order
-    if (!kSelect) {
-        Move m;
-        uint32_t pick;
-        if (kFirst) {
-            m = best_move<kFollow>(G, S, X, i);
-            pick = static_cast<uint32_t>(m.pick);
-        } else {
-            pick = G.pick[i];
-            if (!is_open(pick)) return;  // (the same in every lane)
-            m = best_move<kFollow>(G, S, X, i);
+    if (!kWave && c.n > kRdoqLaneCells) return;  // a wave's
+    const bool stores = !kWave || lane == 0;
+    if constexpr (!kSelect) {
+        uint32_t pick = kFirst ? 0 : G.pick[i];
+        if (!kFirst && !is_open(pick)) return;  // (in a wave: the same in every lane)
+        const Move m = best_move<kFollow>(G, S, X, i);
+        if (kFirst) pick = static_cast<uint32_t>(m.pick);
+        bool blocked = false;
+        if constexpr (!kFirst) {  // (no cell is taken before the first round)
+            blocked = set_taken<kWave, kFollow>(c, S, X, SX, i, lane);
+            if constexpr (kWave) blocked = __any(blocked);
         }
-        bool hit = false;
-        if (!kFirst)  // (no cell is taken before the first round)
-            for (uint32_t t = lane; t < c.n; t += 64) {
-                const uint32_t r = t / c.bw, q = t - r * c.bw;
-                hit = hit || S.taken[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] != 0;
-            }
-        if constexpr (kFollow && !kFirst) hit = hit || flow_taken<true>(*X, *SX, S, i, lane);
-        const bool blocked = __any(hit);
         if (blocked) pick |= kRdoqBlocked;
-        if (lane == 0 && (kFirst || blocked)) G.pick[i] = static_cast<uint8_t>(pick);
-        if (pick && !blocked)
-            for (uint32_t t = lane; t < c.n; t += 64) {
-                const uint32_t r = t / c.bw, q = t - r * c.bw;
-                atomicMin(&S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q], m.key);
-            }
-        if constexpr (kFollow)
-            if (pick && !blocked) flow_claim<true>(*X, *SX, S, i, lane, m.key);
+        if (stores && (kFirst || blocked)) G.pick[i] = static_cast<uint8_t>(pick);
+        if (pick && !blocked) set_claim<kWave, kFollow>(c, S, X, SX, i, lane, m.key);
     } else {
         int s = 0;
         const uint32_t pick = G.pick[i];
-        if (is_open(pick)) {  // (the same in every lane)
+        if (is_open(pick)) {  // (in a wave: the same in every lane)
             const Move m = best_move<kFollow>(G, S, X, i);
-            bool mine = true;
-            for (uint32_t t = lane; t < c.n; t += 64) {
-                const uint32_t r = t / c.bw, q = t - r * c.bw;
-                mine = mine && S.raster[static_cast<size_t>(c.top + r) * S.cells_w + c.left + q] == m.key;
-            }
-            if constexpr (kFollow) mine = mine && flow_mine<true>(*X, *SX, S, i, lane, m.key);
-            if (__all(mine)) s = m.s;
-            if (lane == 0 && s) {
+            bool mine = set_mine<kWave, kFollow>(c, S, X, SX, i, lane, m.key);
+            if constexpr (kWave) mine = __all(mine);
+            if (mine) s = m.s;
+            if (stores && s) {
                 G.lat[i] = static_cast<int8_t>(G.lat[i] + s);
                 G.pick[i] = static_cast<uint8_t>(pick | kRdoqSelected);
             }
         }
-        if (lane == 0 && (kFirst || s)) G.moves[i] = static_cast<int8_t>(s);
+        if (stores && (kFirst || s)) G.moves[i] = static_cast<int8_t>(s);
     }
 }
 
-// kFirst: the kernels of round 0, all that a step of one round runs before the sums.
-template <bool kFirst>
-__global__ __launch_bounds__(64) void rdoq_claim_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                        const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
-                                                        int n_grids, uint32_t n_lane_blocks) {
-    step_body<false, kFirst, false>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, nullptr, nullptr);
+// Every table a kernel reads is a __restrict__ pointer argument of the kernel itself: through a by-value struct of the same pointers
+// (measured: profiles/r14) the compiler can no longer prove that the kernel's stores leave the tables alone, and the bisection of
+// the prefix table, a chain of dependent loads in front of everything a workgroup does, turns from scalar into vector loads.
+
+// Which latent a workgroup's lanes work on: lane i of 64 latents of a grid, or all lanes on one entry of a `big` list.
+template <bool kWave, bool kSelect, bool kFirst, bool kFollow>
+__device__ __forceinline__ void step_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                          const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix, int n_grids,
+                                          uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx, const RdoqSlotX* __restrict__ sx) {
+    const uint32_t u = kWave ? blockIdx.x - n_lane_blocks : blockIdx.x;
+    const int e = entry_of(kWave ? big_prefix : lane_prefix, n_grids, u);
+    const RdoqGrid& G = grids[e];
+    const uint32_t i = kWave ? G.big[u - big_prefix[e]] : (u - lane_prefix[e]) * 64u + threadIdx.x;
+    step_latent<kWave, kSelect, kFirst, kFollow>(G, slots[G.slot], kFollow ? gx + e : nullptr, kFollow ? sx + G.slot : nullptr, i);
 }
 
-template <bool kFirst>
-__global__ __launch_bounds__(64) void rdoq_select_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                         const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
-                                                         int n_grids, uint32_t n_lane_blocks) {
-    step_body<true, kFirst, false>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, nullptr, nullptr);
-}
-
-// The following variants: the same bodies over claim sets.
-template <bool kFirst>
-__global__ __launch_bounds__(64) void rdoq_claim_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                               const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
-                                                               int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
-                                                               const RdoqSlotX* __restrict__ sx) {
-    step_body<false, kFirst, true>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
-}
-template <bool kFirst>
-__global__ __launch_bounds__(64) void rdoq_select_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                                const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
-                                                                int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
-                                                                const RdoqSlotX* __restrict__ sx) {
-    step_body<true, kFirst, true>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
+// kFirst: the kernels of round 0, all that a step of one round runs before the sums.  kFollow: the same body over
+// claim sets; without it gx / sx are null and never read.
+template <bool kSelect, bool kFirst, bool kFollow>
+__global__ __launch_bounds__(64) void rdoq_step_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                       const uint32_t* __restrict__ lane_prefix, const uint32_t* __restrict__ big_prefix,
+                                                       int n_grids, uint32_t n_lane_blocks, const RdoqGridX* __restrict__ gx,
+                                                       const RdoqSlotX* __restrict__ sx) {
+    if (blockIdx.x < n_lane_blocks) step_body<false, kSelect, kFirst, kFollow>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
+    else step_body<true, kSelect, kFirst, kFollow>(grids, slots, lane_prefix, big_prefix, n_grids, n_lane_blocks, gx, sx);
 }
 
 // The flow box of every latent of a following slot, per follow: the bounding rectangle of reach[c] over the cells c of the
@@ -375,9 +307,9 @@ __global__ __launch_bounds__(64) void rdoq_flowbox_kernel(const RdoqGrid* __rest
 // kFollow: the owner is a latent of any slot of the raster owner's component; its slot is the last entry of the component's
 // table of first uids that is not above the uid (a bisection; the partner test is its two-slot case).
 template <bool kFollow>
-__device__ __forceinline__ void settle_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                            const uint32_t* __restrict__ cell_prefix, int n_slots, const RdoqSlotX* __restrict__ sx,
-                                            const uint32_t* __restrict__ comp_uid, const int32_t* __restrict__ comp_slot) {
+__global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                         const uint32_t* __restrict__ cell_prefix, int n_slots, const RdoqSlotX* __restrict__ sx,
+                                                         const uint32_t* __restrict__ comp_uid, const int32_t* __restrict__ comp_slot) {
     const int k = entry_of(cell_prefix, n_slots, blockIdx.x);
     const RdoqSlot& S = slots[k];
     const size_t cell = static_cast<size_t>(blockIdx.x - cell_prefix[k]) * 64u + threadIdx.x;
@@ -385,31 +317,21 @@ __device__ __forceinline__ void settle_body(const RdoqGrid* __restrict__ grids, 
     const unsigned long long key = S.raster[cell];
     if (key == ~0ull) return;  // nobody claimed the cell
     const uint32_t uid = static_cast<uint32_t>(key);
-    const RdoqSlot* T = &S;  // the slot of the uid
+    const RdoqSlot* O = &S;  // the slot of the uid
     if constexpr (kFollow) {
         int lo = sx[k].comp_first, hi = lo + sx[k].comp_n - 1;  // comp_uid[lo] == 0 <= uid
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
             if (comp_uid[mid] <= uid) lo = mid; else hi = mid - 1;
         }
-        T = &slots[comp_slot[lo]];
-    } else if (S.partner >= 0 && grids[slots[S.partner].first_grid].first <= uid) T = &slots[S.partner];
+        O = &slots[comp_slot[lo]];
+    } else if (S.partner >= 0 && grids[slots[S.partner].first_grid].first <= uid) O = &slots[S.partner];
     int g = 0;  // the grid of the uid: first[] ascends over the slot's few grids
-    while (g + 1 < T->n_grids && grids[T->first_grid + g + 1].first <= uid) ++g;
-    const RdoqGrid& G = grids[T->first_grid + g];
+    while (g + 1 < O->n_grids && grids[O->first_grid + g + 1].first <= uid) ++g;
+    const RdoqGrid& G = grids[O->first_grid + g];
     const uint32_t i = uid - G.first;
     if (i < G.n && (G.pick[i] & kRdoqSelected)) S.taken[cell] = 1;
     S.raster[cell] = ~0ull;
-}
-__global__ __launch_bounds__(64) void rdoq_settle_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                         const uint32_t* __restrict__ cell_prefix, int n_slots) {
-    settle_body<false>(grids, slots, cell_prefix, n_slots, nullptr, nullptr, nullptr);
-}
-__global__ __launch_bounds__(64) void rdoq_settle_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                                const uint32_t* __restrict__ cell_prefix, int n_slots,
-                                                                const RdoqSlotX* __restrict__ sx, const uint32_t* __restrict__ comp_uid,
-                                                                const int32_t* __restrict__ comp_slot) {
-    settle_body<true>(grids, slots, cell_prefix, n_slots, sx, comp_uid, comp_slot);
 }
 
 __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
@@ -426,10 +348,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {  // a fixed tree: lan
 // kFollow: the chosen entries of the dependent maps are summed beside d_sse (integers, any order): partial_dep per chunk, then
 // dep_out per slot.
 template <bool kFollow>
-__device__ __forceinline__ void reduce_body(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                            const uint32_t* __restrict__ chunk_prefix, int n_grids, RdoqPartial* __restrict__ partial,
-                                            ccd_rdoq_result* __restrict__ results, int64_t* __restrict__ open, int phase,
-                                            const RdoqGridX* __restrict__ gx, int64_t* __restrict__ partial_dep, int64_t* __restrict__ dep_out) {
+__global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
+                                                         const uint32_t* __restrict__ chunk_prefix, int n_grids, const RdoqSums O, int phase,
+                                                         const RdoqGridX* __restrict__ gx) {
     const uint32_t lane = threadIdx.x;
     RdoqPartial acc = {0, 0, 0, 0.0, 0};
     int64_t dep = 0;
@@ -453,18 +374,18 @@ __device__ __forceinline__ void reduce_body(const RdoqGrid* __restrict__ grids, 
         }
     } else {
         const RdoqSlot& S = slots[blockIdx.x];
-        ccd_rdoq_result& R = results[blockIdx.x];
+        ccd_rdoq_result& R = O.results[blockIdx.x];
         RdoqPartial total = {0, 0, 0, 0.0, 0};
         if constexpr (kFollow) {
-            for (uint32_t c = chunk_prefix[S.first_grid] + lane; c < chunk_prefix[S.first_grid + S.n_grids]; c += 64) dep += partial_dep[c];
+            for (uint32_t c = chunk_prefix[S.first_grid] + lane; c < chunk_prefix[S.first_grid + S.n_grids]; c += 64) dep += O.partial_dep[c];
             dep = wave_sum_i64(dep);
-            if (lane == 0) dep_out[blockIdx.x] = dep;
+            if (lane == 0) O.dep_out[blockIdx.x] = dep;
         }
         for (int g = 0; g < S.n_grids; ++g) {
             const int e = S.first_grid + g;
             acc = {0, 0, 0, 0.0, 0};
             for (uint32_t c = chunk_prefix[e] + lane; c < chunk_prefix[e + 1]; c += 64) {
-                const RdoqPartial P = partial[c];
+                const RdoqPartial P = O.partial[c];
                 acc.n_candidates += P.n_candidates;
                 acc.n_moves += P.n_moves;
                 acc.d_sse += P.d_sse;
@@ -492,7 +413,7 @@ __device__ __forceinline__ void reduce_body(const RdoqGrid* __restrict__ grids, 
             R.d_sse = total.d_sse;
             R.d_bits = total.d_bits;
             R.d_cost = 0.0;  // the host's
-            open[blockIdx.x] = total.n_open;
+            O.open[blockIdx.x] = total.n_open;
         }
         // all ones and no taken cell for the next step's claim (the ordering argument is at the head of this file); a pair's
         // rasters are the leader's to store
@@ -508,70 +429,48 @@ __device__ __forceinline__ void reduce_body(const RdoqGrid* __restrict__ grids, 
     acc.d_sse = wave_sum_i64(acc.d_sse);
     acc.d_bits = wave_sum_f64(acc.d_bits);
     acc.n_open = wave_sum_i64(acc.n_open);
-    if (lane == 0) partial[blockIdx.x] = acc;
+    if (lane == 0) O.partial[blockIdx.x] = acc;
     if constexpr (kFollow) {
         dep = wave_sum_i64(dep);
-        if (lane == 0) partial_dep[blockIdx.x] = dep;
+        if (lane == 0) O.partial_dep[blockIdx.x] = dep;
     }
 }
-__global__ __launch_bounds__(64) void rdoq_reduce_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                         const uint32_t* __restrict__ chunk_prefix, int n_grids,
-                                                         RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
-                                                         int64_t* __restrict__ open, int phase) {
-    reduce_body<false>(grids, slots, chunk_prefix, n_grids, partial, results, open, phase, nullptr, nullptr, nullptr);
-}
-__global__ __launch_bounds__(64) void rdoq_reduce_follow_kernel(const RdoqGrid* __restrict__ grids, const RdoqSlot* __restrict__ slots,
-                                                                const uint32_t* __restrict__ chunk_prefix, int n_grids,
-                                                                RdoqPartial* __restrict__ partial, ccd_rdoq_result* __restrict__ results,
-                                                                int64_t* __restrict__ open, int phase, const RdoqGridX* __restrict__ gx,
-                                                                int64_t* __restrict__ partial_dep, int64_t* __restrict__ dep_out) {
-    reduce_body<true>(grids, slots, chunk_prefix, n_grids, partial, results, open, phase, gx, partial_dep, dep_out);
+// `rounds` times claim, select (and settle between two rounds: after the last round phase 1 of the reduce launch writes both
+// rasters), then the two phases of the reduce launch: 3 R + 1 launches.
+template <bool kFollow>
+hipError_t launch_rounds(const RdoqStepLaunch& L, hipStream_t stream) {
+    const RdoqStepTables& T = L.t;
+    const dim3 units(T.n_lane_blocks + L.n_big), wave(64);
+    for (int k = 0; k < L.rounds; ++k) {
+        hipLaunchKernelGGL((k == 0 ? rdoq_step_kernel<false, true, kFollow> : rdoq_step_kernel<false, false, kFollow>), units, wave, 0, stream, T.grids,
+                           T.slots, T.lane_prefix, T.big_prefix, T.n_grids, T.n_lane_blocks, T.gx, T.sx);
+        hipLaunchKernelGGL((k == 0 ? rdoq_step_kernel<true, true, kFollow> : rdoq_step_kernel<true, false, kFollow>), units, wave, 0, stream, T.grids,
+                           T.slots, T.lane_prefix, T.big_prefix, T.n_grids, T.n_lane_blocks, T.gx, T.sx);
+        if (k + 1 < L.rounds)
+            hipLaunchKernelGGL(rdoq_settle_kernel<kFollow>, dim3(L.n_cell_blocks), wave, 0, stream, T.grids, T.slots, T.cell_prefix, T.n_slots, T.sx,
+                               T.comp_uid, T.comp_slot);
+    }
+    hipLaunchKernelGGL(rdoq_reduce_kernel<kFollow>, dim3(L.n_chunks), wave, 0, stream, T.grids, T.slots, T.chunk_prefix, T.n_grids, L.sums, 0, T.gx);
+    hipLaunchKernelGGL(rdoq_reduce_kernel<kFollow>, dim3(T.n_slots), wave, 0, stream, T.grids, T.slots, T.chunk_prefix, T.n_grids, L.sums, 1, T.gx);
+    return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_rdoq_step(const RdoqGrid* d_grids, const RdoqSlot* d_slots, const uint32_t* d_lane_prefix, const uint32_t* d_big_prefix,
-                            const uint32_t* d_chunk_prefix, const uint32_t* d_cell_prefix, int n_grids, int n_slots, uint32_t n_lane_blocks,
-                            uint32_t n_big, uint32_t n_chunks, uint32_t n_cell_blocks, int rounds, RdoqPartial* d_partial,
-                            ccd_rdoq_result* d_results, int64_t* d_open, hipStream_t stream, const RdoqFollowLaunch* F) {
-    if (n_grids <= 0 || n_slots <= 0 || n_lane_blocks == 0 || n_chunks == 0 || n_cell_blocks == 0 || rounds < 1) return hipSuccess;
-    const dim3 units(n_lane_blocks + n_big);
-    if (F) {  // the variants over claim sets: one memset, the reach launch(es), the flow boxes, then 3 R + 1 launches as below
-        if (F->n_reach[0] + F->n_reach[1] > 0) {
-            if (F->stages & 1) {
-                hipError_t e = hipMemsetAsync(F->reach_mem, 0xff, F->reach_bytes, stream);
-                for (int c = 0; c < 2 && e == hipSuccess; ++c) e = launch_rdoq_reach(F->reach_jobs[c], F->reach_prefix[c], F->n_reach[c], F->reach_blocks[c], c, stream);
-                if (e != hipSuccess) return e;
-            }
-            if (F->stages & 2)
-                hipLaunchKernelGGL(rdoq_flowbox_kernel, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks,
-                                   F->gx, F->sx);
+hipError_t launch_rdoq_step(const RdoqStepLaunch& L, hipStream_t stream) {
+    if (L.t.n_grids <= 0 || L.t.n_slots <= 0 || L.t.n_lane_blocks == 0 || L.n_chunks == 0 || L.n_cell_blocks == 0 || L.rounds < 1) return hipSuccess;
+    if (!L.t.gx) return launch_rounds<false>(L, stream);
+    // the variants over claim sets: one memset, the reach launch(es) and the flow boxes in front of the rounds
+    if (L.n_reach[0] + L.n_reach[1] > 0) {
+        if (L.stages & 1) {
+            hipError_t e = hipMemsetAsync(L.reach_mem, 0xff, L.reach_bytes, stream);
+            for (int c = 0; c < 2 && e == hipSuccess; ++c) e = launch_rdoq_reach(L.reach_jobs[c], L.reach_prefix[c], L.n_reach[c], L.reach_blocks[c], c, stream);
+            if (e != hipSuccess) return e;
         }
-        if (!(F->stages & 4)) return hipGetLastError();  // (a timing run of the tables alone: no result is written)
-        for (int k = 0; k < rounds; ++k) {
-            hipLaunchKernelGGL(k == 0 ? rdoq_claim_follow_kernel<true> : rdoq_claim_follow_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots,
-                               d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks, F->gx, F->sx);
-            hipLaunchKernelGGL(k == 0 ? rdoq_select_follow_kernel<true> : rdoq_select_follow_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots,
-                               d_lane_prefix, d_big_prefix, n_grids, n_lane_blocks, F->gx, F->sx);
-            if (k + 1 < rounds)
-                hipLaunchKernelGGL(rdoq_settle_follow_kernel, dim3(n_cell_blocks), dim3(64), 0, stream, d_grids, d_slots, d_cell_prefix, n_slots, F->sx,
-                                   F->comp_uid, F->comp_slot);
-        }
-        hipLaunchKernelGGL(rdoq_reduce_follow_kernel, dim3(n_chunks), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results,
-                           d_open, 0, F->gx, F->partial_dep, F->dep_out);
-        hipLaunchKernelGGL(rdoq_reduce_follow_kernel, dim3(n_slots), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results,
-                           d_open, 1, F->gx, F->partial_dep, F->dep_out);
-        return hipGetLastError();
+        if (L.stages & 2)
+            hipLaunchKernelGGL(rdoq_flowbox_kernel, dim3(L.t.n_lane_blocks + L.n_big), dim3(64), 0, stream, L.t.grids, L.t.slots, L.t.lane_prefix,
+                               L.t.big_prefix, L.t.n_grids, L.t.n_lane_blocks, L.t.gx, L.t.sx);
     }
-    for (int k = 0; k < rounds; ++k) {
-        hipLaunchKernelGGL(k == 0 ? rdoq_claim_kernel<true> : rdoq_claim_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix,
-                           d_big_prefix, n_grids, n_lane_blocks);
-        hipLaunchKernelGGL(k == 0 ? rdoq_select_kernel<true> : rdoq_select_kernel<false>, units, dim3(64), 0, stream, d_grids, d_slots, d_lane_prefix,
-                           d_big_prefix, n_grids, n_lane_blocks);
-        // after the last round phase 1 of the reduce launch writes both rasters
-        if (k + 1 < rounds) hipLaunchKernelGGL(rdoq_settle_kernel, dim3(n_cell_blocks), dim3(64), 0, stream, d_grids, d_slots, d_cell_prefix, n_slots);
-    }
-    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_chunks), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, d_open, 0);
-    hipLaunchKernelGGL(rdoq_reduce_kernel, dim3(n_slots), dim3(64), 0, stream, d_grids, d_slots, d_chunk_prefix, n_grids, d_partial, d_results, d_open, 1);
-    return hipGetLastError();
+    if (!(L.stages & 4)) return hipGetLastError();  // (a timing run of the tables alone: no result is written)
+    return launch_rounds<true>(L, stream);
 }
 }  // namespace ccd

@@ -185,6 +185,149 @@ int component_uids(const ccd_rdoq& r, std::vector<uint32_t>& uid0, std::vector<i
     }
     return CCD_OK;
 }
+
+// The tables of one step: grids, slots and the four prefix tables, whose last entries are the launches' block counts.
+struct StepTables {
+    std::vector<RdoqGrid> grids;
+    std::vector<RdoqSlot> slots;
+    std::vector<uint32_t> lane_prefix, big_prefix, chunk_prefix, cell_prefix;
+};
+// Stores the step's kD / kR in the slots as it goes.  CCD_ERR_UNSUPPORTED: more blocks than a launch takes.
+int build_step_tables(ccd_rdoq& r, const std::vector<uint32_t>& uid0, const double* kD, const double* kR, const double* min_gain,
+                      const uint64_t* grid_mask, StepTables& B) {
+    const int n_slots = static_cast<int>(r.slots.size());
+    B.slots.resize(n_slots);
+    B.lane_prefix.assign(1, 0); B.big_prefix.assign(1, 0); B.chunk_prefix.assign(1, 0); B.cell_prefix.assign(1, 0);
+    uint64_t lanes = 0, bigs = 0, chunks = 0, cell_blocks = 0;
+    for (int k = 0; k < n_slots; ++k) {
+        RSlot& s = *r.slots[k];
+        char* base = s.mem.as<char>();
+        RdoqSlot& S = B.slots[k];
+        std::memset(&S, 0, sizeof(S));
+        // a follower claims in its leader's rasters, its uids after the leader's (both at most 2^31 - 1: 32 bits hold the pair);
+        // in a component with follows the uids run on over its groups (component_uids)
+        const RSlot& owner = s.leader >= 0 ? *r.slots[s.leader] : s;
+        S.raster = reinterpret_cast<unsigned long long*>(owner.mem.as<char>() + owner.raster_off);
+        S.taken = reinterpret_cast<uint8_t*>(owner.mem.as<char>() + owner.taken_off);
+        S.partner = s.leader >= 0 ? s.leader : s.follower;
+        S.owns_raster = s.leader < 0;
+        S.cells_h = s.geo.cells_h; S.cells_w = s.geo.cells_w;
+        S.kD = s.kD = kD[k]; S.kR = s.kR = kR[k]; S.min_gain = min_gain[k];
+        S.grid_mask = grid_mask[k];
+        S.first_grid = static_cast<int32_t>(B.grids.size()); S.n_grids = s.n_grids;
+        S.raster_units = s.raster_units; S.taken_units = s.taken_units;
+        if (S.owns_raster) cell_blocks += (static_cast<uint64_t>(s.geo.cells_h) * s.geo.cells_w + 63) / 64;  // settle: a lane per cell
+        if (cell_blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+        B.cell_prefix.push_back(static_cast<uint32_t>(cell_blocks));
+        for (int g = 0; g < s.n_grids; ++g) {
+            RdoqGrid G;
+            std::memset(&G, 0, sizeof(G));
+            G.lat = s.lat[g]; G.dd = s.dd[g]; G.db = s.db[g];
+            G.moves = reinterpret_cast<int8_t*>(base + s.moves_off[g]);
+            G.pick = reinterpret_cast<uint8_t*>(base + s.pick_off[g]);
+            G.box = reinterpret_cast<const RdoqBox*>(base + s.box_off[g]);
+            G.big = reinterpret_cast<const uint32_t*>(base + s.big_off[g]);
+            G.n = s.n[g]; G.first = uid0[k] + s.first[g]; G.slot = k; G.grid = g;
+            lanes += (G.n + 63) / 64; bigs += s.n_big[g]; chunks += (G.n + kRdoqChunk - 1) / kRdoqChunk;
+            if (lanes + bigs > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+            B.lane_prefix.push_back(static_cast<uint32_t>(lanes)); B.big_prefix.push_back(static_cast<uint32_t>(bigs));
+            B.chunk_prefix.push_back(static_cast<uint32_t>(chunks));
+            B.grids.push_back(G);
+        }
+    }
+    return CCD_OK;
+}
+
+// With follows or dependent maps: the tables beside grids and slots, the components, the reach jobs.
+struct FollowTables {
+    std::vector<RdoqGridX> gridsx;
+    std::vector<RdoqSlotX> slotsx;
+    std::vector<uint32_t> comp_uid, reach_prefix[2];
+    std::vector<int32_t> comp_slot;
+    std::vector<RdoqReachJob> reach_jobs[2];
+    size_t reach_bytes = 0;  // the reach tables come first in follow_mem (one memset), the flow boxes behind them
+};
+// Lays out ccd_rdoq::follow_mem and ends what an earlier step built there, whatever it returns.  CCD_ERR_NOMEM, CCD_ERR_HIP;
+// CCD_ERR_UNSUPPORTED: more reach blocks than a launch takes.
+int build_follow_tables(ccd_rdoq& r, const std::vector<uint32_t>& uid0, const std::vector<int>& comp, const StepTables& B, FollowTables& F) {
+    const int n_slots = static_cast<int>(r.slots.size());
+    F.gridsx.resize(B.grids.size());
+    F.slotsx.resize(n_slots);
+    std::memset(F.gridsx.data(), 0, F.gridsx.size() * sizeof(RdoqGridX));
+    std::memset(F.slotsx.data(), 0, F.slotsx.size() * sizeof(RdoqSlotX));
+    size_t follow_bytes = 0;
+    for (auto& s : r.slots)
+        for (auto& f : s->follows) {
+            f.reach_off = follow_bytes;
+            follow_bytes += align256(static_cast<size_t>(s->geo.cells_h) * s->geo.cells_w * kRdoqReachWords * sizeof(uint32_t));
+        }
+    F.reach_bytes = follow_bytes;
+    for (auto& s : r.slots)
+        for (auto& f : s->follows)
+            for (int g = 0; g < s->n_grids; ++g) {
+                f.fbox_off[g] = follow_bytes;
+                follow_bytes += align256(static_cast<size_t>(s->n[g]) * sizeof(RdoqBox));
+            }
+    // nothing of an earlier step is in flight: the block may be exchanged, and what ccd_rdoq_slot_reach handed out ends here
+    for (auto& s : r.slots)
+        for (auto& f : s->follows) f.stepped = false;
+    HIP_TRY(hipSetDevice(r.device));
+    if (!r.follow_mem.ensure(r.device, BlockPool::kDevice, std::max<size_t>(follow_bytes, 256))) return CCD_ERR_NOMEM;
+    char* fm = r.follow_mem.as<char>();
+    for (int root = 0; root < n_slots; ++root) {  // a component's slots in the order of their uids: leaders ascending, follower behind
+        if (comp[root] != root) continue;
+        const int32_t first = static_cast<int32_t>(F.comp_uid.size());
+        for (int k = 0; k < n_slots; ++k) {
+            if (comp[k] != root || r.slots[k]->leader >= 0) continue;
+            F.comp_uid.push_back(uid0[k]); F.comp_slot.push_back(k);
+            const int fo = r.slots[k]->follower;
+            if (fo >= 0) { F.comp_uid.push_back(uid0[fo]); F.comp_slot.push_back(fo); }
+        }
+        for (int k = 0; k < n_slots; ++k)
+            if (comp[k] == root) { F.slotsx[k].comp_first = first; F.slotsx[k].comp_n = static_cast<int32_t>(F.comp_uid.size()) - first; }
+    }
+    uint64_t blocks[2] = {0, 0};
+    F.reach_prefix[0].push_back(0); F.reach_prefix[1].push_back(0);
+    for (int k = 0; k < n_slots; ++k) {
+        RSlot& s = *r.slots[k];
+        RdoqSlotX& SX = F.slotsx[k];
+        SX.n_follows = static_cast<int32_t>(s.follows.size());
+        for (size_t q = 0; q < s.follows.size(); ++q) {
+            RSlot::Follow& f = s.follows[q];
+            const RdoqSlot& T = B.slots[f.d.target];  // (raster / taken: its group's)
+            SX.follow[q].reach = reinterpret_cast<const uint32_t*>(fm + f.reach_off);
+            SX.follow[q].raster = T.raster;
+            SX.follow[q].taken = T.taken;
+            RdoqReachJob J;
+            J.motion = f.d.motion; J.reach = reinterpret_cast<uint32_t*>(fm + f.reach_off);
+            J.which = f.d.which; J.H = s.geo.h.img_size[0]; J.W = s.geo.h.img_size[1]; J.n_taps = f.d.warp_filter_size;
+            J.gx = f.d.global_flow[2 * f.d.which]; J.gy = f.d.global_flow[2 * f.d.which + 1];
+            J.cells_h = s.geo.cells_h; J.cells_w = s.geo.cells_w;
+            const int c = f.d.warp_filter_size == 8;
+            blocks[c] += static_cast<uint64_t>(J.cells_h) * J.cells_w;
+            if (blocks[c] > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
+            F.reach_jobs[c].push_back(J);
+            F.reach_prefix[c].push_back(static_cast<uint32_t>(blocks[c]));
+        }
+        for (int g = 0; g < s.n_grids; ++g) {
+            RdoqGridX& X = F.gridsx[B.slots[k].first_grid + g];
+            X.dd_dep = s.dd_dep[g];
+            for (size_t q = 0; q < s.follows.size(); ++q) X.fbox[q] = reinterpret_cast<RdoqBox*>(fm + s.follows[q].fbox_off[g]);
+        }
+    }
+    return CCD_OK;
+}
+
+// Congruent rasters: the same picture in the same cells, and boxes widened for the same planes.
+bool congruent(const RSlot& a, const RSlot& b) {
+    return a.frame_data_type == b.frame_data_type && a.geo.h.img_size[0] == b.geo.h.img_size[0] && a.geo.h.img_size[1] == b.geo.h.img_size[1];
+}
+
+// The slot a getter answers for: one that exists and that a finished step covers, with no step in flight; else nullptr.
+const RSlot* covered_slot(const ccd_rdoq* r, int slot) {
+    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return nullptr;
+    return r->slots[slot].get();
+}
 }  // namespace
 
 extern "C" {
@@ -310,9 +453,7 @@ int ccd_rdoq_link(ccd_rdoq* r, int slot, int leader) {
     RSlot& f = *r->slots[slot];
     RSlot& l = *r->slots[leader];
     if (f.leader >= 0 || f.follower >= 0 || l.leader >= 0 || l.follower >= 0) return CCD_ERR_ARG;  // pairs only
-    // congruent rasters: the same picture in the same cells, and boxes widened for the same planes
-    if (f.frame_data_type != l.frame_data_type || f.geo.h.img_size[0] != l.geo.h.img_size[0] || f.geo.h.img_size[1] != l.geo.h.img_size[1])
-        return CCD_ERR_VALUE;
+    if (!congruent(f, l)) return CCD_ERR_VALUE;
     f.leader = leader;
     l.follower = slot;
     std::vector<uint32_t> uid0;
@@ -332,11 +473,10 @@ int ccd_rdoq_lane_cells(void) { return static_cast<int>(kRdoqLaneCells); }
 // candidate, 1 / 2 a candidate for -1 / +1, with 4 once selected and 8 once blocked; neither: open after the last round.
 int64_t ccd_rdoq_debug_picks(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {
     if (!r || !dev_ptr || slot < 0 || grid < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
-    const RSlot& s = *r->slots[slot];
-    if (grid >= s.n_grids || !s.covered) return CCD_ERR_ARG;
-    *dev_ptr = s.mem.as<char>() + s.pick_off[grid];
-    return static_cast<int64_t>(s.n[grid]);
+    const RSlot* s = covered_slot(r, slot);
+    if (!s || grid >= s->n_grids) return CCD_ERR_ARG;
+    *dev_ptr = s->mem.as<char>() + s->pick_off[grid];
+    return static_cast<int64_t>(s->n[grid]);
 }
 
 // Not part of include/ccd.h (tools/rd_bench.py --follow, as ccd_dsens_debug_stages): which stages of a step with follows are
@@ -357,9 +497,7 @@ int ccd_rdoq_follow(ccd_rdoq* r, int slot, const ccd_rdoq_follow_desc* f) {
     RSlot& s = *r->slots[slot];
     if (static_cast<int>(s.follows.size()) >= kRdoqMaxFollows) return CCD_ERR_ARG;
     if (f->target == slot || !warp_filter_ok(f->warp_filter_size)) return CCD_ERR_VALUE;
-    const RSlot& t = *r->slots[f->target];  // congruent rasters, as ccd_rdoq_link asks
-    if (t.frame_data_type != s.frame_data_type || t.geo.h.img_size[0] != s.geo.h.img_size[0] || t.geo.h.img_size[1] != s.geo.h.img_size[1])
-        return CCD_ERR_VALUE;
+    if (!congruent(s, *r->slots[f->target])) return CCD_ERR_VALUE;  // as ccd_rdoq_link asks
     RSlot::Follow fo;
     fo.d = *f;
     s.follows.push_back(fo);
@@ -393,12 +531,10 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
     if (!r || !kD || !kR || !min_gain || !grid_mask || max_rounds < 1 || max_rounds > kRdoqMaxRounds) return CCD_ERR_ARG;
     if (r->pending) return CCD_ERR_ARG;
     const int n_slots = static_cast<int>(r->slots.size());
-    int n_grids = 0;
     for (int k = 0; k < n_slots; ++k) {
         if (!(std::isfinite(kD[k]) && kD[k] >= 0 && std::isfinite(kR[k]) && kR[k] >= 0 && std::isfinite(min_gain[k]) && min_gain[k] >= 0))
             return CCD_ERR_ARG;
         if (!r->slots[k]->have_maps) return CCD_ERR_ARG;
-        n_grids += r->slots[k]->n_grids;
     }
     if (n_slots == 0) return CCD_OK;
     // the flows are followed as they are: no move of a followed frame's motion cool-chic in the same step
@@ -411,170 +547,62 @@ int ccd_rdoq_step_rounds(ccd_rdoq* r, const double* kD, const double* kR, const 
     }
     std::vector<uint32_t> uid0;
     std::vector<int> comp;
-    {
-        const int rc = component_uids(*r, uid0, comp);
-        if (rc < 0) return rc;
-    }
-    // the tables of this step: grids, slots and the four prefix tables, one block, one copy
-    std::vector<RdoqGrid> grids;
-    std::vector<RdoqSlot> slots(n_slots);
-    std::vector<uint32_t> lane_prefix(n_grids + 1, 0), big_prefix(n_grids + 1, 0), chunk_prefix(n_grids + 1, 0), cell_prefix(n_slots + 1, 0);
-    uint64_t lanes = 0, bigs = 0, chunks = 0, cell_blocks = 0;
-    for (int k = 0; k < n_slots; ++k) {
-        RSlot& s = *r->slots[k];
-        char* base = s.mem.as<char>();
-        RdoqSlot& S = slots[k];
-        std::memset(&S, 0, sizeof(S));
-        // a follower claims in its leader's rasters, its uids after the leader's (both at most 2^31 - 1: 32 bits hold the pair);
-        // in a component with follows the uids run on over its groups (component_uids)
-        const RSlot& owner = s.leader >= 0 ? *r->slots[s.leader] : s;
-        S.raster = reinterpret_cast<unsigned long long*>(owner.mem.as<char>() + owner.raster_off);
-        S.taken = reinterpret_cast<uint8_t*>(owner.mem.as<char>() + owner.taken_off);
-        S.partner = s.leader >= 0 ? s.leader : s.follower;
-        S.owns_raster = s.leader < 0;
-        S.cells_h = s.geo.cells_h; S.cells_w = s.geo.cells_w;
-        S.kD = s.kD = kD[k]; S.kR = s.kR = kR[k]; S.min_gain = min_gain[k];
-        S.grid_mask = grid_mask[k];
-        S.first_grid = static_cast<int32_t>(grids.size()); S.n_grids = s.n_grids;
-        S.raster_units = s.raster_units; S.taken_units = s.taken_units;
-        if (S.owns_raster) cell_blocks += (static_cast<uint64_t>(s.geo.cells_h) * s.geo.cells_w + 63) / 64;  // settle: a lane per cell
-        if (cell_blocks > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
-        cell_prefix[k + 1] = static_cast<uint32_t>(cell_blocks);
-        for (int g = 0; g < s.n_grids; ++g) {
-            RdoqGrid G;
-            std::memset(&G, 0, sizeof(G));
-            G.lat = s.lat[g]; G.dd = s.dd[g]; G.db = s.db[g];
-            G.moves = reinterpret_cast<int8_t*>(base + s.moves_off[g]);
-            G.pick = reinterpret_cast<uint8_t*>(base + s.pick_off[g]);
-            G.box = reinterpret_cast<const RdoqBox*>(base + s.box_off[g]);
-            G.big = reinterpret_cast<const uint32_t*>(base + s.big_off[g]);
-            G.n = s.n[g]; G.first = uid0[k] + s.first[g]; G.slot = k; G.grid = g;
-            lanes += (G.n + 63) / 64; bigs += s.n_big[g]; chunks += (G.n + kRdoqChunk - 1) / kRdoqChunk;
-            if (lanes + bigs > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
-            const size_t e = grids.size();
-            lane_prefix[e + 1] = static_cast<uint32_t>(lanes); big_prefix[e + 1] = static_cast<uint32_t>(bigs);
-            chunk_prefix[e + 1] = static_cast<uint32_t>(chunks);
-            grids.push_back(G);
-        }
-    }
-    // with follows or dependent maps: the tables beside grids and slots, the components, the reach jobs; the reach tables come
-    // first in follow_mem (one memset), the flow boxes behind them
-    std::vector<RdoqGridX> gridsx;
-    std::vector<RdoqSlotX> slotsx;
-    std::vector<uint32_t> comp_uid, reach_prefix[2];
-    std::vector<int32_t> comp_slot;
-    std::vector<RdoqReachJob> reach_jobs[2];
-    size_t reach_bytes = 0, follow_bytes = 0;
-    if (following) {
-        gridsx.resize(n_grids);
-        slotsx.resize(n_slots);
-        std::memset(gridsx.data(), 0, gridsx.size() * sizeof(RdoqGridX));
-        std::memset(slotsx.data(), 0, slotsx.size() * sizeof(RdoqSlotX));
-        for (int k = 0; k < n_slots; ++k)
-            for (auto& f : r->slots[k]->follows) {
-                f.reach_off = follow_bytes;
-                follow_bytes += align256(static_cast<size_t>(r->slots[k]->geo.cells_h) * r->slots[k]->geo.cells_w * kRdoqReachWords * sizeof(uint32_t));
-            }
-        reach_bytes = follow_bytes;
-        for (int k = 0; k < n_slots; ++k)
-            for (auto& f : r->slots[k]->follows)
-                for (int g = 0; g < r->slots[k]->n_grids; ++g) {
-                    f.fbox_off[g] = follow_bytes;
-                    follow_bytes += align256(static_cast<size_t>(r->slots[k]->n[g]) * sizeof(RdoqBox));
-                }
-        // nothing of an earlier step is in flight: the block may be exchanged, and what ccd_rdoq_slot_reach handed out ends here
-        for (auto& s : r->slots)
-            for (auto& f : s->follows) f.stepped = false;
-        HIP_TRY(hipSetDevice(r->device));
-        if (!r->follow_mem.ensure(r->device, BlockPool::kDevice, std::max<size_t>(follow_bytes, 256))) return CCD_ERR_NOMEM;
-        char* fm = r->follow_mem.as<char>();
-        for (int root = 0; root < n_slots; ++root) {  // a component's slots in the order of their uids: leaders ascending, follower behind
-            if (comp[root] != root) continue;
-            const int32_t first = static_cast<int32_t>(comp_uid.size());
-            for (int k = 0; k < n_slots; ++k) {
-                if (comp[k] != root || r->slots[k]->leader >= 0) continue;
-                comp_uid.push_back(uid0[k]); comp_slot.push_back(k);
-                const int fo = r->slots[k]->follower;
-                if (fo >= 0) { comp_uid.push_back(uid0[fo]); comp_slot.push_back(fo); }
-            }
-            for (int k = 0; k < n_slots; ++k)
-                if (comp[k] == root) { slotsx[k].comp_first = first; slotsx[k].comp_n = static_cast<int32_t>(comp_uid.size()) - first; }
-        }
-        uint64_t blocks[2] = {0, 0};
-        reach_prefix[0].push_back(0); reach_prefix[1].push_back(0);
-        for (int k = 0; k < n_slots; ++k) {
-            RSlot& s = *r->slots[k];
-            RdoqSlotX& SX = slotsx[k];
-            SX.n_follows = static_cast<int32_t>(s.follows.size());
-            for (size_t q = 0; q < s.follows.size(); ++q) {
-                RSlot::Follow& f = s.follows[q];
-                const RdoqSlot& T = slots[f.d.target];  // (raster / taken: its group's)
-                SX.follow[q].reach = reinterpret_cast<const uint32_t*>(fm + f.reach_off);
-                SX.follow[q].raster = T.raster;
-                SX.follow[q].taken = T.taken;
-                RdoqReachJob J;
-                J.motion = f.d.motion; J.reach = reinterpret_cast<uint32_t*>(fm + f.reach_off);
-                J.which = f.d.which; J.H = s.geo.h.img_size[0]; J.W = s.geo.h.img_size[1]; J.n_taps = f.d.warp_filter_size;
-                J.gx = f.d.global_flow[2 * f.d.which]; J.gy = f.d.global_flow[2 * f.d.which + 1];
-                J.cells_h = s.geo.cells_h; J.cells_w = s.geo.cells_w;
-                const int c = f.d.warp_filter_size == 8;
-                blocks[c] += static_cast<uint64_t>(J.cells_h) * J.cells_w;
-                if (blocks[c] > 0x7fffffffu) return CCD_ERR_UNSUPPORTED;
-                reach_jobs[c].push_back(J);
-                reach_prefix[c].push_back(static_cast<uint32_t>(blocks[c]));
-            }
-            for (int g = 0; g < s.n_grids; ++g) {
-                RdoqGridX& X = gridsx[slots[k].first_grid + g];
-                X.dd_dep = s.dd_dep[g];
-                for (size_t q = 0; q < s.follows.size(); ++q) X.fbox[q] = reinterpret_cast<RdoqBox*>(fm + s.follows[q].fbox_off[g]);
-            }
-        }
-    }
+    StepTables B;
+    FollowTables F;
+    int rc = component_uids(*r, uid0, comp);
+    if (rc == CCD_OK) rc = build_step_tables(*r, uid0, kD, kR, min_gain, grid_mask, B);
+    if (rc == CCD_OK && following) rc = build_follow_tables(*r, uid0, comp, B, F);
+    if (rc < 0) return rc;
+    // one block, one copy
     TableImage img;
-    const size_t o_grids = img.put(grids), o_slots = img.put(slots);
-    const size_t o_lane = img.put(lane_prefix), o_big = img.put(big_prefix), o_chunk = img.put(chunk_prefix), o_cell = img.put(cell_prefix);
-    const size_t o_gx = img.put(gridsx), o_sx = img.put(slotsx), o_cuid = img.put(comp_uid), o_cslot = img.put(comp_slot);
-    const size_t o_rj[2] = {img.put(reach_jobs[0]), img.put(reach_jobs[1])}, o_rp[2] = {img.put(reach_prefix[0]), img.put(reach_prefix[1])};
+    const size_t o_grids = img.put(B.grids), o_slots = img.put(B.slots);
+    const size_t o_lane = img.put(B.lane_prefix), o_big = img.put(B.big_prefix), o_chunk = img.put(B.chunk_prefix), o_cell = img.put(B.cell_prefix);
+    const size_t o_gx = img.put(F.gridsx), o_sx = img.put(F.slotsx), o_cuid = img.put(F.comp_uid), o_cslot = img.put(F.comp_slot);
+    const size_t o_rj[2] = {img.put(F.reach_jobs[0]), img.put(F.reach_jobs[1])}, o_rp[2] = {img.put(F.reach_prefix[0]), img.put(F.reach_prefix[1])};
     const std::vector<char>& buf = img.bytes;
     HIP_TRY(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     r->streams.note(st);
     // nothing of an earlier step is in flight (its wait synchronised), so the blocks may be exchanged for larger ones
     // the results, then one int64 per slot: its open candidates
+    const size_t n_chunks = B.chunk_prefix.back();
     const size_t open_off = static_cast<size_t>(n_slots) * sizeof(ccd_rdoq_result);
     const size_t dep_off = open_off + static_cast<size_t>(n_slots) * sizeof(int64_t);  // (following) and one more: its dependent sum
     const size_t res_bytes = dep_off + (following ? static_cast<size_t>(n_slots) * sizeof(int64_t) : 0);
-    const size_t partial_dep_off = align256(chunks * sizeof(RdoqPartial));
+    const size_t partial_dep_off = align256(n_chunks * sizeof(RdoqPartial));
     if (!r->tables.ensure(r->device, buf.size()) ||
-        !r->partial.ensure(r->device, BlockPool::kDevice, partial_dep_off + (following ? chunks * sizeof(int64_t) : 0)) ||
+        !r->partial.ensure(r->device, BlockPool::kDevice, partial_dep_off + (following ? n_chunks * sizeof(int64_t) : 0)) ||
         !r->results.ensure(r->device, res_bytes))
         return CCD_ERR_NOMEM;
     std::memcpy(r->tables.host.p, buf.data(), buf.size());
     const Mirror& T = r->tables;
-    RdoqFollowLaunch F;
+    RdoqStepLaunch L = {};
+    L.t.grids = T.dev_at<RdoqGrid>(o_grids); L.t.slots = T.dev_at<RdoqSlot>(o_slots);
+    L.t.lane_prefix = T.dev_at<uint32_t>(o_lane); L.t.big_prefix = T.dev_at<uint32_t>(o_big);
+    L.t.chunk_prefix = T.dev_at<uint32_t>(o_chunk); L.t.cell_prefix = T.dev_at<uint32_t>(o_cell);
+    L.t.n_grids = static_cast<int32_t>(B.grids.size()); L.t.n_slots = n_slots;
+    L.t.n_lane_blocks = B.lane_prefix.back();
+    L.n_big = B.big_prefix.back(); L.n_chunks = B.chunk_prefix.back(); L.n_cell_blocks = B.cell_prefix.back();
+    L.rounds = max_rounds;
+    L.sums.partial = r->partial.as<RdoqPartial>();
+    L.sums.results = r->results.dev.as<ccd_rdoq_result>();
+    L.sums.open = reinterpret_cast<int64_t*>(r->results.dev.as<char>() + open_off);
     if (following) {
-        F.gx = T.dev_at<RdoqGridX>(o_gx); F.sx = T.dev_at<RdoqSlotX>(o_sx);
-        F.comp_uid = T.dev_at<uint32_t>(o_cuid); F.comp_slot = T.dev_at<int32_t>(o_cslot);
+        L.t.gx = T.dev_at<RdoqGridX>(o_gx); L.t.sx = T.dev_at<RdoqSlotX>(o_sx);
+        L.t.comp_uid = T.dev_at<uint32_t>(o_cuid); L.t.comp_slot = T.dev_at<int32_t>(o_cslot);
         for (int c = 0; c < 2; ++c) {
-            F.reach_jobs[c] = T.dev_at<RdoqReachJob>(o_rj[c]);
-            F.reach_prefix[c] = T.dev_at<uint32_t>(o_rp[c]);
-            F.n_reach[c] = static_cast<int>(reach_jobs[c].size());
-            F.reach_blocks[c] = reach_prefix[c].back();
+            L.reach_jobs[c] = T.dev_at<RdoqReachJob>(o_rj[c]);
+            L.reach_prefix[c] = T.dev_at<uint32_t>(o_rp[c]);
+            L.n_reach[c] = static_cast<int>(F.reach_jobs[c].size());
+            L.reach_blocks[c] = F.reach_prefix[c].back();
         }
-        F.reach_mem = r->follow_mem.p; F.reach_bytes = reach_bytes;
-        F.partial_dep = reinterpret_cast<int64_t*>(r->partial.as<char>() + partial_dep_off);
-        F.dep_out = reinterpret_cast<int64_t*>(r->results.dev.as<char>() + dep_off);
-        F.stages = r->debug_stages;
+        L.reach_mem = r->follow_mem.p; L.reach_bytes = F.reach_bytes;
+        L.sums.partial_dep = reinterpret_cast<int64_t*>(r->partial.as<char>() + partial_dep_off);
+        L.sums.dep_out = reinterpret_cast<int64_t*>(r->results.dev.as<char>() + dep_off);
+        L.stages = r->debug_stages;
     }
-    const bool ok =
-        r->tables.upload(buf.size(), st) == hipSuccess &&
-        launch_rdoq_step(T.dev_at<RdoqGrid>(o_grids), T.dev_at<RdoqSlot>(o_slots), T.dev_at<uint32_t>(o_lane), T.dev_at<uint32_t>(o_big),
-                         T.dev_at<uint32_t>(o_chunk), T.dev_at<uint32_t>(o_cell), n_grids,
-                         n_slots, static_cast<uint32_t>(lanes), static_cast<uint32_t>(bigs), static_cast<uint32_t>(chunks),
-                         static_cast<uint32_t>(cell_blocks), max_rounds, r->partial.as<RdoqPartial>(),
-                         r->results.dev.as<ccd_rdoq_result>(), reinterpret_cast<int64_t*>(r->results.dev.as<char>() + open_off),
-                         st, following ? &F : nullptr) == hipSuccess &&
-        r->results.download(res_bytes, st) == hipSuccess;
+    const bool ok = r->tables.upload(buf.size(), st) == hipSuccess && launch_rdoq_step(L, st) == hipSuccess &&
+                    r->results.download(res_bytes, st) == hipSuccess;
     if (!ok) {  // part of the step may have been enqueued: drain it; no slot has a result, no step is in flight
         (void)hipStreamSynchronize(st);
         for (auto& s : r->slots) {
@@ -621,49 +649,48 @@ int ccd_rdoq_wait(ccd_rdoq* r, void* stream) {
 
 int ccd_rdoq_slot_result(const ccd_rdoq* r, int slot, ccd_rdoq_result* out) {
     if (!r || !out || slot < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
-    *out = r->slots[slot]->result;
+    const RSlot* s = covered_slot(r, slot);
+    if (!s) return CCD_ERR_ARG;
+    *out = s->result;
     return CCD_OK;
 }
 
 int64_t ccd_rdoq_slot_open(const ccd_rdoq* r, int slot) {
     if (!r || slot < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
-    return r->slots[slot]->n_open;
+    const RSlot* s = covered_slot(r, slot);
+    return s ? s->n_open : CCD_ERR_ARG;
 }
 
 int ccd_rdoq_slot_dep_sse(const ccd_rdoq* r, int slot, int64_t* out) {
     if (!r || !out || slot < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending || !r->slots[slot]->covered) return CCD_ERR_ARG;
-    *out = r->slots[slot]->dep_sse;
+    const RSlot* s = covered_slot(r, slot);
+    if (!s) return CCD_ERR_ARG;
+    *out = s->dep_sse;
     return CCD_OK;
 }
 
 int64_t ccd_rdoq_slot_reach(const ccd_rdoq* r, int slot, int follow, void** dev_ptr) {
     if (!r || !dev_ptr || slot < 0 || follow < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
-    const RSlot& s = *r->slots[slot];
-    if (follow >= static_cast<int>(s.follows.size()) || !s.covered || !s.follows[follow].stepped) return CCD_ERR_ARG;
-    *dev_ptr = r->follow_mem.as<char>() + s.follows[follow].reach_off;
-    return static_cast<int64_t>(s.geo.cells_h) * s.geo.cells_w;
+    const RSlot* s = covered_slot(r, slot);
+    if (!s || follow >= static_cast<int>(s->follows.size()) || !s->follows[follow].stepped) return CCD_ERR_ARG;
+    *dev_ptr = r->follow_mem.as<char>() + s->follows[follow].reach_off;
+    return static_cast<int64_t>(s->geo.cells_h) * s->geo.cells_w;
 }
 
 int64_t ccd_rdoq_slot_flow_boxes(const ccd_rdoq* r, int slot, int follow, int grid, void** dev_ptr) {
     if (!r || !dev_ptr || slot < 0 || follow < 0 || grid < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
-    const RSlot& s = *r->slots[slot];
-    if (follow >= static_cast<int>(s.follows.size()) || grid >= s.n_grids || !s.covered || !s.follows[follow].stepped) return CCD_ERR_ARG;
-    *dev_ptr = r->follow_mem.as<char>() + s.follows[follow].fbox_off[grid];
-    return static_cast<int64_t>(s.n[grid]);
+    const RSlot* s = covered_slot(r, slot);
+    if (!s || follow >= static_cast<int>(s->follows.size()) || grid >= s->n_grids || !s->follows[follow].stepped) return CCD_ERR_ARG;
+    *dev_ptr = r->follow_mem.as<char>() + s->follows[follow].fbox_off[grid];
+    return static_cast<int64_t>(s->n[grid]);
 }
 
 int64_t ccd_rdoq_slot_moves(const ccd_rdoq* r, int slot, int grid, void** dev_ptr) {
     if (!r || !dev_ptr || slot < 0 || grid < 0) return CCD_ERR_ARG;
-    if (slot >= static_cast<int>(r->slots.size()) || r->pending) return CCD_ERR_ARG;
-    const RSlot& s = *r->slots[slot];
-    if (grid >= s.n_grids || !s.covered) return CCD_ERR_ARG;
-    *dev_ptr = s.mem.as<char>() + s.moves_off[grid];
-    return static_cast<int64_t>(s.n[grid]);
+    const RSlot* s = covered_slot(r, slot);
+    if (!s || grid >= s->n_grids) return CCD_ERR_ARG;
+    *dev_ptr = s->mem.as<char>() + s->moves_off[grid];
+    return static_cast<int64_t>(s->n[grid]);
 }
 
 }  // extern "C"

@@ -214,6 +214,46 @@ class Rounds:
         self.selected = [c for won in self.per_round for c in won]
 
 
+LANE_CELLS = 32  # ccd_rdoq_lane_cells(): an own box of more cells is walked by a wave, the lanes over its cells
+DECISIONS = ("blocked, own box", "blocked, flow box only", "lost, own box", "lost, flow box only", "selected")
+
+
+def decisions(handle, cands, max_rounds):
+    """What the rounds of Rounds decide, by the route the device takes to it: {(wave, what): [candidates]} with `wave` whether
+    the own box has more than LANE_CELLS cells and `what` of DECISIONS - blocked by a taken cell of the own box, or of a flow box
+    alone; lost a select through a cell of the own box, or of a flow box alone (once per round lost); selected."""
+    taken = handle.rasters(False, bool)
+    claims = {c[:2]: handle.claim(c) for c in cands}
+    open_, out = list(cands), {}
+
+    def note(c, what):
+        _, rs, cs = claims[c[:2]][0]
+        out.setdefault(((rs.stop - rs.start) * (cs.stop - cs.start) > LANE_CELLS, what), []).append(c)
+
+    for _ in range(max_rounds):
+        hit = {c[:2]: [bool(taken[k][rs, cs].any()) for k, rs, cs in claims[c[:2]]] for c in open_}
+        for c in open_:
+            if any(hit[c[:2]]):
+                note(c, DECISIONS[0] if hit[c[:2]][0] else DECISIONS[1])
+        open_ = [c for c in open_ if not any(hit[c[:2]])]
+        raster = handle.rasters(ONES, np.uint64)
+        for c in open_:
+            for k, rs, cs in claims[c[:2]]:
+                np.minimum(raster[k][rs, cs], np.uint64(c[0]), out=raster[k][rs, cs])
+        still = []
+        for c in open_:
+            mine = [bool((raster[k][rs, cs] == np.uint64(c[0])).all()) for k, rs, cs in claims[c[:2]]]
+            note(c, DECISIONS[4] if all(mine) else DECISIONS[3] if mine[0] else DECISIONS[2])
+            if all(mine):
+                for k, rs, cs in claims[c[:2]]:
+                    taken[k][rs, cs] = True
+            else:
+                still.append(c)
+        open_ = still
+    assert sorted(out.get((False, DECISIONS[4]), []) + out.get((True, DECISIONS[4]), [])) == sorted(Rounds(handle, cands, max_rounds).selected)
+    return out
+
+
 def greedy(handle, cands):
     """The walk over the candidates of every component in ascending key order: a candidate is taken unless its claim set holds a
     taken cell.  (Components do not share a raster, so one walk over (component, key) serves them all.)"""

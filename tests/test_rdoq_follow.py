@@ -307,6 +307,45 @@ def test_the_rounds_over_claim_sets_end_at_the_greedy_walk(name, amplitude):
     assert len(plain.selected) > seen, (name, len(plain.selected), seen)
 
 
+# Three coarse latents of odd100x37 (grid 3: own boxes of 35 .. 65 of the 65 cells, a wave's), one per raster of the component.  The
+# reference of slot 0 has the best key; the one of slot 1 meets it in F's raster alone, through the two flow boxes; F's own
+# latent meets its flow box with its own box.
+WAVE_OFFERS = [(0, 3, 2, 6, -1000), (1, 3, 2, 6, -100), (2, 3, 2, 6, -50)]
+
+
+def _place(comp, offers):
+    """offers: [(slot, g, y, x, cost)] as the only candidates of a crafted component."""
+    for c in comp.cases:
+        c.dd = [np.full_like(a, SENTINEL) for a in c.dd]
+        c.syn.dd = c.dd
+    for slot, g, y, x, cost in offers:
+        comp.cases[slot].offer(g, y, x, cost)
+
+
+def test_the_cases_reach_every_route_of_the_step():
+    """A condition on the inputs of the GPU tests below, not a measurement: the device walks an own box of up to 32 cells in its
+    latent's lane and a larger one in a wave, and either can be blocked by a taken cell of the own box or of a flow box alone,
+    lose a select through a cell of the own box or of a flow box alone, or be selected.  The seeded components (8 rounds) and
+    the crafted waves (3 rounds) together hold a candidate for every one of the ten."""
+    from cool_chic_amd._lib import lib
+
+    assert lib().ccd_rdoq_lane_cells() == fr.LANE_CELLS  # the threshold the restatement sorts lane from wave by is the device's
+    seen = {}
+    for name, amplitude in SEEDED:
+        comp = _component(name, amplitude=amplitude)
+        for route, cands in fr.decisions(comp.handle, comp.cands(), 8).items():
+            seen[route] = seen.get(route, 0) + len(cands)
+    lanes_alone = dict(seen)
+    comp = _component("odd100x37", amplitude=3.0, crafted=True)
+    _place(comp, WAVE_OFFERS)
+    for route, cands in fr.decisions(comp.handle, comp.cands(), 3).items():
+        seen[route] = seen.get(route, 0) + len(cands)
+    for wave in (False, True):
+        for what in fr.DECISIONS:
+            assert seen.get((wave, what), 0) > 0, (wave, what, seen)
+    assert all(lanes_alone.get((False, what), 0) > 0 for what in fr.DECISIONS), lanes_alone  # (odd18x65 has no wave's box at all)
+
+
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
 def _np(dev_array):
     import torch
@@ -368,11 +407,7 @@ def _find(comp, cond, slots, grids=(0, 1)):
 
 def _crafted_step(gpu, comp, offers, rounds_list, what, masks=None):
     """offers: [(slot, g, y, x, cost)].  One fresh handle per number of rounds; returns {rounds: Rounds}."""
-    for c in comp.cases:
-        c.dd = [np.full_like(a, SENTINEL) for a in c.dd]
-        c.syn.dd = c.dd
-    for slot, g, y, x, cost in offers:
-        comp.cases[slot].offer(g, y, x, cost)
+    _place(comp, offers)
     out = {}
     for rounds in rounds_list:
         step, dev, keep = comp.device(gpu)
@@ -408,6 +443,22 @@ def test_crafted_offers_meet_through_the_flows(gpu):
         assert len(second.selected) == 1 and sum(second.n_open) == 0 and [(c[1],) + c[2:5] for c in second.blocked] == [(slots[1],) + b], what
         # without follows both are selected at once: what the step did before claims followed the flows
         assert len(fr.Rounds(plain, comp.cands(), 1).selected) == 2, what
+
+
+@pytest.mark.gpu
+def test_crafted_waves_take_every_route(gpu):
+    """WAVE_OFFERS on odd100x37, the smallest fixture whose coarse latents have a wave's box: round 1 selects the wave of slot 0;
+    the wave of slot 1 loses through its flow box alone and the wave of slot 2 through its own box, and round 2 blocks them the
+    same way.  Every route of a wave through claim and select, against the restatement for 1, 2 and 3 rounds."""
+    comp = _component("odd100x37", amplitude=3.0, crafted=True)
+    res = _crafted_step(gpu, comp, WAVE_OFFERS, (1, 2, 3), "waves")
+    routes = fr.decisions(comp.handle, comp.cands(), 3)
+    assert {route: [c[1] for c in cands] for route, cands in routes.items()} == {
+        (True, "selected"): [0], (True, "lost, flow box only"): [1], (True, "lost, own box"): [2],
+        (True, "blocked, flow box only"): [1], (True, "blocked, own box"): [2]}
+    assert [c[1] for c in res[1].selected] == [0] and res[1].n_open == (0, 1, 1, 0)
+    for rounds in (2, 3):
+        assert [c[1] for c in res[rounds].selected] == [0] and sorted(c[1] for c in res[rounds].blocked) == [1, 2] and sum(res[rounds].n_open) == 0
 
 
 @pytest.mark.gpu
